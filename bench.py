@@ -7,7 +7,9 @@ solve! -> get_next_control; /root/reference/src/ros_integration.jl:96-99,124) fo
 inputs resident in HBM before the timed region.  Weak scaling: every rank owns its own 4096 instances (seed 12345 + rank).
 
 `python bench.py --gpus N` started as a plain process launches its N ranks itself (torch.distributed.run as a child, before any GPU call).
-The JSON line also carries the other BASELINE configs and SURVEY 8(d) items as secondary objects (rank 0, N = 1 only where they need the CPU):
+A plain run is set-up, --warmup steps, exactly --steps timed steps and the JSON line; `--dump-outputs DIR` writes what the last timed step computed as .npy files.
+With `--full` the timed block is repeated (--repeats, default 5) and the JSON line also carries the other BASELINE configs and SURVEY 8(d) items as secondary objects
+(rank 0, N = 1 only where they need the CPU):
   roofline (+ roofline.valu: algorithmic-FLOP fraction of the fp64 vector peak from live iteration counts), iteration histograms,
   hji_lookup (7-D grid, and the 4-D variant), decoupled_n50 (config 5), fp32 (config 3), cpu_baseline (OSQP-port on the host cores for the
   headline and the decoupled config, config 1 = single-instance closed loop GPU vs CPU, measured accuracy against the exact optimum).
@@ -282,6 +284,24 @@ def emit(full, path=None):
     print(compact_line(full), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES, seed=12345):
+    """Write `arrays` (name -> array, first axis = instance) as d/<name>.npy: floating arrays keep float32 / float64, integer ones go out as float64 (exact).
+    Above `limit` bytes in all, every array keeps the same fraction of its rows, a fixed seeded sample, and its row indices go to d/<name>_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    out = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    frac = 1.0 if total <= limit else 0.95 * limit / total          # (0.95: room for the index files)
+    for k, v in out.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(seed).choice(len(v), size=max(1, int(len(v) * frac)), replace=False))
+            v = v[rows]
+            np.save(os.path.join(d, f"{k}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(d, f"{k}.npy"), v)
+
+
 def phases_of(m, n=3, cold=True, u_ptr=None):
     """Per-phase device time of a step of handle `m` (median over n steps, HIP events on the launch stream): the library's instrumentation (option "phase_timing": four event
     records per step, 13-25 us of stream time) is switched on for these steps only -- the timed loops of this file run without it, as the library does by default."""
@@ -401,8 +421,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hji", action="store_true")
     ap.add_argument("--no-decoupled", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region is repeated this many times (each: --steps steps between two barrier + synchronize brackets); "
-                                                            "`value` is the MEDIAN block, min / max / every block go to bench_full.json (VERDICT r5: one 10 ms shot is thin as a measurement)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region is repeated this many times (each: --steps steps between two barrier + synchronize brackets); "
+                                                               "`value` is the MEDIAN block, min / max / every block go to bench_full.json (VERDICT r5: one 10 ms shot is thin as a measurement); "
+                                                               "default 1 (exactly --steps timed steps), 5 with --full")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated timed blocks, per-phase times and roofline, warm steps, the other BASELINE "
+                                                        "configs, HJI lookups, closed loops, CPU baseline and accuracy checks (the --no-* options trim this set); "
+                                                        "without it the run is set-up, warm-up, the timed steps and the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed (controls, status, iterations, "
+                                                                         "predicted trajectories) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-f32", action="store_true")
     ap.add_argument("--no-rollout", action="store_true", help="skip the closed-loop rollout object")
     ap.add_argument("--no-warm", action="store_true", help="skip the warm-step loop (the profile campaign uses it so that every k_solve launch of the trace is a cold headline launch)")
@@ -413,6 +439,8 @@ def main():
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64",
                     help="arithmetic type of the headline run: f64 = BASELINE configs[1] (default, the metric's config); f32 with --batch 8192 --gpus 8 = configs[3]")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     # `python bench.py --gpus N` (N > 1) started as a plain process: launch the N ranks ourselves, one process per GPU, through torch.distributed.run as a
     # CHILD process -- decided before anything here touches the GPU (no HIP call, no torch.cuda call has happened yet; a process that initialised the GPU
@@ -517,6 +545,10 @@ def main():
         torch.cuda.synchronize()
         sync()
         blocks.append(time.perf_counter() - t_begin)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (N > 1: the gathered controls of every rank, this rank's status / iterations / trajectories)
+        st_d, it_d, _, _ = mpc.solve_info(); x_d, _ = mpc.solution()
+        dump_outputs(args.dump_outputs, {"controls": (gathered if world > 1 else u_out).cpu().numpy(), "status": st_d, "ipm_iters": it_d, "solution_x": x_d})
     rank_ms = None; gather_ms = None
     if world > 1:
         # a scaling run is the timed loop, the gather check and ONE JSON line: every secondary object below is skipped when world > 1 (rank 0 would otherwise build
@@ -530,7 +562,7 @@ def main():
         rank_ms = {"min": 1e3 * float(per_rank[:, mid].min()) / args.steps, "max": 1e3 * float(per_rank[:, mid].max()) / args.steps}
         # how long the collective itself takes (so that a weak-scaling efficiency below 0.9 can be attributed: launch overhead or the gather): a few more steps with an
         # event pair around each all_gather on the communication stream, outside the timed region
-        if comm_stream is not None:
+        if comm_stream is not None and args.full:
             g_ev = []
             for _ in range(6):
                 one_step()
@@ -549,23 +581,27 @@ def main():
     timing = {"repeats": len(blocks), "steps_per_block": args.steps, "block_s": blocks, "value_is": "median block", "ms_per_step_min": 1e3 * min(blocks) / args.steps,
               "ms_per_step_median": 1e3 * elapsed / args.steps, "ms_per_step_max": 1e3 * max(blocks) / args.steps}
 
-    # per-phase device time (HIP events recorded by pg_step_dev on the launch stream): mean over a few extra steps outside the timed region
-    mpc.set_option("phase_timing", 1)
-    ph = []
-    for _ in range(5):
-        one_step(); torch.cuda.synchronize(); ph.append(mpc.phase_ms())
-    mpc.set_option("phase_timing", 0)
-    ph = np.mean(np.array(ph), axis=0)
+    # (--full) per-phase device time (HIP events recorded by pg_step_dev on the launch stream): mean over a few extra steps outside the timed region
+    ph = None
+    if args.full:
+        mpc.set_option("phase_timing", 1)
+        ph = []
+        for _ in range(5):
+            one_step(); torch.cuda.synchronize(); ph.append(mpc.phase_ms())
+        mpc.set_option("phase_timing", 0)
+        ph = np.mean(np.array(ph), axis=0)
     st, it, act, mu = mpc.solve_info(); pol = mpc.polish_info()
     ok = int(pkg.is_solved(st).sum())
-    # warm steps (second and later consecutive steps on the same inputs: warm nodes + warm start of the active set): reported as an extra, not as `value`
-    sync(); tw = time.perf_counter()
-    for _ in range(0 if args.no_warm else args.steps):
-        one_step(cold=False)
-    sync(); warm_elapsed = time.perf_counter() - tw
+    # (--full) warm steps (second and later consecutive steps on the same inputs: warm nodes + warm start of the active set): reported as an extra, not as `value`
+    warm_elapsed = None
+    if args.full and not args.no_warm:
+        sync(); tw = time.perf_counter()
+        for _ in range(args.steps):
+            one_step(cold=False)
+        sync(); warm_elapsed = time.perf_counter() - tw
     # the same cold workload with the active-set guess OFF (every instance through the interior point; round-2-mid behaviour), as a reference for what the guess buys
     ipm_only = None; fused_line = None; per_phase_line = None
-    if rank == 0 and world == 1 and not args.no_warm:
+    if args.full and rank == 0 and world == 1 and not args.no_warm:
         m0 = pkg.BatchedTrajectoryTrackingMPC(traj, B, device=local, precision=args.precision, cold_guess=0, phase_timing=False)
         m0.set_stream(torch.cuda.current_stream().cuda_stream)
         m0.set_inputs_dev(B, d_state.data_ptr(), d_control.data_ptr(), d_t0.data_ptr(), None, d_toff.data_ptr())
@@ -606,7 +642,7 @@ def main():
     # a user-level way to more throughput: the same batch as two halves on two handles / two streams, submitted alternately -- the latency-bound nodes kernel of one
     # half (64 wavefronts on a 1024-SIMD part) runs under the throughput-bound kernels of the other.  Reported beside the headline, never as `value`.
     two_streams = None
-    if rank == 0 and world == 1 and not args.no_warm and B % 2 == 0 and B >= 2048:
+    if args.full and rank == 0 and world == 1 and not args.no_warm and B % 2 == 0 and B >= 2048:
         hs = []
         for k in range(2):
             sl = slice(k * B // 2, (k + 1) * B // 2)
@@ -628,7 +664,7 @@ def main():
     # ... and two WHOLE batches in flight on one GPU (two handles, two streams, steps submitted alternately): the nodes + update_QP launch of one batch runs on the SIMDs
     # the solve launch of the other leaves idle (its tail) and vice versa.  Twice the instances per GPU -- not the benchmark's configuration: reported beside it.
     two_batches = None
-    if rank == 0 and world == 1 and not args.no_warm and B >= 2048:
+    if args.full and rank == 0 and world == 1 and not args.no_warm and B >= 2048:
         hs = []
         for k in range(2):
             m2 = pkg.BatchedTrajectoryTrackingMPC(traj, B, device=local, precision=args.precision, phase_timing=False)
@@ -651,7 +687,7 @@ def main():
     # SURVEY 8(d), config 2 "repeat for vail" and "a second run with time_offset = NaN (path mode; coupled_lat_long.jl:115)": the same cold step on the reference's
     # other long test path and on the benchmark path with every instance in path-tracking mode -- two short secondary numbers
     variants = None
-    if rank == 0 and world == 1 and not args.no_warm:
+    if args.full and rank == 0 and world == 1 and not args.no_warm:
         variants = {}
         for key, path, tmode in (("vail", "vail", True), ("path_mode", "skidpadoval", False)):
             tj = pkg.load_path_fixture(path)
@@ -676,7 +712,7 @@ def main():
     # closed-loop rollouts resident on the device (pg_simulate_dev = simulate of model_predictive_control.jl:80-100 for the whole batch): per step the
     # four compute phases + the plant's RK4 step; warm branch of the nodes and warm start of the active set (vs the same loop with that warm start off)
     roll = None
-    if rank == 0 and world == 1 and not args.no_rollout:
+    if args.full and rank == 0 and world == 1 and not args.no_rollout:
         roll = {"workload": f"{B} controllers in closed loop on the device, 40 steps of 10 ms after 4 warm-up steps (skidpadoval, config-2 initial states), {args.precision}"}
         for warm in (True, False):
             mr = pkg.BatchedTrajectoryTrackingMPC(traj, B, device=local, precision=args.precision, warm_polish=warm, phase_timing=False)
@@ -691,7 +727,7 @@ def main():
 
     # BASELINE config 5: decoupled (lateral) MPC, N = 50 (N_short = 10, N_long = 40), same batch, cold every step (pg_reset before each: the nodes of that formulation have no warm branch, its solver does)
     dec = None
-    if rank == 0 and world == 1 and not args.no_decoupled:
+    if args.full and rank == 0 and world == 1 and not args.no_decoupled:
         def run_dec(walls, polish=None):
             mpc_d = pkg.DecoupledTrajectoryTrackingMPC(pkg.X1(), traj, B, N_short=10, N_long=40, device=local, precision=args.precision, walls=walls, polish=polish, phase_timing=False)
             mpc_d.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -746,7 +782,7 @@ def main():
 
     # HJI value/gradient lookup (the bandwidth-bound kernel of the path): 2^20 random in-grid relative states against the config-3 grid
     hji = None
-    if rank == 0 and world == 1 and not args.no_hji:
+    if args.full and rank == 0 and world == 1 and not args.no_hji:
         import ctypes as C
 
         def lookup_rate(knots, Vg, gg, label):
@@ -806,7 +842,7 @@ def main():
 
     # BASELINE config 3: coupled MPC + HJI safety constraint on the precomputed 7-D grid, fp32 (libpigeon_hip_f32.so: same translation unit, real = float)
     f32 = None
-    if rank == 0 and world == 1 and not args.no_f32 and args.precision == "f64":
+    if args.full and rank == 0 and world == 1 and not args.no_f32 and args.precision == "f64":
         m32 = pkg.BatchedTrajectoryTrackingMPC(traj, B, device=local, precision="f32", phase_timing=False)
         m32.set_stream(torch.cuda.current_stream().cuda_stream)
         TR32 = {"kernels": (TR or {}).get("kernels_f32", {})}
@@ -864,72 +900,73 @@ def main():
     if rank == 0:
         total = world * B * args.steps
         value = total / elapsed
-        names = ["nodes(time_steps+project+nodes)", "update_qp(hji+linearize)", "solve(k_solve+extract)"]
-        # pg_set_pipeline (default for 2048..8192 instances with cold ones): nodes and update_QP are ONE launch (k_nodes_linearize) and the event between
-        # the two phases falls behind it -- the first phase then holds both
-        pipelined = float(ph[1]) < 0.02 and float(ph[0]) > 0.1
-        if pipelined:
-            names = ["nodes+update_qp(time_steps+project, then ONE pipelined launch k_nodes_linearize)", "update_qp(nothing left: see the first phase)", "solve(k_solve+extract)"]
-        lin_ms = float(ph[0]) if pipelined else float(ph[1])
-        dom = int(np.argmax(ph))
-        dom_ms = float(ph[dom])
-        bytes_per_solve = BYTES_PER_SOLVE_COLD_FP64 if args.precision == "f64" else 68        # 112 B fp64; fp32 = 9 floats + t0 (double) in, 3 floats + status + iters out
-        achieved = B * bytes_per_solve / (dom_ms * 1e-3) / 1e9
-        traffic = None; traffic_src = None; traffic_stale = None; tr = None; dom_extra = {}
-        try:
-            tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-            # the counters were taken with a particular build: traffic.json records the hash of the kernel sources it was taken at (tools/summarize_profiles.py), and the
-            # line says so when the sources have changed since (the GPU box has no .git: a content hash, not a commit)
-            traffic_stale = tr.get("kernel_source_sha16") != kernel_source_sha16()
-            kern = {0: "k_nodes_linearize" if pipelined else "k_nodes", 1: "k_linearize", 2: "k_solve"}[dom]                  # the kernel that makes up the dominant phase (no HJI row in the headline run)
-            hit = [v for k, v in tr.get("kernels", {}).items() if kern in k]
-            traffic = hit[0]["hbm_bytes_per_launch"] if hit else tr.get("hbm_bytes_per_launch"); traffic_src = (hit[0] if hit else tr).get("source")
-            dom_extra = {k: hit[0][k] for k in ("valu_issue_frac", "valu_insts_per_launch", "avg_launch_ns_rocprof", "min_launch_ns_rocprof", "max_launch_ns_rocprof", "stddev_launch_ns_rocprof") if hit and k in hit[0]}
-        except Exception:
-            pass
-        # The linearisation's flops are COUNTED, not modelled (round 6; rounds 1-5 priced the launch with the forward-mode count of an algorithm it no longer runs: 130 + 260 per
-        # direction and evaluation, 1.0e10 per launch, i.e. "0.42 of the vector peak" -- above anything the 80.6 M counted VALU instructions could deliver).  What runs: the
-        # right-hand side with its local Jacobian once per RK4 stage (tracking_jac: 356 flops by hand with every reciprocal / square root / sincos counted as one), then
-        # ~51 flops per tangent direction (+ 6 for a control direction) -- 832 per ramp stage, 699 per zero-order-hold stage by hand; the ISA of the stage loops (software
-        # sincos, refined reciprocals and square roots included) holds 1204 / 912: tools/isa_mix.py -> profiles/isa_mix.json, per interval x (N_short, N_long) x B.
-        lin_fl, isa_lin = linearize_flops_from_isa(B, mpc.N_short, mpc.N - mpc.N_short, args.precision)
-        peak_lin = FP64_VALU_PEAK_TF if args.precision == "f64" else 2 * FP64_VALU_PEAK_TF
-        valu_lin = {"bound": "valu-" + args.precision, "kernel": "k_nodes_linearize" if pipelined else "k_linearize", "algorithmic_flops_per_launch": lin_fl, "achieved": lin_fl / (lin_ms * 1e-3) / 1e12, "peak": peak_lin,
-                    "unit": "TFLOP/s", "frac": lin_fl / (lin_ms * 1e-3) / 1e12 / peak_lin, "avg_launch_ms": lin_ms, "isa": isa_lin,
-                    # an UPPER bound on executed arithmetic: every fp64 arithmetic instruction of the launch (ISA count) taken as a 64-lane multiply-add
-                    "executed_fp64_frac": None if not isa_lin else isa_lin["arith_wave_insts"] * 128.0 / (lin_ms * 1e-3) / 1e12 / peak_lin,
-                    "source": "flops counted from the ISA of the kernel's loop nests x trip counts (tools/isa_mix.py, profiles/isa_mix.json; the nodes recurrence -- 2 % of the instructions -- is not in it); time live (HIP events: " + ("the nodes + update_qp phase -- projection, the nodes recurrence and the linearisation running under it" if pipelined else "the update_qp phase") + ", no HJI row in the headline run)"}
-        # secondary roofline of the dominant kernel: ALGORITHMIC flops (model above x the iteration counts of THIS run) against the fp64 / fp32 vector peak --
-        # the resource class that binds (the step moves 112 B per solve through HBM, so its HBM fraction is ~1e-5 by construction)
-        rounds = np.where(pol > 0, pol, np.where(pol < 0, 6, 0))
-        fl = float(np.sum(solve_flops(mpc.N, it.astype(np.float64), rounds.astype(np.float64))))
-        peak_tf = FP64_VALU_PEAK_TF if args.precision == "f64" else 2 * FP64_VALU_PEAK_TF
-        valu = {"bound": "valu-" + args.precision, "kernel": "k_solve", "algorithmic_flops_per_launch": fl, "flops_per_solve_mean": fl / B, "achieved": fl / (float(ph[2]) * 1e-3) / 1e12,
-                "peak": peak_tf, "unit": "TFLOP/s", "frac": fl / (float(ph[2]) * 1e-3) / 1e12 / peak_tf, "avg_launch_ms": float(ph[2]),
-                "source": "flop model of the stage-structured interior point (bench.py solve_flops, EXPERIMENTS.md 6) x live iteration / polish-round counts; time live (HIP events)"}
-        # the two kernels that make up the step (nodes + update_QP! launch, solve launch), each with what the committed counter passes say about it: the headline `roofline`
-        # names the longer one and lists BOTH (their phases are within a few per cent of each other and swap places from run to run)
-        def kernel_entry(name, match, ms, flop_obj):
-            e = {"kernel": name, "avg_launch_ms": ms, "hbm_frac": B * bytes_per_solve / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "valu_flop_frac": flop_obj["frac"]}
-            if flop_obj.get("executed_fp64_frac") is not None:
-                e["executed_fp64_frac"] = flop_obj["executed_fp64_frac"]
-            hit_ = [v for k, v in (tr or {}).get("kernels" if args.precision == "f64" else "kernels_f32", {}).items() if match in k]
-            if hit_:
-                h_ = hit_[0]
-                e["traffic"] = h_.get("hbm_bytes_per_launch"); e["valu_issue_frac"] = h_.get("valu_issue_frac"); e["avg_launch_ms_rocprof"] = (h_.get("avg_launch_ns_rocprof") or 0) * 1e-6 or None
-                hw_ = h_.get("hw_flops")
-                if isinstance(hw_, dict) and hw_.get("valu_flops_per_launch"):
-                    # the hardware's own count of executed arithmetic (SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 of the committed PMC pass) over the LIVE duration
-                    e["hw_valu_flop_frac"] = hw_["valu_flops_per_launch"] / (ms * 1e-3) / 1e12 / hw_["peak_tflops"]; e["hw_arith_share_of_valu_insts"] = hw_.get("arith_share_of_valu_insts")
-                    # ... which IS the flop fraction of this kernel: the model / ISA count stays beside it as `model_flop_frac`
-                    e["model_flop_frac"] = e["valu_flop_frac"]; e["valu_flop_frac"] = e["hw_valu_flop_frac"]; e["valu_flop_frac_source"] = "counters: 64 x (ADD + MUL + TRANS + 2 FMA) wave instructions of the committed PMC pass / live duration"
-                m_ = h_.get("mfma")
-                if isinstance(m_, dict):
-                    e["mfma_busy_frac"] = m_.get("busy_frac_of_simd_time"); e["mfma_flop_frac"] = m_.get("frac_of_peak")
-            return e
-        lin_match = ("k_nodes_linearize" if pipelined else "k_linearize")
-        kernels = [kernel_entry("k_solve", "k_solve<false, false, false, false", float(ph[2]), valu), kernel_entry(lin_match, lin_match, lin_ms, valu_lin)]
-        kernels.sort(key=lambda e: -e["avg_launch_ms"])
+        if args.full:          # roofline and phase times: from the phase-timed steps above
+            names = ["nodes(time_steps+project+nodes)", "update_qp(hji+linearize)", "solve(k_solve+extract)"]
+            # pg_set_pipeline (default for 2048..8192 instances with cold ones): nodes and update_QP are ONE launch (k_nodes_linearize) and the event between
+            # the two phases falls behind it -- the first phase then holds both
+            pipelined = float(ph[1]) < 0.02 and float(ph[0]) > 0.1
+            if pipelined:
+                names = ["nodes+update_qp(time_steps+project, then ONE pipelined launch k_nodes_linearize)", "update_qp(nothing left: see the first phase)", "solve(k_solve+extract)"]
+            lin_ms = float(ph[0]) if pipelined else float(ph[1])
+            dom = int(np.argmax(ph))
+            dom_ms = float(ph[dom])
+            bytes_per_solve = BYTES_PER_SOLVE_COLD_FP64 if args.precision == "f64" else 68        # 112 B fp64; fp32 = 9 floats + t0 (double) in, 3 floats + status + iters out
+            achieved = B * bytes_per_solve / (dom_ms * 1e-3) / 1e9
+            traffic = None; traffic_src = None; traffic_stale = None; tr = None; dom_extra = {}
+            try:
+                tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+                # the counters were taken with a particular build: traffic.json records the hash of the kernel sources it was taken at (tools/summarize_profiles.py), and the
+                # line says so when the sources have changed since (a copy of the tree may have no .git: a content hash, not a commit)
+                traffic_stale = tr.get("kernel_source_sha16") != kernel_source_sha16()
+                kern = {0: "k_nodes_linearize" if pipelined else "k_nodes", 1: "k_linearize", 2: "k_solve"}[dom]                  # the kernel that makes up the dominant phase (no HJI row in the headline run)
+                hit = [v for k, v in tr.get("kernels", {}).items() if kern in k]
+                traffic = hit[0]["hbm_bytes_per_launch"] if hit else tr.get("hbm_bytes_per_launch"); traffic_src = (hit[0] if hit else tr).get("source")
+                dom_extra = {k: hit[0][k] for k in ("valu_issue_frac", "valu_insts_per_launch", "avg_launch_ns_rocprof", "min_launch_ns_rocprof", "max_launch_ns_rocprof", "stddev_launch_ns_rocprof") if hit and k in hit[0]}
+            except Exception:
+                pass
+            # The linearisation's flops are COUNTED, not modelled (round 6; rounds 1-5 priced the launch with the forward-mode count of an algorithm it no longer runs: 130 + 260 per
+            # direction and evaluation, 1.0e10 per launch, i.e. "0.42 of the vector peak" -- above anything the 80.6 M counted VALU instructions could deliver).  What runs: the
+            # right-hand side with its local Jacobian once per RK4 stage (tracking_jac: 356 flops by hand with every reciprocal / square root / sincos counted as one), then
+            # ~51 flops per tangent direction (+ 6 for a control direction) -- 832 per ramp stage, 699 per zero-order-hold stage by hand; the ISA of the stage loops (software
+            # sincos, refined reciprocals and square roots included) holds 1204 / 912: tools/isa_mix.py -> profiles/isa_mix.json, per interval x (N_short, N_long) x B.
+            lin_fl, isa_lin = linearize_flops_from_isa(B, mpc.N_short, mpc.N - mpc.N_short, args.precision)
+            peak_lin = FP64_VALU_PEAK_TF if args.precision == "f64" else 2 * FP64_VALU_PEAK_TF
+            valu_lin = {"bound": "valu-" + args.precision, "kernel": "k_nodes_linearize" if pipelined else "k_linearize", "algorithmic_flops_per_launch": lin_fl, "achieved": lin_fl / (lin_ms * 1e-3) / 1e12, "peak": peak_lin,
+                        "unit": "TFLOP/s", "frac": lin_fl / (lin_ms * 1e-3) / 1e12 / peak_lin, "avg_launch_ms": lin_ms, "isa": isa_lin,
+                        # an UPPER bound on executed arithmetic: every fp64 arithmetic instruction of the launch (ISA count) taken as a 64-lane multiply-add
+                        "executed_fp64_frac": None if not isa_lin else isa_lin["arith_wave_insts"] * 128.0 / (lin_ms * 1e-3) / 1e12 / peak_lin,
+                        "source": "flops counted from the ISA of the kernel's loop nests x trip counts (tools/isa_mix.py, profiles/isa_mix.json; the nodes recurrence -- 2 % of the instructions -- is not in it); time live (HIP events: " + ("the nodes + update_qp phase -- projection, the nodes recurrence and the linearisation running under it" if pipelined else "the update_qp phase") + ", no HJI row in the headline run)"}
+            # secondary roofline of the dominant kernel: ALGORITHMIC flops (model above x the iteration counts of THIS run) against the fp64 / fp32 vector peak --
+            # the resource class that binds (the step moves 112 B per solve through HBM, so its HBM fraction is ~1e-5 by construction)
+            rounds = np.where(pol > 0, pol, np.where(pol < 0, 6, 0))
+            fl = float(np.sum(solve_flops(mpc.N, it.astype(np.float64), rounds.astype(np.float64))))
+            peak_tf = FP64_VALU_PEAK_TF if args.precision == "f64" else 2 * FP64_VALU_PEAK_TF
+            valu = {"bound": "valu-" + args.precision, "kernel": "k_solve", "algorithmic_flops_per_launch": fl, "flops_per_solve_mean": fl / B, "achieved": fl / (float(ph[2]) * 1e-3) / 1e12,
+                    "peak": peak_tf, "unit": "TFLOP/s", "frac": fl / (float(ph[2]) * 1e-3) / 1e12 / peak_tf, "avg_launch_ms": float(ph[2]),
+                    "source": "flop model of the stage-structured interior point (bench.py solve_flops, EXPERIMENTS.md 6) x live iteration / polish-round counts; time live (HIP events)"}
+            # the two kernels that make up the step (nodes + update_QP! launch, solve launch), each with what the committed counter passes say about it: the headline `roofline`
+            # names the longer one and lists BOTH (their phases are within a few per cent of each other and swap places from run to run)
+            def kernel_entry(name, match, ms, flop_obj):
+                e = {"kernel": name, "avg_launch_ms": ms, "hbm_frac": B * bytes_per_solve / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "valu_flop_frac": flop_obj["frac"]}
+                if flop_obj.get("executed_fp64_frac") is not None:
+                    e["executed_fp64_frac"] = flop_obj["executed_fp64_frac"]
+                hit_ = [v for k, v in (tr or {}).get("kernels" if args.precision == "f64" else "kernels_f32", {}).items() if match in k]
+                if hit_:
+                    h_ = hit_[0]
+                    e["traffic"] = h_.get("hbm_bytes_per_launch"); e["valu_issue_frac"] = h_.get("valu_issue_frac"); e["avg_launch_ms_rocprof"] = (h_.get("avg_launch_ns_rocprof") or 0) * 1e-6 or None
+                    hw_ = h_.get("hw_flops")
+                    if isinstance(hw_, dict) and hw_.get("valu_flops_per_launch"):
+                        # the hardware's own count of executed arithmetic (SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 of the committed PMC pass) over the LIVE duration
+                        e["hw_valu_flop_frac"] = hw_["valu_flops_per_launch"] / (ms * 1e-3) / 1e12 / hw_["peak_tflops"]; e["hw_arith_share_of_valu_insts"] = hw_.get("arith_share_of_valu_insts")
+                        # ... which IS the flop fraction of this kernel: the model / ISA count stays beside it as `model_flop_frac`
+                        e["model_flop_frac"] = e["valu_flop_frac"]; e["valu_flop_frac"] = e["hw_valu_flop_frac"]; e["valu_flop_frac_source"] = "counters: 64 x (ADD + MUL + TRANS + 2 FMA) wave instructions of the committed PMC pass / live duration"
+                    m_ = h_.get("mfma")
+                    if isinstance(m_, dict):
+                        e["mfma_busy_frac"] = m_.get("busy_frac_of_simd_time"); e["mfma_flop_frac"] = m_.get("frac_of_peak")
+                return e
+            lin_match = ("k_nodes_linearize" if pipelined else "k_linearize")
+            kernels = [kernel_entry("k_solve", "k_solve<false, false, false, false", float(ph[2]), valu), kernel_entry(lin_match, lin_match, lin_ms, valu_lin)]
+            kernels.sort(key=lambda e: -e["avg_launch_ms"])
         try:
             fallbacks = int(mpc.pipeline_fallbacks())
         except Exception:
@@ -943,22 +980,23 @@ def main():
                        "batch_per_gpu": B, "parallelism": f"batch-sharded x{world}, all_gather of controls ({args.backend})" if world > 1 else "single GPU",
                        "solver": "active-set rounds from the empty set on the stage-structured QP (Riccati; pg_config.cold_guess = 8 + structural rules for the steering rows), verified KKT point; instances the rounds do not serve: "
                                  "Mehrotra interior point to mu <= " + ("3e-6" if args.precision == "f64" else "1e-4") + ", then active-set polish (verified KKT point)",
-                       "accuracy": "measured in this run: cpu_baseline.accuracy (sample of 256); every one of the 4096 instances <= 1e-6 is asserted by tests/test_gpu_full_size.py (measured max 5e-11)",
+                       "accuracy": "measured in a --full run: cpu_baseline.accuracy (sample of 256); every one of the 4096 instances <= 1e-6 is asserted by tests/test_gpu_full_size.py (measured max 5e-11)",
                        "instrumentation": "the library's default (option phase_timing = 0: no per-phase HIP events on the stream) in every timed loop; phase_ms / roofline launch times come from "
                                           "separate steps with the events on (they cost 13-25 us of stream time per step)"},
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale, "avg_launch_ms": dom_ms, **dom_extra, "mfma": mfma_util(tr, 2, pipelined), "valu": valu, "valu_linearize": valu_lin,
-                         "kernels": kernels,
-                         "note": f"algorithmic HBM bytes are {bytes_per_solve} B/solve (SURVEY 8d): the step is VALU/LDS/latency bound by construction, not HBM bound; see roofline.kernels (valu_flop_frac, valu_issue_frac, mfma_busy_frac) and roofline.hji_lookup (the bandwidth-bound kernel of the path)"},
-            "phase_ms": {n: float(v) for n, v in zip(names, ph)},
-            "phase_ms_short": {"nodes+update_qp" if pipelined else "nodes": float(ph[0]), "update_qp": float(ph[1]), "solve": float(ph[2])},
             "pipeline_fallbacks": fallbacks, "env": pg_environment(),
-            "warm_value": None if args.no_warm else world * B * args.steps / warm_elapsed,
+            "warm_value": None if warm_elapsed is None else world * B * args.steps / warm_elapsed,
             "solved": f"{ok}/{B}", "gather_ok": gather_ok, "ranks": world if world == 1 else dist.get_world_size(), "collective": None if world == 1 else ("rccl" if args.backend == "nccl" else "gloo"),
             "per_rank_ms_per_step": rank_ms, "gather_ms": gather_ms, "rccl_version": rccl_version(torch) if world > 1 else None, "xgmi": XGMI if world > 1 else None, "ipm_iters_mean": float(np.mean(it)), "ipm_iters_max": int(np.max(it)), "ipm_iters_hist": hist(it),
             "polish_rounds_hist": hist(pol), "polish_note": "k >= 1: verified in round k; 0: not run; -1: not verified (interior-point iterate at 1e-12 kept)",
             "served_by_active_set_guess_alone": int((it == 0).sum()),
         }
+        if args.full:
+            line["roofline"] = {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale, "avg_launch_ms": dom_ms, **dom_extra, "mfma": mfma_util(tr, 2, pipelined), "valu": valu, "valu_linearize": valu_lin,
+                                "kernels": kernels,
+                                "note": f"algorithmic HBM bytes are {bytes_per_solve} B/solve (SURVEY 8d): the step is VALU/LDS/latency bound by construction, not HBM bound; see roofline.kernels (valu_flop_frac, valu_issue_frac, mfma_busy_frac) and roofline.hji_lookup (the bandwidth-bound kernel of the path)"}
+            line["phase_ms"] = {n: float(v) for n, v in zip(names, ph)}
+            line["phase_ms_short"] = {"nodes+update_qp" if pipelined else "nodes": float(ph[0]), "update_qp": float(ph[1]), "solve": float(ph[2])}
         if ipm_only is not None:
             line["interior_point_only"] = ipm_only
         if two_streams is not None:
@@ -981,7 +1019,7 @@ def main():
             line["decoupled_n50"] = dec
         if f32 is not None:
             line["fp32"] = f32
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(pkg, traj, mpc, state, control, t0, toff, args.precision, local)
         # headline numbers of the other BASELINE configs, for the compact line (everything else about them: bench_full.json)
         sec = {"warm_solves_per_s": line["warm_value"]}

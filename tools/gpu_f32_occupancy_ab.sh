@@ -1,7 +1,7 @@
 # What does a second wave per SIMD buy k_solve?  The fp32 kernel is built for two (PG_F32_WAVES=2, shipped) and for one (libpigeon_hip_f32_w1.so: -DPG_F32_WAVES=1);
 # same source, same batch, no stragglers since the settle rule of round 3.  Solve-phase time at 4096 / 8192 / 16384 cold instances.
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-B="bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-decoupled --no-rollout --no-warm --no-hji --no-f32 --precision f32"
+B="bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-decoupled --no-rollout --no-warm --no-hji --no-f32 --precision f32"
 for lib in shipped w1; do
   if [ $lib = w1 ]; then export PIGEON_HIP_LIB_F32=$PWD/pigeon.jl_amd/csrc/libpigeon_hip_f32_w1.so; fi
   for n in 4096 8192 16384; do

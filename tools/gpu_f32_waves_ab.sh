@@ -1,7 +1,7 @@
 # fp32 A/B of an alternative build of the fp32 library (libpigeon_hip_f32_w1.so: whatever experiment it was built with) against the shipped one: config 3, 4096 without the row, 8192 per GPU
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-B="bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-decoupled --no-rollout --no-warm"
+B="bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-decoupled --no-rollout --no-warm"
 run() {
   timeout -k 10 300 python $B > gpurun_out/bench_c3_$1.log 2>&1
   tail -1 gpurun_out/bench_c3_$1.log | python -c "

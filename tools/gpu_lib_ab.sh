@@ -2,7 +2,7 @@
 # instances, phase times) and closed loop; PG_AB_FULL=1 adds the all-paths probe and the solver tests
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-B="bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-hji --no-decoupled --no-f32"
+B="bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-hji --no-decoupled --no-f32"
 run() {
   timeout -k 10 300 python $B > gpurun_out/bench_$1.log 2>&1
   tail -1 gpurun_out/bench_$1.log | python -c "
