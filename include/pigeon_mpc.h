@@ -221,6 +221,27 @@ int pg_simulate_clock(pg_handle* h, double dt, int32_t steps, int32_t B, const d
 /* current device-resident inputs: state [B][6], control [B][3], t0 [B] (host pointers, any may be NULL) */
 int pg_get_state(pg_handle* h, double* state, double* control, double* t0);
 
+/* Safety rollout: simulate (src/model_predictive_control.jl:80-100) with the control the ROS node sends fed back -- the HJI policy when use_hji_policy and V <= HJI_eps in
+ * trajectory mode, else the MPC control (src/ros_integration.jl:114-124; the same decision and bits as pg_get_next_control_hji) -- against a MOVING other car, the human of
+ * relative_dynamics (src/HJI_computation.jl:74-88): SimpleCarState (E, N, psi, V), control (omega, a).  Per step and instance: record state, control and other car (:88-89);
+ * the four compute calls as pg_simulate_dev makes them (with a grid: the step's relative state and its lookup V, gradV); select the control; ego state = propagate(state, OLD
+ * control, dt) as pg_simulate_dev; other car = RK4(other, (omega, a), dt) with rk4_substeps sub-steps of (-V sin psi, V cos psi, omega, a) (psi from North as for the ego,
+ * src/vehicle_dynamics.jl:127-129); control = the selected control; t = the next element of the clock of pg_simulate_dev (same continuation and restart rules).
+ * (omega, a) is held for the step; human_mode: 0 hold = (0, 0) (constant speed and heading: an other car of speed 0 is the frozen car of pg_simulate_dev), 1 worst case =
+ * optimal_disturbance (dMode :min, src/HJI_computation.jl:90-131) at the step's relative state and gradient (no grid or out of the grid: gradV = 0 gives (0, 0)), 2 scripted =
+ * human_u_dev [steps][B][2] = (omega, a).  Without a grid V = +Inf and the MPC control is applied.  Build-defined (the reference only receives the other car from ROS): the
+ * other car's integrator, V <- max(V, 0) after each sub-step, and optimal_disturbance := (0, 0) where the other car's speed is <= 0 (the reference divides by it).
+ * Histories may be NULL: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B] (library element type), source [steps][B] (int32:
+ * 0 MPC, 1 HJI policy, 2 V <= eps with the policy off).  Coupled formulation only (PG_ERR_STATE); human_mode outside {0, 1, 2}, mode 2 without human_u_dev, steps < 1 or
+ * dt <= 0: PG_ERR_INVALID.  Asynchronous on the handle's stream.  Not covered: the NaN fallback (src/ros_integration.jl:134-151) and the low-speed pause (:84-87). */
+int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const pg_real_dev* human_u_dev,
+                           pg_real_dev* state_hist_dev, pg_real_dev* control_hist_dev, pg_real_dev* other_hist_dev,
+                           pg_real_dev* human_hist_dev, pg_real_dev* V_hist_dev, int32_t* source_hist_dev);
+/* other car now [B][4]; per instance since the clock last restarted (pg_set_inputs*, or a rollout with another dt or path end): V_min [B] = the smallest V a safety step
+ * looked up (+Inf: none), first_breach [B] = the first step index (the clock's, continuing across calls) with V <= 0 or -1, policy_steps [B] = steps whose control was the
+ * HJI policy.  Host pointers, any may be NULL. */
+int pg_get_safety_state(pg_handle* h, double* other_car, double* V_min, int32_t* first_breach, int32_t* policy_steps);
+
 /* stream to launch on (hipStream_t as void*); NULL = the null stream.  pg_set_inputs and pg_step are ASYNCHRONOUS on the handle's stream (copies from / into one pinned
  * staging buffer, synchronised at the next entry that needs it): switching streams first waits for whatever is still queued on the old one. */
 int pg_set_stream(pg_handle* h, void* hip_stream);

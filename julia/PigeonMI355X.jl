@@ -199,6 +199,28 @@ function simulate!(mpc::BatchedTrajectoryTrackingMPC, steps::Integer; dt=0.01)
     mpc.current_state, mpc.current_control
 end
 
+const HUMAN_MODES = Dict(:hold => Int32(0), :worst => Int32(1), :script => Int32(2))
+
+"""simulate! with the control the ROS loop sends fed back (src/ros_integration.jl:114-124) against an other car that moves (pg_simulate_safety_dev): human = :hold
+((ω, a) = (0, 0)), :worst (optimal_disturbance, src/HJI_computation.jl:90-131) or :script (human_u_dev: a device array [steps][B][2] of the library's element type).
+Not executed here (no Julia toolchain); the Python mirror simulate_safety_ and tests/test_gpu_safety_rollout.py exercise the same ABI."""
+function simulate_safety!(mpc::BatchedTrajectoryTrackingMPC, steps::Integer; dt=0.01, use_HJI_policy::Bool=true, human::Symbol=:hold, human_u_dev::Ptr{Cvoid}=C_NULL)
+    check(mpc, ccall(sym(mpc, :pg_simulate_safety_dev), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Int32, Ptr{Cvoid}, ntuple(_ -> Ptr{Cvoid}, 6)...),
+                     mpc.handle, steps, dt, use_HJI_policy, HUMAN_MODES[human], human_u_dev, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL), "pg_simulate_safety_dev")
+    check(mpc, ccall(sym(mpc, :pg_get_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mpc.handle, mpc.current_state, mpc.current_control, mpc.t), "pg_get_state")
+    check(mpc, ccall(sym(mpc, :pg_get_safety_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                     mpc.handle, mpc.other_car_state, C_NULL, C_NULL, C_NULL), "pg_get_safety_state")
+    mpc.current_state, mpc.current_control, mpc.other_car_state
+end
+
+"Per controller since the rollout's clock last restarted: (V_min, first step index with V <= 0 or -1, steps on the HJI policy)"
+function safety_summary(mpc::BatchedTrajectoryTrackingMPC)
+    V_min = Vector{Float64}(undef, mpc.B); first_breach = Vector{Int32}(undef, mpc.B); policy_steps = Vector{Int32}(undef, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_safety_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                     mpc.handle, C_NULL, V_min, first_breach, policy_steps), "pg_get_safety_state")
+    V_min, first_breach, policy_steps
+end
+
 "Outcome of the active-set polish per instance: k >= 1 verified in round k (exact optimum on its active set), 0 not run, -1 not verified"
 function polish_info(mpc::BatchedTrajectoryTrackingMPC)
     p = Vector{Int32}(undef, mpc.B)

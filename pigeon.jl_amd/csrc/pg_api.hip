@@ -57,6 +57,8 @@ struct pg_handle {
     real* u_direct = nullptr; bool u_written = false;               // pg_step_dev: the caller's control array for k_solve to write (SolveOut::u_out2), and whether the launch did
     int* d_order = nullptr; int order_B = 0;  // [cap] + 2 counters: launch order filed by the nodes kernels of the current step (likely slow instances first); order_B = batch it is valid for
     real *d_pol_u2 = nullptr, *d_pol_u = nullptr; int* d_pol_src = nullptr;   // HJI fallback policy (HJI_computation.jl:133-158)
+    real* d_vmin = nullptr; int* d_breach = nullptr;          // summary of pg_simulate_safety_dev: V_min [cap]; first_breach [cap] then policy_steps [cap] (k_advance_safety)
+    bool sum_fresh = true;                                    // the summary restarts at the next safety step (the clock restarted since it was last written)
     int *d_status = nullptr, *d_iters = nullptr, *d_polish = nullptr; uint16_t* d_active = nullptr;
     // HJI grid
     HjiView hv; float *d_knots = nullptr, *d_hnodes = nullptr, *d_hcells = nullptr; bool has_hji = false;
@@ -218,7 +220,7 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_ws4, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_ws4, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
@@ -286,6 +288,7 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
 #endif
     if (cfg->walls) { ALLOC(h->d_walls, cap * N * 2, real); C.walls = 1; C.wall_weight = (real)cfg->wall_weight; C.wall_edges = h->d_walls; if (h->solve_quad) { g_create_error = "the experimental quad solver does not carry the wall rows"; free_all(h); delete h; return PG_ERR_INVALID; } }
     ALLOC(h->d_pol_u2, cap * 2, real); ALLOC(h->d_pol_u, cap * 3, real); ALLOC(h->d_pol_src, cap, int);
+    ALLOC(h->d_vmin, cap, real); ALLOC(h->d_breach, 2 * cap, int);
     // The lateral formulation has a solve kernel of its own (k_solve_lat, pg_solve_lat.hip) for horizons beyond 20 intervals.  Shorter ones -- the reference's on-vehicle
     // N_short = 5, N_long = 10 among them -- stay with the embedding in k_solve when the polish is on: its active-set rounds from the empty set serve a short lateral QP
     // without any interior-point iteration (N = 15, 4096 instances: 0.12 ms against 0.37), an advantage that is gone at N = 30 (2.4 against 1.5 ms) and reversed at
@@ -650,7 +653,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0;      // (new times: the clock of pg_simulate_dev restarts from them)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     int rc;
     if (host) {
@@ -1147,17 +1150,21 @@ int pg_step_dev(pg_handle* h, void* u_out_dev) {
     h->timing_valid = ev;
     return PG_OK;
 }
+// the loop's clock (:87): t takes the elements of 0:dt:trajectory.t[end], here shifted by each instance's start time.  A call continues the clock of the previous one
+// (same dt, same path end, no pg_set_inputs in between); otherwise it restarts from the times the inputs carry (and so does the safety summary)
+static int clock_start(pg_handle* h, double dt) {
+    if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
+        HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true;
+    }
+    return PG_OK;
+}
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev_, void* control_hist_dev_) {
     int rc = check_ready(h); if (rc) return rc;
     REQUIRE(h, steps >= 1 && dt > 0.0, "pg_simulate_dev: steps >= 1 and dt > 0 required");
     const int B = h->B;
     real* state_hist_dev = (real*)state_hist_dev_; real* control_hist_dev = (real*)control_hist_dev_;
-    // the loop's clock (:87): t takes the elements of 0:dt:trajectory.t[end], here shifted by each instance's start time.  A call continues the clock of the previous one
-    // (same dt, same path end, no pg_set_inputs in between); otherwise it restarts from the times the inputs carry
-    if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
-        HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end;
-    }
+    if ((rc = clock_start(h, dt))) return rc;                           // the loop's clock (:87)
     for (int k = 0; k < steps; k++) {
         if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(state_hist_dev + (size_t)k * B * 6, h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // push!(qs, state) :88
         if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(control_hist_dev + (size_t)k * B * 3, h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream)); // push!(us, control) :89
@@ -1166,6 +1173,50 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
         hipLaunchKernelGGL(k_advance, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx);      // :94-95
         LAUNCH_CHECK(h);
     }
+    return PG_OK;
+}
+// simulate (:80-100) with the control the ROS node sends (ros_integration.jl:114-124) fed back and the other car moving (k_advance_safety, pg_kernels.hip).  Per step: the four
+// compute calls exactly as pg_simulate_dev makes them (fusion, pipelining and the split solve unchanged; with a grid they leave the step's relative state d_x7 and its
+// lookup d_vg8), then ONE launch for the records, the selection, both plants, the new control, the clock and the summary
+int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev_,
+                           void* state_hist_dev_, void* control_hist_dev_, void* other_hist_dev_, void* human_hist_dev_, void* V_hist_dev_, int32_t* source_hist_dev) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dc.formulation != PG_COUPLED) { h->err = "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row"; return PG_ERR_STATE; }
+    REQUIRE(h, steps >= 1 && dt > 0.0, "pg_simulate_safety_dev: steps >= 1 and dt > 0 required");
+    REQUIRE(h, human_mode >= 0 && human_mode <= 2, "pg_simulate_safety_dev: human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
+    REQUIRE(h, human_mode != 2 || human_u_dev_, "pg_simulate_safety_dev: human_mode 2 needs human_u_dev [steps][B][2]");
+    const int B = h->B; const size_t Bz = (size_t)B;
+    const real* human_u_dev = (const real*)human_u_dev_;
+    real *sh = (real*)state_hist_dev_, *ch = (real*)control_hist_dev_, *oh = (real*)other_hist_dev_, *hh = (real*)human_hist_dev_, *vh = (real*)V_hist_dev_;
+    if ((rc = clock_start(h, dt))) return rc;
+    for (int k = 0; k < steps; k++) {
+        if ((rc = launch_nodes(h, true)) || (rc = update_and_solve(h, nullptr))) return rc;          // :90-93
+        const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
+        h->sim_idx++;
+        SafetyIO io{human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr, sh ? sh + (size_t)k * Bz * 6 : nullptr, ch ? ch + (size_t)k * Bz * 3 : nullptr,
+                    oh ? oh + (size_t)k * Bz * 4 : nullptr, hh ? hh + (size_t)k * Bz * 2 : nullptr, vh ? vh + (size_t)k * Bz : nullptr,
+                    source_hist_dev ? source_hist_dev + (size_t)k * Bz : nullptr, h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
+        hipLaunchKernelGGL(k_advance_safety, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji,
+                           (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
+        LAUNCH_CHECK(h);
+        h->sum_fresh = false;
+    }
+    return PG_OK;
+}
+int pg_get_safety_state(pg_handle* h, double* other_car, double* V_min, int32_t* first_breach, int32_t* policy_steps) {
+    int rc = check_ready(h); if (rc) return rc;
+    const size_t B = h->B;
+    if ((rc = down(h, other_car, h->d_other, B * 4))) return rc;
+    if (h->sum_fresh) {                  // no safety step since the clock (re)started
+        for (size_t b = 0; b < B; b++) {
+            if (V_min) V_min[b] = INFINITY;
+            if (first_breach) first_breach[b] = -1;
+            if (policy_steps) policy_steps[b] = 0;
+        }
+        return PG_OK;
+    }
+    if ((rc = down(h, V_min, h->d_vmin, B)) || (rc = down_raw(h, first_breach, h->d_breach, B * sizeof(int32_t))) ||
+        (rc = down_raw(h, policy_steps, h->d_breach + h->cfg.batch_capacity, B * sizeof(int32_t)))) return rc;
     return PG_OK;
 }
 int pg_simulate_clock(pg_handle* h, double dt, int32_t steps, int32_t B, const double* t_start, double* out) {

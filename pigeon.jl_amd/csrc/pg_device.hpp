@@ -605,5 +605,47 @@ PG_DEV real adiff(real x, real y) {
     if (d < real(0.0)) d += twopi;
     return d <= real(3.14159265358979323846) ? d : d - twopi;
 }
+// optimal_disturbance (dMode = :min) HJI_computation.jl:90-131: the human's worst-case control (omega, a) at relative state x = (dE, dN, dpsi, Ux, Uy, V, r)
+// against gradient g = gradV[0..6].  As written in the reference: a zero gradient gives (0, 0) through lam_norm < 1e-3 (:106-107), and V <= 0 divides by zero
+// (the caller decides what that means: k_hji_constraint keeps the reference's NaN; k_advance_safety defines (0, 0))
+PG_DEV void optimal_disturbance(const DevVehicle& P, const real* x, const real* g, real& uH0, real& uH1) {
+    real Ax_max = P.Fx_max / P.m, Pmx = P.Px_max / P.m, maxA = real(0.9) * P.mu * P.G;
+    real Vh = x[5], lam_Ax = g[5], lam_Ay = g[2] / Vh;
+    real nrm = (lam_Ax != lam_Ax || lam_Ay != lam_Ay) ? NAN : hypot(lam_Ax, lam_Ay);
+    if (nrm < real(1e-3)) { uH0 = real(0.0); uH1 = real(0.0); }
+    else {
+        real desAx = -lam_Ax * maxA / nrm, desAy = -lam_Ay * maxA / nrm;
+        real maxAx = jmin(Ax_max, Pmx / Vh), maxAy = P.kappa_max * Vh * Vh;
+        if (desAx > maxAx) {
+            if (fabs(desAy) < maxAy) maxAy = jmin(maxAy, sqrt(maxA * maxA - maxAx * maxAx));
+            uH0 = copysign(maxAy, desAy) / Vh; uH1 = maxAx;
+        } else if (fabs(desAy) > maxAy) {
+            if (desAx > real(0.0)) { maxAx = jmin(sqrt(maxA * maxA - maxAy * maxAy), maxAx); uH0 = copysign(maxAy, desAy) / Vh; uH1 = maxAx; }
+            else { uH0 = copysign(maxAy, desAy) / Vh; uH1 = -sqrt(maxA * maxA - maxAy * maxAy); }
+        } else { uH0 = desAy / Vh; uH1 = maxAx; }
+    }
+}
+// The other car of the safety rollout (build-defined: the reference only receives it from ROS): SimpleCarState (E, N, psi, V) with control (omega, a), the model
+// relative_dynamics integrates (HJI_computation.jl:74-88); psi measured from North as for the ego (vehicle_dynamics.jl:127-129, ros_integration.jl:154).
+// nsub classical RK4 sub-steps of length h with (omega, a) held; V <- max(V, 0) after every sub-step (a car does not reverse under braking)
+PG_DEV void unicycle_rhs(const real* y, real w, real a, real* o) {
+    real s, c; pg_sincos(y[2], &s, &c);
+    o[0] = -y[3] * s; o[1] = y[3] * c; o[2] = w; o[3] = a;
+}
+PG_DEV void advance_unicycle(real* x, real w, real a, real h, int nsub) {
+#pragma unroll 1
+    for (int i = 0; i < nsub; i++) {
+        real k1[4], k2[4], k3[4], k4[4], y[4];
+        unicycle_rhs(x, w, a, k1);
+        for (int k = 0; k < 4; k++) y[k] = x[k] + k1[k] * (h * real(0.5));
+        unicycle_rhs(y, w, a, k2);
+        for (int k = 0; k < 4; k++) y[k] = x[k] + k2[k] * (h * real(0.5));
+        unicycle_rhs(y, w, a, k3);
+        for (int k = 0; k < 4; k++) y[k] = x[k] + k3[k] * h;
+        unicycle_rhs(y, w, a, k4);
+        for (int k = 0; k < 4; k++) x[k] += (k1[k] + real(2.0) * k2[k] + real(2.0) * k3[k] + k4[k]) * (h / real(6.0));
+        x[3] = x[3] < real(0.0) ? real(0.0) : x[3];
+    }
+}
 
 }  // namespace pg

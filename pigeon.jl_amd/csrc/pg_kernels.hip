@@ -848,6 +848,28 @@ template <bool STAGED, int LPI, int WAVES = 1> __global__ __launch_bounds__(64, 
     PG_NL_MARK(2, wall_clock64());
 }
 
+// the plant's RK4 of one step, in place: x = (E, N, psi, Ux, Uy, r), control (delta, Fx) held, nsub sub-steps of length h -- the arithmetic of k_advance below, for
+// k_advance_safety (k_advance keeps its own statement of it: calling this from there regroups the fp32 build's packed FMAs and so changes that library's bits)
+PG_DEV void advance_ego(const DevCfg& C, real* x, real d, real Fx, real h, int nsub) {
+    auto rhs = [&](const real* y, real* o) {
+        real s, c; pg_sincos(y[2], &s, &c);
+        o[0] = -y[3] * s - y[4] * c; o[1] = y[3] * c - y[4] * s; o[2] = y[5];          // psi measured from North (:127-129)
+        world_body_rhs<real>(C.veh, y[3], y[4], y[5], d, Fx, o[3], o[4], o[5]);
+    };
+#pragma unroll 1
+    for (int i = 0; i < nsub; i++) {
+        real k1[6], k2[6], k3[6], k4[6], y[6];
+        rhs(x, k1);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k1[k] * (h * real(0.5));
+        rhs(y, k2);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k2[k] * (h * real(0.5));
+        rhs(y, k3);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k3[k] * h;
+        rhs(y, k4);
+        for (int k = 0; k < 6; k++) x[k] += (k1[k] + real(2.0) * k2[k] + real(2.0) * k3[k] + k4[k]) * (h / real(6.0));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Closed-loop plant step of `simulate` (model_predictive_control.jl:94-95), lane = instance:
 //   state   <- propagate(dynamics, state, StepControl(dt, BicycleControl2(current_control)))   (RK4, nsub sub-steps, world-frame BicycleModel
@@ -1327,23 +1349,7 @@ __global__ __launch_bounds__(64) void k_hji_constraint(DevCfg C, int B, const re
     o[3] = Vv;
     if (Vv > C.hji_eps) { o[0] = real(0.0); o[1] = real(0.0); o[2] = real(1.0); return; }           // :163-164
     real uH0, uH1;
-    {
-        real Ax_max = P.Fx_max / P.m, Pmx = P.Px_max / P.m, maxA = real(0.9) * P.mu * P.G;
-        real Vh = x[5], lam_Ax = g[5], lam_Ay = g[2] / Vh;
-        real nrm = (lam_Ax != lam_Ax || lam_Ay != lam_Ay) ? NAN : hypot(lam_Ax, lam_Ay);
-        if (nrm < real(1e-3)) { uH0 = real(0.0); uH1 = real(0.0); }
-        else {
-            real desAx = -lam_Ax * maxA / nrm, desAy = -lam_Ay * maxA / nrm;
-            real maxAx = jmin(Ax_max, Pmx / Vh), maxAy = P.kappa_max * Vh * Vh;
-            if (desAx > maxAx) {
-                if (fabs(desAy) < maxAy) maxAy = jmin(maxAy, sqrt(maxA * maxA - maxAx * maxAx));
-                uH0 = copysign(maxAy, desAy) / Vh; uH1 = maxAx;
-            } else if (fabs(desAy) > maxAy) {
-                if (desAx > real(0.0)) { maxAx = jmin(sqrt(maxA * maxA - maxAy * maxAy), maxAx); uH0 = copysign(maxAy, desAy) / Vh; uH1 = maxAx; }
-                else { uH0 = copysign(maxAy, desAy) / Vh; uH1 = -sqrt(maxA * maxA - maxAy * maxAy); }
-            } else { uH0 = desAy / Vh; uH1 = maxAx; }
-        }
-    }
+    optimal_disturbance(P, x, g, uH0, uH1);
     const real* u = control + (size_t)b * 3;
     real uR0 = u[0], uR1 = u[1] + u[2];
     D2 dUx, dUy, dr;
@@ -1356,15 +1362,9 @@ __global__ __launch_bounds__(64) void k_hji_constraint(DevCfg C, int B, const re
     o[2] = Hm.v - (M0 * uR0 + M1 * uR1);                                           // :168
 }
 
-// optimal_control (uMode=:max, N=50) HJI_computation.jl:133-158 and the control selection of the ROS loop (ros_integration.jl:114-124), lane = instance.
-// u2 [B][2] = (delta_opt, Fx_opt) whenever the relative state is inside the grid; u_next [B][3] = the policy's BicycleControl when it takes over
-// (traj mode, use_policy, V <= eps), else the MPC control u_mpc; source: 0 MPC, 1 HJI policy, 2 V <= eps but the policy is switched off.
-__global__ __launch_bounds__(64) void k_hji_policy(DevCfg C, int B, int use_policy, const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
-                                                   const real* __restrict__ u_mpc, real* __restrict__ u2, real* __restrict__ u_next, int* __restrict__ source) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const DevVehicle& P = C.veh;
-    const real* x = x7 + (size_t)b * 7; const real* vg = vg8 + (size_t)b * 8; const real* g = vg + 1;
+// optimal_control (uMode=:max, N=50) HJI_computation.jl:133-158 at relative state x and gradient g = gradV[0..6]: (delta_opt, Fx_opt).  The line search keeps the FIRST
+// strict maximum of the 50 candidates (NaN never wins), one lane per instance
+PG_DEV void hji_optimal_control(const DevVehicle& P, const real* x, const real* g, real& d_opt_out, real& Fx_opt_out) {
     const real Ux = x[3], Uy = x[4], r = x[6];
     const real A = g[3] / P.m, Bc = g[4] / P.m + P.a * g[6] / P.Izz, Cc = g[4] / P.m - P.b * g[6] / P.Izz;      // :140-142
     const real d_opt = Bc >= real(0.0) ? P.delta_max : -P.delta_max;                                                   // :143
@@ -1382,16 +1382,102 @@ __global__ __launch_bounds__(64) void k_hji_policy(DevCfg C, int B, int use_poli
         real V = A * Fx + Bc * Fyf + Cc * Fyr;
         if (V > V_opt) { Fx_opt = Fx; V_opt = V; }
     }
+    d_opt_out = d_opt; Fx_opt_out = Fx_opt;
+}
+// the control selection of the ROS loop (ros_integration.jl:114-124): 0 MPC, 1 HJI policy (traj mode, use_policy, V <= eps), 2 V <= eps but the policy is switched off
+PG_DEV int hji_source(const DevCfg& C, int use_policy, real V, tdouble toff) {
+    const bool traj_mode = toff == toff;
+    const bool unsafe = traj_mode && V <= C.hji_eps;
+    return unsafe ? (use_policy ? 1 : 2) : 0;
+}
+// BicycleControl(longitudinal_params, BicycleControl2(delta_opt, Fx_opt))  (vehicle_dynamics.jl:284)
+PG_DEV void hji_policy_control(const DevVehicle& P, real d_opt, real Fx_opt, real& o0, real& o1, real& o2) {
+    o0 = d_opt; o1 = Fx_opt > real(0.0) ? Fx_opt * P.fwd_frac : Fx_opt * P.fwb_frac; o2 = Fx_opt > real(0.0) ? Fx_opt * P.rwd_frac : Fx_opt * P.rwb_frac;
+}
+
+// optimal_control and the control selection (above) as the one-step call pg_get_next_control_hji makes them, lane = instance.
+// u2 [B][2] = (delta_opt, Fx_opt) whenever the relative state is inside the grid; u_next [B][3] = the policy's BicycleControl when it takes over
+// (traj mode, use_policy, V <= eps), else the MPC control u_mpc; source: 0 MPC, 1 HJI policy, 2 V <= eps but the policy is switched off.
+__global__ __launch_bounds__(64) void k_hji_policy(DevCfg C, int B, int use_policy, const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                   const real* __restrict__ u_mpc, real* __restrict__ u2, real* __restrict__ u_next, int* __restrict__ source) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevVehicle& P = C.veh;
+    const real* x = x7 + (size_t)b * 7; const real* vg = vg8 + (size_t)b * 8; const real* g = vg + 1;
+    real d_opt, Fx_opt;
+    hji_optimal_control(P, x, g, d_opt, Fx_opt);
     u2[(size_t)b * 2] = d_opt; u2[(size_t)b * 2 + 1] = Fx_opt;
-    const bool traj_mode = toff[b] == toff[b];
-    const bool unsafe = traj_mode && vg[0] <= C.hji_eps;
-    int src = unsafe ? (use_policy ? 1 : 2) : 0;
+    const int src = hji_source(C, use_policy, vg[0], toff[b]);
     real o0 = u_mpc[(size_t)b * 3], o1 = u_mpc[(size_t)b * 3 + 1], o2 = u_mpc[(size_t)b * 3 + 2];
-    if (src == 1) {                  // BicycleControl(longitudinal_params, BicycleControl2(delta_opt, Fx_opt))  (vehicle_dynamics.jl:284)
-        o0 = d_opt; o1 = Fx_opt > real(0.0) ? Fx_opt * P.fwd_frac : Fx_opt * P.fwb_frac; o2 = Fx_opt > real(0.0) ? Fx_opt * P.rwd_frac : Fx_opt * P.rwb_frac;
-    }
+    if (src == 1) hji_policy_control(P, d_opt, Fx_opt, o0, o1, o2);
     u_next[(size_t)b * 3] = o0; u_next[(size_t)b * 3 + 1] = o1; u_next[(size_t)b * 3 + 2] = o2;
     source[b] = src;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Safety rollout (pg_simulate_safety_dev): the controller Pigeon deploys, in closed loop against a MOVING other car.  One step is the order of `simulate`
+// (model_predictive_control.jl:88-95) with the control the ROS node sends (ros_integration.jl:114-124) fed back; this kernel is everything after the solve, lane = instance:
+//   records  state, control, other car at the start of the step (push!, :88-89), the human's (omega, a), V and the source of the control
+//   select   hji_source / hji_optimal_control / hji_policy_control, the same device functions (and bits) as k_hji_policy; no grid: V = +Inf, source 0 (x7 / vg8 are not read)
+//   ego      advance_ego with the OLD control (one-step actuation delay), as k_advance
+//   other    advance_unicycle (pg_device.hpp) with (omega, a) held: mode 0 (0, 0); mode 1 optimal_disturbance (dMode :min, HJI_computation.jl:90-131) at this step's
+//            relative state and gradient; mode 2 the caller's script
+//   control  <- the selected control;  t <- the next element of the loop's clock (as k_advance)
+//   summary  V_min, first step index with V <= 0 (-1: none), steps with source 1; `restart` starts them afresh (the clock restarted)
+// Build-defined (the reference only receives the other car from ROS): the other car's RK4 and the clamp V >= 0 after each sub-step, and optimal_disturbance := (0, 0) where the
+// other car's speed is <= 0 (the reference divides by it there).
+struct SafetyIO {
+    const real* human_u;                                                 // [B][2] this step's script (human mode 2), else nullptr
+    real *state_h, *control_h, *other_h, *human_h, *V_h; int* src_h;       // this step's records [B][6] / [B][3] / [B][4] / [B][2] / [B] / [B]: each may be nullptr
+    real* V_min; int* first_breach; int* policy_steps;                   // summary [B]
+};
+__global__ __launch_bounds__(64) void k_advance_safety(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart, int step,
+                                                       real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                       const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                       tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, SafetyIO io) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevVehicle& P = C.veh;
+    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3; real* ot = other + (size_t)b * 4;
+    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+    real uc[3] = {u[0], u[1], u[2]};
+    real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
+    if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
+    if (io.control_h) for (int k = 0; k < 3; k++) io.control_h[(size_t)b * 3 + k] = uc[k];
+    if (io.other_h) for (int k = 0; k < 4; k++) io.other_h[(size_t)b * 4 + k] = oc[k];
+    // select (ros_integration.jl:114-124)
+    const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);
+    const int src = has_hji ? hji_source(C, use_policy, V, toff[b]) : 0;
+    real n0 = u_mpc[(size_t)b * 3], n1 = u_mpc[(size_t)b * 3 + 1], n2 = u_mpc[(size_t)b * 3 + 2];
+    if (src == 1) {
+        real d_opt, Fx_opt;
+        hji_optimal_control(P, x7 + (size_t)b * 7, vg8 + (size_t)b * 8 + 1, d_opt, Fx_opt);
+        hji_policy_control(P, d_opt, Fx_opt, n0, n1, n2);
+    }
+    // the human's control, held for the step
+    real w = real(0.0), a = real(0.0);
+    if (human_mode == 1 && has_hji) {
+        const real* xr = x7 + (size_t)b * 7;
+        if (xr[5] > real(0.0)) optimal_disturbance(P, xr, vg8 + (size_t)b * 8 + 1, w, a);
+    } else if (human_mode == 2) {
+        w = io.human_u[(size_t)b * 2]; a = io.human_u[(size_t)b * 2 + 1];
+    }
+    const int nsub = C.nsub; const real h = dtp / nsub;
+    advance_ego(C, x, uc[0], uc[1] + uc[2], h, nsub);
+    advance_unicycle(oc, w, a, h, nsub);
+    for (int k = 0; k < 6; k++) q[k] = x[k];
+    for (int k = 0; k < 4; k++) ot[k] = oc[k];
+    u[0] = n0; u[1] = n1; u[2] = n2;
+    t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
+    if (io.human_h) { io.human_h[(size_t)b * 2] = w; io.human_h[(size_t)b * 2 + 1] = a; }
+    if (io.V_h) io.V_h[b] = V;
+    if (io.src_h) io.src_h[b] = src;
+    real vmin = restart ? real(INFINITY) : io.V_min[b];
+    int fb = restart ? -1 : io.first_breach[b], ps = restart ? 0 : io.policy_steps[b];
+    if (V < vmin) vmin = V;
+    if (fb < 0 && V <= real(0.0)) fb = step;
+    if (src == 1) ps++;
+    io.V_min[b] = vmin; io.first_breach[b] = fb; io.policy_steps[b] = ps;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

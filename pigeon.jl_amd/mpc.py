@@ -248,6 +248,46 @@ class BatchedTrajectoryTrackingMPC:
             qh = dq.cpu().numpy().astype(np.float64); uh = du.cpu().numpy().astype(np.float64)
         return s, c, t, qh, uh
 
+    HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
+
+    def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False):
+        """Safety rollout (pg_simulate_safety_dev): simulate with the control the ROS node sends (ros_integration.jl:114-124) fed back, against an other car that moves.
+        human: "hold" (omega, a) = (0, 0), "worst" optimal_disturbance (HJI_computation.jl:90-131), "script" human_u [steps][B][2] = (omega, a).  Returns (state, control, t,
+        other) after `steps` steps and, with record=True, a dict of histories: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B],
+        source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step."""
+        import ctypes as C_
+        import torch
+        assert human in self.HUMAN_MODES, human
+        dev = f"cuda:{self.cfg.device}"
+        tdt = torch.float32 if self.precision == "f32" else torch.float64         # device arrays have the library's own element type
+        hu = None
+        if human == "script":
+            if human_u is None:
+                raise ValueError('human="script" needs human_u [steps][B][2]')
+            hu = torch.as_tensor(np.ascontiguousarray(human_u, dtype=np.float64).reshape(steps, self.B, 2)).to(device=dev, dtype=tdt).contiguous()
+        shapes = {"state": (6,), "control": (3,), "other": (4,), "human": (2,), "V": ()}
+        hist = {k: torch.empty((steps, self.B) + s, dtype=tdt, device=dev) for k, s in shapes.items()} if record else {}
+        if record:
+            hist["source"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
+        ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C_.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
+                                                  *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
+        s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
+        self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
+        self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
+        if not record:
+            return s, c, t, o
+        out = {k: v.cpu().numpy() for k, v in hist.items()}
+        for k in shapes:
+            out[k] = out[k].astype(np.float64)
+        return s, c, t, o, out
+
+    def safety_summary(self):
+        """Per instance since the rollout's clock last restarted: (V_min [B], first_breach [B] (first step index with V <= 0, -1: none), policy_steps [B])."""
+        vmin = np.zeros(self.B); fb = np.zeros(self.B, dtype=np.int32); ps = np.zeros(self.B, dtype=np.int32)
+        self._chk(self.lib.pg_get_safety_state(self.h, None, _p(vmin), _p(fb, C.POINTER(C.c_int32)), _p(ps, C.POINTER(C.c_int32))), "pg_get_safety_state")
+        return vmin, fb, ps
+
     def simulate_clock(self, steps, t_start, dt=0.01):
         """The times the rollout's loop variable takes, per instance: (t_start .+ (0:dt:trajectory.t[end]))[1:steps] as Julia's range arithmetic gives them
         (model_predictive_control.jl:87; pg_simulate_clock) -- [steps][B]."""
