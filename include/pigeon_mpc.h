@@ -233,7 +233,8 @@ int pg_get_state(pg_handle* h, double* state, double* control, double* t0);
  * other car's integrator, V <- max(V, 0) after each sub-step, and optimal_disturbance := (0, 0) where the other car's speed is <= 0 (the reference divides by it).
  * Histories may be NULL: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B] (library element type), source [steps][B] (int32:
  * 0 MPC, 1 HJI policy, 2 V <= eps with the policy off).  Coupled formulation only (PG_ERR_STATE); human_mode outside {0, 1, 2}, mode 2 without human_u_dev, steps < 1 or
- * dt <= 0: PG_ERR_INVALID.  Asynchronous on the handle's stream.  Not covered: the NaN fallback (src/ros_integration.jl:134-151) and the low-speed pause (:84-87). */
+ * dt <= 0: PG_ERR_INVALID.  Asynchronous on the handle's stream.  The gates of the node (pre_flag, the trajectory-time window, the low-speed pause), the NaN fallback and
+ * the decoupled formulation are pg_simulate_node_dev's (below). */
 int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const pg_real_dev* human_u_dev,
                            pg_real_dev* state_hist_dev, pg_real_dev* control_hist_dev, pg_real_dev* other_hist_dev,
                            pg_real_dev* human_hist_dev, pg_real_dev* V_hist_dev, int32_t* source_hist_dev);
@@ -241,6 +242,40 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
  * looked up (+Inf: none), first_breach [B] = the first step index (the clock's, continuing across calls) with V <= 0 or -1, policy_steps [B] = steps whose control was the
  * HJI policy.  Host pointers, any may be NULL. */
 int pg_get_safety_state(pg_handle* h, double* other_car, double* V_min, int32_t* first_breach, int32_t* policy_steps);
+
+/* Node callback: the per-message decision of from_autobox_callback (src/ros_integration.jl:48-151) for every instance of the batch.  Per instance, in order: V, gradV looked
+ * up (:55-57, before any gate); pre_flag == 0: return (:70-73); trajectory mode (time_offset not NaN) and t0 < 0 or t0 > trajectory.t[end] of the instance's trajectory:
+ * return (:79-82); Ux < 1 (the literal 1 m/s, :84-87): return; else the four compute calls and heartbeat + 1 (:94-112), the selection of pg_get_next_control_hji (:114-124),
+ * and the NaN fallback (:134-147): a NaN (not an Inf) in any published component publishes the current message instead, sets the message to 0 and starts the solver cold
+ * (solved = false).  A return publishes nothing and leaves the instance's solver state exactly as it was.  Events: */
+enum pg_node_event {
+    PG_NODE_MPC = 0,                /* the MPC control was published */
+    PG_NODE_HJI_POLICY = 1,         /* the HJI policy was published (trajectory mode, use_hji_policy, V <= HJI_eps) */
+    PG_NODE_FEATHER = 2,            /* V <= HJI_eps in trajectory mode with the policy off: the MPC control was published */
+    PG_NODE_NAN_FALLBACK = 3,       /* the selected control had a NaN: the previous message was published, the message is now 0 */
+    PG_NODE_PRE_FLAG_OFF = 4,       /* gated out: pre_flag == 0 */
+    PG_NODE_OUTSIDE_TRAJECTORY = 5, /* gated out: trajectory mode, t outside [0, trajectory.t[end]] */
+    PG_NODE_LOW_SPEED = 6           /* gated out: Ux < 1 m/s */
+};
+/* One callback for every instance on the installed inputs.  The installed control plays current_control, the to_autobox message (:52); on return it is the message after
+ * the callback (the published command, 0 after a fallback, unchanged when gated out).  Device outputs, each may be NULL: cmd_out [B][3] the published command (lanes that
+ * publish nothing are not written), se_out [B][2] (s, e) of the step's projection (:114), event [B] (int32, pg_node_event).  pre_flag_dev [B] (uint8) or NULL = engaged.
+ * The clock does not advance.  Decoupled handles: V = +Inf, use_hji_policy != 0 is PG_ERR_STATE.  Gated-out instances are computed too (their results are discarded):
+ * the call costs a full step.  Asynchronous on the handle's stream. */
+int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_flag_dev, pg_real_dev* cmd_out_dev, pg_real_dev* se_out_dev, int32_t* event_dev);
+/* The node's closed loop.  Each instance keeps two controls: the message (the installed control) and the applied command (what the plant executes; initialised from the
+ * installed control whenever the clock restarts).  Per step: the gates; the compute calls as pg_simulate_safety_dev makes them; the callback's decision as above; the records
+ * (state and applied command at the step's start, the step's V, the event); ego state = propagate(state, applied command at the step's start, dt); applied command = the
+ * published one where something was published; the other car as pg_simulate_safety_dev (human_mode, human_u_dev); the clock of pg_simulate_dev (continuing past the range's
+ * end with the same element formula); the safety summary of pg_get_safety_state (V_min and first breach at every step, policy steps: published policy commands).
+ * pre_flag_dev [steps][B] or NULL.  Histories may be NULL: state [steps][B][6], applied [steps][B][3], V [steps][B] (library element type), event [steps][B] (int32).
+ * With every gate open and no NaN this is pg_simulate_safety_dev.  steps < 1, dt <= 0, human_mode outside {0, 1, 2}, mode 2 without human_u_dev: PG_ERR_INVALID;
+ * use_hji_policy on a decoupled handle: PG_ERR_STATE.  Asynchronous on the handle's stream. */
+int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const pg_real_dev* human_u_dev, const uint8_t* pre_flag_dev,
+                         pg_real_dev* state_hist_dev, pg_real_dev* applied_hist_dev, int32_t* event_hist_dev, pg_real_dev* V_hist_dev);
+/* applied command [B][3]; heartbeat [B] (callbacks that ran the compute calls; zero at the first node call, never reset); counts [B][4] = steps with pre_flag off, outside
+ * the window, low speed, NaN fallback since the clock last restarted (the restart rule of pg_get_safety_state).  Host pointers, any may be NULL. */
+int pg_get_node_state(pg_handle* h, double* applied, int32_t* heartbeat, int32_t* counts);
 
 /* stream to launch on (hipStream_t as void*); NULL = the null stream.  pg_set_inputs and pg_step are ASYNCHRONOUS on the handle's stream (copies from / into one pinned
  * staging buffer, synchronised at the next entry that needs it): switching streams first waits for whatever is still queued on the old one. */

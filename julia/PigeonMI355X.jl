@@ -221,6 +221,39 @@ function safety_summary(mpc::BatchedTrajectoryTrackingMPC)
     V_min, first_breach, policy_steps
 end
 
+"""from_autobox_callback (src/ros_integration.jl:48-151) for every controller on the installed inputs (pg_node_step_dev): the gates (pre_flag, the trajectory-time window,
+Ux < 1), the compute calls, the selection and the NaN fallback.  current_control plays the to_autobox message and holds the message after the callback on return.
+pre_flag_dev, cmd_out_dev, se_out_dev, event_dev: device arrays or C_NULL (pre_flag [B] UInt8; cmd [B][3], se [B][2] of the library's element type; event [B] Int32).
+Not executed here (no Julia toolchain); the Python mirror node_step_ and tests/test_gpu_node.py exercise the same ABI."""
+function from_autobox_step!(mpc::BatchedTrajectoryTrackingMPC; use_HJI_policy::Bool=false, pre_flag_dev::Ptr{Cvoid}=C_NULL, cmd_out_dev::Ptr{Cvoid}=C_NULL,
+                            se_out_dev::Ptr{Cvoid}=C_NULL, event_dev::Ptr{Cvoid}=C_NULL)
+    check(mpc, ccall(sym(mpc, :pg_node_step_dev), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     mpc.handle, use_HJI_policy, pre_flag_dev, cmd_out_dev, se_out_dev, event_dev), "pg_node_step_dev")
+    check(mpc, ccall(sym(mpc, :pg_get_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mpc.handle, mpc.current_state, mpc.current_control, mpc.t), "pg_get_state")
+    mpc.current_control
+end
+
+"""The node's closed loop (pg_simulate_node_dev): simulate_safety! with the node's gates and NaN fallback, the plant driven by the command last published (the applied
+command).  pre_flag_dev: a device array [steps][B] UInt8 or C_NULL (engaged).  Returns (state, message, other car, applied command); node_state gives heartbeat and counts.
+Not executed here (no Julia toolchain); the Python mirror simulate_node_ and tests/test_gpu_node.py exercise the same ABI."""
+function simulate_node!(mpc::BatchedTrajectoryTrackingMPC, steps::Integer; dt=0.01, use_HJI_policy::Bool=false, human::Symbol=:hold, human_u_dev::Ptr{Cvoid}=C_NULL,
+                        pre_flag_dev::Ptr{Cvoid}=C_NULL)
+    check(mpc, ccall(sym(mpc, :pg_simulate_node_dev), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, ntuple(_ -> Ptr{Cvoid}, 4)...),
+                     mpc.handle, steps, dt, use_HJI_policy, HUMAN_MODES[human], human_u_dev, pre_flag_dev, C_NULL, C_NULL, C_NULL, C_NULL), "pg_simulate_node_dev")
+    check(mpc, ccall(sym(mpc, :pg_get_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mpc.handle, mpc.current_state, mpc.current_control, mpc.t), "pg_get_state")
+    check(mpc, ccall(sym(mpc, :pg_get_safety_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                     mpc.handle, mpc.other_car_state, C_NULL, C_NULL, C_NULL), "pg_get_safety_state")
+    applied, _, _ = node_state(mpc)
+    mpc.current_state, mpc.current_control, mpc.other_car_state, applied
+end
+
+"Per controller: applied command [3, B], heartbeat (callbacks that computed), counts [4, B] (pre_flag off, outside the window, low speed, NaN fallback since the clock restarted)"
+function node_state(mpc::BatchedTrajectoryTrackingMPC)
+    applied = Matrix{Float64}(undef, 3, mpc.B); heartbeat = Vector{Int32}(undef, mpc.B); counts = Matrix{Int32}(undef, 4, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_node_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}), mpc.handle, applied, heartbeat, counts), "pg_get_node_state")
+    applied, heartbeat, counts
+end
+
 "Outcome of the active-set polish per instance: k >= 1 verified in round k (exact optimum on its active set), 0 not run, -1 not verified"
 function polish_info(mpc::BatchedTrajectoryTrackingMPC)
     p = Vector{Int32}(undef, mpc.B)

@@ -59,6 +59,13 @@ struct pg_handle {
     real *d_pol_u2 = nullptr, *d_pol_u = nullptr; int* d_pol_src = nullptr;   // HJI fallback policy (HJI_computation.jl:133-158)
     real* d_vmin = nullptr; int* d_breach = nullptr;          // summary of pg_simulate_safety_dev: V_min [cap]; first_breach [cap] then policy_steps [cap] (k_advance_safety)
     bool sum_fresh = true;                                    // the summary restarts at the next safety step (the clock restarted since it was last written)
+    // node callback (pg_node_step_dev / pg_simulate_node_dev), allocated at the first call of one of them: the keep buffer of gated-out instances' warm state (KeepView,
+    // pg_kernels.hip), d_node = gate [cap], heartbeat [cap], counts [cap][4], two cold words (k_node_finish -> k_nodes_recheck, used alternately: node_parity is the one the
+    // next recheck reads); the applied command [cap][3]; trajectory.t[end] per installed trajectory, fp64
+    char* d_keep = nullptr; KeepView kv{}; int* d_node = nullptr; real* d_applied = nullptr; double* d_tend = nullptr;
+    std::vector<double> traj_ends; bool tend_dirty = true;
+    int node_parity = 0; bool node_recheck = false;           // node_recheck: the last step was a node step (some instance may have no solution: launch_nodes queues k_nodes_recheck)
+    bool node_fresh = true;                                   // the node counts restart at the next node step (the clock restarted since they were last written)
     int *d_status = nullptr, *d_iters = nullptr, *d_polish = nullptr; uint16_t* d_active = nullptr;
     // HJI grid
     HjiView hv; float *d_knots = nullptr, *d_hnodes = nullptr, *d_hcells = nullptr; bool has_hji = false;
@@ -220,7 +227,7 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_ws4, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_ws4, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
@@ -536,6 +543,8 @@ static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_
     HIPCHK(h, hipMalloc((void**)&h->d_traj_len, (size_t)n_traj * sizeof(int)));
     HIPCHK(h, hipMemcpy(h->d_traj_len, L, (size_t)n_traj * sizeof(int), hipMemcpyHostToDevice));
     h->traj_t_end = channels[(size_t)L[0] - 1];          // trajectory.t[end] of trajectory 0 (channel 0 = t): the stop of pg_simulate_dev's clock range
+    h->traj_ends.assign((size_t)n_traj, 0.0); h->tend_dirty = true;      // ... and of every trajectory, fp64 (the window gate of the node callback)
+    for (int k = 0; k < n_traj; k++) h->traj_ends[(size_t)k] = channels[(size_t)k * stride + (size_t)L[k] - 1];
     TrajView& T = h->dc.traj; T.L = L[0];
     const real* p = h->d_traj; const size_t c = (size_t)Lmax;
     T.t = p; T.s = p + c; T.V = p + 2 * c; T.A = p + 3 * c; T.E = p + 4 * c; T.N = p + 5 * c; T.psi = p + 6 * c; T.kappa = p + 7 * c; T.edge_L = p + 8 * c; T.edge_R = p + 9 * c;
@@ -653,7 +662,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     int rc;
     if (host) {
@@ -737,6 +746,7 @@ static bool pipeline_applies(const pg_handle* h) {
 }
 static int launch_nodes(pg_handle* h, bool with_time_grid) {
     const int B = h->B;
+    const bool recheck = h->node_recheck && !h->sg.capturing; h->node_recheck = false;
     const bool pipelined = with_time_grid && pipeline_applies(h);
     h->lin_done = false;
     const size_t cap = (size_t)h->cfg.batch_capacity;
@@ -766,6 +776,16 @@ static int launch_nodes(pg_handle* h, bool with_time_grid) {
             const long nth = (long)B * h->dc.NN;
             hipLaunchKernelGGL(kern, dim3((unsigned)((nth + 255) / 256)), dim3(256), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_sep, h->d_ts, h->d_prev_ts, h->d_solx,
                                h->d_nodes, F);
+            if (recheck) {          // behind a node step: instances without a solution are known on the device only (k_nodes_recheck, predicated on the word k_node_finish filed)
+                LAUNCH_CHECK(h);
+                const int* cold = h->d_node + (size_t)6 * cap + h->node_parity;
+                const OrderOut Fr{h->d_status, h->d_iters, h->d_polish, nullptr, nullptr, nullptr};      // (the launch order stays as k_nodes_warm filed it)
+                auto rk = staged ? k_nodes_recheck<true> : k_nodes_recheck<false>;
+                hipLaunchKernelGGL(rk, dim3((B + NODES_IPB - 1) / NODES_IPB), block, traj_lds, h->stream, h->dc, B, cold, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep,
+                                   h->d_ts, h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, Fr, h->d_naux);
+                LAUNCH_CHECK(h);
+                hipLaunchKernelGGL(k_nodes_angles, dim3(64), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, cold);
+            }
         } else if (pipelined) {
             { int rc = launch_hji_rows_compute(h); if (rc) return rc; }      // (M, b) of the safety row: read by the lanes that linearise interval 0
             const int lpi = h->lin_lpi, ipb = 64 / lpi;
@@ -1155,7 +1175,7 @@ int pg_step_dev(pg_handle* h, void* u_out_dev) {
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true;
     }
     return PG_OK;
 }
@@ -1219,6 +1239,114 @@ int pg_get_safety_state(pg_handle* h, double* other_car, double* V_min, int32_t*
         (rc = down_raw(h, policy_steps, h->d_breach + h->cfg.batch_capacity, B * sizeof(int32_t)))) return rc;
     return PG_OK;
 }
+// ---- node callback (from_autobox_callback, ros_integration.jl:48-151) --------------------------------------------
+// first call: the keep buffer at batch capacity (one carve-up of one allocation), the node words, the applied command (zeroed: heartbeat and counts start at 0)
+static int node_prepare(pg_handle* h) {
+    const size_t cap = (size_t)h->cfg.batch_capacity; const int N = h->dc.N, NN = h->dc.NN;
+    const int naux_cap = h->dc.formulation == PG_DECOUPLED ? 64 * LAT_AUX : 0;
+    KeepView& K = h->kv;
+    if (!h->d_keep) {
+        const size_t dbl = cap * (size_t)(NN + N + NN), rl = cap * (size_t)(NN * 8 + N * 3 + N * 16 + 3 + 1 + naux_cap), it = cap * 5, u16 = cap * (size_t)N;
+        const size_t bytes = dbl * sizeof(double) + rl * sizeof(real) + it * sizeof(int) + u16 * sizeof(uint16_t);
+        HIPCHK(h, hipMalloc((void**)&h->d_keep, bytes));
+        char* p = h->d_keep;
+        auto take = [&](auto*& dst, size_t n) { dst = (std::remove_reference_t<decltype(dst)>)p; p += n * sizeof(*dst); };
+        take(K.k_ts, cap * NN); take(K.k_dt, cap * N); take(K.k_prev_ts, cap * NN);
+        take(K.k_solx, cap * NN * 8); take(K.k_sigma, cap * N * 3); take(K.k_lam, cap * N * 16); take(K.k_u, cap * 3); take(K.k_mu, cap); take(K.k_aux, cap * naux_cap);
+        take(K.k_solved, cap); take(K.k_wfail, cap); take(K.k_status, cap); take(K.k_iters, cap); take(K.k_polish, cap); take(K.k_active, cap * N);
+        HIPCHK(h, hipMalloc((void**)&h->d_node, (cap * 6 + 2) * sizeof(int)));
+        HIPCHK(h, hipMemset(h->d_node, 0, (cap * 6 + 2) * sizeof(int)));
+        HIPCHK(h, hipMalloc((void**)&h->d_applied, cap * 3 * sizeof(real)));
+        HIPCHK(h, hipMemset(h->d_applied, 0, cap * 3 * sizeof(real)));
+    }
+    if (h->tend_dirty) {
+        if (h->d_tend) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_tend); h->d_tend = nullptr; }
+        HIPCHK(h, hipMalloc((void**)&h->d_tend, h->traj_ends.size() * sizeof(double)));
+        HIPCHK(h, hipMemcpy(h->d_tend, h->traj_ends.data(), h->traj_ends.size() * sizeof(double), hipMemcpyHostToDevice));
+        h->tend_dirty = false;
+    }
+    // the live side (k_solve_lat's multiplier block exists while that kernel is the handle's solver: option "lateral_solver" may change it)
+    K.NN = NN; K.N = N; K.naux = (h->solve_lat && h->d_lat_aux) ? 64 * LAT_AUX : 0;
+    K.ts = h->d_ts; K.dt = h->d_dt; K.prev_ts = h->d_prev_ts; K.solx = h->d_solx; K.sigma = h->d_sigma; K.lam = h->d_lam; K.u = h->d_u; K.mu = h->d_mu; K.aux = h->d_lat_aux;
+    K.solved = h->d_solved; K.wfail = h->d_wfail; K.status = h->d_status; K.iters = h->d_iters; K.polish = h->d_polish; K.active = h->d_active;
+    return PG_OK;
+}
+static int node_gate(pg_handle* h, const uint8_t* pre_flag) {
+    const int B = h->B; const size_t cap = (size_t)h->cfg.batch_capacity;
+    hipLaunchKernelGGL(k_node_gate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, h->d_state, h->d_t0, h->d_toff, h->d_tend, pre_flag, h->d_node,
+                       h->d_node + 6 * cap + (h->node_parity ^ 1), h->kv);
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
+// the compute calls of the step, as pg_simulate_dev / pg_simulate_safety_dev make them (:94-112)
+static int node_compute(pg_handle* h) {
+    int rc;
+    if ((rc = launch_nodes(h, true)) || (rc = update_and_solve(h, nullptr))) return rc;
+    return PG_OK;
+}
+static NodeIO node_io(pg_handle* h) {
+    const size_t cap = (size_t)h->cfg.batch_capacity;
+    NodeIO io{};
+    io.gate = h->d_node; io.heartbeat = h->d_node + cap; io.counts = h->d_node + 2 * cap; io.cold = h->d_node + 6 * cap + (h->node_parity ^ 1); io.applied = h->d_applied; io.sep = h->d_sep;
+    return io;
+}
+static void node_done(pg_handle* h) { h->node_parity ^= 1; h->node_recheck = true; h->node_fresh = false; }
+
+int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_flag_dev, void* cmd_out_dev, void* se_out_dev, int32_t* event_dev) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_node_step_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
+    if ((rc = node_prepare(h)) || (rc = node_gate(h, pre_flag_dev)) || (rc = node_compute(h))) return rc;
+    NodeIO io = node_io(h);
+    io.cmd_out = (real*)cmd_out_dev; io.se_out = (real*)se_out_dev; io.event = event_dev;
+    const int B = h->B;
+    hipLaunchKernelGGL(k_node_finish<false>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, 0.0, (int)(use_hji_policy != 0), 0, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+                       (int)h->node_fresh, 0, 0, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, 0, h->kv, io);
+    LAUNCH_CHECK(h);
+    node_done(h);
+    return PG_OK;
+}
+// the node's closed loop: per step gate, the compute calls, then ONE launch for the restore, the selection, the fallback, the message, the records, both plants, the applied
+// command, the clock, the summary and the counts (k_node_finish<true>)
+int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev_, const uint8_t* pre_flag_dev,
+                         void* state_hist_dev_, void* applied_hist_dev_, int32_t* event_hist_dev, void* V_hist_dev_) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
+    REQUIRE(h, steps >= 1 && dt > 0.0, "pg_simulate_node_dev: steps >= 1 and dt > 0 required");
+    REQUIRE(h, human_mode >= 0 && human_mode <= 2, "pg_simulate_node_dev: human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
+    REQUIRE(h, human_mode != 2 || human_u_dev_, "pg_simulate_node_dev: human_mode 2 needs human_u_dev [steps][B][2]");
+    if ((rc = node_prepare(h))) return rc;
+    const int B = h->B; const size_t Bz = (size_t)B;
+    const real* human_u_dev = (const real*)human_u_dev_;
+    real *sh = (real*)state_hist_dev_, *ah = (real*)applied_hist_dev_, *vh = (real*)V_hist_dev_;
+    const bool restart = h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end;
+    if ((rc = clock_start(h, dt))) return rc;
+    if (restart) HIPCHK(h, hipMemcpyAsync(h->d_applied, h->d_control, Bz * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // the applied command starts as the message
+    const int has = (int)(h->has_hji && h->dc.formulation == PG_COUPLED);
+    for (int k = 0; k < steps; k++) {
+        if ((rc = node_gate(h, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr)) || (rc = node_compute(h))) return rc;
+        const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
+        h->sim_idx++;
+        NodeIO io = node_io(h);
+        io.human_u = human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr;
+        io.state_h = sh ? sh + (size_t)k * Bz * 6 : nullptr; io.applied_h = ah ? ah + (size_t)k * Bz * 3 : nullptr; io.V_h = vh ? vh + (size_t)k * Bz : nullptr;
+        io.event_h = event_hist_dev ? event_hist_dev + (size_t)k * Bz : nullptr;
+        io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
+        hipLaunchKernelGGL(k_node_finish<true>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, has,
+                           (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, h->kv, io);
+        LAUNCH_CHECK(h);
+        h->sum_fresh = false;
+        node_done(h);
+    }
+    return PG_OK;
+}
+int pg_get_node_state(pg_handle* h, double* applied, int32_t* heartbeat, int32_t* counts) {
+    int rc = check_ready(h); if (rc) return rc;
+    if ((rc = node_prepare(h))) return rc;
+    const size_t B = h->B, cap = (size_t)h->cfg.batch_capacity;
+    if ((rc = down(h, applied, h->d_applied, B * 3)) || (rc = down_raw(h, heartbeat, h->d_node + cap, B * sizeof(int32_t)))) return rc;
+    if (h->node_fresh) { if (counts) memset(counts, 0, B * 4 * sizeof(int32_t)); return PG_OK; }      // no node step since the clock (re)started
+    return down_raw(h, counts, h->d_node + 2 * cap, B * 4 * sizeof(int32_t));
+}
 int pg_simulate_clock(pg_handle* h, double dt, int32_t steps, int32_t B, const double* t_start, double* out) {
 #pragma clang fp contract(off)
     if (!h) return PG_ERR_INVALID;
@@ -1262,7 +1390,7 @@ static void stage_block(pg_handle* h, int32_t B, const double* s_, const double*
 static int step_by_graph(pg_handle* h, int32_t B, const double* state, const double* control, const double* t0, const double* other, const double* toff, bool* done) {
     *done = false;
     auto& G = h->sg;
-    if (!h->graph_mode || G.disabled || B != h->cfg.batch_capacity || B > 256 || h->B != B || h->warm_B < B || h->fuse != 0 || !h->d_traj) return PG_OK;
+    if (!h->graph_mode || G.disabled || B != h->cfg.batch_capacity || B > 256 || h->B != B || h->warm_B < B || h->fuse != 0 || !h->d_traj || h->node_recheck) return PG_OK;
     if (h->dc.n_traj > 1 && h->traj_idx_B < B) return PG_OK;
     if (hipSetDevice(h->cfg.device) != hipSuccess) return PG_OK;
     const bool same = G.x && G.B == B && G.user == h->stream && G.fuse == h->fuse && G.pipeline == h->pipeline && G.has_hji == (int)h->has_hji && G.traj_L == h->traj_L &&

@@ -1481,6 +1481,160 @@ __global__ __launch_bounds__(64) void k_advance_safety(DevCfg C, int B, tdouble 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Node callback (pg_node_step_dev / pg_simulate_node_dev): the per-message decision of from_autobox_callback (ros_integration.jl:48-151) for every instance of a batch.
+// The compute kernels of the step run unchanged on the whole batch; k_node_gate before them and k_node_finish after them make a gated-out instance behave as if it had
+// never been stepped: its WARM STATE -- what the next step reads before writing it -- is copied into a keep buffer before the step and back after it.
+// Gate codes (enum pg_node_event): 0 open, 4 pre_flag == 0 (:70-73), 5 trajectory mode and t0 outside [0, trajectory.t[end]] (:79-82), 6 Ux < 1 (:84-87), in that order.
+struct KeepView {
+    int NN, N, naux;                                                     // per-instance lengths; naux: k_solve_lat's multiplier block (64 x LAT_AUX, 0 without that kernel)
+    tdouble *ts, *dt, *prev_ts; real *solx, *sigma, *lam, *u, *mu, *aux; int *solved, *wfail, *status, *iters, *polish; uint16_t* active;
+    tdouble *k_ts, *k_dt, *k_prev_ts; real *k_solx, *k_sigma, *k_lam, *k_u, *k_mu, *k_aux; int *k_solved, *k_wfail, *k_status, *k_iters, *k_polish; uint16_t* k_active;
+};
+// one instance's warm state between the handle's buffers and the keep buffer, all 64 lanes of the wave together (lane-strided: coalesced)
+template <typename T> PG_DEV void keep_seg(T* live, T* keep, int b, int n, int lane, bool save) {
+    T* a = live + (size_t)b * n; T* k = keep + (size_t)b * n;
+    for (int i = lane; i < n; i += 64) { if (save) k[i] = a[i]; else a[i] = k[i]; }
+}
+PG_DEV void keep_move(const KeepView& K, int b, int lane, bool save) {
+    keep_seg(K.ts, K.k_ts, b, K.NN, lane, save); keep_seg(K.dt, K.k_dt, b, K.N, lane, save); keep_seg(K.prev_ts, K.k_prev_ts, b, K.NN, lane, save);
+    keep_seg(K.solx, K.k_solx, b, K.NN * 8, lane, save); keep_seg(K.sigma, K.k_sigma, b, K.N * 3, lane, save); keep_seg(K.lam, K.k_lam, b, K.N * 16, lane, save);
+    keep_seg(K.u, K.k_u, b, 3, lane, save); keep_seg(K.mu, K.k_mu, b, 1, lane, save); keep_seg(K.active, K.k_active, b, K.N, lane, save);
+    keep_seg(K.solved, K.k_solved, b, 1, lane, save); keep_seg(K.wfail, K.k_wfail, b, 1, lane, save); keep_seg(K.status, K.k_status, b, 1, lane, save);
+    keep_seg(K.iters, K.k_iters, b, 1, lane, save); keep_seg(K.polish, K.k_polish, b, 1, lane, save);
+    if (K.naux) keep_seg(K.aux, K.k_aux, b, K.naux, lane, save);
+}
+// the gates, lane = instance; then the wave copies the warm state of its gated-out instances (a wave without one is done after the decision).  Also zeroes the device
+// word the finish kernel of this step files its cold instances in (cold_next)
+__global__ __launch_bounds__(64) void k_node_gate(DevCfg C, int B, const real* __restrict__ state, const tdouble* __restrict__ t0, const tdouble* __restrict__ toff,
+                                                  const tdouble* __restrict__ t_end, const uint8_t* __restrict__ pre_flag, int* __restrict__ gate, int* __restrict__ cold_next, KeepView K) {
+    const int lane = (int)threadIdx.x, b = blockIdx.x * 64 + lane;
+    const bool valid = b < B;
+    int code = 0;
+    if (valid) {
+        const tdouble tm = toff[b], t = t0[b];
+        const tdouble tend = t_end[C.n_traj > 1 ? C.traj_idx[b] : 0];
+        if (pre_flag && pre_flag[b] == 0) code = 4;                                             // :70-73
+        else if (tm == tm && (t < tdouble(0.0) || t > tend)) code = 5;                          // :79-82 (trajectory mode only; both ends inside)
+        else if (state[(size_t)b * 6 + 3] < real(1.0)) code = 6;                                // :84-87 (the literal 1 m/s)
+        gate[b] = code;
+    }
+    if (blockIdx.x == 0 && lane == 0) *cold_next = 0;
+    unsigned long long m = __ballot(code != 0);
+    while (m) {
+        const int j = __ffsll((long long)m) - 1; m &= m - 1;
+        keep_move(K, blockIdx.x * 64 + j, lane, true);
+    }
+}
+// Everything after the step's compute calls, lane = instance:
+//   restore  the warm state of the gated-out instances of the wave (all lanes together, as k_node_gate saved it)
+//   select   (gated in) hji_source / hji_optimal_control / hji_policy_control as k_hji_policy and k_advance_safety (:114-124); no grid or no safety row: V = +Inf, MPC
+//   fallback (gated in) a NaN in any of the three components (:134-147): publish the message (the installed control), message <- 0, solved = wfail = 0 (as k_reset)
+//   message  control <- the published command (unchanged when gated out or after a fallback: 0); heartbeat + 1 when gated in (:112)
+//   PLANT    the records of the step; the ego plant with the APPLIED command of the step's start (advance_ego); applied <- the published command; the other car as
+//            k_advance_safety; the clock as k_advance; the safety summary (V every step, policy steps: published policy commands)
+// Counts [B][4]: steps with pre_flag off, outside the window, low speed, NaN fallback; restart_cnt starts them afresh, restart_sum the safety summary (PLANT).
+struct NodeIO {
+    const int* gate; real* cmd_out; real* se_out; int* event;            // [B] / [B][3] / [B][2] / [B]: outputs of the one-shot call, each may be nullptr
+    int* heartbeat; int* counts; int* cold; real* applied;               // [B] / [B][4] / 1 word: set when some instance leaves the step without a solution / [B][3]
+    const real* sep;                                                     // [B][4] the step's path coordinates
+    // PLANT only
+    const real* human_u; real *state_h, *applied_h, *V_h; int* event_h;  // script [B][2]; records [B][6] / [B][3] / [B] / [B], each may be nullptr
+    real* V_min; int* first_breach; int* policy_steps;                   // summary [B]
+};
+template <bool PLANT>
+__global__ __launch_bounds__(64) void k_node_finish(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart_cnt, int restart_sum, int step,
+                                                    real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                    const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, KeepView K, NodeIO io) {
+    const int lane = (int)threadIdx.x, b = blockIdx.x * 64 + lane;
+    const bool valid = b < B;
+    const int code = valid ? io.gate[b] : 0;
+    unsigned long long m = __ballot(code != 0);
+    while (m) {
+        const int j = __ffsll((long long)m) - 1; m &= m - 1;
+        keep_move(K, blockIdx.x * 64 + j, lane, false);
+    }
+    bool cold = false;
+    if (valid) {
+        const DevVehicle& P = C.veh;
+        real* u = control + (size_t)b * 3;
+        const real msg0 = u[0], msg1 = u[1], msg2 = u[2];                // current_control: the message last published (:52)
+        const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);  // looked up before any gate (:55-57)
+        int ev = code, src = 0;
+        bool pub = false;
+        real p0 = msg0, p1 = msg1, p2 = msg2;                             // the published command
+        if (code == 0) {
+            src = has_hji ? hji_source(C, use_policy, V, toff[b]) : 0;
+            real n0 = u_mpc[(size_t)b * 3], n1 = u_mpc[(size_t)b * 3 + 1], n2 = u_mpc[(size_t)b * 3 + 2];
+            if (src == 1) {
+                real d_opt, Fx_opt;
+                hji_optimal_control(P, x7 + (size_t)b * 7, vg8 + (size_t)b * 8 + 1, d_opt, Fx_opt);
+                hji_policy_control(P, d_opt, Fx_opt, n0, n1, n2);
+            }
+            pub = true;
+            if (n0 != n0 || n1 != n1 || n2 != n2) {                       // :134-147
+                ev = 3; cold = true;
+                u[0] = real(0.0); u[1] = real(0.0); u[2] = real(0.0);
+                K.solved[b] = 0; K.wfail[b] = 0;
+            } else {
+                ev = src;
+                p0 = n0; p1 = n1; p2 = n2;
+                u[0] = n0; u[1] = n1; u[2] = n2;
+            }
+            io.heartbeat[b] += 1;
+        } else cold = K.k_solved[b] == 0;
+        if (io.cmd_out && pub) { io.cmd_out[(size_t)b * 3] = p0; io.cmd_out[(size_t)b * 3 + 1] = p1; io.cmd_out[(size_t)b * 3 + 2] = p2; }
+        if (io.se_out) { io.se_out[(size_t)b * 2] = io.sep[(size_t)b * 4]; io.se_out[(size_t)b * 2 + 1] = io.sep[(size_t)b * 4 + 1]; }
+        if (io.event) io.event[b] = ev;
+        int* cn = io.counts + (size_t)b * 4;
+        int c4[4] = {restart_cnt ? 0 : cn[0], restart_cnt ? 0 : cn[1], restart_cnt ? 0 : cn[2], restart_cnt ? 0 : cn[3]};
+        if (ev >= 4) c4[ev - 4]++;
+        if (ev == 3) c4[3]++;
+        cn[0] = c4[0]; cn[1] = c4[1]; cn[2] = c4[2]; cn[3] = c4[3];
+        if constexpr (PLANT) {
+            real* q = state + (size_t)b * 6; real* ap = io.applied + (size_t)b * 3; real* ot = other + (size_t)b * 4;
+            real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+            real ac[3] = {ap[0], ap[1], ap[2]};
+            real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
+            if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
+            if (io.applied_h) for (int k = 0; k < 3; k++) io.applied_h[(size_t)b * 3 + k] = ac[k];
+            if (io.V_h) io.V_h[b] = V;
+            if (io.event_h) io.event_h[b] = ev;
+            real w = real(0.0), a = real(0.0);
+            if (human_mode == 1 && has_hji) {
+                const real* xr = x7 + (size_t)b * 7;
+                if (xr[5] > real(0.0)) optimal_disturbance(P, xr, vg8 + (size_t)b * 8 + 1, w, a);
+            } else if (human_mode == 2) {
+                w = io.human_u[(size_t)b * 2]; a = io.human_u[(size_t)b * 2 + 1];
+            }
+            const int nsub = C.nsub; const real h = dtp / nsub;
+            advance_ego(C, x, ac[0], ac[1] + ac[2], h, nsub);            // the command applied at the step's start (one-step delay, as k_advance)
+            advance_unicycle(oc, w, a, h, nsub);
+            for (int k = 0; k < 6; k++) q[k] = x[k];
+            for (int k = 0; k < 4; k++) ot[k] = oc[k];
+            if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
+            t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
+            real vmin = restart_sum ? real(INFINITY) : io.V_min[b];
+            int fb = restart_sum ? -1 : io.first_breach[b], ps = restart_sum ? 0 : io.policy_steps[b];
+            if (V < vmin) vmin = V;
+            if (fb < 0 && V <= real(0.0)) fb = step;
+            if (ev == 1) ps++;
+            io.V_min[b] = vmin; io.first_breach[b] = fb; io.policy_steps[b] = ps;
+        }
+    }
+    if (__ballot(cold) != 0ull && lane == 0) atomicOr(io.cold, 1);
+}
+// the warm-branch nodes kernel (k_nodes_warm) serves a batch the host knows to be all warm; after a node step some instances may have no solution (gated out before
+// their first solve, or reset by the NaN fallback), which only the device knows.  Queued behind k_nodes_warm and predicated on the word k_node_finish filed: when set,
+// the nodes of the whole batch again through the per-instance branch of k_nodes (bit-identical for the warm instances); the deferred angles follow (k_nodes_angles, same word)
+template <bool STAGED> __global__ __launch_bounds__(64) void k_nodes_recheck(DevCfg C, int B, const int* __restrict__ cold, const real* __restrict__ state, const real* __restrict__ control,
+                        const tdouble* __restrict__ toff, const int* __restrict__ solved, const real* __restrict__ sep, const tdouble* __restrict__ ts, const tdouble* __restrict__ dt,
+                        const tdouble* __restrict__ prev_ts, const real* __restrict__ prev_x, real* __restrict__ nodes, OrderOut F, real* __restrict__ naux) {
+    if (*cold == 0) return;
+    nodes_body<STAGED, false>(C, B, (int)blockIdx.x, state, control, toff, solved, sep, ts, dt, prev_ts, prev_x, nodes, F, naux, nullptr, 0ull);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // QP solve: one wavefront per instance.  See tools/ipm_prototype.py for the algorithm statement and DESIGN.md for the derivation.
 // State x_k = (q_k, u_k) in R^8, input v_k = u_{k+1} - u_k; 16 inequality rows per transition k (node k+1):
 //   0: Ux >= V_min   1: Ux <= V_max   2: Fx >= Fx_min   3: delta <= dmax   4: delta >= dmin   5: Fx <= fxmax

@@ -288,6 +288,71 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_safety_state(self.h, None, _p(vmin), _p(fb, C.POINTER(C.c_int32)), _p(ps, C.POINTER(C.c_int32))), "pg_get_safety_state")
         return vmin, fb, ps
 
+    # ---- from_autobox_callback (ros_integration.jl:48-151) for every instance: pg_node_step_dev / pg_simulate_node_dev ----
+    NODE_EVENTS = {"mpc": 0, "hji_policy": 1, "feather": 2, "nan_fallback": 3, "pre_flag_off": 4, "outside_trajectory": 5, "low_speed": 6}
+
+    def _pre_flag_dev(self, pre_flag, shape):
+        import torch
+        if pre_flag is None:
+            return None
+        return torch.as_tensor(np.ascontiguousarray(pre_flag, dtype=np.uint8).reshape(shape)).to(device=f"cuda:{self.cfg.device}").contiguous()
+
+    def node_step_(self, use_HJI_policy=False, pre_flag=None):
+        """One node callback per instance on the installed inputs (pg_node_step_dev): the installed control is the to_autobox message.  pre_flag [B] (None: engaged).
+        Returns (cmd [B][3], se [B][2], event [B], message [B][3]): the published command (NaN where nothing was published), (s, e) of the step's projection, the
+        pg_node_event code, and the message after the callback (the installed control now).  The clock does not advance."""
+        import ctypes as C_
+        import torch
+        dev = f"cuda:{self.cfg.device}"
+        tdt = torch.float32 if self.precision == "f32" else torch.float64
+        cmd = torch.full((self.B, 3), float("nan"), dtype=tdt, device=dev); se = torch.empty((self.B, 2), dtype=tdt, device=dev)
+        ev = torch.empty(self.B, dtype=torch.int32, device=dev)
+        pf = self._pre_flag_dev(pre_flag, (self.B,))
+        ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.pg_node_step_dev(self.h, int(bool(use_HJI_policy)), ptr(pf), ptr(cmd), ptr(se), ptr(ev)), "pg_node_step_dev")
+        c = np.zeros((self.B, 3))
+        self._chk(self.lib.pg_get_state(self.h, None, _p(c), None), "pg_get_state")
+        return cmd.cpu().numpy().astype(np.float64), se.cpu().numpy().astype(np.float64), ev.cpu().numpy(), c
+
+    def simulate_node_(self, steps, dt=0.01, use_HJI_policy=False, human="hold", human_u=None, pre_flag=None, record=False):
+        """The node's closed loop (pg_simulate_node_dev): per step the gates, the compute calls, the callback's decision (NaN fallback included), the ego plant driven by the
+        APPLIED command of the step's start, the other car as simulate_safety_.  pre_flag [steps][B] (None: engaged).  Returns (state, message, t, other, applied) after `steps`
+        steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event)."""
+        import ctypes as C_
+        import torch
+        assert human in self.HUMAN_MODES, human
+        dev = f"cuda:{self.cfg.device}"
+        tdt = torch.float32 if self.precision == "f32" else torch.float64
+        hu = None
+        if human == "script":
+            if human_u is None:
+                raise ValueError('human="script" needs human_u [steps][B][2]')
+            hu = torch.as_tensor(np.ascontiguousarray(human_u, dtype=np.float64).reshape(steps, self.B, 2)).to(device=dev, dtype=tdt).contiguous()
+        pf = self._pre_flag_dev(pre_flag, (steps, self.B))
+        shapes = {"state": (6,), "applied": (3,), "V": ()}
+        hist = {k: torch.empty((steps, self.B) + s, dtype=tdt, device=dev) for k, s in shapes.items()} if record else {}
+        if record:
+            hist["event"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
+        ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C_.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),
+                                                *(ptr(hist.get(k)) for k in ("state", "applied", "event", "V"))), "pg_simulate_node_dev")
+        s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4)); a = np.zeros((self.B, 3))
+        self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
+        self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
+        self._chk(self.lib.pg_get_node_state(self.h, _p(a), None, None), "pg_get_node_state")
+        if not record:
+            return s, c, t, o, a
+        out = {k: v.cpu().numpy() for k, v in hist.items()}
+        for k in shapes:
+            out[k] = out[k].astype(np.float64)
+        return s, c, t, o, a, out
+
+    def node_summary(self):
+        """(applied [B][3], heartbeat [B], counts [B][4] = steps with pre_flag off / outside the window / low speed / NaN fallback since the clock last restarted)."""
+        a = np.zeros((self.B, 3)); hb = np.zeros(self.B, dtype=np.int32); cn = np.zeros((self.B, 4), dtype=np.int32)
+        self._chk(self.lib.pg_get_node_state(self.h, _p(a), _p(hb, C.POINTER(C.c_int32)), _p(cn, C.POINTER(C.c_int32))), "pg_get_node_state")
+        return a, hb, cn
+
     def simulate_clock(self, steps, t_start, dt=0.01):
         """The times the rollout's loop variable takes, per instance: (t_start .+ (0:dt:trajectory.t[end]))[1:steps] as Julia's range arithmetic gives them
         (model_predictive_control.jl:87; pg_simulate_clock) -- [steps][B]."""
