@@ -10,8 +10,9 @@
  *   get_next_control(mpc)                src/model_predictive_control.jl:78   (-> src/coupled_lat_long.jl:370-374)
  * called from src/ros_integration.jl:96-99,124 and src/model_predictive_control.jl:90-95.  Each entry point below names
  * the reference interface it replaces.  A batch of B independent MPC instances shares one handle (one vehicle, one
- * set of control parameters, one reference trajectory, one HJI grid); per-instance persistent state (solved flag,
- * previous time grid, previous primal solution) lives in device memory inside the handle.
+ * HJI grid; one reference trajectory or a library of them with a per-instance selection, pg_set_trajectories; one set
+ * of control parameters or a library of sets with a per-instance selection, pg_set_control_param_sets); per-instance
+ * persistent state (solved flag, previous time grid, previous primal solution) lives in device memory inside the handle.
  *
  * Conventions: every function returns 0 on success or a negative pg_status; no exceptions cross the ABI; all
  * arrays are instance-major ("array of structs": state[b*6 + k]) in double precision; pointers are HOST pointers
@@ -162,6 +163,29 @@ int pg_set_trajectories(pg_handle* h, int32_t n_traj, int32_t Lmax, const int32_
  * With n_traj > 1 the phase calls return PG_ERR_STATE until an index covering the current batch is installed. */
 int pg_set_trajectory_index(pg_handle* h, int32_t B, const int32_t* index);
 
+/* control_params of one controller per instance (src/coupled_lat_long.jl:42-60, src/decoupled_lat_long.jl:32-50): a library of control-parameter sets and a per-instance
+ * selection, the counterpart of pg_set_trajectories / pg_set_trajectory_index for the controller's tuning -- a tuning sweep or robustness study (the same starts and paths
+ * under many weightings, speed bounds and steering-rate limits) runs as ONE batch.  With no library the handle behaves as pg_config.control says.  A library of ONE set
+ * applies to every instance without an index (a handle is retuned this way without being recreated).  With n_sets > 1 the phase calls, pg_step*, pg_simulate*_dev and
+ * pg_node_step_dev return PG_ERR_STATE until an index covering the current batch is installed.  Library and index persist until replaced; installing a library drops the
+ * previous index.  An instance whose effective set changes (compared field by field) -- through a new library, a new index entry or pg_clear_control_param_sets -- is reset
+ * as pg_reset does it (its warm start belonged to another QP); the others keep their solver state.  A rejected call (PG_ERR_INVALID) leaves the handle unchanged; a call
+ * that fails with PG_ERR_HIP may have installed its library or index with the resets still owed -- pg_reset(h, NULL) settles that.  pg_get_config keeps
+ * returning the creation-time config.  PG_ERR_INVALID: n_sets < 1; a set with a non-finite field, V_min >= V_max, deltadot_max <= 0, a negative weight (Q_*, W_*, R_*),
+ * R_ddelta <= 0 or (coupled handle) R_dFx <= 0 -- the two rate weights make the optimum unique; pg_create does not validate pg_config.control and that stays so --; a set
+ * whose N_HJI differs from the handle's (N_HJI decides which rows exist: structure, not tuning); an index entry outside [0, n_sets); B outside [1, batch_capacity].  Every
+ * other field may differ between sets, W_HJI included; a decoupled handle uses the subset of fields listed at pg_default_config_decoupled.
+ * Cost with n_sets > 1: a kernel keeps the address of its instance's record and loads each parameter where it uses it (scalar loads where a wavefront serves one instance,
+ * per-lane loads elsewhere); the pipelined nodes + update_QP launch (pg_set_pipeline) is followed by one more small launch that rewrites the 2 B N steering-rate bounds of
+ * the QP data per instance.  With no library or a library of one nothing is loaded: the set is a launch argument, as pg_config.control is.  The lateral solver keeps its
+ * arrangement (four instances per wavefront) under a library. */
+int pg_set_control_param_sets(pg_handle* h, int32_t n_sets, const pg_control_params* sets);
+int pg_set_control_param_index(pg_handle* h, int32_t B, const int32_t* index);   /* index[b] in [0, n_sets) */
+int pg_clear_control_param_sets(pg_handle* h);                                    /* back to pg_config.control */
+/* the installed library: *n_sets = its size (0: none); out[0 .. min(n_sets, max_sets)) the sets as installed; index[0 .. B) the installed selection, -1 for instances the
+ * index does not cover.  n_sets, out and index may each be NULL. */
+int pg_get_control_param_sets(pg_handle* h, int32_t* n_sets, pg_control_params* out, int32_t max_sets, int32_t* index, int32_t B);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -198,7 +222,7 @@ int pg_get_next_control_hji_dev(pg_handle* h, int32_t use_hji_policy, pg_real_de
 /* all five for every instance: host buffers in, host buffers out (status/iters may be NULL).
  * A batch that fills the handle (B == batch_capacity) travels in one copy per direction.  Opt-in (pg_set_option "graph" = 1): when such a batch has at most 256
  * instances and every one of them is warm, the whole step -- copy in, the kernels of a warm step, copy out -- is captured once into a hipGraph and replayed
- * (re-captured whenever something its launches depend on has changed; results identical to the ordinary launches; pg_get_phase_ms has no timing for replayed
+ * (re-captured whenever something its launches depend on has changed, a control-parameter library or index among them; results identical to the ordinary launches; pg_get_phase_ms has no timing for replayed
  * steps; with no stream installed the graph runs on a blocking stream of its own, ordered against the null stream).  Measured: 2-7 % per step, against ~7 ms for
  * every capture -- worth it for a long run on one path, not for a loop that re-installs its path every few steps; hence off by default. */
 int pg_step(pg_handle* h, int32_t B, const double* state, const double* control, const double* t0, const double* other_car,

@@ -156,6 +156,24 @@ function set_trajectories!(mpc::BatchedTrajectoryTrackingMPC, tubes::Vector{Traj
     check(mpc, ccall(sym(mpc, :pg_set_trajectory_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_trajectory_index")
 end
 
+"One controller per (x0, control_params) pair (src/coupled_lat_long.jl:42-60, src/decoupled_lat_long.jl:32-50): a library of parameter sets in the ABI's layout and the set each instance runs under (0-based index; may be empty for a library of one)"
+function set_control_params!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgControlParams}, index::Vector{Int32}=Int32[])
+    check(mpc, ccall(sym(mpc, :pg_set_control_param_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgControlParams}), mpc.handle, length(sets), sets), "pg_set_control_param_sets")
+    isempty(index) || set_control_param_index!(mpc, index)
+end
+set_control_param_index!(mpc::BatchedTrajectoryTrackingMPC, index::Vector{Int32}) =
+    check(mpc, ccall(sym(mpc, :pg_set_control_param_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_control_param_index")
+"back to the control_params the controller was constructed with"
+clear_control_params!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_control_param_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_control_param_sets")
+"(sets, index over the first B instances; -1 where no index covers an instance) as installed"
+function control_param_sets(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_control_param_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgControlParams}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_control_param_sets")
+    sets = Vector{PgControlParams}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_control_param_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgControlParams}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_control_param_sets")
+    sets, index
+end
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

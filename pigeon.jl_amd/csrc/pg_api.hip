@@ -2,6 +2,7 @@
 // The product path has NO CPU fallback: without a HIP device pg_create fails with PG_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +35,10 @@ struct pg_handle {
     std::string err;
     // device buffers
     real *d_traj = nullptr; int traj_L = 0; int *d_traj_len = nullptr, *d_traj_idx = nullptr; int traj_idx_B = 0;
+    // control-parameter library (pg_set_control_param_sets / pg_set_control_param_index): the device records and index DevCfg points to, the sets and index as the caller
+    // installed them (pg_get_control_param_sets), and the set every instance currently runs under (cp_eff, [capacity]: an instance whose entry changes is reset)
+    DevControlRec* d_cp_sets = nullptr; int* d_cp_idx = nullptr; int cp_idx_B = 0;
+    std::vector<pg_control_params> cp_sets, cp_eff; std::vector<int32_t> cp_index;
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -134,16 +139,28 @@ static int down_raw(pg_handle* h, void* dst, const void* src, size_t bytes) {   
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PG_OK;
 }
+static void fill_dev_control(DevControl& U, const pg_control_params& u);
 static void fill_dev_params(DevCfg& C, const pg_config* cfg) {
     const pg_vehicle& v = cfg->vehicle; DevVehicle& V = C.veh;
     V.G = (real)v.G; V.m = (real)v.m; V.Izz = (real)v.Izz; V.L = (real)v.L; V.a = (real)v.a; V.b = (real)v.b; V.h = (real)v.h; V.mu = (real)v.mu;
     V.Caf = (real)v.Caf; V.Car = (real)v.Car; V.Cd0 = (real)v.Cd0; V.Cd1 = (real)v.Cd1; V.Cd2 = (real)v.Cd2;
     V.fwd_frac = (real)v.fwd_frac; V.rwd_frac = (real)v.rwd_frac; V.fwb_frac = (real)v.fwb_frac; V.rwb_frac = (real)v.rwb_frac;
     V.Fx_max = (real)v.Fx_max; V.Fx_min = (real)v.Fx_min; V.Px_max = (real)v.Px_max; V.delta_max = (real)v.delta_max; V.kappa_max = (real)v.kappa_max;
-    const pg_control_params& u = cfg->control; DevControl& U = C.cp;
+    fill_dev_control(C.cp, cfg->control);
+}
+static void fill_dev_control(DevControl& U, const pg_control_params& u) {
     U.V_min = (real)u.V_min; U.V_max = (real)u.V_max; U.k_V = (real)u.k_V; U.k_s = (real)u.k_s; U.deltadot_max = (real)u.deltadot_max;
     U.Q_ds = (real)u.Q_ds; U.Q_dpsi = (real)u.Q_dpsi; U.Q_e = (real)u.Q_e; U.W_beta = (real)u.W_beta; U.W_r = (real)u.W_r; U.W_HJI = (real)u.W_HJI;
     U.R_delta = (real)u.R_delta; U.R_ddelta = (real)u.R_ddelta; U.R_Fx = (real)u.R_Fx; U.R_dFx = (real)u.R_dFx; U.N_HJI = u.N_HJI;
+}
+
+// One set of control parameters as the kernels read it, with what is derived from it: the inert slots of the embedded lateral problem pinned (decoupled formulation), and
+// the value of its inert Ux slot, strictly inside [V_min, V_max] of THIS set.  pg_create makes the uniform set of the handle with it, the library every one of its sets.
+static DevControlRec make_control_rec(int formulation, const pg_control_params& u) {
+    DevControlRec r; fill_dev_control(r.cp, u);
+    r.ux_dummy = (real)(0.5 * (u.V_min + u.V_max));
+    if (formulation == PG_DECOUPLED) { r.cp.Q_ds = 0.0; r.cp.R_Fx = 0.0; r.cp.R_dFx = 1.0; r.cp.N_HJI = 0; r.cp.W_HJI = 0.0; }
+    return r;
 }
 
 // Lateral formulation: which kernel solves it, and the buffers that kernel needs.  Called by pg_create and by pg_set_option("lateral_solver" / "lat_workspace").
@@ -226,7 +243,7 @@ int pg_default_config_decoupled(pg_config* c) {
 }
 
 static void free_all(pg_handle* h) {
-    void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
+    void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_cp_sets, h->d_cp_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
                     h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_ws4, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
@@ -268,12 +285,12 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
     C.tg_short = jl_scalar_times_unitrange(cfg->dt_short, 0, cfg->N_short); C.tg_long = jl_scalar_times_unitrange(cfg->dt_long, 1, cfg->N_long); C.time_grid_naive = 0;
     C.un0 = (real)cfg->vehicle.delta_max; C.un1 = (real)fmax(-cfg->vehicle.Fx_min, cfg->vehicle.Fx_max);      // coupled_lat_long.jl:199
     C.fxmin_n = (real)(cfg->vehicle.Fx_min / fmax(-cfg->vehicle.Fx_min, cfg->vehicle.Fx_max));
-    C.formulation = cfg->formulation; C.ux_dummy = (real)(0.5 * (cfg->control.V_min + cfg->control.V_max));
+    C.formulation = cfg->formulation;
+    C.cp_sets = nullptr; C.cp_idx = nullptr; C.n_cp = 0; C.cp_epoch = 0;      // no control-parameter library: every kernel reads C.cp / C.ux_dummy
     C.dbg_poison = 0; C.dbg_instance = -1;                              // (-DPG_DIAG builds: option "diag_instance")
-    if (cfg->formulation == PG_DECOUPLED) {          // no u normalisation in the lateral QP (decoupled_lat_long.jl:134-226); inert slots pinned
-        C.un0 = 1.0; C.un1 = 1.0; C.fxmin_n = -1.0;
-        C.cp.Q_ds = 0.0; C.cp.R_Fx = 0.0; C.cp.R_dFx = 1.0; C.cp.N_HJI = 0; C.cp.W_HJI = 0.0;
-    }
+    if (cfg->formulation == PG_DECOUPLED) { C.un0 = 1.0; C.un1 = 1.0; C.fxmin_n = -1.0; }          // no u normalisation in the lateral QP (decoupled_lat_long.jl:134-226)
+    { const DevControlRec r = make_control_rec(cfg->formulation, cfg->control); C.cp = r.cp; C.ux_dummy = r.ux_dummy; }
+    h->cp_eff.assign((size_t)cfg->batch_capacity, cfg->control);
     C.qp_len = 84 * C.N + 11;
     C.ipm_max_iter = cfg->ipm_max_iter; C.ipm_tol = (real)cfg->ipm_tol; C.ipm_mu0 = (real)cfg->ipm_mu0;
     C.polish = cfg->polish != 0; C.polish_rho = (real)cfg->polish_rho; C.polish_tol = (real)cfg->polish_tol; C.polish_ipm_tol = (real)cfg->polish_ipm_tol; C.warm_polish = cfg->warm_polish != 0; C.cold_guess = cfg->cold_guess > 0 ? cfg->cold_guess : 0;
@@ -586,6 +603,101 @@ int pg_set_trajectory_index(pg_handle* h, int32_t B, const int32_t* index) {
     return PG_OK;
 }
 
+__global__ void k_reset(int B, const uint8_t* mask, int* solved, int* wfail) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B && (!mask || mask[b])) { solved[b] = 0; wfail[b] = 0; }
+}
+
+// ---- control-parameter library: control_params of one controller per instance (coupled_lat_long.jl:42-60, decoupled_lat_long.jl:32-50) ----
+static const char* control_set_problem(const pg_handle* h, const pg_control_params& u) {
+    const double f[15] = {u.V_min, u.V_max, u.k_V, u.k_s, u.deltadot_max, u.Q_ds, u.Q_dpsi, u.Q_e, u.W_beta, u.W_r, u.W_HJI, u.R_delta, u.R_ddelta, u.R_Fx, u.R_dFx};
+    for (double v : f) if (!std::isfinite(v)) return "a set has a non-finite field";
+    if (!(u.V_min < u.V_max)) return "a set needs V_min < V_max";
+    if (!(u.deltadot_max > 0.0)) return "a set needs deltadot_max > 0";
+    for (int i = 5; i < 15; i++) if (f[i] < 0.0) return "a set has a negative weight";
+    if (!(u.R_ddelta > 0.0)) return "a set needs R_ddelta > 0 (the rate weights make the optimum unique)";
+    if (h->cfg.formulation == PG_COUPLED && !(u.R_dFx > 0.0)) return "a set of a coupled handle needs R_dFx > 0 (the rate weights make the optimum unique)";
+    if (u.N_HJI != h->cfg.control.N_HJI) return "N_HJI of a set differs from the handle's (it decides which rows exist: structure, not tuning)";
+    return nullptr;
+}
+static bool same_control(const pg_control_params& a, const pg_control_params& b) {
+    return a.V_min == b.V_min && a.V_max == b.V_max && a.k_V == b.k_V && a.k_s == b.k_s && a.deltadot_max == b.deltadot_max && a.Q_ds == b.Q_ds && a.Q_dpsi == b.Q_dpsi && a.Q_e == b.Q_e &&
+           a.W_beta == b.W_beta && a.W_r == b.W_r && a.W_HJI == b.W_HJI && a.R_delta == b.R_delta && a.R_ddelta == b.R_ddelta && a.R_Fx == b.R_Fx && a.R_dFx == b.R_dFx && a.N_HJI == b.N_HJI;
+}
+// instances [0, n) now run under eff(b): those whose set changed start cold, as pg_reset leaves them (their warm start belonged to another QP); the others keep their state
+// (eff(b): the one set `single`, or set index[b] of the installed library)
+static int control_sets_changed(pg_handle* h, int n, const pg_control_params* single, const int32_t* index) {
+    auto eff = [&](int b) -> const pg_control_params& { return index ? h->cp_sets[(size_t)index[b]] : *single; };
+    std::vector<uint8_t> mask((size_t)n, 0); bool any = false;
+    for (int b = 0; b < n; b++) if (!same_control(eff(b), h->cp_eff[(size_t)b])) { mask[(size_t)b] = 1; any = true; }
+    h->dc.cp_epoch++;                                          // (the captured step compares DevCfg: re-captured)
+    if (!any) return PG_OK;
+    h->warm_B = 0; h->order_B = 0;
+    HIPCHK(h, hipMemcpyAsync(h->d_mask, mask.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_reset, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->d_mask, h->d_solved, h->d_wfail);
+    LAUNCH_CHECK(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int b = 0; b < n; b++) if (mask[(size_t)b]) h->cp_eff[(size_t)b] = eff(b);      // (only now: a failed reset leaves the instances marked as running under their old set, and the next install resets them)
+    return PG_OK;
+}
+int pg_set_control_param_sets(pg_handle* h, int32_t n_sets, const pg_control_params* sets) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, n_sets >= 1 && sets, "pg_set_control_param_sets: need n_sets >= 1 and the sets");
+    for (int k = 0; k < n_sets; k++) { const char* why = control_set_problem(h, sets[k]); REQUIRE(h, !why, std::string("pg_set_control_param_sets: ") + why); }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    DevControlRec* d_new = nullptr;
+    if (n_sets > 1) {
+        std::vector<DevControlRec> recs((size_t)n_sets);
+        for (int k = 0; k < n_sets; k++) recs[(size_t)k] = make_control_rec(h->cfg.formulation, sets[k]);
+        HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(DevControlRec)));
+        if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(DevControlRec), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = "pg_set_control_param_sets: copy failed"; return PG_ERR_HIP; }
+    }
+    if (h->d_cp_sets) (void)hipFree(h->d_cp_sets);
+    h->d_cp_sets = d_new; h->cp_sets.assign(sets, sets + n_sets);
+    h->cp_index.clear(); h->cp_idx_B = 0;                       // installing a library drops the previous index
+    DevCfg& C = h->dc; C.n_cp = n_sets; C.cp_sets = d_new; C.cp_idx = nullptr;
+    if (n_sets > 1) { C.cp_epoch++; return PG_OK; }            // (which instance runs under which set is known once the index arrives)
+    // a library of one: the set becomes the uniform set of the handle -- every kernel reads it as the launch argument
+    { const DevControlRec r = make_control_rec(h->cfg.formulation, sets[0]); C.cp = r.cp; C.ux_dummy = r.ux_dummy; }
+    return control_sets_changed(h, h->cfg.batch_capacity, &h->cp_sets[0], nullptr);
+}
+int pg_set_control_param_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, h->dc.n_cp >= 1, "pg_set_control_param_index: no control-parameter library installed");
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_control_param_index: need 1 <= B <= batch_capacity and an index array");
+    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < h->dc.n_cp, "pg_set_control_param_index: index out of range of the installed library");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!h->d_cp_idx) {
+        HIPCHK(h, hipMalloc((void**)&h->d_cp_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
+        HIPCHK(h, hipMemset(h->d_cp_idx, 0, (size_t)h->cfg.batch_capacity * sizeof(int)));      // (entries beyond the indexed batch select set 0: never an address outside the library)
+    }
+    HIPCHK(h, hipMemcpy(h->d_cp_idx, index, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    h->cp_index.assign(index, index + B); h->cp_idx_B = B;
+    if (h->dc.n_cp > 1) h->dc.cp_idx = h->d_cp_idx;            // (a library of one needs no index: every entry is 0)
+    return control_sets_changed(h, B, nullptr, index);
+}
+int pg_clear_control_param_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_cp_sets) { (void)hipFree(h->d_cp_sets); h->d_cp_sets = nullptr; }
+    h->cp_sets.clear(); h->cp_index.clear(); h->cp_idx_B = 0;
+    DevCfg& C = h->dc; C.n_cp = 0; C.cp_sets = nullptr; C.cp_idx = nullptr;
+    { const DevControlRec r = make_control_rec(h->cfg.formulation, h->cfg.control); C.cp = r.cp; C.ux_dummy = r.ux_dummy; }
+    return control_sets_changed(h, h->cfg.batch_capacity, &h->cfg.control, nullptr);
+}
+int pg_get_control_param_sets(pg_handle* h, int32_t* n_sets, pg_control_params* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), "pg_get_control_param_sets: need max_sets >= 0 and 0 <= B <= batch_capacity");
+    const int n = (int)h->cp_sets.size();
+    if (n_sets) *n_sets = n;
+    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = h->cp_sets[(size_t)k];
+    if (index) for (int b = 0; b < B; b++) index[b] = b < h->cp_idx_B ? h->cp_index[(size_t)b] : -1;
+    return PG_OK;
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -635,11 +747,6 @@ int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_conc
     (void)hipFree(h->d_hnodes); h->d_hnodes = nullptr; h->hv.nodes = nullptr;
     h->has_hji = true; h->dc.has_hji = 1;
     return PG_OK;
-}
-
-__global__ void k_reset(int B, const uint8_t* mask, int* solved, int* wfail) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B && (!mask || mask[b])) { solved[b] = 0; wfail[b] = 0; }
 }
 
 int pg_reset(pg_handle* h, const uint8_t* mask) {
@@ -714,6 +821,7 @@ static int check_ready(pg_handle* h) {
     if (h->B <= 0) { h->err = "no inputs installed (call pg_set_inputs first)"; return PG_ERR_STATE; }
     if (!h->d_traj) { h->err = "no trajectory installed (call pg_set_trajectory first)"; return PG_ERR_STATE; }
     if (h->dc.n_traj > 1 && h->traj_idx_B < h->B) { h->err = "a trajectory library is installed but pg_set_trajectory_index does not cover the batch"; return PG_ERR_STATE; }
+    if (h->dc.n_cp > 1 && h->cp_idx_B < h->B) { h->err = "a control-parameter library is installed but pg_set_control_param_index does not cover the batch"; return PG_ERR_STATE; }
     if (hipSetDevice(h->cfg.device) != hipSuccess) { h->err = "hipSetDevice failed"; return PG_ERR_HIP; }
     return PG_OK;
 }
@@ -820,6 +928,13 @@ static int launch_nodes(pg_handle* h, bool with_time_grid) {
                 const int nbz = (int)((nz + 63) / 64), nbr = (int)((nr + 63) / 64);
                 auto ksplit = lpi == 1 ? k_linearize_split<1> : k_linearize_split<2>;
                 hipLaunchKernelGGL(ksplit, dim3(512), dim3(64), 0, h->stream, h->dc, B, nbz, h->d_nodes, h->d_dt, h->d_Mb, h->d_qp, flt, nbz + nbr);
+            }
+            // Under a library (n_cp > 1) the pipelined launch has written the steering-rate rows of the QP data from DevCfg::cp -- pg_config.control, or the set of a
+            // one-set library installed earlier: NOT any instance's set -- and k_rate_limits overwrites them per instance, on the same stream, behind the predicated repair
+            // launches (which read the library themselves) and before anything reads the QP data.  Nothing may be queued between the two that consumes ddmin / ddmax.
+            if (h->dc.n_cp > 1) {
+                const long nt = (long)B * h->dc.N;
+                hipLaunchKernelGGL(k_rate_limits, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_qp);
             }
             h->lin_done = true; h->stat_pipelined++;
         } else {
@@ -1392,6 +1507,7 @@ static int step_by_graph(pg_handle* h, int32_t B, const double* state, const dou
     auto& G = h->sg;
     if (!h->graph_mode || G.disabled || B != h->cfg.batch_capacity || B > 256 || h->B != B || h->warm_B < B || h->fuse != 0 || !h->d_traj || h->node_recheck) return PG_OK;
     if (h->dc.n_traj > 1 && h->traj_idx_B < B) return PG_OK;
+    if (h->dc.n_cp > 1 && h->cp_idx_B < B) return PG_OK;      // (the ordinary path reports it)
     if (hipSetDevice(h->cfg.device) != hipSuccess) return PG_OK;
     const bool same = G.x && G.B == B && G.user == h->stream && G.fuse == h->fuse && G.pipeline == h->pipeline && G.has_hji == (int)h->has_hji && G.traj_L == h->traj_L &&
                       memcmp(&G.dc, &h->dc, sizeof(DevCfg)) == 0 && memcmp(&G.hv, &h->hv, sizeof(HjiView)) == 0;

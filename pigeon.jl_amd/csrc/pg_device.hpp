@@ -25,6 +25,8 @@ typedef double tdouble;
 // device-side mirrors of pg_vehicle / pg_control_params (include/pigeon_mpc.h) in the arithmetic type of the build
 struct DevVehicle { real G, m, Izz, L, a, b, h, mu, Caf, Car, Cd0, Cd1, Cd2, fwd_frac, rwd_frac, fwb_frac, rwb_frac, Fx_max, Fx_min, Px_max, delta_max, kappa_max; };
 struct DevControl { real V_min, V_max, k_V, k_s, deltadot_max, Q_ds, Q_dpsi, Q_e, W_beta, W_r, W_HJI, R_delta, R_ddelta, R_Fx, R_dFx; int N_HJI; };
+// one set of a control-parameter library (pg_set_control_param_sets): the parameters as the kernels read them, with what pg_create derives from them beside them
+struct DevControlRec { DevControl cp; real ux_dummy; };
 // reciprocal: hardware seed + Newton steps (~1 ulp); the IEEE division sequence costs ~5x more issue slots
 #ifdef PG_F32
 PG_DEV float frcp(float x) { float r = __builtin_amdgcn_rcpf(x); float e = fmaf(-x, r, 1.0f); return fmaf(r, e, r); }

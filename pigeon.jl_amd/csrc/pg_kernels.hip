@@ -51,6 +51,10 @@ struct DevCfg {
     long traj_stride;             // doubles between consecutive trajectories of the library ([n_traj][10][Lmax])
     const int* traj_idx;          // [B] per-instance selection (nullptr when n_traj == 1)
     const int* traj_len;          // [n_traj] valid nodes of each trajectory
+    const DevControlRec* cp_sets; // control-parameter library (pg_set_control_param_sets), [n_cp] records; nullptr unless n_cp > 1
+    const int* cp_idx;            // [B] per-instance selection (nullptr unless n_cp > 1)
+    int n_cp;                     // library size (0: none installed, 1: `cp` and `ux_dummy` ARE the one set; both read the launch argument)
+    int cp_epoch;                 // counts the installs of a library or an index (nothing reads it on the device: the captured step compares DevCfg and is re-captured)
     int walls;                    // build-defined extension: soft rows edge_R - sw <= e <= edge_L + sw, sw >= 0 at nodes 2..N+1 (decoupled formulation only)
     real wall_weight;           // linear penalty on sw (per second, like W_beta)
     real* wall_edges;           // [B][N][2] (edge_L, edge_R) at node k+1, written by k_nodes_dec, read by k_solve
@@ -81,6 +85,41 @@ PG_DEV TrajView traj_of(const DevCfg& C, int b) {
     }
     return T;
 }
+
+// The control parameters of instance b (control_params of that controller: coupled_lat_long.jl:42-60, decoupled_lat_long.jl:32-50).  Every read of C.cp.* / C.ux_dummy in
+// the kernels goes through this view: PG_CP(view, field), view.ux_dummy().  Without a library, or with a library of one set, a read IS the read of the launch argument it
+// was (the test on n_cp is a scalar compare on a launch argument).  With a library the view holds the address of the instance's record -- one or two registers -- and every
+// read loads its field where it is used: a kernel keeps no copy of the set alive (a copy in registers cost k_nodes and k_linearize a wave of occupancy and the full k_solve
+// 60 B of scratch when it was tried), and fields it does not use are never loaded.
+//   WAVE = false: lane = instance (or a 16-lane row of k_solve_lat's four-per-wavefront arrangement): the record address is per lane, the loads are vector loads.
+//   WAVE = true:  b is the same for every lane of the wavefront (k_solve, the one-instance-per-wavefront arrangements of k_solve_lat): index and fields are read through the
+//                 constant address space at a wave-uniform address -- scalar loads into scalar registers, where the launch argument lives too.
+// The library is written by the host between launches only.  N_HJI is structure, equal in every set: read from C.cp.
+#define PG_CONST_AS __attribute__((address_space(4)))
+template <bool WAVE> struct ControlView {
+    const DevCfg& C; const DevControlRec* rec;
+    // (late: the view is made where its one read is, at the end of a register-tight kernel -- the opaque move keeps the compiler from loading the index at the kernel's top and
+    //  carrying the address through it; that cost the fp32 k_linearize<1> and k_nodes_linearize a wave of occupancy)
+    PG_DEV ControlView(const DevCfg& C_, int b, bool late = false) : C(C_), rec(nullptr) {
+        if (C_.n_cp > 1) {
+            if (late) asm volatile("" : "+v"(b));
+            if constexpr (WAVE) rec = C_.cp_sets + ((const PG_CONST_AS int*)C_.cp_idx)[__builtin_amdgcn_readfirstlane(b)];
+            else rec = C_.cp_sets + C_.cp_idx[b];
+        }
+    }
+    PG_DEV bool lib() const { return C.n_cp > 1; }
+    PG_DEV real load(const real* p) const { if constexpr (WAVE) return *(const PG_CONST_AS real*)p; else return *p; }
+    PG_DEV real ux_dummy() const { return lib() ? load(&rec->ux_dummy) : C.ux_dummy; }
+};
+// the four parameters of the commanded acceleration: the first four fields of a set, one 32-byte read under a library (ONE test per node of the seeding recurrence: four
+// tests -- one per field -- cost the serial chain of the pipelined launch 3 us of its 325 on the uniform path when that was measured; the recurrence inlined twice, once per
+// path with no test at all, cost k_nodes a wave of occupancy)
+struct SeedGains { real V_min, V_max, k_V, k_s; };
+PG_DEV SeedGains uniform_gains(const DevCfg& C) { SeedGains g; g.V_min = C.cp.V_min; g.V_max = C.cp.V_max; g.k_V = C.cp.k_V; g.k_s = C.cp.k_s; return g; }
+PG_DEV SeedGains library_gains(const DevControlRec* rec) { const real* p = &rec->cp.V_min; SeedGains g; g.V_min = p[0]; g.V_max = p[1]; g.k_V = p[2]; g.k_s = p[3]; return g; }
+static_assert(offsetof(DevControl, V_max) == sizeof(real) && offsetof(DevControl, k_V) == 2 * sizeof(real) && offsetof(DevControl, k_s) == 3 * sizeof(real), "library_gains reads V_min, V_max, k_V, k_s as one run");
+PG_DEV SeedGains seed_gains(const ControlView<false>& cv) { return cv.lib() ? library_gains(cv.rec) : uniform_gains(cv.C); }
+#define PG_CP(view, field) ((view).lib() ? (view).load(&(view).rec->cp.field) : (view).C.cp.field)
 
 // Stage block as k_solve keeps it in LDS (packed from the QP data on the way in): rows 0..5 of Abar = [A | B0+Bf] at a row stride of 9 doubles (odd stride: the 8 rows land on distinct LDS
 // banks, so the row-indexed reads of the Riccati passes are conflict-free), then Bbar = Bf (12) at SB_B, cbar = c (6) at SB_C.
@@ -249,7 +288,7 @@ PG_DEV void advance_vs(real& V, real& s, real A, real tau) {
     V = V + A * tau;
     s = s + V * tau + A * tau * tau * real(0.5);
 }
-PG_DEV real commanded_accel(const DevControl& cp, real trajA, real trajV, real V, real ds, real tau, bool traj_mode) {
+PG_DEV real commanded_accel(const SeedGains& cp, real trajA, real trajV, real V, real ds, real tau, bool traj_mode) {
 #pragma clang fp contract(off)
     real A_des = trajA + cp.k_V * (trajV - V) / tau + (traj_mode ? -cp.k_s * ds / tau / tau : real(0.0));
     return jmin(jmax(A_des, (cp.V_min - V) / tau), (cp.V_max - V) / tau);
@@ -309,6 +348,7 @@ template <bool STAGED, bool PUB> PG_DEV void nodes_body(const DevCfg& C, int B, 
     if constexpr (PUB) publish = __all(solved[b] == 0) != 0;          // (over the live lanes of the wavefront; lane 0 is always live)
     if constexpr (!STAGED) T = traj_of(C, b);
     const DevVehicle& P = C.veh;
+    const ControlView<false> cv(C, b);
     const real* q0 = state + (size_t)b * 6; const real* u0 = control + (size_t)b * 3;
     const tdouble* TS = ts + (size_t)b * C.NN; const tdouble* DT = dt + (size_t)b * C.N;
     real* ND = nodes + (size_t)b * C.NN * 10;
@@ -360,7 +400,7 @@ template <bool STAGED, bool PUB> PG_DEV void nodes_body(const DevCfg& C, int B, 
         real tau = (i == C.NN - 1) ? DT[i - 1] : DT[i];
         real s_ref; traj_lookup2(T, s, TS[i], tj, s_ref);
         real ds = s - s_ref;
-        const real A_des = commanded_accel(C.cp, tj.A, tj.V, V, ds, tau, traj_mode);
+        const real A_des = commanded_accel(seed_gains(cv), tj.A, tj.V, V, ds, tau, traj_mode);
         const bool shortp = i <= C.Ns;
         // :122 short nodes: one iteration from the measured (r0, beta0, delta0, Fyf0); :128 long nodes: four iterations from (V kappa, 0, 0, 0)
         Steady est = steady_state(P, V, A_des, tj.kappa, shortp ? 1 : 4, shortp ? r0 : V * tj.kappa, shortp ? beta0 : real(0.0), shortp ? sb0 : real(0.0), shortp ? cb0 : real(1.0),
@@ -399,7 +439,7 @@ template <bool STAGED, bool PUB> PG_DEV void nodes_body(const DevCfg& C, int B, 
                 const real tau = (ii == C.NN - 1) ? DT[ii - 1] : DT[ii];
                 TrajS tjj; real s_ref; traj_lookup2(T, ss, TS[ii], tjj, s_ref);
                 const real ds = ss - s_ref;
-                const real A_des = commanded_accel(C.cp, tjj.A, tjj.V, Vs, ds, tau, traj_mode);
+                const real A_des = commanded_accel(seed_gains(cv), tjj.A, tjj.V, Vs, ds, tau, traj_mode);
                 real At = A_des, Ar; limit_accel(P, Vs, tjj.kappa, At, Ar);
                 if (j == lp) { Vm = Vs; sm = ss; Adm = A_des; kpm = tjj.kappa; taum = tau; dsm = ds; pVm = tjj.V; Agm = At; }
                 Vst[j] = Vs; sst[j] = ss; tauj[j] = tau; Agj[j] = At;
@@ -447,7 +487,7 @@ template <bool STAGED, bool PUB> PG_DEV void nodes_body(const DevCfg& C, int B, 
         }
     }
     if (F.order && lead) {
-        bool slow = fabs(d1 - d0) > real(1.5) * C.cp.deltadot_max * ((real)C.Ns * (real)C.dt_short);
+        bool slow = fabs(d1 - d0) > real(1.5) * PG_CP(cv, deltadot_max) * ((real)C.Ns * (real)C.dt_short);
         const Envelope e = stable_limits(P, Ux0, Fx1 > real(0.0) ? Fx1 * P.fwd_frac : Fx1 * P.fwb_frac, Fx1 > real(0.0) ? Fx1 * P.rwd_frac : Fx1 * P.rwb_frac);
 #pragma unroll
         for (int k = 0; k < 4; k++) slow = slow || (e.H[k][0] * Uy0 + e.H[k][1] * r0 - e.G[k] > real(-0.05));
@@ -537,7 +577,9 @@ template <bool STAGED> __global__ __launch_bounds__(256) void k_nodes_warm(DevCf
 // ND = 6: an interval of the short horizon (zero-order hold: uf is not a variable, directions 6 and 7 vanish identically) with the six remaining directions on
 // G = 6 / K lanes; the Bf block is written as zeros and c sums the same six products in the same order -- the same bits as ND = 8 gives on such an interval.
 // (n0, n1: the node records of the interval's two ends -- in the nodes array, or a copy of them: k_nodes_linearize)
-template <int K, int ND = 8>
+// (CPLIB = false, k_nodes_linearize only: the steering-rate rows are written from the uniform set and, under a control-parameter library, rewritten per instance by
+//  k_rate_limits behind the launch -- the fp32 instantiations of that kernel sit at their register limit and lost a wave of occupancy to the per-instance read)
+template <int K, int ND = 8, bool CPLIB = true>
 PG_DEV void linearize_lanes_at(const DevCfg& C, int b, int t, int g, bool live, const real* __restrict__ n0, const real* __restrict__ n1, const tdouble* __restrict__ dt,
                                const real* __restrict__ hji_Mb, real* __restrict__ qp) {
     constexpr int G = ND / K;
@@ -690,8 +732,10 @@ PG_DEV void linearize_lanes_at(const DevCfg& C, int b, int t, int g, bool live, 
         Q[o.dmin + t] = jmax(e.dmin, -C.veh.delta_max) / C.un0;
         Q[o.dmax + t] = jmin(e.dmax, C.veh.delta_max) / C.un0;
         Q[o.fxmax + t] = jmin(C.veh.Px_max / Uxt, C.veh.Fx_max) / C.un1;
-        Q[o.ddmin + t] = -C.cp.deltadot_max * h_total / C.un0;
-        Q[o.ddmax + t] = C.cp.deltadot_max * h_total / C.un0;
+        real ddot_max = C.cp.deltadot_max;
+        if constexpr (CPLIB) { const ControlView<false> cv(C, b, true); ddot_max = PG_CP(cv, deltadot_max); }
+        Q[o.ddmin + t] = -ddot_max * h_total / C.un0;
+        Q[o.ddmax + t] = ddot_max * h_total / C.un0;
         Q[o.dt + t] = h_total;
     }
 }
@@ -843,9 +887,23 @@ template <bool STAGED, int LPI, int WAVES = 1> __global__ __launch_bounds__(64, 
             }
         }
     }
-    if (t < C.Ns) linearize_lanes_at<6 / LPI, 6>(C, b, t, g, live, rec, rec + 10, dt, hji_Mb, qp);
-    else linearize_lanes_at<8 / LPI, 8>(C, b, t, g, live, rec, rec + 10, dt, hji_Mb, qp);
+    if (t < C.Ns) linearize_lanes_at<6 / LPI, 6, false>(C, b, t, g, live, rec, rec + 10, dt, hji_Mb, qp);
+    else linearize_lanes_at<8 / LPI, 8, false>(C, b, t, g, live, rec, rec + 10, dt, hji_Mb, qp);
     PG_NL_MARK(2, wall_clock64());
+}
+
+// The steering-rate rows of update_QP! (coupled_lat_long.jl:323-333) of a batch under a control-parameter library, behind the pipelined launch: the same expression on the
+// same operands as linearize_lanes_at writes (the interval length is read back from the QP data), with the instance's own deltadot_max.  lane = (instance, interval)
+__global__ __launch_bounds__(256) void k_rate_limits(DevCfg C, int B, real* __restrict__ qp) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)B * C.N) return;
+    const int b = (int)(gid / C.N), t = (int)(gid - (long)b * C.N);
+    const QpOff o = qp_offsets(C.N);
+    real* Q = qp + (size_t)b * C.qp_len;
+    const ControlView<false> cv(C, b);
+    const real ddot_max = PG_CP(cv, deltadot_max), h_total = Q[o.dt + t];
+    Q[o.ddmin + t] = -ddot_max * h_total / C.un0;
+    Q[o.ddmax + t] = ddot_max * h_total / C.un0;
 }
 
 // the plant's RK4 of one step, in place: x = (E, N, psi, Ux, Uy, r), control (delta, Fx) held, nsub sub-steps of length h -- the arithmetic of k_advance below, for
@@ -940,6 +998,7 @@ template <bool STAGED> __global__ __launch_bounds__(64) void k_nodes_dec(DevCfg 
     const bool lead = lp == 0;                              // (the lane that stores what all lanes of the instance compute alike)
     if constexpr (!STAGED) T = traj_of(C, b);
     const DevVehicle& P = C.veh;
+    const ControlView<false> cv(C, b);
     const real* q0 = state + (size_t)b * 6; const real* u0 = control + (size_t)b * 3;
     const tdouble* TS = ts + (size_t)b * C.NN; const tdouble* DT = dt + (size_t)b * C.N;
     real* ND = nodes + (size_t)b * C.NN * 10;
@@ -967,7 +1026,7 @@ template <bool STAGED> __global__ __launch_bounds__(64) void k_nodes_dec(DevCfg 
         const real tau = (i == C.NN - 1) ? DT[i - 1] : DT[i];
         TrajS tj; real s_ref; int jk; real wk;
         traj_lookup2(T, s, TS[i], tj, s_ref, &jk, &wk);
-        const real A_des = commanded_accel(C.cp, tj.A, tj.V, V, s - s_ref, tau, traj_mode);                                   // :76-77
+        const real A_des = commanded_accel(seed_gains(cv), tj.A, tj.V, V, s - s_ref, tau, traj_mode);                                   // :76-77
         NodeRec r; real A;
         real* ax = naux + ((size_t)b * C.NN + i) * 4;
         r.q0 = real(0.0); r.pV = real(0.0); r.pK = tj.kappa;
@@ -1008,7 +1067,7 @@ template <bool STAGED> __global__ __launch_bounds__(64) void k_nodes_dec(DevCfg 
                 const real tau = (ii == C.NN - 1) ? DT[ii - 1] : DT[ii];
                 TrajS tjj; real s_ref; int jk; real wk;
                 traj_lookup2(T, ss, TS[ii], tjj, s_ref, &jk, &wk);
-                const real A_des = commanded_accel(C.cp, tjj.A, tjj.V, Vs, ss - s_ref, tau, traj_mode);
+                const real A_des = commanded_accel(seed_gains(cv), tjj.A, tjj.V, Vs, ss - s_ref, tau, traj_mode);
                 real At = A_des, Ar; limit_accel(P, Vs, tjj.kappa, At, Ar);
                 if (j == lp) { Vm = Vs; Adm = A_des; kpm = tjj.kappa; Agm = At; jkm = jk; wkm = wk; }
                 Vst[j] = Vs; sst[j] = ss; tauj[j] = tau;
@@ -1126,7 +1185,7 @@ __global__ __launch_bounds__(128) void k_qp_dec(DevCfg C, int B, const real* __r
     real Uxt = n1[1], Fx = n1[7];
     real Fxf = Fx > real(0.0) ? Fx * C.veh.fwd_frac : Fx * C.veh.fwb_frac, Fxr = Fx > real(0.0) ? Fx * C.veh.rwd_frac : Fx * C.veh.rwb_frac;
     Envelope e = stable_limits(C.veh, Uxt, Fxf, Fxr);
-    const real dmin_t = jmax(e.dmin, -C.veh.delta_max), dmax_t = jmin(e.dmax, C.veh.delta_max), ddmin_t = -C.cp.deltadot_max * T, ddmax_t = C.cp.deltadot_max * T;
+    const real dmin_t = jmax(e.dmin, -C.veh.delta_max), dmax_t = jmin(e.dmax, C.veh.delta_max), ddot_max = PG_CP(ControlView<false>(C, b), deltadot_max), ddmin_t = -ddot_max * T, ddmax_t = ddot_max * T;
     // ---- embedded coupled layout ----
     QpOff o = qp_offsets(C.N);
     real* Q = qp + (size_t)b * C.qp_len;
@@ -1156,7 +1215,7 @@ __global__ __launch_bounds__(128) void k_qp_dec(DevCfg C, int B, const real* __r
         for (int i = 49; i < LATP; i++) Lp[i] = real(0.0);
     }
     if (t == 0) {
-        Q[o.qcurr] = real(0.0); Q[o.qcurr + 1] = C.ux_dummy; for (int k = 0; k < 4; k++) Q[o.qcurr + 2 + k] = q[k];
+        Q[o.qcurr] = real(0.0); Q[o.qcurr + 1] = ControlView<false>(C, b).ux_dummy(); for (int k = 0; k < 4; k++) Q[o.qcurr + 2 + k] = q[k];
         Q[o.ucurr] = n0[6]; Q[o.ucurr + 1] = real(0.0); Q[o.M] = real(0.0); Q[o.M + 1] = real(0.0); Q[o.b] = real(1.0);
     }
 }
@@ -1824,6 +1883,7 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
     const real x0_fill = lane < 6 ? Q[o.qcurr + lane] : Q[o.ucurr + (lane < 8 ? lane - 6 : 0)];
     const int prev_solved = O.solved[b], prev_status = O.status[b];      // (the warm-start test further down: loaded with the batch, not in a round trip of its own)
     const real hji_b = Q[o.b];
+    const ControlView<true> cv(C, b);                           // (b is wave-uniform: scalar registers, like the launch argument)
     if (lane < 4) sZero[lane] = lane < 2 ? real(0.0) : real(1.0);
     if (lane < 32) sCst[lane] = (lane == 6 || lane == 15 || lane == 16 || lane == 19) ? real(1.0) : real(0.0);
 
@@ -1837,15 +1897,15 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
     // sw >= 0, and sw takes the slot of the (absent) safety-row slack: the third stage-locally eliminated slack group
     const bool wall_on = act && C.walls != 0;
     const real dts = Q[o.dt + s];
-    const real Rd0 = real(2.0) * C.cp.R_ddelta / dts, Rd1 = real(2.0) * C.cp.R_dFx / dts;
-    const real wb = C.cp.W_beta * dts, wr = C.cp.W_r * dts, wh = C.cp.W_HJI;
+    const real Rd0 = real(2.0) * PG_CP(cv, R_ddelta) / dts, Rd1 = real(2.0) * PG_CP(cv, R_dFx) / dts;
+    const real wb = PG_CP(cv, W_beta) * dts, wr = PG_CP(cv, W_r) * dts, wh = PG_CP(cv, W_HJI);
 #pragma unroll
     for (int i = 0; i < 4; i++) { h0[i] = Q[o.H + 8 * s + 2 * i]; h1[i] = Q[o.H + 8 * s + 2 * i + 1]; bb[6 + i] = Q[o.G + 4 * s + i]; }
-    bb[0] = -C.cp.V_min; bb[1] = C.cp.V_max; bb[2] = -C.fxmin_n; bb[3] = Q[o.dmax + s]; bb[4] = -Q[o.dmin + s]; bb[5] = Q[o.fxmax + s];
+    bb[0] = -PG_CP(cv, V_min); bb[1] = PG_CP(cv, V_max); bb[2] = -C.fxmin_n; bb[3] = Q[o.dmax + s]; bb[4] = -Q[o.dmin + s]; bb[5] = Q[o.fxmax + s];
     bb[10] = real(0.0); bb[11] = real(0.0); bb[12] = Q[o.ddmax + s]; bb[13] = -Q[o.ddmin + s]; bb[14] = Q[o.b]; bb[15] = real(0.0);
     if (wall_on) { const real* w = C.wall_edges + ((size_t)b * N + s) * 2; bb[0] = w[0]; bb[1] = -w[1]; bb[2] = real(0.0); }
     const real ww = C.wall_weight * dts;
-    const real Qd5 = real(2.0) * C.cp.Q_e * dts;
+    const real Qd5 = real(2.0) * PG_CP(cv, Q_e) * dts;
     if (!RING) {      // (the loads issued at the top have had the whole constant set-up to arrive)
 #pragma unroll
         for (int u = 0; u < NFILL; u++) {
@@ -1857,12 +1917,12 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
     if (lane < 8) sx0[lane] = x0_fill;
     if (act) {   // entries of the stage cost that never change
         real* Qo = sQ + 10 * (s + 1);
-        Qo[0] = real(2.0) * C.cp.Q_ds * dts; Qo[4] = real(2.0) * C.cp.Q_dpsi * dts; Qo[5] = real(2.0) * C.cp.Q_e * dts;
+        Qo[0] = real(2.0) * PG_CP(cv, Q_ds) * dts; Qo[4] = real(2.0) * PG_CP(cv, Q_dpsi) * dts; Qo[5] = real(2.0) * PG_CP(cv, Q_e) * dts;
         real* qo = sq + 8 * (s + 1);
         qo[0] = real(0.0); qo[4] = real(0.0); qo[5] = real(0.0);
         sR[2 * s + 1] = Rd1; sr[2 * s + 1] = real(0.0);
     }
-    const real Qd6 = real(2.0) * C.cp.R_delta * dts, Qd7 = real(2.0) * C.cp.R_Fx * dts;
+    const real Qd6 = real(2.0) * PG_CP(cv, R_delta) * dts, Qd7 = real(2.0) * PG_CP(cv, R_Fx) * dts;
     __syncthreads();
 
     // slack of every row at the point w = (x[8], v0, s1, s2, sh)
@@ -2864,7 +2924,7 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
     if (status == PG_SOLVED && C.polish && pstat < 0) status = PG_SOLVED_UNVERIFIED;      // an interior-point iterate no active-set round could verify (pigeon_mpc.h)
     if (status == PG_SOLVED || status == PG_SOLVED_UNVERIFIED) {
         real Ux0 = sx0[1], Fx0 = sx0[7];
-        if (Ux0 < C.cp.V_min || Ux0 > C.cp.V_max || Fx0 < C.fxmin_n) status = PG_INFEASIBLE_X0;
+        if (Ux0 < PG_CP(cv, V_min) || Ux0 > PG_CP(cv, V_max) || Fx0 < C.fxmin_n) status = PG_INFEASIBLE_X0;
     }
     // ---- outputs ----
     real* SX = O.sol_x + (size_t)b * NN * 8;

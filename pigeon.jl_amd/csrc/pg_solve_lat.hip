@@ -171,6 +171,7 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
     const int b_raw = listm ? (idx_raw < n_list ? (HAND == 2 && idx_raw >= n_front ? O.list[B - 1 - (idx_raw - n_front)] : O.list[idx_raw]) : B) : idx_raw;
     const bool valid = b_raw < B;
     const int b = valid ? b_raw : B - 1;                 // (a ragged last wavefront solves the last instance again and stores nothing)
+    const ControlView<LPI == 64> cv(C, b);             // (one instance per wavefront: scalar reads, as in k_solve; four: the record is per 16-lane row, read per lane)
     extern __shared__ real lds[];
     real* const sI = lds + (size_t)g * N * LAT_STRIDE;   // this instance's region: rec[N][12] then tab[N][12]
     real* const sRec = sI; real* const sTab = sI + (size_t)N * LAT_REC;
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
     const real* const Xb = XLDS ? sMat : Lb;
     const real* const colp = Xb + (c < 7 ? c : 7);
     const real cx4 = (c == 4 || c == 5) ? real(1.0) : real(0.0);
-    const real cpsi = c == 2 ? real(2.0) * C.cp.Q_dpsi : real(0.0);      // Qhat[2][2] = 2 Q_dpsi dt_k is not stored: lane 2 forms it from dt_k
+    const real cpsi = c == 2 ? real(2.0) * PG_CP(cv, Q_dpsi) : real(0.0);      // Qhat[2][2] = 2 Q_dpsi dt_k is not stored: lane 2 forms it from dt_k
     // table slot lane c writes after a stage of the matrix pass: K[c] (c < 5), kff (lane 6 -> slot 5), Sinv (lane 5 -> slot 6)
     const int wslot = c < 5 ? c : (c == 6 ? 5 : (c == 5 ? 6 : -1));
     const real m6 = c == 6 ? real(1.0) : real(0.0), m5lt = c < 5 ? real(1.0) : real(0.0);
@@ -607,7 +608,7 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
         E.d1 = lat_rcp(W[2] + W[3] + W[6]); E.d2 = lat_rcp(W[4] + W[5] + W[7]);
         E.c10 = -(W[2] * S.h0[0] + W[3] * S.h0[1]); E.c11 = -(W[2] * S.h1[0] + W[3] * S.h1[1]);
         E.c20 = -(W[4] * S.h0[2] + W[5] * S.h0[3]); E.c21 = -(W[4] * S.h1[2] + W[5] * S.h1[3]);
-        E.g1 = C.cp.W_beta * S.dts - ell[2] - ell[3] - ell[6]; E.g2 = C.cp.W_r * S.dts - ell[4] - ell[5] - ell[7];
+        E.g1 = PG_CP(cv, W_beta) * S.dts - ell[2] - ell[3] - ell[6]; E.g2 = PG_CP(cv, W_r) * S.dts - ell[4] - ell[5] - ell[7];
         if constexpr (WALLS) { E.dh = lat_rcp(W[10] + W[11] + W[12]); E.ch = -(W[10] - W[11]); E.gh = C.wall_weight * S.dts - ell[10] - ell[11] - ell[12]; }
         else { E.dh = real(0.0); E.ch = real(0.0); E.gh = real(0.0); }
     };
@@ -653,8 +654,8 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
     // every stage-locally eliminated slack needs a pivot: a group without an active row gets its sigma >= 0 row, whose multiplier is then known (the linear cost of the slack)
     auto polish_pivots = [&](unsigned& am, real* Ll, const StageC& S) __attribute__((always_inline)) -> bool {
         bool touched = false;
-        if (!(am & 0x04Cu)) { am |= 1u << 6; Ll[6] = C.cp.W_beta * S.dts; touched = true; }
-        if (!(am & 0x0B0u)) { am |= 1u << 7; Ll[7] = C.cp.W_r * S.dts; touched = true; }
+        if (!(am & 0x04Cu)) { am |= 1u << 6; Ll[6] = PG_CP(cv, W_beta) * S.dts; touched = true; }
+        if (!(am & 0x0B0u)) { am |= 1u << 7; Ll[7] = PG_CP(cv, W_r) * S.dts; touched = true; }
         if constexpr (WALLS) { if (!(am & 0x1C00u)) { am |= 1u << 12; Ll[12] = C.wall_weight * S.dts; touched = true; } }
         return touched;
     };
@@ -682,7 +683,7 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
     // gradient of the Lagrangian in the pinned input of stage sj at the roll-out's point: F x_s + Bbar'y + S v  (x_s: the node the stage starts from; S = Rhat0 + Bbar'P Bbar)
     auto pin_gradient = [&](int sj, const StageC& S, real v) __attribute__((always_inline)) -> real {
         const real* ax = aux + (size_t)sj * LAT_AUX;
-        real g = ax[6] + (real(2.0) * C.cp.R_ddelta * frcp(S.dts) + ax[5]) * v;
+        real g = ax[6] + (real(2.0) * PG_CP(cv, R_ddelta) * frcp(S.dts) + ax[5]) * v;
         if (sj > 0) {
             const real* xp = sRec + LAT_REC * (sj - 1);
 #pragma unroll
@@ -720,10 +721,10 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
                 rec[0] = yy - E.c10 * E.c10 * E.d1 - E.c20 * E.c20 * E.d2;
                 rec[1] = yr - E.c10 * E.c11 * E.d1 - E.c20 * E.c21 * E.d2;
                 rec[2] = rr - E.c11 * E.c11 * E.d1 - E.c21 * E.c21 * E.d2;
-                rec[3] = real(2.0) * C.cp.Q_e * S.dts;
+                rec[3] = real(2.0) * PG_CP(cv, Q_e) * S.dts;
                 if constexpr (WALLS) rec[3] += W[10] + W[11] - E.ch * E.ch * E.dh;
-                rec[4] = real(2.0) * C.cp.R_delta * S.dts + W[0] + W[1];
-                rec[5] = pn.on ? BIGP : real(2.0) * C.cp.R_ddelta * frcp(S.dts) + W[8] + W[9];
+                rec[4] = real(2.0) * PG_CP(cv, R_delta) * S.dts + W[0] + W[1];
+                rec[5] = pn.on ? BIGP : real(2.0) * PG_CP(cv, R_ddelta) * frcp(S.dts) + W[8] + W[9];
             }
         }
     };
@@ -738,7 +739,7 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
         real g0 = real(0.0), g1 = real(0.0);
 #pragma unroll
         for (int i = 0; i < 4; i++) { g0 += S.h0[i] * ell[2 + i]; g1 += S.h1[i] * ell[2 + i]; }
-        const real G1 = (with_const ? C.cp.W_beta * S.dts : real(0.0)) - ell[2] - ell[3] - ell[6], G2 = (with_const ? C.cp.W_r * S.dts : real(0.0)) - ell[4] - ell[5] - ell[7];
+        const real G1 = (with_const ? PG_CP(cv, W_beta) * S.dts : real(0.0)) - ell[2] - ell[3] - ell[6], G2 = (with_const ? PG_CP(cv, W_r) * S.dts : real(0.0)) - ell[4] - ell[5] - ell[7];
         out[0] = g0 - E.c10 * G1 * E.d1 - E.c20 * G2 * E.d2;
         out[1] = g1 - E.c11 * G1 * E.d1 - E.c21 * G2 * E.d2;
         if constexpr (WALLS) out[2] = (ell[10] - ell[11]) - E.ch * ((with_const ? C.wall_weight * S.dts : real(0.0)) - ell[10] - ell[11] - ell[12]) * E.dh; else out[2] = real(0.0);
@@ -829,15 +830,15 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
         if constexpr (WALLS) sw = fmax(wipm ? SGj[2] : real(0.0), fmax(real(0.0), -fmin(sl[10], sl[11])) + sig0);
         slacks(S, xs, vst, s1, s2, sw, sl);
         if (actj && valid) {
-            SXj[0] = real(0.0); SXj[1] = C.ux_dummy; SXj[7] = real(0.0);      // the embedded layout pg_get_solution documents: (0, Ux slot, Uy, r, dpsi, e, delta, 0)
+            SXj[0] = real(0.0); SXj[1] = cv.ux_dummy(); SXj[7] = real(0.0);      // the embedded layout pg_get_solution documents: (0, Ux slot, Uy, r, dpsi, e, delta, 0)
 #pragma unroll
             for (int m = 0; m < 5; m++) SXj[2 + m] = xs[m];
             SGj[0] = s1; SGj[1] = s2; SGj[2] = sw;
         }
         // cost of the starting point (tracking terms on node s + 1, the linear penalties of the soft-row slacks): it sets the scale of the first barrier parameter below
         if (actj) {
-            real j0s = real(0.5) * S.dts * (real(2.0) * C.cp.Q_dpsi * xs[2] * xs[2] + real(2.0) * C.cp.Q_e * xs[3] * xs[3] + real(2.0) * C.cp.R_delta * xs[4] * xs[4])
-                       + S.dts * (C.cp.W_beta * s1 + C.cp.W_r * s2 + (WALLS ? C.wall_weight * sw : real(0.0)));
+            real j0s = real(0.5) * S.dts * (real(2.0) * PG_CP(cv, Q_dpsi) * xs[2] * xs[2] + real(2.0) * PG_CP(cv, Q_e) * xs[3] * xs[3] + real(2.0) * PG_CP(cv, R_delta) * xs[4] * xs[4])
+                       + S.dts * (PG_CP(cv, W_beta) * s1 + PG_CP(cv, W_r) * s2 + (WALLS ? C.wall_weight * sw : real(0.0)));
             j0 += j0s;
         }
         real Tl[NR], Ll[NR], Cl[NR];
@@ -1261,7 +1262,7 @@ __global__ __launch_bounds__(64, 1) void k_solve_lat(DevCfg C, int B, const real
     }
     if (valid && !deferred) {
         real* SX = O.sol_x + (size_t)b * NN * 8;
-        if (cs < 8) SX[cs] = cs == 1 ? C.ux_dummy : (cs >= 2 && cs < 6 ? Q[o.qcurr + cs] : (cs == 6 ? Q[o.ucurr] : real(0.0)));
+        if (cs < 8) SX[cs] = cs == 1 ? cv.ux_dummy() : (cs >= 2 && cs < 6 ? Q[o.qcurr + cs] : (cs == 6 ? Q[o.ucurr] : real(0.0)));
         for_slots([&](int j) __attribute__((always_inline)) {
             if (is_act(j)) {
                 real Tl[NR], Ll[NR], Cl[NR]; get_tl(j, Tl, Ll); get_cr(j, Cl);

@@ -154,6 +154,47 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_set_trajectory_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_trajectory_index")
         self.trajectory_index = index
 
+    # ---- one controller per (x0, control_params) pair: a library of parameter sets and a per-instance selection (a tuning sweep in one batch) ----
+    def pack_control_params(self, sets):
+        """dicts (missing fields: the handle's own control_params) or pg_control_params structures -> a ctypes array of pg_control_params."""
+        sets = list(sets)
+        arr = (_lib.pg_control_params * len(sets))()
+        for k, cp in enumerate(sets):
+            if isinstance(cp, _lib.pg_control_params):
+                C.memmove(C.byref(arr[k]), C.byref(cp), C.sizeof(_lib.pg_control_params))
+                continue
+            C.memmove(C.byref(arr[k]), C.byref(self.cfg.control), C.sizeof(_lib.pg_control_params))
+            for name, _ in _lib.pg_control_params._fields_:
+                if name != "_pad" and name in cp:
+                    setattr(arr[k], name, int(cp[name]) if name == "N_HJI" else float(cp[name]))
+        return arr
+
+    def set_control_params(self, sets, index=None):
+        """One set (dict / structure) for the whole batch, or a list of sets; select per instance with `index` or set_control_param_index."""
+        if isinstance(sets, (dict, _lib.pg_control_params)):
+            sets = [sets]
+        arr = self.pack_control_params(sets)
+        self._chk(self.lib.pg_set_control_param_sets(self.h, len(arr), arr), "pg_set_control_param_sets")
+        if index is not None:
+            self.set_control_param_index(index)
+
+    def set_control_param_index(self, index):
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        self._chk(self.lib.pg_set_control_param_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_control_param_index")
+
+    def clear_control_params(self):
+        self._chk(self.lib.pg_clear_control_param_sets(self.h), "pg_clear_control_param_sets")
+
+    def control_param_sets(self):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        n = C.c_int32(0)
+        self._chk(self.lib.pg_get_control_param_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_control_param_sets")
+        arr = (_lib.pg_control_params * max(n.value, 1))()
+        index = np.full(self.B, -1, dtype=np.int32)
+        self._chk(self.lib.pg_get_control_param_sets(self.h, C.byref(n), arr, n.value, _p(index, C.POINTER(C.c_int32)), self.B), "pg_get_control_param_sets")
+        names = [name for name, _ in _lib.pg_control_params._fields_ if name != "_pad"]
+        return [{name: getattr(arr[k], name) for name in names} for k in range(n.value)], index
+
     # ---- mpc.HJI_cache = HJICache(...) (Pigeon.jl:40) ----
     def set_hji_cache(self, grid_knots, V_raw, gradV_raw):
         dims = np.array([len(k) for k in grid_knots], dtype=np.int32)
