@@ -29,7 +29,7 @@ struct pg_handle {
     int solve_parity = 0;                                     // which of the two to-do counters the next solve launch counts into (the other one holds the previous launch's count: see launch_solve)
     bool cnt_cleared = false;                                 // this step's projection kernel has zeroed the counter launch_solve is about to use
     bool lin_done = false;                                    // this step's launch_nodes already linearised (update_and_solve skips update_QP)
-    int* d_progress = nullptr;                                // [cap / NODES_IPB + 8] nodes completed per nodes wavefront (k_nodes_linearize), then the fault word of the launch; last entry: fall-backs so far
+    int* d_progress = nullptr;                                // progress and fault words of the pipelined launch (k_nodes_linearize): layout below (pipe_fault_word)
     int64_t fallback_total = 0; int fallback_seen = 0;        // pg_get_pipeline_fallbacks: 64-bit total kept on the host, last value of the device's 32-bit word
     int fuse = 0;                                             // pg_step_dev / pg_simulate_dev: linearisation fused into the solve kernel (pg_set_fusion): 0 never (default), 1 always, 2 for all-warm batches
     std::string err;
@@ -56,17 +56,16 @@ struct pg_handle {
     int pipe_min = 2304, pipe_max = 256 * NODES_IPB;                    // batch sizes the pipelined launch serves (options "pipe_min" / "pipe_max"; its nodes blocks must be resident at once: <= 16384)
     int lin_lpi = 1;                                          // lanes per (instance, interval) of the large-batch linearisation (k_linearize_split / k_nodes_linearize): one lane with all eight
                                                               // directions (option "lin_lanes" = 2: the lane pair of rounds 1-3, for A/B runs; same bits in fp64, rounding-level differences in fp32)
-    int* d_todo = nullptr; int split_solve = 1, split_lat = 1;      // d_todo [cap + 8]: instances the rounds-only k_solve leaves to the full kernel; behind them the control words of the solve launches:
-                                                                    // [0], [1] two to-do counters used alternately (this launch's count / the previous launch's)
+    int* d_todo = nullptr; int split_solve = 1, split_lat = 1;      // d_todo: instances one solve launch leaves to the next; behind them the control words of the solve launches: layout below (solve_ctl)
     int phase_timing = 0;                                           // option "phase_timing": 1 = pg_step_dev records the four HIP events pg_get_phase_ms reads (13-25 us of stream time per step at B = 4096: 2-4 %); 0 (default) = no instrumentation on the stream
     real* u_direct = nullptr; bool u_written = false;               // pg_step_dev: the caller's control array for k_solve to write (SolveOut::u_out2), and whether the launch did
-    int* d_order = nullptr; int order_B = 0;  // [cap] + 2 counters: launch order filed by the nodes kernels of the current step (likely slow instances first); order_B = batch it is valid for
+    int* d_order = nullptr; int order_B = 0;  // launch order filed by the nodes kernels of the current step (likely slow instances first): layout below (order_cnt); order_B = batch it is valid for
     real *d_pol_u2 = nullptr, *d_pol_u = nullptr; int* d_pol_src = nullptr;   // HJI fallback policy (HJI_computation.jl:133-158)
     real* d_vmin = nullptr; int* d_breach = nullptr;          // summary of pg_simulate_safety_dev: V_min [cap]; first_breach [cap] then policy_steps [cap] (k_advance_safety)
     bool sum_fresh = true;                                    // the summary restarts at the next safety step (the clock restarted since it was last written)
     // node callback (pg_node_step_dev / pg_simulate_node_dev), allocated at the first call of one of them: the keep buffer of gated-out instances' warm state (KeepView,
-    // pg_kernels.hip), d_node = gate [cap], heartbeat [cap], counts [cap][4], two cold words (k_node_finish -> k_nodes_recheck, used alternately: node_parity is the one the
-    // next recheck reads); the applied command [cap][3]; trajectory.t[end] per installed trajectory, fp64
+    // pg_kernels.hip), the node words d_node (layout below: node_cold; node_parity is the cold word the next recheck reads); the applied command [cap][3];
+    // trajectory.t[end] per installed trajectory, fp64
     char* d_keep = nullptr; KeepView kv{}; int* d_node = nullptr; real* d_applied = nullptr; double* d_tend = nullptr;
     std::vector<double> traj_ends; bool tend_dirty = true;
     int node_parity = 0; bool node_recheck = false;           // node_recheck: the last step was a node step (some instance may have no solution: launch_nodes queues k_nodes_recheck)
@@ -95,7 +94,6 @@ struct pg_handle {
     char* d_in = nullptr; char* d_out = nullptr;             // the five input arrays / (u, status, iters) as ONE allocation each: a batch that fills the handle travels in one copy per direction
     size_t in_bytes = 0, out_bytes = 0, in_dbl_off = 0;        // (layout by capacity: [state 6][control 3][other 4] real, then at in_dbl_off [t0][time_offset] double; [u 3] real, [status][iters] int)
     char* h_stage = nullptr; size_t stage_bytes = 0;            // pinned host staging of pg_set_inputs / pg_step (one stream synchronisation per call instead of one per array)
-    real* d_ws4 = nullptr; bool solve_quad = false; size_t solve4_lds = 0;   // k_solve4 (four instances per wavefront)
     bool qp_embedded = true; int lat_pack_only = 1;            // lateral formulation: the embedded QP block is current (k_qp_dec wrote it) / option "lat_pack_only": steps write the packed records only
     bool qp_stale = false;                                    // the lateral solver was switched (option "lateral_solver") after the last update_QP!: pg_solve returns PG_ERR_STATE until the QP data are rebuilt
     bool solve_lat = false; size_t lat_lds = 0;               // lateral formulation: its own kernel k_solve_lat (option "lateral_solver" = 2 keeps the embedding in k_solve)
@@ -106,6 +104,53 @@ struct pg_handle {
 #define REQUIRE(h, cond, msg) do { if (!(cond)) { if (h) (h)->err = (msg); return PG_ERR_INVALID; } } while (0)
 
 static std::string g_create_error;
+
+// ---- The device words the launches share: each layout is defined HERE only -- the allocations take their sizes from it, every launch its addresses. ----
+// d_todo [cap + CTL_WORDS] (the words zeroed by pg_create): the to-do list [cap] one solve launch files for the next, then the control words of the solve launches
+enum SolveCtl {
+    CTL_TODO0 = 0, CTL_TODO1 = 1,      // k_solve's split launch: two to-do counters used alternately -- [solve_parity] is zeroed by k_project of the step (or a memset in launch_solve_coupled) and
+                                       // counted by this launch, the other holds the previous launch's count (SolveOut::mode).  k_solve_lat's two-launch warm solve: [0] = length of the list the
+                                       // warm attempts leave (memset, counted by them).  k_solve_lat's hand-over (memset of [0..2], counted by the launch that hands over): [0] listed from the
+    CTL_HAND_BACK = 2,                 // front, [1] finished instances, [2] listed from the back
+    CTL_TIMELINE = 4,                  // pg_debug_solve_cycles with "diag_timeline": the to-do counter of its rounds-only launch (memset there)
+    CTL_WHOLE = 5,                     // launches in which the full k_solve took the whole batch (SolveOut::n_whole: counted by k_solve, read by option "stat_whole_batch_solves")
+    CTL_WORDS = 8
+};
+// d_order [2 cap + ORDER_CNT_WORDS]: the launch order [cap]; two counters (filed from the front / from the back: zeroed by k_project of the step or by launch_hji_order, counted by
+// the nodes kernels and k_order_hji); the verdict per instance [cap] (the same kernels)
+// d_node [6 cap + NODE_COLD_WORDS], zeroed by node_prepare: gate [cap] (k_node_gate), heartbeat [cap] and counts [cap][4] (k_node_finish), two cold words used alternately (zeroed
+// by k_node_gate, set by k_node_finish of the same step, read by k_nodes_recheck of the next)
+// d_progress [cap / NODES_IPB + PIPE_WORDS], zeroed by pg_create: nodes completed per nodes wavefront [nbn <= cap / NODES_IPB + 1] of the pipelined launch (k_nodes_linearize), then the
+// fault word of the launch (set by a waiting wavefront that gave up, read by the predicated repair) -- k_project of the step zeroes these nbn + 1 words --; last word: fall-backs so
+// far (counted by the wavefronts that gave up, never reset: pg_get_pipeline_fallbacks)
+enum { ORDER_CNT_WORDS = 2, NODE_COLD_WORDS = 2, PIPE_WORDS = 8 };
+static size_t cap_of(const pg_handle* h) { return (size_t)h->cfg.batch_capacity; }
+static int* solve_ctl(const pg_handle* h, int word) { return h->d_todo + cap_of(h) + word; }
+static int* order_cnt(const pg_handle* h) { return h->d_order + cap_of(h); }                     static int* order_slow(const pg_handle* h) { return order_cnt(h) + ORDER_CNT_WORDS; }
+static int* node_heartbeat(const pg_handle* h) { return h->d_node + cap_of(h); }                 static int* node_counts(const pg_handle* h) { return h->d_node + 2 * cap_of(h); }
+static int* node_cold(const pg_handle* h, int parity) { return h->d_node + 6 * cap_of(h) + parity; }
+static size_t pipe_words(const pg_handle* h) { return cap_of(h) / NODES_IPB + PIPE_WORDS; }
+static int* pipe_fault_word(const pg_handle* h, int nbn) { return h->d_progress + nbn; }         static int* pipe_fallbacks(const pg_handle* h) { return h->d_progress + pipe_words(h) - 1; }
+// ---- the solve kernels' launches (templates: ahead of the extern "C" block) ----
+// the outputs every solve launch writes, `order` = the launch order (nullptr: index order); everything else zero -- each arrangement below sets the fields it uses
+static SolveOut solve_out(const pg_handle* h, const int* order) {
+    SolveOut O{}; O.sol_x = h->d_solx; O.sol_sigma = h->d_sigma; O.u_out = h->d_u; O.status = h->d_status; O.iters = h->d_iters; O.active = h->d_active; O.mu = h->d_mu;
+    O.solved = h->d_solved; O.polish = h->d_polish; O.lam = h->d_lam; O.order_in = order; O.wfail = h->d_wfail;
+    return O;
+}
+// one k_solve launch, one wavefront per instance, `n` blocks
+template <bool PROF, bool RING, bool FUSE, bool IPM = true>
+static void launch_k_solve(pg_handle* h, hipStream_t st, int n, const SolveOut& O, unsigned long long* prof = nullptr) {
+    hipLaunchKernelGGL((k_solve<PROF, RING, FUSE, IPM>), dim3(n), dim3(64), h->solve_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, prof, h->d_dt, h->d_Mb);
+}
+// one k_solve_lat launch: the instantiation with or without the wall rows, the row state in registers (MEM = 0), in the workspace (1) or where the handle keeps it (LAT_MEM_ANY)
+enum { LAT_MEM_ANY = 2 };
+template <int MEM, int LPI, int HAND>
+static void launch_k_solve_lat(pg_handle* h, dim3 grid, size_t lds, hipStream_t st, const SolveOut& O, unsigned long long* prof) {
+    if constexpr (MEM == LAT_MEM_ANY) { if (h->lat_mem) launch_k_solve_lat<1, LPI, HAND>(h, grid, lds, st, O, prof); else launch_k_solve_lat<0, LPI, HAND>(h, grid, lds, st, O, prof); }
+    else if (h->dc.walls) hipLaunchKernelGGL((k_solve_lat<1, true, MEM != 0, LPI, HAND>), grid, dim3(64), lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, prof);
+    else hipLaunchKernelGGL((k_solve_lat<1, false, MEM != 0, LPI, HAND>), grid, dim3(64), lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, prof);
+}
 
 // Host <-> device transfers of path data.  The ABI speaks double on the host side; device buffers are `real` (double in libpigeon_hip.so,
 // float in libpigeon_hip_f32.so).  *_dev entry points take device pointers in the library's own element type (times are always double).
@@ -167,7 +212,7 @@ static DevControlRec make_control_rec(int formulation, const pg_control_params& 
 static int configure_lateral(pg_handle* h, std::string* why) {
     DevCfg& C = h->dc; const pg_config* cfg = &h->cfg; const int N = C.N; const size_t cap = (size_t)cfg->batch_capacity;
     const bool want = h->lateral_solver == 1 || (h->lateral_solver != 2 && !(cfg->polish && N <= 20));
-    h->solve_lat = cfg->formulation == PG_DECOUPLED && want && !h->solve_quad;
+    h->solve_lat = cfg->formulation == PG_DECOUPLED && want;
     if (!h->solve_lat) { C.lat_pack = nullptr; return PG_OK; }
     if (!h->d_lat && hipMalloc((void**)&h->d_lat, cap * N * LATP * sizeof(real)) != hipSuccess) { *why = "hipMalloc failed for the packed lateral stage records"; return PG_ERR_HIP; }
     C.lat_pack = h->d_lat;
@@ -178,7 +223,7 @@ static int configure_lateral(pg_handle* h, std::string* why) {
     // (round 4: with the wall rows the two-slot register variant spills 720 B per lane since the warm start was added -- 1.57 ms at N = 30 against 1.36 ms through the
     // workspace; without them the registers still win, 0.94 against 1.01 ms)
     // (round 6: horizons of 17..32 intervals WITHOUT the wall rows used the two-slot register instantiation, k_solve_lat<2, .., false> -- 512 registers + 300 B of scratch, the
-    // largest code of the kernel.  With this round's edits hipcc 7.2 allocated one accumulation register to two live values there (rocgdb, precise memory violations on: the
+    // largest code of the kernel.  With this round's edits hipcc 7.2 allocated one accumulation register to two live values there (a debugger session, precise memory violations on: the
     // stage index of a slot visit read back from a76 was the high word of a double; memory access fault at the first launch).  Not a source bug that could be found: the
     // instantiation is retired, those horizons take the workspace variant like the longer ones -- and its straggler hand-over with it)
     h->lat_mem = N > 16 || h->lat_mem_forced;
@@ -244,7 +289,7 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_cp_sets, h->d_cp_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_ws4, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
@@ -305,12 +350,8 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
     ALLOC(h->d_sep, cap * 4, real); ALLOC(h->d_nodes, cap * NN * 10, real); ALLOC(h->d_qp, cap * C.qp_len, real);
     ALLOC(h->d_x7, cap * 7, real); ALLOC(h->d_vg8, cap * 8, real); ALLOC(h->d_Mb, cap * 4, real);
     ALLOC(h->d_solx, cap * NN * 8, real); ALLOC(h->d_sigma, cap * N * 3, real); ALLOC(h->d_mu, cap, real);
-    ALLOC(h->d_polish, cap, int); ALLOC(h->d_todo, cap + 8, int); ALLOC(h->d_lam, cap * N * 16, real); ALLOC(h->d_order, 2 * cap + 2, int); ALLOC(h->d_naux, cap * NN * 4, real); ALLOC(h->d_progress, cap / NODES_IPB + 8, int); ALLOC(h->d_active, cap * N, uint16_t);
-#ifdef PG_EXPERIMENTAL_SOLVE4
-    { const char* e = getenv("PG_SOLVER"); h->solve_quad = N <= 32 && e && strcmp(e, "quad") == 0; }   // experimental four-instances-per-wavefront kernel (experimental/pg_solve4.hip)
-    if (h->solve_quad) ALLOC(h->d_ws4, cap * ws4_len(N), real);
-#endif
-    if (cfg->walls) { ALLOC(h->d_walls, cap * N * 2, real); C.walls = 1; C.wall_weight = (real)cfg->wall_weight; C.wall_edges = h->d_walls; if (h->solve_quad) { g_create_error = "the experimental quad solver does not carry the wall rows"; free_all(h); delete h; return PG_ERR_INVALID; } }
+    ALLOC(h->d_polish, cap, int); ALLOC(h->d_todo, cap + CTL_WORDS, int); ALLOC(h->d_lam, cap * N * 16, real); ALLOC(h->d_order, 2 * cap + ORDER_CNT_WORDS, int); ALLOC(h->d_naux, cap * NN * 4, real); ALLOC(h->d_progress, pipe_words(h), int); ALLOC(h->d_active, cap * N, uint16_t);
+    if (cfg->walls) { ALLOC(h->d_walls, cap * N * 2, real); C.walls = 1; C.wall_weight = (real)cfg->wall_weight; C.wall_edges = h->d_walls; }
     ALLOC(h->d_pol_u2, cap * 2, real); ALLOC(h->d_pol_u, cap * 3, real); ALLOC(h->d_pol_src, cap, int);
     ALLOC(h->d_vmin, cap, real); ALLOC(h->d_breach, 2 * cap, int);
     // The lateral formulation has a solve kernel of its own (k_solve_lat, pg_solve_lat.hip) for horizons beyond 20 intervals.  Shorter ones -- the reference's on-vehicle
@@ -336,13 +377,13 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
         (void)hipMemcpy(h->d_prev_ts, ts.data(), ts.size() * 8, hipMemcpyHostToDevice);
         (void)hipMemcpy(h->d_dt, dt.data(), dt.size() * 8, hipMemcpyHostToDevice);
         (void)hipMemset(h->d_solved, 0, 2 * cap * sizeof(int));
-        (void)hipMemset(h->d_progress, 0, (cap / NODES_IPB + 8) * sizeof(int));
+        (void)hipMemset(h->d_progress, 0, pipe_words(h) * sizeof(int));
         (void)hipMemset(h->d_status, 0, cap * sizeof(int));
         (void)hipMemset(h->d_other, 0, cap * 4 * sizeof(real));
         (void)hipMemset(h->d_solx, 0, cap * NN * 8 * sizeof(real));
         (void)hipMemset(h->d_lam, 0, cap * N * 16 * sizeof(real));          // pg_get_multipliers promises 0 off the working set: the kernels write only the rows they own
         (void)hipMemset(h->d_active, 0, cap * N * sizeof(uint16_t));
-        (void)hipMemset(h->d_todo + cap, 0, 8 * sizeof(int));
+        (void)hipMemset(solve_ctl(h, 0), 0, CTL_WORDS * sizeof(int));
         if (hipDeviceSynchronize() != hipSuccess) { g_create_error = "initial fills failed"; free_all(h); delete h; return PG_ERR_HIP; }   // hipMemset may return before the fill has run
     }
     for (int i = 0; i < 4; i++) if (hipEventCreate(&h->ev[i]) != hipSuccess) { g_create_error = "hipEventCreate failed"; free_all(h); delete h; return PG_ERR_HIP; }
@@ -351,9 +392,6 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
     C.hji_seed = 0; C.clip_guess = 1; C.clip_stops = 0; C.ck_riccati = 1; C.warm_trivial_cold = 1; C.hji_rounds = 0;
     // horizons up to 32 intervals keep their dynamics blocks resident in LDS (one pass over the QP data); longer ones stream them through a 4-slot ring
     h->solve_ring = N > 32;
-#ifdef PG_EXPERIMENTAL_SOLVE4
-    h->solve4_lds = lds4_bytes(N);
-#endif
     h->solve_lds = (size_t)((h->solve_ring ? 4 : N) * SB + 10 * NN + 8 * NN + 2 * N + 2 * N + 16 * N + 4 * N + 8 * N + 2 * N + 8 * NN + 2 * N + 72 + 100 + 8 + 72 + 4 + 32 + 2 * N + 11 * N) * sizeof(real);
     if (h->solve_lds > 160 * 1024) { g_create_error = "horizon too long for LDS staging"; free_all(h); delete h; return PG_ERR_INVALID; }
     // hipFuncSetAttribute applies to the CURRENT DEVICE's copy of a kernel, and a later handle with a shorter horizon must not lower the limit an earlier handle of the same
@@ -522,7 +560,7 @@ int pg_get_option(pg_handle* h, const char* name, double* value) {
     if (strcmp(name, "lat_workspace") == 0) { *value = h->lat_mem ? 1.0 : 0.0; return PG_OK; }
     if (strcmp(name, "stat_whole_batch_solves") == 0) {      // counted ON THE DEVICE by the full k_solve whenever it takes the whole batch (SolveOut::mode): drains the stream
         HIPCHK(h, hipSetDevice(h->cfg.device)); HIPCHK(h, hipStreamSynchronize(h->stream));
-        int v = 0; HIPCHK(h, hipMemcpy(&v, h->d_todo + (size_t)h->cfg.batch_capacity + 5, sizeof(int), hipMemcpyDeviceToHost));
+        int v = 0; HIPCHK(h, hipMemcpy(&v, solve_ctl(h, CTL_WHOLE), sizeof(int), hipMemcpyDeviceToHost));
         *value = (double)v; return PG_OK;
     }
     if (strcmp(name, "lateral_solver_in_use") == 0) { *value = h->solve_lat ? 1.0 : (h->cfg.formulation == PG_DECOUPLED ? 2.0 : 0.0); return PG_OK; }
@@ -536,7 +574,7 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
     HIPCHK(h, hipSetDevice(h->cfg.device));                 // (a multi-GPU process: the copy below must not depend on whichever device happens to be current)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     int v = 0;
-    HIPCHK(h, hipMemcpy(&v, h->d_progress + (size_t)h->cfg.batch_capacity / NODES_IPB + 7, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&v, pipe_fallbacks(h), sizeof(int), hipMemcpyDeviceToHost));
     // the device word is a 32-bit counter of waiting wavefronts that gave up: the host keeps the 64-bit total and folds the device word into it (a wrap of the 32-bit
     // word between two calls would need 2^31 fall-backs -- at one per 20 ms wait, more than a year of nothing but fall-backs)
     h->fallback_total += (int64_t)(uint32_t)((uint32_t)v - (uint32_t)h->fallback_seen);
@@ -771,7 +809,6 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     HIPCHK(h, hipSetDevice(h->cfg.device));
     h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    int rc;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
         // from there with asynchronous copies ordered before the kernels on the handle's stream: no synchronisation on the way in.  A previous call's
@@ -791,14 +828,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
         if (o_) for (size_t i = 0; i < (size_t)B * 4; i++) ot[i] = (real)o_[i];
         memcpy(tt, t0, (size_t)B * 8);
         if (toff) memcpy(ft, toff, (size_t)B * 8);
-        HIPCHK(h, hipMemcpyAsync(h->d_state, st, (size_t)B * 6 * sizeof(real), kind, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_control, ct, (size_t)B * 3 * sizeof(real), kind, h->stream));
-        if (o_) HIPCHK(h, hipMemcpyAsync(h->d_other, ot, (size_t)B * 4 * sizeof(real), kind, h->stream));
-        else HIPCHK(h, hipMemsetAsync(h->d_other, 0, (size_t)B * 4 * sizeof(real), h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_t0, tt, (size_t)B * 8, kind, h->stream));
-        if (toff) HIPCHK(h, hipMemcpyAsync(h->d_toff, ft, (size_t)B * 8, kind, h->stream));
-        else HIPCHK(h, hipMemsetAsync(h->d_toff, 0xFF, (size_t)B * 8, h->stream));      // all-ones bit pattern is a NaN: path-tracking mode
-        return PG_OK;
+        state = st; control = ct; t0 = tt; if (o_) other = ot; if (toff) toff = ft;      // (the five copies below, from the staging buffer)
     }
     HIPCHK(h, hipMemcpyAsync(h->d_state, state, (size_t)B * 6 * sizeof(real), kind, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_control, control, (size_t)B * 3 * sizeof(real), kind, h->stream));
@@ -852,102 +882,122 @@ static bool pipeline_applies(const pg_handle* h) {
     const bool fuse_wanted = h->fuse == 1;
     return h->pipeline == 1 && C.formulation != PG_DECOUPLED && h->warm_B < h->B && h->B >= h->pipe_min && h->B <= h->pipe_max && C.Ns > 0 && C.Ns < C.N && !fuse_wanted;
 }
+// the nodes kernels' view of the launch order: what the previous solve left per instance, and where the order of this step is filed (order == nullptr: not filed)
+static OrderOut order_out(const pg_handle* h, int* order) {
+    OrderOut F{}; F.prev_status = h->d_status; F.prev_iters = h->d_iters; F.prev_polish = h->d_polish; F.order = order; F.cnt = order_cnt(h); F.slow = order_slow(h);
+    return F;
+}
+// The four branches of launch_nodes behind the projection.  staged / traj_lds: the trajectory travels through LDS; F: where the launch order of the step is filed.
+static int launch_nodes_decoupled(pg_handle* h, bool staged, size_t traj_lds) {
+    const int B = h->B;
+    auto kern = staged ? k_nodes_dec<true> : k_nodes_dec<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((B + NODES_DEC_IPB - 1) / NODES_DEC_IPB)), dim3(64), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_toff, h->d_sep, h->d_ts, h->d_dt, h->d_nodes, h->d_naux);      // (NODES_DEC_LPN lanes per instance)
+    LAUNCH_CHECK(h);
+    const long nn = (long)B * h->dc.NN;
+    hipLaunchKernelGGL(k_nodes_angles, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, (const int*)nullptr);
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
+// every instance takes the warm branch: lane = (instance, node)
+static int launch_nodes_warm(pg_handle* h, bool staged, size_t traj_lds, const OrderOut& F, bool recheck) {
+    const int B = h->B;
+    auto kern = staged ? k_nodes_warm<true> : k_nodes_warm<false>;
+    const long nth = (long)B * h->dc.NN;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nth + 255) / 256)), dim3(256), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_sep, h->d_ts, h->d_prev_ts, h->d_solx,
+                       h->d_nodes, F);
+    if (recheck) {          // behind a node step: instances without a solution are known on the device only (k_nodes_recheck, predicated on the word k_node_finish filed)
+        LAUNCH_CHECK(h);
+        const int* cold = node_cold(h, h->node_parity);
+        OrderOut Fr = order_out(h, nullptr); Fr.cnt = nullptr; Fr.slow = nullptr;      // (the launch order stays as k_nodes_warm filed it)
+        auto rk = staged ? k_nodes_recheck<true> : k_nodes_recheck<false>;
+        hipLaunchKernelGGL(rk, dim3((B + NODES_IPB - 1) / NODES_IPB), dim3(64), traj_lds, h->stream, h->dc, B, cold, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep,
+                           h->d_ts, h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, Fr, h->d_naux);
+        LAUNCH_CHECK(h);
+        hipLaunchKernelGGL(k_nodes_angles, dim3(64), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, cold);
+    }
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
+// nodes + update_QP! as one pipelined launch (k_nodes_linearize), its predicated repair, and the rate rows of a control-parameter library
+static int launch_nodes_pipelined(pg_handle* h, bool staged, size_t traj_lds, const OrderOut& F) {
+    const int B = h->B;
+    { int rc = launch_hji_rows_compute(h); if (rc) return rc; }      // (M, b) of the safety row: read by the lanes that linearise interval 0
+    const int lpi = h->lin_lpi, ipb = 64 / lpi;
+    const int nbn = (B + NODES_IPB - 1) / NODES_IPB, nbt = (B + ipb - 1) / ipb;
+    const size_t lds = traj_lds > 64 * 20 * sizeof(real) ? traj_lds : 64 * 20 * sizeof(real);
+    auto kern = lpi == 1 ? (staged ? k_nodes_linearize<true, 1> : k_nodes_linearize<false, 1>) : (staged ? k_nodes_linearize<true, 2> : k_nodes_linearize<false, 2>);
+#ifdef PG_F32
+    if (lpi == 1 && B >= 6144) kern = staged ? k_nodes_linearize<true, 1, 2> : k_nodes_linearize<false, 1, 2>;      // (two waves per SIMD once the linearisation is more than one round of them)
+#endif
+    int nzf = (1024 - nbn + nbt - 1) / nbt;               // short-horizon intervals that go first: one wavefront for every SIMD the recurrence leaves free
+    if (h->pipe_first > 0) nzf = h->pipe_first;
+    if (nzf > h->dc.Ns) nzf = h->dc.Ns;
+    if (nzf < 1) nzf = 1;
+    // nodes after which the recurrence publishes its progress (each publication is a device-scope release, i.e. an L2 write-back): every third node of the
+    // short horizon, every fifth of the long one (N = 30, Ns = 10: nodes 3, 6, 9, 14, 19, 24); the end of the recurrence always publishes
+    unsigned long long pub = 0ull;
+    for (int i = 1; i < h->dc.N - 2 && i < 63; i++)
+        if (i <= h->dc.Ns ? i % h->pipe_pub_short == 0 : (i - h->dc.Ns) % h->pipe_pub_long == h->pipe_pub_long - 1) pub |= 1ull << i;
+    if (h->pipe_fault) pub = 1ull << 63;                  // test hook: nothing is ever published (tests/test_gpu_api_contract.py)
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nbn + nbt * h->dc.N)), dim3(64), lds, h->stream, h->dc, B, nbn, nzf, pub, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
+                       h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, F, h->d_naux, h->d_progress, h->d_Mb, h->d_qp, pipe_fault_word(h, nbn), pipe_fallbacks(h));
+    LAUNCH_CHECK(h);
+    // repair, queued unconditionally and predicated on the device: if any waiting wavefront of the launch above gave up (its fault word, zeroed by the
+    // projection kernel of the step), the deferred angles and update_QP! of the WHOLE batch run launch per phase -- the same kernels on the same nodes, so the QP
+    // data are the ones the pipeline would have written.  When nothing gave up the two launches return at once (~3 us together).
+    {
+        const int* flt = pipe_fault_word(h, nbn);
+        hipLaunchKernelGGL(k_nodes_angles, dim3(64), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, flt);               // (small grids, striding over the work:
+        const long nz = (long)B * h->dc.Ns * lpi, nr = (long)B * (h->dc.N - h->dc.Ns) * lpi;                                           //  an empty launch is cheap)
+        const int nbz = (int)((nz + 63) / 64), nbr = (int)((nr + 63) / 64);
+        auto ksplit = lpi == 1 ? k_linearize_split<1> : k_linearize_split<2>;
+        hipLaunchKernelGGL(ksplit, dim3(512), dim3(64), 0, h->stream, h->dc, B, nbz, h->d_nodes, h->d_dt, h->d_Mb, h->d_qp, flt, nbz + nbr);
+    }
+    // Under a library (n_cp > 1) the pipelined launch has written the steering-rate rows of the QP data from DevCfg::cp -- pg_config.control, or the set of a
+    // one-set library installed earlier: NOT any instance's set -- and k_rate_limits overwrites them per instance, on the same stream, behind the predicated repair
+    // launches (which read the library themselves) and before anything reads the QP data.  Nothing may be queued between the two that consumes ddmin / ddmax.
+    if (h->dc.n_cp > 1) {
+        const long nt = (long)B * h->dc.N;
+        hipLaunchKernelGGL(k_rate_limits, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_qp);
+    }
+    h->lin_done = true; h->stat_pipelined++;
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
+// some instance is cold: the recurrence, one lane group per instance, then the deferred angles
+static int launch_nodes_cold(pg_handle* h, bool staged, size_t traj_lds, const OrderOut& F) {
+    const int B = h->B;
+    auto kern = staged ? k_nodes<true> : k_nodes<false>;
+    hipLaunchKernelGGL(kern, dim3((B + NODES_IPB - 1) / NODES_IPB), dim3(64), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
+                       h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, F, h->d_naux);
+    LAUNCH_CHECK(h);
+    const long nn = (long)B * h->dc.NN;
+    hipLaunchKernelGGL(k_nodes_angles, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes);
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
 static int launch_nodes(pg_handle* h, bool with_time_grid) {
     const int B = h->B;
     const bool recheck = h->node_recheck && !h->sg.capturing; h->node_recheck = false;
     const bool pipelined = with_time_grid && pipeline_applies(h);
     h->lin_done = false;
-    const size_t cap = (size_t)h->cfg.batch_capacity;
     const bool file = h->dc.formulation != PG_DECOUPLED && h->dc.polish;
-    int* const order_cnt = file ? h->d_order + cap : (int*)nullptr;            // the two counters of the launch order start from zero: the projection kernel clears them (no memset of its own)
-    int* const solve_ctl = h->d_todo + cap;                                    // ... and the control words of this step's solve launches (launch_solve): the to-do counter it counts into
+    int* const cnt = file ? order_cnt(h) : (int*)nullptr;                      // the two counters of the launch order start from zero: the projection kernel clears them (no memset of its own)
+    int* const ctl = solve_ctl(h, CTL_TODO0);                                  // ... and the control words of this step's solve launches (launch_solve_coupled): the to-do counter it counts into
     h->cnt_cleared = !h->sg.capturing;
     if (with_time_grid) hipLaunchKernelGGL(k_project<true>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep, h->d_t0, h->d_ts, h->d_dt, h->d_prev_ts,
-                                           pipelined ? h->d_progress : (int*)nullptr, (B + NODES_IPB - 1) / NODES_IPB + 1, order_cnt, solve_ctl, h->solve_parity);      // (+ 1: the fault word of the pipelined launch)
+                                           pipelined ? h->d_progress : (int*)nullptr, (B + NODES_IPB - 1) / NODES_IPB + 1, cnt, ctl, h->solve_parity);      // (+ 1: the fault word of the pipelined launch)
     else hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
-                            (double*)nullptr, (int*)nullptr, 0, order_cnt, solve_ctl, h->solve_parity);
+                            (double*)nullptr, (int*)nullptr, 0, cnt, ctl, h->solve_parity);
     LAUNCH_CHECK(h);
     const bool staged = h->dc.n_traj == 1 && h->traj_L <= 2048;
     const size_t traj_lds = staged ? (size_t)2 * h->traj_L * sizeof(real) : 0;
-    const dim3 grid((B + 63) / 64), block(64);
-    OrderOut F{h->d_status, h->d_iters, h->d_polish, file ? h->d_order : nullptr, h->d_order + cap, h->d_order + cap + 2};
+    const OrderOut F = order_out(h, file ? h->d_order : nullptr);
     h->order_B = file ? B : 0;
-    if (h->dc.formulation == PG_DECOUPLED) {
-        auto kern = staged ? k_nodes_dec<true> : k_nodes_dec<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((B + NODES_DEC_IPB - 1) / NODES_DEC_IPB)), block, traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_toff, h->d_sep, h->d_ts, h->d_dt, h->d_nodes, h->d_naux);      // (NODES_DEC_LPN lanes per instance)
-        LAUNCH_CHECK(h);
-        const long nn = (long)B * h->dc.NN;
-        hipLaunchKernelGGL(k_nodes_angles, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, (const int*)nullptr);
-    } else {
-        if (h->warm_B >= B) {           // every instance takes the warm branch: lane = (instance, node)
-            auto kern = staged ? k_nodes_warm<true> : k_nodes_warm<false>;
-            const long nth = (long)B * h->dc.NN;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((nth + 255) / 256)), dim3(256), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_sep, h->d_ts, h->d_prev_ts, h->d_solx,
-                               h->d_nodes, F);
-            if (recheck) {          // behind a node step: instances without a solution are known on the device only (k_nodes_recheck, predicated on the word k_node_finish filed)
-                LAUNCH_CHECK(h);
-                const int* cold = h->d_node + (size_t)6 * cap + h->node_parity;
-                const OrderOut Fr{h->d_status, h->d_iters, h->d_polish, nullptr, nullptr, nullptr};      // (the launch order stays as k_nodes_warm filed it)
-                auto rk = staged ? k_nodes_recheck<true> : k_nodes_recheck<false>;
-                hipLaunchKernelGGL(rk, dim3((B + NODES_IPB - 1) / NODES_IPB), block, traj_lds, h->stream, h->dc, B, cold, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep,
-                                   h->d_ts, h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, Fr, h->d_naux);
-                LAUNCH_CHECK(h);
-                hipLaunchKernelGGL(k_nodes_angles, dim3(64), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, cold);
-            }
-        } else if (pipelined) {
-            { int rc = launch_hji_rows_compute(h); if (rc) return rc; }      // (M, b) of the safety row: read by the lanes that linearise interval 0
-            const int lpi = h->lin_lpi, ipb = 64 / lpi;
-            const int nbn = (B + NODES_IPB - 1) / NODES_IPB, nbt = (B + ipb - 1) / ipb;
-            const size_t lds = traj_lds > 64 * 20 * sizeof(real) ? traj_lds : 64 * 20 * sizeof(real);
-            auto kern = lpi == 1 ? (staged ? k_nodes_linearize<true, 1> : k_nodes_linearize<false, 1>) : (staged ? k_nodes_linearize<true, 2> : k_nodes_linearize<false, 2>);
-#ifdef PG_F32
-            if (lpi == 1 && B >= 6144) kern = staged ? k_nodes_linearize<true, 1, 2> : k_nodes_linearize<false, 1, 2>;      // (two waves per SIMD once the linearisation is more than one round of them)
-#endif
-            int nzf = (1024 - nbn + nbt - 1) / nbt;               // short-horizon intervals that go first: one wavefront for every SIMD the recurrence leaves free
-            if (h->pipe_first > 0) nzf = h->pipe_first;
-            if (nzf > h->dc.Ns) nzf = h->dc.Ns;
-            if (nzf < 1) nzf = 1;
-            // nodes after which the recurrence publishes its progress (each publication is a device-scope release, i.e. an L2 write-back): every third node of the
-            // short horizon, every fifth of the long one (N = 30, Ns = 10: nodes 3, 6, 9, 14, 19, 24); the end of the recurrence always publishes
-            unsigned long long pub = 0ull;
-            for (int i = 1; i < h->dc.N - 2 && i < 63; i++)
-                if (i <= h->dc.Ns ? i % h->pipe_pub_short == 0 : (i - h->dc.Ns) % h->pipe_pub_long == h->pipe_pub_long - 1) pub |= 1ull << i;
-            if (h->pipe_fault) pub = 1ull << 63;                  // test hook: nothing is ever published (tests/test_gpu_api_contract.py)
-            hipLaunchKernelGGL(kern, dim3((unsigned)(nbn + nbt * h->dc.N)), block, lds, h->stream, h->dc, B, nbn, nzf, pub, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
-                               h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, F, h->d_naux, h->d_progress, h->d_Mb, h->d_qp, h->d_progress + nbn, h->d_progress + cap / NODES_IPB + 7);
-            LAUNCH_CHECK(h);
-            // repair, queued unconditionally and predicated on the device: if any waiting wavefront of the launch above gave up (its fault word, zeroed by the
-            // projection kernel of the step), the deferred angles and update_QP! of the WHOLE batch run launch per phase -- the same kernels on the same nodes, so the QP
-            // data are the ones the pipeline would have written.  When nothing gave up the two launches return at once (~3 us together).
-            {
-                const int* flt = h->d_progress + nbn;
-                const long nn = (long)B * h->dc.NN;
-                (void)nn;
-                hipLaunchKernelGGL(k_nodes_angles, dim3(64), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, flt);               // (small grids, striding over the work:
-                const long nz = (long)B * h->dc.Ns * lpi, nr = (long)B * (h->dc.N - h->dc.Ns) * lpi;                                           //  an empty launch is cheap)
-                const int nbz = (int)((nz + 63) / 64), nbr = (int)((nr + 63) / 64);
-                auto ksplit = lpi == 1 ? k_linearize_split<1> : k_linearize_split<2>;
-                hipLaunchKernelGGL(ksplit, dim3(512), dim3(64), 0, h->stream, h->dc, B, nbz, h->d_nodes, h->d_dt, h->d_Mb, h->d_qp, flt, nbz + nbr);
-            }
-            // Under a library (n_cp > 1) the pipelined launch has written the steering-rate rows of the QP data from DevCfg::cp -- pg_config.control, or the set of a
-            // one-set library installed earlier: NOT any instance's set -- and k_rate_limits overwrites them per instance, on the same stream, behind the predicated repair
-            // launches (which read the library themselves) and before anything reads the QP data.  Nothing may be queued between the two that consumes ddmin / ddmax.
-            if (h->dc.n_cp > 1) {
-                const long nt = (long)B * h->dc.N;
-                hipLaunchKernelGGL(k_rate_limits, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_qp);
-            }
-            h->lin_done = true; h->stat_pipelined++;
-        } else {
-            auto kern = staged ? k_nodes<true> : k_nodes<false>;
-            hipLaunchKernelGGL(kern, dim3((B + NODES_IPB - 1) / NODES_IPB), block, traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
-                               h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, F, h->d_naux);
-            LAUNCH_CHECK(h);
-            const long nn = (long)B * h->dc.NN;
-            hipLaunchKernelGGL(k_nodes_angles, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes);
-        }
-    }
-    LAUNCH_CHECK(h);
-    return PG_OK;
+    if (h->dc.formulation == PG_DECOUPLED) return launch_nodes_decoupled(h, staged, traj_lds);
+    if (h->warm_B >= B) return launch_nodes_warm(h, staged, traj_lds, F, recheck);
+    if (pipelined) return launch_nodes_pipelined(h, staged, traj_lds, F);
+    return launch_nodes_cold(h, staged, traj_lds, F);
 }
 static int launch_hji_lookup(pg_handle* h, int B, const real* x7_dev, real* out8_dev) {
     dim3 grid((unsigned)(((size_t)B * 16 + 255) / 256));
@@ -974,9 +1024,8 @@ static int launch_hji_order(pg_handle* h) {
     if (!h->has_hji) return PG_OK;
     const int B = h->B;
     if (h->dc.polish && h->order_B == B) {              // launch order again, now that the safety rows are known (k_order_hji)
-        const size_t cap = (size_t)h->cfg.batch_capacity;
-        OrderOut F{h->d_status, h->d_iters, h->d_polish, h->d_order, h->d_order + cap, h->d_order + cap + 2};
-        HIPCHK(h, hipMemsetAsync(h->d_order + cap, 0, 2 * sizeof(int), h->stream));
+        const OrderOut F = order_out(h, h->d_order);
+        HIPCHK(h, hipMemsetAsync(order_cnt(h), 0, ORDER_CNT_WORDS * sizeof(int), h->stream));
         hipLaunchKernelGGL(k_order_hji, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_control, h->d_Mb, F);
         LAUNCH_CHECK(h);
     }
@@ -1033,93 +1082,87 @@ int pg_update_qp(pg_handle* h) {
     if ((rc = launch_hji_rows(h))) return rc;
     return launch_linearize(h, B);
 }
-// k_solve over `n` instances on stream `st`: the whole batch in index order (order == nullptr) or the sub-range order[0..n) of the launch order
-static int launch_solve(pg_handle* h, hipStream_t st, const int* order, int n, unsigned long long* lat_prof = nullptr) {
-    SolveOut O{h->d_solx, h->d_sigma, h->d_u, h->d_status, h->d_iters, h->d_active, h->d_mu, h->d_solved, h->d_polish, h->d_lam, order, h->d_wfail, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-#ifdef PG_EXPERIMENTAL_SOLVE4
-    if (h->solve_quad) { hipLaunchKernelGGL((k_solve4<2, false>), dim3((h->B + 3) / 4), dim3(64), h->solve4_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, h->d_ws4, O, (unsigned long long*)nullptr); LAUNCH_CHECK(h); return PG_OK; }
-#endif
-    if (h->solve_lat) {      // lateral formulation: four instances per wavefront, always the whole batch in index order
-        const dim3 grid((unsigned)((h->B + 3) / 4));
-#ifdef PG_DIAG
-        if (h->dc.dbg_poison) {      // (every byte 0xFF: NaN in both precisions)
-            const size_t cap = (size_t)h->cfg.batch_capacity;
-            if (h->d_lat_ws) HIPCHK(h, hipMemsetAsync(h->d_lat_ws, 0xFF, lat_ws_bytes(cap), st));
-            if (h->d_lat_aux) HIPCHK(h, hipMemsetAsync(h->d_lat_aux, 0xFF, (cap + 1) * 64 * LAT_AUX * sizeof(real), st));
-            if (h->d_lat_spc) HIPCHK(h, hipMemsetAsync(h->d_lat_spc, 0xFF, lat_spc_bytes((int)cap, h->dc.N), st));
-        }
-#endif
-        const int slots = (h->dc.N + 15) / 16;
-#define PG_LAT_LAUNCH(NS, W, M) hipLaunchKernelGGL((k_solve_lat<NS, W, M>), grid, dim3(64), h->lat_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof)
-#define PG_LAT_LAUNCH_ANY() do { \
-        if (h->dc.walls) { if (h->lat_mem) PG_LAT_LAUNCH(1, true, true); else PG_LAT_LAUNCH(1, true, false); } \
-        else { if (h->lat_mem) PG_LAT_LAUNCH(1, false, true); else PG_LAT_LAUNCH(1, false, false); } } while (0)
-        // A batch in which every instance carries a previous solution (a closed loop after its first step) is solved in TWO launches: the warm attempts, then -- over the
-        // list the first launch leaves -- the cold solves of what they did not serve, packed four per wavefront again (see k_solve_lat).  Option "lat_split" = 0: one launch.
-        const bool two = h->split_lat && h->dc.polish && h->dc.warm_polish && h->dc.lat_warm_rounds > 0 && h->warm_B >= h->B && !lat_prof && !h->sg.capturing;
-        if (two) {
-            const size_t cap = (size_t)h->cfg.batch_capacity;
-            HIPCHK(h, hipMemsetAsync(h->d_todo + cap, 0, sizeof(int), st)); h->stat_lat_two++;
-            O.todo = h->d_todo; O.n_todo = h->d_todo + cap;
-            PG_LAT_LAUNCH_ANY();
-            LAUNCH_CHECK(h);
-            O.todo = nullptr; O.n_todo = nullptr; O.list = h->d_todo; O.n_list = h->d_todo + cap;
-            // (round 6) a list of up to `lat_single_max` instances is solved ONE instance per wavefront (see "small batches" below: 871 unserved instances of the benchmark
-            // batch 1.5 instead of 2.1 ms); the host does not know the length, so both arrangements are queued and the device word picks one (an idle launch: ~4 us)
-            if (h->lat_single_max > 0 && h->dc.N > 16) {
-                const unsigned nb1 = (unsigned)(h->B < h->lat_single_max ? h->B : h->lat_single_max);
-                const size_t lds1 = lat_lds_doubles(h->dc.N, 1) * sizeof(real);
-                O.list_lo = 0; O.list_hi = h->lat_single_max;
-                if (h->dc.walls) hipLaunchKernelGGL((k_solve_lat<1, true, false, 64, 0>), dim3(nb1), dim3(64), lds1, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-                else hipLaunchKernelGGL((k_solve_lat<1, false, false, 64, 0>), dim3(nb1), dim3(64), lds1, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-                LAUNCH_CHECK(h);
-                O.list_lo = h->lat_single_max + 1; O.list_hi = 0;
-            }
-        }
-        // Straggler hand-over (round 6, see k_solve_lat): a batch that starts cold interior points runs as TWO launches -- the first stops at a trip boundary once at most
-        // `lat_hand_target` instances of the batch are unfinished and files them, the second resumes those, ONE instance per wavefront (option "lat_handover" = 0: one launch
-        // as in round 5.  Measured and removed: resuming four per wavefront again, i.e. compaction only -- 3.34 against 3.25 ms for the single launch).  Only where the row
-        // state lives in the workspace (N > 32, or the wall rows), and not behind the warm attempts' own two launches.
-        // Small batches (round 6): with at most one wavefront per SIMD to fill anyway, every instance gets a wavefront of its own from the start -- the mapping of the resuming
-        // launch (lane = stage in the stage-parallel passes, one slot visit instead of four, the row state in registers): a trip costs 57 us instead of 84.  Not behind warm
-        // attempts (their launches are a round or two of the polish: four per wavefront is the cheaper shape there).
-        if (!two && !h->sg.capturing && h->warm_B < h->B && h->B <= h->lat_single_max && h->dc.N > 16) {
-            const size_t lds1 = lat_lds_doubles(h->dc.N, 1) * sizeof(real);
-            if (h->dc.walls) hipLaunchKernelGGL((k_solve_lat<1, true, false, 64, 0>), dim3((unsigned)h->B), dim3(64), lds1, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-            else hipLaunchKernelGGL((k_solve_lat<1, false, false, 64, 0>), dim3((unsigned)h->B), dim3(64), lds1, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-            LAUNCH_CHECK(h); h->stat_lat_single++;
-            return PG_OK;
-        }
-        const bool hand = h->lat_handover != 0 && h->lat_mem && !two && !h->sg.capturing && h->B >= h->lat_hand_batch ;
-        if (hand) {
-            const size_t cap = (size_t)h->cfg.batch_capacity;
-            int* const ctl = h->d_todo + cap;
-            HIPCHK(h, hipMemsetAsync(ctl, 0, 3 * sizeof(int), st)); h->stat_lat_hand++;      // [0] listed from the front, [1] finished instances, [2] listed from the back
-            O.todo = h->d_todo; O.n_todo = ctl; O.hand_mode = 1;
-            // When to stop the first launch.  Default: after a fixed number of trips (16 with the wall rows, 11 without: mean interior-point iterations + 2..3 on the benchmark
-            // batches) -- a rule that depends on the data only, so that the same call gives the same bits.  Option "lat_hand_target" > 0 stops when that few instances of the
-            // batch are unfinished instead (counted on the device: adapts to the batch -- vail + walls 2.09 against 2.19 ms -- but WHEN a wavefront sees the count is a matter
-            // of timing, and an instance resumed one trip earlier or later ends 1e-8 away: two verified KKT points of the same QP, not the same bits).
-            O.hand_cap = h->lat_hand_cap > 0 ? h->lat_hand_cap : ((h->lat_hand_target > 0 || h->lat_hand_work > 0) ? 0 : (h->dc.walls ? 16 : 11)); O.hand_target = h->lat_hand_target; O.hand_min = h->lat_hand_min; O.hand_done = ctl + 1; O.hand_work = h->lat_hand_work; O.hand_w0 = h->lat_hand_w0;
-            O.hand_r = h->d_hand_r; O.hand_i = h->d_hand_i;
-            if (h->dc.walls) hipLaunchKernelGGL((k_solve_lat<1, true, true, 16, 1>), grid, dim3(64), h->lat_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-            else hipLaunchKernelGGL((k_solve_lat<1, false, true, 16, 1>), grid, dim3(64), h->lat_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-            LAUNCH_CHECK(h);
-            O.todo = nullptr; O.n_todo = nullptr; O.list = h->d_todo; O.n_list = ctl; O.hand_mode = 2;
-            const size_t lds1 = lat_lds_doubles(h->dc.N, 1) * sizeof(real);          // one wavefront per listed instance; blocks beyond the list return at once
-            if (h->dc.walls) hipLaunchKernelGGL((k_solve_lat<1, true, false, 64, 2>), dim3((unsigned)h->B), dim3(64), lds1, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-            else hipLaunchKernelGGL((k_solve_lat<1, false, false, 64, 2>), dim3((unsigned)h->B), dim3(64), lds1, st, h->dc, h->B, h->d_qp, h->d_nodes, O, lat_prof);
-            LAUNCH_CHECK(h);
-            return PG_OK;
-        }
-        PG_LAT_LAUNCH_ANY();
-#undef PG_LAT_LAUNCH_ANY
-#undef PG_LAT_LAUNCH
+static const int* solve_order(const pg_handle* h) { return (h->dc.polish && h->order_B == h->B) ? h->d_order : nullptr; }      // the launch order the nodes kernels of this step filed (likely slow instances first)
+static void mark_solved(pg_handle* h) { if (h->B > h->warm_B) h->warm_B = h->B; }      // model_predictive_control.jl:76: solved = true for every instance of the batch
+static dim3 lat_grid4(const pg_handle* h) { return dim3((unsigned)((h->B + 3) / 4)); }                              // four instances per wavefront
+static size_t lat_lds1(const pg_handle* h) { return lat_lds_doubles(h->dc.N, 1) * sizeof(real); }                  // LDS of one instance per wavefront
+
+// ---- the arrangements of the lateral solve (k_solve_lat), always the whole batch in index order; the plain one (one launch, four instances per wavefront) closes launch_solve_lat ----
+// A batch in which every instance carries a previous solution (a closed loop after its first step) is solved in TWO launches: the warm attempts, then -- over the
+// list the first launch leaves -- the cold solves of what they did not serve, packed four per wavefront again (see k_solve_lat).  Option "lat_split" = 0: one launch.
+// (queues the warm attempts and leaves O in list mode for the plain launch behind them)
+static int lat_solve_warm_attempts(pg_handle* h, hipStream_t st, SolveOut& O, unsigned long long* prof) {
+    int* const n_list = solve_ctl(h, CTL_TODO0);
+    HIPCHK(h, hipMemsetAsync(n_list, 0, sizeof(int), st)); h->stat_lat_two++;
+    O.todo = h->d_todo; O.n_todo = n_list;
+    launch_k_solve_lat<LAT_MEM_ANY, 16, 0>(h, lat_grid4(h), h->lat_lds, st, O, prof);
+    LAUNCH_CHECK(h);
+    O.todo = nullptr; O.n_todo = nullptr; O.list = h->d_todo; O.n_list = n_list;
+    // (round 6) a list of up to `lat_single_max` instances is solved ONE instance per wavefront (see "small batches" below: 871 unserved instances of the benchmark
+    // batch 1.5 instead of 2.1 ms); the host does not know the length, so both arrangements are queued and the device word picks one (an idle launch: ~4 us)
+    if (h->lat_single_max > 0 && h->dc.N > 16) {
+        const unsigned nb1 = (unsigned)(h->B < h->lat_single_max ? h->B : h->lat_single_max);
+        O.list_lo = 0; O.list_hi = h->lat_single_max;
+        launch_k_solve_lat<0, 64, 0>(h, dim3(nb1), lat_lds1(h), st, O, prof);
         LAUNCH_CHECK(h);
-        return PG_OK;
+        O.list_lo = h->lat_single_max + 1; O.list_hi = 0;
     }
+    return PG_OK;
+}
+// Small batches (round 6): with at most one wavefront per SIMD to fill anyway, every instance gets a wavefront of its own from the start -- the mapping of the resuming
+// launch (lane = stage in the stage-parallel passes, one slot visit instead of four, the row state in registers): a trip costs 57 us instead of 84.  Not behind warm
+// attempts (their launches are a round or two of the polish: four per wavefront is the cheaper shape there).
+static int lat_solve_one_per_wavefront(pg_handle* h, hipStream_t st, const SolveOut& O, unsigned long long* prof) {
+    launch_k_solve_lat<0, 64, 0>(h, dim3((unsigned)h->B), lat_lds1(h), st, O, prof);
+    LAUNCH_CHECK(h); h->stat_lat_single++;
+    return PG_OK;
+}
+// Straggler hand-over (round 6, see k_solve_lat): a batch that starts cold interior points runs as TWO launches -- the first stops at a trip boundary once at most
+// `lat_hand_target` instances of the batch are unfinished and files them, the second resumes those, ONE instance per wavefront (option "lat_handover" = 0: one launch
+// as in round 5.  Measured and removed: resuming four per wavefront again, i.e. compaction only -- 3.34 against 3.25 ms for the single launch).  Only where the row
+// state lives in the workspace (N > 16, or option "lat_workspace"), and not behind the warm attempts' own two launches.
+static int lat_solve_handover(pg_handle* h, hipStream_t st, SolveOut O, unsigned long long* prof) {
+    int* const ctl = solve_ctl(h, CTL_TODO0);
+    HIPCHK(h, hipMemsetAsync(ctl, 0, (CTL_HAND_BACK + 1) * sizeof(int), st)); h->stat_lat_hand++;      // [0] listed from the front, [1] finished instances, [2] listed from the back
+    O.todo = h->d_todo; O.n_todo = ctl; O.hand_mode = 1;
+    // When to stop the first launch.  Default: after a fixed number of trips (16 with the wall rows, 11 without: mean interior-point iterations + 2..3 on the benchmark
+    // batches) -- a rule that depends on the data only, so that the same call gives the same bits.  Option "lat_hand_target" > 0 stops when that few instances of the
+    // batch are unfinished instead (counted on the device: adapts to the batch -- vail + walls 2.09 against 2.19 ms -- but WHEN a wavefront sees the count is a matter
+    // of timing, and an instance resumed one trip earlier or later ends 1e-8 away: two verified KKT points of the same QP, not the same bits).
+    O.hand_cap = h->lat_hand_cap > 0 ? h->lat_hand_cap : ((h->lat_hand_target > 0 || h->lat_hand_work > 0) ? 0 : (h->dc.walls ? 16 : 11)); O.hand_target = h->lat_hand_target; O.hand_min = h->lat_hand_min; O.hand_done = solve_ctl(h, CTL_TODO1); O.hand_work = h->lat_hand_work; O.hand_w0 = h->lat_hand_w0;
+    O.hand_r = h->d_hand_r; O.hand_i = h->d_hand_i;
+    launch_k_solve_lat<1, 16, 1>(h, lat_grid4(h), h->lat_lds, st, O, prof);
+    LAUNCH_CHECK(h);
+    O.todo = nullptr; O.n_todo = nullptr; O.list = h->d_todo; O.n_list = ctl; O.hand_mode = 2;
+    launch_k_solve_lat<0, 64, 2>(h, dim3((unsigned)h->B), lat_lds1(h), st, O, prof);          // one wavefront per listed instance; blocks beyond the list return at once
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
+// lateral formulation: four instances per wavefront unless an arrangement above says otherwise
+static int launch_solve_lat(pg_handle* h, hipStream_t st, unsigned long long* lat_prof) {
+    SolveOut O = solve_out(h, nullptr);
+#ifdef PG_DIAG
+    if (h->dc.dbg_poison) {      // (every byte 0xFF: NaN in both precisions)
+        const size_t cap = (size_t)h->cfg.batch_capacity;
+        if (h->d_lat_ws) HIPCHK(h, hipMemsetAsync(h->d_lat_ws, 0xFF, lat_ws_bytes(cap), st));
+        if (h->d_lat_aux) HIPCHK(h, hipMemsetAsync(h->d_lat_aux, 0xFF, (cap + 1) * 64 * LAT_AUX * sizeof(real), st));
+        if (h->d_lat_spc) HIPCHK(h, hipMemsetAsync(h->d_lat_spc, 0xFF, lat_spc_bytes((int)cap, h->dc.N), st));
+    }
+#endif
+    const bool two = h->split_lat && h->dc.polish && h->dc.warm_polish && h->dc.lat_warm_rounds > 0 && h->warm_B >= h->B && !lat_prof && !h->sg.capturing;
+    if (two) { const int rc = lat_solve_warm_attempts(h, st, O, lat_prof); if (rc) return rc; }
+    else if (!h->sg.capturing && h->warm_B < h->B && h->B <= h->lat_single_max && h->dc.N > 16) return lat_solve_one_per_wavefront(h, st, O, lat_prof);
+    else if (!h->sg.capturing && h->lat_handover != 0 && h->lat_mem && h->B >= h->lat_hand_batch) return lat_solve_handover(h, st, O, lat_prof);
+    launch_k_solve_lat<LAT_MEM_ANY, 16, 0>(h, lat_grid4(h), h->lat_lds, st, O, lat_prof);
+    LAUNCH_CHECK(h);
+    return PG_OK;
+}
+// coupled formulation (and the lateral one embedded in it), one wavefront per instance: `n` instances, the whole batch in index order (order == nullptr) or the
+// sub-range order[0..n) of the launch order
+static int launch_solve_coupled(pg_handle* h, hipStream_t st, const int* order, int n) {
+    SolveOut O = solve_out(h, order);
     if (h->u_direct) { O.u_out2 = h->u_direct; h->u_written = true; }      // (every k_solve instantiation below writes the caller's array itself)
-    if (h->solve_ring) hipLaunchKernelGGL((k_solve<false, true, false>), dim3(n), dim3(64), h->solve_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, (unsigned long long*)nullptr, h->d_dt, h->d_Mb);
+    if (h->solve_ring) launch_k_solve<false, true, false>(h, st, n, O);
     else if (h->split_solve && h->dc.polish && (h->dc.cold_guess > 0 || h->dc.warm_polish) && !h->has_hji && !h->sg.capturing) {
         // Two launches: the rounds-only instantiation (no scratch: the interior point's state and code are not in it) serves the instances an active-set attempt
         // verifies -- all of them on the tracking batches --; what it leaves (SolveOut::todo) goes through the full kernel in list mode, its blocks returning at once
@@ -1132,30 +1175,28 @@ static int launch_solve(pg_handle* h, hipStream_t st, const int* order, int n, u
         // same launches whatever the host's timing (round 4 read a pinned copy of the count that an asynchronous copy filled "whenever it arrived").  Two counters are used
         // alternately -- this launch counts into one while the other still holds the previous launch's count --; the projection kernel of the step zeroes the one about to be
         // used (a solve without a nodes phase in front -- replayed QPs -- zeroes it here).
-        const size_t cap = (size_t)h->cfg.batch_capacity;
-        int* const ctl = h->d_todo + cap; int* const cnt = ctl + h->solve_parity; const int* const prev = ctl + (h->solve_parity ^ 1);
+        int* const cnt = solve_ctl(h, CTL_TODO0 + h->solve_parity); const int* const prev = solve_ctl(h, CTL_TODO0 + (h->solve_parity ^ 1));
         if (!h->cnt_cleared) HIPCHK(h, hipMemsetAsync(cnt, 0, sizeof(int), st));
         h->cnt_cleared = false; h->solve_parity ^= 1; h->stat_split++;
-        O.todo = h->d_todo; O.n_todo = cnt; O.mode = prev; O.n_whole = ctl + 5;
-        hipLaunchKernelGGL((k_solve<false, false, false, false>), dim3(n), dim3(64), h->solve_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, (unsigned long long*)nullptr, h->d_dt, h->d_Mb);
+        O.todo = h->d_todo; O.n_todo = cnt; O.mode = prev; O.n_whole = solve_ctl(h, CTL_WHOLE);
+        launch_k_solve<false, false, false, false>(h, st, n, O);
         LAUNCH_CHECK(h);
         SolveOut O2 = O; O2.todo = nullptr; O2.list = h->d_todo; O2.n_list = cnt;      // (order_in stays: the whole-batch mode uses the launch order)
-        hipLaunchKernelGGL((k_solve<false, false, false, true>), dim3(n), dim3(64), h->solve_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O2, (unsigned long long*)nullptr, h->d_dt, h->d_Mb);
+        launch_k_solve<false, false, false, true>(h, st, n, O2);
     }
     else {
         h->stat_single++;
-        hipLaunchKernelGGL((k_solve<false, false, false>), dim3(n), dim3(64), h->solve_lds, st, h->dc, h->B, h->d_qp, h->d_nodes, O, (unsigned long long*)nullptr, h->d_dt, h->d_Mb);
+        launch_k_solve<false, false, false>(h, st, n, O);
     }
     LAUNCH_CHECK(h);
     return PG_OK;
 }
+static int launch_solve(pg_handle* h, hipStream_t st, const int* order, int n) { return h->solve_lat ? launch_solve_lat(h, st, nullptr) : launch_solve_coupled(h, st, order, n); }
 int pg_solve(pg_handle* h) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->qp_stale) { h->err = "pg_solve: the lateral solver was switched (pg_set_option \"lateral_solver\") after the last update_QP!: call pg_update_qp first"; return PG_ERR_STATE; }
-    // launch order: the one the nodes kernels of this step filed (likely slow instances first)
-    const bool use_order = h->dc.polish && h->order_B == h->B;
-    if ((rc = launch_solve(h, h->stream, use_order ? h->d_order : nullptr, h->B))) return rc;
-    if (h->B > h->warm_B) h->warm_B = h->B;           // model_predictive_control.jl:76: solved = true for every instance of the batch
+    if ((rc = launch_solve(h, h->stream, solve_order(h), h->B))) return rc;
+    mark_solved(h);
     return PG_OK;
 }
 // update_QP! + solve! of one step.  For the coupled formulation with N <= 32 both run in ONE kernel (k_solve<.., FUSE = true>): the wavefront that solves an instance
@@ -1169,28 +1210,19 @@ int pg_solve(pg_handle* h) {
 // the two-kernel sequence wins there too (0.91 vs 0.99, 1.06 vs 1.11, 0.87 vs 0.98 ms per closed-loop step).  Hence OFF by default (pg_set_fusion:
 // 0 never, 1 always, 2 for all-warm batches of >= 1024 instances).
 static int update_and_solve(pg_handle* h, hipEvent_t after_update) {
-    int rc;
     const bool want = h->fuse == 1 || (h->fuse == 2 && h->warm_B >= h->B && h->B >= 1024);
-    const bool fused = want && h->dc.formulation != PG_DECOUPLED && !h->solve_ring && 2 * h->dc.N <= 64 && !h->solve_quad;
-    if (h->lin_done) {                   // the QP data of this step are already there (k_nodes_linearize)
-        h->lin_done = false;
-        if ((rc = launch_hji_order(h))) return rc;
-        if (after_update) HIPCHK(h, hipEventRecord(after_update, h->stream));
-        return pg_solve(h);
-    }
-    if (!fused) {
-        if ((rc = pg_update_qp(h))) return rc;
-        if (after_update) HIPCHK(h, hipEventRecord(after_update, h->stream));
-        return pg_solve(h);
-    }
-    if ((rc = launch_hji_rows(h))) return rc;
+    const bool lin_done = h->lin_done;      // the QP data of this step are already there (k_nodes_linearize)
+    const bool fused = !lin_done && want && h->dc.formulation != PG_DECOUPLED && !h->solve_ring && 2 * h->dc.N <= 64;
+    h->lin_done = false;
+    const int rc = lin_done ? launch_hji_order(h) : (fused ? launch_hji_rows(h) : pg_update_qp(h));
+    if (rc) return rc;
     if (after_update) HIPCHK(h, hipEventRecord(after_update, h->stream));
-    const bool use_order = h->dc.polish && h->order_B == h->B;
-    SolveOut O{h->d_solx, h->d_sigma, h->d_u, h->d_status, h->d_iters, h->d_active, h->d_mu, h->d_solved, h->d_polish, h->d_lam, use_order ? h->d_order : nullptr, h->d_wfail, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!fused) return pg_solve(h);
+    SolveOut O = solve_out(h, solve_order(h));
     if (h->u_direct) { O.u_out2 = h->u_direct; h->u_written = true; }
-    hipLaunchKernelGGL((k_solve<false, false, true>), dim3(h->B), dim3(64), h->solve_lds, h->stream, h->dc, h->B, h->d_qp, h->d_nodes, O, (unsigned long long*)nullptr, h->d_dt, h->d_Mb);
+    launch_k_solve<false, false, true>(h, h->stream, h->B, O);
     LAUNCH_CHECK(h);
-    if (h->B > h->warm_B) h->warm_B = h->B;
+    mark_solved(h);
     return PG_OK;
 }
 #ifdef PG_DIAG
@@ -1201,21 +1233,16 @@ int pg_debug_solve_cycles(pg_handle* h, unsigned long long* out) {
     unsigned long long* d = nullptr;
     HIPCHK(h, hipMalloc((void**)&d, ((size_t)h->B * 9 + 1024) * 8));
     HIPCHK(h, hipMemset(d, 0, ((size_t)h->B * 9 + 1024) * 8));
-    SolveOut O{h->d_solx, h->d_sigma, h->d_u, h->d_status, h->d_iters, h->d_active, h->d_mu, h->d_solved, h->d_polish, h->d_lam,
-               (h->dc.polish && h->order_B == h->B) ? h->d_order : nullptr, h->d_wfail, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};            // (the launch order pg_solve would use: the timeline is the product's)
-    if (h->solve_lat) { if ((rc = launch_solve(h, h->stream, nullptr, h->B, d))) { (void)hipFree(d); return rc; } } else
-#ifdef PG_EXPERIMENTAL_SOLVE4
-    if (h->solve_quad) hipLaunchKernelGGL((k_solve4<2, true>), dim3((h->B + 3) / 4), dim3(64), h->solve4_lds, h->stream, h->dc, h->B, h->d_qp, h->d_nodes, h->d_ws4, O, d);
-    else
-#endif
-    if (h->solve_ring) hipLaunchKernelGGL((k_solve<true, true, false>), dim3(h->B), dim3(64), h->solve_lds, h->stream, h->dc, h->B, h->d_qp, h->d_nodes, O, d, h->d_dt, h->d_Mb);
+    SolveOut O = solve_out(h, solve_order(h));            // (the launch order pg_solve would use: the timeline is the product's)
+    if (h->solve_lat) { if ((rc = launch_solve_lat(h, h->stream, d))) { (void)hipFree(d); return rc; } }
+    else if (h->solve_ring) launch_k_solve<true, true, false>(h, h->stream, h->B, O, d);
     else if (h->debug_timeline) {      // the product's kernel (the rounds-only instantiation of the split launch): timeline only
-        int* const cnt = h->d_todo + (size_t)h->cfg.batch_capacity + 4;
+        int* const cnt = solve_ctl(h, CTL_TIMELINE);
         HIPCHK(h, hipMemsetAsync(cnt, 0, sizeof(int), h->stream));
         O.todo = h->d_todo; O.n_todo = cnt;
-        hipLaunchKernelGGL((k_solve<false, false, false, false>), dim3(h->B), dim3(64), h->solve_lds, h->stream, h->dc, h->B, h->d_qp, h->d_nodes, O, d, h->d_dt, h->d_Mb);
+        launch_k_solve<false, false, false, false>(h, h->stream, h->B, O, d);
     }
-    else hipLaunchKernelGGL((k_solve<true, false, false>), dim3(h->B), dim3(64), h->solve_lds, h->stream, h->dc, h->B, h->d_qp, h->d_nodes, O, d, h->d_dt, h->d_Mb);
+    else launch_k_solve<true, false, false>(h, h->stream, h->B, O, d);
     LAUNCH_CHECK(h);
     HIPCHK(h, hipMemcpy(out, d, ((size_t)h->B * 9 + 1024) * 8, hipMemcpyDeviceToHost));      // out: [B][6] cycles + 1024-double trace of the "diag_instance" instance + [B][3] timeline (k_solve: entry, exit on the 100 MHz wall clock, HW_ID | XCC_ID << 32)
     (void)hipFree(d);
@@ -1287,6 +1314,16 @@ int pg_step_dev(pg_handle* h, void* u_out_dev) {
 }
 // the loop's clock (:87): t takes the elements of 0:dt:trajectory.t[end], here shifted by each instance's start time.  A call continues the clock of the previous one
 // (same dt, same path end, no pg_set_inputs in between); otherwise it restarts from the times the inputs carry (and so does the safety summary)
+// the compute calls of one closed-loop step (model_predictive_control.jl:90-93; the time grid rides in the projection launch): fusion, pipelining and the split solve as pg_step_dev has them
+static int step_compute(pg_handle* h) { const int rc = launch_nodes(h, true); return rc ? rc : update_and_solve(h, nullptr); }
+// the arguments the rollouts share (`who`: the entry point, for the message; a rollout without a human passes mode 0)
+static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, double dt, int32_t human_mode, const void* human_u_dev) {
+    const std::string w(who);
+    REQUIRE(h, steps >= 1 && dt > 0.0, w + ": steps >= 1 and dt > 0 required");
+    REQUIRE(h, human_mode >= 0 && human_mode <= 2, w + ": human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
+    REQUIRE(h, human_mode != 2 || human_u_dev, w + ": human_mode 2 needs human_u_dev [steps][B][2]");
+    return PG_OK;
+}
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -1296,14 +1333,14 @@ static int clock_start(pg_handle* h, double dt) {
 }
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev_, void* control_hist_dev_) {
     int rc = check_ready(h); if (rc) return rc;
-    REQUIRE(h, steps >= 1 && dt > 0.0, "pg_simulate_dev: steps >= 1 and dt > 0 required");
+    if ((rc = check_rollout_args(h, "pg_simulate_dev", steps, dt, 0, nullptr))) return rc;
     const int B = h->B;
     real* state_hist_dev = (real*)state_hist_dev_; real* control_hist_dev = (real*)control_hist_dev_;
     if ((rc = clock_start(h, dt))) return rc;                           // the loop's clock (:87)
     for (int k = 0; k < steps; k++) {
         if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(state_hist_dev + (size_t)k * B * 6, h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // push!(qs, state) :88
         if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(control_hist_dev + (size_t)k * B * 3, h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream)); // push!(us, control) :89
-        if ((rc = launch_nodes(h, true)) || (rc = update_and_solve(h, nullptr))) return rc;          // :90-93 (time grid fused into the projection launch)
+        if ((rc = step_compute(h))) return rc;                                                        // :90-93
         h->sim_idx++;                                                                                                                                         // (t0 now holds element sim_idx of the clock)
         hipLaunchKernelGGL(k_advance, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx);      // :94-95
         LAUNCH_CHECK(h);
@@ -1317,15 +1354,13 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
                            void* state_hist_dev_, void* control_hist_dev_, void* other_hist_dev_, void* human_hist_dev_, void* V_hist_dev_, int32_t* source_hist_dev) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED) { h->err = "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row"; return PG_ERR_STATE; }
-    REQUIRE(h, steps >= 1 && dt > 0.0, "pg_simulate_safety_dev: steps >= 1 and dt > 0 required");
-    REQUIRE(h, human_mode >= 0 && human_mode <= 2, "pg_simulate_safety_dev: human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
-    REQUIRE(h, human_mode != 2 || human_u_dev_, "pg_simulate_safety_dev: human_mode 2 needs human_u_dev [steps][B][2]");
+    if ((rc = check_rollout_args(h, "pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev_))) return rc;
     const int B = h->B; const size_t Bz = (size_t)B;
     const real* human_u_dev = (const real*)human_u_dev_;
     real *sh = (real*)state_hist_dev_, *ch = (real*)control_hist_dev_, *oh = (real*)other_hist_dev_, *hh = (real*)human_hist_dev_, *vh = (real*)V_hist_dev_;
     if ((rc = clock_start(h, dt))) return rc;
     for (int k = 0; k < steps; k++) {
-        if ((rc = launch_nodes(h, true)) || (rc = update_and_solve(h, nullptr))) return rc;          // :90-93
+        if ((rc = step_compute(h))) return rc;                                                        // :90-93
         const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
         h->sim_idx++;
         SafetyIO io{human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr, sh ? sh + (size_t)k * Bz * 6 : nullptr, ch ? ch + (size_t)k * Bz * 3 : nullptr,
@@ -1369,8 +1404,8 @@ static int node_prepare(pg_handle* h) {
         take(K.k_ts, cap * NN); take(K.k_dt, cap * N); take(K.k_prev_ts, cap * NN);
         take(K.k_solx, cap * NN * 8); take(K.k_sigma, cap * N * 3); take(K.k_lam, cap * N * 16); take(K.k_u, cap * 3); take(K.k_mu, cap); take(K.k_aux, cap * naux_cap);
         take(K.k_solved, cap); take(K.k_wfail, cap); take(K.k_status, cap); take(K.k_iters, cap); take(K.k_polish, cap); take(K.k_active, cap * N);
-        HIPCHK(h, hipMalloc((void**)&h->d_node, (cap * 6 + 2) * sizeof(int)));
-        HIPCHK(h, hipMemset(h->d_node, 0, (cap * 6 + 2) * sizeof(int)));
+        HIPCHK(h, hipMalloc((void**)&h->d_node, (cap * 6 + NODE_COLD_WORDS) * sizeof(int)));
+        HIPCHK(h, hipMemset(h->d_node, 0, (cap * 6 + NODE_COLD_WORDS) * sizeof(int)));
         HIPCHK(h, hipMalloc((void**)&h->d_applied, cap * 3 * sizeof(real)));
         HIPCHK(h, hipMemset(h->d_applied, 0, cap * 3 * sizeof(real)));
     }
@@ -1387,22 +1422,15 @@ static int node_prepare(pg_handle* h) {
     return PG_OK;
 }
 static int node_gate(pg_handle* h, const uint8_t* pre_flag) {
-    const int B = h->B; const size_t cap = (size_t)h->cfg.batch_capacity;
+    const int B = h->B;
     hipLaunchKernelGGL(k_node_gate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, h->d_state, h->d_t0, h->d_toff, h->d_tend, pre_flag, h->d_node,
-                       h->d_node + 6 * cap + (h->node_parity ^ 1), h->kv);
+                       node_cold(h, h->node_parity ^ 1), h->kv);
     LAUNCH_CHECK(h);
     return PG_OK;
 }
-// the compute calls of the step, as pg_simulate_dev / pg_simulate_safety_dev make them (:94-112)
-static int node_compute(pg_handle* h) {
-    int rc;
-    if ((rc = launch_nodes(h, true)) || (rc = update_and_solve(h, nullptr))) return rc;
-    return PG_OK;
-}
 static NodeIO node_io(pg_handle* h) {
-    const size_t cap = (size_t)h->cfg.batch_capacity;
     NodeIO io{};
-    io.gate = h->d_node; io.heartbeat = h->d_node + cap; io.counts = h->d_node + 2 * cap; io.cold = h->d_node + 6 * cap + (h->node_parity ^ 1); io.applied = h->d_applied; io.sep = h->d_sep;
+    io.gate = h->d_node; io.heartbeat = node_heartbeat(h); io.counts = node_counts(h); io.cold = node_cold(h, h->node_parity ^ 1); io.applied = h->d_applied; io.sep = h->d_sep;
     return io;
 }
 static void node_done(pg_handle* h) { h->node_parity ^= 1; h->node_recheck = true; h->node_fresh = false; }
@@ -1410,7 +1438,7 @@ static void node_done(pg_handle* h) { h->node_parity ^= 1; h->node_recheck = tru
 int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_flag_dev, void* cmd_out_dev, void* se_out_dev, int32_t* event_dev) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_node_step_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
-    if ((rc = node_prepare(h)) || (rc = node_gate(h, pre_flag_dev)) || (rc = node_compute(h))) return rc;
+    if ((rc = node_prepare(h)) || (rc = node_gate(h, pre_flag_dev)) || (rc = step_compute(h))) return rc;
     NodeIO io = node_io(h);
     io.cmd_out = (real*)cmd_out_dev; io.se_out = (real*)se_out_dev; io.event = event_dev;
     const int B = h->B;
@@ -1426,9 +1454,7 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
                          void* state_hist_dev_, void* applied_hist_dev_, int32_t* event_hist_dev, void* V_hist_dev_) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
-    REQUIRE(h, steps >= 1 && dt > 0.0, "pg_simulate_node_dev: steps >= 1 and dt > 0 required");
-    REQUIRE(h, human_mode >= 0 && human_mode <= 2, "pg_simulate_node_dev: human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
-    REQUIRE(h, human_mode != 2 || human_u_dev_, "pg_simulate_node_dev: human_mode 2 needs human_u_dev [steps][B][2]");
+    if ((rc = check_rollout_args(h, "pg_simulate_node_dev", steps, dt, human_mode, human_u_dev_))) return rc;
     if ((rc = node_prepare(h))) return rc;
     const int B = h->B; const size_t Bz = (size_t)B;
     const real* human_u_dev = (const real*)human_u_dev_;
@@ -1438,7 +1464,7 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
     if (restart) HIPCHK(h, hipMemcpyAsync(h->d_applied, h->d_control, Bz * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // the applied command starts as the message
     const int has = (int)(h->has_hji && h->dc.formulation == PG_COUPLED);
     for (int k = 0; k < steps; k++) {
-        if ((rc = node_gate(h, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr)) || (rc = node_compute(h))) return rc;
+        if ((rc = node_gate(h, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr)) || (rc = step_compute(h))) return rc;
         const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
         h->sim_idx++;
         NodeIO io = node_io(h);
@@ -1457,10 +1483,10 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
 int pg_get_node_state(pg_handle* h, double* applied, int32_t* heartbeat, int32_t* counts) {
     int rc = check_ready(h); if (rc) return rc;
     if ((rc = node_prepare(h))) return rc;
-    const size_t B = h->B, cap = (size_t)h->cfg.batch_capacity;
-    if ((rc = down(h, applied, h->d_applied, B * 3)) || (rc = down_raw(h, heartbeat, h->d_node + cap, B * sizeof(int32_t)))) return rc;
+    const size_t B = h->B;
+    if ((rc = down(h, applied, h->d_applied, B * 3)) || (rc = down_raw(h, heartbeat, node_heartbeat(h), B * sizeof(int32_t)))) return rc;
     if (h->node_fresh) { if (counts) memset(counts, 0, B * 4 * sizeof(int32_t)); return PG_OK; }      // no node step since the clock (re)started
-    return down_raw(h, counts, h->d_node + 2 * cap, B * 4 * sizeof(int32_t));
+    return down_raw(h, counts, node_counts(h), B * 4 * sizeof(int32_t));
 }
 int pg_simulate_clock(pg_handle* h, double dt, int32_t steps, int32_t B, const double* t_start, double* out) {
 #pragma clang fp contract(off)
@@ -1608,26 +1634,25 @@ int pg_get_path_coordinates(pg_handle* h, double* sep) {
     for (size_t b = 0; b < B; b++) for (int k = 0; k < 3; k++) sep[b * 3 + k] = s4[b * 4 + k];
     return PG_OK;
 }
+// the last update_QP! of a lateral handle may have written the packed records only: the embedded block now, from the same nodes
+static int embed_lateral_qp(pg_handle* h) {
+    if (h->dc.formulation != PG_DECOUPLED || h->qp_embedded) return PG_OK;
+    const long nt = (long)h->B * h->dc.N;
+    hipLaunchKernelGGL(k_qp_dec, dim3((unsigned)((nt + 127) / 128)), dim3(128), 0, h->stream, h->dc, h->B, h->d_nodes, h->d_dt, h->d_qp, 1);
+    LAUNCH_CHECK(h);
+    h->qp_embedded = true;
+    return PG_OK;
+}
 int pg_get_qp(pg_handle* h, int32_t b0, int32_t n, double* out) {
     int rc = check_ready(h); if (rc) return rc;
     REQUIRE(h, out && b0 >= 0 && n >= 1 && b0 + n <= h->B, "pg_get_qp: range outside the batch");
-    if (h->dc.formulation == PG_DECOUPLED && !h->qp_embedded) {      // the last update_QP! of this lateral handle wrote the packed records only: the embedded block now, from the same nodes
-        const long nt = (long)h->B * h->dc.N;
-        hipLaunchKernelGGL(k_qp_dec, dim3((unsigned)((nt + 127) / 128)), dim3(128), 0, h->stream, h->dc, h->B, h->d_nodes, h->d_dt, h->d_qp, 1);
-        LAUNCH_CHECK(h);
-        h->qp_embedded = true;
-    }
+    if ((rc = embed_lateral_qp(h))) return rc;
     return down(h, out, h->d_qp + (size_t)b0 * h->dc.qp_len, (size_t)n * h->dc.qp_len);
 }
 int pg_set_qp(pg_handle* h, int32_t b0, int32_t n, const double* in) {
     int rc = check_ready(h); if (rc) return rc;
     REQUIRE(h, in && b0 >= 0 && n >= 1 && b0 + n <= h->B, "pg_set_qp: range outside the batch");
-    if (h->dc.formulation == PG_DECOUPLED && !h->qp_embedded) {      // (a partial install on top of a step that wrote the packed records only: complete the embedded block first)
-        const long nt_ = (long)h->B * h->dc.N;
-        hipLaunchKernelGGL(k_qp_dec, dim3((unsigned)((nt_ + 127) / 128)), dim3(128), 0, h->stream, h->dc, h->B, h->d_nodes, h->d_dt, h->d_qp, 1);
-        LAUNCH_CHECK(h);
-        h->qp_embedded = true;
-    }
+    if ((rc = embed_lateral_qp(h))) return rc;      // (a partial install on top of a step that wrote the packed records only: complete the embedded block first)
     if ((rc = up(h, h->d_qp + (size_t)b0 * h->dc.qp_len, in, (size_t)n * h->dc.qp_len))) return rc;
     if (h->solve_lat) {      // k_solve_lat reads the packed stage records: refresh them from the installed block
         const long nt = (long)n * h->dc.N;

@@ -928,6 +928,10 @@ PG_DEV void advance_ego(const DevCfg& C, real* x, real d, real Fx, real h, int n
     }
 }
 
+// the loop's clock of instance b moves to element idx of its range (see k_advance: t)
+PG_DEV void clock_next(const DevCfg& C, tdouble dtp, tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, const JlRange& clk, int idx, int b) {
+    t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
+}
 // ------------------------------------------------------------------------------------------------------------------
 // Closed-loop plant step of `simulate` (model_predictive_control.jl:94-95), lane = instance:
 //   state   <- propagate(dynamics, state, StepControl(dt, BicycleControl2(current_control)))   (RK4, nsub sub-steps, world-frame BicycleModel
@@ -962,7 +966,7 @@ __global__ __launch_bounds__(64) void k_advance(DevCfg C, int B, tdouble dtp, re
     }
     for (int k = 0; k < 6; k++) q[k] = x[k];
     u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
-    t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
+    clock_next(C, dtp, t0, t_start, clk, idx, b);
 }
 
 // ==================================================================================================================
@@ -1453,6 +1457,43 @@ PG_DEV int hji_source(const DevCfg& C, int use_policy, real V, tdouble toff) {
 PG_DEV void hji_policy_control(const DevVehicle& P, real d_opt, real Fx_opt, real& o0, real& o1, real& o2) {
     o0 = d_opt; o1 = Fx_opt > real(0.0) ? Fx_opt * P.fwd_frac : Fx_opt * P.fwb_frac; o2 = Fx_opt > real(0.0) ? Fx_opt * P.rwd_frac : Fx_opt * P.rwb_frac;
 }
+// What the after-solve kernels of the rollouts share (k_advance_safety, k_node_finish), each for instance b:
+// select: the source of the control (no grid: 0) and the control itself -- the MPC's, or the policy's when it takes over (source 1: the only case that runs optimal_control)
+PG_DEV int hji_select(const DevCfg& C, int use_policy, int has_hji, real V, const tdouble* __restrict__ toff, const real* __restrict__ u_mpc, const real* __restrict__ x7,
+                      const real* __restrict__ vg8, int b, real& n0, real& n1, real& n2) {
+    const int src = has_hji ? hji_source(C, use_policy, V, toff[b]) : 0;
+    n0 = u_mpc[(size_t)b * 3]; n1 = u_mpc[(size_t)b * 3 + 1]; n2 = u_mpc[(size_t)b * 3 + 2];
+    if (src == 1) {
+        real d_opt, Fx_opt; hji_optimal_control(C.veh, x7 + (size_t)b * 7, vg8 + (size_t)b * 8 + 1, d_opt, Fx_opt);
+        hji_policy_control(C.veh, d_opt, Fx_opt, n0, n1, n2);
+    }
+    return src;
+}
+// the human's control (omega, a), held for the step (modes: see k_advance_safety)
+PG_DEV void human_control(const DevVehicle& P, int human_mode, int has_hji, const real* __restrict__ x7, const real* __restrict__ vg8, const real* __restrict__ human_u, int b, real& w, real& a) {
+    w = real(0.0); a = real(0.0);
+    if (human_mode == 1 && has_hji) {
+        const real* xr = x7 + (size_t)b * 7;
+        if (xr[5] > real(0.0)) optimal_disturbance(P, xr, vg8 + (size_t)b * 8 + 1, w, a);
+    } else if (human_mode == 2) { w = human_u[(size_t)b * 2]; a = human_u[(size_t)b * 2 + 1]; }
+}
+// both plants over the step, their controls held: the ego x (stored at q) under (d, Fx), the other car oc (stored at ot) under (w, a)
+PG_DEV void advance_plants(const DevCfg& C, tdouble dtp, real* x, real d, real Fx, real* __restrict__ q, real* oc, real w, real a, real* __restrict__ ot) {
+    const int nsub = C.nsub; const real h = dtp / nsub;
+    advance_ego(C, x, d, Fx, h, nsub);
+    advance_unicycle(oc, w, a, h, nsub);
+    for (int k = 0; k < 6; k++) q[k] = x[k];
+    for (int k = 0; k < 4; k++) ot[k] = oc[k];
+}
+// the safety summary: V_min, the first step index with V <= 0 (-1: none), the steps the policy drove; `restart` starts them afresh
+PG_DEV void safety_summary(real* __restrict__ V_min, int* __restrict__ first_breach, int* __restrict__ policy_steps, int b, int restart, real V, int step, bool policy_step) {
+    real vmin = restart ? real(INFINITY) : V_min[b];
+    int fb = restart ? -1 : first_breach[b], ps = restart ? 0 : policy_steps[b];
+    if (V < vmin) vmin = V;
+    if (fb < 0 && V <= real(0.0)) fb = step;
+    if (policy_step) ps++;
+    V_min[b] = vmin; first_breach[b] = fb; policy_steps[b] = ps;
+}
 
 // optimal_control and the control selection (above) as the one-step call pg_get_next_control_hji makes them, lane = instance.
 // u2 [B][2] = (delta_opt, Fx_opt) whenever the relative state is inside the grid; u_next [B][3] = the policy's BicycleControl when it takes over
@@ -1466,6 +1507,7 @@ __global__ __launch_bounds__(64) void k_hji_policy(DevCfg C, int B, int use_poli
     real d_opt, Fx_opt;
     hji_optimal_control(P, x, g, d_opt, Fx_opt);
     u2[(size_t)b * 2] = d_opt; u2[(size_t)b * 2 + 1] = Fx_opt;
+    // (the selection of hji_select below, stated here because this call reports optimal_control for EVERY instance: it has run already, and must not run twice)
     const int src = hji_source(C, use_policy, vg[0], toff[b]);
     real o0 = u_mpc[(size_t)b * 3], o1 = u_mpc[(size_t)b * 3 + 1], o2 = u_mpc[(size_t)b * 3 + 2];
     if (src == 1) hji_policy_control(P, d_opt, Fx_opt, o0, o1, o2);
@@ -1506,37 +1548,16 @@ __global__ __launch_bounds__(64) void k_advance_safety(DevCfg C, int B, tdouble 
     if (io.other_h) for (int k = 0; k < 4; k++) io.other_h[(size_t)b * 4 + k] = oc[k];
     // select (ros_integration.jl:114-124)
     const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);
-    const int src = has_hji ? hji_source(C, use_policy, V, toff[b]) : 0;
-    real n0 = u_mpc[(size_t)b * 3], n1 = u_mpc[(size_t)b * 3 + 1], n2 = u_mpc[(size_t)b * 3 + 2];
-    if (src == 1) {
-        real d_opt, Fx_opt;
-        hji_optimal_control(P, x7 + (size_t)b * 7, vg8 + (size_t)b * 8 + 1, d_opt, Fx_opt);
-        hji_policy_control(P, d_opt, Fx_opt, n0, n1, n2);
-    }
-    // the human's control, held for the step
-    real w = real(0.0), a = real(0.0);
-    if (human_mode == 1 && has_hji) {
-        const real* xr = x7 + (size_t)b * 7;
-        if (xr[5] > real(0.0)) optimal_disturbance(P, xr, vg8 + (size_t)b * 8 + 1, w, a);
-    } else if (human_mode == 2) {
-        w = io.human_u[(size_t)b * 2]; a = io.human_u[(size_t)b * 2 + 1];
-    }
-    const int nsub = C.nsub; const real h = dtp / nsub;
-    advance_ego(C, x, uc[0], uc[1] + uc[2], h, nsub);
-    advance_unicycle(oc, w, a, h, nsub);
-    for (int k = 0; k < 6; k++) q[k] = x[k];
-    for (int k = 0; k < 4; k++) ot[k] = oc[k];
+    real n0, n1, n2, w, a;
+    const int src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
+    human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
+    advance_plants(C, dtp, x, uc[0], uc[1] + uc[2], q, oc, w, a, ot);
     u[0] = n0; u[1] = n1; u[2] = n2;
-    t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
+    clock_next(C, dtp, t0, t_start, clk, idx, b);
     if (io.human_h) { io.human_h[(size_t)b * 2] = w; io.human_h[(size_t)b * 2 + 1] = a; }
     if (io.V_h) io.V_h[b] = V;
     if (io.src_h) io.src_h[b] = src;
-    real vmin = restart ? real(INFINITY) : io.V_min[b];
-    int fb = restart ? -1 : io.first_breach[b], ps = restart ? 0 : io.policy_steps[b];
-    if (V < vmin) vmin = V;
-    if (fb < 0 && V <= real(0.0)) fb = step;
-    if (src == 1) ps++;
-    io.V_min[b] = vmin; io.first_breach[b] = fb; io.policy_steps[b] = ps;
+    safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);      // (the selected control is the one fed back: every source-1 step is a policy step)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1623,13 +1644,8 @@ __global__ __launch_bounds__(64) void k_node_finish(DevCfg C, int B, tdouble dtp
         bool pub = false;
         real p0 = msg0, p1 = msg1, p2 = msg2;                             // the published command
         if (code == 0) {
-            src = has_hji ? hji_source(C, use_policy, V, toff[b]) : 0;
-            real n0 = u_mpc[(size_t)b * 3], n1 = u_mpc[(size_t)b * 3 + 1], n2 = u_mpc[(size_t)b * 3 + 2];
-            if (src == 1) {
-                real d_opt, Fx_opt;
-                hji_optimal_control(P, x7 + (size_t)b * 7, vg8 + (size_t)b * 8 + 1, d_opt, Fx_opt);
-                hji_policy_control(P, d_opt, Fx_opt, n0, n1, n2);
-            }
+            real n0, n1, n2;
+            src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
             pub = true;
             if (n0 != n0 || n1 != n1 || n2 != n2) {                       // :134-147
                 ev = 3; cold = true;
@@ -1659,26 +1675,12 @@ __global__ __launch_bounds__(64) void k_node_finish(DevCfg C, int B, tdouble dtp
             if (io.applied_h) for (int k = 0; k < 3; k++) io.applied_h[(size_t)b * 3 + k] = ac[k];
             if (io.V_h) io.V_h[b] = V;
             if (io.event_h) io.event_h[b] = ev;
-            real w = real(0.0), a = real(0.0);
-            if (human_mode == 1 && has_hji) {
-                const real* xr = x7 + (size_t)b * 7;
-                if (xr[5] > real(0.0)) optimal_disturbance(P, xr, vg8 + (size_t)b * 8 + 1, w, a);
-            } else if (human_mode == 2) {
-                w = io.human_u[(size_t)b * 2]; a = io.human_u[(size_t)b * 2 + 1];
-            }
-            const int nsub = C.nsub; const real h = dtp / nsub;
-            advance_ego(C, x, ac[0], ac[1] + ac[2], h, nsub);            // the command applied at the step's start (one-step delay, as k_advance)
-            advance_unicycle(oc, w, a, h, nsub);
-            for (int k = 0; k < 6; k++) q[k] = x[k];
-            for (int k = 0; k < 4; k++) ot[k] = oc[k];
+            real w, a;
+            human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
+            advance_plants(C, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
             if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
-            t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
-            real vmin = restart_sum ? real(INFINITY) : io.V_min[b];
-            int fb = restart_sum ? -1 : io.first_breach[b], ps = restart_sum ? 0 : io.policy_steps[b];
-            if (V < vmin) vmin = V;
-            if (fb < 0 && V <= real(0.0)) fb = step;
-            if (ev == 1) ps++;
-            io.V_min[b] = vmin; io.first_breach[b] = fb; io.policy_steps[b] = ps;
+            clock_next(C, dtp, t0, t_start, clk, idx, b);
+            safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)
         }
     }
     if (__ballot(cold) != 0ull && lane == 0) atomicOr(io.cold, 1);
@@ -2954,9 +2956,5 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
 }
 
 #include "pg_solve_lat.hip"         // the lateral formulation's own solve kernel (5-state stage, sixteen lanes per instance)
-
-#ifdef PG_EXPERIMENTAL_SOLVE4      // four instances per wavefront: a measured negative result (EXPERIMENTS.md 4.1), kept out of the shipped libraries
-#include "experimental/pg_solve4.hip"
-#endif
 
 }  // namespace pg
