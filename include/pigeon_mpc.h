@@ -9,8 +9,8 @@
  *   solve!(mpc)                          src/model_predictive_control.jl:76   (-> Parametron -> OSQP, third-party)
  *   get_next_control(mpc)                src/model_predictive_control.jl:78   (-> src/coupled_lat_long.jl:370-374)
  * called from src/ros_integration.jl:96-99,124 and src/model_predictive_control.jl:90-95.  Each entry point below names
- * the reference interface it replaces.  A batch of B independent MPC instances shares one handle (one vehicle, one
- * HJI grid; one reference trajectory or a library of them with a per-instance selection, pg_set_trajectories; one set
+ * the reference interface it replaces.  A batch of B independent MPC instances shares one handle (one vehicle for the
+ * controller -- the PLANT of the rollouts may differ per instance, pg_set_plant_sets --, one HJI grid; one reference trajectory or a library of them with a per-instance selection, pg_set_trajectories; one set
  * of control parameters or a library of sets with a per-instance selection, pg_set_control_param_sets); per-instance
  * persistent state (solved flag, previous time grid, previous primal solution) lives in device memory inside the handle.
  *
@@ -186,6 +186,28 @@ int pg_clear_control_param_sets(pg_handle* h);                                  
  * index does not cover.  n_sets, out and index may each be NULL. */
 int pg_get_control_param_sets(pg_handle* h, int32_t* n_sets, pg_control_params* out, int32_t max_sets, int32_t* index, int32_t B);
 
+/* Plant sets: the vehicle the PLANT of a rollout integrates, per instance -- model-mismatch studies (the tuning under mu = 0.6 instead of 0.92; a grid of plants x tunings x
+ * starts) as ONE batch.  A library of pg_vehicle sets and a per-instance selection, shaped like pg_set_control_param_sets.
+ * What it replaces: mpc.dynamics in exactly ONE place, the ego `propagate` of a rollout step (src/model_predictive_control.jl:94; RK4, rk4_substeps sub-steps, world-frame
+ * bicycle model through the actuator limits), in pg_simulate_dev, pg_simulate_safety_dev and pg_simulate_node_dev.  The controller's side keeps pg_config.vehicle: nodes,
+ * linearisation, QP, u_normalization, the HJI relative dynamics and policy, optimal_disturbance.  pg_step*, the five phase calls and pg_node_step_dev never read the plant
+ * library: they run with a library installed and no index.
+ * Lifetime: a library of ONE set applies to every instance without an index.  With n_sets > 1 the three rollouts return PG_ERR_STATE until an index covering the batch is
+ * installed.  Library and index persist until replaced; installing a library drops the previous index.  n_sets may be as large as batch_capacity (one plant per instance:
+ * Monte Carlo).  With no library the plant is pg_config.vehicle, and the rollouts launch exactly the kernels they launched before this call existed.
+ * No side effects: the plant is NO PART OF ANY QP, so -- unlike pg_set_control_param_sets -- installing, changing or clearing it resets nothing: solver state and warm
+ * starts, the rollout clock, the safety, node and tracking summaries are untouched, and the captured pg_step graph is not affected.
+ * PG_ERR_INVALID (the handle is left unchanged): n_sets < 1; a non-finite field; any of G, m, Izz, L, a, b, mu, Caf, Car, Fx_max, Px_max, delta_max <= 0; Fx_min >= 0; an
+ * index entry outside [0, n_sets); B outside [1, batch_capacity].
+ * Cost: under a library the kernel that moves the plant is another one (k_advance_plant, k_advance_safety_plant, k_node_finish_plant: lane = instance, the lane's record
+ * copied into registers once per step); the launch sequence of a step does not depend on the data. */
+int pg_set_plant_sets(pg_handle* h, int32_t n_sets, const pg_vehicle* sets);
+int pg_set_plant_index(pg_handle* h, int32_t B, const int32_t* index);   /* index[b] in [0, n_sets) */
+int pg_clear_plant_sets(pg_handle* h);                                    /* back to pg_config.vehicle */
+/* the installed library: *n_sets = its size (0: none); out[0 .. min(n_sets, max_sets)) the sets as installed; index[0 .. B) the installed selection, -1 for instances the
+ * index does not cover.  n_sets, out and index may each be NULL. */
+int pg_get_plant_sets(pg_handle* h, int32_t* n_sets, pg_vehicle* out, int32_t max_sets, int32_t* index, int32_t B);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -301,6 +323,20 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
  * the window, low speed, NaN fallback since the clock last restarted (the restart rule of pg_get_safety_state).  Host pointers, any may be NULL. */
 int pg_get_node_state(pg_handle* h, double* applied, int32_t* heartbeat, int32_t* counts);
 
+/* Tracking summary of the rollouts (opt-in: option "tracking_summary" = 1; 0, the default, adds no launch anywhere).  With the option on, each step of pg_simulate_dev,
+ * pg_simulate_safety_dev and pg_simulate_node_dev runs one small lane-per-instance kernel (k_track) behind the step's projection and ahead of the kernel that moves the plant.
+ * per instance since the rollout clock last restarted (the restart rule of pg_get_safety_state): summary [B][6] =
+ * (max |e|, sum e^2, max |Uy / Ux|, max |r|, min Ux, s of the last step), steps [B] = rollout steps counted,
+ * first_exit [B] = first step index (the clock's) at which e lay outside [edge_R(s), edge_L(s)] of the instance's
+ * trajectory, or -1.  (s, e) are the step's path_coordinates -- the s_m, e_m the node publishes
+ * (ros_integration.jl:114,129-130) -- so step k describes the state recorded at step k.  Host pointers, any may be NULL.
+ * The edges at s are the interp_by_s channels the wall rows read (a trajectory library: the instance's own tube).  In the node rollout every step counts, gated out or not
+ * (the plant moves either way).  e is formed from differences to the knots of the projection's segment and its two neighbours, not from the foot point in map coordinates
+ * as the projection forms it: the same distance, without that rounding (fp32 library: 1e-7 m instead of 1e-5 m on a path 300 m from the map's origin, which the squares double).
+ * Before the first counted step: (0, 0, 0, 0, +Inf, NaN), steps 0, first_exit -1.  Sums are kept in the library's arithmetic type.
+ * PG_ERR_STATE with the option off. */
+int pg_get_tracking_state(pg_handle* h, double* summary, int32_t* steps, int32_t* first_exit);
+
 /* stream to launch on (hipStream_t as void*); NULL = the null stream.  pg_set_inputs and pg_step are ASYNCHRONOUS on the handle's stream (copies from / into one pinned
  * staging buffer, synchronised at the next entry that needs it): switching streams first waits for whatever is still queued on the old one. */
 int pg_set_stream(pg_handle* h, void* hip_stream);
@@ -344,6 +380,7 @@ int pg_synchronize(pg_handle* h);
  *     "phase_timing" 0/1 (0)     1 = pg_step_dev records the HIP events pg_get_phase_ms reads (four event records per step on the handle's stream: measured 13-25 us per step, 2-4 % of a
  *                                4096-instance step); 0 = no instrumentation, pg_get_phase_ms returns PG_ERR_STATE
  *     "graph" 0/1 (0)            pg_step of a small warm batch as one hipGraph launch (see pg_step)
+ *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact
  *                                rational (0.01 = 1/100, 0.2 = 1/5), every element ONE rounding -- a restatement of Julia 1.0's Base that could not be executed here;

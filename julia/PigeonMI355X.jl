@@ -174,6 +174,31 @@ function control_param_sets(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
     sets, index
 end
 
+# Plant sets and the tracking summary (pg_set_plant_sets ..., pg_get_tracking_state): like everything in this file, NOT EXECUTED in the build container.
+"The vehicle the PLANT of a rollout integrates, per instance (src/model_predictive_control.jl:94 only; the controller keeps its own vehicle): a library of vehicles in the ABI's layout (`_vehicle(X1())`) and the set each instance runs under (0-based index; may be empty for a library of one).  Resets nothing."
+function set_plants!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgVehicle}, index::Vector{Int32}=Int32[])
+    check(mpc, ccall(sym(mpc, :pg_set_plant_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgVehicle}), mpc.handle, length(sets), sets), "pg_set_plant_sets")
+    isempty(index) || set_plant_index!(mpc, index)
+end
+set_plant_index!(mpc::BatchedTrajectoryTrackingMPC, index::Vector{Int32}) =
+    check(mpc, ccall(sym(mpc, :pg_set_plant_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_plant_index")
+"back to the vehicle the controller was constructed with"
+clear_plants!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_plant_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_plant_sets")
+"(sets, index over the first B instances; -1 where no index covers an instance) as installed"
+function plant_sets(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_plant_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgVehicle}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_plant_sets")
+    sets = Vector{PgVehicle}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_plant_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgVehicle}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_plant_sets")
+    sets, index
+end
+"Tracking summary of the rollouts since the clock last restarted (option \"tracking_summary\" = 1 first): (summary 6 x B = max |e|, sum e^2, max |Uy / Ux|, max |r|, min Ux, last s; steps; first_exit, 0-based step index or -1)"
+function tracking_summary(mpc::BatchedTrajectoryTrackingMPC)
+    summary = zeros(6, mpc.B); steps = zeros(Int32, mpc.B); first_exit = zeros(Int32, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_tracking_state), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}), mpc.handle, summary, steps, first_exit), "pg_get_tracking_state")
+    summary, steps, first_exit
+end
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

@@ -39,6 +39,13 @@ struct pg_handle {
     // installed them (pg_get_control_param_sets), and the set every instance currently runs under (cp_eff, [capacity]: an instance whose entry changes is reset)
     DevControlRec* d_cp_sets = nullptr; int* d_cp_idx = nullptr; int cp_idx_B = 0;
     std::vector<pg_control_params> cp_sets, cp_eff; std::vector<int32_t> cp_index;
+    // plant library (pg_set_plant_sets / pg_set_plant_index): the vehicles the ego plant of the rollouts integrates, per instance; the device records and index the *_plant kernels
+    // read, and the sets and index as the caller installed them (pg_get_plant_sets).  Nothing on the controller's side reads any of it
+    DevVehicle* d_plants = nullptr; int* d_plant_idx = nullptr; int plant_idx_B = 0;
+    std::vector<pg_vehicle> plant_sets; std::vector<int32_t> plant_index;
+    // tracking summary (option "tracking_summary"; pg_get_tracking_state): [cap][6] sums, steps [cap] then first_exit [cap] (k_track), allocated when the option is first used
+    int tracking = 0; real* d_track = nullptr; int* d_track_i = nullptr;
+    bool track_fresh = true;                                  // the tracking summary restarts at the next rollout step (the clock restarted since it was last written)
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -185,12 +192,14 @@ static int down_raw(pg_handle* h, void* dst, const void* src, size_t bytes) {   
     return PG_OK;
 }
 static void fill_dev_control(DevControl& U, const pg_control_params& u);
-static void fill_dev_params(DevCfg& C, const pg_config* cfg) {
-    const pg_vehicle& v = cfg->vehicle; DevVehicle& V = C.veh;
+static void fill_dev_vehicle(DevVehicle& V, const pg_vehicle& v) {
     V.G = (real)v.G; V.m = (real)v.m; V.Izz = (real)v.Izz; V.L = (real)v.L; V.a = (real)v.a; V.b = (real)v.b; V.h = (real)v.h; V.mu = (real)v.mu;
     V.Caf = (real)v.Caf; V.Car = (real)v.Car; V.Cd0 = (real)v.Cd0; V.Cd1 = (real)v.Cd1; V.Cd2 = (real)v.Cd2;
     V.fwd_frac = (real)v.fwd_frac; V.rwd_frac = (real)v.rwd_frac; V.fwb_frac = (real)v.fwb_frac; V.rwb_frac = (real)v.rwb_frac;
     V.Fx_max = (real)v.Fx_max; V.Fx_min = (real)v.Fx_min; V.Px_max = (real)v.Px_max; V.delta_max = (real)v.delta_max; V.kappa_max = (real)v.kappa_max;
+}
+static void fill_dev_params(DevCfg& C, const pg_config* cfg) {
+    fill_dev_vehicle(C.veh, cfg->vehicle);
     fill_dev_control(C.cp, cfg->control);
 }
 static void fill_dev_control(DevControl& U, const pg_control_params& u) {
@@ -289,7 +298,7 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_cp_sets, h->d_cp_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_plants, h->d_plant_idx, h->d_track, h->d_track_i};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
@@ -479,6 +488,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "phase_timing") return I(&h->phase_timing, 0, 1);
     if (n == "hji_cell_dims") return I(&h->hji_cell_dims, 3, 7);
     if (n == "time_grid_naive") return I(&C.time_grid_naive, 0, 1);
+    if (n == "tracking_summary") return I(&h->tracking, 0, 1);
     // k_solve_lat (lateral QP)
     if (n == "lateral_solver") return I(&h->lateral_solver, 0, 2);
     if (n == "lat_split") return I(&h->split_lat, 0, 1);
@@ -736,6 +746,68 @@ int pg_get_control_param_sets(pg_handle* h, int32_t* n_sets, pg_control_params* 
     return PG_OK;
 }
 
+// ---- plant library: the vehicle the ego plant of a rollout step integrates, per instance (model_predictive_control.jl:94).  No part of any QP: nothing is reset ----
+static const char* plant_set_problem(const pg_vehicle& v) {
+    const double f[22] = {v.G, v.m, v.Izz, v.L, v.a, v.b, v.mu, v.Caf, v.Car, v.Fx_max, v.Px_max, v.delta_max,      // [0, 12): must be > 0
+                          v.h, v.Cd0, v.Cd1, v.Cd2, v.fwd_frac, v.rwd_frac, v.fwb_frac, v.rwb_frac, v.Fx_min, v.kappa_max};
+    for (double x : f) if (!std::isfinite(x)) return "a set has a non-finite field";
+    for (int i = 0; i < 12; i++) if (!(f[i] > 0.0)) return "a set needs G, m, Izz, L, a, b, mu, Caf, Car, Fx_max, Px_max and delta_max > 0";
+    if (!(v.Fx_min < 0.0)) return "a set needs Fx_min < 0";
+    return nullptr;
+}
+int pg_set_plant_sets(pg_handle* h, int32_t n_sets, const pg_vehicle* sets) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, n_sets >= 1 && sets, "pg_set_plant_sets: need n_sets >= 1 and the sets");
+    for (int k = 0; k < n_sets; k++) { const char* why = plant_set_problem(sets[k]); REQUIRE(h, !why, std::string("pg_set_plant_sets: ") + why); }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
+    std::vector<DevVehicle> recs((size_t)n_sets);
+    for (int k = 0; k < n_sets; k++) fill_dev_vehicle(recs[(size_t)k], sets[k]);
+    DevVehicle* d_new = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(DevVehicle)));
+    if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(DevVehicle), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = "pg_set_plant_sets: copy failed"; return PG_ERR_HIP; }
+    if (h->d_plants) (void)hipFree(h->d_plants);
+    h->d_plants = d_new; h->plant_sets.assign(sets, sets + n_sets);
+    h->plant_index.clear(); h->plant_idx_B = 0;                 // installing a library drops the previous index
+    return PG_OK;
+}
+int pg_set_plant_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    const int n = (int)h->plant_sets.size();
+    REQUIRE(h, n >= 1, "pg_set_plant_index: no plant library installed");
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_plant_index: need 1 <= B <= batch_capacity and an index array");
+    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < n, "pg_set_plant_index: index out of range of the installed library");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!h->d_plant_idx) {
+        HIPCHK(h, hipMalloc((void**)&h->d_plant_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
+        HIPCHK(h, hipMemset(h->d_plant_idx, 0, (size_t)h->cfg.batch_capacity * sizeof(int)));
+    }
+    // (the whole array is rewritten: entries beyond the indexed batch select set 0 -- never an address outside the library, whatever an earlier, larger library left there)
+    std::vector<int> full((size_t)h->cfg.batch_capacity, 0);
+    for (int b = 0; b < B; b++) full[(size_t)b] = index[b];
+    HIPCHK(h, hipMemcpy(h->d_plant_idx, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->plant_index.assign(index, index + B); h->plant_idx_B = B;
+    return PG_OK;
+}
+int pg_clear_plant_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_plants) { (void)hipFree(h->d_plants); h->d_plants = nullptr; }
+    h->plant_sets.clear(); h->plant_index.clear(); h->plant_idx_B = 0;
+    return PG_OK;
+}
+int pg_get_plant_sets(pg_handle* h, int32_t* n_sets, pg_vehicle* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), "pg_get_plant_sets: need max_sets >= 0 and 0 <= B <= batch_capacity");
+    const int n = (int)h->plant_sets.size();
+    if (n_sets) *n_sets = n;
+    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = h->plant_sets[(size_t)k];
+    if (index) for (int b = 0; b < B; b++) index[b] = b < h->plant_idx_B ? h->plant_index[(size_t)b] : -1;
+    return PG_OK;
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -807,7 +879,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1324,16 +1396,38 @@ static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, doub
     REQUIRE(h, human_mode != 2 || human_u_dev, w + ": human_mode 2 needs human_u_dev [steps][B][2]");
     return PG_OK;
 }
+// what a rollout needs beyond check_ready: a plant library of several sets wants an index that covers the batch; the tracking summary its buffers
+static int rollout_ready(pg_handle* h) {
+    if (h->plant_sets.size() > 1 && h->plant_idx_B < h->B) { h->err = "a plant library is installed but pg_set_plant_index does not cover the batch"; return PG_ERR_STATE; }
+    if (h->tracking && !h->d_track) {
+        const size_t cap = cap_of(h);
+        HIPCHK(h, hipMalloc((void**)&h->d_track, cap * 6 * sizeof(real)));
+        HIPCHK(h, hipMalloc((void**)&h->d_track_i, cap * 2 * sizeof(int)));
+    }
+    return PG_OK;
+}
+// the plant library as the *_plant kernels take it (the host knows whether one is installed: that alone picks the kernel)
+static bool plant_lib_on(const pg_handle* h) { return !h->plant_sets.empty(); }
+static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->d_plants, h->plant_sets.size() > 1 ? h->d_plant_idx : (const int*)nullptr}; }
+// the step's tracking summary (option "tracking_summary"): behind the projection of this step (step_compute), ahead of the kernel that moves the plant
+static int launch_track(pg_handle* h, int step) {
+    if (!h->tracking) { h->track_fresh = true; return PG_OK; }      // (off: no launch; steps that went unseen must not be continued when it comes back on)
+    const int B = h->B;
+    hipLaunchKernelGGL(k_track, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)h->track_fresh, step, h->d_state, h->d_sep, h->d_track, h->d_track_i, h->d_track_i + cap_of(h));
+    LAUNCH_CHECK(h);
+    h->track_fresh = false;
+    return PG_OK;
+}
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true;
     }
     return PG_OK;
 }
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev_, void* control_hist_dev_) {
     int rc = check_ready(h); if (rc) return rc;
-    if ((rc = check_rollout_args(h, "pg_simulate_dev", steps, dt, 0, nullptr))) return rc;
+    if ((rc = check_rollout_args(h, "pg_simulate_dev", steps, dt, 0, nullptr)) || (rc = rollout_ready(h))) return rc;
     const int B = h->B;
     real* state_hist_dev = (real*)state_hist_dev_; real* control_hist_dev = (real*)control_hist_dev_;
     if ((rc = clock_start(h, dt))) return rc;                           // the loop's clock (:87)
@@ -1341,8 +1435,10 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
         if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(state_hist_dev + (size_t)k * B * 6, h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // push!(qs, state) :88
         if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(control_hist_dev + (size_t)k * B * 3, h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream)); // push!(us, control) :89
         if ((rc = step_compute(h))) return rc;                                                        // :90-93
+        if ((rc = launch_track(h, h->sim_idx - 1))) return rc;
         h->sim_idx++;                                                                                                                                         // (t0 now holds element sim_idx of the clock)
-        hipLaunchKernelGGL(k_advance, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx);      // :94-95
+        if (plant_lib_on(h)) hipLaunchKernelGGL(k_advance_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, plant_lib(h));
+        else hipLaunchKernelGGL(k_advance, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx);      // :94-95
         LAUNCH_CHECK(h);
     }
     return PG_OK;
@@ -1354,7 +1450,7 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
                            void* state_hist_dev_, void* control_hist_dev_, void* other_hist_dev_, void* human_hist_dev_, void* V_hist_dev_, int32_t* source_hist_dev) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED) { h->err = "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row"; return PG_ERR_STATE; }
-    if ((rc = check_rollout_args(h, "pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev_))) return rc;
+    if ((rc = check_rollout_args(h, "pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev_)) || (rc = rollout_ready(h))) return rc;
     const int B = h->B; const size_t Bz = (size_t)B;
     const real* human_u_dev = (const real*)human_u_dev_;
     real *sh = (real*)state_hist_dev_, *ch = (real*)control_hist_dev_, *oh = (real*)other_hist_dev_, *hh = (real*)human_hist_dev_, *vh = (real*)V_hist_dev_;
@@ -1362,11 +1458,14 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
     for (int k = 0; k < steps; k++) {
         if ((rc = step_compute(h))) return rc;                                                        // :90-93
         const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
+        if ((rc = launch_track(h, step))) return rc;
         h->sim_idx++;
         SafetyIO io{human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr, sh ? sh + (size_t)k * Bz * 6 : nullptr, ch ? ch + (size_t)k * Bz * 3 : nullptr,
                     oh ? oh + (size_t)k * Bz * 4 : nullptr, hh ? hh + (size_t)k * Bz * 2 : nullptr, vh ? vh + (size_t)k * Bz : nullptr,
                     source_hist_dev ? source_hist_dev + (size_t)k * Bz : nullptr, h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-        hipLaunchKernelGGL(k_advance_safety, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji,
+        if (plant_lib_on(h)) hipLaunchKernelGGL(k_advance_safety_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji,
+                           (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io, plant_lib(h));
+        else hipLaunchKernelGGL(k_advance_safety, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji,
                            (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
         LAUNCH_CHECK(h);
         h->sum_fresh = false;
@@ -1387,6 +1486,22 @@ int pg_get_safety_state(pg_handle* h, double* other_car, double* V_min, int32_t*
     }
     if ((rc = down(h, V_min, h->d_vmin, B)) || (rc = down_raw(h, first_breach, h->d_breach, B * sizeof(int32_t))) ||
         (rc = down_raw(h, policy_steps, h->d_breach + h->cfg.batch_capacity, B * sizeof(int32_t)))) return rc;
+    return PG_OK;
+}
+int pg_get_tracking_state(pg_handle* h, double* summary, int32_t* steps, int32_t* first_exit) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!h->tracking) { h->err = "the tracking summary is off: pg_set_option(h, \"tracking_summary\", 1), then a rollout"; return PG_ERR_STATE; }
+    const size_t B = h->B;
+    if (h->track_fresh || !h->d_track) {             // no rollout step since the clock (re)started
+        for (size_t b = 0; b < B; b++) {
+            if (summary) { double* S = summary + b * 6; S[0] = S[1] = S[2] = S[3] = 0.0; S[4] = INFINITY; S[5] = NAN; }
+            if (steps) steps[b] = 0;
+            if (first_exit) first_exit[b] = -1;
+        }
+        return PG_OK;
+    }
+    if ((rc = down(h, summary, h->d_track, B * 6)) || (rc = down_raw(h, steps, h->d_track_i, B * sizeof(int32_t))) ||
+        (rc = down_raw(h, first_exit, h->d_track_i + cap_of(h), B * sizeof(int32_t)))) return rc;
     return PG_OK;
 }
 // ---- node callback (from_autobox_callback, ros_integration.jl:48-151) --------------------------------------------
@@ -1454,7 +1569,7 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
                          void* state_hist_dev_, void* applied_hist_dev_, int32_t* event_hist_dev, void* V_hist_dev_) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
-    if ((rc = check_rollout_args(h, "pg_simulate_node_dev", steps, dt, human_mode, human_u_dev_))) return rc;
+    if ((rc = check_rollout_args(h, "pg_simulate_node_dev", steps, dt, human_mode, human_u_dev_)) || (rc = rollout_ready(h))) return rc;
     if ((rc = node_prepare(h))) return rc;
     const int B = h->B; const size_t Bz = (size_t)B;
     const real* human_u_dev = (const real*)human_u_dev_;
@@ -1466,13 +1581,16 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
     for (int k = 0; k < steps; k++) {
         if ((rc = node_gate(h, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr)) || (rc = step_compute(h))) return rc;
         const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
+        if ((rc = launch_track(h, step))) return rc;                                                  // (every step counts, gated out or not: the plant moves either way)
         h->sim_idx++;
         NodeIO io = node_io(h);
         io.human_u = human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr;
         io.state_h = sh ? sh + (size_t)k * Bz * 6 : nullptr; io.applied_h = ah ? ah + (size_t)k * Bz * 3 : nullptr; io.V_h = vh ? vh + (size_t)k * Bz : nullptr;
         io.event_h = event_hist_dev ? event_hist_dev + (size_t)k * Bz : nullptr;
         io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-        hipLaunchKernelGGL(k_node_finish<true>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, has,
+        if (plant_lib_on(h)) hipLaunchKernelGGL(k_node_finish_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, has,
+                           (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, h->kv, io, plant_lib(h));
+        else hipLaunchKernelGGL(k_node_finish<true>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, has,
                            (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, h->kv, io);
         LAUNCH_CHECK(h);
         h->sum_fresh = false;

@@ -928,6 +928,38 @@ PG_DEV void advance_ego(const DevCfg& C, real* x, real d, real Fx, real h, int n
     }
 }
 
+// Plant library (pg_set_plant_sets / pg_set_plant_index): the vehicle the EGO PLANT of a rollout step integrates (model_predictive_control.jl:94), per instance.  Only the
+// *_plant kernels take it -- they are launched when a library is installed, a fact of the handle the host knows; the controller's side of every kernel keeps C.veh.
+// The kernels of the uniform path (k_advance, k_advance_safety, k_node_finish and the device functions they call) are left EXACTLY as they were: routing them and the
+// *_plant kernels through shared bodies was tried and regrouped the instructions of k_advance_safety and k_node_finish in both builds (other FMA operand orders in fp64,
+// another schedule in fp32) -- the uniform path must keep its bits and its cost, so the library path restates the few lines it needs (same statements, P in place of C.veh).
+// A lane copies its record into registers once, ahead of the RK4 loop (idx == nullptr: a library of one, every lane reads record 0).  These kernels run one 64-lane block per
+// 64 instances -- a wavefront or two per CU at B = 4096 -- so the registers a resident record takes cost no occupancy anyone uses, and the serial chain of 4 nsub right-hand
+// sides per step reads no memory at all; loading each field where it is used (ControlView's arrangement, made for register-tight kernels at full occupancy) would put
+// ~20 L2-latency loads into every one of those right-hand sides.
+struct PlantLib { const DevVehicle* sets; const int* idx; };
+PG_DEV DevVehicle plant_of(const PlantLib& L, int b) { return L.sets[L.idx ? L.idx[b] : 0]; }
+// advance_ego with the plant's own vehicle
+PG_DEV void advance_ego_plant(const DevVehicle& P, real* x, real d, real Fx, real h, int nsub) {
+    auto rhs = [&](const real* y, real* o) {
+        real s, c; pg_sincos(y[2], &s, &c);
+        o[0] = -y[3] * s - y[4] * c; o[1] = y[3] * c - y[4] * s; o[2] = y[5];          // psi measured from North (:127-129)
+        world_body_rhs<real>(P, y[3], y[4], y[5], d, Fx, o[3], o[4], o[5]);
+    };
+#pragma unroll 1
+    for (int i = 0; i < nsub; i++) {
+        real k1[6], k2[6], k3[6], k4[6], y[6];
+        rhs(x, k1);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k1[k] * (h * real(0.5));
+        rhs(y, k2);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k2[k] * (h * real(0.5));
+        rhs(y, k3);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k3[k] * h;
+        rhs(y, k4);
+        for (int k = 0; k < 6; k++) x[k] += (k1[k] + real(2.0) * k2[k] + real(2.0) * k3[k] + k4[k]) * (h / real(6.0));
+    }
+}
+
 // the loop's clock of instance b moves to element idx of its range (see k_advance: t)
 PG_DEV void clock_next(const DevCfg& C, tdouble dtp, tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, const JlRange& clk, int idx, int b) {
     t0[b] = C.time_grid_naive ? t0[b] + dtp : jl_shifted_elem(clk, t_start[b], idx);
@@ -967,6 +999,68 @@ __global__ __launch_bounds__(64) void k_advance(DevCfg C, int B, tdouble dtp, re
     for (int k = 0; k < 6; k++) q[k] = x[k];
     u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
     clock_next(C, dtp, t0, t_start, clk, idx, b);
+}
+// ... under a plant library: the same step with the instance's own vehicle in the plant (advance_ego_plant's statement of the RK4)
+__global__ __launch_bounds__(64) void k_advance_plant(DevCfg C, int B, tdouble dtp, real* __restrict__ state, real* __restrict__ control, const real* __restrict__ u_next,
+                                                      tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, PlantLib lib) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevVehicle P = plant_of(lib, b);
+    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3;
+    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+    const int nsub = C.nsub; const real h = dtp / nsub;
+    advance_ego_plant(P, x, u[0], u[1] + u[2], h, nsub);
+    for (int k = 0; k < 6; k++) q[k] = x[k];
+    u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
+    clock_next(C, dtp, t0, t_start, clk, idx, b);
+}
+
+// Tracking summary (option "tracking_summary"; pg_get_tracking_state), lane = instance: one launch per rollout step, behind the step's projection (sep = (s, e, t, segment)
+// of the state the step records) and ahead of the kernel that moves the plant.  sum [B][6] = (max |e|, sum e^2, max |Uy / Ux|, max |r|, min Ux, s of the last step);
+// steps [B]; first_exit [B] = the first step (the clock's index) with e outside [edge_R(s), edge_L(s)] of the instance's trajectory -- the interp_by_s channels the wall
+// rows read (traj_edges_at_s) --, or -1.  `restart` starts them afresh (the clock restarted).
+// e is the step's lateral offset restated without the rounding of the foot point: seg_dist2 forms it at the magnitude of the map coordinates (skidpadoval lies 300 m from
+// its origin: 1e-5 m in fp32, enough to rank two segments that meet near the foot point the other way round, and twice that, relatively, in e^2), seg_offset forms it
+// from differences to the segment's own knot (1e-7 m), over the projection's segment and its two neighbours.  Same value; s is the projection's (continuous across knots).
+PG_DEV real seg_offset(const TrajView& T, int i, real x, real y, real& side) {
+    const real vx = T.E[i + 1] - T.E[i], vy = T.N[i + 1] - T.N[i], wx = x - T.E[i], wy = y - T.N[i];
+    real lam = (vx * wx + vy * wy) / (vx * vx + vy * vy);
+    lam = lam < real(0.0) ? real(0.0) : (lam > real(1.0) ? real(1.0) : lam);
+    const real dx = wx - lam * vx, dy = wy - lam * vy;
+    side = sgn(vx * wy - vy * wx);
+    return sqrt(dx * dx + dy * dy);
+}
+__global__ __launch_bounds__(64) void k_track(DevCfg C, int B, int restart, int step, const real* __restrict__ state, const real* __restrict__ sep, real* __restrict__ sum,
+                                              int* __restrict__ steps, int* __restrict__ first_exit) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const real s = sep[(size_t)b * 4];
+    real e = sep[(size_t)b * 4 + 1];
+    const real Ux = state[(size_t)b * 6 + 3], Uy = state[(size_t)b * 6 + 4], r = state[(size_t)b * 6 + 5];
+    real* S = sum + (size_t)b * 6;
+    real emax = restart ? real(0.0) : S[0], e2 = restart ? real(0.0) : S[1], bmax = restart ? real(0.0) : S[2], rmax = restart ? real(0.0) : S[3];
+    real uxmin = restart ? real(INFINITY) : S[4];
+    int n = restart ? 0 : steps[b], fx = restart ? -1 : first_exit[b];
+    const TrajView T = traj_of(C, b);
+    real eL, eR; traj_edges_at_s(T, s, eL, eR);
+    if (e == e) {                                           // (a non-finite pose: k_project left NaN and no segment)
+        const int i0 = clampi((int)sep[(size_t)b * 4 + 3], 0, T.L - 2), i_lo = i0 > 0 ? i0 - 1 : 0, i_hi = i0 < T.L - 2 ? i0 + 1 : T.L - 2;
+        const real x = state[(size_t)b * 6], y = state[(size_t)b * 6 + 1];
+        real best = INFINITY;
+        for (int i = i_lo; i <= i_hi; i++) {
+            real side; const real d = seg_offset(T, i, x, y, side);
+            if (d < best) { best = d; e = d * side; }       // strict '<': the lowest index keeps a tie, as in k_project
+        }
+    }
+    if (fabs(e) > emax) emax = fabs(e);
+    e2 += e * e;
+    const real beta = fabs(Uy / Ux);
+    if (beta > bmax) bmax = beta;
+    if (fabs(r) > rmax) rmax = fabs(r);
+    if (Ux < uxmin) uxmin = Ux;
+    if (fx < 0 && (e > eL || e < eR)) fx = step;
+    S[0] = emax; S[1] = e2; S[2] = bmax; S[3] = rmax; S[4] = uxmin; S[5] = s;
+    steps[b] = n + 1; first_exit[b] = fx;
 }
 
 // ==================================================================================================================
@@ -1559,6 +1653,41 @@ __global__ __launch_bounds__(64) void k_advance_safety(DevCfg C, int B, tdouble 
     if (io.src_h) io.src_h[b] = src;
     safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);      // (the selected control is the one fed back: every source-1 step is a policy step)
 }
+// ... under a plant library (PlantLib above): k_advance_safety with the instance's own vehicle in the ego plant; selection, policy and the human's optimal_disturbance keep C.veh
+PG_DEV void advance_plants_lib(const DevCfg& C, const DevVehicle& Pl, tdouble dtp, real* x, real d, real Fx, real* __restrict__ q, real* oc, real w, real a, real* __restrict__ ot) {
+    const int nsub = C.nsub; const real h = dtp / nsub;
+    advance_ego_plant(Pl, x, d, Fx, h, nsub);
+    advance_unicycle(oc, w, a, h, nsub);
+    for (int k = 0; k < 6; k++) q[k] = x[k];
+    for (int k = 0; k < 4; k++) ot[k] = oc[k];
+}
+__global__ __launch_bounds__(64) void k_advance_safety_plant(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart, int step,
+                                                             real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                             const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                             tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, SafetyIO io, PlantLib lib) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevVehicle& P = C.veh;
+    const DevVehicle Pl = plant_of(lib, b);
+    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3; real* ot = other + (size_t)b * 4;
+    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+    real uc[3] = {u[0], u[1], u[2]};
+    real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
+    if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
+    if (io.control_h) for (int k = 0; k < 3; k++) io.control_h[(size_t)b * 3 + k] = uc[k];
+    if (io.other_h) for (int k = 0; k < 4; k++) io.other_h[(size_t)b * 4 + k] = oc[k];
+    const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);
+    real n0, n1, n2, w, a;
+    const int src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
+    human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
+    advance_plants_lib(C, Pl, dtp, x, uc[0], uc[1] + uc[2], q, oc, w, a, ot);
+    u[0] = n0; u[1] = n1; u[2] = n2;
+    clock_next(C, dtp, t0, t_start, clk, idx, b);
+    if (io.human_h) { io.human_h[(size_t)b * 2] = w; io.human_h[(size_t)b * 2 + 1] = a; }
+    if (io.V_h) io.V_h[b] = V;
+    if (io.src_h) io.src_h[b] = src;
+    safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Node callback (pg_node_step_dev / pg_simulate_node_dev): the per-message decision of from_autobox_callback (ros_integration.jl:48-151) for every instance of a batch.
@@ -1678,6 +1807,71 @@ __global__ __launch_bounds__(64) void k_node_finish(DevCfg C, int B, tdouble dtp
             real w, a;
             human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
             advance_plants(C, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
+            if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
+            clock_next(C, dtp, t0, t_start, clk, idx, b);
+            safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)
+        }
+    }
+    if (__ballot(cold) != 0ull && lane == 0) atomicOr(io.cold, 1);
+}
+// ... the step of the node ROLLOUT under a plant library (PlantLib above): k_node_finish<true> with the instance's own vehicle in the ego plant
+__global__ __launch_bounds__(64) void k_node_finish_plant(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart_cnt, int restart_sum, int step,
+                                                    real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                    const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, KeepView K, NodeIO io, PlantLib lib) {
+    const int lane = (int)threadIdx.x, b = blockIdx.x * 64 + lane;
+    const bool valid = b < B;
+    const int code = valid ? io.gate[b] : 0;
+    unsigned long long m = __ballot(code != 0);
+    while (m) {
+        const int j = __ffsll((long long)m) - 1; m &= m - 1;
+        keep_move(K, blockIdx.x * 64 + j, lane, false);
+    }
+    bool cold = false;
+    if (valid) {
+        const DevVehicle& P = C.veh;
+        real* u = control + (size_t)b * 3;
+        const real msg0 = u[0], msg1 = u[1], msg2 = u[2];                // current_control: the message last published (:52)
+        const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);  // looked up before any gate (:55-57)
+        int ev = code, src = 0;
+        bool pub = false;
+        real p0 = msg0, p1 = msg1, p2 = msg2;                             // the published command
+        if (code == 0) {
+            real n0, n1, n2;
+            src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
+            pub = true;
+            if (n0 != n0 || n1 != n1 || n2 != n2) {                       // :134-147
+                ev = 3; cold = true;
+                u[0] = real(0.0); u[1] = real(0.0); u[2] = real(0.0);
+                K.solved[b] = 0; K.wfail[b] = 0;
+            } else {
+                ev = src;
+                p0 = n0; p1 = n1; p2 = n2;
+                u[0] = n0; u[1] = n1; u[2] = n2;
+            }
+            io.heartbeat[b] += 1;
+        } else cold = K.k_solved[b] == 0;
+        if (io.cmd_out && pub) { io.cmd_out[(size_t)b * 3] = p0; io.cmd_out[(size_t)b * 3 + 1] = p1; io.cmd_out[(size_t)b * 3 + 2] = p2; }
+        if (io.se_out) { io.se_out[(size_t)b * 2] = io.sep[(size_t)b * 4]; io.se_out[(size_t)b * 2 + 1] = io.sep[(size_t)b * 4 + 1]; }
+        if (io.event) io.event[b] = ev;
+        int* cn = io.counts + (size_t)b * 4;
+        int c4[4] = {restart_cnt ? 0 : cn[0], restart_cnt ? 0 : cn[1], restart_cnt ? 0 : cn[2], restart_cnt ? 0 : cn[3]};
+        if (ev >= 4) c4[ev - 4]++;
+        if (ev == 3) c4[3]++;
+        cn[0] = c4[0]; cn[1] = c4[1]; cn[2] = c4[2]; cn[3] = c4[3];
+        {
+            const DevVehicle Pl = plant_of(lib, b);
+            real* q = state + (size_t)b * 6; real* ap = io.applied + (size_t)b * 3; real* ot = other + (size_t)b * 4;
+            real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+            real ac[3] = {ap[0], ap[1], ap[2]};
+            real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
+            if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
+            if (io.applied_h) for (int k = 0; k < 3; k++) io.applied_h[(size_t)b * 3 + k] = ac[k];
+            if (io.V_h) io.V_h[b] = V;
+            if (io.event_h) io.event_h[b] = ev;
+            real w, a;
+            human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
+            advance_plants_lib(C, Pl, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
             if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
             clock_next(C, dtp, t0, t_start, clk, idx, b);
             safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)

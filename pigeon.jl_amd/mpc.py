@@ -195,6 +195,53 @@ class BatchedTrajectoryTrackingMPC:
         names = [name for name, _ in _lib.pg_control_params._fields_ if name != "_pad"]
         return [{name: getattr(arr[k], name) for name in names} for k in range(n.value)], index
 
+    # ---- the PLANT of the rollouts, per instance (model-mismatch studies): a library of vehicles and a per-instance selection.  The controller keeps self.vehicle ----
+    def pack_vehicles(self, sets):
+        """vehicle dicts (vehicles.X1(**overrides); missing fields: the handle's own vehicle) or pg_vehicle structures -> a ctypes array of pg_vehicle."""
+        sets = list(sets)
+        arr = (_lib.pg_vehicle * len(sets))()
+        for k, v in enumerate(sets):
+            if isinstance(v, _lib.pg_vehicle):
+                C.memmove(C.byref(arr[k]), C.byref(v), C.sizeof(_lib.pg_vehicle))
+                continue
+            for name, _ in _lib.pg_vehicle._fields_:
+                setattr(arr[k], name, float(v[name] if name in v else self.vehicle[name]))
+        return arr
+
+    def set_plants(self, sets, index=None):
+        """The vehicle the ego plant of simulate_ / simulate_safety_ / simulate_node_ integrates (pg_set_plant_sets): one set (dict / structure) for the whole batch, or a
+        list of sets; select per instance with `index` or set_plant_index.  Resets nothing: the plant is no part of any QP."""
+        if isinstance(sets, (dict, _lib.pg_vehicle)):
+            sets = [sets]
+        arr = self.pack_vehicles(sets)
+        self._chk(self.lib.pg_set_plant_sets(self.h, len(arr), arr), "pg_set_plant_sets")
+        if index is not None:
+            self.set_plant_index(index)
+
+    def set_plant_index(self, index):
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        self._chk(self.lib.pg_set_plant_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_plant_index")
+
+    def clear_plants(self):
+        self._chk(self.lib.pg_clear_plant_sets(self.h), "pg_clear_plant_sets")
+
+    def plant_sets(self):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        n = C.c_int32(0)
+        self._chk(self.lib.pg_get_plant_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_plant_sets")
+        arr = (_lib.pg_vehicle * max(n.value, 1))()
+        index = np.full(self.B, -1, dtype=np.int32)
+        self._chk(self.lib.pg_get_plant_sets(self.h, C.byref(n), arr, n.value, _p(index, C.POINTER(C.c_int32)), self.B), "pg_get_plant_sets")
+        names = [name for name, _ in _lib.pg_vehicle._fields_]
+        return [{name: getattr(arr[k], name) for name in names} for k in range(n.value)], index
+
+    def tracking_summary(self):
+        """Per instance since the rollout's clock last restarted (option "tracking_summary" = 1 first; pg_get_tracking_state): (summary [B][6] = max |e|, sum e^2,
+        max |Uy / Ux|, max |r|, min Ux, s of the last step; steps [B]; first_exit [B]: first step index with e outside the tube's edges, -1: none)."""
+        sm = np.zeros((self.B, 6)); n = np.zeros(self.B, dtype=np.int32); fx = np.zeros(self.B, dtype=np.int32)
+        self._chk(self.lib.pg_get_tracking_state(self.h, _p(sm), _p(n, C.POINTER(C.c_int32)), _p(fx, C.POINTER(C.c_int32))), "pg_get_tracking_state")
+        return sm, n, fx
+
     # ---- mpc.HJI_cache = HJICache(...) (Pigeon.jl:40) ----
     def set_hji_cache(self, grid_knots, V_raw, gradV_raw):
         dims = np.array([len(k) for k in grid_knots], dtype=np.int32)

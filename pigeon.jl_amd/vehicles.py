@@ -2,29 +2,39 @@
 import math
 
 
-def X1():
+X1_BASE_FIELDS = ("G", "mfl", "mfr", "mrl", "mrr", "Ixx", "Iyy", "Izz", "L", "d", "hf", "hr", "h1", "mu", "Caf", "Car", "Fx_max", "Px_max", "Cd0", "Cd1", "Cd2",
+                  "fwd_frac", "fwb_frac", "delta_max")
+
+
+def X1(**overrides):
+    """X1() is the reference's dictionary.  X1(mu=0.5, mfl=580.0, ...) overrides BASE fields (X1_BASE_FIELDS) and recomputes the derived ones -- m, a, b, h, rwd_frac,
+    rwb_frac, Fx_min, kappa_max -- by the same formulas (vehicles.jl:10-56): a plant variant for set_plants."""
+    for k in overrides:
+        if k not in X1_BASE_FIELDS:
+            raise KeyError(f"{k} is not a base field of X1 (derived fields are recomputed: {X1_BASE_FIELDS})")
+    o = lambda name, default: float(overrides.get(name, default))
     X = {}
-    X["G"] = 9.80665
-    X["mfl"], X["mfr"], X["mrl"], X["mrr"] = 484.0, 455.0, 521.0, 504.0
+    X["G"] = o("G", 9.80665)
+    X["mfl"], X["mfr"], X["mrl"], X["mrr"] = o("mfl", 484.0), o("mfr", 455.0), o("mrl", 521.0), o("mrr", 504.0)
     X["m"] = X["mfl"] + X["mfr"] + X["mrl"] + X["mrr"]
-    X["Ixx"], X["Iyy"], X["Izz"] = 175.0, 1000.0, 2900.0
-    X["L"] = 2.87
-    X["d"] = 1.63
+    X["Ixx"], X["Iyy"], X["Izz"] = o("Ixx", 175.0), o("Iyy", 1000.0), o("Izz", 2900.0)
+    X["L"] = o("L", 2.87)
+    X["d"] = o("d", 1.63)
     X["a"] = (X["mrl"] + X["mrr"]) / X["m"] * X["L"]
     X["b"] = (X["mfl"] + X["mfr"]) / X["m"] * X["L"]
-    X["hf"], X["hr"], X["h1"] = 0.1, 0.1, 0.37
+    X["hf"], X["hr"], X["h1"] = o("hf", 0.1), o("hr", 0.1), o("h1", 0.37)
     X["h"] = X["hf"] * X["b"] / X["L"] + X["hr"] * X["a"] / X["L"] + X["h1"]
-    X["mu"] = 0.92
-    X["Caf"], X["Car"] = 150e3, 220e3
-    X["Fx_max"], X["Px_max"] = 5600.0, 75e3
-    X["Cd0"], X["Cd1"], X["Cd2"] = 241.0, 25.1, 0.0
-    X["fwd_frac"] = 0.0
+    X["mu"] = o("mu", 0.92)
+    X["Caf"], X["Car"] = o("Caf", 150e3), o("Car", 220e3)
+    X["Fx_max"], X["Px_max"] = o("Fx_max", 5600.0), o("Px_max", 75e3)
+    X["Cd0"], X["Cd1"], X["Cd2"] = o("Cd0", 241.0), o("Cd1", 25.1), o("Cd2", 0.0)
+    X["fwd_frac"] = o("fwd_frac", 0.0)
     X["rwd_frac"] = 1 - X["fwd_frac"]
-    X["fwb_frac"] = 0.6
+    X["fwb_frac"] = o("fwb_frac", 0.6)
     X["rwb_frac"] = 1 - X["fwb_frac"]
     X["Fx_min"] = max(-X["m"] * X["G"] * X["a"] * X["mu"] / (X["L"] * X["rwb_frac"] + X["mu"] * X["h"]),
                       -X["m"] * X["G"] * X["b"] * X["mu"] / (X["L"] * X["fwb_frac"] - X["mu"] * X["h"]))
-    X["delta_max"] = 18 * math.pi / 180
+    X["delta_max"] = o("delta_max", 18 * math.pi / 180)
     X["kappa_max"] = math.tan(X["delta_max"]) / X["L"]
     return X
 
