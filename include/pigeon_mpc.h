@@ -208,6 +208,50 @@ int pg_clear_plant_sets(pg_handle* h);                                    /* bac
  * index does not cover.  n_sets, out and index may each be NULL. */
 int pg_get_plant_sets(pg_handle* h, int32_t* n_sets, pg_vehicle* out, int32_t max_sets, int32_t* index, int32_t B);
 
+/* Sensor sets: the state the CONTROLLER of a rollout step reads, per instance -- tuning x plant x sensor-noise studies as ONE batch.  A library of pg_sensor sets and a
+ * per-instance selection, shaped like pg_set_plant_sets.  On the car `from_autobox` carries an ESTIMATE of (E, N, psi, Ux, Uy, r) (src/ros_integration.jl:48-66); every gate,
+ * projection, linearisation and HJI lookup of the callback runs on it.  With a library installed each step of pg_simulate_dev, pg_simulate_safety_dev and
+ * pg_simulate_node_dev splits the state in two:
+ *   TRUE state      what the plant integrates (also under a plant library), what state_hist records, pg_get_state returns and the tracking summary describes;
+ *   MEASURED state  = true + bias[c] + sigma[c] z[c] per channel, in the library's element type: what everything the controller does in that step reads -- the node gate
+ *                   (the Ux < 1 pause; a NaN), the projection and the time grid in path mode, nodes, linearisation, QP and solve, the HJI relative state, lookup and
+ *                   policy selection (and with them the worst-case human, who is computed from that lookup), the (s, e) a node step publishes.
+ *                   A channel with sigma == 0 and bias == 0 is COPIED: bit-equal, -0.0 and NaN payloads included.
+ * The other car, the commands and the clock are not perturbed.  pg_step*, the five phase calls and pg_node_step_dev never read the sensor library: a caller who owns the
+ * state can perturb it themselves.
+ * The draws depend on nothing but (seed, stream[b], step, channel): z is standard normal from the counter-based generator Philox4x32-10 (the Random123 definition:
+ * multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85, ten rounds) with key = (seed_lo, seed_hi) and counter = (step, j, stream_lo, stream_hi).
+ * step is the rollout clock's step index (the one first_breach and first_exit use: it continues across calls and restarts with the clock); stream[b] is a 64-bit id per
+ * instance, b by default.  Block j = 0 yields words x0..x3: (z_E, z_N) from (x0, x1), (z_psi, z_Ux) from (x2, x3); block j = 1 yields (z_Uy, z_r) from its (x0, x1) (its
+ * x2, x3 are reserved).  A pair (xa, xb) becomes two normals by Box-Muller: u1 = ((xa >> 8) + 0.5) 2^-24, u2 = ((xb >> 8) + 0.5) 2^-24, rho = sqrt(-2 ln u1),
+ * (rho cos 2 pi u2, rho sin 2 pi u2), the transcendentals in the library's arithmetic type.  TRUNCATION: u1 >= 2^-25, so |z| <= sqrt(-2 ln 2^-25) = 5.887.
+ * (u1, u2 are exact in double.  In float n + 0.5 is exact below n = 2^23 only: the fp32 library forms ln u1 of the upper half as log1p of the complement
+ * -(2^24 - n - 0.5) 2^-24, which is exact, and rounds u2 with the angle.)  Consequences: the same instance sees the same noise whatever the batch size or its position
+ * in the batch; a rollout split into two calls continues the sequence; restarting the clock (pg_set_inputs*) replays it; a fresh realisation is a new seed.
+ * Lifetime: a library of ONE set applies to every instance without an index.  With n_sets > 1 the three rollouts return PG_ERR_STATE until an index covering the batch is
+ * installed.  Installing a library drops the previous index; seed and streams persist (also across pg_clear_sensor_sets).  With no library the controller reads the true
+ * state, nothing is allocated and the rollouts queue exactly the launches they queued before this call existed.
+ * No side effects: installing, changing or clearing library, index, seed or streams resets nothing -- solver state and warm starts, the rollout clock, the safety, node and
+ * tracking summaries are untouched, and the captured pg_step graph is not affected.
+ * PG_ERR_INVALID (the handle is left unchanged): n_sets < 1; a non-finite field; sigma[c] < 0; an index entry outside [0, n_sets); B outside [1, batch_capacity].
+ * Cost: one lane-per-instance launch per rollout step (k_measure) ahead of the step's gate and compute kernels, which are handed the measured buffer in place of the state
+ * (no copy, no kernel changed); with the tracking summary on, one more projection launch, of the true state (the step's own projection is the measured one). */
+typedef struct pg_sensor { double sigma[6]; double bias[6]; } pg_sensor;      /* (E, N, psi, Ux, Uy, r) */
+int pg_set_sensor_sets(pg_handle* h, int32_t n_sets, const pg_sensor* sets);
+int pg_set_sensor_index(pg_handle* h, int32_t B, const int32_t* index);          /* index[b] in [0, n_sets) */
+/* seed (default 0) and stream ids: stream [B], or NULL for stream[b] = b; instances the array does not cover keep stream[b] = b.  Needs no library */
+int pg_set_sensor_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream);
+int pg_clear_sensor_sets(pg_handle* h);                                          /* back to measured = true */
+/* the installed library, as pg_get_plant_sets */
+int pg_get_sensor_sets(pg_handle* h, int32_t* n_sets, pg_sensor* out, int32_t max_sets, int32_t* index, int32_t B);
+/* the z the rollouts draw for clock steps [step0, step0 + steps), z [steps][B][6] on the host, computed ON THE DEVICE by the function k_measure calls (k_sensor_draws) --
+ * what pg_simulate_clock is to the clock.  Reads seed and streams only: needs no library and no inputs.  step0 >= 0, steps >= 1, B in [1, batch_capacity] */
+int pg_sensor_draws(pg_handle* h, int32_t step0, int32_t steps, int32_t B, double* z);
+/* measured [B][6] of the last rollout step that ran under a library; PG_ERR_STATE before one (installing inputs or clearing the library forgets it) */
+int pg_get_measured_state(pg_handle* h, double* measured);
+/* the NEXT rollout call writes the measured state of its step k < steps to buf[k][B][6] (library element type); one-shot -- that call consumes the registration whether it succeeds or returns an error --; NULL cancels.  PG_ERR_STATE without a library */
+int pg_set_measured_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -380,6 +424,7 @@ int pg_synchronize(pg_handle* h);
  *     "phase_timing" 0/1 (0)     1 = pg_step_dev records the HIP events pg_get_phase_ms reads (four event records per step on the handle's stream: measured 13-25 us per step, 2-4 % of a
  *                                4096-instance step); 0 = no instrumentation, pg_get_phase_ms returns PG_ERR_STATE
  *     "graph" 0/1 (0)            pg_step of a small warm batch as one hipGraph launch (see pg_step)
+ *     "stat_sensor_steps"        (read-only) rollout steps that ran under a sensor library (k_measure launches) since pg_create
  *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact

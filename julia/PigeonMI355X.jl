@@ -199,6 +199,46 @@ function tracking_summary(mpc::BatchedTrajectoryTrackingMPC)
     summary, steps, first_exit
 end
 
+# Sensor sets (pg_set_sensor_sets ...): seeded measurement noise in the three rollouts.  NOT EXECUTED in the build container, like the rest of this file.
+"One sensor: per channel of (E, N, psi, Ux, Uy, r) a standard deviation and a constant bias (pg_sensor)"
+struct PgSensor
+    sigma::NTuple{6,Float64}
+    bias::NTuple{6,Float64}
+end
+PgSensor(; sigma=zeros(6), bias=zeros(6)) = PgSensor(Tuple(Float64.(sigma)), Tuple(Float64.(bias)))
+"What the CONTROLLER of a rollout step reads in place of the true state: measured = true + bias + sigma z per channel (the plant, the records and the tracking summary keep the truth).  A library of sensors, the set each instance runs under (0-based; may be empty for a library of one), the seed and the 64-bit stream ids of the draws (empty: stream[b] = b).  Resets nothing."
+function set_sensors!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgSensor}, index::Vector{Int32}=Int32[]; seed::UInt64=UInt64(0), streams::Vector{UInt64}=UInt64[])
+    check(mpc, ccall(sym(mpc, :pg_set_sensor_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgSensor}), mpc.handle, length(sets), sets), "pg_set_sensor_sets")
+    isempty(index) || check(mpc, ccall(sym(mpc, :pg_set_sensor_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_sensor_index")
+    check(mpc, ccall(sym(mpc, :pg_set_sensor_seed), Cint, (Ptr{Cvoid}, UInt64, Int32, Ptr{UInt64}), mpc.handle, seed, isempty(streams) ? max(mpc.B, 1) : length(streams),
+                     isempty(streams) ? C_NULL : streams), "pg_set_sensor_seed")
+end
+"back to measured = true"
+clear_sensors!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_sensor_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_sensor_sets")
+"(sets, index over the first B instances; -1 where no index covers an instance) as installed"
+function sensors(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_sensor_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgSensor}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_sensor_sets")
+    sets = Vector{PgSensor}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_sensor_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgSensor}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_sensor_sets")
+    sets, index
+end
+"The standard normals the rollouts draw at clock steps step0 .. step0 + steps - 1 (0-based), 6 x B x steps, computed on the device by the function the rollouts call"
+function sensor_draws(mpc::BatchedTrajectoryTrackingMPC, step0::Integer, steps::Integer, B::Integer=mpc.B)
+    z = zeros(6, B, steps)
+    check(mpc, ccall(sym(mpc, :pg_sensor_draws), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}), mpc.handle, step0, steps, B, z), "pg_sensor_draws")
+    z
+end
+"6 x B: what the controller read at the last rollout step under a sensor library"
+function measured_state(mpc::BatchedTrajectoryTrackingMPC)
+    m = zeros(6, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_measured_state), Cint, (Ptr{Cvoid}, Ptr{Float64}), mpc.handle, m), "pg_get_measured_state")
+    m
+end
+"The NEXT rollout call writes the measured state of its step k < steps to a device array 6 x B x steps of the library's element type (one-shot; C_NULL cancels)"
+set_measured_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_measured_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_measured_history_dev")
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

@@ -46,6 +46,14 @@ struct pg_handle {
     // tracking summary (option "tracking_summary"; pg_get_tracking_state): [cap][6] sums, steps [cap] then first_exit [cap] (k_track), allocated when the option is first used
     int tracking = 0; real* d_track = nullptr; int* d_track_i = nullptr;
     bool track_fresh = true;                                  // the tracking summary restarts at the next rollout step (the clock restarted since it was last written)
+    // sensor library (pg_set_sensor_sets / pg_set_sensor_index / pg_set_sensor_seed): what the controller of a rollout step is handed in place of the true state.  Device: the
+    // records, the index, the stream ids [cap] (uploaded when a rollout or pg_sensor_draws first needs them and whenever they changed), the measured state d_meas [cap][6] and,
+    // with the tracking summary, the projection of the TRUE state d_sep_true [cap][4].  Host: sets, index and streams as installed.  Nothing is allocated without a library
+    DevSensor* d_sens = nullptr; int* d_sens_idx = nullptr; int sens_idx_B = 0; unsigned long long* d_sens_stream = nullptr; bool sens_stream_dirty = true;
+    std::vector<pg_sensor> sens_sets; std::vector<int32_t> sens_index; std::vector<uint64_t> sens_stream; uint64_t sens_seed = 0;
+    real *d_meas = nullptr, *d_sep_true = nullptr; bool meas_valid = false;
+    real* meas_hist = nullptr; int meas_hist_steps = 0;          // pg_set_measured_history_dev: one-shot, consumed by the next rollout call
+    int64_t stat_sensor_steps = 0;                                // read-only option "stat_sensor_steps"
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -298,7 +306,7 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_cp_sets, h->d_cp_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_plants, h->d_plant_idx, h->d_track, h->d_track_i};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_plants, h->d_plant_idx, h->d_track, h->d_track_i, h->d_sens, h->d_sens_idx, h->d_sens_stream, h->d_meas, h->d_sep_true};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
@@ -516,6 +524,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "lat_wtau") return R(&C.lat_wtau, 1e-300, 1e300);
     // read-only launch statistics of this handle
     if (n == "stat_pipelined_launches") return S(&h->stat_pipelined);
+    if (n == "stat_sensor_steps") return S(&h->stat_sensor_steps);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -808,6 +817,118 @@ int pg_get_plant_sets(pg_handle* h, int32_t* n_sets, pg_vehicle* out, int32_t ma
     return PG_OK;
 }
 
+// ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
+// solver state: nothing is reset ----
+static const char* sensor_set_problem(const pg_sensor& s) {
+    for (int c = 0; c < 6; c++) {
+        if (!std::isfinite(s.sigma[c]) || !std::isfinite(s.bias[c])) return "a set has a non-finite field";
+        if (s.sigma[c] < 0.0) return "a set needs sigma >= 0";
+    }
+    return nullptr;
+}
+int pg_set_sensor_sets(pg_handle* h, int32_t n_sets, const pg_sensor* sets) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, n_sets >= 1 && sets, "pg_set_sensor_sets: need n_sets >= 1 and the sets");
+    for (int k = 0; k < n_sets; k++) { const char* why = sensor_set_problem(sets[k]); REQUIRE(h, !why, std::string("pg_set_sensor_sets: ") + why); }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
+    std::vector<DevSensor> recs((size_t)n_sets);
+    for (int k = 0; k < n_sets; k++) for (int c = 0; c < 6; c++) { recs[(size_t)k].sigma[c] = (real)sets[k].sigma[c]; recs[(size_t)k].bias[c] = (real)sets[k].bias[c]; }
+    DevSensor* d_new = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(DevSensor)));
+    if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(DevSensor), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = "pg_set_sensor_sets: copy failed"; return PG_ERR_HIP; }
+    if (h->d_sens) (void)hipFree(h->d_sens);
+    h->d_sens = d_new; h->sens_sets.assign(sets, sets + n_sets);
+    h->sens_index.clear(); h->sens_idx_B = 0;                   // installing a library drops the previous index (seed and streams persist)
+    return PG_OK;
+}
+int pg_set_sensor_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    const int n = (int)h->sens_sets.size();
+    REQUIRE(h, n >= 1, "pg_set_sensor_index: no sensor library installed");
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_sensor_index: need 1 <= B <= batch_capacity and an index array");
+    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < n, "pg_set_sensor_index: index out of range of the installed library");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!h->d_sens_idx) HIPCHK(h, hipMalloc((void**)&h->d_sens_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
+    // (the whole array is rewritten: entries beyond the indexed batch select set 0 -- never an address outside the library)
+    std::vector<int> full((size_t)h->cfg.batch_capacity, 0);
+    for (int b = 0; b < B; b++) full[(size_t)b] = index[b];
+    HIPCHK(h, hipMemcpy(h->d_sens_idx, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->sens_index.assign(index, index + B); h->sens_idx_B = B;
+    return PG_OK;
+}
+int pg_set_sensor_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_set_sensor_seed: need 1 <= B <= batch_capacity");
+    h->sens_seed = seed;                                        // (a launch argument: a rollout already queued keeps the seed it was launched with)
+    if (stream) h->sens_stream.assign(stream, stream + B); else h->sens_stream.clear();      // instances the array does not cover: stream[b] = b
+    h->sens_stream_dirty = true;
+    return PG_OK;
+}
+int pg_clear_sensor_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_sens) { (void)hipFree(h->d_sens); h->d_sens = nullptr; }
+    h->sens_sets.clear(); h->sens_index.clear(); h->sens_idx_B = 0; h->meas_valid = false; h->meas_hist = nullptr; h->meas_hist_steps = 0;
+    return PG_OK;
+}
+int pg_get_sensor_sets(pg_handle* h, int32_t* n_sets, pg_sensor* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), "pg_get_sensor_sets: need max_sets >= 0 and 0 <= B <= batch_capacity");
+    const int n = (int)h->sens_sets.size();
+    if (n_sets) *n_sets = n;
+    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = h->sens_sets[(size_t)k];
+    if (index) for (int b = 0; b < B; b++) index[b] = b < h->sens_idx_B ? h->sens_index[(size_t)b] : -1;
+    return PG_OK;
+}
+// the stream ids on the device, [capacity]: the installed ones, then stream[b] = b
+static int sensor_streams_sync(pg_handle* h) {
+    if (h->d_sens_stream && !h->sens_stream_dirty) return PG_OK;
+    const size_t cap = (size_t)h->cfg.batch_capacity;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!h->d_sens_stream) HIPCHK(h, hipMalloc((void**)&h->d_sens_stream, cap * sizeof(unsigned long long)));
+    std::vector<unsigned long long> full(cap);
+    for (size_t b = 0; b < cap; b++) full[b] = b < h->sens_stream.size() ? (unsigned long long)h->sens_stream[b] : (unsigned long long)b;
+    HIPCHK(h, hipMemcpy(h->d_sens_stream, full.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    h->sens_stream_dirty = false;
+    return PG_OK;
+}
+int pg_sensor_draws(pg_handle* h, int32_t step0, int32_t steps, int32_t B, double* z) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, step0 >= 0 && steps >= 1 && z, "pg_sensor_draws: need step0 >= 0, steps >= 1 and the output array");
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_sensor_draws: need 1 <= B <= batch_capacity");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = sensor_streams_sync(h); if (rc) return rc;
+    const size_t n = (size_t)steps * (size_t)B * 6;
+    real* d = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d, n * sizeof(real)));
+    hipLaunchKernelGGL(k_sensor_draws, dim3((unsigned)(((size_t)steps * B + 63) / 64)), dim3(64), 0, h->stream, (int)B, (int)step0, (int)steps, h->d_sens_stream, (unsigned long long)h->sens_seed, d);
+    std::vector<real> tmp(n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), d, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { h->err = std::string("pg_sensor_draws: ") + hipGetErrorString(e); return PG_ERR_HIP; }
+    for (size_t i = 0; i < n; i++) z[i] = (double)tmp[i];
+    return PG_OK;
+}
+int pg_set_measured_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
+    if (!h) return PG_ERR_INVALID;
+    if (!buf) { h->meas_hist = nullptr; h->meas_hist_steps = 0; return PG_OK; }
+    REQUIRE(h, steps >= 1, "pg_set_measured_history_dev: steps >= 1 required");
+    if (h->sens_sets.empty()) { h->err = "pg_set_measured_history_dev: no sensor library installed (the measured state is the true one: record state_hist)"; return PG_ERR_STATE; }
+    h->meas_hist = (real*)buf; h->meas_hist_steps = steps;
+    return PG_OK;
+}
+static int check_ready(pg_handle* h);
+int pg_get_measured_state(pg_handle* h, double* measured) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!h->meas_valid || !h->d_meas) { h->err = "pg_get_measured_state: no rollout step under a sensor library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, measured, h->d_meas, (size_t)h->B * 6);
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -879,7 +1000,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1404,7 +1525,38 @@ static int rollout_ready(pg_handle* h) {
         HIPCHK(h, hipMalloc((void**)&h->d_track, cap * 6 * sizeof(real)));
         HIPCHK(h, hipMalloc((void**)&h->d_track_i, cap * 2 * sizeof(int)));
     }
+    if (!h->sens_sets.empty()) {
+        if (h->sens_sets.size() > 1 && h->sens_idx_B < h->B) { h->err = "a sensor library is installed but pg_set_sensor_index does not cover the batch"; return PG_ERR_STATE; }
+        const size_t cap = cap_of(h);
+        if (!h->d_meas) HIPCHK(h, hipMalloc((void**)&h->d_meas, cap * 6 * sizeof(real)));
+        if (h->tracking && !h->d_sep_true) HIPCHK(h, hipMalloc((void**)&h->d_sep_true, cap * 4 * sizeof(real)));
+        const int rc = sensor_streams_sync(h); if (rc) return rc;
+    }
     return PG_OK;
+}
+// the sensor library (the host knows whether one is installed: that alone adds k_measure to a rollout step).  sensor_take_history: the one-shot registration of
+// pg_set_measured_history_dev, consumed by the rollout call that starts now
+static bool sensor_lib_on(const pg_handle* h) { return !h->sens_sets.empty(); }
+struct MeasHist { real* buf; int steps; };
+static MeasHist sensor_take_history(pg_handle* h) { const MeasHist m{h->meas_hist, h->meas_hist_steps}; h->meas_hist = nullptr; h->meas_hist_steps = 0; return m; }
+// the controller's side of one rollout step: the node gate (node rollout) and the compute calls.  Under a sensor library k_measure writes the measured state of clock step
+// `step` first, and the handle's state pointer names THAT buffer while the gate and the compute kernels are queued -- they all take the state from the handle --, then the true
+// one again for the summary, the records and the plant: no copy, no restore launch, no kernel changed.  Without a library: the gate and the compute calls, nothing else
+static int node_gate(pg_handle* h, const uint8_t* pre_flag);
+static int rollout_compute(pg_handle* h, int step, int k, const MeasHist& mh, bool gate, const uint8_t* pre_flag) {
+    int rc;
+    if (!sensor_lib_on(h)) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
+    const int B = h->B;
+    const SensorLib lib{h->d_sens, h->sens_sets.size() > 1 ? h->d_sens_idx : (const int*)nullptr, h->d_sens_stream, (unsigned long long)h->sens_seed};
+    hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, h->d_meas, (mh.buf && k < mh.steps) ? mh.buf + (size_t)k * B * 6 : (real*)nullptr);
+    LAUNCH_CHECK(h);
+    h->meas_valid = true; h->stat_sensor_steps++;
+    real* const true_state = h->d_state;
+    h->d_state = h->d_meas;
+    rc = gate ? node_gate(h, pre_flag) : PG_OK;
+    if (!rc) rc = step_compute(h);
+    h->d_state = true_state;
+    return rc;
 }
 // the plant library as the *_plant kernels take it (the host knows whether one is installed: that alone picks the kernel)
 static bool plant_lib_on(const pg_handle* h) { return !h->plant_sets.empty(); }
@@ -1413,7 +1565,14 @@ static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->d_plants, h->
 static int launch_track(pg_handle* h, int step) {
     if (!h->tracking) { h->track_fresh = true; return PG_OK; }      // (off: no launch; steps that went unseen must not be continued when it comes back on)
     const int B = h->B;
-    hipLaunchKernelGGL(k_track, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)h->track_fresh, step, h->d_state, h->d_sep, h->d_track, h->d_track_i, h->d_track_i + cap_of(h));
+    const real* sep = h->d_sep;
+    if (sensor_lib_on(h)) {      // d_sep holds the projection of the MEASURED state (the node publishes its (s, e)): the summary describes the true one, projected once more
+        hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep_true, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
+                           (double*)nullptr, (int*)nullptr, 0, (int*)nullptr, (int*)nullptr, 0);
+        LAUNCH_CHECK(h);
+        sep = h->d_sep_true;
+    }
+    hipLaunchKernelGGL(k_track, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)h->track_fresh, step, h->d_state, sep, h->d_track, h->d_track_i, h->d_track_i + cap_of(h));
     LAUNCH_CHECK(h);
     h->track_fresh = false;
     return PG_OK;
@@ -1426,6 +1585,7 @@ static int clock_start(pg_handle* h, double dt) {
     return PG_OK;
 }
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev_, void* control_hist_dev_) {
+    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};      // one-shot: THIS call consumes the registration, also when it fails below
     int rc = check_ready(h); if (rc) return rc;
     if ((rc = check_rollout_args(h, "pg_simulate_dev", steps, dt, 0, nullptr)) || (rc = rollout_ready(h))) return rc;
     const int B = h->B;
@@ -1434,7 +1594,7 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
     for (int k = 0; k < steps; k++) {
         if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(state_hist_dev + (size_t)k * B * 6, h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // push!(qs, state) :88
         if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(control_hist_dev + (size_t)k * B * 3, h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream)); // push!(us, control) :89
-        if ((rc = step_compute(h))) return rc;                                                        // :90-93
+        if ((rc = rollout_compute(h, h->sim_idx - 1, k, mh, false, nullptr))) return rc;              // :90-93 (on the measured state under a sensor library)
         if ((rc = launch_track(h, h->sim_idx - 1))) return rc;
         h->sim_idx++;                                                                                                                                         // (t0 now holds element sim_idx of the clock)
         if (plant_lib_on(h)) hipLaunchKernelGGL(k_advance_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, plant_lib(h));
@@ -1448,6 +1608,7 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
 // lookup d_vg8), then ONE launch for the records, the selection, both plants, the new control, the clock and the summary
 int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev_,
                            void* state_hist_dev_, void* control_hist_dev_, void* other_hist_dev_, void* human_hist_dev_, void* V_hist_dev_, int32_t* source_hist_dev) {
+    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};      // one-shot: THIS call consumes the registration, also when it fails below
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED) { h->err = "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row"; return PG_ERR_STATE; }
     if ((rc = check_rollout_args(h, "pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev_)) || (rc = rollout_ready(h))) return rc;
@@ -1456,8 +1617,8 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
     real *sh = (real*)state_hist_dev_, *ch = (real*)control_hist_dev_, *oh = (real*)other_hist_dev_, *hh = (real*)human_hist_dev_, *vh = (real*)V_hist_dev_;
     if ((rc = clock_start(h, dt))) return rc;
     for (int k = 0; k < steps; k++) {
-        if ((rc = step_compute(h))) return rc;                                                        // :90-93
         const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
+        if ((rc = rollout_compute(h, step, k, mh, false, nullptr))) return rc;                        // :90-93
         if ((rc = launch_track(h, step))) return rc;
         h->sim_idx++;
         SafetyIO io{human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr, sh ? sh + (size_t)k * Bz * 6 : nullptr, ch ? ch + (size_t)k * Bz * 3 : nullptr,
@@ -1567,6 +1728,7 @@ int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_fl
 // command, the clock, the summary and the counts (k_node_finish<true>)
 int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev_, const uint8_t* pre_flag_dev,
                          void* state_hist_dev_, void* applied_hist_dev_, int32_t* event_hist_dev, void* V_hist_dev_) {
+    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};      // one-shot: THIS call consumes the registration, also when it fails below
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
     if ((rc = check_rollout_args(h, "pg_simulate_node_dev", steps, dt, human_mode, human_u_dev_)) || (rc = rollout_ready(h))) return rc;
@@ -1579,8 +1741,8 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
     if (restart) HIPCHK(h, hipMemcpyAsync(h->d_applied, h->d_control, Bz * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // the applied command starts as the message
     const int has = (int)(h->has_hji && h->dc.formulation == PG_COUPLED);
     for (int k = 0; k < steps; k++) {
-        if ((rc = node_gate(h, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr)) || (rc = step_compute(h))) return rc;
         const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
+        if ((rc = rollout_compute(h, step, k, mh, true, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr))) return rc;
         if ((rc = launch_track(h, step))) return rc;                                                  // (every step counts, gated out or not: the plant moves either way)
         h->sim_idx++;
         NodeIO io = node_io(h);

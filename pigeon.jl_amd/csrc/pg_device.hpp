@@ -650,4 +650,52 @@ PG_DEV void advance_unicycle(real* x, real w, real a, real h, int nsub) {
     }
 }
 
+// ---- measurement noise of the rollouts (pg_set_sensor_sets; build-defined: the reference's node receives its estimate from the car) ----
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 definition): a counter-based generator, so a draw is
+// a pure function of (key, counter) -- no state to carry, no dependence on the batch.  Plain C++: two 32 x 32 -> 64 multiplies per round.
+PG_DEV void philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;                             // (the Weyl bump between rounds; the one behind the last round is dead)
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// two words -> two standard normals (Box-Muller): u = ((x >> 8) + 0.5) 2^-24 in (0, 1), rho = sqrt(-2 ln u1), (rho cos 2 pi u2, rho sin 2 pi u2).  u1 >= 2^-25, so
+// |z| <= sqrt(-2 ln 2^-25) = 5.887: the tails beyond that are cut off (probability 4e-9 per draw).  Transcendentals in `real`.
+// n + 0.5 with n < 2^24 has 25 significant bits: exact in double, but in float only below 2^23.  The fp32 library therefore takes ln u1 of the upper half from the
+// complement, ln u1 = log1p(-(2^24 - n - 0.5) 2^-24), whose argument IS exact (else rho near u1 = 1, where it is sqrt(2 (1 - u1)), would lose all its digits);
+// u2 is rounded to float with the angle it scales (2^-25 relative, below the rounding of the angle itself).
+PG_DEV void box_muller(uint32_t xa, uint32_t xb, real& za, real& zb) {
+    const uint32_t n1 = xa >> 8, n2 = xb >> 8;
+#ifdef PG_F32
+    const float l1 = n1 < (1u << 23) ? logf(((float)n1 + 0.5f) * 0x1p-24f) : log1pf(-(((float)((1u << 24) - n1) - 0.5f) * 0x1p-24f));
+    const float rho = sqrtf(-2.0f * l1);
+    const float u2 = ((float)n2 + 0.5f) * 0x1p-24f;
+    float s, c; sincosf(6.28318530717958647692f * u2, &s, &c);
+#else
+    const double rho = sqrt(-2.0 * log(((double)n1 + 0.5) * 0x1p-24));
+    const double u2 = ((double)n2 + 0.5) * 0x1p-24;
+    double s, c; sincos(6.28318530717958647692 * u2, &s, &c);
+#endif
+    za = rho * c; zb = rho * s;
+}
+// the six draws of one (seed, stream, step): key = (seed_lo, seed_hi), counter = (step, j, stream_lo, stream_hi); block j = 0 gives (z_E, z_N) from (x0, x1) and
+// (z_psi, z_Ux) from (x2, x3), block j = 1 gives (z_Uy, z_r) from its (x0, x1) (x2, x3 of block 1 are reserved)
+PG_DEV void sensor_draws(uint64_t seed, uint64_t stream, uint32_t step, real z[6]) {
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t ctr[4] = {step, 0u, (uint32_t)stream, (uint32_t)(stream >> 32)}, x[4];
+    philox4x32_10(ctr, key, x);
+    box_muller(x[0], x[1], z[0], z[1]);
+    box_muller(x[2], x[3], z[2], z[3]);
+    ctr[1] = 1u;
+    philox4x32_10(ctr, key, x);
+    box_muller(x[0], x[1], z[4], z[5]);
+}
+// one set of a sensor library (pg_set_sensor_sets) in the arithmetic type of the build, channels (E, N, psi, Ux, Uy, r)
+struct DevSensor { real sigma[6], bias[6]; };
+
 }  // namespace pg

@@ -1063,6 +1063,36 @@ __global__ __launch_bounds__(64) void k_track(DevCfg C, int B, int restart, int 
     steps[b] = n + 1; first_exit[b] = fx;
 }
 
+// Sensor library (pg_set_sensor_sets), lane = instance: the MEASURED state of a rollout step, measured = true + bias + sigma z per channel of (E, N, psi, Ux, Uy, r),
+// written to a buffer of its own (and to the step's row of the measured history when one is registered).  The true state is only read: the plant kernel, the records
+// and k_track keep it; the gate and the compute kernels of the step are handed `meas` in its place.  z = sensor_draws(seed, stream[b], step): a function of the
+// instance's stream id and the clock's step index alone (not of b, not of B).  A channel with sigma == 0 and bias == 0 is COPIED (no arithmetic: -0.0 and NaN payloads
+// survive); a lane whose six sigmas are all zero draws nothing.  idx == nullptr: a library of one, every lane reads record 0.
+struct SensorLib { const DevSensor* sets; const int* idx; const unsigned long long* stream; unsigned long long seed; };
+__global__ __launch_bounds__(64) void k_measure(int B, int step, SensorLib lib, const real* __restrict__ state, real* __restrict__ meas, real* __restrict__ hist) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevSensor S = lib.sets[lib.idx ? lib.idx[b] : 0];
+    bool noisy = false;
+    for (int c = 0; c < 6; c++) noisy = noisy || S.sigma[c] != real(0.0);
+    real z[6] = {real(0.0), real(0.0), real(0.0), real(0.0), real(0.0), real(0.0)};
+    if (noisy) sensor_draws(lib.seed, lib.stream[b], (uint32_t)step, z);
+    for (int c = 0; c < 6; c++) {
+        const real x = state[(size_t)b * 6 + c];
+        const real m = (S.sigma[c] == real(0.0) && S.bias[c] == real(0.0)) ? x : (x + S.bias[c]) + S.sigma[c] * z[c];
+        meas[(size_t)b * 6 + c] = m;
+        if (hist) hist[(size_t)b * 6 + c] = m;
+    }
+}
+// pg_sensor_draws: z [steps][B][6] of the clock steps [step0, step0 + steps) through the function k_measure calls, lane = (step, instance)
+__global__ __launch_bounds__(64) void k_sensor_draws(int B, int step0, int steps, const unsigned long long* __restrict__ stream, unsigned long long seed, real* __restrict__ z) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)steps * B) return;
+    const int k = (int)(i / B), b = (int)(i % B);
+    real d[6]; sensor_draws(seed, stream[b], (uint32_t)step0 + (uint32_t)k, d);      // (added as unsigned: the counter word wraps, no signed overflow)
+    for (int c = 0; c < 6; c++) z[(size_t)i * 6 + c] = d[c];
+}
+
 // ==================================================================================================================
 // Decoupled (lateral) formulation: decoupled_lat_long.jl.  The lateral QP (state (Uy, r, dpsi, e), input delta) is EMBEDDED in the
 // 8-state stage structure k_solve works on: x = (0, Ux_dummy, Uy, r, dpsi, e, delta, 0) with identity dynamics, zero cost and

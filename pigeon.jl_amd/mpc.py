@@ -242,6 +242,79 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_tracking_state(self.h, _p(sm), _p(n, C.POINTER(C.c_int32)), _p(fx, C.POINTER(C.c_int32))), "pg_get_tracking_state")
         return sm, n, fx
 
+    # ---- the SENSOR of the rollouts, per instance (measurement noise): a library of (sigma, bias) sets, a per-instance selection, a seed and stream ids ----
+    SENSOR_CHANNELS = ("E", "N", "psi", "Ux", "Uy", "r")
+
+    def pack_sensors(self, sets):
+        """sensor dicts {"sigma": [6] or {channel: value}, "bias": ...} (missing: 0), (sigma, bias) pairs or pg_sensor structures -> a ctypes array of pg_sensor."""
+        def six(v):
+            if v is None:
+                return [0.0] * 6
+            if isinstance(v, dict):
+                return [float(v.get(c, 0.0)) for c in self.SENSOR_CHANNELS]
+            return [float(x) for x in np.asarray(v, dtype=np.float64).reshape(6)]
+        sets = list(sets)
+        arr = (_lib.pg_sensor * len(sets))()
+        for k, v in enumerate(sets):
+            if isinstance(v, _lib.pg_sensor):
+                C.memmove(C.byref(arr[k]), C.byref(v), C.sizeof(_lib.pg_sensor))
+                continue
+            sg, bs = (v.get("sigma"), v.get("bias")) if isinstance(v, dict) else v
+            arr[k].sigma[:] = six(sg); arr[k].bias[:] = six(bs)
+        return arr
+
+    def set_sensors(self, sets, index=None, seed=0, streams=None):
+        """What the controller of simulate_ / simulate_safety_ / simulate_node_ reads in place of the true state (pg_set_sensor_sets): measured = true + bias + sigma z per
+        channel of (E, N, psi, Ux, Uy, r).  One set (dict / structure) for the whole batch, or a list of sets selected per instance with `index`; `seed` and the 64-bit
+        `streams` [B] (None: stream[b] = b) fix the draws (pg_set_sensor_seed).  Resets nothing.  Unlike the C calls, where seed and streams persist across installs, EVERY call here
+        installs seed and streams too: re-installing a library without them puts the seed back to 0 and the streams back to b (set_sensor_seed afterwards, or pass them again)."""
+        if isinstance(sets, (dict, _lib.pg_sensor)):
+            sets = [sets]
+        arr = self.pack_sensors(sets)
+        self._chk(self.lib.pg_set_sensor_sets(self.h, len(arr), arr), "pg_set_sensor_sets")
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.int32)
+            self._chk(self.lib.pg_set_sensor_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_sensor_index")
+        self.set_sensor_seed(seed, streams)
+
+    def set_sensor_seed(self, seed=0, streams=None):
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
+        self._chk(self.lib.pg_set_sensor_seed(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), "pg_set_sensor_seed")
+
+    def clear_sensors(self):
+        self._chk(self.lib.pg_clear_sensor_sets(self.h), "pg_clear_sensor_sets")
+
+    def sensors(self):
+        """(list of {"sigma": [6], "bias": [6]}, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        n = C.c_int32(0)
+        self._chk(self.lib.pg_get_sensor_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_sensor_sets")
+        arr = (_lib.pg_sensor * max(n.value, 1))()
+        index = np.full(self.B, -1, dtype=np.int32)
+        self._chk(self.lib.pg_get_sensor_sets(self.h, C.byref(n), arr, n.value, _p(index, C.POINTER(C.c_int32)), self.B), "pg_get_sensor_sets")
+        return [{"sigma": list(arr[k].sigma), "bias": list(arr[k].bias)} for k in range(n.value)], index
+
+    def sensor_draws(self, step0, steps, B=None):
+        """The standard normals z [steps][B][6] the rollouts draw at clock steps [step0, step0 + steps), computed on the device by the function k_measure calls (pg_sensor_draws)."""
+        B = self.B if B is None else int(B)
+        z = np.zeros((int(steps), B, 6))
+        self._chk(self.lib.pg_sensor_draws(self.h, int(step0), int(steps), B, _p(z)), "pg_sensor_draws")
+        return z
+
+    def measured_state(self):
+        """[B][6]: what the controller read at the last rollout step under a sensor library (pg_get_measured_state)."""
+        m = np.zeros((self.B, 6))
+        self._chk(self.lib.pg_get_measured_state(self.h, _p(m)), "pg_get_measured_state")
+        return m
+
+    def _measured_hist(self, measured, steps):
+        """registers a [steps][B][6] device record of the measured state with the next rollout call (pg_set_measured_history_dev); None unless asked for"""
+        if not measured:
+            return None
+        import torch
+        buf = torch.empty(int(steps), self.B, 6, dtype=torch.float32 if self.precision == "f32" else torch.float64, device=f"cuda:{self.cfg.device}")
+        self._chk(self.lib.pg_set_measured_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_measured_history_dev")
+        return buf
+
     # ---- mpc.HJI_cache = HJICache(...) (Pigeon.jl:40) ----
     def set_hji_cache(self, grid_knots, V_raw, gradV_raw):
         dims = np.array([len(k) for k in grid_knots], dtype=np.int32)
@@ -320,11 +393,13 @@ class BatchedTrajectoryTrackingMPC:
     def step_dev(self, u_out_ptr=None):
         self._chk(self.lib.pg_step_dev(self.h, C.c_void_p(u_out_ptr) if u_out_ptr else None), "pg_step_dev")
 
-    def simulate_(self, steps, dt=0.01, record=False):
+    def simulate_(self, steps, dt=0.01, record=False, measured=False):
         """simulate (model_predictive_control.jl:80-100) on the device from the inputs last installed; returns (state, control, t) after `steps`
-        steps and, with record=True, the histories qs [steps][B][6], us [steps][B][3] (the values pushed at :88-89)."""
+        steps and, with record=True, the histories qs [steps][B][6], us [steps][B][3] (the values pushed at :88-89).  measured=True (a sensor library is installed)
+        appends the measured history [steps][B][6] to what is returned."""
         import ctypes as C_
         qh = uh = None; dq = du = None
+        mbuf = self._measured_hist(measured, steps)
         if record:
             import torch
             tdt = torch.float32 if self.precision == "f32" else torch.float64         # device records have the library's own element type
@@ -334,15 +409,18 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
         if record:
             qh = dq.cpu().numpy().astype(np.float64); uh = du.cpu().numpy().astype(np.float64)
+        if mbuf is not None:
+            return s, c, t, qh, uh, mbuf.cpu().numpy().astype(np.float64)
         return s, c, t, qh, uh
 
     HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
 
-    def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False):
+    def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False, measured=False):
         """Safety rollout (pg_simulate_safety_dev): simulate with the control the ROS node sends (ros_integration.jl:114-124) fed back, against an other car that moves.
         human: "hold" (omega, a) = (0, 0), "worst" optimal_disturbance (HJI_computation.jl:90-131), "script" human_u [steps][B][2] = (omega, a).  Returns (state, control, t,
         other) after `steps` steps and, with record=True, a dict of histories: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B],
-        source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step."""
+        source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step.
+        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned."""
         import ctypes as C_
         import torch
         assert human in self.HUMAN_MODES, human
@@ -358,17 +436,19 @@ class BatchedTrajectoryTrackingMPC:
         if record:
             hist["source"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
         ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+        mbuf = self._measured_hist(measured, steps)
         self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C_.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
                                                   *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
         s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
         self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
+        tail = () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
         if not record:
-            return s, c, t, o
+            return (s, c, t, o) + tail
         out = {k: v.cpu().numpy() for k, v in hist.items()}
         for k in shapes:
             out[k] = out[k].astype(np.float64)
-        return s, c, t, o, out
+        return (s, c, t, o, out) + tail
 
     def safety_summary(self):
         """Per instance since the rollout's clock last restarted: (V_min [B], first_breach [B] (first step index with V <= 0, -1: none), policy_steps [B])."""
@@ -402,10 +482,11 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_state(self.h, None, _p(c), None), "pg_get_state")
         return cmd.cpu().numpy().astype(np.float64), se.cpu().numpy().astype(np.float64), ev.cpu().numpy(), c
 
-    def simulate_node_(self, steps, dt=0.01, use_HJI_policy=False, human="hold", human_u=None, pre_flag=None, record=False):
+    def simulate_node_(self, steps, dt=0.01, use_HJI_policy=False, human="hold", human_u=None, pre_flag=None, record=False, measured=False):
         """The node's closed loop (pg_simulate_node_dev): per step the gates, the compute calls, the callback's decision (NaN fallback included), the ego plant driven by the
         APPLIED command of the step's start, the other car as simulate_safety_.  pre_flag [steps][B] (None: engaged).  Returns (state, message, t, other, applied) after `steps`
-        steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event)."""
+        steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event).
+        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned."""
         import ctypes as C_
         import torch
         assert human in self.HUMAN_MODES, human
@@ -422,18 +503,20 @@ class BatchedTrajectoryTrackingMPC:
         if record:
             hist["event"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
         ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+        mbuf = self._measured_hist(measured, steps)
         self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C_.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),
                                                 *(ptr(hist.get(k)) for k in ("state", "applied", "event", "V"))), "pg_simulate_node_dev")
         s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4)); a = np.zeros((self.B, 3))
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
         self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
         self._chk(self.lib.pg_get_node_state(self.h, _p(a), None, None), "pg_get_node_state")
+        tail = () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
         if not record:
-            return s, c, t, o, a
+            return (s, c, t, o, a) + tail
         out = {k: v.cpu().numpy() for k, v in hist.items()}
         for k in shapes:
             out[k] = out[k].astype(np.float64)
-        return s, c, t, o, a, out
+        return (s, c, t, o, a, out) + tail
 
     def node_summary(self):
         """(applied [B][3], heartbeat [B], counts [B][4] = steps with pre_flag off / outside the window / low speed / NaN fallback since the clock last restarted)."""
