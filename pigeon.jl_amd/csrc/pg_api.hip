@@ -13,6 +13,19 @@
 
 using namespace pg;
 
+// One per-instance selection into a library: the device array [capacity] (entries beyond the covered batch select set 0) and the index as the caller installed it.
+// `what` / `setter` name the library and its entry point in the messages
+struct IndexArray {
+    const char *what, *setter; int* d = nullptr; std::vector<int32_t> host;
+    int covered() const { return (int)host.size(); }
+    void release() { if (d) (void)hipFree(d); d = nullptr; host.clear(); }
+};
+// One library of per-instance sets: the sets as the caller installed them, their device records, the selection (setlib_install / setlib_clear / setlib_get below)
+template <class Host, class Dev> struct SetLib {
+    IndexArray idx; std::vector<Host> sets; Dev* d = nullptr;
+    void release() { if (d) (void)hipFree(d); d = nullptr; sets.clear(); idx.release(); }
+};
+
 struct pg_handle {
     pg_config cfg;
     DevCfg dc;
@@ -34,23 +47,21 @@ struct pg_handle {
     int fuse = 0;                                             // pg_step_dev / pg_simulate_dev: linearisation fused into the solve kernel (pg_set_fusion): 0 never (default), 1 always, 2 for all-warm batches
     std::string err;
     // device buffers
-    real *d_traj = nullptr; int traj_L = 0; int *d_traj_len = nullptr, *d_traj_idx = nullptr; int traj_idx_B = 0;
-    // control-parameter library (pg_set_control_param_sets / pg_set_control_param_index): the device records and index DevCfg points to, the sets and index as the caller
-    // installed them (pg_get_control_param_sets), and the set every instance currently runs under (cp_eff, [capacity]: an instance whose entry changes is reset)
-    DevControlRec* d_cp_sets = nullptr; int* d_cp_idx = nullptr; int cp_idx_B = 0;
-    std::vector<pg_control_params> cp_sets, cp_eff; std::vector<int32_t> cp_index;
-    // plant library (pg_set_plant_sets / pg_set_plant_index): the vehicles the ego plant of the rollouts integrates, per instance; the device records and index the *_plant kernels
-    // read, and the sets and index as the caller installed them (pg_get_plant_sets).  Nothing on the controller's side reads any of it
-    DevVehicle* d_plants = nullptr; int* d_plant_idx = nullptr; int plant_idx_B = 0;
-    std::vector<pg_vehicle> plant_sets; std::vector<int32_t> plant_index;
+    real *d_traj = nullptr; int traj_L = 0; int *d_traj_len = nullptr; IndexArray traj_idx{"trajectory", "pg_set_trajectory_index"};
+    // control-parameter library (pg_set_control_param_sets / pg_set_control_param_index): device records (a library of several sets only) and index are what DevCfg points
+    // to; cp_eff [capacity] is the set every instance currently runs under (an instance whose entry changes is reset)
+    SetLib<pg_control_params, DevControlRec> cp{{"control-parameter", "pg_set_control_param_index"}}; std::vector<pg_control_params> cp_eff;
+    // plant library (pg_set_plant_sets / pg_set_plant_index): the vehicles the ego plant of the rollouts integrates, per instance, read by the *_plant kernels.  Nothing on
+    // the controller's side reads any of it
+    SetLib<pg_vehicle, DevVehicle> plants{{"plant", "pg_set_plant_index"}};
     // tracking summary (option "tracking_summary"; pg_get_tracking_state): [cap][6] sums, steps [cap] then first_exit [cap] (k_track), allocated when the option is first used
     int tracking = 0; real* d_track = nullptr; int* d_track_i = nullptr;
     bool track_fresh = true;                                  // the tracking summary restarts at the next rollout step (the clock restarted since it was last written)
-    // sensor library (pg_set_sensor_sets / pg_set_sensor_index / pg_set_sensor_seed): what the controller of a rollout step is handed in place of the true state.  Device: the
-    // records, the index, the stream ids [cap] (uploaded when a rollout or pg_sensor_draws first needs them and whenever they changed), the measured state d_meas [cap][6] and,
-    // with the tracking summary, the projection of the TRUE state d_sep_true [cap][4].  Host: sets, index and streams as installed.  Nothing is allocated without a library
-    DevSensor* d_sens = nullptr; int* d_sens_idx = nullptr; int sens_idx_B = 0; unsigned long long* d_sens_stream = nullptr; bool sens_stream_dirty = true;
-    std::vector<pg_sensor> sens_sets; std::vector<int32_t> sens_index; std::vector<uint64_t> sens_stream; uint64_t sens_seed = 0;
+    // sensor library (pg_set_sensor_sets / pg_set_sensor_index / pg_set_sensor_seed): what the controller of a rollout step is handed in place of the true state.  Beside the
+    // sets: the stream ids [cap] (host as installed; uploaded when a rollout or pg_sensor_draws first needs them and whenever they changed), the seed, the measured state
+    // d_meas [cap][6] and, with the tracking summary, the projection of the TRUE state d_sep_true [cap][4].  Nothing is allocated without a library
+    SetLib<pg_sensor, DevSensor> sens{{"sensor", "pg_set_sensor_index"}};
+    unsigned long long* d_sens_stream = nullptr; bool sens_stream_dirty = true; std::vector<uint64_t> sens_stream; uint64_t sens_seed = 0;
     real *d_meas = nullptr, *d_sep_true = nullptr; bool meas_valid = false;
     real* meas_hist = nullptr; int meas_hist_steps = 0;          // pg_set_measured_history_dev: one-shot, consumed by the next rollout call
     int64_t stat_sensor_steps = 0;                                // read-only option "stat_sensor_steps"
@@ -305,9 +316,10 @@ int pg_default_config_decoupled(pg_config* c) {
 }
 
 static void free_all(pg_handle* h) {
-    void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_traj_idx, h->d_cp_sets, h->d_cp_idx, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_plants, h->d_plant_idx, h->d_track, h->d_track_i, h->d_sens, h->d_sens_idx, h->d_sens_stream, h->d_meas, h->d_sep_true};
+    void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release();
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
     if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
@@ -603,14 +615,76 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
 }
 int pg_synchronize(pg_handle* h) { if (!h) return PG_ERR_INVALID; HIPCHK(h, hipStreamSynchronize(h->stream)); return PG_OK; }
 
-// install a library: channels[n_traj][10][Lmax] (t, s, V, A, E, N, psi, kappa, edge_L, edge_R), L[k] valid nodes of trajectory k
+// ---- what the four libraries share (trajectories, control parameters, plants, sensors): one index rule and one install / clear / get protocol ----
+// Installs the selection of `B` instances into a library of `n_sets`.  The WHOLE [capacity] array is written, entries beyond B as 0: never an address outside the library,
+// whatever an earlier, larger library left there
+static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, const int32_t* index) {
+    const std::string who(arr.setter);
+    REQUIRE(h, n_sets >= 1, who + ": no " + arr.what + " library installed");
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, who + ": need 1 <= B <= batch_capacity and an index array");
+    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < n_sets, who + ": index out of range of the installed library");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!arr.d) HIPCHK(h, hipMalloc((void**)&arr.d, cap_of(h) * sizeof(int)));
+    std::vector<int> full(cap_of(h), 0);
+    for (int b = 0; b < B; b++) full[(size_t)b] = index[b];
+    HIPCHK(h, hipMemcpy(arr.d, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
+    arr.host.assign(index, index + B);
+    return PG_OK;
+}
+// a library of several sets wants an index that covers the batch
+static int index_covers(pg_handle* h, size_t n_sets, const IndexArray& arr) {
+    if (n_sets <= 1 || arr.covered() >= h->B) return PG_OK;
+    h->err = std::string("a ") + arr.what + " library is installed but " + arr.setter + " does not cover the batch";
+    return PG_ERR_STATE;
+}
+}  // extern "C" (the set library's templates have C++ linkage)
+// problem(set): why a set is refused, or nullptr; fill(record, set): the device record of a set.  The new records replace the old ones only once they are on the device
+// (on_device = false: a library that needs none); installing a library drops the previous index
+template <class Host, class Dev, class Problem, class Fill>
+static int setlib_install(pg_handle* h, const char* who_, SetLib<Host, Dev>& L, int32_t n_sets, const Host* sets, Problem problem, Fill fill, bool on_device = true) {
+    const std::string who(who_);
+    REQUIRE(h, n_sets >= 1 && sets, who + ": need n_sets >= 1 and the sets");
+    for (int k = 0; k < n_sets; k++) { const char* why = problem(sets[k]); REQUIRE(h, !why, who + ": " + why); }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
+    Dev* d_new = nullptr;
+    if (on_device) {
+        std::vector<Dev> recs((size_t)n_sets);
+        for (int k = 0; k < n_sets; k++) fill(recs[(size_t)k], sets[k]);
+        HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(Dev)));
+        if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(Dev), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = who + ": copy failed"; return PG_ERR_HIP; }
+    }
+    if (L.d) (void)hipFree(L.d);
+    L.d = d_new; L.sets.assign(sets, sets + n_sets); L.idx.host.clear();
+    return PG_OK;
+}
+template <class Host, class Dev>
+static int setlib_clear(pg_handle* h, SetLib<Host, Dev>& L) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    L.release();
+    return PG_OK;
+}
+// the sets and the index as installed: *n_sets always, up to max_sets sets, index[b] = -1 where no index covers instance b
+template <class Host, class Dev>
+static int setlib_get(pg_handle* h, const char* who, const SetLib<Host, Dev>& L, int32_t* n_sets, Host* out, int32_t max_sets, int32_t* index, int32_t B) {
+    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), std::string(who) + ": need max_sets >= 0 and 0 <= B <= batch_capacity");
+    const int n = (int)L.sets.size();
+    if (n_sets) *n_sets = n;
+    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = L.sets[(size_t)k];
+    if (index) for (int b = 0; b < B; b++) index[b] = b < L.idx.covered() ? L.idx.host[(size_t)b] : -1;
+    return PG_OK;
+}
+extern "C" {
+
+// install a trajectory library: channels[n_traj][10][Lmax] (t, s, V, A, E, N, psi, kappa, edge_L, edge_R), L[k] valid nodes of trajectory k
 static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_t* L, const double* channels) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->d_traj) { (void)hipFree(h->d_traj); h->d_traj = nullptr; }
     if (h->d_traj_len) { (void)hipFree(h->d_traj_len); h->d_traj_len = nullptr; }
-    if (h->d_traj_idx) { (void)hipFree(h->d_traj_idx); h->d_traj_idx = nullptr; }
-    h->traj_idx_B = 0;
+    h->traj_idx.host.clear();
     const size_t stride = (size_t)10 * Lmax;
     HIPCHK(h, hipMalloc((void**)&h->d_traj, (size_t)n_traj * stride * sizeof(real)));
     { int rc = up(h, h->d_traj, channels, (size_t)n_traj * stride); if (rc) return rc; }
@@ -649,14 +723,8 @@ int pg_set_trajectories(pg_handle* h, int32_t n_traj, int32_t Lmax, const int32_
 
 int pg_set_trajectory_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, h->d_traj, "pg_set_trajectory_index: no trajectory library installed");
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_trajectory_index: need 1 <= B <= batch_capacity and an index array");
-    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < h->dc.n_traj, "pg_set_trajectory_index: index out of range of the installed library");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_traj_idx) HIPCHK(h, hipMalloc((void**)&h->d_traj_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
-    HIPCHK(h, hipMemcpy(h->d_traj_idx, index, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-    h->dc.traj_idx = h->d_traj_idx; h->traj_idx_B = B;
+    const int rc = index_install(h, h->d_traj ? h->dc.n_traj : 0, h->traj_idx, B, index); if (rc) return rc;
+    h->dc.traj_idx = h->traj_idx.d;
     return PG_OK;
 }
 
@@ -684,7 +752,7 @@ static bool same_control(const pg_control_params& a, const pg_control_params& b)
 // instances [0, n) now run under eff(b): those whose set changed start cold, as pg_reset leaves them (their warm start belonged to another QP); the others keep their state
 // (eff(b): the one set `single`, or set index[b] of the installed library)
 static int control_sets_changed(pg_handle* h, int n, const pg_control_params* single, const int32_t* index) {
-    auto eff = [&](int b) -> const pg_control_params& { return index ? h->cp_sets[(size_t)index[b]] : *single; };
+    auto eff = [&](int b) -> const pg_control_params& { return index ? h->cp.sets[(size_t)index[b]] : *single; };
     std::vector<uint8_t> mask((size_t)n, 0); bool any = false;
     for (int b = 0; b < n; b++) if (!same_control(eff(b), h->cp_eff[(size_t)b])) { mask[(size_t)b] = 1; any = true; }
     h->dc.cp_epoch++;                                          // (the captured step compares DevCfg: re-captured)
@@ -699,60 +767,32 @@ static int control_sets_changed(pg_handle* h, int n, const pg_control_params* si
 }
 int pg_set_control_param_sets(pg_handle* h, int32_t n_sets, const pg_control_params* sets) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, n_sets >= 1 && sets, "pg_set_control_param_sets: need n_sets >= 1 and the sets");
-    for (int k = 0; k < n_sets; k++) { const char* why = control_set_problem(h, sets[k]); REQUIRE(h, !why, std::string("pg_set_control_param_sets: ") + why); }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    DevControlRec* d_new = nullptr;
-    if (n_sets > 1) {
-        std::vector<DevControlRec> recs((size_t)n_sets);
-        for (int k = 0; k < n_sets; k++) recs[(size_t)k] = make_control_rec(h->cfg.formulation, sets[k]);
-        HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(DevControlRec)));
-        if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(DevControlRec), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = "pg_set_control_param_sets: copy failed"; return PG_ERR_HIP; }
-    }
-    if (h->d_cp_sets) (void)hipFree(h->d_cp_sets);
-    h->d_cp_sets = d_new; h->cp_sets.assign(sets, sets + n_sets);
-    h->cp_index.clear(); h->cp_idx_B = 0;                       // installing a library drops the previous index
-    DevCfg& C = h->dc; C.n_cp = n_sets; C.cp_sets = d_new; C.cp_idx = nullptr;
+    // (device records for a library of several sets only: a library of one is the uniform set of the handle)
+    const int rc = setlib_install(h, "pg_set_control_param_sets", h->cp, n_sets, sets, [h](const pg_control_params& u) { return control_set_problem(h, u); },
+                                  [h](DevControlRec& r, const pg_control_params& u) { r = make_control_rec(h->cfg.formulation, u); }, n_sets > 1);
+    if (rc) return rc;
+    DevCfg& C = h->dc; C.n_cp = n_sets; C.cp_sets = h->cp.d; C.cp_idx = nullptr;
     if (n_sets > 1) { C.cp_epoch++; return PG_OK; }            // (which instance runs under which set is known once the index arrives)
     // a library of one: the set becomes the uniform set of the handle -- every kernel reads it as the launch argument
     { const DevControlRec r = make_control_rec(h->cfg.formulation, sets[0]); C.cp = r.cp; C.ux_dummy = r.ux_dummy; }
-    return control_sets_changed(h, h->cfg.batch_capacity, &h->cp_sets[0], nullptr);
+    return control_sets_changed(h, h->cfg.batch_capacity, &h->cp.sets[0], nullptr);
 }
 int pg_set_control_param_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, h->dc.n_cp >= 1, "pg_set_control_param_index: no control-parameter library installed");
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_control_param_index: need 1 <= B <= batch_capacity and an index array");
-    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < h->dc.n_cp, "pg_set_control_param_index: index out of range of the installed library");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_cp_idx) {
-        HIPCHK(h, hipMalloc((void**)&h->d_cp_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
-        HIPCHK(h, hipMemset(h->d_cp_idx, 0, (size_t)h->cfg.batch_capacity * sizeof(int)));      // (entries beyond the indexed batch select set 0: never an address outside the library)
-    }
-    HIPCHK(h, hipMemcpy(h->d_cp_idx, index, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-    h->cp_index.assign(index, index + B); h->cp_idx_B = B;
-    if (h->dc.n_cp > 1) h->dc.cp_idx = h->d_cp_idx;            // (a library of one needs no index: every entry is 0)
+    const int rc = index_install(h, h->dc.n_cp, h->cp.idx, B, index); if (rc) return rc;
+    if (h->dc.n_cp > 1) h->dc.cp_idx = h->cp.idx.d;            // (a library of one needs no index: every entry is 0)
     return control_sets_changed(h, B, nullptr, index);
 }
 int pg_clear_control_param_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_cp_sets) { (void)hipFree(h->d_cp_sets); h->d_cp_sets = nullptr; }
-    h->cp_sets.clear(); h->cp_index.clear(); h->cp_idx_B = 0;
+    const int rc = setlib_clear(h, h->cp); if (rc) return rc;
     DevCfg& C = h->dc; C.n_cp = 0; C.cp_sets = nullptr; C.cp_idx = nullptr;
     { const DevControlRec r = make_control_rec(h->cfg.formulation, h->cfg.control); C.cp = r.cp; C.ux_dummy = r.ux_dummy; }
     return control_sets_changed(h, h->cfg.batch_capacity, &h->cfg.control, nullptr);
 }
 int pg_get_control_param_sets(pg_handle* h, int32_t* n_sets, pg_control_params* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), "pg_get_control_param_sets: need max_sets >= 0 and 0 <= B <= batch_capacity");
-    const int n = (int)h->cp_sets.size();
-    if (n_sets) *n_sets = n;
-    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = h->cp_sets[(size_t)k];
-    if (index) for (int b = 0; b < B; b++) index[b] = b < h->cp_idx_B ? h->cp_index[(size_t)b] : -1;
-    return PG_OK;
+    return setlib_get(h, "pg_get_control_param_sets", h->cp, n_sets, out, max_sets, index, B);
 }
 
 // ---- plant library: the vehicle the ego plant of a rollout step integrates, per instance (model_predictive_control.jl:94).  No part of any QP: nothing is reset ----
@@ -766,55 +806,19 @@ static const char* plant_set_problem(const pg_vehicle& v) {
 }
 int pg_set_plant_sets(pg_handle* h, int32_t n_sets, const pg_vehicle* sets) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, n_sets >= 1 && sets, "pg_set_plant_sets: need n_sets >= 1 and the sets");
-    for (int k = 0; k < n_sets; k++) { const char* why = plant_set_problem(sets[k]); REQUIRE(h, !why, std::string("pg_set_plant_sets: ") + why); }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
-    std::vector<DevVehicle> recs((size_t)n_sets);
-    for (int k = 0; k < n_sets; k++) fill_dev_vehicle(recs[(size_t)k], sets[k]);
-    DevVehicle* d_new = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(DevVehicle)));
-    if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(DevVehicle), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = "pg_set_plant_sets: copy failed"; return PG_ERR_HIP; }
-    if (h->d_plants) (void)hipFree(h->d_plants);
-    h->d_plants = d_new; h->plant_sets.assign(sets, sets + n_sets);
-    h->plant_index.clear(); h->plant_idx_B = 0;                 // installing a library drops the previous index
-    return PG_OK;
+    return setlib_install(h, "pg_set_plant_sets", h->plants, n_sets, sets, plant_set_problem, fill_dev_vehicle);
 }
 int pg_set_plant_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    const int n = (int)h->plant_sets.size();
-    REQUIRE(h, n >= 1, "pg_set_plant_index: no plant library installed");
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_plant_index: need 1 <= B <= batch_capacity and an index array");
-    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < n, "pg_set_plant_index: index out of range of the installed library");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_plant_idx) {
-        HIPCHK(h, hipMalloc((void**)&h->d_plant_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
-        HIPCHK(h, hipMemset(h->d_plant_idx, 0, (size_t)h->cfg.batch_capacity * sizeof(int)));
-    }
-    // (the whole array is rewritten: entries beyond the indexed batch select set 0 -- never an address outside the library, whatever an earlier, larger library left there)
-    std::vector<int> full((size_t)h->cfg.batch_capacity, 0);
-    for (int b = 0; b < B; b++) full[(size_t)b] = index[b];
-    HIPCHK(h, hipMemcpy(h->d_plant_idx, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
-    h->plant_index.assign(index, index + B); h->plant_idx_B = B;
-    return PG_OK;
+    return index_install(h, (int)h->plants.sets.size(), h->plants.idx, B, index);
 }
 int pg_clear_plant_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_plants) { (void)hipFree(h->d_plants); h->d_plants = nullptr; }
-    h->plant_sets.clear(); h->plant_index.clear(); h->plant_idx_B = 0;
-    return PG_OK;
+    return setlib_clear(h, h->plants);
 }
 int pg_get_plant_sets(pg_handle* h, int32_t* n_sets, pg_vehicle* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), "pg_get_plant_sets: need max_sets >= 0 and 0 <= B <= batch_capacity");
-    const int n = (int)h->plant_sets.size();
-    if (n_sets) *n_sets = n;
-    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = h->plant_sets[(size_t)k];
-    if (index) for (int b = 0; b < B; b++) index[b] = b < h->plant_idx_B ? h->plant_index[(size_t)b] : -1;
-    return PG_OK;
+    return setlib_get(h, "pg_get_plant_sets", h->plants, n_sets, out, max_sets, index, B);
 }
 
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
@@ -826,37 +830,14 @@ static const char* sensor_set_problem(const pg_sensor& s) {
     }
     return nullptr;
 }
+static void fill_dev_sensor(DevSensor& S, const pg_sensor& s) { for (int c = 0; c < 6; c++) { S.sigma[c] = (real)s.sigma[c]; S.bias[c] = (real)s.bias[c]; } }
 int pg_set_sensor_sets(pg_handle* h, int32_t n_sets, const pg_sensor* sets) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, n_sets >= 1 && sets, "pg_set_sensor_sets: need n_sets >= 1 and the sets");
-    for (int k = 0; k < n_sets; k++) { const char* why = sensor_set_problem(sets[k]); REQUIRE(h, !why, std::string("pg_set_sensor_sets: ") + why); }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
-    std::vector<DevSensor> recs((size_t)n_sets);
-    for (int k = 0; k < n_sets; k++) for (int c = 0; c < 6; c++) { recs[(size_t)k].sigma[c] = (real)sets[k].sigma[c]; recs[(size_t)k].bias[c] = (real)sets[k].bias[c]; }
-    DevSensor* d_new = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(DevSensor)));
-    if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(DevSensor), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = "pg_set_sensor_sets: copy failed"; return PG_ERR_HIP; }
-    if (h->d_sens) (void)hipFree(h->d_sens);
-    h->d_sens = d_new; h->sens_sets.assign(sets, sets + n_sets);
-    h->sens_index.clear(); h->sens_idx_B = 0;                   // installing a library drops the previous index (seed and streams persist)
-    return PG_OK;
+    return setlib_install(h, "pg_set_sensor_sets", h->sens, n_sets, sets, sensor_set_problem, fill_dev_sensor);      // (seed and streams persist)
 }
 int pg_set_sensor_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    const int n = (int)h->sens_sets.size();
-    REQUIRE(h, n >= 1, "pg_set_sensor_index: no sensor library installed");
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity && index, "pg_set_sensor_index: need 1 <= B <= batch_capacity and an index array");
-    for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < n, "pg_set_sensor_index: index out of range of the installed library");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_sens_idx) HIPCHK(h, hipMalloc((void**)&h->d_sens_idx, (size_t)h->cfg.batch_capacity * sizeof(int)));
-    // (the whole array is rewritten: entries beyond the indexed batch select set 0 -- never an address outside the library)
-    std::vector<int> full((size_t)h->cfg.batch_capacity, 0);
-    for (int b = 0; b < B; b++) full[(size_t)b] = index[b];
-    HIPCHK(h, hipMemcpy(h->d_sens_idx, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
-    h->sens_index.assign(index, index + B); h->sens_idx_B = B;
-    return PG_OK;
+    return index_install(h, (int)h->sens.sets.size(), h->sens.idx, B, index);
 }
 int pg_set_sensor_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
     if (!h) return PG_ERR_INVALID;
@@ -868,20 +849,13 @@ int pg_set_sensor_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* s
 }
 int pg_clear_sensor_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_sens) { (void)hipFree(h->d_sens); h->d_sens = nullptr; }
-    h->sens_sets.clear(); h->sens_index.clear(); h->sens_idx_B = 0; h->meas_valid = false; h->meas_hist = nullptr; h->meas_hist_steps = 0;
+    const int rc = setlib_clear(h, h->sens); if (rc) return rc;
+    h->meas_valid = false; h->meas_hist = nullptr; h->meas_hist_steps = 0;
     return PG_OK;
 }
 int pg_get_sensor_sets(pg_handle* h, int32_t* n_sets, pg_sensor* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, (!out || max_sets >= 0) && (!index || (B >= 0 && B <= h->cfg.batch_capacity)), "pg_get_sensor_sets: need max_sets >= 0 and 0 <= B <= batch_capacity");
-    const int n = (int)h->sens_sets.size();
-    if (n_sets) *n_sets = n;
-    if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = h->sens_sets[(size_t)k];
-    if (index) for (int b = 0; b < B; b++) index[b] = b < h->sens_idx_B ? h->sens_index[(size_t)b] : -1;
-    return PG_OK;
+    return setlib_get(h, "pg_get_sensor_sets", h->sens, n_sets, out, max_sets, index, B);
 }
 // the stream ids on the device, [capacity]: the installed ones, then stream[b] = b
 static int sensor_streams_sync(pg_handle* h) {
@@ -918,7 +892,7 @@ int pg_set_measured_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
     if (!h) return PG_ERR_INVALID;
     if (!buf) { h->meas_hist = nullptr; h->meas_hist_steps = 0; return PG_OK; }
     REQUIRE(h, steps >= 1, "pg_set_measured_history_dev: steps >= 1 required");
-    if (h->sens_sets.empty()) { h->err = "pg_set_measured_history_dev: no sensor library installed (the measured state is the true one: record state_hist)"; return PG_ERR_STATE; }
+    if (h->sens.sets.empty()) { h->err = "pg_set_measured_history_dev: no sensor library installed (the measured state is the true one: record state_hist)"; return PG_ERR_STATE; }
     h->meas_hist = (real*)buf; h->meas_hist_steps = steps;
     return PG_OK;
 }
@@ -1043,8 +1017,7 @@ static int check_ready(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     if (h->B <= 0) { h->err = "no inputs installed (call pg_set_inputs first)"; return PG_ERR_STATE; }
     if (!h->d_traj) { h->err = "no trajectory installed (call pg_set_trajectory first)"; return PG_ERR_STATE; }
-    if (h->dc.n_traj > 1 && h->traj_idx_B < h->B) { h->err = "a trajectory library is installed but pg_set_trajectory_index does not cover the batch"; return PG_ERR_STATE; }
-    if (h->dc.n_cp > 1 && h->cp_idx_B < h->B) { h->err = "a control-parameter library is installed but pg_set_control_param_index does not cover the batch"; return PG_ERR_STATE; }
+    if (index_covers(h, (size_t)h->dc.n_traj, h->traj_idx) || index_covers(h, (size_t)h->dc.n_cp, h->cp.idx)) return PG_ERR_STATE;
     if (hipSetDevice(h->cfg.device) != hipSuccess) { h->err = "hipSetDevice failed"; return PG_ERR_HIP; }
     return PG_OK;
 }
@@ -1519,14 +1492,14 @@ static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, doub
 }
 // what a rollout needs beyond check_ready: a plant library of several sets wants an index that covers the batch; the tracking summary its buffers
 static int rollout_ready(pg_handle* h) {
-    if (h->plant_sets.size() > 1 && h->plant_idx_B < h->B) { h->err = "a plant library is installed but pg_set_plant_index does not cover the batch"; return PG_ERR_STATE; }
+    if (index_covers(h, h->plants.sets.size(), h->plants.idx)) return PG_ERR_STATE;
     if (h->tracking && !h->d_track) {
         const size_t cap = cap_of(h);
         HIPCHK(h, hipMalloc((void**)&h->d_track, cap * 6 * sizeof(real)));
         HIPCHK(h, hipMalloc((void**)&h->d_track_i, cap * 2 * sizeof(int)));
     }
-    if (!h->sens_sets.empty()) {
-        if (h->sens_sets.size() > 1 && h->sens_idx_B < h->B) { h->err = "a sensor library is installed but pg_set_sensor_index does not cover the batch"; return PG_ERR_STATE; }
+    if (!h->sens.sets.empty()) {
+        if (index_covers(h, h->sens.sets.size(), h->sens.idx)) return PG_ERR_STATE;
         const size_t cap = cap_of(h);
         if (!h->d_meas) HIPCHK(h, hipMalloc((void**)&h->d_meas, cap * 6 * sizeof(real)));
         if (h->tracking && !h->d_sep_true) HIPCHK(h, hipMalloc((void**)&h->d_sep_true, cap * 4 * sizeof(real)));
@@ -1536,7 +1509,7 @@ static int rollout_ready(pg_handle* h) {
 }
 // the sensor library (the host knows whether one is installed: that alone adds k_measure to a rollout step).  sensor_take_history: the one-shot registration of
 // pg_set_measured_history_dev, consumed by the rollout call that starts now
-static bool sensor_lib_on(const pg_handle* h) { return !h->sens_sets.empty(); }
+static bool sensor_lib_on(const pg_handle* h) { return !h->sens.sets.empty(); }
 struct MeasHist { real* buf; int steps; };
 static MeasHist sensor_take_history(pg_handle* h) { const MeasHist m{h->meas_hist, h->meas_hist_steps}; h->meas_hist = nullptr; h->meas_hist_steps = 0; return m; }
 // the controller's side of one rollout step: the node gate (node rollout) and the compute calls.  Under a sensor library k_measure writes the measured state of clock step
@@ -1547,7 +1520,7 @@ static int rollout_compute(pg_handle* h, int step, int k, const MeasHist& mh, bo
     int rc;
     if (!sensor_lib_on(h)) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
     const int B = h->B;
-    const SensorLib lib{h->d_sens, h->sens_sets.size() > 1 ? h->d_sens_idx : (const int*)nullptr, h->d_sens_stream, (unsigned long long)h->sens_seed};
+    const SensorLib lib{h->sens.d, h->sens.sets.size() > 1 ? h->sens.idx.d : (const int*)nullptr, h->d_sens_stream, (unsigned long long)h->sens_seed};
     hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, h->d_meas, (mh.buf && k < mh.steps) ? mh.buf + (size_t)k * B * 6 : (real*)nullptr);
     LAUNCH_CHECK(h);
     h->meas_valid = true; h->stat_sensor_steps++;
@@ -1559,8 +1532,8 @@ static int rollout_compute(pg_handle* h, int step, int k, const MeasHist& mh, bo
     return rc;
 }
 // the plant library as the *_plant kernels take it (the host knows whether one is installed: that alone picks the kernel)
-static bool plant_lib_on(const pg_handle* h) { return !h->plant_sets.empty(); }
-static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->d_plants, h->plant_sets.size() > 1 ? h->d_plant_idx : (const int*)nullptr}; }
+static bool plant_lib_on(const pg_handle* h) { return !h->plants.sets.empty(); }
+static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->plants.d, h->plants.sets.size() > 1 ? h->plants.idx.d : (const int*)nullptr}; }
 // the step's tracking summary (option "tracking_summary"): behind the projection of this step (step_compute), ahead of the kernel that moves the plant
 static int launch_track(pg_handle* h, int step) {
     if (!h->tracking) { h->track_fresh = true; return PG_OK; }      // (off: no launch; steps that went unseen must not be continued when it comes back on)
@@ -1584,54 +1557,67 @@ static int clock_start(pg_handle* h, double dt) {
     }
     return PG_OK;
 }
-int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev_, void* control_hist_dev_) {
-    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};      // one-shot: THIS call consumes the registration, also when it fails below
+static int node_start(pg_handle* h, double dt);
+}  // extern "C" (the rollouts' templates have C++ linkage)
+// the last launch of a rollout step, one lane per instance: `uniform`, or under a plant library `with_plant` -- the same arguments and the library behind them
+template <class K, class KP, class... A>
+static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, const A&... args) {
+    const dim3 grid((h->B + 63) / 64), block(64);
+    if (plant_lib_on(h)) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
+    else hipLaunchKernelGGL(uniform, grid, block, 0, h->stream, args...);
+}
+// The rollouts' shared driver.  Prologue, in this order: the one-shot measured-history registration is taken (THIS call consumes it, also when it fails below), check_ready,
+// the entry point's own precondition (coupled_only: the message for a lateral handle, nullptr: none), the shared arguments, rollout_ready, the node's buffers (node: the
+// rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records(k) ahead of the compute calls, the
+// controller's side (:90-93, on the measured state under a sensor library), the tracking summary, the clock index, then finish(k, step): the step's last launch, which moves
+// the plant (step: index of the clock element t0 held -- steps continue across calls)
+struct RolloutArgs { const char* who; int32_t steps; double dt; int32_t human_mode; const void* human_u; const char* coupled_only; bool node; const uint8_t* pre_flag; };
+template <class Records, class Finish>
+static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish finish) {
+    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};
     int rc = check_ready(h); if (rc) return rc;
-    if ((rc = check_rollout_args(h, "pg_simulate_dev", steps, dt, 0, nullptr)) || (rc = rollout_ready(h))) return rc;
-    const int B = h->B;
-    real* state_hist_dev = (real*)state_hist_dev_; real* control_hist_dev = (real*)control_hist_dev_;
-    if ((rc = clock_start(h, dt))) return rc;                           // the loop's clock (:87)
-    for (int k = 0; k < steps; k++) {
-        if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(state_hist_dev + (size_t)k * B * 6, h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // push!(qs, state) :88
-        if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(control_hist_dev + (size_t)k * B * 3, h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream)); // push!(us, control) :89
-        if ((rc = rollout_compute(h, h->sim_idx - 1, k, mh, false, nullptr))) return rc;              // :90-93 (on the measured state under a sensor library)
-        if ((rc = launch_track(h, h->sim_idx - 1))) return rc;
-        h->sim_idx++;                                                                                                                                         // (t0 now holds element sim_idx of the clock)
-        if (plant_lib_on(h)) hipLaunchKernelGGL(k_advance_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, plant_lib(h));
-        else hipLaunchKernelGGL(k_advance, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx);      // :94-95
+    if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
+    if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u)) || (rc = rollout_ready(h)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
+    for (int k = 0; k < a.steps; k++) {
+        const int step = h->sim_idx - 1;
+        if ((rc = records(k)) || (rc = rollout_compute(h, step, k, mh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr)) || (rc = launch_track(h, step))) return rc;
+        h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)
+        finish(k, step);
         LAUNCH_CHECK(h);
     }
     return PG_OK;
 }
+static int no_records(int) { return PG_OK; }
+// record k of a [steps][B][width] history (nullptr: not recorded)
+template <class T> static T* hist_at(T* hist, int k, int B, int width) { return hist ? hist + (size_t)k * B * width : nullptr; }
+extern "C" {
+int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev, void* control_hist_dev) {
+    return rollout(h, RolloutArgs{"pg_simulate_dev", steps, dt, 0, nullptr, nullptr, false, nullptr},
+        [&](int k) -> int {
+            const int B = h->B;
+            if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)state_hist_dev, k, B, 6), h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));          // push!(qs, state) :88
+            if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)control_hist_dev, k, B, 3), h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));  // push!(us, control) :89
+            return PG_OK;
+        },
+        [&](int, int) { launch_plant_step(h, k_advance, k_advance_plant, h->dc, h->B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
+}
 // simulate (:80-100) with the control the ROS node sends (ros_integration.jl:114-124) fed back and the other car moving (k_advance_safety, pg_kernels.hip).  Per step: the four
 // compute calls exactly as pg_simulate_dev makes them (fusion, pipelining and the split solve unchanged; with a grid they leave the step's relative state d_x7 and its
 // lookup d_vg8), then ONE launch for the records, the selection, both plants, the new control, the clock and the summary
-int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev_,
-                           void* state_hist_dev_, void* control_hist_dev_, void* other_hist_dev_, void* human_hist_dev_, void* V_hist_dev_, int32_t* source_hist_dev) {
-    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};      // one-shot: THIS call consumes the registration, also when it fails below
-    int rc = check_ready(h); if (rc) return rc;
-    if (h->dc.formulation != PG_COUPLED) { h->err = "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row"; return PG_ERR_STATE; }
-    if ((rc = check_rollout_args(h, "pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev_)) || (rc = rollout_ready(h))) return rc;
-    const int B = h->B; const size_t Bz = (size_t)B;
-    const real* human_u_dev = (const real*)human_u_dev_;
-    real *sh = (real*)state_hist_dev_, *ch = (real*)control_hist_dev_, *oh = (real*)other_hist_dev_, *hh = (real*)human_hist_dev_, *vh = (real*)V_hist_dev_;
-    if ((rc = clock_start(h, dt))) return rc;
-    for (int k = 0; k < steps; k++) {
-        const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
-        if ((rc = rollout_compute(h, step, k, mh, false, nullptr))) return rc;                        // :90-93
-        if ((rc = launch_track(h, step))) return rc;
-        h->sim_idx++;
-        SafetyIO io{human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr, sh ? sh + (size_t)k * Bz * 6 : nullptr, ch ? ch + (size_t)k * Bz * 3 : nullptr,
-                    oh ? oh + (size_t)k * Bz * 4 : nullptr, hh ? hh + (size_t)k * Bz * 2 : nullptr, vh ? vh + (size_t)k * Bz : nullptr,
-                    source_hist_dev ? source_hist_dev + (size_t)k * Bz : nullptr, h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-        if (plant_lib_on(h)) hipLaunchKernelGGL(k_advance_safety_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji,
-                           (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io, plant_lib(h));
-        else hipLaunchKernelGGL(k_advance_safety, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji,
-                           (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
-        LAUNCH_CHECK(h);
-        h->sum_fresh = false;
-    }
-    return PG_OK;
+int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev,
+                           void* state_hist_dev, void* control_hist_dev, void* other_hist_dev, void* human_hist_dev, void* V_hist_dev, int32_t* source_hist_dev) {
+    return rollout(h, RolloutArgs{"pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev,
+                                  "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row", false, nullptr},
+        no_records,
+        [&](int k, int step) {
+            const int B = h->B;
+            SafetyIO io{human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr, hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
+                        hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
+                        h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
+            launch_plant_step(h, k_advance_safety, k_advance_safety_plant, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji, (int)h->sum_fresh, step,
+                              h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
+            h->sum_fresh = false;
+        });
 }
 int pg_get_safety_state(pg_handle* h, double* other_car, double* V_min, int32_t* first_breach, int32_t* policy_steps) {
     int rc = check_ready(h); if (rc) return rc;
@@ -1724,41 +1710,32 @@ int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_fl
     node_done(h);
     return PG_OK;
 }
-// the node's closed loop: per step gate, the compute calls, then ONE launch for the restore, the selection, the fallback, the message, the records, both plants, the applied
-// command, the clock, the summary and the counts (k_node_finish<true>)
-int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev_, const uint8_t* pre_flag_dev,
-                         void* state_hist_dev_, void* applied_hist_dev_, int32_t* event_hist_dev, void* V_hist_dev_) {
-    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};      // one-shot: THIS call consumes the registration, also when it fails below
-    int rc = check_ready(h); if (rc) return rc;
-    if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
-    if ((rc = check_rollout_args(h, "pg_simulate_node_dev", steps, dt, human_mode, human_u_dev_)) || (rc = rollout_ready(h))) return rc;
-    if ((rc = node_prepare(h))) return rc;
-    const int B = h->B; const size_t Bz = (size_t)B;
-    const real* human_u_dev = (const real*)human_u_dev_;
-    real *sh = (real*)state_hist_dev_, *ah = (real*)applied_hist_dev_, *vh = (real*)V_hist_dev_;
-    const bool restart = h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end;
-    if ((rc = clock_start(h, dt))) return rc;
-    if (restart) HIPCHK(h, hipMemcpyAsync(h->d_applied, h->d_control, Bz * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));      // the applied command starts as the message
-    const int has = (int)(h->has_hji && h->dc.formulation == PG_COUPLED);
-    for (int k = 0; k < steps; k++) {
-        const int step = h->sim_idx - 1;                                                              // (index of the clock element t0 holds: steps continue across calls)
-        if ((rc = rollout_compute(h, step, k, mh, true, pre_flag_dev ? pre_flag_dev + (size_t)k * Bz : nullptr))) return rc;
-        if ((rc = launch_track(h, step))) return rc;                                                  // (every step counts, gated out or not: the plant moves either way)
-        h->sim_idx++;
-        NodeIO io = node_io(h);
-        io.human_u = human_mode == 2 ? human_u_dev + (size_t)k * Bz * 2 : nullptr;
-        io.state_h = sh ? sh + (size_t)k * Bz * 6 : nullptr; io.applied_h = ah ? ah + (size_t)k * Bz * 3 : nullptr; io.V_h = vh ? vh + (size_t)k * Bz : nullptr;
-        io.event_h = event_hist_dev ? event_hist_dev + (size_t)k * Bz : nullptr;
-        io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-        if (plant_lib_on(h)) hipLaunchKernelGGL(k_node_finish_plant, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, has,
-                           (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, h->kv, io, plant_lib(h));
-        else hipLaunchKernelGGL(k_node_finish<true>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, has,
-                           (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, h->kv, io);
-        LAUNCH_CHECK(h);
-        h->sum_fresh = false;
-        node_done(h);
-    }
+// the node rollout's buffers, and the applied command of a clock that is about to restart: it starts as the message
+static int node_start(pg_handle* h, double dt) {
+    int rc = node_prepare(h); if (rc) return rc;
+    if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) HIPCHK(h, hipMemcpyAsync(h->d_applied, h->d_control, (size_t)h->B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
     return PG_OK;
+}
+// the node's closed loop: per step gate, the compute calls, then ONE launch for the restore, the selection, the fallback, the message, the records, both plants, the applied
+// command, the clock, the summary and the counts (k_node_finish<true>); every step counts for the tracking summary, gated out or not: the plant moves either way
+int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev, const uint8_t* pre_flag_dev,
+                         void* state_hist_dev, void* applied_hist_dev, int32_t* event_hist_dev, void* V_hist_dev) {
+    return rollout(h, RolloutArgs{"pg_simulate_node_dev", steps, dt, human_mode, human_u_dev,
+                                  use_hji_policy ? "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)" : nullptr, true, pre_flag_dev},
+        no_records,
+        [&](int k, int step) {
+            const int B = h->B;
+            NodeIO io = node_io(h);
+            io.human_u = human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr;
+            io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
+            io.event_h = hist_at(event_hist_dev, k, B, 1);
+            io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
+            launch_plant_step(h, k_node_finish<true>, k_node_finish_plant, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+                              (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
+                              h->sim_idx, h->kv, io);
+            h->sum_fresh = false;
+            node_done(h);
+        });
 }
 int pg_get_node_state(pg_handle* h, double* applied, int32_t* heartbeat, int32_t* counts) {
     int rc = check_ready(h); if (rc) return rc;
@@ -1812,8 +1789,7 @@ static int step_by_graph(pg_handle* h, int32_t B, const double* state, const dou
     *done = false;
     auto& G = h->sg;
     if (!h->graph_mode || G.disabled || B != h->cfg.batch_capacity || B > 256 || h->B != B || h->warm_B < B || h->fuse != 0 || !h->d_traj || h->node_recheck) return PG_OK;
-    if (h->dc.n_traj > 1 && h->traj_idx_B < B) return PG_OK;
-    if (h->dc.n_cp > 1 && h->cp_idx_B < B) return PG_OK;      // (the ordinary path reports it)
+    if (index_covers(h, (size_t)h->dc.n_traj, h->traj_idx) || index_covers(h, (size_t)h->dc.n_cp, h->cp.idx)) return PG_OK;      // (h->B == B; the ordinary path reports it)
     if (hipSetDevice(h->cfg.device) != hipSuccess) return PG_OK;
     const bool same = G.x && G.B == B && G.user == h->stream && G.fuse == h->fuse && G.pipeline == h->pipeline && G.has_hji == (int)h->has_hji && G.traj_L == h->traj_L &&
                       memcmp(&G.dc, &h->dc, sizeof(DevCfg)) == 0 && memcmp(&G.hv, &h->hv, sizeof(HjiView)) == 0;

@@ -15,6 +15,7 @@ from .trajectories import TrajectoryTube
 from .vehicles import X1, CoupledControlParams, DecoupledControlParams
 
 c_dp = C.POINTER(C.c_double)
+c_i32p = C.POINTER(C.c_int32)
 
 SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 
@@ -150,90 +151,89 @@ class BatchedTrajectoryTrackingMPC:
             self.set_trajectory_index(index)
 
     def set_trajectory_index(self, index):
+        self.trajectory_index = self._set_index("trajectory", index)
+
+    # ---- the per-instance libraries share one protocol (pg_set_<name>_sets / pg_set_<name>_index / pg_clear_<name>_sets / pg_get_<name>_sets): the four routines below ----
+    @staticmethod
+    def _pack(ctype, sets, fill):
+        """structures of `ctype` (copied) or whatever fill(record, item) understands -> a ctypes array of `ctype`."""
+        sets = list(sets)
+        arr = (ctype * len(sets))()
+        for k, v in enumerate(sets):
+            if isinstance(v, ctype):
+                C.memmove(C.byref(arr[k]), C.byref(v), C.sizeof(ctype))
+            else:
+                fill(arr[k], v)
+        return arr
+
+    def _set_index(self, name, index):
         index = np.ascontiguousarray(index, dtype=np.int32)
-        self._chk(self.lib.pg_set_trajectory_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_trajectory_index")
-        self.trajectory_index = index
+        self._chk(getattr(self.lib, f"pg_set_{name}_index")(self.h, len(index), _p(index, c_i32p)), f"pg_set_{name}_index")
+        return index
+
+    def _set_sets(self, name, ctype, pack, sets, index):
+        """one set (dict / structure) for the whole batch, or a list of sets; then the per-instance selection, if given."""
+        arr = pack([sets] if isinstance(sets, (dict, ctype)) else sets)
+        self._chk(getattr(self.lib, f"pg_set_{name}_sets")(self.h, len(arr), arr), f"pg_set_{name}_sets")
+        if index is not None:
+            self._set_index(name, index)
+
+    def _get_sets(self, name, ctype, as_dict):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        get = getattr(self.lib, f"pg_get_{name}_sets")
+        n = C.c_int32(0)
+        self._chk(get(self.h, C.byref(n), None, 0, None, 0), f"pg_get_{name}_sets")           # first call: how many sets
+        arr = (ctype * max(n.value, 1))()
+        index = np.full(self.B, -1, dtype=np.int32)
+        self._chk(get(self.h, C.byref(n), arr, n.value, _p(index, c_i32p), self.B), f"pg_get_{name}_sets")
+        return [as_dict(arr[k]) for k in range(n.value)], index
 
     # ---- one controller per (x0, control_params) pair: a library of parameter sets and a per-instance selection (a tuning sweep in one batch) ----
     def pack_control_params(self, sets):
         """dicts (missing fields: the handle's own control_params) or pg_control_params structures -> a ctypes array of pg_control_params."""
-        sets = list(sets)
-        arr = (_lib.pg_control_params * len(sets))()
-        for k, cp in enumerate(sets):
-            if isinstance(cp, _lib.pg_control_params):
-                C.memmove(C.byref(arr[k]), C.byref(cp), C.sizeof(_lib.pg_control_params))
-                continue
-            C.memmove(C.byref(arr[k]), C.byref(self.cfg.control), C.sizeof(_lib.pg_control_params))
+        def fill(rec, cp):
+            C.memmove(C.byref(rec), C.byref(self.cfg.control), C.sizeof(_lib.pg_control_params))
             for name, _ in _lib.pg_control_params._fields_:
                 if name != "_pad" and name in cp:
-                    setattr(arr[k], name, int(cp[name]) if name == "N_HJI" else float(cp[name]))
-        return arr
+                    setattr(rec, name, int(cp[name]) if name == "N_HJI" else float(cp[name]))
+        return self._pack(_lib.pg_control_params, sets, fill)
 
     def set_control_params(self, sets, index=None):
         """One set (dict / structure) for the whole batch, or a list of sets; select per instance with `index` or set_control_param_index."""
-        if isinstance(sets, (dict, _lib.pg_control_params)):
-            sets = [sets]
-        arr = self.pack_control_params(sets)
-        self._chk(self.lib.pg_set_control_param_sets(self.h, len(arr), arr), "pg_set_control_param_sets")
-        if index is not None:
-            self.set_control_param_index(index)
+        self._set_sets("control_param", _lib.pg_control_params, self.pack_control_params, sets, index)
 
     def set_control_param_index(self, index):
-        index = np.ascontiguousarray(index, dtype=np.int32)
-        self._chk(self.lib.pg_set_control_param_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_control_param_index")
+        self._set_index("control_param", index)
 
     def clear_control_params(self):
         self._chk(self.lib.pg_clear_control_param_sets(self.h), "pg_clear_control_param_sets")
 
     def control_param_sets(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
-        n = C.c_int32(0)
-        self._chk(self.lib.pg_get_control_param_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_control_param_sets")
-        arr = (_lib.pg_control_params * max(n.value, 1))()
-        index = np.full(self.B, -1, dtype=np.int32)
-        self._chk(self.lib.pg_get_control_param_sets(self.h, C.byref(n), arr, n.value, _p(index, C.POINTER(C.c_int32)), self.B), "pg_get_control_param_sets")
-        names = [name for name, _ in _lib.pg_control_params._fields_ if name != "_pad"]
-        return [{name: getattr(arr[k], name) for name in names} for k in range(n.value)], index
+        return self._get_sets("control_param", _lib.pg_control_params, lambda r: {name: getattr(r, name) for name, _ in r._fields_ if name != "_pad"})
 
     # ---- the PLANT of the rollouts, per instance (model-mismatch studies): a library of vehicles and a per-instance selection.  The controller keeps self.vehicle ----
     def pack_vehicles(self, sets):
         """vehicle dicts (vehicles.X1(**overrides); missing fields: the handle's own vehicle) or pg_vehicle structures -> a ctypes array of pg_vehicle."""
-        sets = list(sets)
-        arr = (_lib.pg_vehicle * len(sets))()
-        for k, v in enumerate(sets):
-            if isinstance(v, _lib.pg_vehicle):
-                C.memmove(C.byref(arr[k]), C.byref(v), C.sizeof(_lib.pg_vehicle))
-                continue
+        def fill(rec, v):
             for name, _ in _lib.pg_vehicle._fields_:
-                setattr(arr[k], name, float(v[name] if name in v else self.vehicle[name]))
-        return arr
+                setattr(rec, name, float(v[name] if name in v else self.vehicle[name]))
+        return self._pack(_lib.pg_vehicle, sets, fill)
 
     def set_plants(self, sets, index=None):
         """The vehicle the ego plant of simulate_ / simulate_safety_ / simulate_node_ integrates (pg_set_plant_sets): one set (dict / structure) for the whole batch, or a
         list of sets; select per instance with `index` or set_plant_index.  Resets nothing: the plant is no part of any QP."""
-        if isinstance(sets, (dict, _lib.pg_vehicle)):
-            sets = [sets]
-        arr = self.pack_vehicles(sets)
-        self._chk(self.lib.pg_set_plant_sets(self.h, len(arr), arr), "pg_set_plant_sets")
-        if index is not None:
-            self.set_plant_index(index)
+        self._set_sets("plant", _lib.pg_vehicle, self.pack_vehicles, sets, index)
 
     def set_plant_index(self, index):
-        index = np.ascontiguousarray(index, dtype=np.int32)
-        self._chk(self.lib.pg_set_plant_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_plant_index")
+        self._set_index("plant", index)
 
     def clear_plants(self):
         self._chk(self.lib.pg_clear_plant_sets(self.h), "pg_clear_plant_sets")
 
     def plant_sets(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
-        n = C.c_int32(0)
-        self._chk(self.lib.pg_get_plant_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_plant_sets")
-        arr = (_lib.pg_vehicle * max(n.value, 1))()
-        index = np.full(self.B, -1, dtype=np.int32)
-        self._chk(self.lib.pg_get_plant_sets(self.h, C.byref(n), arr, n.value, _p(index, C.POINTER(C.c_int32)), self.B), "pg_get_plant_sets")
-        names = [name for name, _ in _lib.pg_vehicle._fields_]
-        return [{name: getattr(arr[k], name) for name in names} for k in range(n.value)], index
+        return self._get_sets("plant", _lib.pg_vehicle, lambda r: {name: getattr(r, name) for name, _ in r._fields_})
 
     def tracking_summary(self):
         """Per instance since the rollout's clock last restarted (option "tracking_summary" = 1 first; pg_get_tracking_state): (summary [B][6] = max |e|, sum e^2,
@@ -253,28 +253,18 @@ class BatchedTrajectoryTrackingMPC:
             if isinstance(v, dict):
                 return [float(v.get(c, 0.0)) for c in self.SENSOR_CHANNELS]
             return [float(x) for x in np.asarray(v, dtype=np.float64).reshape(6)]
-        sets = list(sets)
-        arr = (_lib.pg_sensor * len(sets))()
-        for k, v in enumerate(sets):
-            if isinstance(v, _lib.pg_sensor):
-                C.memmove(C.byref(arr[k]), C.byref(v), C.sizeof(_lib.pg_sensor))
-                continue
+
+        def fill(rec, v):
             sg, bs = (v.get("sigma"), v.get("bias")) if isinstance(v, dict) else v
-            arr[k].sigma[:] = six(sg); arr[k].bias[:] = six(bs)
-        return arr
+            rec.sigma[:] = six(sg); rec.bias[:] = six(bs)
+        return self._pack(_lib.pg_sensor, sets, fill)
 
     def set_sensors(self, sets, index=None, seed=0, streams=None):
         """What the controller of simulate_ / simulate_safety_ / simulate_node_ reads in place of the true state (pg_set_sensor_sets): measured = true + bias + sigma z per
         channel of (E, N, psi, Ux, Uy, r).  One set (dict / structure) for the whole batch, or a list of sets selected per instance with `index`; `seed` and the 64-bit
         `streams` [B] (None: stream[b] = b) fix the draws (pg_set_sensor_seed).  Resets nothing.  Unlike the C calls, where seed and streams persist across installs, EVERY call here
         installs seed and streams too: re-installing a library without them puts the seed back to 0 and the streams back to b (set_sensor_seed afterwards, or pass them again)."""
-        if isinstance(sets, (dict, _lib.pg_sensor)):
-            sets = [sets]
-        arr = self.pack_sensors(sets)
-        self._chk(self.lib.pg_set_sensor_sets(self.h, len(arr), arr), "pg_set_sensor_sets")
-        if index is not None:
-            index = np.ascontiguousarray(index, dtype=np.int32)
-            self._chk(self.lib.pg_set_sensor_index(self.h, len(index), _p(index, C.POINTER(C.c_int32))), "pg_set_sensor_index")
+        self._set_sets("sensor", _lib.pg_sensor, self.pack_sensors, sets, index)
         self.set_sensor_seed(seed, streams)
 
     def set_sensor_seed(self, seed=0, streams=None):
@@ -286,12 +276,7 @@ class BatchedTrajectoryTrackingMPC:
 
     def sensors(self):
         """(list of {"sigma": [6], "bias": [6]}, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
-        n = C.c_int32(0)
-        self._chk(self.lib.pg_get_sensor_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_sensor_sets")
-        arr = (_lib.pg_sensor * max(n.value, 1))()
-        index = np.full(self.B, -1, dtype=np.int32)
-        self._chk(self.lib.pg_get_sensor_sets(self.h, C.byref(n), arr, n.value, _p(index, C.POINTER(C.c_int32)), self.B), "pg_get_sensor_sets")
-        return [{"sigma": list(arr[k].sigma), "bias": list(arr[k].bias)} for k in range(n.value)], index
+        return self._get_sets("sensor", _lib.pg_sensor, lambda r: {"sigma": list(r.sigma), "bias": list(r.bias)})
 
     def sensor_draws(self, step0, steps, B=None):
         """The standard normals z [steps][B][6] the rollouts draw at clock steps [step0, step0 + steps), computed on the device by the function k_measure calls (pg_sensor_draws)."""
@@ -306,12 +291,17 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_measured_state(self.h, _p(m)), "pg_get_measured_state")
         return m
 
+    def _torch(self):
+        """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""
+        import torch
+        return torch, torch.float32 if self.precision == "f32" else torch.float64, f"cuda:{self.cfg.device}"
+
     def _measured_hist(self, measured, steps):
         """registers a [steps][B][6] device record of the measured state with the next rollout call (pg_set_measured_history_dev); None unless asked for"""
         if not measured:
             return None
-        import torch
-        buf = torch.empty(int(steps), self.B, 6, dtype=torch.float32 if self.precision == "f32" else torch.float64, device=f"cuda:{self.cfg.device}")
+        torch, tdt, dev = self._torch()
+        buf = torch.empty(int(steps), self.B, 6, dtype=tdt, device=dev)
         self._chk(self.lib.pg_set_measured_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_measured_history_dev")
         return buf
 
@@ -393,27 +383,41 @@ class BatchedTrajectoryTrackingMPC:
     def step_dev(self, u_out_ptr=None):
         self._chk(self.lib.pg_step_dev(self.h, C.c_void_p(u_out_ptr) if u_out_ptr else None), "pg_step_dev")
 
+    HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
+
+    def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True):
+        """The rollouts' shared plumbing.  Device records [steps][B] + shapes[name] in the library's element type and one int32 record `int_record` (record=True), the scripted
+        human [steps][B][2], the measured history; call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
+        ((state, control, t[, other]), the records as fp64 / int32 numpy arrays or None, (measured history,) or ())."""
+        assert human in self.HUMAN_MODES, human
+        hu = None; hist = {}
+        if human == "script":
+            if human_u is None:
+                raise ValueError('human="script" needs human_u [steps][B][2]')
+            torch, tdt, dev = self._torch()
+            hu = torch.as_tensor(np.ascontiguousarray(human_u, dtype=np.float64).reshape(steps, self.B, 2)).to(device=dev, dtype=tdt).contiguous()
+        if record:
+            torch, tdt, dev = self._torch()
+            hist = {k: torch.empty((steps, self.B) + s, dtype=tdt, device=dev) for k, s in shapes.items()}
+            if int_record:
+                hist[int_record] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
+        mbuf = self._measured_hist(measured, steps)
+        call(lambda t: C.c_void_p(t.data_ptr()) if t is not None else None, hu, hist)
+        s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
+        self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
+        if other:
+            self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
+        out = {k: v.cpu().numpy().astype(np.float64 if k in shapes else np.int32) for k, v in hist.items()} if record else None
+        return (s, c, t, o) if other else (s, c, t), out, () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
+
     def simulate_(self, steps, dt=0.01, record=False, measured=False):
         """simulate (model_predictive_control.jl:80-100) on the device from the inputs last installed; returns (state, control, t) after `steps`
         steps and, with record=True, the histories qs [steps][B][6], us [steps][B][3] (the values pushed at :88-89).  measured=True (a sensor library is installed)
         appends the measured history [steps][B][6] to what is returned."""
-        import ctypes as C_
-        qh = uh = None; dq = du = None
-        mbuf = self._measured_hist(measured, steps)
-        if record:
-            import torch
-            tdt = torch.float32 if self.precision == "f32" else torch.float64         # device records have the library's own element type
-            dq = torch.empty(steps, self.B, 6, dtype=tdt, device=f"cuda:{self.cfg.device}"); du = torch.empty(steps, self.B, 3, dtype=tdt, device=f"cuda:{self.cfg.device}")
-        self._chk(self.lib.pg_simulate_dev(self.h, steps, C_.c_double(dt), C_.c_void_p(dq.data_ptr()) if record else None, C_.c_void_p(du.data_ptr()) if record else None), "pg_simulate_dev")
-        s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B)
-        self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
-        if record:
-            qh = dq.cpu().numpy().astype(np.float64); uh = du.cpu().numpy().astype(np.float64)
-        if mbuf is not None:
-            return s, c, t, qh, uh, mbuf.cpu().numpy().astype(np.float64)
-        return s, c, t, qh, uh
-
-    HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
+        def call(ptr, hu, hist):
+            self._chk(self.lib.pg_simulate_dev(self.h, steps, C.c_double(dt), ptr(hist.get("state")), ptr(hist.get("control"))), "pg_simulate_dev")
+        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,)}, None, call, other=False)
+        return st + ((out["state"], out["control"]) if record else (None, None)) + tail
 
     def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False, measured=False):
         """Safety rollout (pg_simulate_safety_dev): simulate with the control the ROS node sends (ros_integration.jl:114-124) fed back, against an other car that moves.
@@ -421,34 +425,11 @@ class BatchedTrajectoryTrackingMPC:
         other) after `steps` steps and, with record=True, a dict of histories: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B],
         source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step.
         measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned."""
-        import ctypes as C_
-        import torch
-        assert human in self.HUMAN_MODES, human
-        dev = f"cuda:{self.cfg.device}"
-        tdt = torch.float32 if self.precision == "f32" else torch.float64         # device arrays have the library's own element type
-        hu = None
-        if human == "script":
-            if human_u is None:
-                raise ValueError('human="script" needs human_u [steps][B][2]')
-            hu = torch.as_tensor(np.ascontiguousarray(human_u, dtype=np.float64).reshape(steps, self.B, 2)).to(device=dev, dtype=tdt).contiguous()
-        shapes = {"state": (6,), "control": (3,), "other": (4,), "human": (2,), "V": ()}
-        hist = {k: torch.empty((steps, self.B) + s, dtype=tdt, device=dev) for k, s in shapes.items()} if record else {}
-        if record:
-            hist["source"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
-        ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
-        mbuf = self._measured_hist(measured, steps)
-        self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C_.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
-                                                  *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
-        s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
-        self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
-        self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
-        tail = () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
-        if not record:
-            return (s, c, t, o) + tail
-        out = {k: v.cpu().numpy() for k, v in hist.items()}
-        for k in shapes:
-            out[k] = out[k].astype(np.float64)
-        return (s, c, t, o, out) + tail
+        def call(ptr, hu, hist):
+            self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
+                                                      *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
+        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,), "other": (4,), "human": (2,), "V": ()}, "source", call, human, human_u)
+        return st + ((out,) if record else ()) + tail
 
     def safety_summary(self):
         """Per instance since the rollout's clock last restarted: (V_min [B], first_breach [B] (first step index with V <= 0, -1: none), policy_steps [B])."""
@@ -460,23 +441,20 @@ class BatchedTrajectoryTrackingMPC:
     NODE_EVENTS = {"mpc": 0, "hji_policy": 1, "feather": 2, "nan_fallback": 3, "pre_flag_off": 4, "outside_trajectory": 5, "low_speed": 6}
 
     def _pre_flag_dev(self, pre_flag, shape):
-        import torch
         if pre_flag is None:
             return None
-        return torch.as_tensor(np.ascontiguousarray(pre_flag, dtype=np.uint8).reshape(shape)).to(device=f"cuda:{self.cfg.device}").contiguous()
+        torch, _, dev = self._torch()
+        return torch.as_tensor(np.ascontiguousarray(pre_flag, dtype=np.uint8).reshape(shape)).to(device=dev).contiguous()
 
     def node_step_(self, use_HJI_policy=False, pre_flag=None):
         """One node callback per instance on the installed inputs (pg_node_step_dev): the installed control is the to_autobox message.  pre_flag [B] (None: engaged).
         Returns (cmd [B][3], se [B][2], event [B], message [B][3]): the published command (NaN where nothing was published), (s, e) of the step's projection, the
         pg_node_event code, and the message after the callback (the installed control now).  The clock does not advance."""
-        import ctypes as C_
-        import torch
-        dev = f"cuda:{self.cfg.device}"
-        tdt = torch.float32 if self.precision == "f32" else torch.float64
+        torch, tdt, dev = self._torch()
         cmd = torch.full((self.B, 3), float("nan"), dtype=tdt, device=dev); se = torch.empty((self.B, 2), dtype=tdt, device=dev)
         ev = torch.empty(self.B, dtype=torch.int32, device=dev)
         pf = self._pre_flag_dev(pre_flag, (self.B,))
-        ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         self._chk(self.lib.pg_node_step_dev(self.h, int(bool(use_HJI_policy)), ptr(pf), ptr(cmd), ptr(se), ptr(ev)), "pg_node_step_dev")
         c = np.zeros((self.B, 3))
         self._chk(self.lib.pg_get_state(self.h, None, _p(c), None), "pg_get_state")
@@ -487,36 +465,14 @@ class BatchedTrajectoryTrackingMPC:
         APPLIED command of the step's start, the other car as simulate_safety_.  pre_flag [steps][B] (None: engaged).  Returns (state, message, t, other, applied) after `steps`
         steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event).
         measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned."""
-        import ctypes as C_
-        import torch
-        assert human in self.HUMAN_MODES, human
-        dev = f"cuda:{self.cfg.device}"
-        tdt = torch.float32 if self.precision == "f32" else torch.float64
-        hu = None
-        if human == "script":
-            if human_u is None:
-                raise ValueError('human="script" needs human_u [steps][B][2]')
-            hu = torch.as_tensor(np.ascontiguousarray(human_u, dtype=np.float64).reshape(steps, self.B, 2)).to(device=dev, dtype=tdt).contiguous()
-        pf = self._pre_flag_dev(pre_flag, (steps, self.B))
-        shapes = {"state": (6,), "applied": (3,), "V": ()}
-        hist = {k: torch.empty((steps, self.B) + s, dtype=tdt, device=dev) for k, s in shapes.items()} if record else {}
-        if record:
-            hist["event"] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
-        ptr = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None
-        mbuf = self._measured_hist(measured, steps)
-        self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C_.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),
-                                                *(ptr(hist.get(k)) for k in ("state", "applied", "event", "V"))), "pg_simulate_node_dev")
-        s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4)); a = np.zeros((self.B, 3))
-        self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
-        self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
+        def call(ptr, hu, hist):
+            pf = self._pre_flag_dev(pre_flag, (steps, self.B))
+            self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),
+                                                    *(ptr(hist.get(k)) for k in ("state", "applied", "event", "V"))), "pg_simulate_node_dev")
+        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "applied": (3,), "V": ()}, "event", call, human, human_u)
+        a = np.zeros((self.B, 3))
         self._chk(self.lib.pg_get_node_state(self.h, _p(a), None, None), "pg_get_node_state")
-        tail = () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
-        if not record:
-            return (s, c, t, o, a) + tail
-        out = {k: v.cpu().numpy() for k, v in hist.items()}
-        for k in shapes:
-            out[k] = out[k].astype(np.float64)
-        return (s, c, t, o, a, out) + tail
+        return st + (a,) + ((out,) if record else ()) + tail
 
     def node_summary(self):
         """(applied [B][3], heartbeat [B], counts [B][4] = steps with pre_flag off / outside the window / low speed / NaN fallback since the clock last restarted)."""
@@ -527,9 +483,8 @@ class BatchedTrajectoryTrackingMPC:
     def simulate_clock(self, steps, t_start, dt=0.01):
         """The times the rollout's loop variable takes, per instance: (t_start .+ (0:dt:trajectory.t[end]))[1:steps] as Julia's range arithmetic gives them
         (model_predictive_control.jl:87; pg_simulate_clock) -- [steps][B]."""
-        import ctypes as C_
         ts = _f64(t_start).reshape(-1).copy(); out = np.zeros((steps, len(ts)))
-        self._chk(self.lib.pg_simulate_clock(self.h, C_.c_double(dt), int(steps), len(ts), _p(ts), _p(out)), "pg_simulate_clock")
+        self._chk(self.lib.pg_simulate_clock(self.h, C.c_double(dt), int(steps), len(ts), _p(ts), _p(out)), "pg_simulate_clock")
         return out
 
     def synchronize(self):
