@@ -252,6 +252,48 @@ int pg_get_measured_state(pg_handle* h, double* measured);
 /* the NEXT rollout call writes the measured state of its step k < steps to buf[k][B][6] (library element type); one-shot -- that call consumes the registration whether it succeeds or returns an error --; NULL cancels.  PG_ERR_STATE without a library */
 int pg_set_measured_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
 
+/* Actuator sets: what the PLANT of a rollout step integrates in place of the command, per instance -- tuning x plant x sensor x actuator studies as ONE batch.  A library of
+ * pg_actuator_set and a per-instance selection, shaped like pg_set_plant_sets.  BUILD-DEFINED: the reference has no actuator.  Its `simulate` applies the command of the
+ * previous step exactly (src/model_predictive_control.jl:94-95); on the car `from_autobox_callback` (src/ros_integration.jl:51-52) sets `current_control` to the command
+ * last SENT (:52), the line that would take the steering and forces last MEASURED is commented out above it (:51), so the node linearises and rate-limits about an input
+ * the car has not reached yet.  With a library installed pg_simulate_dev and pg_simulate_safety_dev keep, per instance and channel j of (delta, Fxf, Fxr), at clock
+ * step k with command c_k (what `control` holds at the start of the step):
+ *   g   = c_{k - delay_steps}                            (entries before the clock's first step = c at the clock start)
+ *   y   = tau == 0 ? g : a_{k-1} + alpha (g - a_{k-1}),  alpha = -expm1(-dt / tau), in the library's element type
+ *   a_k = rate == +Inf ? y : a_{k-1} + clamp(y - a_{k-1}, -rate dt, +rate dt),      a_{-1} = c at the clock start
+ * (tau, rate) = (tau_delta, rate_delta) for delta and (tau_fx, rate_fx) for each of Fxf, Fxr.  The plant of step k integrates a_k, held for the step (the StepControl of :94
+ * with a_k in place of c_k).  tau == 0 and rate == +Inf are COPIES without arithmetic: the identity set {0, 0, 0, 0, +Inf, +Inf} reproduces the handle without a library bit
+ * for bit, -0.0 and NaN payloads included.
+ * feedback: 0 = the controller's current_control (node 0 of the horizon, u_curr of the QP, the steering-rate rows) is the command last sent (:52, the deployed node);
+ *           1 = it is the actuator's position a_k (:51, the commented-out line).
+ * The control RECORD of a rollout under a library (control_hist_dev of pg_simulate_dev, the `push!(us, ...)` of :89; control_hist_dev of pg_simulate_safety_dev) is the APPLIED
+ * control a_k: the recorded step replays through the plant.  The commands are available through pg_set_command_history_dev; pg_get_state's control stays the command.
+ * State: a [B][3], the last PG_ACT_MAX_DELAY commands and their position restart WITH THE ROLLOUT CLOCK (pg_set_inputs*, another dt, another path end); a rollout call that
+ * continues the clock continues them.  Installing sets or an index between rollouts resets nothing: an instance whose delay grew reads older commands that are already there.
+ * Lifetime, index rule and errors as pg_set_plant_sets.  PG_ERR_INVALID (the handle is left unchanged): delay_steps outside [0, PG_ACT_MAX_DELAY]; tau_delta / tau_fx
+ * negative or not finite; rate_delta / rate_fx not > 0 (NaN included; +Inf is valid); feedback other than 0 / 1 -- the message names the field and the set.
+ * OUT OF SCOPE: the node callback keeps "message" and "applied" apart and leaves `applied` unwritten for a gated-out instance, so the next command cannot be handed back by a
+ * plain copy: pg_simulate_node_dev and pg_node_step_dev return PG_ERR_STATE while an actuator library is installed.  pg_step* and the phase calls ignore the library.
+ * Cost: one lane-per-instance launch (k_actuate) ahead of the step's compute kernels and one device-to-device copy of B x 3 elements behind the plant kernel, which is
+ * handed a buffer holding a_k as its `control` and leaves the next command there (no kernel changed).  Without a library: nothing allocated, the launches of before. */
+#define PG_ACT_MAX_DELAY 16
+typedef struct pg_actuator_set { int32_t delay_steps; int32_t feedback; double tau_delta; double tau_fx; double rate_delta; double rate_fx; } pg_actuator_set;
+int pg_set_actuator_sets(pg_handle* h, int32_t n_sets, const pg_actuator_set* sets);
+int pg_set_actuator_index(pg_handle* h, int32_t B, const int32_t* index);        /* index[b] in [0, n_sets) */
+int pg_clear_actuator_sets(pg_handle* h);                                        /* back to applied = command */
+/* the installed library, as pg_get_plant_sets */
+int pg_get_actuator_sets(pg_handle* h, int32_t* n_sets, pg_actuator_set* out, int32_t max_sets, int32_t* index, int32_t B);
+/* the NEXT rollout call writes a_k (applied) / c_k (command) of its step k < steps to buf[k][B][3] (library element type); one-shot -- that call consumes the registration
+ * whether it succeeds or returns an error --; NULL cancels.  PG_ERR_STATE without a library */
+int pg_set_applied_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
+int pg_set_command_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
+/* applied [B][3] = a of the last rollout step under a library; before the first such step since the clock restarted: the handle's control */
+int pg_get_actuator_state(pg_handle* h, double* applied);
+/* the law alone, ON THE DEVICE through the function k_actuate calls (k_actuator_response): commands [steps][B][3] on the host -> applied [steps][B][3], with the installed
+ * library and index over the current batch B (pg_set_inputs*), from a fresh state (a_{-1} = commands[0]).  Touches neither the rollout clock nor the handle's actuator
+ * state (scratch of its own).  steps >= 1, dt > 0; PG_ERR_STATE without inputs, without a library or with an index that does not cover the batch */
+int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* commands, double* applied);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -299,7 +341,8 @@ int pg_step_dev(pg_handle* h, pg_real_dev* u_out_dev);
 /* simulate(mpc, q0, u0, dt)  src/model_predictive_control.jl:80-100 for every instance, entirely on the device (no host round trip between
  * steps): per step  record -> the four compute calls -> state = propagate(dynamics, state, StepControl(dt, old control)) -> control = get_next_control
  * -> t = the next element of the loop's range (see pg_simulate_clock below).  Starts from the inputs last installed (pg_set_inputs*: state, control, t0, time_offset) and leaves the final ones there
- * (pg_get_state reads them).  state_hist_dev [steps][B][6] / control_hist_dev [steps][B][3] may be NULL.  Asynchronous on the handle's stream. */
+ * (pg_get_state reads them).  state_hist_dev [steps][B][6] / control_hist_dev [steps][B][3] may be NULL.  Asynchronous on the handle's stream.
+ * Under an actuator library (pg_set_actuator_sets) control_hist_dev records the APPLIED control a_k, the input the plant of step k integrates. */
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, pg_real_dev* state_hist_dev, pg_real_dev* control_hist_dev);
 /* The loop variable of that rollout: `for t in 0:dt:mpc.trajectory.t[end]` (src/model_predictive_control.jl:87) is a Julia RANGE -- element k is ONE rounding of k dt with dt lifted
  * to its exact rational (0.01 = 1/100) when dt and the path's end time have one, `fl(k dt)` otherwise -- not the accumulation t += dt (which is 0.2900000000000001 at step 29 and
@@ -324,7 +367,8 @@ int pg_get_state(pg_handle* h, double* state, double* control, double* t0);
  * Histories may be NULL: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B] (library element type), source [steps][B] (int32:
  * 0 MPC, 1 HJI policy, 2 V <= eps with the policy off).  Coupled formulation only (PG_ERR_STATE); human_mode outside {0, 1, 2}, mode 2 without human_u_dev, steps < 1 or
  * dt <= 0: PG_ERR_INVALID.  Asynchronous on the handle's stream.  The gates of the node (pre_flag, the trajectory-time window, the low-speed pause), the NaN fallback and
- * the decoupled formulation are pg_simulate_node_dev's (below). */
+ * the decoupled formulation are pg_simulate_node_dev's (below).  Under an actuator library (pg_set_actuator_sets) the control history is the APPLIED control a_k: the kernel
+ * records the control it is handed, and it is handed the actuator's output. */
 int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const pg_real_dev* human_u_dev,
                            pg_real_dev* state_hist_dev, pg_real_dev* control_hist_dev, pg_real_dev* other_hist_dev,
                            pg_real_dev* human_hist_dev, pg_real_dev* V_hist_dev, int32_t* source_hist_dev);
@@ -351,7 +395,7 @@ enum pg_node_event {
  * the callback (the published command, 0 after a fallback, unchanged when gated out).  Device outputs, each may be NULL: cmd_out [B][3] the published command (lanes that
  * publish nothing are not written), se_out [B][2] (s, e) of the step's projection (:114), event [B] (int32, pg_node_event).  pre_flag_dev [B] (uint8) or NULL = engaged.
  * The clock does not advance.  Decoupled handles: V = +Inf, use_hji_policy != 0 is PG_ERR_STATE.  Gated-out instances are computed too (their results are discarded):
- * the call costs a full step.  Asynchronous on the handle's stream. */
+ * the call costs a full step.  Asynchronous on the handle's stream.  PG_ERR_STATE while an actuator library is installed (pg_set_actuator_sets: out of scope). */
 int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_flag_dev, pg_real_dev* cmd_out_dev, pg_real_dev* se_out_dev, int32_t* event_dev);
 /* The node's closed loop.  Each instance keeps two controls: the message (the installed control) and the applied command (what the plant executes; initialised from the
  * installed control whenever the clock restarts).  Per step: the gates; the compute calls as pg_simulate_safety_dev makes them; the callback's decision as above; the records
@@ -360,7 +404,8 @@ int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_fl
  * end with the same element formula); the safety summary of pg_get_safety_state (V_min and first breach at every step, policy steps: published policy commands).
  * pre_flag_dev [steps][B] or NULL.  Histories may be NULL: state [steps][B][6], applied [steps][B][3], V [steps][B] (library element type), event [steps][B] (int32).
  * With every gate open and no NaN this is pg_simulate_safety_dev.  steps < 1, dt <= 0, human_mode outside {0, 1, 2}, mode 2 without human_u_dev: PG_ERR_INVALID;
- * use_hji_policy on a decoupled handle: PG_ERR_STATE.  Asynchronous on the handle's stream. */
+ * use_hji_policy on a decoupled handle: PG_ERR_STATE.  Asynchronous on the handle's stream.  PG_ERR_STATE while an actuator library is installed (pg_set_actuator_sets:
+ * the hand-back of the next command is not a plain copy here -- a gated-out instance leaves `applied` unwritten). */
 int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const pg_real_dev* human_u_dev, const uint8_t* pre_flag_dev,
                          pg_real_dev* state_hist_dev, pg_real_dev* applied_hist_dev, int32_t* event_hist_dev, pg_real_dev* V_hist_dev);
 /* applied command [B][3]; heartbeat [B] (callbacks that ran the compute calls; zero at the first node call, never reset); counts [B][4] = steps with pre_flag off, outside
@@ -425,6 +470,7 @@ int pg_synchronize(pg_handle* h);
  *                                4096-instance step); 0 = no instrumentation, pg_get_phase_ms returns PG_ERR_STATE
  *     "graph" 0/1 (0)            pg_step of a small warm batch as one hipGraph launch (see pg_step)
  *     "stat_sensor_steps"        (read-only) rollout steps that ran under a sensor library (k_measure launches) since pg_create
+ *     "stat_actuator_steps"      (read-only) rollout steps whose plant launch ran under an actuator library (k_actuate launches) since pg_create
  *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact

@@ -239,6 +239,58 @@ end
 set_measured_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
     check(mpc, ccall(sym(mpc, :pg_set_measured_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_measured_history_dev")
 
+# Actuator sets (pg_set_actuator_sets ...): command delay, lag and slew between the controller and the plant of the rollouts.  NOT EXECUTED in the build container, like the rest of this file.
+const PG_ACT_MAX_DELAY = 16
+"One actuator (pg_actuator_set): transport delay in rollout steps (0 .. PG_ACT_MAX_DELAY), what the controller sees as current_control (0: the command last sent, src/ros_integration.jl:52; 1: the actuator's position, the commented-out :51), first-order time constants (s; 0 = none) and slew limits (rad/s, N/s; Inf = none) of steering and of each longitudinal force channel.  PgActuatorSet() is the identity: the handle without a library, bit for bit."
+struct PgActuatorSet
+    delay_steps::Int32
+    feedback::Int32
+    tau_delta::Float64
+    tau_fx::Float64
+    rate_delta::Float64
+    rate_fx::Float64
+end
+PgActuatorSet(; delay_steps=0, feedback=0, tau_delta=0.0, tau_fx=0.0, rate_delta=Inf, rate_fx=Inf) = PgActuatorSet(Int32(delay_steps), Int32(feedback), Float64(tau_delta), Float64(tau_fx), Float64(rate_delta), Float64(rate_fx))
+"layout self-check of the hand copy above against include/pigeon_mpc.h (two int32, then four doubles: 40 bytes, no padding)"
+function check_actuator_layout()
+    off(f) = Int(fieldoffset(PgActuatorSet, Base.fieldindex(PgActuatorSet, f)))
+    (sizeof(PgActuatorSet), off(:delay_steps), off(:feedback), off(:tau_delta), off(:tau_fx), off(:rate_delta), off(:rate_fx)) == (40, 0, 4, 8, 16, 24, 32) ||
+        error("PigeonMI355X.jl: PgActuatorSet differs from pg_actuator_set of include/pigeon_mpc.h")
+end
+"What the PLANT of simulate / the safety rollout integrates in place of the command: a library of actuators and the set each instance runs under (0-based; may be empty for a library of one).  Resets nothing.  The node rollout refuses to run under a library."
+function set_actuators!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgActuatorSet}, index::Vector{Int32}=Int32[])
+    check_actuator_layout()
+    check(mpc, ccall(sym(mpc, :pg_set_actuator_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgActuatorSet}), mpc.handle, length(sets), sets), "pg_set_actuator_sets")
+    isempty(index) || check(mpc, ccall(sym(mpc, :pg_set_actuator_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_actuator_index")
+end
+"back to applied = command"
+clear_actuators!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_actuator_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_actuator_sets")
+"(sets, index over the first B instances; -1 where no index covers an instance) as installed"
+function actuators(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_actuator_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgActuatorSet}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_actuator_sets")
+    sets = Vector{PgActuatorSet}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_actuator_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgActuatorSet}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_actuator_sets")
+    sets, index
+end
+"3 x B: the applied control of the last rollout step under an actuator library (the handle's control before the first one since the clock restarted)"
+function actuator_state(mpc::BatchedTrajectoryTrackingMPC)
+    a = zeros(3, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_actuator_state), Cint, (Ptr{Cvoid}, Ptr{Float64}), mpc.handle, a), "pg_get_actuator_state")
+    a
+end
+"The law alone, on the device: commands 3 x B x steps -> applied 3 x B x steps under the installed library and index, from a fresh state"
+function actuator_response(mpc::BatchedTrajectoryTrackingMPC, commands::Array{Float64,3}, dt::Float64)
+    applied = similar(commands)
+    check(mpc, ccall(sym(mpc, :pg_actuator_response), Cint, (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}), mpc.handle, size(commands, 3), dt, commands, applied), "pg_actuator_response")
+    applied
+end
+"The NEXT rollout call writes the applied control / the command of its step k < steps to a device array 3 x B x steps of the library's element type (one-shot; C_NULL cancels)"
+set_applied_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_applied_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_applied_history_dev")
+set_command_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_command_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_command_history_dev")
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

@@ -65,6 +65,15 @@ struct pg_handle {
     real *d_meas = nullptr, *d_sep_true = nullptr; bool meas_valid = false;
     real* meas_hist = nullptr; int meas_hist_steps = 0;          // pg_set_measured_history_dev: one-shot, consumed by the next rollout call
     int64_t stat_sensor_steps = 0;                                // read-only option "stat_sensor_steps"
+    // actuator library (pg_set_actuator_sets / pg_set_actuator_index): what the plant of a rollout step is handed in place of the command.  Beside the sets, allocated when a
+    // rollout first runs under a library: the actuator's position d_act [cap][3], the command ring d_act_ring [PG_ACT_MAX_DELAY][cap][3], d_plant_u [cap][3] (the plant
+    // kernel's `control`: a_k going in, the next command coming out) and, while some installed set has feedback == 1, d_seen [cap][3] (the compute kernels' current_control)
+    SetLib<pg_actuator_set, DevActuator> acts{{"actuator", "pg_set_actuator_index"}};
+    real *d_act = nullptr, *d_act_ring = nullptr, *d_plant_u = nullptr, *d_seen = nullptr;
+    bool act_feedback = false;                                    // some installed set has feedback == 1
+    bool act_fresh = true;                                        // the actuator state restarts at the next step under a library (the clock restarted, or no step ran under one since)
+    real *applied_hist = nullptr, *command_hist = nullptr; int applied_hist_steps = 0, command_hist_steps = 0;      // pg_set_applied_history_dev / pg_set_command_history_dev: one-shot
+    int64_t stat_actuator_steps = 0;                              // read-only option "stat_actuator_steps"
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -317,9 +326,9 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release();
+    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release();
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
     if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
@@ -537,6 +546,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     // read-only launch statistics of this handle
     if (n == "stat_pipelined_launches") return S(&h->stat_pipelined);
     if (n == "stat_sensor_steps") return S(&h->stat_sensor_steps);
+    if (n == "stat_actuator_steps") return S(&h->stat_actuator_steps);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -615,7 +625,7 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
 }
 int pg_synchronize(pg_handle* h) { if (!h) return PG_ERR_INVALID; HIPCHK(h, hipStreamSynchronize(h->stream)); return PG_OK; }
 
-// ---- what the four libraries share (trajectories, control parameters, plants, sensors): one index rule and one install / clear / get protocol ----
+// ---- what the five libraries share (trajectories, control parameters, plants, sensors, actuators): one index rule and one install / clear / get protocol ----
 // Installs the selection of `B` instances into a library of `n_sets`.  The WHOLE [capacity] array is written, entries beyond B as 0: never an address outside the library,
 // whatever an earlier, larger library left there
 static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, const int32_t* index) {
@@ -903,6 +913,91 @@ int pg_get_measured_state(pg_handle* h, double* measured) {
     return down(h, measured, h->d_meas, (size_t)h->B * 6);
 }
 
+// ---- actuator library: the control the PLANT of a rollout step integrates, a_k = actuator(c_{k - delay}, a_{k-1}) per channel (k_actuate).  Build-defined (the reference
+// applies the command exactly, model_predictive_control.jl:94-95; ros_integration.jl:51-52 is the choice `feedback` restates).  No part of any QP's structure: nothing is reset ----
+static const char* actuator_field_problem(const pg_actuator_set& s) {
+    if (s.delay_steps < 0 || s.delay_steps > PG_ACT_MAX_DELAY) return "delay_steps outside [0, PG_ACT_MAX_DELAY = 16]";
+    if (!std::isfinite(s.tau_delta) || s.tau_delta < 0.0) return "tau_delta must be finite and >= 0";
+    if (!std::isfinite(s.tau_fx) || s.tau_fx < 0.0) return "tau_fx must be finite and >= 0";
+    if (!(s.rate_delta > 0.0)) return "rate_delta must be > 0 or +Inf";
+    if (!(s.rate_fx > 0.0)) return "rate_fx must be > 0 or +Inf";
+    if (s.feedback != 0 && s.feedback != 1) return "feedback must be 0 or 1";
+    return nullptr;
+}
+static void fill_dev_actuator(DevActuator& A, const pg_actuator_set& s) {
+    A.delay = s.delay_steps; A.feedback = s.feedback; A.tau_delta = (real)s.tau_delta; A.tau_fx = (real)s.tau_fx; A.rate_delta = (real)s.rate_delta; A.rate_fx = (real)s.rate_fx;
+}
+int pg_set_actuator_sets(pg_handle* h, int32_t n_sets, const pg_actuator_set* sets) {
+    if (!h) return PG_ERR_INVALID;
+    std::string why;                                            // (the message names the field and the set)
+    const int rc = setlib_install(h, "pg_set_actuator_sets", h->acts, n_sets, sets, [&](const pg_actuator_set& s) -> const char* {
+        const char* f = actuator_field_problem(s);
+        if (!f) return nullptr;
+        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
+        return why.c_str();
+    }, fill_dev_actuator);
+    if (rc) return rc;
+    h->act_feedback = false;
+    for (const pg_actuator_set& s : h->acts.sets) h->act_feedback = h->act_feedback || s.feedback == 1;
+    return PG_OK;
+}
+int pg_set_actuator_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    return index_install(h, (int)h->acts.sets.size(), h->acts.idx, B, index);
+}
+int pg_clear_actuator_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    const int rc = setlib_clear(h, h->acts); if (rc) return rc;
+    h->act_feedback = false; h->act_fresh = true;               // (a library installed later starts from the command it finds)
+    h->applied_hist = nullptr; h->command_hist = nullptr; h->applied_hist_steps = 0; h->command_hist_steps = 0;
+    return PG_OK;
+}
+int pg_get_actuator_sets(pg_handle* h, int32_t* n_sets, pg_actuator_set* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    return setlib_get(h, "pg_get_actuator_sets", h->acts, n_sets, out, max_sets, index, B);
+}
+static int actuator_set_history(pg_handle* h, const char* who, real*& slot, int& slot_steps, pg_real_dev* buf, int32_t steps) {
+    if (!h) return PG_ERR_INVALID;
+    if (!buf) { slot = nullptr; slot_steps = 0; return PG_OK; }
+    REQUIRE(h, steps >= 1, std::string(who) + ": steps >= 1 required");
+    if (h->acts.sets.empty()) { h->err = std::string(who) + ": no actuator library installed (applied = command: record control_hist)"; return PG_ERR_STATE; }
+    slot = (real*)buf; slot_steps = steps;
+    return PG_OK;
+}
+int pg_set_applied_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
+    return h ? actuator_set_history(h, "pg_set_applied_history_dev", h->applied_hist, h->applied_hist_steps, buf, steps) : PG_ERR_INVALID;
+}
+int pg_set_command_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
+    return h ? actuator_set_history(h, "pg_set_command_history_dev", h->command_hist, h->command_hist_steps, buf, steps) : PG_ERR_INVALID;
+}
+int pg_get_actuator_state(pg_handle* h, double* applied) {
+    int rc = check_ready(h); if (rc) return rc;
+    const bool stepped = !h->acts.sets.empty() && !h->act_fresh && h->d_act;      // (else: no step under a library since the clock restarted -- the position is the command)
+    return down(h, applied, stepped ? h->d_act : h->d_control, (size_t)h->B * 3);
+}
+int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* commands, double* applied) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, steps >= 1 && dt > 0.0 && commands && applied, "pg_actuator_response: steps >= 1, dt > 0 and both arrays required");
+    if (h->B <= 0) { h->err = "pg_actuator_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
+    if (h->acts.sets.empty()) { h->err = "pg_actuator_response: no actuator library installed"; return PG_ERR_STATE; }
+    if (index_covers(h, h->acts.sets.size(), h->acts.idx)) return PG_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = h->B;
+    const size_t n = (size_t)steps * (size_t)B * 3;
+    real* d = nullptr;                                           // scratch of the call: commands, applied, ring
+    HIPCHK(h, hipMalloc((void**)&d, (2 * n + (size_t)PG_ACT_MAX_DELAY * B * 3) * sizeof(real)));
+    int rc = up(h, d, commands, n);
+    if (!rc) {
+        hipLaunchKernelGGL(k_actuator_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, (int)steps, (real)dt, h->acts.d,
+                           h->acts.sets.size() > 1 ? h->acts.idx.d : (const int*)nullptr, d + 2 * n, d, d + n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { h->err = std::string("pg_actuator_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
+    }
+    if (!rc) rc = down(h, applied, d + n, n);
+    (void)hipFree(d);
+    return rc;
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -974,7 +1069,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1505,6 +1600,35 @@ static int rollout_ready(pg_handle* h) {
         if (h->tracking && !h->d_sep_true) HIPCHK(h, hipMalloc((void**)&h->d_sep_true, cap * 4 * sizeof(real)));
         const int rc = sensor_streams_sync(h); if (rc) return rc;
     }
+    if (!h->acts.sets.empty()) {
+        if (index_covers(h, h->acts.sets.size(), h->acts.idx)) return PG_ERR_STATE;
+        const size_t cap = cap_of(h);
+        if (!h->d_act) HIPCHK(h, hipMalloc((void**)&h->d_act, cap * 3 * sizeof(real)));
+        if (!h->d_act_ring) HIPCHK(h, hipMalloc((void**)&h->d_act_ring, (size_t)PG_ACT_MAX_DELAY * cap * 3 * sizeof(real)));
+        if (!h->d_plant_u) HIPCHK(h, hipMalloc((void**)&h->d_plant_u, cap * 3 * sizeof(real)));
+        if (h->act_feedback && !h->d_seen) HIPCHK(h, hipMalloc((void**)&h->d_seen, cap * 3 * sizeof(real)));
+    }
+    return PG_OK;
+}
+// the actuator library (the host knows whether one is installed: that alone adds k_actuate and the copy-back to a rollout step).  actuator_take_history: the one-shot
+// registrations of pg_set_applied_history_dev / pg_set_command_history_dev, consumed by the rollout call that starts now
+static bool actuator_lib_on(const pg_handle* h) { return !h->acts.sets.empty(); }
+struct ActHist { real *applied, *command; int applied_steps, command_steps; };
+static ActHist actuator_take_history(pg_handle* h) {
+    const ActHist a{h->applied_hist, h->command_hist, h->applied_hist_steps, h->command_hist_steps};
+    h->applied_hist = nullptr; h->command_hist = nullptr; h->applied_hist_steps = 0; h->command_hist_steps = 0;
+    return a;
+}
+// the top of a rollout step under a library: a_k of clock step `step` from the command the handle's control buffer holds, into d_act, d_plant_u (and d_seen)
+static int launch_actuate(pg_handle* h, int step, int k, double dt, const ActHist& ah) {
+    const int B = h->B;
+    const ActuatorLib lib{h->acts.d, h->acts.sets.size() > 1 ? h->acts.idx.d : (const int*)nullptr, h->d_act, h->d_act_ring, h->d_plant_u,
+                          h->act_feedback ? h->d_seen : (real*)nullptr, (int)cap_of(h)};
+    hipLaunchKernelGGL(k_actuate, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, (int)h->act_fresh, (real)dt, lib, h->d_control,
+                       (ah.applied && k < ah.applied_steps) ? ah.applied + (size_t)k * B * 3 : (real*)nullptr,
+                       (ah.command && k < ah.command_steps) ? ah.command + (size_t)k * B * 3 : (real*)nullptr);
+    LAUNCH_CHECK(h);
+    h->act_fresh = false;
     return PG_OK;
 }
 // the sensor library (the host knows whether one is installed: that alone adds k_measure to a rollout step).  sensor_take_history: the one-shot registration of
@@ -1553,7 +1677,7 @@ static int launch_track(pg_handle* h, int step) {
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true;
     }
     return PG_OK;
 }
@@ -1571,19 +1695,40 @@ static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, const A&..
 // rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records(k) ahead of the compute calls, the
 // controller's side (:90-93, on the measured state under a sensor library), the tracking summary, the clock index, then finish(k, step): the step's last launch, which moves
 // the plant (step: index of the clock element t0 held -- steps continue across calls)
+static const char* const ACTUATOR_NODE_REFUSAL = "an actuator library is installed and the node callback is outside its scope (k_node_finish keeps message and applied command "
+                                                 "apart and leaves `applied` unwritten for a gated-out instance: no plain hand-back of the next command); pg_clear_actuator_sets first";
 struct RolloutArgs { const char* who; int32_t steps; double dt; int32_t human_mode; const void* human_u; const char* coupled_only; bool node; const uint8_t* pre_flag; };
 template <class Records, class Finish>
 static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish finish) {
     const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};
+    const ActHist ah = h ? actuator_take_history(h) : ActHist{nullptr, nullptr, 0, 0};
     int rc = check_ready(h); if (rc) return rc;
     if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
+    if (a.node && actuator_lib_on(h)) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
     if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u)) || (rc = rollout_ready(h)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
+    // Under an actuator library the handle's control pointer names, while the launches are QUEUED: d_plant_u (= a_k) for the records and the plant launch, d_seen for the
+    // compute calls when some set has feedback == 1 -- k_nodes*, the QP's u_curr and the steering-rate rows all take the pointer from the handle --, and its own allocation
+    // (the command) everywhere else and whenever this function returns.  The plant kernel leaves the next command in d_plant_u: one copy moves it to the control buffer
+    const bool act = actuator_lib_on(h);
+    real* const command = h->d_control;
     for (int k = 0; k < a.steps; k++) {
         const int step = h->sim_idx - 1;
-        if ((rc = records(k)) || (rc = rollout_compute(h, step, k, mh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr)) || (rc = launch_track(h, step))) return rc;
+        if (act && (rc = launch_actuate(h, step, k, a.dt, ah))) return rc;
+        if (act) h->d_control = h->d_plant_u;
+        rc = records(k);
+        if (act) h->d_control = h->act_feedback ? h->d_seen : command;
+        if (!rc) rc = rollout_compute(h, step, k, mh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
+        h->d_control = command;
+        if (rc || (rc = launch_track(h, step))) return rc;
         h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)
+        if (act) h->d_control = h->d_plant_u;
         finish(k, step);
+        h->d_control = command;
         LAUNCH_CHECK(h);
+        if (act) {
+            HIPCHK(h, hipMemcpyAsync(command, h->d_plant_u, (size_t)h->B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
+            h->stat_actuator_steps++;
+        }
     }
     return PG_OK;
 }
@@ -1700,6 +1845,7 @@ static void node_done(pg_handle* h) { h->node_parity ^= 1; h->node_recheck = tru
 int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_flag_dev, void* cmd_out_dev, void* se_out_dev, int32_t* event_dev) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_node_step_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
+    if (!h->acts.sets.empty()) { h->err = std::string("pg_node_step_dev: ") + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
     if ((rc = node_prepare(h)) || (rc = node_gate(h, pre_flag_dev)) || (rc = step_compute(h))) return rc;
     NodeIO io = node_io(h);
     io.cmd_out = (real*)cmd_out_dev; io.se_out = (real*)se_out_dev; io.event = event_dev;

@@ -698,4 +698,44 @@ PG_DEV void sensor_draws(uint64_t seed, uint64_t stream, uint32_t step, real z[6
 // one set of a sensor library (pg_set_sensor_sets) in the arithmetic type of the build, channels (E, N, psi, Ux, Uy, r)
 struct DevSensor { real sigma[6], bias[6]; };
 
+// ---- actuator of the rollouts (pg_set_actuator_sets; build-defined: the reference's `simulate` applies the command exactly, model_predictive_control.jl:94-95, and the node
+// takes current_control from the command last sent, ros_integration.jl:51-52) ----
+// one set of an actuator library in the arithmetic type of the build: transport delay in rollout steps, first-order time constants and slew limits of steering and of each
+// longitudinal force channel, and what the controller is shown as current_control (0: the command, 1: the actuator's position)
+#define PG_ACT_RING PG_ACT_MAX_DELAY                                        // commands kept per instance (a power of two: slots by mask)
+static_assert((PG_ACT_RING & (PG_ACT_RING - 1)) == 0, "the ring's slots are taken by mask");
+struct DevActuator { int delay, feedback; real tau_delta, tau_fx, rate_delta, rate_fx; };
+PG_DEV float pg_expm1(float x) { return expm1f(x); }
+PG_DEV double pg_expm1(double x) { return expm1(x); }
+// The law for one instance and one clock step, channels (delta, Fxf, Fxr): g = the delayed command, a = the actuator's position (in: a_{k-1}, out: a_k).
+//   y = tau == 0 ? g : a + alpha (g - a), alpha = -expm1(-dt / tau);   a_k = rate == +Inf ? y : a + clamp(y - a, -rate dt, +rate dt)
+// tau == 0 and rate == +Inf are COPIES (no arithmetic: -0.0 and NaN payloads survive).  No contraction: every product and sum is rounded once, as the numpy twin rounds it
+PG_DEV void actuator_step(const DevActuator& A, real dt, const real g[3], real a[3]) {
+#pragma clang fp contract(off)
+    for (int j = 0; j < 3; j++) {
+        const real tau = j == 0 ? A.tau_delta : A.tau_fx, rate = j == 0 ? A.rate_delta : A.rate_fx;
+        real y = g[j];
+        if (tau != real(0.0)) { const real alpha = -pg_expm1(-dt / tau); y = a[j] + alpha * (g[j] - a[j]); }
+        if (rate != real(INFINITY)) {
+            const real lim = rate * dt, d = y - a[j];
+            y = a[j] + (d < -lim ? -lim : (d > lim ? lim : d));
+        }
+        a[j] = y;
+    }
+}
+// One clock step of instance b with its command ring [PG_ACT_RING][cap][3] (slot-major: the lanes of a wavefront read one slot contiguously): the delayed command is read
+// from slot (step - delay) mod PG_ACT_RING BEFORE this step's command goes into slot step mod PG_ACT_RING (delay = PG_ACT_RING names the same slot), then the law.
+// restart: the clock starts here -- every slot and a_{-1} are the command c.  The ring is read and written by its own lane only
+PG_DEV void actuator_advance(const DevActuator& A, real dt, int step, bool restart, int b, int cap, real* ring, const real c[3], real a[3]) {
+    if (restart) {
+        for (int s = 0; s < PG_ACT_RING; s++) for (int j = 0; j < 3; j++) ring[((size_t)s * cap + b) * 3 + j] = c[j];
+        for (int j = 0; j < 3; j++) a[j] = c[j];
+    }
+    real g[3] = {c[0], c[1], c[2]};
+    if (A.delay > 0) { const real* r = ring + ((size_t)((step - A.delay) & (PG_ACT_RING - 1)) * cap + b) * 3; g[0] = r[0]; g[1] = r[1]; g[2] = r[2]; }
+    real* w = ring + ((size_t)(step & (PG_ACT_RING - 1)) * cap + b) * 3;
+    w[0] = c[0]; w[1] = c[1]; w[2] = c[2];
+    actuator_step(A, dt, g, a);
+}
+
 }  // namespace pg

@@ -1093,6 +1093,45 @@ __global__ __launch_bounds__(64) void k_sensor_draws(int B, int step0, int steps
     for (int c = 0; c < 6; c++) z[(size_t)i * 6 + c] = d[c];
 }
 
+// Actuator library (pg_set_actuator_sets), lane = instance: the control the PLANT of a rollout step integrates, a_k = actuator(c_{k - delay}, a_{k-1}) per channel of
+// (delta, Fxf, Fxr) (actuator_advance / actuator_step, pg_device.hpp).  Queued at the top of the step, ahead of the compute calls.  Reads `control` (= c_k, only read), the
+// instance's record (copied into registers once), act [cap][3] and the ring; writes the ring slot, act and plant_u [cap][3] (= a_k: the buffer the plant kernel is handed as
+// its `control`), seen [cap][3] (feedback ? a_k : c_k: what the compute kernels are handed as current_control; nullptr when no installed set has feedback == 1) and the
+// step's rows of the applied / command histories when registered.  idx == nullptr: a library of one.  `restart`: the clock starts at this step
+struct ActuatorLib { const DevActuator* sets; const int* idx; real* act; real* ring; real* plant_u; real* seen; int cap; };
+__global__ __launch_bounds__(64) void k_actuate(int B, int step, int restart, real dt, ActuatorLib lib, const real* __restrict__ control, real* __restrict__ applied_h,
+                                                real* __restrict__ command_h) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevActuator A = lib.sets[lib.idx ? lib.idx[b] : 0];
+    const real c[3] = {control[(size_t)b * 3], control[(size_t)b * 3 + 1], control[(size_t)b * 3 + 2]};
+    real a[3] = {real(0.0), real(0.0), real(0.0)};
+    if (!restart) for (int j = 0; j < 3; j++) a[j] = lib.act[(size_t)b * 3 + j];
+    actuator_advance(A, dt, step, restart != 0, b, lib.cap, lib.ring, c, a);
+    for (int j = 0; j < 3; j++) {
+        lib.act[(size_t)b * 3 + j] = a[j];
+        lib.plant_u[(size_t)b * 3 + j] = a[j];
+        if (lib.seen) lib.seen[(size_t)b * 3 + j] = A.feedback ? a[j] : c[j];
+        if (applied_h) applied_h[(size_t)b * 3 + j] = a[j];
+        if (command_h) command_h[(size_t)b * 3 + j] = c[j];
+    }
+}
+// pg_actuator_response: the applied sequence [steps][B][3] of a caller's command sequence [steps][B][3] through the function k_actuate calls, from a fresh state, with a
+// scratch ring [PG_ACT_RING][B][3] of the call's own (lane = instance; the steps in order)
+__global__ __launch_bounds__(64) void k_actuator_response(int B, int steps, real dt, const DevActuator* __restrict__ sets, const int* __restrict__ idx, real* ring,
+                                                          const real* __restrict__ commands, real* __restrict__ applied) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevActuator A = sets[idx ? idx[b] : 0];
+    real a[3] = {real(0.0), real(0.0), real(0.0)};
+    for (int k = 0; k < steps; k++) {
+        const size_t at = ((size_t)k * B + b) * 3;
+        const real c[3] = {commands[at], commands[at + 1], commands[at + 2]};
+        actuator_advance(A, dt, k, k == 0, b, B, ring, c, a);
+        for (int j = 0; j < 3; j++) applied[at + j] = a[j];
+    }
+}
+
 // ==================================================================================================================
 // Decoupled (lateral) formulation: decoupled_lat_long.jl.  The lateral QP (state (Uy, r, dpsi, e), input delta) is EMBEDDED in the
 // 8-state stage structure k_solve works on: x = (0, Ux_dummy, Uy, r, dpsi, e, delta, 0) with identity dynamics, zero cost and

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -291,6 +291,64 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_measured_state(self.h, _p(m)), "pg_get_measured_state")
         return m
 
+    # ---- the ACTUATOR of the rollouts, per instance (command delay, lag, slew): a library of pg_actuator_set and a per-instance selection ----
+    @classmethod
+    def pack_actuators(cls, sets):
+        """actuator dicts (vehicles.actuator(**overrides); missing fields: the identity's) or pg_actuator_set structures -> a ctypes array of pg_actuator_set."""
+        def fill(rec, v):
+            a = _identity_actuator(**v)
+            d = int(a["delay_steps"])
+            if d != a["delay_steps"] or not 0 <= d <= _lib.PG_ACT_MAX_DELAY:
+                raise ValueError(f"delay_steps = {a['delay_steps']} is outside 0 .. PG_ACT_MAX_DELAY = {_lib.PG_ACT_MAX_DELAY} rollout steps")
+            rec.delay_steps = d; rec.feedback = int(a["feedback"])
+            for name in ("tau_delta", "tau_fx", "rate_delta", "rate_fx"):
+                setattr(rec, name, float(a[name]))
+        return cls._pack(_lib.pg_actuator_set, sets, fill)
+
+    def set_actuators(self, sets, idx=None):
+        """What the plant of simulate_ / simulate_safety_ integrates in place of the command (pg_set_actuator_sets): per channel of (delta, Fxf, Fxr) the command delayed by
+        delay_steps, through a first-order lag tau and a slew limit rate; feedback = 1 shows the controller the actuator's position as current_control.  One set (dict /
+        structure) for the whole batch, or a list of sets selected per instance with `idx`.  Resets nothing.  simulate_node_ / node_step_ refuse to run under a library."""
+        self._set_sets("actuator", _lib.pg_actuator_set, self.pack_actuators, sets, idx)
+
+    def set_actuator_index(self, idx):
+        self._set_index("actuator", idx)
+
+    def clear_actuators(self):
+        self._chk(self.lib.pg_clear_actuator_sets(self.h), "pg_clear_actuator_sets")
+
+    def get_actuators(self):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        return self._get_sets("actuator", _lib.pg_actuator_set, lambda r: {name: getattr(r, name) for name, _ in r._fields_})
+
+    def actuator_state(self):
+        """[B][3]: the applied control a of the last rollout step under a library; the handle's control before the first one since the clock restarted (pg_get_actuator_state)."""
+        a = np.zeros((self.B, 3))
+        self._chk(self.lib.pg_get_actuator_state(self.h, _p(a)), "pg_get_actuator_state")
+        return a
+
+    def actuator_response(self, commands, dt):
+        """The law alone, on the device through the function the rollouts call (pg_actuator_response): commands [steps][B][3] -> applied [steps][B][3] under the installed
+        library and index, from a fresh state.  B is the batch of the inputs last installed."""
+        c = _f64(commands).reshape(-1, self.B, 3)
+        out = np.zeros_like(c)
+        self._chk(self.lib.pg_actuator_response(self.h, c.shape[0], C.c_double(dt), _p(c), _p(out)), "pg_actuator_response")
+        return out
+
+    def _actuator_hists(self, record, steps):
+        """registers [steps][B][3] device records of the applied control and of the command with the next rollout call; {} unless record and a library is installed"""
+        if not record:
+            return {}
+        n = C.c_int32(0)
+        self._chk(self.lib.pg_get_actuator_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_actuator_sets")
+        if n.value == 0:
+            return {}
+        torch, tdt, dev = self._torch()
+        bufs = {k: torch.empty(int(steps), self.B, 3, dtype=tdt, device=dev) for k in ("applied", "command")}
+        for k, buf in bufs.items():
+            self._chk(getattr(self.lib, f"pg_set_{k}_history_dev")(self.h, C.c_void_p(buf.data_ptr()), int(steps)), f"pg_set_{k}_history_dev")
+        return bufs
+
     def _torch(self):
         """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""
         import torch
@@ -387,7 +445,8 @@ class BatchedTrajectoryTrackingMPC:
 
     def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True):
         """The rollouts' shared plumbing.  Device records [steps][B] + shapes[name] in the library's element type and one int32 record `int_record` (record=True), the scripted
-        human [steps][B][2], the measured history; call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
+        human [steps][B][2], the measured history, under an actuator library the applied / command histories [steps][B][3] (record=True; they join the records as "applied"
+        and "command"); call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
         ((state, control, t[, other]), the records as fp64 / int32 numpy arrays or None, (measured history,) or ())."""
         assert human in self.HUMAN_MODES, human
         hu = None; hist = {}
@@ -402,29 +461,35 @@ class BatchedTrajectoryTrackingMPC:
             if int_record:
                 hist[int_record] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
         mbuf = self._measured_hist(measured, steps)
+        abuf = self._actuator_hists(record, steps)
         call(lambda t: C.c_void_p(t.data_ptr()) if t is not None else None, hu, hist)
         s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
         if other:
             self._chk(self.lib.pg_get_safety_state(self.h, _p(o), None, None, None), "pg_get_safety_state")
         out = {k: v.cpu().numpy().astype(np.float64 if k in shapes else np.int32) for k, v in hist.items()} if record else None
+        for k, v in abuf.items():
+            out[k] = v.cpu().numpy().astype(np.float64)
         return (s, c, t, o) if other else (s, c, t), out, () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
 
     def simulate_(self, steps, dt=0.01, record=False, measured=False):
         """simulate (model_predictive_control.jl:80-100) on the device from the inputs last installed; returns (state, control, t) after `steps`
         steps and, with record=True, the histories qs [steps][B][6], us [steps][B][3] (the values pushed at :88-89).  measured=True (a sensor library is installed)
-        appends the measured history [steps][B][6] to what is returned."""
+        appends the measured history [steps][B][6] to what is returned.  Under an actuator library `us` is the APPLIED control, and record=True appends
+        {"command": [steps][B][3], "applied": [steps][B][3]} as the last element."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_dev(self.h, steps, C.c_double(dt), ptr(hist.get("state")), ptr(hist.get("control"))), "pg_simulate_dev")
         st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,)}, None, call, other=False)
-        return st + ((out["state"], out["control"]) if record else (None, None)) + tail
+        act = ({k: out[k] for k in ("command", "applied")},) if record and "applied" in out else ()
+        return st + ((out["state"], out["control"]) if record else (None, None)) + tail + act
 
     def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False, measured=False):
         """Safety rollout (pg_simulate_safety_dev): simulate with the control the ROS node sends (ros_integration.jl:114-124) fed back, against an other car that moves.
         human: "hold" (omega, a) = (0, 0), "worst" optimal_disturbance (HJI_computation.jl:90-131), "script" human_u [steps][B][2] = (omega, a).  Returns (state, control, t,
         other) after `steps` steps and, with record=True, a dict of histories: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B],
         source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step.
-        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned."""
+        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned.  Under an actuator library "control" is the APPLIED
+        control and the dict also holds "command" and "applied" [steps][B][3]."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
                                                       *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")

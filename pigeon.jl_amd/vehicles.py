@@ -60,3 +60,17 @@ def DecoupledControlParams(**kw):
             raise KeyError(k)
         p[k] = v
     return p
+
+
+ACTUATOR_FIELDS = ("delay_steps", "tau_delta", "tau_fx", "rate_delta", "rate_fx", "feedback")
+
+
+def actuator(**overrides):
+    """One actuator set for set_actuators (pg_actuator_set).  actuator() is the identity -- no delay, no lag, no slew limit, the controller sees the command it sent --, which
+    reproduces the handle without a library bit for bit; actuator(delay_steps=3, tau_delta=0.1, feedback=1) overrides fields.  Build-defined: the reference has no actuator."""
+    a = dict(delay_steps=0, tau_delta=0.0, tau_fx=0.0, rate_delta=math.inf, rate_fx=math.inf, feedback=0)
+    for k, v in overrides.items():
+        if k not in a:
+            raise KeyError(f"{k} is not a field of an actuator set: {ACTUATOR_FIELDS}")
+        a[k] = v
+    return a
