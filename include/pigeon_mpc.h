@@ -294,6 +294,59 @@ int pg_get_actuator_state(pg_handle* h, double* applied);
  * state (scratch of its own).  steps >= 1, dt > 0; PG_ERR_STATE without inputs, without a library or with an index that does not cover the batch */
 int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* commands, double* applied);
 
+/* Disturbance sets: what acts on the car FROM OUTSIDE in a rollout step, per instance -- a side wind, a headwind or grade force, a seeded gust, a low-friction window in the
+ * middle of a corner -- tuning x plant x sensor x actuator x disturbance studies as ONE batch.  A library of pg_disturbance, a per-instance selection, a seed and 64-bit
+ * stream ids, shaped like pg_set_sensor_sets.  BUILD-DEFINED: the reference has no counterpart.  Its `simulate` integrates the nominal model
+ * (src/model_predictive_control.jl:94) and the tube's theta, phi are carried and read by nothing.
+ * With a library installed the EGO plant of a step of pg_simulate_dev, pg_simulate_safety_dev and pg_simulate_node_dev integrates the body model plus
+ * w_k = (wFx, wFy, wMz, wmu), held for the step.  Per instance at clock step k (the step index of first_breach, first_exit and the sensor draws):
+ *   (z_x, z_y) = Box-Muller of words (x0, x1) of Philox4x32-10 block j = 2: counter (k, 2, stream_lo, stream_hi), key = the DISTURBANCE library's own seed; u and the
+ *                Box-Muller construction as for the sensor draws (blocks 0 and 1 belong to them; words x2, x3 of block 2 are reserved).  stream[b] defaults to b.
+ *   n_k        = z_k                                                                    when there is no state of step k - 1, or tau_gust == 0
+ *              = rho n_{k-1} + sqrt(-expm1(-2 dt / tau_gust)) z_k,  rho = exp(-dt / tau_gust)      otherwise, per component, in the library's element type, every product
+ *                and sum rounded once.  Both forms are stationary with unit variance.  The state advances at EVERY step under a library, inside the window or not.
+ *                "No state of step k - 1": the clock's first step (pg_set_inputs*, another dt, another path end restart it, as they restart the actuator state) and the
+ *                first step after a library was installed on a handle that had none (pg_clear_disturbance_sets drops the state).  Installing sets, an index, a seed or
+ *                streams over an installed library resets nothing.
+ *   active     = step_on <= k and (step_off < 0 or k < step_off)
+ *   w_k        = (0, 0, 0, 1)                                                           when not active
+ *              = (Fx + sigma_Fx n_x,  Fy + g_y,  Mz + x_cp g_y,  mu_scale),  g_y = sigma_Fy n_y     when active.  A sigma of exactly 0 contributes nothing: no multiply
+ *                and no add (the component is the constant itself).
+ * The plant of step k integrates, in EVERY RK4 sub-step, dUx += wFx / m, dUy += wFy / m, dr += wMz / Izz on top of the body model, whose tire model uses mu * wmu.
+ * m, Izz and mu are those of the plant's own vehicle: the instance's plant set under a plant library, else pg_config.vehicle.
+ * ZERO RULE: a component of w that is exactly 0 is not added and wmu == 1 is not multiplied, so the identity set {0, -1, 0, 0, 0, 0, 0, 0, 0, 1} and any set outside its
+ * window reproduce the handle without a library bit for bit.
+ * The CONTROLLER never sees w: nodes, linearisation, QP, HJI dynamics and policy keep pg_config.vehicle and no force.  The other car is not disturbed.  pg_step*, the phase
+ * calls and pg_node_step_dev ignore the library.
+ * Lifetime, index rule and errors as pg_set_plant_sets.  PG_ERR_INVALID (the handle is left unchanged; the message names the field and the set): a non-finite field;
+ * sigma_Fx / sigma_Fy < 0; tau_gust < 0; mu_scale <= 0; step_on < 0.
+ * Cost: one lane-per-instance launch (k_disturb) at the top of the step, and the step's plant kernel is the *_dist twin of the *_plant one.  Without a library: nothing
+ * allocated, the launches of before. */
+typedef struct pg_disturbance {
+    int32_t step_on, step_off;     /* active at clock steps k with step_on <= k and (step_off < 0 or k < step_off) */
+    double  Fx, Fy, Mz;            /* body-frame force at the CG (N), yaw moment (N m), constant while active */
+    double  sigma_Fx, sigma_Fy;    /* stationary standard deviation of the gust force (N) */
+    double  x_cp;                  /* the gust's Fy acts x_cp metres ahead of the CG: gust moment = x_cp * gust Fy */
+    double  tau_gust;              /* correlation time of the gust (s); 0 = white */
+    double  mu_scale;              /* the plant's mu is multiplied by this while active */
+} pg_disturbance;                  /* 72 bytes */
+int pg_set_disturbance_sets(pg_handle* h, int32_t n_sets, const pg_disturbance* sets);
+int pg_set_disturbance_index(pg_handle* h, int32_t B, const int32_t* index);     /* index[b] in [0, n_sets) */
+/* key of the draws and stream[b] for b < B (NULL: stream[b] = b; instances beyond B: b), as pg_set_sensor_seed.  Both persist across pg_clear_disturbance_sets and a later install */
+int pg_set_disturbance_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream);
+int pg_clear_disturbance_sets(pg_handle* h);                                     /* back to the undisturbed plant */
+/* the installed library, as pg_get_plant_sets */
+int pg_get_disturbance_sets(pg_handle* h, int32_t* n_sets, pg_disturbance* out, int32_t max_sets, int32_t* index, int32_t B);
+/* the law alone, ON THE DEVICE through the function k_disturb calls (k_disturbance_response): w_out [steps][B][4] on the host = w of the clock steps [step0, step0 + steps)
+ * with the installed library, index, seed and streams over the current batch B (pg_set_inputs*), from a FRESH gust state at step0.  Touches neither the rollout clock nor
+ * the handle's gust state.  step0 >= 0, steps >= 1, dt > 0; PG_ERR_STATE without inputs, without a library or with an index that does not cover the batch */
+int pg_disturbance_response(pg_handle* h, int32_t step0, int32_t steps, double dt, double* w_out);
+/* w [B][4] of the last rollout step under a library; PG_ERR_STATE before the first one since the inputs were installed */
+int pg_get_disturbance_state(pg_handle* h, double* w);
+/* the NEXT rollout call writes w of its step k < steps to buf[k][B][4] (library element type); one-shot -- that call consumes the registration whether it succeeds or
+ * returns an error --; NULL cancels.  PG_ERR_STATE without a library */
+int pg_set_disturbance_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -471,6 +524,7 @@ int pg_synchronize(pg_handle* h);
  *     "graph" 0/1 (0)            pg_step of a small warm batch as one hipGraph launch (see pg_step)
  *     "stat_sensor_steps"        (read-only) rollout steps that ran under a sensor library (k_measure launches) since pg_create
  *     "stat_actuator_steps"      (read-only) rollout steps whose plant launch ran under an actuator library (k_actuate launches) since pg_create
+ *     "stat_disturbance_steps"   (read-only) rollout steps that ran under a disturbance library (k_disturb launches) since pg_create
  *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact

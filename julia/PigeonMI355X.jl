@@ -291,6 +291,66 @@ set_applied_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::
 set_command_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
     check(mpc, ccall(sym(mpc, :pg_set_command_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_command_history_dev")
 
+# Disturbance sets (pg_set_disturbance_sets ...): forces, a seeded gust and low-friction windows on the ego plant of the rollouts.  NOT EXECUTED in the build container, like the rest of this file.
+
+"One disturbance (pg_disturbance): the window in clock steps (step_on <= k, and k < step_off unless step_off < 0), the constant body-frame force (N) and yaw moment (N m), the gust's standard deviations (N), the lever arm of its side force (m), its correlation time (s; 0 = white) and the factor on the plant's mu while active.  PgDisturbance() is the identity: the handle without a library, bit for bit."
+struct PgDisturbance
+    step_on::Int32
+    step_off::Int32
+    Fx::Float64
+    Fy::Float64
+    Mz::Float64
+    sigma_Fx::Float64
+    sigma_Fy::Float64
+    x_cp::Float64
+    tau_gust::Float64
+    mu_scale::Float64
+end
+PgDisturbance(; step_on=0, step_off=-1, Fx=0.0, Fy=0.0, Mz=0.0, sigma_Fx=0.0, sigma_Fy=0.0, x_cp=0.0, tau_gust=0.0, mu_scale=1.0) =
+    PgDisturbance(Int32(step_on), Int32(step_off), Float64(Fx), Float64(Fy), Float64(Mz), Float64(sigma_Fx), Float64(sigma_Fy), Float64(x_cp), Float64(tau_gust), Float64(mu_scale))
+"the layout include/pigeon_mpc.h states (72 bytes): checked before the first install"
+function check_disturbance_layout()
+    off(f) = Int(fieldoffset(PgDisturbance, Base.fieldindex(PgDisturbance, f)))
+    (sizeof(PgDisturbance), off(:step_on), off(:step_off), off(:Fx), off(:Fy), off(:Mz), off(:sigma_Fx), off(:sigma_Fy), off(:x_cp), off(:tau_gust), off(:mu_scale)) ==
+        (72, 0, 4, 8, 16, 24, 32, 40, 48, 56, 64) || error("PigeonMI355X.jl: PgDisturbance differs from pg_disturbance of include/pigeon_mpc.h")
+end
+"What acts on the ego PLANT of the three rollouts from outside: a library of disturbances and the set each instance runs under (0-based; may be empty for a library of one).  The controller never sees it.  Resets nothing."
+function set_disturbances!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgDisturbance}, index::Vector{Int32}=Int32[])
+    check_disturbance_layout()
+    check(mpc, ccall(sym(mpc, :pg_set_disturbance_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgDisturbance}), mpc.handle, length(sets), sets), "pg_set_disturbance_sets")
+    isempty(index) || check(mpc, ccall(sym(mpc, :pg_set_disturbance_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_disturbance_index")
+    nothing
+end
+"Key of the gust's draws and the 64-bit stream id of every instance (empty: stream[b] = b); both persist across a clear"
+function set_disturbance_seed!(mpc::BatchedTrajectoryTrackingMPC, seed::UInt64, streams::Vector{UInt64}=UInt64[])
+    check(mpc, ccall(sym(mpc, :pg_set_disturbance_seed), Cint, (Ptr{Cvoid}, UInt64, Int32, Ptr{UInt64}), mpc.handle, seed, isempty(streams) ? mpc.B : length(streams),
+                     isempty(streams) ? C_NULL : pointer(streams)), "pg_set_disturbance_seed")
+end
+clear_disturbances!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_disturbance_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_disturbance_sets")
+"(sets, index over B instances; -1 where no index covers an instance) as installed"
+function disturbances(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_disturbance_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgDisturbance}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_disturbance_sets")
+    sets = Vector{PgDisturbance}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_disturbance_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgDisturbance}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_disturbance_sets")
+    sets, index
+end
+"The law alone, on the device: w 4 x B x steps = (wFx, wFy, wMz, wmu) of the clock steps step0 .. step0 + steps - 1 under the installed library, index, seed and streams, from a fresh gust state"
+function disturbance_response(mpc::BatchedTrajectoryTrackingMPC, step0::Integer, steps::Integer, dt::Float64)
+    w = zeros(4, mpc.B, steps)
+    check(mpc, ccall(sym(mpc, :pg_disturbance_response), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}), mpc.handle, step0, steps, dt, w), "pg_disturbance_response")
+    w
+end
+"4 x B: w of the last rollout step under a disturbance library"
+function disturbance_state(mpc::BatchedTrajectoryTrackingMPC)
+    w = zeros(4, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_disturbance_state), Cint, (Ptr{Cvoid}, Ptr{Float64}), mpc.handle, w), "pg_get_disturbance_state")
+    w
+end
+"The NEXT rollout call writes w of its step k < steps to a device array 4 x B x steps of the library's element type (one-shot; C_NULL cancels)"
+set_disturbance_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_disturbance_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_disturbance_history_dev")
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

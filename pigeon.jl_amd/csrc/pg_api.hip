@@ -74,6 +74,17 @@ struct pg_handle {
     bool act_fresh = true;                                        // the actuator state restarts at the next step under a library (the clock restarted, or no step ran under one since)
     real *applied_hist = nullptr, *command_hist = nullptr; int applied_hist_steps = 0, command_hist_steps = 0;      // pg_set_applied_history_dev / pg_set_command_history_dev: one-shot
     int64_t stat_actuator_steps = 0;                              // read-only option "stat_actuator_steps"
+    // disturbance library (pg_set_disturbance_sets / pg_set_disturbance_index / pg_set_disturbance_seed): what acts on the ego plant of a rollout step from outside.  Beside
+    // the sets: the stream ids [cap] and the seed (as the sensor library keeps its own), and, allocated when a rollout first runs under a library: the gust state
+    // d_dist_n [cap][2], this step's w d_dist_w [cap][4] (k_disturb writes it, the *_dist plant kernel reads it) and d_dist_veh, ONE record holding the handle's own vehicle:
+    // the library of one the *_dist kernels are handed when no plant library is installed
+    SetLib<pg_disturbance, DevDisturbance> dists{{"disturbance", "pg_set_disturbance_index"}};
+    unsigned long long* d_dist_stream = nullptr; bool dist_stream_dirty = true; std::vector<uint64_t> dist_stream; uint64_t dist_seed = 0;
+    real *d_dist_n = nullptr, *d_dist_w = nullptr; DevVehicle* d_dist_veh = nullptr;
+    bool dist_fresh = true;                                       // no gust state of the previous step exists (the clock restarted, or no step ran under a library since one was installed)
+    bool dist_valid = false;                                      // d_dist_w holds w of a rollout step since the inputs were installed
+    real* dist_hist = nullptr; int dist_hist_steps = 0;           // pg_set_disturbance_history_dev: one-shot, consumed by the next rollout call
+    int64_t stat_disturbance_steps = 0;                           // read-only option "stat_disturbance_steps"
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -326,9 +337,9 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen, h->d_dist_stream, h->d_dist_n, h->d_dist_w, h->d_dist_veh};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release();
+    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release(); h->dists.release();
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
     if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
@@ -547,6 +558,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "stat_pipelined_launches") return S(&h->stat_pipelined);
     if (n == "stat_sensor_steps") return S(&h->stat_sensor_steps);
     if (n == "stat_actuator_steps") return S(&h->stat_actuator_steps);
+    if (n == "stat_disturbance_steps") return S(&h->stat_disturbance_steps);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -625,7 +637,7 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
 }
 int pg_synchronize(pg_handle* h) { if (!h) return PG_ERR_INVALID; HIPCHK(h, hipStreamSynchronize(h->stream)); return PG_OK; }
 
-// ---- what the five libraries share (trajectories, control parameters, plants, sensors, actuators): one index rule and one install / clear / get protocol ----
+// ---- what the six libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances): one index rule and one install / clear / get protocol ----
 // Installs the selection of `B` instances into a library of `n_sets`.  The WHOLE [capacity] array is written, entries beyond B as 0: never an address outside the library,
 // whatever an earlier, larger library left there
 static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, const int32_t* index) {
@@ -867,18 +879,19 @@ int pg_get_sensor_sets(pg_handle* h, int32_t* n_sets, pg_sensor* out, int32_t ma
     if (!h) return PG_ERR_INVALID;
     return setlib_get(h, "pg_get_sensor_sets", h->sens, n_sets, out, max_sets, index, B);
 }
-// the stream ids on the device, [capacity]: the installed ones, then stream[b] = b
-static int sensor_streams_sync(pg_handle* h) {
-    if (h->d_sens_stream && !h->sens_stream_dirty) return PG_OK;
+// the stream ids of a seeded library on the device, [capacity]: the installed ones, then stream[b] = b
+static int streams_sync(pg_handle* h, unsigned long long*& d, bool& dirty, const std::vector<uint64_t>& installed) {
+    if (d && !dirty) return PG_OK;
     const size_t cap = (size_t)h->cfg.batch_capacity;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->d_sens_stream) HIPCHK(h, hipMalloc((void**)&h->d_sens_stream, cap * sizeof(unsigned long long)));
+    if (!d) HIPCHK(h, hipMalloc((void**)&d, cap * sizeof(unsigned long long)));
     std::vector<unsigned long long> full(cap);
-    for (size_t b = 0; b < cap; b++) full[b] = b < h->sens_stream.size() ? (unsigned long long)h->sens_stream[b] : (unsigned long long)b;
-    HIPCHK(h, hipMemcpy(h->d_sens_stream, full.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    h->sens_stream_dirty = false;
+    for (size_t b = 0; b < cap; b++) full[b] = b < installed.size() ? (unsigned long long)installed[b] : (unsigned long long)b;
+    HIPCHK(h, hipMemcpy(d, full.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    dirty = false;
     return PG_OK;
 }
+static int sensor_streams_sync(pg_handle* h) { return streams_sync(h, h->d_sens_stream, h->sens_stream_dirty, h->sens_stream); }
 int pg_sensor_draws(pg_handle* h, int32_t step0, int32_t steps, int32_t B, double* z) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, step0 >= 0 && steps >= 1 && z, "pg_sensor_draws: need step0 >= 0, steps >= 1 and the output array");
@@ -998,6 +1011,91 @@ int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* c
     return rc;
 }
 
+// ---- disturbance library: what acts on the EGO PLANT of a rollout step from outside, w = (wFx, wFy, wMz, wmu) per instance (k_disturb; the *_dist plant kernels).
+// Build-defined (the reference integrates the nominal model, model_predictive_control.jl:94).  No part of any QP and invisible to the controller: nothing is reset ----
+static const char* disturbance_field_problem(const pg_disturbance& s) {
+    const struct { const char* name; double v; } f[8] = {{"Fx", s.Fx}, {"Fy", s.Fy}, {"Mz", s.Mz}, {"sigma_Fx", s.sigma_Fx}, {"sigma_Fy", s.sigma_Fy}, {"x_cp", s.x_cp},
+                                                         {"tau_gust", s.tau_gust}, {"mu_scale", s.mu_scale}};
+    static thread_local std::string msg;
+    for (const auto& x : f) if (!std::isfinite(x.v)) { msg = std::string(x.name) + " is not finite"; return msg.c_str(); }
+    if (s.sigma_Fx < 0.0) return "sigma_Fx must be >= 0";
+    if (s.sigma_Fy < 0.0) return "sigma_Fy must be >= 0";
+    if (s.tau_gust < 0.0) return "tau_gust must be >= 0";
+    if (!(s.mu_scale > 0.0)) return "mu_scale must be > 0";
+    if (s.step_on < 0) return "step_on must be >= 0";
+    return nullptr;
+}
+static void fill_dev_disturbance(DevDisturbance& D, const pg_disturbance& s) {
+    D.step_on = s.step_on; D.step_off = s.step_off; D.Fx = (real)s.Fx; D.Fy = (real)s.Fy; D.Mz = (real)s.Mz; D.sigma_Fx = (real)s.sigma_Fx; D.sigma_Fy = (real)s.sigma_Fy;
+    D.x_cp = (real)s.x_cp; D.tau_gust = (real)s.tau_gust; D.mu_scale = (real)s.mu_scale;
+}
+int pg_set_disturbance_sets(pg_handle* h, int32_t n_sets, const pg_disturbance* sets) {
+    if (!h) return PG_ERR_INVALID;
+    std::string why;                                            // (the message names the field and the set; seed, streams and the gust state persist)
+    return setlib_install(h, "pg_set_disturbance_sets", h->dists, n_sets, sets, [&](const pg_disturbance& s) -> const char* {
+        const char* f = disturbance_field_problem(s);
+        if (!f) return nullptr;
+        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
+        return why.c_str();
+    }, fill_dev_disturbance);
+}
+int pg_set_disturbance_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    return index_install(h, (int)h->dists.sets.size(), h->dists.idx, B, index);
+}
+int pg_set_disturbance_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_set_disturbance_seed: need 1 <= B <= batch_capacity");
+    h->dist_seed = seed;                                        // (a launch argument: a rollout already queued keeps the seed it was launched with)
+    if (stream) h->dist_stream.assign(stream, stream + B); else h->dist_stream.clear();      // instances the array does not cover: stream[b] = b
+    h->dist_stream_dirty = true;
+    return PG_OK;
+}
+int pg_clear_disturbance_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    const int rc = setlib_clear(h, h->dists); if (rc) return rc;
+    h->dist_fresh = true; h->dist_valid = false; h->dist_hist = nullptr; h->dist_hist_steps = 0;      // (a library installed later starts a gust of its own)
+    return PG_OK;
+}
+int pg_get_disturbance_sets(pg_handle* h, int32_t* n_sets, pg_disturbance* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    return setlib_get(h, "pg_get_disturbance_sets", h->dists, n_sets, out, max_sets, index, B);
+}
+int pg_set_disturbance_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
+    if (!h) return PG_ERR_INVALID;
+    if (!buf) { h->dist_hist = nullptr; h->dist_hist_steps = 0; return PG_OK; }
+    REQUIRE(h, steps >= 1, "pg_set_disturbance_history_dev: steps >= 1 required");
+    if (h->dists.sets.empty()) { h->err = "pg_set_disturbance_history_dev: no disturbance library installed (w = (0, 0, 0, 1) at every step)"; return PG_ERR_STATE; }
+    h->dist_hist = (real*)buf; h->dist_hist_steps = steps;
+    return PG_OK;
+}
+int pg_get_disturbance_state(pg_handle* h, double* w) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->dists.sets.empty() || !h->dist_valid || !h->d_dist_w) { h->err = "pg_get_disturbance_state: no rollout step under a disturbance library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, w, h->d_dist_w, (size_t)h->B * 4);
+}
+int pg_disturbance_response(pg_handle* h, int32_t step0, int32_t steps, double dt, double* w_out) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, step0 >= 0 && steps >= 1 && dt > 0.0 && w_out, "pg_disturbance_response: step0 >= 0, steps >= 1, dt > 0 and the output array required");
+    if (h->B <= 0) { h->err = "pg_disturbance_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
+    if (h->dists.sets.empty()) { h->err = "pg_disturbance_response: no disturbance library installed"; return PG_ERR_STATE; }
+    if (index_covers(h, h->dists.sets.size(), h->dists.idx)) return PG_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = streams_sync(h, h->d_dist_stream, h->dist_stream_dirty, h->dist_stream); if (rc) return rc;
+    const int B = h->B;
+    const size_t n = (size_t)steps * (size_t)B * 4;
+    real* d = nullptr;                                           // scratch of the call (the gust state lives in the lanes' registers)
+    HIPCHK(h, hipMalloc((void**)&d, n * sizeof(real)));
+    hipLaunchKernelGGL(k_disturbance_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, (int)step0, (int)steps, (real)dt, h->dists.d,
+                       h->dists.sets.size() > 1 ? h->dists.idx.d : (const int*)nullptr, h->d_dist_stream, (unsigned long long)h->dist_seed, d);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { h->err = std::string("pg_disturbance_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
+    if (!rc) rc = down(h, w_out, d, n);
+    else (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -1069,7 +1167,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true; h->dist_fresh = true; h->dist_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1608,6 +1706,32 @@ static int rollout_ready(pg_handle* h) {
         if (!h->d_plant_u) HIPCHK(h, hipMalloc((void**)&h->d_plant_u, cap * 3 * sizeof(real)));
         if (h->act_feedback && !h->d_seen) HIPCHK(h, hipMalloc((void**)&h->d_seen, cap * 3 * sizeof(real)));
     }
+    if (!h->dists.sets.empty()) {
+        if (index_covers(h, h->dists.sets.size(), h->dists.idx)) return PG_ERR_STATE;
+        const size_t cap = cap_of(h);
+        if (!h->d_dist_n) HIPCHK(h, hipMalloc((void**)&h->d_dist_n, cap * 2 * sizeof(real)));
+        if (!h->d_dist_w) HIPCHK(h, hipMalloc((void**)&h->d_dist_w, cap * 4 * sizeof(real)));
+        if (!h->d_dist_veh) {                                    // (the controller's vehicle as the kernels hold it: DevCfg's record, bit for bit)
+            HIPCHK(h, hipMalloc((void**)&h->d_dist_veh, sizeof(DevVehicle)));
+            HIPCHK(h, hipMemcpy(h->d_dist_veh, &h->dc.veh, sizeof(DevVehicle), hipMemcpyHostToDevice));
+        }
+        const int rc = streams_sync(h, h->d_dist_stream, h->dist_stream_dirty, h->dist_stream); if (rc) return rc;
+    }
+    return PG_OK;
+}
+// the disturbance library (the host knows whether one is installed: that alone adds k_disturb to a rollout step and picks the *_dist plant kernel).
+// disturbance_take_history: the one-shot registration of pg_set_disturbance_history_dev, consumed by the rollout call that starts now
+static bool disturbance_lib_on(const pg_handle* h) { return !h->dists.sets.empty(); }
+struct DistHist { real* buf; int steps; };
+static DistHist disturbance_take_history(pg_handle* h) { const DistHist d{h->dist_hist, h->dist_hist_steps}; h->dist_hist = nullptr; h->dist_hist_steps = 0; return d; }
+// the top of a rollout step under a library: w of clock step `step` into d_dist_w, the gust state advanced (fresh: the host knows that no state of step - 1 exists)
+static int launch_disturb(pg_handle* h, int step, int k, double dt, const DistHist& dh) {
+    const int B = h->B;
+    const DisturbanceLib lib{h->dists.d, h->dists.sets.size() > 1 ? h->dists.idx.d : (const int*)nullptr, h->d_dist_stream, (unsigned long long)h->dist_seed, h->d_dist_n, h->d_dist_w};
+    hipLaunchKernelGGL(k_disturb, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, (int)h->dist_fresh, (real)dt, lib,
+                       (dh.buf && k < dh.steps) ? dh.buf + (size_t)k * B * 4 : (real*)nullptr);
+    LAUNCH_CHECK(h);
+    h->dist_fresh = false; h->dist_valid = true; h->stat_disturbance_steps++;
     return PG_OK;
 }
 // the actuator library (the host knows whether one is installed: that alone adds k_actuate and the copy-back to a rollout step).  actuator_take_history: the one-shot
@@ -1677,20 +1801,22 @@ static int launch_track(pg_handle* h, int step) {
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true; h->dist_fresh = true;
     }
     return PG_OK;
 }
 static int node_start(pg_handle* h, double dt);
 }  // extern "C" (the rollouts' templates have C++ linkage)
-// the last launch of a rollout step, one lane per instance: `uniform`, or under a plant library `with_plant` -- the same arguments and the library behind them
-template <class K, class KP, class... A>
-static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, const A&... args) {
+// the last launch of a rollout step, one lane per instance: `uniform`, or under a plant library `with_plant` -- the same arguments and the library behind them --, or
+// under a disturbance library `with_dist`: the plant library (without one: the library of one made of the handle's own vehicle) and w of this step behind them
+template <class K, class KP, class KD, class... A>
+static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_dist, const A&... args) {
     const dim3 grid((h->B + 63) / 64), block(64);
-    if (plant_lib_on(h)) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
+    if (disturbance_lib_on(h)) hipLaunchKernelGGL(with_dist, grid, block, 0, h->stream, args..., plant_lib_on(h) ? plant_lib(h) : PlantLib{h->d_dist_veh, nullptr}, (const real*)h->d_dist_w);
+    else if (plant_lib_on(h)) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
     else hipLaunchKernelGGL(uniform, grid, block, 0, h->stream, args...);
 }
-// The rollouts' shared driver.  Prologue, in this order: the one-shot measured-history registration is taken (THIS call consumes it, also when it fails below), check_ready,
+// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance) are taken (THIS call consumes them, also when it fails below), check_ready,
 // the entry point's own precondition (coupled_only: the message for a lateral handle, nullptr: none), the shared arguments, rollout_ready, the node's buffers (node: the
 // rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records(k) ahead of the compute calls, the
 // controller's side (:90-93, on the measured state under a sensor library), the tracking summary, the clock index, then finish(k, step): the step's last launch, which moves
@@ -1702,6 +1828,7 @@ template <class Records, class Finish>
 static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish finish) {
     const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};
     const ActHist ah = h ? actuator_take_history(h) : ActHist{nullptr, nullptr, 0, 0};
+    const DistHist dh = h ? disturbance_take_history(h) : DistHist{nullptr, 0};
     int rc = check_ready(h); if (rc) return rc;
     if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
     if (a.node && actuator_lib_on(h)) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
@@ -1709,11 +1836,12 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
     // Under an actuator library the handle's control pointer names, while the launches are QUEUED: d_plant_u (= a_k) for the records and the plant launch, d_seen for the
     // compute calls when some set has feedback == 1 -- k_nodes*, the QP's u_curr and the steering-rate rows all take the pointer from the handle --, and its own allocation
     // (the command) everywhere else and whenever this function returns.  The plant kernel leaves the next command in d_plant_u: one copy moves it to the control buffer
-    const bool act = actuator_lib_on(h);
+    const bool act = actuator_lib_on(h), dist = disturbance_lib_on(h);
     real* const command = h->d_control;
     for (int k = 0; k < a.steps; k++) {
         const int step = h->sim_idx - 1;
         if (act && (rc = launch_actuate(h, step, k, a.dt, ah))) return rc;
+        if (dist && (rc = launch_disturb(h, step, k, a.dt, dh))) return rc;      // (w of this step: read by the step's last launch only)
         if (act) h->d_control = h->d_plant_u;
         rc = records(k);
         if (act) h->d_control = h->act_feedback ? h->d_seen : command;
@@ -1744,7 +1872,7 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
             if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)control_hist_dev, k, B, 3), h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));  // push!(us, control) :89
             return PG_OK;
         },
-        [&](int, int) { launch_plant_step(h, k_advance, k_advance_plant, h->dc, h->B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
+        [&](int, int) { launch_plant_step(h, k_advance, k_advance_plant, k_advance_dist, h->dc, h->B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
 }
 // simulate (:80-100) with the control the ROS node sends (ros_integration.jl:114-124) fed back and the other car moving (k_advance_safety, pg_kernels.hip).  Per step: the four
 // compute calls exactly as pg_simulate_dev makes them (fusion, pipelining and the split solve unchanged; with a grid they leave the step's relative state d_x7 and its
@@ -1759,7 +1887,7 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
             SafetyIO io{human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr, hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
                         hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
                         h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-            launch_plant_step(h, k_advance_safety, k_advance_safety_plant, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji, (int)h->sum_fresh, step,
+            launch_plant_step(h, k_advance_safety, k_advance_safety_plant, k_advance_safety_dist, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji, (int)h->sum_fresh, step,
                               h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
             h->sum_fresh = false;
         });
@@ -1876,7 +2004,7 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
             io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
             io.event_h = hist_at(event_hist_dev, k, B, 1);
             io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-            launch_plant_step(h, k_node_finish<true>, k_node_finish_plant, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+            launch_plant_step(h, k_node_finish<true>, k_node_finish_plant, k_node_finish_dist, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
                               (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
                               h->sim_idx, h->kv, io);
             h->sum_fresh = false;

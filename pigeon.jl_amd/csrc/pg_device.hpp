@@ -738,4 +738,38 @@ PG_DEV void actuator_advance(const DevActuator& A, real dt, int step, bool resta
     actuator_step(A, dt, g, a);
 }
 
+// ---- disturbance of the rollouts (pg_set_disturbance_sets; build-defined: the reference's `simulate` integrates the nominal model, model_predictive_control.jl:94, and the
+// tube's theta, phi are read by nothing) ----
+// one set of a disturbance library in the arithmetic type of the build: the window in clock steps, the constant body-frame force and yaw moment, the gust's standard
+// deviations, its lever arm and correlation time, and the factor on the plant's mu
+struct DevDisturbance { int step_on, step_off; real Fx, Fy, Mz, sigma_Fx, sigma_Fy, x_cp, tau_gust, mu_scale; };
+PG_DEV float pg_exp(float x) { return expf(x); }
+PG_DEV double pg_exp(double x) { return exp(x); }
+// The law for one instance and one clock step.  (z_x, z_y) = Box-Muller of words (x0, x1) of Philox block j = 2 on (seed; step, 2, stream) -- blocks 0 and 1 are the
+// sensor's (sensor_draws), words x2, x3 of block 2 are reserved.  n (in: n_{k-1}, out: n_k) is the normalised gust state:
+//   n_k = z_k                                                       when `fresh` (no state of step k - 1) or tau_gust == 0
+//   n_k = rho n_{k-1} + sqrt(-expm1(-2 dt / tau_gust)) z_k,  rho = exp(-dt / tau_gust)     otherwise  (both stationary with unit variance)
+// It advances whether the window is open or not.  w = (wFx, wFy, wMz, wmu):
+//   outside the window (0, 0, 0, 1);  inside (Fx + sigma_Fx n_x, Fy + g_y, Mz + x_cp g_y, mu_scale) with g_y = sigma_Fy n_y
+// A sigma of 0 contributes nothing (no multiply, no add).  No contraction: every product and sum is rounded once, as the numpy twin rounds it
+PG_DEV void disturbance_advance(const DevDisturbance& D, uint64_t seed, uint64_t stream, uint32_t step, bool fresh, real dt, real n[2], real w[4]) {
+#pragma clang fp contract(off)
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const uint32_t ctr[4] = {step, 2u, (uint32_t)stream, (uint32_t)(stream >> 32)};
+    uint32_t x[4];
+    philox4x32_10(ctr, key, x);
+    real z[2]; box_muller(x[0], x[1], z[0], z[1]);
+    if (fresh || D.tau_gust == real(0.0)) { n[0] = z[0]; n[1] = z[1]; }
+    else {
+        const real rho = pg_exp(-dt / D.tau_gust), g = sqrt(-pg_expm1(real(-2.0) * dt / D.tau_gust));
+        n[0] = rho * n[0] + g * z[0]; n[1] = rho * n[1] + g * z[1];
+    }
+    const bool active = (int)step >= D.step_on && (D.step_off < 0 || (int)step < D.step_off);
+    if (!active) { w[0] = real(0.0); w[1] = real(0.0); w[2] = real(0.0); w[3] = real(1.0); return; }
+    w[0] = D.sigma_Fx == real(0.0) ? D.Fx : D.Fx + D.sigma_Fx * n[0];
+    w[1] = D.Fy; w[2] = D.Mz;
+    if (D.sigma_Fy != real(0.0)) { const real gy = D.sigma_Fy * n[1]; w[1] = D.Fy + gy; w[2] = D.Mz + D.x_cp * gy; }
+    w[3] = D.mu_scale;
+}
+
 }  // namespace pg

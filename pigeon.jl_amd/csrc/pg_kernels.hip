@@ -1014,6 +1014,56 @@ __global__ __launch_bounds__(64) void k_advance_plant(DevCfg C, int B, tdouble d
     u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
     clock_next(C, dtp, t0, t_start, clk, idx, b);
 }
+// Disturbance library (pg_set_disturbance_sets): the *_dist kernels are the *_plant kernels with w = (wFx, wFy, wMz, wmu) of the instance (k_disturb wrote it at the top of
+// the step) acting on the ego plant, held for the step: the tire model sees mu * wmu -- the lane scales P.mu in its register copy of the vehicle record -- and every RK4
+// sub-step adds wFx / m, wFy / m, wMz / Izz behind world_body_rhs.  ZERO RULE: a component that is exactly 0 is not added and wmu == 1 is not multiplied, so w = (0, 0, 0, 1)
+// leaves the statements of advance_ego_plant -- and a lane whose whole w is (0, 0, 0, 1) runs advance_ego_plant itself (advance_ego_under): the conditional adds alone
+// regrouped the fp64 FMAs of the right-hand side, and the identity set must give the bits of the handle without a library.  Launched only when a disturbance library is installed; without a plant library the host hands them a library of one made
+// of the handle's own vehicle (three kernels, not six).  advance_ego_plant's statement of the RK4, restated (see PlantLib above: no existing body is shared)
+PG_DEV void advance_ego_dist(DevVehicle P, const real* __restrict__ w, real* x, real d, real Fx, real h, int nsub) {
+    const real wFx = w[0], wFy = w[1], wMz = w[2], wmu = w[3];
+    if (wmu != real(1.0)) P.mu = P.mu * wmu;
+    const bool has_x = wFx != real(0.0), has_y = wFy != real(0.0), has_r = wMz != real(0.0);
+    const real ax = wFx / P.m, ay = wFy / P.m, ar = wMz / P.Izz;
+    auto rhs = [&](const real* y, real* o) {
+        real s, c; pg_sincos(y[2], &s, &c);
+        o[0] = -y[3] * s - y[4] * c; o[1] = y[3] * c - y[4] * s; o[2] = y[5];          // psi measured from North (:127-129)
+        world_body_rhs<real>(P, y[3], y[4], y[5], d, Fx, o[3], o[4], o[5]);
+        if (has_x) o[3] += ax;
+        if (has_y) o[4] += ay;
+        if (has_r) o[5] += ar;
+    };
+#pragma unroll 1
+    for (int i = 0; i < nsub; i++) {
+        real k1[6], k2[6], k3[6], k4[6], y[6];
+        rhs(x, k1);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k1[k] * (h * real(0.5));
+        rhs(y, k2);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k2[k] * (h * real(0.5));
+        rhs(y, k3);
+        for (int k = 0; k < 6; k++) y[k] = x[k] + k3[k] * h;
+        rhs(y, k4);
+        for (int k = 0; k < 6; k++) x[k] += (k1[k] + real(2.0) * k2[k] + real(2.0) * k3[k] + k4[k]) * (h / real(6.0));
+    }
+}
+PG_DEV void advance_ego_under(const DevVehicle& P, const real* __restrict__ w, real* x, real d, real Fx, real h, int nsub) {
+    if (w[0] == real(0.0) && w[1] == real(0.0) && w[2] == real(0.0) && w[3] == real(1.0)) advance_ego_plant(P, x, d, Fx, h, nsub);
+    else advance_ego_dist(P, w, x, d, Fx, h, nsub);
+}
+// ... k_advance_plant under a disturbance library: dist [B][4] = w of this step
+__global__ __launch_bounds__(64) void k_advance_dist(DevCfg C, int B, tdouble dtp, real* __restrict__ state, real* __restrict__ control, const real* __restrict__ u_next,
+                                                     tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, PlantLib lib, const real* __restrict__ dist) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevVehicle P = plant_of(lib, b);
+    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3;
+    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+    const int nsub = C.nsub; const real h = dtp / nsub;
+    advance_ego_under(P, dist + (size_t)b * 4, x, u[0], u[1] + u[2], h, nsub);
+    for (int k = 0; k < 6; k++) q[k] = x[k];
+    u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
+    clock_next(C, dtp, t0, t_start, clk, idx, b);
+}
 
 // Tracking summary (option "tracking_summary"; pg_get_tracking_state), lane = instance: one launch per rollout step, behind the step's projection (sep = (s, e, t, segment)
 // of the state the step records) and ahead of the kernel that moves the plant.  sum [B][6] = (max |e|, sum e^2, max |Uy / Ux|, max |r|, min Ux, s of the last step);
@@ -1129,6 +1179,39 @@ __global__ __launch_bounds__(64) void k_actuator_response(int B, int steps, real
         const real c[3] = {commands[at], commands[at + 1], commands[at + 2]};
         actuator_advance(A, dt, k, k == 0, b, B, ring, c, a);
         for (int j = 0; j < 3; j++) applied[at + j] = a[j];
+    }
+}
+
+// Disturbance library (pg_set_disturbance_sets), lane = instance: w = (wFx, wFy, wMz, wmu) the ego plant of this rollout step integrates (disturbance_advance,
+// pg_device.hpp).  Queued at the top of the step, next to k_actuate.  Reads the instance's record (copied into registers once), its stream id and, unless `fresh`, the
+// gust state n [cap][2]; writes n, w [cap][4] (what the *_dist plant kernel of the step reads) and the step's row of the history when one is registered.  The draw is a
+// function of (seed, stream id, clock step) alone, not of b or B.  idx == nullptr: a library of one.  `fresh`: no state of the previous step exists
+struct DisturbanceLib { const DevDisturbance* sets; const int* idx; const unsigned long long* stream; unsigned long long seed; real* n; real* w; };
+__global__ __launch_bounds__(64) void k_disturb(int B, int step, int fresh, real dt, DisturbanceLib lib, real* __restrict__ hist) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevDisturbance D = lib.sets[lib.idx ? lib.idx[b] : 0];
+    real n[2] = {real(0.0), real(0.0)}, w[4];
+    if (!fresh) { n[0] = lib.n[(size_t)b * 2]; n[1] = lib.n[(size_t)b * 2 + 1]; }
+    disturbance_advance(D, lib.seed, lib.stream[b], (uint32_t)step, fresh != 0, dt, n, w);
+    lib.n[(size_t)b * 2] = n[0]; lib.n[(size_t)b * 2 + 1] = n[1];
+    for (int j = 0; j < 4; j++) {
+        lib.w[(size_t)b * 4 + j] = w[j];
+        if (hist) hist[(size_t)b * 4 + j] = w[j];
+    }
+}
+// pg_disturbance_response: w [steps][B][4] of the clock steps [step0, step0 + steps) through the function k_disturb calls, from a fresh gust state at step0 kept in
+// registers (lane = instance; the steps in order)
+__global__ __launch_bounds__(64) void k_disturbance_response(int B, int step0, int steps, real dt, const DevDisturbance* __restrict__ sets, const int* __restrict__ idx,
+                                                             const unsigned long long* __restrict__ stream, unsigned long long seed, real* __restrict__ w_out) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevDisturbance D = sets[idx ? idx[b] : 0];
+    const unsigned long long id = stream[b];
+    real n[2] = {real(0.0), real(0.0)}, w[4];
+    for (int k = 0; k < steps; k++) {
+        disturbance_advance(D, seed, id, (uint32_t)step0 + (uint32_t)k, k == 0, dt, n, w);
+        for (int j = 0; j < 4; j++) w_out[((size_t)k * B + b) * 4 + j] = w[j];
     }
 }
 
@@ -1757,6 +1840,43 @@ __global__ __launch_bounds__(64) void k_advance_safety_plant(DevCfg C, int B, td
     if (io.src_h) io.src_h[b] = src;
     safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);
 }
+// ... under a disturbance library (advance_ego_dist above): k_advance_safety_plant with w of this step, dist [B][4], on the ego plant.  The other car is not disturbed
+PG_DEV void advance_plants_dist(const DevCfg& C, const DevVehicle& Pl, const real* __restrict__ w, tdouble dtp, real* x, real d, real Fx, real* __restrict__ q, real* oc, real ow, real oa,
+                                real* __restrict__ ot) {
+    const int nsub = C.nsub; const real h = dtp / nsub;
+    advance_ego_under(Pl, w, x, d, Fx, h, nsub);
+    advance_unicycle(oc, ow, oa, h, nsub);
+    for (int k = 0; k < 6; k++) q[k] = x[k];
+    for (int k = 0; k < 4; k++) ot[k] = oc[k];
+}
+__global__ __launch_bounds__(64) void k_advance_safety_dist(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart, int step,
+                                                            real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                            const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                            tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, SafetyIO io, PlantLib lib,
+                                                            const real* __restrict__ dist) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevVehicle& P = C.veh;
+    const DevVehicle Pl = plant_of(lib, b);
+    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3; real* ot = other + (size_t)b * 4;
+    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+    real uc[3] = {u[0], u[1], u[2]};
+    real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
+    if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
+    if (io.control_h) for (int k = 0; k < 3; k++) io.control_h[(size_t)b * 3 + k] = uc[k];
+    if (io.other_h) for (int k = 0; k < 4; k++) io.other_h[(size_t)b * 4 + k] = oc[k];
+    const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);
+    real n0, n1, n2, w, a;
+    const int src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
+    human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
+    advance_plants_dist(C, Pl, dist + (size_t)b * 4, dtp, x, uc[0], uc[1] + uc[2], q, oc, w, a, ot);
+    u[0] = n0; u[1] = n1; u[2] = n2;
+    clock_next(C, dtp, t0, t_start, clk, idx, b);
+    if (io.human_h) { io.human_h[(size_t)b * 2] = w; io.human_h[(size_t)b * 2 + 1] = a; }
+    if (io.V_h) io.V_h[b] = V;
+    if (io.src_h) io.src_h[b] = src;
+    safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Node callback (pg_node_step_dev / pg_simulate_node_dev): the per-message decision of from_autobox_callback (ros_integration.jl:48-151) for every instance of a batch.
@@ -1941,6 +2061,73 @@ __global__ __launch_bounds__(64) void k_node_finish_plant(DevCfg C, int B, tdoub
             real w, a;
             human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
             advance_plants_lib(C, Pl, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
+            if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
+            clock_next(C, dtp, t0, t_start, clk, idx, b);
+            safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)
+        }
+    }
+    if (__ballot(cold) != 0ull && lane == 0) atomicOr(io.cold, 1);
+}
+// ... the step of the node ROLLOUT under a disturbance library (advance_ego_dist): k_node_finish_plant with w of this step, dist [B][4], on the ego plant -- only the plant
+// part differs; restore, selection, fallback, message and counts are the callback's
+__global__ __launch_bounds__(64) void k_node_finish_dist(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart_cnt, int restart_sum, int step,
+                                                    real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                    const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, KeepView K, NodeIO io, PlantLib lib,
+                                                    const real* __restrict__ dist) {
+    const int lane = (int)threadIdx.x, b = blockIdx.x * 64 + lane;
+    const bool valid = b < B;
+    const int code = valid ? io.gate[b] : 0;
+    unsigned long long m = __ballot(code != 0);
+    while (m) {
+        const int j = __ffsll((long long)m) - 1; m &= m - 1;
+        keep_move(K, blockIdx.x * 64 + j, lane, false);
+    }
+    bool cold = false;
+    if (valid) {
+        const DevVehicle& P = C.veh;
+        real* u = control + (size_t)b * 3;
+        const real msg0 = u[0], msg1 = u[1], msg2 = u[2];                // current_control: the message last published (:52)
+        const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);  // looked up before any gate (:55-57)
+        int ev = code, src = 0;
+        bool pub = false;
+        real p0 = msg0, p1 = msg1, p2 = msg2;                             // the published command
+        if (code == 0) {
+            real n0, n1, n2;
+            src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
+            pub = true;
+            if (n0 != n0 || n1 != n1 || n2 != n2) {                       // :134-147
+                ev = 3; cold = true;
+                u[0] = real(0.0); u[1] = real(0.0); u[2] = real(0.0);
+                K.solved[b] = 0; K.wfail[b] = 0;
+            } else {
+                ev = src;
+                p0 = n0; p1 = n1; p2 = n2;
+                u[0] = n0; u[1] = n1; u[2] = n2;
+            }
+            io.heartbeat[b] += 1;
+        } else cold = K.k_solved[b] == 0;
+        if (io.cmd_out && pub) { io.cmd_out[(size_t)b * 3] = p0; io.cmd_out[(size_t)b * 3 + 1] = p1; io.cmd_out[(size_t)b * 3 + 2] = p2; }
+        if (io.se_out) { io.se_out[(size_t)b * 2] = io.sep[(size_t)b * 4]; io.se_out[(size_t)b * 2 + 1] = io.sep[(size_t)b * 4 + 1]; }
+        if (io.event) io.event[b] = ev;
+        int* cn = io.counts + (size_t)b * 4;
+        int c4[4] = {restart_cnt ? 0 : cn[0], restart_cnt ? 0 : cn[1], restart_cnt ? 0 : cn[2], restart_cnt ? 0 : cn[3]};
+        if (ev >= 4) c4[ev - 4]++;
+        if (ev == 3) c4[3]++;
+        cn[0] = c4[0]; cn[1] = c4[1]; cn[2] = c4[2]; cn[3] = c4[3];
+        {
+            const DevVehicle Pl = plant_of(lib, b);
+            real* q = state + (size_t)b * 6; real* ap = io.applied + (size_t)b * 3; real* ot = other + (size_t)b * 4;
+            real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
+            real ac[3] = {ap[0], ap[1], ap[2]};
+            real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
+            if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
+            if (io.applied_h) for (int k = 0; k < 3; k++) io.applied_h[(size_t)b * 3 + k] = ac[k];
+            if (io.V_h) io.V_h[b] = V;
+            if (io.event_h) io.event_h[b] = ev;
+            real w, a;
+            human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
+            advance_plants_dist(C, Pl, dist + (size_t)b * 4, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
             if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
             clock_next(C, dtp, t0, t_start, clk, idx, b);
             safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)

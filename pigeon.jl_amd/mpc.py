@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -349,6 +349,69 @@ class BatchedTrajectoryTrackingMPC:
             self._chk(getattr(self.lib, f"pg_set_{k}_history_dev")(self.h, C.c_void_p(buf.data_ptr()), int(steps)), f"pg_set_{k}_history_dev")
         return bufs
 
+    # ---- the DISTURBANCE of the rollouts, per instance (forces, gusts, low-friction windows): a library of pg_disturbance, a per-instance selection, a seed and stream ids ----
+    @classmethod
+    def pack_disturbances(cls, sets):
+        """disturbance dicts (vehicles.disturbance(**overrides); missing fields: the identity's) or pg_disturbance structures -> a ctypes array of pg_disturbance."""
+        def fill(rec, v):
+            d = _identity_disturbance(**v)
+            for name in ("step_on", "step_off"):
+                if int(d[name]) != d[name]:
+                    raise ValueError(f"{name} = {d[name]} is not a whole number of rollout steps")
+                setattr(rec, name, int(d[name]))
+            for name in ("Fx", "Fy", "Mz", "sigma_Fx", "sigma_Fy", "x_cp", "tau_gust", "mu_scale"):
+                setattr(rec, name, float(d[name]))
+        return cls._pack(_lib.pg_disturbance, sets, fill)
+
+    def set_disturbances(self, sets, index=None, seed=0, streams=None):
+        """What acts on the ego plant of simulate_ / simulate_safety_ / simulate_node_ from outside (pg_set_disturbance_sets): inside the window [step_on, step_off) a
+        body-frame force (Fx, Fy), a yaw moment Mz, a seeded coloured gust (sigma_Fx, sigma_Fy, x_cp, tau_gust) and a factor mu_scale on the plant's friction, held for
+        the step.  One set (dict / structure) for the whole batch, or a list of sets selected per instance with `index`; `seed` and the 64-bit `streams` [B] (None:
+        stream[b] = b) fix the gust (pg_set_disturbance_seed).  The controller never sees any of it.  Resets nothing.  As set_sensors, EVERY call here installs seed and
+        streams too (set_disturbance_seed afterwards, or pass them again)."""
+        self._set_sets("disturbance", _lib.pg_disturbance, self.pack_disturbances, sets, index)
+        self.set_disturbance_seed(seed, streams)
+
+    def set_disturbance_index(self, index):
+        self._set_index("disturbance", index)
+
+    def set_disturbance_seed(self, seed=0, streams=None):
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
+        self._chk(self.lib.pg_set_disturbance_seed(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), "pg_set_disturbance_seed")
+
+    def clear_disturbances(self):
+        self._chk(self.lib.pg_clear_disturbance_sets(self.h), "pg_clear_disturbance_sets")
+
+    def disturbances(self):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        return self._get_sets("disturbance", _lib.pg_disturbance, lambda r: {name: getattr(r, name) for name, _ in r._fields_})
+
+    def disturbance_response(self, step0, steps, dt):
+        """The law alone, on the device through the function the rollouts call (pg_disturbance_response): w [steps][B][4] = (wFx, wFy, wMz, wmu) of the clock steps
+        [step0, step0 + steps) under the installed library, index, seed and streams, from a fresh gust state at step0.  B is the batch of the inputs last installed."""
+        w = np.zeros((int(steps), self.B, 4))
+        self._chk(self.lib.pg_disturbance_response(self.h, int(step0), int(steps), C.c_double(dt), _p(w)), "pg_disturbance_response")
+        return w
+
+    def disturbance_state(self):
+        """[B][4]: w of the last rollout step under a disturbance library (pg_get_disturbance_state)."""
+        w = np.zeros((self.B, 4))
+        self._chk(self.lib.pg_get_disturbance_state(self.h, _p(w)), "pg_get_disturbance_state")
+        return w
+
+    def _disturbance_hist(self, record, steps):
+        """registers a [steps][B][4] device record of w with the next rollout call; {} unless record and a library is installed"""
+        if not record:
+            return {}
+        n = C.c_int32(0)
+        self._chk(self.lib.pg_get_disturbance_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_disturbance_sets")
+        if n.value == 0:
+            return {}
+        torch, tdt, dev = self._torch()
+        buf = torch.empty(int(steps), self.B, 4, dtype=tdt, device=dev)
+        self._chk(self.lib.pg_set_disturbance_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_disturbance_history_dev")
+        return {"disturbance": buf}
+
     def _torch(self):
         """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""
         import torch
@@ -446,7 +509,7 @@ class BatchedTrajectoryTrackingMPC:
     def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True):
         """The rollouts' shared plumbing.  Device records [steps][B] + shapes[name] in the library's element type and one int32 record `int_record` (record=True), the scripted
         human [steps][B][2], the measured history, under an actuator library the applied / command histories [steps][B][3] (record=True; they join the records as "applied"
-        and "command"); call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
+        and "command"), under a disturbance library the history of w [steps][B][4] (record=True; "disturbance"); call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
         ((state, control, t[, other]), the records as fp64 / int32 numpy arrays or None, (measured history,) or ())."""
         assert human in self.HUMAN_MODES, human
         hu = None; hist = {}
@@ -462,6 +525,7 @@ class BatchedTrajectoryTrackingMPC:
                 hist[int_record] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
         mbuf = self._measured_hist(measured, steps)
         abuf = self._actuator_hists(record, steps)
+        abuf.update(self._disturbance_hist(record, steps))
         call(lambda t: C.c_void_p(t.data_ptr()) if t is not None else None, hu, hist)
         s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
@@ -476,11 +540,13 @@ class BatchedTrajectoryTrackingMPC:
         """simulate (model_predictive_control.jl:80-100) on the device from the inputs last installed; returns (state, control, t) after `steps`
         steps and, with record=True, the histories qs [steps][B][6], us [steps][B][3] (the values pushed at :88-89).  measured=True (a sensor library is installed)
         appends the measured history [steps][B][6] to what is returned.  Under an actuator library `us` is the APPLIED control, and record=True appends
-        {"command": [steps][B][3], "applied": [steps][B][3]} as the last element."""
+        {"command": [steps][B][3], "applied": [steps][B][3]} as the last element; under a disturbance library that last dictionary holds "disturbance": w [steps][B][4]
+        (it is appended for either library)."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_dev(self.h, steps, C.c_double(dt), ptr(hist.get("state")), ptr(hist.get("control"))), "pg_simulate_dev")
         st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,)}, None, call, other=False)
-        act = ({k: out[k] for k in ("command", "applied")},) if record and "applied" in out else ()
+        act = {k: out[k] for k in ("command", "applied", "disturbance") if record and k in out}
+        act = (act,) if act else ()
         return st + ((out["state"], out["control"]) if record else (None, None)) + tail + act
 
     def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False, measured=False):
@@ -489,7 +555,7 @@ class BatchedTrajectoryTrackingMPC:
         other) after `steps` steps and, with record=True, a dict of histories: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B],
         source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step.
         measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned.  Under an actuator library "control" is the APPLIED
-        control and the dict also holds "command" and "applied" [steps][B][3]."""
+        control and the dict also holds "command" and "applied" [steps][B][3]; under a disturbance library it holds "disturbance": w [steps][B][4]."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
                                                       *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
@@ -529,7 +595,8 @@ class BatchedTrajectoryTrackingMPC:
         """The node's closed loop (pg_simulate_node_dev): per step the gates, the compute calls, the callback's decision (NaN fallback included), the ego plant driven by the
         APPLIED command of the step's start, the other car as simulate_safety_.  pre_flag [steps][B] (None: engaged).  Returns (state, message, t, other, applied) after `steps`
         steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event).
-        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned."""
+        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned.  Under a disturbance library the dict also holds
+        "disturbance": w [steps][B][4]."""
         def call(ptr, hu, hist):
             pf = self._pre_flag_dev(pre_flag, (steps, self.B))
             self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),

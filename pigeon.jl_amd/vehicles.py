@@ -74,3 +74,18 @@ def actuator(**overrides):
             raise KeyError(f"{k} is not a field of an actuator set: {ACTUATOR_FIELDS}")
         a[k] = v
     return a
+
+
+DISTURBANCE_FIELDS = ("step_on", "step_off", "Fx", "Fy", "Mz", "sigma_Fx", "sigma_Fy", "x_cp", "tau_gust", "mu_scale")
+
+
+def disturbance(**overrides):
+    """One disturbance set for set_disturbances (pg_disturbance).  disturbance() is the identity -- always active, no force, no moment, no gust, mu unscaled --, which
+    reproduces the handle without a library bit for bit; disturbance(Fy=2000.0, sigma_Fy=800.0, tau_gust=0.3, step_on=3, step_off=9) overrides fields (step_off < 0: the
+    window never closes).  Build-defined: the reference has no disturbance."""
+    d = dict(step_on=0, step_off=-1, Fx=0.0, Fy=0.0, Mz=0.0, sigma_Fx=0.0, sigma_Fy=0.0, x_cp=0.0, tau_gust=0.0, mu_scale=1.0)
+    for k, v in overrides.items():
+        if k not in d:
+            raise KeyError(f"{k} is not a field of a disturbance set: {DISTURBANCE_FIELDS}")
+        d[k] = v
+    return d
