@@ -199,7 +199,7 @@ int pg_get_control_param_sets(pg_handle* h, int32_t* n_sets, pg_control_params* 
  * starts, the rollout clock, the safety, node and tracking summaries are untouched, and the captured pg_step graph is not affected.
  * PG_ERR_INVALID (the handle is left unchanged): n_sets < 1; a non-finite field; any of G, m, Izz, L, a, b, mu, Caf, Car, Fx_max, Px_max, delta_max <= 0; Fx_min >= 0; an
  * index entry outside [0, n_sets); B outside [1, batch_capacity].
- * Cost: under a library the kernel that moves the plant is another one (k_advance_plant, k_advance_safety_plant, k_node_finish_plant: lane = instance, the lane's record
+ * Cost: under a library the kernel that moves the plant is another one (k_advance_lib, k_advance_safety_lib, k_node_finish_lib: lane = instance, the lane's record
  * copied into registers once per step); the launch sequence of a step does not depend on the data. */
 int pg_set_plant_sets(pg_handle* h, int32_t n_sets, const pg_vehicle* sets);
 int pg_set_plant_index(pg_handle* h, int32_t B, const int32_t* index);   /* index[b] in [0, n_sets) */
@@ -320,7 +320,7 @@ int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* c
  * calls and pg_node_step_dev ignore the library.
  * Lifetime, index rule and errors as pg_set_plant_sets.  PG_ERR_INVALID (the handle is left unchanged; the message names the field and the set): a non-finite field;
  * sigma_Fx / sigma_Fy < 0; tau_gust < 0; mu_scale <= 0; step_on < 0.
- * Cost: one lane-per-instance launch (k_disturb) at the top of the step, and the step's plant kernel is the *_dist twin of the *_plant one.  Without a library: nothing
+ * Cost: one lane-per-instance launch (k_disturb) at the top of the step, and the step's plant kernel is the library kernel's instantiation with a disturbance.  Without a library: nothing
  * allocated, the launches of before. */
 typedef struct pg_disturbance {
     int32_t step_on, step_off;     /* active at clock steps k with step_on <= k and (step_off < 0 or k < step_off) */

@@ -51,7 +51,7 @@ struct pg_handle {
     // control-parameter library (pg_set_control_param_sets / pg_set_control_param_index): device records (a library of several sets only) and index are what DevCfg points
     // to; cp_eff [capacity] is the set every instance currently runs under (an instance whose entry changes is reset)
     SetLib<pg_control_params, DevControlRec> cp{{"control-parameter", "pg_set_control_param_index"}}; std::vector<pg_control_params> cp_eff;
-    // plant library (pg_set_plant_sets / pg_set_plant_index): the vehicles the ego plant of the rollouts integrates, per instance, read by the *_plant kernels.  Nothing on
+    // plant library (pg_set_plant_sets / pg_set_plant_index): the vehicles the ego plant of the rollouts integrates, per instance, read by the library kernels (k_*_lib).  Nothing on
     // the controller's side reads any of it
     SetLib<pg_vehicle, DevVehicle> plants{{"plant", "pg_set_plant_index"}};
     // tracking summary (option "tracking_summary"; pg_get_tracking_state): [cap][6] sums, steps [cap] then first_exit [cap] (k_track), allocated when the option is first used
@@ -76,8 +76,8 @@ struct pg_handle {
     int64_t stat_actuator_steps = 0;                              // read-only option "stat_actuator_steps"
     // disturbance library (pg_set_disturbance_sets / pg_set_disturbance_index / pg_set_disturbance_seed): what acts on the ego plant of a rollout step from outside.  Beside
     // the sets: the stream ids [cap] and the seed (as the sensor library keeps its own), and, allocated when a rollout first runs under a library: the gust state
-    // d_dist_n [cap][2], this step's w d_dist_w [cap][4] (k_disturb writes it, the *_dist plant kernel reads it) and d_dist_veh, ONE record holding the handle's own vehicle:
-    // the library of one the *_dist kernels are handed when no plant library is installed
+    // d_dist_n [cap][2], this step's w d_dist_w [cap][4] (k_disturb writes it, the library kernel's <DistW> instantiation reads it) and d_dist_veh, ONE record holding the handle's own vehicle:
+    // the library of one that instantiation is handed when no plant library is installed
     SetLib<pg_disturbance, DevDisturbance> dists{{"disturbance", "pg_set_disturbance_index"}};
     unsigned long long* d_dist_stream = nullptr; bool dist_stream_dirty = true; std::vector<uint64_t> dist_stream; uint64_t dist_seed = 0;
     real *d_dist_n = nullptr, *d_dist_w = nullptr; DevVehicle* d_dist_veh = nullptr;
@@ -1011,7 +1011,7 @@ int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* c
     return rc;
 }
 
-// ---- disturbance library: what acts on the EGO PLANT of a rollout step from outside, w = (wFx, wFy, wMz, wmu) per instance (k_disturb; the *_dist plant kernels).
+// ---- disturbance library: what acts on the EGO PLANT of a rollout step from outside, w = (wFx, wFy, wMz, wmu) per instance (k_disturb; the <DistW> instantiations of the library kernels).
 // Build-defined (the reference integrates the nominal model, model_predictive_control.jl:94).  No part of any QP and invisible to the controller: nothing is reset ----
 static const char* disturbance_field_problem(const pg_disturbance& s) {
     const struct { const char* name; double v; } f[8] = {{"Fx", s.Fx}, {"Fy", s.Fy}, {"Mz", s.Mz}, {"sigma_Fx", s.sigma_Fx}, {"sigma_Fy", s.sigma_Fy}, {"x_cp", s.x_cp},
@@ -1719,7 +1719,7 @@ static int rollout_ready(pg_handle* h) {
     }
     return PG_OK;
 }
-// the disturbance library (the host knows whether one is installed: that alone adds k_disturb to a rollout step and picks the *_dist plant kernel).
+// the disturbance library (the host knows whether one is installed: that alone adds k_disturb to a rollout step and picks the <DistW> instantiation of the library kernel).
 // disturbance_take_history: the one-shot registration of pg_set_disturbance_history_dev, consumed by the rollout call that starts now
 static bool disturbance_lib_on(const pg_handle* h) { return !h->dists.sets.empty(); }
 struct DistHist { real* buf; int steps; };
@@ -1779,7 +1779,7 @@ static int rollout_compute(pg_handle* h, int step, int k, const MeasHist& mh, bo
     h->d_state = true_state;
     return rc;
 }
-// the plant library as the *_plant kernels take it (the host knows whether one is installed: that alone picks the kernel)
+// the plant library as the library kernels (k_*_lib) take it (the host knows whether one is installed: that alone picks the kernel)
 static bool plant_lib_on(const pg_handle* h) { return !h->plants.sets.empty(); }
 static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->plants.d, h->plants.sets.size() > 1 ? h->plants.idx.d : (const int*)nullptr}; }
 // the step's tracking summary (option "tracking_summary"): behind the projection of this step (step_compute), ahead of the kernel that moves the plant
@@ -1807,8 +1807,9 @@ static int clock_start(pg_handle* h, double dt) {
 }
 static int node_start(pg_handle* h, double dt);
 }  // extern "C" (the rollouts' templates have C++ linkage)
-// the last launch of a rollout step, one lane per instance: `uniform`, or under a plant library `with_plant` -- the same arguments and the library behind them --, or
-// under a disturbance library `with_dist`: the plant library (without one: the library of one made of the handle's own vehicle) and w of this step behind them
+// the last launch of a rollout step, one lane per instance: `uniform`, or the family's library kernel -- under a plant library its instantiation `with_plant`, the same
+// arguments and the library behind them; under a disturbance library its instantiation `with_dist` (W = DistW), the plant library (without one: the library of one made of
+// the handle's own vehicle) and w of this step behind them
 template <class K, class KP, class KD, class... A>
 static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_dist, const A&... args) {
     const dim3 grid((h->B + 63) / 64), block(64);
@@ -1872,7 +1873,7 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
             if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)control_hist_dev, k, B, 3), h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));  // push!(us, control) :89
             return PG_OK;
         },
-        [&](int, int) { launch_plant_step(h, k_advance, k_advance_plant, k_advance_dist, h->dc, h->B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
+        [&](int, int) { launch_plant_step(h, k_advance, k_advance_lib<>, k_advance_lib<DistW>, h->dc, h->B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
 }
 // simulate (:80-100) with the control the ROS node sends (ros_integration.jl:114-124) fed back and the other car moving (k_advance_safety, pg_kernels.hip).  Per step: the four
 // compute calls exactly as pg_simulate_dev makes them (fusion, pipelining and the split solve unchanged; with a grid they leave the step's relative state d_x7 and its
@@ -1887,7 +1888,7 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
             SafetyIO io{human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr, hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
                         hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
                         h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-            launch_plant_step(h, k_advance_safety, k_advance_safety_plant, k_advance_safety_dist, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji, (int)h->sum_fresh, step,
+            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji, (int)h->sum_fresh, step,
                               h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
             h->sum_fresh = false;
         });
@@ -2004,7 +2005,7 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
             io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
             io.event_h = hist_at(event_hist_dev, k, B, 1);
             io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-            launch_plant_step(h, k_node_finish<true>, k_node_finish_plant, k_node_finish_dist, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
                               (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
                               h->sim_idx, h->kv, io);
             h->sum_fresh = false;

@@ -929,10 +929,12 @@ PG_DEV void advance_ego(const DevCfg& C, real* x, real d, real Fx, real h, int n
 }
 
 // Plant library (pg_set_plant_sets / pg_set_plant_index): the vehicle the EGO PLANT of a rollout step integrates (model_predictive_control.jl:94), per instance.  Only the
-// *_plant kernels take it -- they are launched when a library is installed, a fact of the handle the host knows; the controller's side of every kernel keeps C.veh.
+// library kernels take it -- ONE template per family, k_advance_lib, k_advance_safety_lib and k_node_finish_lib, each with an optional disturbance behind the library (the
+// trailing pack W: empty, or the one pointer to w of this step; see advance_ego_lib).  They are launched when a library is installed, a fact of the handle the host knows;
+// the controller's side of every kernel keeps C.veh.
 // The kernels of the uniform path (k_advance, k_advance_safety, k_node_finish and the device functions they call) are left EXACTLY as they were: routing them and the
-// *_plant kernels through shared bodies was tried and regrouped the instructions of k_advance_safety and k_node_finish in both builds (other FMA operand orders in fp64,
-// another schedule in fp32) -- the uniform path must keep its bits and its cost, so the library path restates the few lines it needs (same statements, P in place of C.veh).
+// library kernels through shared bodies was tried and regrouped the instructions of k_advance_safety and k_node_finish in both builds (other FMA operand orders in fp64,
+// another schedule in fp32) -- the uniform path must keep its bits and its cost, so the library path has its own statement of the few lines it needs (P in place of C.veh).
 // A lane copies its record into registers once, ahead of the RK4 loop (idx == nullptr: a library of one, every lane reads record 0).  These kernels run one 64-lane block per
 // 64 instances -- a wavefront or two per CU at B = 4096 -- so the registers a resident record takes cost no occupancy anyone uses, and the serial chain of 4 nsub right-hand
 // sides per step reads no memory at all; loading each field where it is used (ControlView's arrangement, made for register-tight kernels at full occupancy) would put
@@ -1000,26 +1002,14 @@ __global__ __launch_bounds__(64) void k_advance(DevCfg C, int B, tdouble dtp, re
     u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
     clock_next(C, dtp, t0, t_start, clk, idx, b);
 }
-// ... under a plant library: the same step with the instance's own vehicle in the plant (advance_ego_plant's statement of the RK4)
-__global__ __launch_bounds__(64) void k_advance_plant(DevCfg C, int B, tdouble dtp, real* __restrict__ state, real* __restrict__ control, const real* __restrict__ u_next,
-                                                      tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, PlantLib lib) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const DevVehicle P = plant_of(lib, b);
-    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3;
-    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
-    const int nsub = C.nsub; const real h = dtp / nsub;
-    advance_ego_plant(P, x, u[0], u[1] + u[2], h, nsub);
-    for (int k = 0; k < 6; k++) q[k] = x[k];
-    u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
-    clock_next(C, dtp, t0, t_start, clk, idx, b);
-}
-// Disturbance library (pg_set_disturbance_sets): the *_dist kernels are the *_plant kernels with w = (wFx, wFy, wMz, wmu) of the instance (k_disturb wrote it at the top of
-// the step) acting on the ego plant, held for the step: the tire model sees mu * wmu -- the lane scales P.mu in its register copy of the vehicle record -- and every RK4
-// sub-step adds wFx / m, wFy / m, wMz / Izz behind world_body_rhs.  ZERO RULE: a component that is exactly 0 is not added and wmu == 1 is not multiplied, so w = (0, 0, 0, 1)
-// leaves the statements of advance_ego_plant -- and a lane whose whole w is (0, 0, 0, 1) runs advance_ego_plant itself (advance_ego_under): the conditional adds alone
-// regrouped the fp64 FMAs of the right-hand side, and the identity set must give the bits of the handle without a library.  Launched only when a disturbance library is installed; without a plant library the host hands them a library of one made
-// of the handle's own vehicle (three kernels, not six).  advance_ego_plant's statement of the RK4, restated (see PlantLib above: no existing body is shared)
+// Disturbance library (pg_set_disturbance_sets): a library kernel instantiated with the pointer to dist [B][4] moves the ego plant under w = (wFx, wFy, wMz, wmu) of the
+// instance (k_disturb wrote it at the top of the step), held for the step: the tire model sees mu * wmu -- the lane scales P.mu in its register copy of the vehicle record --
+// and every RK4 sub-step adds wFx / m, wFy / m, wMz / Izz behind world_body_rhs.  ZERO RULE: a component that is exactly 0 is not added and wmu == 1 is not multiplied, so
+// w = (0, 0, 0, 1) leaves the statements of advance_ego_plant -- and a lane whose whole w is (0, 0, 0, 1) runs advance_ego_plant itself (advance_ego_lib): the conditional
+// adds alone regrouped the fp64 FMAs of the right-hand side, and the identity set must give the bits of the handle without a library.  That instantiation is launched only
+// when a disturbance library is installed; without a plant library the host hands it a library of one made of the handle's own vehicle.
+// advance_ego_dist keeps its own statement of the RK4 loop: one loop function behind it and advance_ego_plant gave the kernels that inline both another schedule in both
+// builds (EXPERIMENTS 22)
 PG_DEV void advance_ego_dist(DevVehicle P, const real* __restrict__ w, real* x, real d, real Fx, real h, int nsub) {
     const real wFx = w[0], wFy = w[1], wMz = w[2], wmu = w[3];
     if (wmu != real(1.0)) P.mu = P.mu * wmu;
@@ -1046,20 +1036,24 @@ PG_DEV void advance_ego_dist(DevVehicle P, const real* __restrict__ w, real* x, 
         for (int k = 0; k < 6; k++) x[k] += (k1[k] + real(2.0) * k2[k] + real(2.0) * k3[k] + k4[k]) * (h / real(6.0));
     }
 }
-PG_DEV void advance_ego_under(const DevVehicle& P, const real* __restrict__ w, real* x, real d, real Fx, real h, int nsub) {
+// the ego plant of a library kernel over one step, as the kernel's pack W selects it: the plant's own vehicle alone, or w of the instance on it (identity: see above)
+PG_DEV void advance_ego_lib(const DevVehicle& P, real* x, real d, real Fx, real h, int nsub) { advance_ego_plant(P, x, d, Fx, h, nsub); }
+PG_DEV void advance_ego_lib(const DevVehicle& P, real* x, real d, real Fx, real h, int nsub, const real* __restrict__ w) {
     if (w[0] == real(0.0) && w[1] == real(0.0) && w[2] == real(0.0) && w[3] == real(1.0)) advance_ego_plant(P, x, d, Fx, h, nsub);
     else advance_ego_dist(P, w, x, d, Fx, h, nsub);
 }
-// ... k_advance_plant under a disturbance library: dist [B][4] = w of this step
-__global__ __launch_bounds__(64) void k_advance_dist(DevCfg C, int B, tdouble dtp, real* __restrict__ state, real* __restrict__ control, const real* __restrict__ u_next,
-                                                     tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, PlantLib lib, const real* __restrict__ dist) {
+// ... under a plant library: k_advance's step with the instance's own vehicle in the plant, and with W = DistW the disturbance of this step on it, dist [B][4]
+using DistW = const real* __restrict__;
+template <class... W>
+__global__ __launch_bounds__(64) void k_advance_lib(DevCfg C, int B, tdouble dtp, real* __restrict__ state, real* __restrict__ control, const real* __restrict__ u_next,
+                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, PlantLib lib, W... dist) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const DevVehicle P = plant_of(lib, b);
     real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3;
     real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
     const int nsub = C.nsub; const real h = dtp / nsub;
-    advance_ego_under(P, dist + (size_t)b * 4, x, u[0], u[1] + u[2], h, nsub);
+    advance_ego_lib(P, x, u[0], u[1] + u[2], h, nsub, (dist + (size_t)b * 4)...);
     for (int k = 0; k < 6; k++) q[k] = x[k];
     u[0] = u_next[(size_t)b * 3]; u[1] = u_next[(size_t)b * 3 + 1]; u[2] = u_next[(size_t)b * 3 + 2];
     clock_next(C, dtp, t0, t_start, clk, idx, b);
@@ -1184,7 +1178,7 @@ __global__ __launch_bounds__(64) void k_actuator_response(int B, int steps, real
 
 // Disturbance library (pg_set_disturbance_sets), lane = instance: w = (wFx, wFy, wMz, wmu) the ego plant of this rollout step integrates (disturbance_advance,
 // pg_device.hpp).  Queued at the top of the step, next to k_actuate.  Reads the instance's record (copied into registers once), its stream id and, unless `fresh`, the
-// gust state n [cap][2]; writes n, w [cap][4] (what the *_dist plant kernel of the step reads) and the step's row of the history when one is registered.  The draw is a
+// gust state n [cap][2]; writes n, w [cap][4] (what the step's library kernel reads, instantiated with DistW) and the step's row of the history when one is registered.  The draw is a
 // function of (seed, stream id, clock step) alone, not of b or B.  idx == nullptr: a library of one.  `fresh`: no state of the previous step exists
 struct DisturbanceLib { const DevDisturbance* sets; const int* idx; const unsigned long long* stream; unsigned long long seed; real* n; real* w; };
 __global__ __launch_bounds__(64) void k_disturb(int B, int step, int fresh, real dt, DisturbanceLib lib, real* __restrict__ hist) {
@@ -1805,55 +1799,21 @@ __global__ __launch_bounds__(64) void k_advance_safety(DevCfg C, int B, tdouble 
     if (io.src_h) io.src_h[b] = src;
     safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);      // (the selected control is the one fed back: every source-1 step is a policy step)
 }
-// ... under a plant library (PlantLib above): k_advance_safety with the instance's own vehicle in the ego plant; selection, policy and the human's optimal_disturbance keep C.veh
-PG_DEV void advance_plants_lib(const DevCfg& C, const DevVehicle& Pl, tdouble dtp, real* x, real d, real Fx, real* __restrict__ q, real* oc, real w, real a, real* __restrict__ ot) {
+// ... under a plant library (PlantLib above): k_advance_safety with the instance's own vehicle in the ego plant; selection, policy and the human's optimal_disturbance keep
+// C.veh.  W = DistW: w of this step, dist [B][4], on the ego plant as well (advance_ego_lib).  The other car is not disturbed
+template <class... W>
+PG_DEV void advance_plants_lib(const DevCfg& C, const DevVehicle& Pl, tdouble dtp, real* x, real d, real Fx, real* __restrict__ q, real* oc, real ow, real oa, real* __restrict__ ot, W... w) {
     const int nsub = C.nsub; const real h = dtp / nsub;
-    advance_ego_plant(Pl, x, d, Fx, h, nsub);
-    advance_unicycle(oc, w, a, h, nsub);
-    for (int k = 0; k < 6; k++) q[k] = x[k];
-    for (int k = 0; k < 4; k++) ot[k] = oc[k];
-}
-__global__ __launch_bounds__(64) void k_advance_safety_plant(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart, int step,
-                                                             real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
-                                                             const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
-                                                             tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, SafetyIO io, PlantLib lib) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const DevVehicle& P = C.veh;
-    const DevVehicle Pl = plant_of(lib, b);
-    real* q = state + (size_t)b * 6; real* u = control + (size_t)b * 3; real* ot = other + (size_t)b * 4;
-    real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
-    real uc[3] = {u[0], u[1], u[2]};
-    real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
-    if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
-    if (io.control_h) for (int k = 0; k < 3; k++) io.control_h[(size_t)b * 3 + k] = uc[k];
-    if (io.other_h) for (int k = 0; k < 4; k++) io.other_h[(size_t)b * 4 + k] = oc[k];
-    const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);
-    real n0, n1, n2, w, a;
-    const int src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
-    human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
-    advance_plants_lib(C, Pl, dtp, x, uc[0], uc[1] + uc[2], q, oc, w, a, ot);
-    u[0] = n0; u[1] = n1; u[2] = n2;
-    clock_next(C, dtp, t0, t_start, clk, idx, b);
-    if (io.human_h) { io.human_h[(size_t)b * 2] = w; io.human_h[(size_t)b * 2 + 1] = a; }
-    if (io.V_h) io.V_h[b] = V;
-    if (io.src_h) io.src_h[b] = src;
-    safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart, V, step, src == 1);
-}
-// ... under a disturbance library (advance_ego_dist above): k_advance_safety_plant with w of this step, dist [B][4], on the ego plant.  The other car is not disturbed
-PG_DEV void advance_plants_dist(const DevCfg& C, const DevVehicle& Pl, const real* __restrict__ w, tdouble dtp, real* x, real d, real Fx, real* __restrict__ q, real* oc, real ow, real oa,
-                                real* __restrict__ ot) {
-    const int nsub = C.nsub; const real h = dtp / nsub;
-    advance_ego_under(Pl, w, x, d, Fx, h, nsub);
+    advance_ego_lib(Pl, x, d, Fx, h, nsub, w...);
     advance_unicycle(oc, ow, oa, h, nsub);
     for (int k = 0; k < 6; k++) q[k] = x[k];
     for (int k = 0; k < 4; k++) ot[k] = oc[k];
 }
-__global__ __launch_bounds__(64) void k_advance_safety_dist(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart, int step,
-                                                            real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
-                                                            const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
-                                                            tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, SafetyIO io, PlantLib lib,
-                                                            const real* __restrict__ dist) {
+template <class... W>
+__global__ __launch_bounds__(64) void k_advance_safety_lib(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart, int step,
+                                                           real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
+                                                           const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
+                                                           tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, SafetyIO io, PlantLib lib, W... dist) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const DevVehicle& P = C.veh;
@@ -1869,7 +1829,7 @@ __global__ __launch_bounds__(64) void k_advance_safety_dist(DevCfg C, int B, tdo
     real n0, n1, n2, w, a;
     const int src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
     human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
-    advance_plants_dist(C, Pl, dist + (size_t)b * 4, dtp, x, uc[0], uc[1] + uc[2], q, oc, w, a, ot);
+    advance_plants_lib<W...>(C, Pl, dtp, x, uc[0], uc[1] + uc[2], q, oc, w, a, ot, (dist + (size_t)b * 4)...);
     u[0] = n0; u[1] = n1; u[2] = n2;
     clock_next(C, dtp, t0, t_start, clk, idx, b);
     if (io.human_h) { io.human_h[(size_t)b * 2] = w; io.human_h[(size_t)b * 2 + 1] = a; }
@@ -2003,11 +1963,13 @@ __global__ __launch_bounds__(64) void k_node_finish(DevCfg C, int B, tdouble dtp
     }
     if (__ballot(cold) != 0ull && lane == 0) atomicOr(io.cold, 1);
 }
-// ... the step of the node ROLLOUT under a plant library (PlantLib above): k_node_finish<true> with the instance's own vehicle in the ego plant
-__global__ __launch_bounds__(64) void k_node_finish_plant(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart_cnt, int restart_sum, int step,
+// ... the step of the node ROLLOUT under a plant library (PlantLib above): k_node_finish<true> with the instance's own vehicle in the ego plant, and with W = DistW w of
+// this step, dist [B][4], on it (advance_ego_lib) -- only the plant part differs; restore, selection, fallback, message and counts are the callback's
+template <class... W>
+__global__ __launch_bounds__(64) void k_node_finish_lib(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart_cnt, int restart_sum, int step,
                                                     real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
                                                     const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
-                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, KeepView K, NodeIO io, PlantLib lib) {
+                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, KeepView K, NodeIO io, PlantLib lib, W... dist) {
     const int lane = (int)threadIdx.x, b = blockIdx.x * 64 + lane;
     const bool valid = b < B;
     const int code = valid ? io.gate[b] : 0;
@@ -2060,74 +2022,7 @@ __global__ __launch_bounds__(64) void k_node_finish_plant(DevCfg C, int B, tdoub
             if (io.event_h) io.event_h[b] = ev;
             real w, a;
             human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
-            advance_plants_lib(C, Pl, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
-            if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
-            clock_next(C, dtp, t0, t_start, clk, idx, b);
-            safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)
-        }
-    }
-    if (__ballot(cold) != 0ull && lane == 0) atomicOr(io.cold, 1);
-}
-// ... the step of the node ROLLOUT under a disturbance library (advance_ego_dist): k_node_finish_plant with w of this step, dist [B][4], on the ego plant -- only the plant
-// part differs; restore, selection, fallback, message and counts are the callback's
-__global__ __launch_bounds__(64) void k_node_finish_dist(DevCfg C, int B, tdouble dtp, int use_policy, int human_mode, int has_hji, int restart_cnt, int restart_sum, int step,
-                                                    real* __restrict__ state, real* __restrict__ control, real* __restrict__ other, const real* __restrict__ u_mpc,
-                                                    const real* __restrict__ x7, const real* __restrict__ vg8, const tdouble* __restrict__ toff,
-                                                    tdouble* __restrict__ t0, const tdouble* __restrict__ t_start, JlRange clk, int idx, KeepView K, NodeIO io, PlantLib lib,
-                                                    const real* __restrict__ dist) {
-    const int lane = (int)threadIdx.x, b = blockIdx.x * 64 + lane;
-    const bool valid = b < B;
-    const int code = valid ? io.gate[b] : 0;
-    unsigned long long m = __ballot(code != 0);
-    while (m) {
-        const int j = __ffsll((long long)m) - 1; m &= m - 1;
-        keep_move(K, blockIdx.x * 64 + j, lane, false);
-    }
-    bool cold = false;
-    if (valid) {
-        const DevVehicle& P = C.veh;
-        real* u = control + (size_t)b * 3;
-        const real msg0 = u[0], msg1 = u[1], msg2 = u[2];                // current_control: the message last published (:52)
-        const real V = has_hji ? vg8[(size_t)b * 8] : real(INFINITY);  // looked up before any gate (:55-57)
-        int ev = code, src = 0;
-        bool pub = false;
-        real p0 = msg0, p1 = msg1, p2 = msg2;                             // the published command
-        if (code == 0) {
-            real n0, n1, n2;
-            src = hji_select(C, use_policy, has_hji, V, toff, u_mpc, x7, vg8, b, n0, n1, n2);
-            pub = true;
-            if (n0 != n0 || n1 != n1 || n2 != n2) {                       // :134-147
-                ev = 3; cold = true;
-                u[0] = real(0.0); u[1] = real(0.0); u[2] = real(0.0);
-                K.solved[b] = 0; K.wfail[b] = 0;
-            } else {
-                ev = src;
-                p0 = n0; p1 = n1; p2 = n2;
-                u[0] = n0; u[1] = n1; u[2] = n2;
-            }
-            io.heartbeat[b] += 1;
-        } else cold = K.k_solved[b] == 0;
-        if (io.cmd_out && pub) { io.cmd_out[(size_t)b * 3] = p0; io.cmd_out[(size_t)b * 3 + 1] = p1; io.cmd_out[(size_t)b * 3 + 2] = p2; }
-        if (io.se_out) { io.se_out[(size_t)b * 2] = io.sep[(size_t)b * 4]; io.se_out[(size_t)b * 2 + 1] = io.sep[(size_t)b * 4 + 1]; }
-        if (io.event) io.event[b] = ev;
-        int* cn = io.counts + (size_t)b * 4;
-        int c4[4] = {restart_cnt ? 0 : cn[0], restart_cnt ? 0 : cn[1], restart_cnt ? 0 : cn[2], restart_cnt ? 0 : cn[3]};
-        if (ev >= 4) c4[ev - 4]++;
-        if (ev == 3) c4[3]++;
-        cn[0] = c4[0]; cn[1] = c4[1]; cn[2] = c4[2]; cn[3] = c4[3];
-        {
-            const DevVehicle Pl = plant_of(lib, b);
-            real* q = state + (size_t)b * 6; real* ap = io.applied + (size_t)b * 3; real* ot = other + (size_t)b * 4;
-            real x[6] = {q[0], q[1], q[2], q[3], q[4], q[5]};
-            real ac[3] = {ap[0], ap[1], ap[2]};
-            real oc[4] = {ot[0], ot[1], ot[2], ot[3]};
-            if (io.state_h) for (int k = 0; k < 6; k++) io.state_h[(size_t)b * 6 + k] = x[k];
-            if (io.applied_h) for (int k = 0; k < 3; k++) io.applied_h[(size_t)b * 3 + k] = ac[k];
-            if (io.V_h) io.V_h[b] = V;
-            if (io.event_h) io.event_h[b] = ev;
-            real w, a;
-            human_control(P, human_mode, has_hji, x7, vg8, io.human_u, b, w, a);
-            advance_plants_dist(C, Pl, dist + (size_t)b * 4, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot);      // the command applied at the step's start (one-step delay, as k_advance)
+            advance_plants_lib<W...>(C, Pl, dtp, x, ac[0], ac[1] + ac[2], q, oc, w, a, ot, (dist + (size_t)b * 4)...);      // the command applied at the step's start (one-step delay, as k_advance)
             if (pub) { ap[0] = p0; ap[1] = p1; ap[2] = p2; }
             clock_next(C, dtp, t0, t_start, clk, idx, b);
             safety_summary(io.V_min, io.first_breach, io.policy_steps, b, restart_sum, V, step, ev == 1);      // (ev, not src: a gated-out step or a NaN fallback publishes no policy command)

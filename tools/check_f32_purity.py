@@ -7,7 +7,8 @@ expression to fp64 in the fp32 build.  This reads the gfx950 assembly of that bu
 instruction it is not entitled to:
   * every kernel may convert / compare / frexp fp64 values (v_cvt_*, v_cmp_*, v_frexp_*: reading the double time grid, libm's sincosf reduction);
   * the kernels that compute with ABSOLUTE TIME (tdouble: k_time_steps and the k_project<true> instantiation that carries the time grid in the fused launch, the
-    warm-branch interpolation weights of k_nodes / k_nodes_warm / k_nodes_recheck, the clock of k_advance, k_advance_safety and k_node_finish and of their plant-library and disturbance-library forms k_*_plant, k_*_dist) may use fp64 arithmetic;
+    warm-branch interpolation weights of k_nodes / k_nodes_warm / k_nodes_recheck, the clock of k_advance, k_advance_safety and k_node_finish and of their library forms, the templates k_advance_lib, k_advance_safety_lib and
+    k_node_finish_lib -- each with and without a disturbance) may use fp64 arithmetic;
   * everything else (k_solve, k_linearize, k_limits, k_qp_dec, k_project, k_hji_*) must be pure fp32.
 Exit status 0 = clean; 1 = violations (listed)."""
 import collections
@@ -16,7 +17,7 @@ import re
 import sys
 
 TIME_KERNELS = ("k_time_steps", "k_nodes", "k_nodes_linearize", "k_nodes_warm", "k_nodes_dec", "k_advance", "k_advance_safety", "k_node_finish", "k_nodes_recheck",
-                "k_advance_plant", "k_advance_safety_plant", "k_node_finish_plant", "k_advance_dist", "k_advance_safety_dist", "k_node_finish_dist")
+                "k_advance_lib", "k_advance_safety_lib", "k_node_finish_lib")
 HARMLESS = re.compile(r"^v_(cvt_|cmp_|cmpx_|frexp_)")
 
 
