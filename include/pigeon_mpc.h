@@ -347,6 +347,52 @@ int pg_get_disturbance_state(pg_handle* h, double* w);
  * returns an error --; NULL cancels.  PG_ERR_STATE without a library */
 int pg_set_disturbance_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
 
+/* Estimator sets: the block between the sensor and the controller of a rollout step, per instance -- a fixed-gain observer that blends the measurement with a model
+ * prediction -- tuning x plant x sensor x actuator x disturbance x estimator studies as ONE batch.  A library of pg_estimator and a per-instance selection, shaped like
+ * pg_set_actuator_sets.  BUILD-DEFINED: the reference has no estimator; its node receives an estimate from the car (src/ros_integration.jl:48-52).
+ * With a library installed the gate and the compute calls of a step of pg_simulate_dev, pg_simulate_safety_dev and pg_simulate_node_dev read the ESTIMATE xh_k in place of
+ * the state.  Per instance at clock step k (the step index of first_breach, first_exit and the sensor draws):
+ *   y_k      = the sensor's output of the step: the measured state under a sensor library, else the true state
+ *   u_{k-1}  = the control the controller was handed at step k - 1 (the command; under an actuator library with feedback == 1 the actuator's position)
+ *   p_k      = advance(xh_{k-1}, u_{k-1}, dt)      predict == 1: one step of the CONTROLLER's model, pg_config.vehicle (never the plant library's) -- RK4 with rk4_substeps
+ *                                                  sub-steps over the rollout's dt, (delta, Fx = Fxf + Fxr) held, exactly as the plant of a handle without libraries integrates
+ *            = xh_{k-1}                            predict == 0: every channel an exponential low-pass of the measurement
+ *   xh_k[c]  = p_k[c] + gain[c] (y_k[c] - p_k[c])  per channel c of (E, N, psi, Ux, Uy, r), in the library's element type, the product and the two sums rounded once each.
+ *                                                  A plain difference on psi as well: the plant's psi is the unwrapped integral of r.  gain[c] == 1 COPIES y_k[c] and
+ *                                                  gain[c] == 0 COPIES p_k[c]: no arithmetic.
+ *   xh_k     = y_k                                 when no estimate of step k - 1 exists: the first rollout step after pg_set_inputs*, after the clock restarted (another
+ *                                                  dt, another path end) or after pg_clear_estimator_sets.  Installing sets or an index resets nothing.
+ *   xh_k     = y_k                                 for an instance whose prior p_k has a non-finite component: that instance's estimator starts again
+ * IDENTITY: a set whose six gains are all 1 runs no prediction and copies y_k, so {predict, 0, {1, 1, 1, 1, 1, 1}} reproduces the handle without a library bit for bit.
+ * What follows the estimate: the node gates (low speed reads xh's Ux), the projection and the (s, e) a node step publishes, the linearisation nodes, the QP's q_curr, the
+ * HJI relative state, the policy selection and the worst-case human.  What keeps the truth: the plant, the records (state_hist), pg_get_state and the tracking summary
+ * (with the summary on, the true state is projected once more per step, as under a sensor library).  pg_step*, the phase calls and pg_node_step_dev ignore the library.
+ * The node rollout runs under it; a gated-out instance's estimator advances like every other.
+ * Lifetime, index rule and errors as pg_set_plant_sets.  PG_ERR_INVALID (the handle is left unchanged; the message names the set and the field): a gain outside [0, 1] or
+ * not finite; predict not 0 or 1; reserved != 0.
+ * Cost: one lane-per-instance launch (k_estimate) per step, behind k_measure; its observer lanes run one RK4 step.  Without a library: nothing allocated, the launches of
+ * before; the read-only option "stat_estimator_steps" (rollout steps that ran under a library) stays 0. */
+typedef struct pg_estimator {
+    int32_t predict;               /* 1: the prior is one step of the controller's model; 0: the prior is the previous estimate */
+    int32_t reserved;              /* must be 0 */
+    double  gain[6];               /* per channel of (E, N, psi, Ux, Uy, r), each in [0, 1]: 1 = the measurement itself, 0 = the prior alone */
+} pg_estimator;                    /* 56 bytes */
+int pg_set_estimator_sets(pg_handle* h, int32_t n_sets, const pg_estimator* sets);
+int pg_set_estimator_index(pg_handle* h, int32_t B, const int32_t* index);       /* index[b] in [0, n_sets) */
+int pg_clear_estimator_sets(pg_handle* h);                                       /* back to the sensor's output; the estimate is dropped */
+/* the installed library, as pg_get_plant_sets */
+int pg_get_estimator_sets(pg_handle* h, int32_t* n_sets, pg_estimator* out, int32_t max_sets, int32_t* index, int32_t B);
+/* estimated [B][6] = xh of the last rollout step under a library; PG_ERR_STATE before the first one since the inputs were installed */
+int pg_get_estimated_state(pg_handle* h, double* estimated);
+/* the NEXT rollout call writes xh of its step k < steps to buf[k][B][6] (library element type); one-shot -- that call consumes the registration whether it succeeds or
+ * returns an error --; NULL cancels.  PG_ERR_STATE without a library */
+int pg_set_estimated_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
+/* the law alone, ON THE DEVICE through the function k_estimate calls (k_estimator_response): y [steps][B][6] and u [steps][B][3] on the host (u[k]: the control the
+ * controller is handed at step k; step k's prior is driven by u[k - 1], so u[steps - 1] is read by nothing) -> xhat [steps][B][6], with the installed library and index
+ * over the current batch B (pg_set_inputs*), from a fresh state (xhat[0] = y[0]).  Touches neither the rollout clock nor the handle's estimate (scratch of its own).
+ * steps >= 1, dt > 0; PG_ERR_STATE without inputs, without a library or with an index that does not cover the batch */
+int pg_estimator_response(pg_handle* h, int32_t steps, double dt, const double* y, const double* u, double* xhat);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -525,6 +571,7 @@ int pg_synchronize(pg_handle* h);
  *     "stat_sensor_steps"        (read-only) rollout steps that ran under a sensor library (k_measure launches) since pg_create
  *     "stat_actuator_steps"      (read-only) rollout steps whose plant launch ran under an actuator library (k_actuate launches) since pg_create
  *     "stat_disturbance_steps"   (read-only) rollout steps that ran under a disturbance library (k_disturb launches) since pg_create
+ *     "stat_estimator_steps"     (read-only) rollout steps that ran under an estimator library (k_estimate launches) since pg_create
  *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact

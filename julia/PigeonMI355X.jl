@@ -351,6 +351,52 @@ end
 set_disturbance_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
     check(mpc, ccall(sym(mpc, :pg_set_disturbance_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_disturbance_history_dev")
 
+# Estimator sets (pg_set_estimator_sets ...): a fixed-gain observer between the sensor and the controller of the rollouts.  NOT EXECUTED in the build container, like the rest of this file.
+
+"One estimator (pg_estimator): predict = 1 takes one step of the controller's own model from the previous estimate as the prior, predict = 0 the previous estimate itself; reserved is 0; gain per channel of (E, N, psi, Ux, Uy, r) in [0, 1], estimate = prior + gain (measurement - prior).  PgEstimator() is the identity (every gain 1): the handle without a library, bit for bit."
+struct PgEstimator
+    predict::Int32
+    reserved::Int32
+    gain::NTuple{6,Float64}
+end
+PgEstimator(; predict=1, gain=ntuple(_ -> 1.0, 6)) = PgEstimator(Int32(predict), Int32(0), gain isa Real ? ntuple(_ -> Float64(gain), 6) : NTuple{6,Float64}(Float64.(Tuple(gain))))
+"the layout include/pigeon_mpc.h states (56 bytes): checked before the first install"
+function check_estimator_layout()
+    off(f) = Int(fieldoffset(PgEstimator, Base.fieldindex(PgEstimator, f)))
+    (sizeof(PgEstimator), off(:predict), off(:reserved), off(:gain)) == (56, 0, 4, 8) || error("PigeonMI355X.jl: PgEstimator differs from pg_estimator of include/pigeon_mpc.h")
+end
+"What the CONTROLLER of the three rollouts reads in place of the sensor's output: a library of estimators and the set each instance runs under (0-based; may be empty for a library of one).  The plant, the records and the summaries keep the truth.  Resets nothing."
+function set_estimators!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgEstimator}, index::Vector{Int32}=Int32[])
+    check_estimator_layout()
+    check(mpc, ccall(sym(mpc, :pg_set_estimator_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgEstimator}), mpc.handle, length(sets), sets), "pg_set_estimator_sets")
+    isempty(index) || check(mpc, ccall(sym(mpc, :pg_set_estimator_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_estimator_index")
+    nothing
+end
+clear_estimators!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_estimator_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_estimator_sets")
+"(sets, index over B instances; -1 where no index covers an instance) as installed"
+function get_estimators(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_estimator_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgEstimator}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_estimator_sets")
+    sets = Vector{PgEstimator}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_estimator_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgEstimator}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_estimator_sets")
+    sets, index
+end
+"6 x B: the estimate the controller read at the last rollout step under an estimator library"
+function estimated_state(mpc::BatchedTrajectoryTrackingMPC)
+    e = zeros(6, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_estimated_state), Cint, (Ptr{Cvoid}, Ptr{Float64}), mpc.handle, e), "pg_get_estimated_state")
+    e
+end
+"The NEXT rollout call writes the estimate of its step k < steps to a device array 6 x B x steps of the library's element type (one-shot; C_NULL cancels)"
+set_estimated_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_estimated_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_estimated_history_dev")
+"The law alone, on the device: measurements y 6 x B x steps and controls u 3 x B x steps (u[:, :, k]: what the controller is handed at step k) -> estimates 6 x B x steps under the installed library and index, from a fresh state"
+function estimator_response(mpc::BatchedTrajectoryTrackingMPC, y::Array{Float64,3}, u::Array{Float64,3}, dt::Float64)
+    xhat = zeros(size(y))
+    check(mpc, ccall(sym(mpc, :pg_estimator_response), Cint, (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mpc.handle, size(y, 3), dt, y, u, xhat), "pg_estimator_response")
+    xhat
+end
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

@@ -85,6 +85,15 @@ struct pg_handle {
     bool dist_valid = false;                                      // d_dist_w holds w of a rollout step since the inputs were installed
     real* dist_hist = nullptr; int dist_hist_steps = 0;           // pg_set_disturbance_history_dev: one-shot, consumed by the next rollout call
     int64_t stat_disturbance_steps = 0;                           // read-only option "stat_disturbance_steps"
+    // estimator library (pg_set_estimator_sets / pg_set_estimator_index): a fixed-gain observer between the sensor and the controller of a rollout step.  Beside the sets,
+    // allocated at the first install: the estimate d_est [cap][6] (what the gate and the compute calls of a step are handed as the state) and d_est_u [cap][3], the control
+    // the controller was handed at the previous step (it drives the prior).  Nothing is allocated without a library
+    SetLib<pg_estimator, DevEstimator> ests{{"estimator", "pg_set_estimator_index"}};
+    real *d_est = nullptr, *d_est_u = nullptr;
+    bool est_fresh = true;                                        // no estimate of the previous step exists (new inputs, the clock restarted, or the library was cleared)
+    bool est_valid = false;                                       // d_est holds the estimate of a rollout step since the inputs were installed
+    real* est_hist = nullptr; int est_hist_steps = 0;             // pg_set_estimated_history_dev: one-shot, consumed by the next rollout call
+    int64_t stat_estimator_steps = 0;                             // read-only option "stat_estimator_steps"
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -337,9 +346,9 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen, h->d_dist_stream, h->d_dist_n, h->d_dist_w, h->d_dist_veh};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen, h->d_dist_stream, h->d_dist_n, h->d_dist_w, h->d_dist_veh, h->d_est, h->d_est_u};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release(); h->dists.release();
+    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release(); h->dists.release(); h->ests.release();
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
     if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
@@ -559,6 +568,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "stat_sensor_steps") return S(&h->stat_sensor_steps);
     if (n == "stat_actuator_steps") return S(&h->stat_actuator_steps);
     if (n == "stat_disturbance_steps") return S(&h->stat_disturbance_steps);
+    if (n == "stat_estimator_steps") return S(&h->stat_estimator_steps);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -637,7 +647,7 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
 }
 int pg_synchronize(pg_handle* h) { if (!h) return PG_ERR_INVALID; HIPCHK(h, hipStreamSynchronize(h->stream)); return PG_OK; }
 
-// ---- what the six libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances): one index rule and one install / clear / get protocol ----
+// ---- what the seven libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances, estimators): one index rule and one install / clear / get protocol ----
 // Installs the selection of `B` instances into a library of `n_sets`.  The WHOLE [capacity] array is written, entries beyond B as 0: never an address outside the library,
 // whatever an earlier, larger library left there
 static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, const int32_t* index) {
@@ -1096,6 +1106,85 @@ int pg_disturbance_response(pg_handle* h, int32_t step0, int32_t steps, double d
     return rc;
 }
 
+// ---- estimator library: the state the CONTROLLER of a rollout step reads, a fixed-gain observer on the sensor's output, xh = p + gain (y - p) per channel with p one step
+// of the controller's own model from the previous estimate (k_estimate).  Build-defined (the reference's node receives its estimate from the car).  No part of any QP's
+// structure: installing sets or an index resets nothing ----
+static const char* estimator_set_problem(const pg_estimator& s) {
+    static const char* const outside[6] = {"gain[0] (E) is outside [0, 1] or not finite", "gain[1] (N) is outside [0, 1] or not finite", "gain[2] (psi) is outside [0, 1] or not finite",
+                                           "gain[3] (Ux) is outside [0, 1] or not finite", "gain[4] (Uy) is outside [0, 1] or not finite", "gain[5] (r) is outside [0, 1] or not finite"};
+    for (int c = 0; c < 6; c++) if (!(s.gain[c] >= 0.0 && s.gain[c] <= 1.0)) return outside[c];      // (false for NaN as well)
+    if (s.predict != 0 && s.predict != 1) return "predict must be 0 or 1";
+    if (s.reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+static void fill_dev_estimator(DevEstimator& E, const pg_estimator& s) { E.predict = s.predict; for (int c = 0; c < 6; c++) E.gain[c] = (real)s.gain[c]; }
+int pg_set_estimator_sets(pg_handle* h, int32_t n_sets, const pg_estimator* sets) {
+    if (!h) return PG_ERR_INVALID;
+    // the buffers first: a library is never installed without them (a failed allocation leaves the handle as it was)
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t cap = (size_t)h->cfg.batch_capacity;
+    if (!h->d_est) HIPCHK(h, hipMalloc((void**)&h->d_est, cap * 6 * sizeof(real)));
+    if (!h->d_est_u) HIPCHK(h, hipMalloc((void**)&h->d_est_u, cap * 3 * sizeof(real)));
+    std::string why;                                            // (the message names the set and the field; the estimate persists)
+    return setlib_install(h, "pg_set_estimator_sets", h->ests, n_sets, sets, [&](const pg_estimator& s) -> const char* {
+        const char* f = estimator_set_problem(s);
+        if (!f) return nullptr;
+        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
+        return why.c_str();
+    }, fill_dev_estimator);
+}
+int pg_set_estimator_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    return index_install(h, (int)h->ests.sets.size(), h->ests.idx, B, index);
+}
+int pg_clear_estimator_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    const int rc = setlib_clear(h, h->ests); if (rc) return rc;
+    h->est_fresh = true; h->est_valid = false; h->est_hist = nullptr; h->est_hist_steps = 0;      // (a library installed later starts from its first measurement)
+    return PG_OK;
+}
+int pg_get_estimator_sets(pg_handle* h, int32_t* n_sets, pg_estimator* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    return setlib_get(h, "pg_get_estimator_sets", h->ests, n_sets, out, max_sets, index, B);
+}
+int pg_set_estimated_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
+    if (!h) return PG_ERR_INVALID;
+    if (!buf) { h->est_hist = nullptr; h->est_hist_steps = 0; return PG_OK; }
+    REQUIRE(h, steps >= 1, "pg_set_estimated_history_dev: steps >= 1 required");
+    if (h->ests.sets.empty()) { h->err = "pg_set_estimated_history_dev: no estimator library installed (the controller reads the sensor's output: record that)"; return PG_ERR_STATE; }
+    h->est_hist = (real*)buf; h->est_hist_steps = steps;
+    return PG_OK;
+}
+int pg_get_estimated_state(pg_handle* h, double* estimated) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->ests.sets.empty() || !h->est_valid || !h->d_est) { h->err = "pg_get_estimated_state: no rollout step under an estimator library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, estimated, h->d_est, (size_t)h->B * 6);
+}
+int pg_estimator_response(pg_handle* h, int32_t steps, double dt, const double* y, const double* u, double* xhat) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, steps >= 1 && dt > 0.0 && y && u && xhat, "pg_estimator_response: steps >= 1, dt > 0, the measurements, the controls and the output array required");
+    if (h->B <= 0) { h->err = "pg_estimator_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
+    if (h->ests.sets.empty()) { h->err = "pg_estimator_response: no estimator library installed"; return PG_ERR_STATE; }
+    if (index_covers(h, h->ests.sets.size(), h->ests.idx)) return PG_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = h->B;
+    const size_t ny = (size_t)steps * (size_t)B * 6, nu = (size_t)steps * (size_t)B * 3;
+    real* d = nullptr;                                           // scratch of the call: y, xhat [steps][B][6], u [steps][B][3] (the estimate lives in the lanes' registers)
+    HIPCHK(h, hipMalloc((void**)&d, (2 * ny + nu) * sizeof(real)));
+    int rc = up(h, d, y, ny);
+    if (!rc) rc = up(h, d + 2 * ny, u, nu);
+    if (!rc) {
+        hipLaunchKernelGGL(k_estimator_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)steps, (real)(dt / h->dc.nsub), h->ests.d,
+                           h->ests.sets.size() > 1 ? h->ests.idx.d : (const int*)nullptr, (const real*)d, (const real*)(d + 2 * ny), d + ny);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { h->err = std::string("pg_estimator_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
+    }
+    if (!rc) rc = down(h, xhat, d + ny, ny);
+    else (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -1167,7 +1256,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true; h->dist_fresh = true; h->dist_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true; h->dist_fresh = true; h->dist_valid = false; h->est_fresh = true; h->est_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1695,9 +1784,11 @@ static int rollout_ready(pg_handle* h) {
         if (index_covers(h, h->sens.sets.size(), h->sens.idx)) return PG_ERR_STATE;
         const size_t cap = cap_of(h);
         if (!h->d_meas) HIPCHK(h, hipMalloc((void**)&h->d_meas, cap * 6 * sizeof(real)));
-        if (h->tracking && !h->d_sep_true) HIPCHK(h, hipMalloc((void**)&h->d_sep_true, cap * 4 * sizeof(real)));
         const int rc = sensor_streams_sync(h); if (rc) return rc;
     }
+    if (!h->ests.sets.empty() && index_covers(h, h->ests.sets.size(), h->ests.idx)) return PG_ERR_STATE;
+    // (under either of the two the controller's (s, e) is not the truth's: launch_track projects the true state once more)
+    if (h->tracking && !h->d_sep_true && (!h->sens.sets.empty() || !h->ests.sets.empty())) HIPCHK(h, hipMalloc((void**)&h->d_sep_true, cap_of(h) * 4 * sizeof(real)));
     if (!h->acts.sets.empty()) {
         if (index_covers(h, h->acts.sets.size(), h->acts.idx)) return PG_ERR_STATE;
         const size_t cap = cap_of(h);
@@ -1758,22 +1849,40 @@ static int launch_actuate(pg_handle* h, int step, int k, double dt, const ActHis
 // the sensor library (the host knows whether one is installed: that alone adds k_measure to a rollout step).  sensor_take_history: the one-shot registration of
 // pg_set_measured_history_dev, consumed by the rollout call that starts now
 static bool sensor_lib_on(const pg_handle* h) { return !h->sens.sets.empty(); }
+// the estimator library (installed: k_estimate joins a rollout step, behind k_measure).  estimator_take_history: the one-shot registration of pg_set_estimated_history_dev
+static bool estimator_lib_on(const pg_handle* h) { return !h->ests.sets.empty(); }
+struct EstHist { real* buf; int steps; };
+static EstHist estimator_take_history(pg_handle* h) { const EstHist e{h->est_hist, h->est_hist_steps}; h->est_hist = nullptr; h->est_hist_steps = 0; return e; }
 struct MeasHist { real* buf; int steps; };
 static MeasHist sensor_take_history(pg_handle* h) { const MeasHist m{h->meas_hist, h->meas_hist_steps}; h->meas_hist = nullptr; h->meas_hist_steps = 0; return m; }
 // the controller's side of one rollout step: the node gate (node rollout) and the compute calls.  Under a sensor library k_measure writes the measured state of clock step
 // `step` first, and the handle's state pointer names THAT buffer while the gate and the compute kernels are queued -- they all take the state from the handle --, then the true
-// one again for the summary, the records and the plant: no copy, no restore launch, no kernel changed.  Without a library: the gate and the compute calls, nothing else
+// one again for the summary, the records and the plant: no copy, no restore launch, no kernel changed.  Under an estimator library k_estimate follows (on the measured state, or on the true one without a sensor library) and
+// the pointer names d_est in the same way: the gates, the projection, the nodes, the QP's q_curr, the HJI relative state and the policy selection all follow the estimate.
+// Without either library: the gate and the compute calls, nothing else
 static int node_gate(pg_handle* h, const uint8_t* pre_flag);
-static int rollout_compute(pg_handle* h, int step, int k, const MeasHist& mh, bool gate, const uint8_t* pre_flag) {
+static int rollout_compute(pg_handle* h, int step, int k, double dt, const MeasHist& mh, const EstHist& eh, bool gate, const uint8_t* pre_flag) {
     int rc;
-    if (!sensor_lib_on(h)) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
+    if (!sensor_lib_on(h) && !estimator_lib_on(h)) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
     const int B = h->B;
-    const SensorLib lib{h->sens.d, h->sens.sets.size() > 1 ? h->sens.idx.d : (const int*)nullptr, h->d_sens_stream, (unsigned long long)h->sens_seed};
-    hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, h->d_meas, (mh.buf && k < mh.steps) ? mh.buf + (size_t)k * B * 6 : (real*)nullptr);
-    LAUNCH_CHECK(h);
-    h->meas_valid = true; h->stat_sensor_steps++;
     real* const true_state = h->d_state;
-    h->d_state = h->d_meas;
+    real* seen = true_state;                                     // what the gate and the compute calls read: the sensor's output, or the estimator's on top of it
+    if (sensor_lib_on(h)) {
+        const SensorLib lib{h->sens.d, h->sens.sets.size() > 1 ? h->sens.idx.d : (const int*)nullptr, h->d_sens_stream, (unsigned long long)h->sens_seed};
+        hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, h->d_meas, (mh.buf && k < mh.steps) ? mh.buf + (size_t)k * B * 6 : (real*)nullptr);
+        LAUNCH_CHECK(h);
+        h->meas_valid = true; h->stat_sensor_steps++;
+        seen = h->d_meas;
+    }
+    if (estimator_lib_on(h)) {      // (h->d_control: what the compute calls below are handed as current_control -- the command, or d_seen under an actuator library with feedback)
+        const EstimatorLib lib{h->ests.d, h->ests.sets.size() > 1 ? h->ests.idx.d : (const int*)nullptr, h->d_est, h->d_est_u};
+        hipLaunchKernelGGL(k_estimate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)h->est_fresh, (real)(dt / h->dc.nsub), lib, (const real*)seen,
+                           (const real*)h->d_control, (eh.buf && k < eh.steps) ? eh.buf + (size_t)k * B * 6 : (real*)nullptr);
+        LAUNCH_CHECK(h);
+        h->est_fresh = false; h->est_valid = true; h->stat_estimator_steps++;
+        seen = h->d_est;
+    }
+    h->d_state = seen;
     rc = gate ? node_gate(h, pre_flag) : PG_OK;
     if (!rc) rc = step_compute(h);
     h->d_state = true_state;
@@ -1787,7 +1896,7 @@ static int launch_track(pg_handle* h, int step) {
     if (!h->tracking) { h->track_fresh = true; return PG_OK; }      // (off: no launch; steps that went unseen must not be continued when it comes back on)
     const int B = h->B;
     const real* sep = h->d_sep;
-    if (sensor_lib_on(h)) {      // d_sep holds the projection of the MEASURED state (the node publishes its (s, e)): the summary describes the true one, projected once more
+    if (sensor_lib_on(h) || estimator_lib_on(h)) {      // d_sep holds the projection of the MEASURED / ESTIMATED state (the node publishes its (s, e)): the summary describes the true one, projected once more
         hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep_true, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
                            (double*)nullptr, (int*)nullptr, 0, (int*)nullptr, (int*)nullptr, 0);
         LAUNCH_CHECK(h);
@@ -1801,7 +1910,7 @@ static int launch_track(pg_handle* h, int step) {
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true; h->dist_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true; h->dist_fresh = true; h->est_fresh = true;
     }
     return PG_OK;
 }
@@ -1817,7 +1926,7 @@ static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_di
     else if (plant_lib_on(h)) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
     else hipLaunchKernelGGL(uniform, grid, block, 0, h->stream, args...);
 }
-// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance) are taken (THIS call consumes them, also when it fails below), check_ready,
+// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated) are taken (THIS call consumes them, also when it fails below), check_ready,
 // the entry point's own precondition (coupled_only: the message for a lateral handle, nullptr: none), the shared arguments, rollout_ready, the node's buffers (node: the
 // rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records(k) ahead of the compute calls, the
 // controller's side (:90-93, on the measured state under a sensor library), the tracking summary, the clock index, then finish(k, step): the step's last launch, which moves
@@ -1830,6 +1939,7 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
     const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};
     const ActHist ah = h ? actuator_take_history(h) : ActHist{nullptr, nullptr, 0, 0};
     const DistHist dh = h ? disturbance_take_history(h) : DistHist{nullptr, 0};
+    const EstHist eh = h ? estimator_take_history(h) : EstHist{nullptr, 0};
     int rc = check_ready(h); if (rc) return rc;
     if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
     if (a.node && actuator_lib_on(h)) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
@@ -1846,7 +1956,7 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
         if (act) h->d_control = h->d_plant_u;
         rc = records(k);
         if (act) h->d_control = h->act_feedback ? h->d_seen : command;
-        if (!rc) rc = rollout_compute(h, step, k, mh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
+        if (!rc) rc = rollout_compute(h, step, k, a.dt, mh, eh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
         h->d_control = command;
         if (rc || (rc = launch_track(h, step))) return rc;
         h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)

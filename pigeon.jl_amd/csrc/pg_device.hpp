@@ -772,4 +772,24 @@ PG_DEV void disturbance_advance(const DevDisturbance& D, uint64_t seed, uint64_t
     w[3] = D.mu_scale;
 }
 
+// ---- estimator of the rollouts (pg_set_estimator_sets; build-defined: the reference's node receives its estimate from the car) ----
+// one set of an estimator library in the arithmetic type of the build: whether the prior is one step of the controller's model (1) or the previous estimate (0), and the
+// fixed gain per channel of (E, N, psi, Ux, Uy, r)
+struct DevEstimator { int predict; real gain[6]; };
+PG_DEV bool estimator_passes(const DevEstimator& E) {
+    bool all_one = true;
+    for (int c = 0; c < 6; c++) all_one = all_one && E.gain[c] == real(1.0);
+    return all_one;
+}
+// The correction of one instance and one clock step: xh[c] = p[c] + gain[c] (y[c] - p[c]), a plain difference on every channel (psi is the unwrapped integral of r).
+// gain == 1 COPIES y[c] and gain == 0 COPIES p[c] (no arithmetic: -0.0 and NaN payloads survive).  No contraction: the product and the two sums are rounded once each, as
+// the numpy twin rounds them
+PG_DEV void estimator_correct(const DevEstimator& E, const real p[6], const real y[6], real xh[6]) {
+#pragma clang fp contract(off)
+    for (int c = 0; c < 6; c++) {
+        const real g = E.gain[c];
+        xh[c] = g == real(1.0) ? y[c] : (g == real(0.0) ? p[c] : p[c] + g * (y[c] - p[c]));
+    }
+}
+
 }  // namespace pg

@@ -1209,6 +1209,66 @@ __global__ __launch_bounds__(64) void k_disturbance_response(int B, int step0, i
     }
 }
 
+// Estimator library (pg_set_estimator_sets): the state the CONTROLLER of a rollout step reads, a fixed-gain observer between the sensor and the controller.  The law for
+// one instance and one clock step -- y: the sensor's output of the step (the measured state, or the true one without a sensor library); u: the control the controller was
+// handed at the previous step; xh (in: the estimate of the previous step, out: this step's):
+//   prior  p = advance_ego(xh, u) over one step of nsub sub-steps of length h -- the CONTROLLER's model C.veh, never the plant library's, Fx = Fxf + Fxr as k_advance
+//          forms it -- when the set's predict == 1;  p = xh when predict == 0 (each channel an exponential low-pass of y)
+//   xh     = p + gain (y - p) per channel (estimator_correct, pg_device.hpp: gain 1 copies y, gain 0 copies p)
+//   xh = y when `fresh` (no estimate of the previous step exists) and for an instance whose prior has a non-finite component: its estimator starts again
+// A lane whose six gains are all 1 copies y and runs no prediction: the identity set leaves the bits of the handle without a library.  The RK4 sits behind a branch of the
+// lane, so a wavefront that mixes such lanes with observer lanes runs it for the latter only
+PG_DEV void estimator_advance(const DevCfg& C, const DevEstimator& E, bool fresh, real h, int nsub, const real y[6], const real u[3], real xh[6]) {
+    if (fresh || estimator_passes(E)) { for (int c = 0; c < 6; c++) xh[c] = y[c]; return; }
+    real p[6] = {xh[0], xh[1], xh[2], xh[3], xh[4], xh[5]};
+    if (E.predict) advance_ego(C, p, u[0], u[1] + u[2], h, nsub);
+    bool finite = true;
+    for (int c = 0; c < 6; c++) finite = finite && (p[c] - p[c] == real(0.0));      // (false for +-Inf and NaN)
+    if (!finite) { for (int c = 0; c < 6; c++) xh[c] = y[c]; return; }
+    estimator_correct(E, p, y, xh);
+}
+// One rollout step under the library, lane = instance, one wavefront per block: queued behind k_measure (when there is one) and ahead of the node gate and the compute
+// calls, which are handed `est` as the state.  Reads y [B][6], est [cap][6] and est_u [cap][3] (unless `fresh`), `control` [B][3] (what the compute calls of THIS step are
+// handed as current_control), the instance's record (copied into registers once) and the index; writes est, the step's row of the history when one is registered, and
+// then this step's control into est_u: the next step's prior is driven by it.  idx == nullptr: a library of one.  h = dt / nsub, rounded by the host as k_advance rounds it
+struct EstimatorLib { const DevEstimator* sets; const int* idx; real* est; real* est_u; };
+__global__ __launch_bounds__(64) void k_estimate(DevCfg C, int B, int fresh, real h, EstimatorLib lib, const real* __restrict__ y, const real* __restrict__ control,
+                                                 real* __restrict__ hist) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevEstimator E = lib.sets[lib.idx ? lib.idx[b] : 0];
+    real yb[6], xh[6] = {real(0.0), real(0.0), real(0.0), real(0.0), real(0.0), real(0.0)}, u[3] = {real(0.0), real(0.0), real(0.0)};
+    for (int c = 0; c < 6; c++) yb[c] = y[(size_t)b * 6 + c];
+    if (!fresh) {
+        for (int c = 0; c < 6; c++) xh[c] = lib.est[(size_t)b * 6 + c];
+        for (int j = 0; j < 3; j++) u[j] = lib.est_u[(size_t)b * 3 + j];
+    }
+    estimator_advance(C, E, fresh != 0, h, C.nsub, yb, u, xh);
+    for (int c = 0; c < 6; c++) {
+        lib.est[(size_t)b * 6 + c] = xh[c];
+        if (hist) hist[(size_t)b * 6 + c] = xh[c];
+    }
+    for (int j = 0; j < 3; j++) lib.est_u[(size_t)b * 3 + j] = control[(size_t)b * 3 + j];
+}
+// pg_estimator_response: the estimates xhat [steps][B][6] of a caller's measurement sequence y [steps][B][6] and control sequence u [steps][B][3] (u[k]: the control the
+// controller is handed at step k; step k's prior is driven by u[k - 1]) through the function k_estimate calls, from a fresh state kept in registers (lane = instance; the
+// steps in order)
+__global__ __launch_bounds__(64) void k_estimator_response(DevCfg C, int B, int steps, real h, const DevEstimator* __restrict__ sets, const int* __restrict__ idx,
+                                                           const real* __restrict__ y, const real* __restrict__ u, real* __restrict__ xhat) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevEstimator E = sets[idx ? idx[b] : 0];
+    real xh[6] = {real(0.0), real(0.0), real(0.0), real(0.0), real(0.0), real(0.0)}, up[3] = {real(0.0), real(0.0), real(0.0)};
+    for (int k = 0; k < steps; k++) {
+        const size_t at = (size_t)k * B + b;
+        real yb[6];
+        for (int c = 0; c < 6; c++) yb[c] = y[at * 6 + c];
+        estimator_advance(C, E, k == 0, h, C.nsub, yb, up, xh);
+        for (int c = 0; c < 6; c++) xhat[at * 6 + c] = xh[c];
+        for (int j = 0; j < 3; j++) up[j] = u[at * 3 + j];
+    }
+}
+
 // ==================================================================================================================
 // Decoupled (lateral) formulation: decoupled_lat_long.jl.  The lateral QP (state (Uy, r, dpsi, e), input delta) is EMBEDDED in the
 // 8-state stage structure k_solve works on: x = (0, Ux_dummy, Uy, r, dpsi, e, delta, 0) with identity dynamics, zero cost and

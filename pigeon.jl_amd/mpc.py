@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -412,6 +412,62 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_set_disturbance_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_disturbance_history_dev")
         return {"disturbance": buf}
 
+    # ---- the ESTIMATOR of the rollouts, per instance (a fixed-gain observer between the sensor and the controller): a library of pg_estimator and a per-instance selection ----
+    @classmethod
+    def pack_estimators(cls, sets):
+        """estimator dicts (vehicles.estimator(**overrides); missing fields: the identity's) or pg_estimator structures -> a ctypes array of pg_estimator."""
+        def fill(rec, v):
+            e = _identity_estimator(**v)
+            for name in ("predict", "reserved"):
+                if int(e[name]) != e[name]:
+                    raise ValueError(f"{name} = {e[name]} is not a whole number")
+                setattr(rec, name, int(e[name]))
+            rec.gain[:] = e["gain"]
+        return cls._pack(_lib.pg_estimator, sets, fill)
+
+    def set_estimators(self, sets, index=None):
+        """What the controller of simulate_ / simulate_safety_ / simulate_node_ reads in place of the sensor's output (pg_set_estimator_sets): per channel of (E, N, psi, Ux,
+        Uy, r) estimate = prior + gain (measurement - prior), the prior one step of the controller's own model from the previous estimate (predict=1) or that estimate
+        itself (predict=0).  One set (dict / structure) for the whole batch, or a list of sets selected per instance with `index`.  The plant, the records and the
+        summaries keep the truth.  Resets nothing."""
+        self._set_sets("estimator", _lib.pg_estimator, self.pack_estimators, sets, index)
+
+    def set_estimator_index(self, index):
+        self._set_index("estimator", index)
+
+    def clear_estimators(self):
+        self._chk(self.lib.pg_clear_estimator_sets(self.h), "pg_clear_estimator_sets")
+
+    def get_estimators(self):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        return self._get_sets("estimator", _lib.pg_estimator, lambda r: {"predict": r.predict, "reserved": r.reserved, "gain": list(r.gain)})
+
+    def estimated_state(self):
+        """[B][6]: what the controller read at the last rollout step under an estimator library (pg_get_estimated_state)."""
+        e = np.zeros((self.B, 6))
+        self._chk(self.lib.pg_get_estimated_state(self.h, _p(e)), "pg_get_estimated_state")
+        return e
+
+    def estimator_response(self, y, u, dt):
+        """The law alone, on the device through the function the rollouts call (pg_estimator_response): measurements y [steps][B][6] and controls u [steps][B][3] (u[k]: what
+        the controller is handed at step k; step k's prior is driven by u[k - 1]) -> estimates [steps][B][6] under the installed library and index, from a fresh state.
+        B is the batch of the inputs last installed."""
+        y = _f64(y).reshape(-1, self.B, 6); u = _f64(u).reshape(-1, self.B, 3)
+        if u.shape[0] != y.shape[0]:
+            raise ValueError(f"y has {y.shape[0]} steps and u has {u.shape[0]}")
+        out = np.zeros_like(y)
+        self._chk(self.lib.pg_estimator_response(self.h, y.shape[0], C.c_double(dt), _p(y), _p(u), _p(out)), "pg_estimator_response")
+        return out
+
+    def _estimated_hist(self, estimated, steps):
+        """registers a [steps][B][6] device record of the estimate with the next rollout call (pg_set_estimated_history_dev); None unless asked for"""
+        if not estimated:
+            return None
+        torch, tdt, dev = self._torch()
+        buf = torch.empty(int(steps), self.B, 6, dtype=tdt, device=dev)
+        self._chk(self.lib.pg_set_estimated_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_estimated_history_dev")
+        return buf
+
     def _torch(self):
         """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""
         import torch
@@ -506,11 +562,12 @@ class BatchedTrajectoryTrackingMPC:
 
     HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
 
-    def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True):
+    def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True, estimated=False):
         """The rollouts' shared plumbing.  Device records [steps][B] + shapes[name] in the library's element type and one int32 record `int_record` (record=True), the scripted
         human [steps][B][2], the measured history, under an actuator library the applied / command histories [steps][B][3] (record=True; they join the records as "applied"
         and "command"), under a disturbance library the history of w [steps][B][4] (record=True; "disturbance"); call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
-        ((state, control, t[, other]), the records as fp64 / int32 numpy arrays or None, (measured history,) or ())."""
+        ((state, control, t[, other]), the records as fp64 / int32 numpy arrays or None, (measured history,) or () followed by (estimated history,) or () -- estimated=True
+        registers the [steps][B][6] record of the estimate, as measured=True registers the measured one)."""
         assert human in self.HUMAN_MODES, human
         hu = None; hist = {}
         if human == "script":
@@ -524,6 +581,7 @@ class BatchedTrajectoryTrackingMPC:
             if int_record:
                 hist[int_record] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
         mbuf = self._measured_hist(measured, steps)
+        ebuf = self._estimated_hist(estimated, steps)
         abuf = self._actuator_hists(record, steps)
         abuf.update(self._disturbance_hist(record, steps))
         call(lambda t: C.c_void_p(t.data_ptr()) if t is not None else None, hu, hist)
@@ -534,32 +592,35 @@ class BatchedTrajectoryTrackingMPC:
         out = {k: v.cpu().numpy().astype(np.float64 if k in shapes else np.int32) for k, v in hist.items()} if record else None
         for k, v in abuf.items():
             out[k] = v.cpu().numpy().astype(np.float64)
-        return (s, c, t, o) if other else (s, c, t), out, () if mbuf is None else (mbuf.cpu().numpy().astype(np.float64),)
+        tail = tuple(b.cpu().numpy().astype(np.float64) for b in (mbuf, ebuf) if b is not None)
+        return (s, c, t, o) if other else (s, c, t), out, tail
 
-    def simulate_(self, steps, dt=0.01, record=False, measured=False):
+    def simulate_(self, steps, dt=0.01, record=False, measured=False, estimated=False):
         """simulate (model_predictive_control.jl:80-100) on the device from the inputs last installed; returns (state, control, t) after `steps`
         steps and, with record=True, the histories qs [steps][B][6], us [steps][B][3] (the values pushed at :88-89).  measured=True (a sensor library is installed)
-        appends the measured history [steps][B][6] to what is returned.  Under an actuator library `us` is the APPLIED control, and record=True appends
+        appends the measured history [steps][B][6] to what is returned, estimated=True (an estimator library is installed) the estimated history [steps][B][6] behind it.
+        Under an actuator library `us` is the APPLIED control, and record=True appends
         {"command": [steps][B][3], "applied": [steps][B][3]} as the last element; under a disturbance library that last dictionary holds "disturbance": w [steps][B][4]
         (it is appended for either library)."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_dev(self.h, steps, C.c_double(dt), ptr(hist.get("state")), ptr(hist.get("control"))), "pg_simulate_dev")
-        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,)}, None, call, other=False)
+        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,)}, None, call, other=False, estimated=estimated)
         act = {k: out[k] for k in ("command", "applied", "disturbance") if record and k in out}
         act = (act,) if act else ()
         return st + ((out["state"], out["control"]) if record else (None, None)) + tail + act
 
-    def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False, measured=False):
+    def simulate_safety_(self, steps, dt=0.01, use_HJI_policy=True, human="hold", human_u=None, record=False, measured=False, estimated=False):
         """Safety rollout (pg_simulate_safety_dev): simulate with the control the ROS node sends (ros_integration.jl:114-124) fed back, against an other car that moves.
         human: "hold" (omega, a) = (0, 0), "worst" optimal_disturbance (HJI_computation.jl:90-131), "script" human_u [steps][B][2] = (omega, a).  Returns (state, control, t,
         other) after `steps` steps and, with record=True, a dict of histories: state [steps][B][6], control [steps][B][3], other [steps][B][4], human [steps][B][2], V [steps][B],
         source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step.
-        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned.  Under an actuator library "control" is the APPLIED
+        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned, estimated=True (an estimator library is installed) the
+        estimated history [steps][B][6] behind it.  Under an actuator library "control" is the APPLIED
         control and the dict also holds "command" and "applied" [steps][B][3]; under a disturbance library it holds "disturbance": w [steps][B][4]."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
                                                       *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
-        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,), "other": (4,), "human": (2,), "V": ()}, "source", call, human, human_u)
+        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "control": (3,), "other": (4,), "human": (2,), "V": ()}, "source", call, human, human_u, estimated=estimated)
         return st + ((out,) if record else ()) + tail
 
     def safety_summary(self):
@@ -591,17 +652,18 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_get_state(self.h, None, _p(c), None), "pg_get_state")
         return cmd.cpu().numpy().astype(np.float64), se.cpu().numpy().astype(np.float64), ev.cpu().numpy(), c
 
-    def simulate_node_(self, steps, dt=0.01, use_HJI_policy=False, human="hold", human_u=None, pre_flag=None, record=False, measured=False):
+    def simulate_node_(self, steps, dt=0.01, use_HJI_policy=False, human="hold", human_u=None, pre_flag=None, record=False, measured=False, estimated=False):
         """The node's closed loop (pg_simulate_node_dev): per step the gates, the compute calls, the callback's decision (NaN fallback included), the ego plant driven by the
         APPLIED command of the step's start, the other car as simulate_safety_.  pre_flag [steps][B] (None: engaged).  Returns (state, message, t, other, applied) after `steps`
         steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event).
-        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned.  Under a disturbance library the dict also holds
+        measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned, estimated=True (an estimator library is installed) the
+        estimated history [steps][B][6] behind it.  Under a disturbance library the dict also holds
         "disturbance": w [steps][B][4]."""
         def call(ptr, hu, hist):
             pf = self._pre_flag_dev(pre_flag, (steps, self.B))
             self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),
                                                     *(ptr(hist.get(k)) for k in ("state", "applied", "event", "V"))), "pg_simulate_node_dev")
-        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "applied": (3,), "V": ()}, "event", call, human, human_u)
+        st, out, tail = self._rollout(steps, record, measured, {"state": (6,), "applied": (3,), "V": ()}, "event", call, human, human_u, estimated=estimated)
         a = np.zeros((self.B, 3))
         self._chk(self.lib.pg_get_node_state(self.h, _p(a), None, None), "pg_get_node_state")
         return st + (a,) + ((out,) if record else ()) + tail

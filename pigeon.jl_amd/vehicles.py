@@ -1,5 +1,6 @@
 """X1 parameter dictionary — mirrors /root/reference/src/vehicles.jl:1-59 (same keys, same formulas)."""
 import math
+import numbers
 
 
 X1_BASE_FIELDS = ("G", "mfl", "mfr", "mrl", "mrr", "Ixx", "Iyy", "Izz", "L", "d", "hf", "hr", "h1", "mu", "Caf", "Car", "Fx_max", "Px_max", "Cd0", "Cd1", "Cd2",
@@ -89,3 +90,32 @@ def disturbance(**overrides):
             raise KeyError(f"{k} is not a field of a disturbance set: {DISTURBANCE_FIELDS}")
         d[k] = v
     return d
+
+
+ESTIMATOR_FIELDS = ("predict", "reserved", "gain")
+ESTIMATOR_CHANNELS = ("E", "N", "psi", "Ux", "Uy", "r")
+
+
+def estimator(**overrides):
+    """One estimator set for set_estimators (pg_estimator).  estimator() is the identity -- every gain 1: the controller reads the sensor's output itself --, which reproduces
+    the handle without a library bit for bit; estimator(gain=0.2) is the fixed-gain observer with that gain on every channel and the controller's model as the prior
+    (predict=1), estimator(gain=[1, 1, 0.2, 0.2, 0, 0.2]) sets the channels (E, N, psi, Ux, Uy, r) one by one, predict=0 makes every channel an exponential low-pass of the
+    measurement.  Build-defined: the reference has no estimator."""
+    e = dict(predict=1, reserved=0, gain=[1.0] * 6)
+    for k, v in overrides.items():
+        if k not in e:
+            raise KeyError(f"{k} is not a field of an estimator set: {ESTIMATOR_FIELDS}")
+        e[k] = v
+    g = e["gain"]
+    if isinstance(g, dict):
+        for c in g:
+            if c not in ESTIMATOR_CHANNELS:
+                raise KeyError(f"{c} is not a channel of an estimator set: {ESTIMATOR_CHANNELS}")
+        e["gain"] = [float(g.get(c, 1.0)) for c in ESTIMATOR_CHANNELS]
+    elif isinstance(g, numbers.Real):                      # (numpy scalars included)
+        e["gain"] = [float(g)] * 6
+    else:
+        e["gain"] = [float(x) for x in g]
+        if len(e["gain"]) != 6:
+            raise ValueError(f"gain has {len(e['gain'])} entries, not one per channel of {ESTIMATOR_CHANNELS}")
+    return e
