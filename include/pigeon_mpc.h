@@ -393,6 +393,61 @@ int pg_set_estimated_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
  * steps >= 1, dt > 0; PG_ERR_STATE without inputs, without a library or with an index that does not cover the batch */
 int pg_estimator_response(pg_handle* h, int32_t steps, double dt, const double* y, const double* u, double* xhat);
 
+/* Human sets: the DRIVER OF THE OTHER CAR in pg_simulate_safety_dev and pg_simulate_node_dev, per instance -- which kind of driver the deployed law keeps V > 0 against, as
+ * ONE batch with the other seven axes.  A library of pg_human and a per-instance selection, shaped like pg_set_disturbance_sets (a seed and 64-bit stream ids of its own).
+ * BUILD-DEFINED: the reference only receives the other car from ROS.
+ * With a library installed the two rollouts queue one lane-per-instance launch (k_human) per step, behind the step's compute calls and tracking summary -- mode 1 reads the
+ * step's relative state and HJI lookup -- and ahead of the launch that moves the plants, which is handed the result as a script (its human_mode = 2: it records and
+ * integrates what it is handed).  Per instance at clock step k (the step index of first_breach, first_exit and the sensor draws):
+ *   not active (k < step_on, or step_off >= 0 and k >= step_off):   u_k = (0, 0)
+ *   active, deciding -- (k - step_on) % hold_steps == 0, or no u of step k - 1 exists (the clock restarted, the first step after a library was installed on a handle that
+ *   had none, the first step after pg_clear_human_sets):
+ *       raw   = (0, 0)                                   mode 0
+ *             = what human_mode = 1 applies               mode 1: optimal_disturbance at the step's relative state; (0, 0) without a grid, on a decoupled handle and where
+ *                                                         the other car's speed is <= 0
+ *             = human_u_dev[k][b]                         mode 2
+ *             = (sigma[0] n_w, sigma[1] n_a)              mode 3: n is the unit-variance AR(1) of the gust (pg_disturbance: n_k = z_k on a missing state or tau == 0, else
+ *                                                         rho n_{k-1} + sqrt(-expm1(-2 dt / tau)) z_k, rho = exp(-dt / tau)), z = Box-Muller of words (x0, x1) of Philox
+ *                                                         block 3, counter (k, 3, stream_lo, stream_hi), key = THIS library's seed (blocks 0 to 2 are the sensor's and the
+ *                                                         gust's).  n advances at every step for an instance whose set has mode 3, active or not.  sigma == 0: exactly 0
+ *       u[c]  = gain[c] raw[c]  (gain[c] == 1 COPIES), then |omega| <= omega_max and a_min <= a <= a_max by compare-and-select: a value inside the limits keeps its bits
+ *   active, not deciding:                                           u_k = u_{k-1}, copied
+ * IDENTITY: {m, 1, 0, -1, {1, 1}, +Inf, -Inf, +Inf, {0, 0}, 0} reproduces a rollout called with human_mode = m on a handle without a library bit for bit, m in {0, 1, 2}.
+ * Under a library the rollouts' human_mode argument is still validated but the sets decide; human_u_dev is required exactly when an installed set has mode 2
+ * (PG_ERR_INVALID otherwise).  pg_simulate_dev, pg_step*, the phase calls and pg_node_step_dev ignore the library.  The driver's state (u_{k-1}, n) restarts with the
+ * rollout clock and continues across calls; installing sets, an index, a seed or streams over an installed library resets nothing.
+ * Lifetime, index rule and errors as pg_set_plant_sets.  PG_ERR_INVALID (the handle is left unchanged; the message names the set and the field): mode outside 0..3;
+ * hold_steps < 1; step_on < 0; a gain outside [0, 1] or not finite; a NaN limit, omega_max < 0, a_min > 0 or a_max < 0; a sigma or tau negative or not finite.
+ * Without a library: nothing allocated, the launches of before; the read-only option "stat_human_steps" (rollout steps that ran under a library) stays 0. */
+typedef struct pg_human {
+    int32_t mode;                  /* 0 hold, 1 worst case (optimal_disturbance), 2 the caller's script, 3 seeded random */
+    int32_t hold_steps;            /* >= 1: the driver decides at active steps with (k - step_on) % hold_steps == 0 and keeps (omega, a) in between */
+    int32_t step_on, step_off;     /* active at clock steps k with step_on <= k and (step_off < 0 or k < step_off), as pg_disturbance */
+    double  gain[2];               /* factor on the decided (omega, a), each in [0, 1] */
+    double  omega_max;             /* |omega| <= omega_max; +Inf: no limit */
+    double  a_min, a_max;          /* a_min <= a <= a_max, a_min <= 0 <= a_max; -Inf / +Inf: no limit */
+    double  sigma[2];              /* mode 3: stationary standard deviation of (omega, a) */
+    double  tau;                   /* mode 3: correlation time (s); 0 = white */
+} pg_human;                        /* 80 bytes */
+int pg_set_human_sets(pg_handle* h, int32_t n_sets, const pg_human* sets);
+int pg_set_human_index(pg_handle* h, int32_t B, const int32_t* index);           /* index[b] in [0, n_sets) */
+/* key of the mode-3 draws and the stream id per instance, as pg_set_disturbance_seed (stream == NULL: stream[b] = b); a library of its own seed: 0 until set */
+int pg_set_human_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream);
+int pg_clear_human_sets(pg_handle* h);                                           /* back to the rollouts' human_mode; the driver's state is dropped */
+/* the installed library, as pg_get_plant_sets */
+int pg_get_human_sets(pg_handle* h, int32_t* n_sets, pg_human* out, int32_t max_sets, int32_t* index, int32_t B);
+/* u [B][2] = (omega, a) of the last rollout step under a library; PG_ERR_STATE before the first one since the inputs were installed */
+int pg_get_human_state(pg_handle* h, double* u);
+/* the NEXT rollout call writes (omega, a) of its step k < steps to buf[k][B][2] (library element type); one-shot -- that call consumes the registration whether it succeeds or
+ * returns an error --; NULL cancels.  PG_ERR_STATE without a library.  (The node rollout has no human history of its own.) */
+int pg_set_human_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
+/* the law alone, ON THE DEVICE through the function k_human calls (k_human_response): x7 [steps][B][7] and vg8 [steps][B][8] (V, then the gradient) on the host, script
+ * [steps][B][2] or NULL (required when an installed set has mode 2) -> u_out [steps][B][2] of the clock steps [step0, step0 + steps), with the installed library, index, seed
+ * and streams over the current batch B (pg_set_inputs*), from a fresh state at step0.  Mode 1 reads the grid as the rollouts do (none, or a decoupled handle: (0, 0)).
+ * Touches neither the rollout clock nor the handle's driver state.  step0 >= 0, steps >= 1, dt > 0; PG_ERR_STATE without inputs, without a library or with an index that
+ * does not cover the batch */
+int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
@@ -572,6 +627,7 @@ int pg_synchronize(pg_handle* h);
  *     "stat_actuator_steps"      (read-only) rollout steps whose plant launch ran under an actuator library (k_actuate launches) since pg_create
  *     "stat_disturbance_steps"   (read-only) rollout steps that ran under a disturbance library (k_disturb launches) since pg_create
  *     "stat_estimator_steps"     (read-only) rollout steps that ran under an estimator library (k_estimate launches) since pg_create
+ *     "stat_human_steps"         (read-only) rollout steps that ran under a human library (k_human launches) since pg_create
  *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact

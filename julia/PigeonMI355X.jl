@@ -397,6 +397,66 @@ function estimator_response(mpc::BatchedTrajectoryTrackingMPC, y::Array{Float64,
     xhat
 end
 
+# Human sets (pg_set_human_sets ...): the driver of the other car in the safety and node rollouts, per instance.  NOT EXECUTED in the build container, like the rest of this file.
+
+"One driver of the other car (pg_human): mode 0 hold, 1 worst case (optimal_disturbance), 2 the caller's script, 3 seeded random; a decision is kept for hold_steps steps, counted from step_on; active at clock steps step_on <= k < step_off (step_off < 0: open-ended); gain on the decided (omega, a) in [0, 1]; |omega| <= omega_max, a_min <= a <= a_max (Inf: no limit); sigma and tau of the random driver.  PgHuman(mode = m) for m in 0:2 is the identity: the rollouts' human_mode = m, bit for bit."
+struct PgHuman
+    mode::Int32
+    hold_steps::Int32
+    step_on::Int32
+    step_off::Int32
+    gain::NTuple{2,Float64}
+    omega_max::Float64
+    a_min::Float64
+    a_max::Float64
+    sigma::NTuple{2,Float64}
+    tau::Float64
+end
+PgHuman(; mode=0, hold_steps=1, step_on=0, step_off=-1, gain=(1.0, 1.0), omega_max=Inf, a_min=-Inf, a_max=Inf, sigma=(0.0, 0.0), tau=0.0) =
+    PgHuman(Int32(mode), Int32(hold_steps), Int32(step_on), Int32(step_off), gain isa Real ? (Float64(gain), Float64(gain)) : NTuple{2,Float64}(Float64.(Tuple(gain))), Float64(omega_max),
+            Float64(a_min), Float64(a_max), sigma isa Real ? (Float64(sigma), Float64(sigma)) : NTuple{2,Float64}(Float64.(Tuple(sigma))), Float64(tau))
+"the layout include/pigeon_mpc.h states (80 bytes): checked before the first install"
+function check_human_layout()
+    off(f) = Int(fieldoffset(PgHuman, Base.fieldindex(PgHuman, f)))
+    (sizeof(PgHuman), off(:mode), off(:hold_steps), off(:step_on), off(:step_off), off(:gain), off(:omega_max), off(:a_min), off(:a_max), off(:sigma), off(:tau)) ==
+        (80, 0, 4, 8, 12, 16, 32, 40, 48, 56, 72) || error("PigeonMI355X.jl: PgHuman differs from pg_human of include/pigeon_mpc.h")
+end
+"Who drives the other car of the safety and node rollouts: a library of drivers and the set each instance runs under (0-based; may be empty for a library of one).  Under a library the rollouts' human_mode no longer decides; human_u is wanted when a set has mode 2.  Resets nothing."
+function set_humans!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgHuman}, index::Vector{Int32}=Int32[])
+    check_human_layout()
+    check(mpc, ccall(sym(mpc, :pg_set_human_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgHuman}), mpc.handle, length(sets), sets), "pg_set_human_sets")
+    isempty(index) || check(mpc, ccall(sym(mpc, :pg_set_human_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_human_index")
+    nothing
+end
+"key of the random driver's draws and the 64-bit stream id per instance (empty: stream[b] = b - 1)"
+set_human_seed!(mpc::BatchedTrajectoryTrackingMPC, seed::UInt64, streams::Vector{UInt64}=UInt64[]) =
+    check(mpc, ccall(sym(mpc, :pg_set_human_seed), Cint, (Ptr{Cvoid}, UInt64, Int32, Ptr{UInt64}), mpc.handle, seed, isempty(streams) ? max(mpc.B, 1) : length(streams), isempty(streams) ? C_NULL : pointer(streams)), "pg_set_human_seed")
+clear_humans!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_human_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_human_sets")
+"(sets, index over B instances; -1 where no index covers an instance) as installed"
+function humans(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_human_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgHuman}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_human_sets")
+    sets = Vector{PgHuman}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_human_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgHuman}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_human_sets")
+    sets, index
+end
+"2 x B: (omega, a) of the last rollout step under a human library"
+function human_state(mpc::BatchedTrajectoryTrackingMPC)
+    u = zeros(2, mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_human_state), Cint, (Ptr{Cvoid}, Ptr{Float64}), mpc.handle, u), "pg_get_human_state")
+    u
+end
+"The NEXT rollout call writes (omega, a) of its step k < steps to a device array 2 x B x steps of the library's element type (one-shot; C_NULL cancels)"
+set_human_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_human_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_human_history_dev")
+"The law alone, on the device: relative states x7 7 x B x steps, lookups vg8 8 x B x steps (V, then the gradient) and a script 2 x B x steps (nothing: none) -> (omega, a) 2 x B x steps of the clock steps step0, step0 + 1, ... under the installed library, index, seed and streams, from a fresh state"
+function human_response(mpc::BatchedTrajectoryTrackingMPC, step0::Integer, x7::Array{Float64,3}, vg8::Array{Float64,3}, dt::Float64, script::Union{Nothing,Array{Float64,3}}=nothing)
+    u = zeros(2, size(x7, 2), size(x7, 3))
+    check(mpc, ccall(sym(mpc, :pg_human_response), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), mpc.handle, step0, size(x7, 3), dt, x7, vg8,
+                     script === nothing ? C_NULL : pointer(script), u), "pg_human_response")
+    u
+end
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

@@ -40,6 +40,7 @@ SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_defaul
            "pg_set_actuator_sets", "pg_set_actuator_index", "pg_clear_actuator_sets", "pg_get_actuator_sets", "pg_set_applied_history_dev", "pg_set_command_history_dev", "pg_get_actuator_state", "pg_actuator_response",
            "pg_set_disturbance_sets", "pg_set_disturbance_index", "pg_set_disturbance_seed", "pg_clear_disturbance_sets", "pg_get_disturbance_sets", "pg_disturbance_response", "pg_get_disturbance_state", "pg_set_disturbance_history_dev",
            "pg_set_estimator_sets", "pg_set_estimator_index", "pg_clear_estimator_sets", "pg_get_estimator_sets", "pg_get_estimated_state", "pg_set_estimated_history_dev", "pg_estimator_response",
+           "pg_set_human_sets", "pg_set_human_index", "pg_set_human_seed", "pg_clear_human_sets", "pg_get_human_sets", "pg_get_human_state", "pg_set_human_history_dev", "pg_human_response",
            "pg_set_hji_grid", "pg_clear_hji_grid", "pg_reset", "pg_set_inputs", "pg_set_inputs_dev", "pg_compute_time_steps",
            "pg_compute_linearization_nodes", "pg_update_qp", "pg_solve", "pg_get_next_control", "pg_get_next_control_dev", "pg_get_next_control_hji", "pg_get_next_control_hji_dev", "pg_step", "pg_step_dev", "pg_simulate_dev", "pg_simulate_clock", "pg_get_state", "pg_simulate_safety_dev", "pg_get_safety_state", "pg_node_step_dev", "pg_simulate_node_dev", "pg_get_node_state",
            "pg_set_stream", "pg_set_fusion", "pg_set_pipeline", "pg_set_option", "pg_get_option", "pg_get_pipeline_fallbacks", "pg_synchronize", "pg_get_time_steps", "pg_get_nodes", "pg_get_path_coordinates", "pg_qp_len", "pg_get_qp", "pg_set_qp", "pg_get_solution",
@@ -142,6 +143,25 @@ ESTIMATOR_SET_PROTOTYPES = {
     "pg_estimator_response": [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
 }
 
+class pg_human(C.Structure):
+    """include/pigeon_mpc.h pg_human: the driver model (0 hold, 1 worst case, 2 the caller's script, 3 seeded random), the steps a decision is kept, the window in clock
+    steps (step_off < 0: open-ended), the factor on the decided (omega, a), the limits (Inf: none) and the random driver's standard deviations and correlation time."""
+    _fields_ = [("mode", C.c_int32), ("hold_steps", C.c_int32), ("step_on", C.c_int32), ("step_off", C.c_int32), ("gain", C.c_double * 2), ("omega_max", C.c_double),
+                ("a_min", C.c_double), ("a_max", C.c_double), ("sigma", C.c_double * 2), ("tau", C.c_double)]
+
+
+# human library (include/pigeon_mpc.h: pg_set_human_sets and its companions)
+HUMAN_SET_PROTOTYPES = {
+    "pg_set_human_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_human)],
+    "pg_set_human_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
+    "pg_set_human_seed": [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)],
+    "pg_clear_human_sets": [C.c_void_p],
+    "pg_get_human_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_human), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    "pg_get_human_state": [C.c_void_p, C.POINTER(C.c_double)],
+    "pg_set_human_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
+    "pg_human_response": [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+}
+
 
 def load_library(precision="f64"):
     """Loads the HIP library of the requested arithmetic type.  PyTorch-ROCm is imported first so that both share ONE HIP runtime in this process."""
@@ -163,7 +183,7 @@ def load_library(precision="f64"):
     lib.pg_last_error.argtypes = [C.c_void_p]
     for s in SYMBOLS:
         getattr(lib, s)
-    for name, argtypes in list(CONTROL_PARAM_SET_PROTOTYPES.items()) + list(PLANT_SET_PROTOTYPES.items()) + list(SENSOR_SET_PROTOTYPES.items()) + list(ACTUATOR_SET_PROTOTYPES.items()) + list(DISTURBANCE_SET_PROTOTYPES.items()) + list(ESTIMATOR_SET_PROTOTYPES.items()):
+    for name, argtypes in list(CONTROL_PARAM_SET_PROTOTYPES.items()) + list(PLANT_SET_PROTOTYPES.items()) + list(SENSOR_SET_PROTOTYPES.items()) + list(ACTUATOR_SET_PROTOTYPES.items()) + list(DISTURBANCE_SET_PROTOTYPES.items()) + list(ESTIMATOR_SET_PROTOTYPES.items()) + list(HUMAN_SET_PROTOTYPES.items()):
         getattr(lib, name).argtypes = argtypes
         getattr(lib, name).restype = C.c_int
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)

@@ -94,6 +94,18 @@ struct pg_handle {
     bool est_valid = false;                                       // d_est holds the estimate of a rollout step since the inputs were installed
     real* est_hist = nullptr; int est_hist_steps = 0;             // pg_set_estimated_history_dev: one-shot, consumed by the next rollout call
     int64_t stat_estimator_steps = 0;                             // read-only option "stat_estimator_steps"
+    // human library (pg_set_human_sets / pg_set_human_index / pg_set_human_seed): the driver of the other car in the safety and node rollouts.  Beside the sets: the stream
+    // ids [cap] and the seed (its own, as the disturbance library keeps its own), and, allocated when a rollout first runs under a library: the driver's control
+    // d_human_u [cap][2] (k_human writes it, the step's plant launch reads it as the script of its human mode 2) and the random driver's state d_human_n [cap][2].
+    // human_script: some installed set has mode 2 (the rollouts then want human_u_dev)
+    SetLib<pg_human, DevHuman> humans{{"human", "pg_set_human_index"}};
+    unsigned long long* d_human_stream = nullptr; bool human_stream_dirty = true; std::vector<uint64_t> human_stream; uint64_t human_seed = 0;
+    real *d_human_u = nullptr, *d_human_n = nullptr;
+    bool human_script = false;
+    bool human_fresh = true;                                      // no u / n of the previous step exists (the clock restarted, or no step ran under a library since one was installed)
+    bool human_valid = false;                                     // d_human_u holds u of a rollout step since the inputs were installed
+    real* human_hist = nullptr; int human_hist_steps = 0;         // pg_set_human_history_dev: one-shot, consumed by the next rollout call
+    int64_t stat_human_steps = 0;                                 // read-only option "stat_human_steps"
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -346,9 +358,9 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen, h->d_dist_stream, h->d_dist_n, h->d_dist_w, h->d_dist_veh, h->d_est, h->d_est_u};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen, h->d_dist_stream, h->d_dist_n, h->d_dist_w, h->d_dist_veh, h->d_est, h->d_est_u, h->d_human_stream, h->d_human_u, h->d_human_n};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release(); h->dists.release(); h->ests.release();
+    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release(); h->dists.release(); h->ests.release(); h->humans.release();
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
     if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
@@ -569,6 +581,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "stat_actuator_steps") return S(&h->stat_actuator_steps);
     if (n == "stat_disturbance_steps") return S(&h->stat_disturbance_steps);
     if (n == "stat_estimator_steps") return S(&h->stat_estimator_steps);
+    if (n == "stat_human_steps") return S(&h->stat_human_steps);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -647,7 +660,7 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
 }
 int pg_synchronize(pg_handle* h) { if (!h) return PG_ERR_INVALID; HIPCHK(h, hipStreamSynchronize(h->stream)); return PG_OK; }
 
-// ---- what the seven libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances, estimators): one index rule and one install / clear / get protocol ----
+// ---- what the eight libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances, estimators, humans): one index rule and one install / clear / get protocol ----
 // Installs the selection of `B` instances into a library of `n_sets`.  The WHOLE [capacity] array is written, entries beyond B as 0: never an address outside the library,
 // whatever an earlier, larger library left there
 static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, const int32_t* index) {
@@ -1185,6 +1198,107 @@ int pg_estimator_response(pg_handle* h, int32_t steps, double dt, const double* 
     return rc;
 }
 
+// ---- human library: the driver of the OTHER CAR in the safety and node rollouts, (omega, a) per instance (k_human; the plant kernels take it through their scripted mode).
+// Build-defined (the reference only receives the other car from ROS).  No part of any QP: installing sets, an index, a seed or streams resets nothing ----
+static const char* human_field_problem(const pg_human& s) {
+    if (s.mode < 0 || s.mode > 3) return "mode must be 0 (hold), 1 (worst case), 2 (scripted) or 3 (seeded random)";
+    if (s.hold_steps < 1) return "hold_steps must be >= 1";
+    if (s.step_on < 0) return "step_on must be >= 0";
+    if (!(s.gain[0] >= 0.0 && s.gain[0] <= 1.0)) return "gain[0] (omega) is outside [0, 1] or not finite";      // (false for NaN as well)
+    if (!(s.gain[1] >= 0.0 && s.gain[1] <= 1.0)) return "gain[1] (a) is outside [0, 1] or not finite";
+    if (!(s.omega_max >= 0.0)) return "omega_max must be >= 0 (+Inf: no limit) and not NaN";
+    if (!(s.a_min <= 0.0)) return "a_min must be <= 0 (-Inf: no limit) and not NaN";
+    if (!(s.a_max >= 0.0)) return "a_max must be >= 0 (+Inf: no limit) and not NaN";
+    if (!(std::isfinite(s.sigma[0]) && s.sigma[0] >= 0.0)) return "sigma[0] (omega) must be >= 0 and finite";
+    if (!(std::isfinite(s.sigma[1]) && s.sigma[1] >= 0.0)) return "sigma[1] (a) must be >= 0 and finite";
+    if (!(std::isfinite(s.tau) && s.tau >= 0.0)) return "tau must be >= 0 and finite";
+    return nullptr;
+}
+static void fill_dev_human(DevHuman& H, const pg_human& s) {
+    H.mode = s.mode; H.hold_steps = s.hold_steps; H.step_on = s.step_on; H.step_off = s.step_off; H.gain[0] = (real)s.gain[0]; H.gain[1] = (real)s.gain[1];
+    H.omega_max = (real)s.omega_max; H.a_min = (real)s.a_min; H.a_max = (real)s.a_max; H.sigma[0] = (real)s.sigma[0]; H.sigma[1] = (real)s.sigma[1]; H.tau = (real)s.tau;
+}
+int pg_set_human_sets(pg_handle* h, int32_t n_sets, const pg_human* sets) {
+    if (!h) return PG_ERR_INVALID;
+    std::string why;                                            // (the message names the set and the field; seed, streams and the driver's state persist)
+    const int rc = setlib_install(h, "pg_set_human_sets", h->humans, n_sets, sets, [&](const pg_human& s) -> const char* {
+        const char* f = human_field_problem(s);
+        if (!f) return nullptr;
+        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
+        return why.c_str();
+    }, fill_dev_human);
+    if (rc) return rc;
+    h->human_script = false;
+    for (const pg_human& s : h->humans.sets) h->human_script = h->human_script || s.mode == 2;
+    return PG_OK;
+}
+int pg_set_human_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    return index_install(h, (int)h->humans.sets.size(), h->humans.idx, B, index);
+}
+int pg_set_human_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_set_human_seed: need 1 <= B <= batch_capacity");
+    h->human_seed = seed;                                       // (a launch argument: a rollout already queued keeps the seed it was launched with)
+    if (stream) h->human_stream.assign(stream, stream + B); else h->human_stream.clear();      // instances the array does not cover: stream[b] = b
+    h->human_stream_dirty = true;
+    return PG_OK;
+}
+int pg_clear_human_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    const int rc = setlib_clear(h, h->humans); if (rc) return rc;
+    h->human_script = false; h->human_fresh = true; h->human_valid = false; h->human_hist = nullptr; h->human_hist_steps = 0;      // (a library installed later starts a driver of its own)
+    return PG_OK;
+}
+int pg_get_human_sets(pg_handle* h, int32_t* n_sets, pg_human* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    return setlib_get(h, "pg_get_human_sets", h->humans, n_sets, out, max_sets, index, B);
+}
+int pg_set_human_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
+    if (!h) return PG_ERR_INVALID;
+    if (!buf) { h->human_hist = nullptr; h->human_hist_steps = 0; return PG_OK; }
+    REQUIRE(h, steps >= 1, "pg_set_human_history_dev: steps >= 1 required");
+    if (h->humans.sets.empty()) { h->err = "pg_set_human_history_dev: no human library installed (the rollouts' human_mode decides: human_hist_dev of pg_simulate_safety_dev records that)"; return PG_ERR_STATE; }
+    h->human_hist = (real*)buf; h->human_hist_steps = steps;
+    return PG_OK;
+}
+int pg_get_human_state(pg_handle* h, double* u) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->humans.sets.empty() || !h->human_valid || !h->d_human_u) { h->err = "pg_get_human_state: no rollout step under a human library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, u, h->d_human_u, (size_t)h->B * 2);
+}
+// what mode 1 is handed as has_hji: a grid on a coupled handle (the safety rollout is coupled only; the node rollout passes its plant kernel the same word)
+static int human_has_hji(const pg_handle* h) { return (int)(h->has_hji && h->dc.formulation == PG_COUPLED); }
+int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, step0 >= 0 && steps >= 1 && dt > 0.0 && x7 && vg8 && u_out, "pg_human_response: step0 >= 0, steps >= 1, dt > 0, x7, vg8 and the output array required");
+    if (h->B <= 0) { h->err = "pg_human_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
+    if (h->humans.sets.empty()) { h->err = "pg_human_response: no human library installed"; return PG_ERR_STATE; }
+    REQUIRE(h, !h->human_script || script, "pg_human_response: an installed set has mode 2 and needs script [steps][B][2]");
+    if (index_covers(h, h->humans.sets.size(), h->humans.idx)) return PG_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = streams_sync(h, h->d_human_stream, h->human_stream_dirty, h->human_stream); if (rc) return rc;
+    const int B = h->B;
+    const size_t sb = (size_t)steps * (size_t)B, nx = sb * 7, nv = sb * 8, nu = sb * 2;
+    real* d = nullptr;                                           // scratch of the call: x7, vg8, script, u (the driver's state lives in the lanes' registers)
+    HIPCHK(h, hipMalloc((void**)&d, (nx + nv + 2 * nu) * sizeof(real)));
+    real *dx = d, *dv = d + nx, *ds = dv + nv, *du = ds + nu;
+    rc = up(h, dx, x7, nx);
+    if (!rc) rc = up(h, dv, vg8, nv);
+    if (!rc && script) rc = up(h, ds, script, nu);
+    if (!rc) {
+        hipLaunchKernelGGL(k_human_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, (int)step0, (int)steps, human_has_hji(h), (real)dt, h->humans.d,
+                           h->humans.sets.size() > 1 ? h->humans.idx.d : (const int*)nullptr, h->d_human_stream, (unsigned long long)h->human_seed, (const real*)dx, (const real*)dv,
+                           script ? (const real*)ds : (const real*)nullptr, du);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { h->err = std::string("pg_human_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
+    }
+    if (!rc) rc = down(h, u_out, du, nu);
+    else (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
+}
+
 int pg_clear_hji_grid(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
@@ -1256,7 +1370,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true; h->dist_fresh = true; h->dist_valid = false; h->est_fresh = true; h->est_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true; h->dist_fresh = true; h->dist_valid = false; h->est_fresh = true; h->est_valid = false; h->human_fresh = true; h->human_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1765,16 +1879,25 @@ int pg_step_dev(pg_handle* h, void* u_out_dev) {
 // the compute calls of one closed-loop step (model_predictive_control.jl:90-93; the time grid rides in the projection launch): fusion, pipelining and the split solve as pg_step_dev has them
 static int step_compute(pg_handle* h) { const int rc = launch_nodes(h, true); return rc ? rc : update_and_solve(h, nullptr); }
 // the arguments the rollouts share (`who`: the entry point, for the message; a rollout without a human passes mode 0)
-static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, double dt, int32_t human_mode, const void* human_u_dev) {
+// human_lib: the rollout runs under a human library -- the sets decide, and the script is wanted exactly when one of them has mode 2
+static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, double dt, int32_t human_mode, const void* human_u_dev, bool human_lib) {
     const std::string w(who);
     REQUIRE(h, steps >= 1 && dt > 0.0, w + ": steps >= 1 and dt > 0 required");
     REQUIRE(h, human_mode >= 0 && human_mode <= 2, w + ": human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
-    REQUIRE(h, human_mode != 2 || human_u_dev, w + ": human_mode 2 needs human_u_dev [steps][B][2]");
+    if (human_lib) REQUIRE(h, !h->human_script || human_u_dev, w + ": a set of the human library has mode 2 and needs human_u_dev [steps][B][2]");
+    else REQUIRE(h, human_mode != 2 || human_u_dev, w + ": human_mode 2 needs human_u_dev [steps][B][2]");
     return PG_OK;
 }
 // what a rollout needs beyond check_ready: a plant library of several sets wants an index that covers the batch; the tracking summary its buffers
-static int rollout_ready(pg_handle* h) {
+static int rollout_ready(pg_handle* h, bool human_lib) {
     if (index_covers(h, h->plants.sets.size(), h->plants.idx)) return PG_ERR_STATE;
+    if (human_lib) {                                             // (a rollout with another car, under a human library)
+        if (index_covers(h, h->humans.sets.size(), h->humans.idx)) return PG_ERR_STATE;
+        const size_t cap = cap_of(h);
+        if (!h->d_human_u) HIPCHK(h, hipMalloc((void**)&h->d_human_u, cap * 2 * sizeof(real)));
+        if (!h->d_human_n) HIPCHK(h, hipMalloc((void**)&h->d_human_n, cap * 2 * sizeof(real)));
+        const int rc = streams_sync(h, h->d_human_stream, h->human_stream_dirty, h->human_stream); if (rc) return rc;
+    }
     if (h->tracking && !h->d_track) {
         const size_t cap = cap_of(h);
         HIPCHK(h, hipMalloc((void**)&h->d_track, cap * 6 * sizeof(real)));
@@ -1823,6 +1946,22 @@ static int launch_disturb(pg_handle* h, int step, int k, double dt, const DistHi
                        (dh.buf && k < dh.steps) ? dh.buf + (size_t)k * B * 4 : (real*)nullptr);
     LAUNCH_CHECK(h);
     h->dist_fresh = false; h->dist_valid = true; h->stat_disturbance_steps++;
+    return PG_OK;
+}
+// the human library (installed: k_human joins a step of the rollouts that have another car, ahead of the plant launch, which is handed d_human_u as the script of its human
+// mode 2).  human_take_history: the one-shot registration of pg_set_human_history_dev, consumed by the rollout call that starts now
+static bool human_lib_on(const pg_handle* h) { return !h->humans.sets.empty(); }
+struct HumanHist { real* buf; int steps; };
+static HumanHist human_take_history(pg_handle* h) { const HumanHist u{h->human_hist, h->human_hist_steps}; h->human_hist = nullptr; h->human_hist_steps = 0; return u; }
+// behind the compute calls of a rollout step under a library (mode 1 reads the step's d_x7, d_vg8): (omega, a) of clock step `step` into d_human_u, the driver's state
+// advanced (fresh: the host knows that no state of step - 1 exists).  script: human_u_dev of the call, [steps][B][2] or nullptr
+static int launch_human(pg_handle* h, int step, int k, double dt, const void* script, const HumanHist& hh) {
+    const int B = h->B;
+    const HumanLib lib{h->humans.d, h->humans.sets.size() > 1 ? h->humans.idx.d : (const int*)nullptr, h->d_human_stream, (unsigned long long)h->human_seed, h->d_human_n, h->d_human_u};
+    hipLaunchKernelGGL(k_human, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, step, (int)h->human_fresh, human_has_hji(h), (real)dt, lib, (const real*)h->d_x7,
+                       (const real*)h->d_vg8, script ? (const real*)script + (size_t)k * B * 2 : (const real*)nullptr, (hh.buf && k < hh.steps) ? hh.buf + (size_t)k * B * 2 : (real*)nullptr);
+    LAUNCH_CHECK(h);
+    h->human_fresh = false; h->human_valid = true; h->stat_human_steps++;
     return PG_OK;
 }
 // the actuator library (the host knows whether one is installed: that alone adds k_actuate and the copy-back to a rollout step).  actuator_take_history: the one-shot
@@ -1910,7 +2049,7 @@ static int launch_track(pg_handle* h, int step) {
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true; h->dist_fresh = true; h->est_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true; h->dist_fresh = true; h->est_fresh = true; h->human_fresh = true;
     }
     return PG_OK;
 }
@@ -1926,24 +2065,26 @@ static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_di
     else if (plant_lib_on(h)) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
     else hipLaunchKernelGGL(uniform, grid, block, 0, h->stream, args...);
 }
-// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated) are taken (THIS call consumes them, also when it fails below), check_ready,
+// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated, human) are taken (THIS call consumes them, also when it fails below), check_ready,
 // the entry point's own precondition (coupled_only: the message for a lateral handle, nullptr: none), the shared arguments, rollout_ready, the node's buffers (node: the
 // rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records(k) ahead of the compute calls, the
 // controller's side (:90-93, on the measured state under a sensor library), the tracking summary, the clock index, then finish(k, step): the step's last launch, which moves
 // the plant (step: index of the clock element t0 held -- steps continue across calls)
 static const char* const ACTUATOR_NODE_REFUSAL = "an actuator library is installed and the node callback is outside its scope (k_node_finish keeps message and applied command "
                                                  "apart and leaves `applied` unwritten for a gated-out instance: no plain hand-back of the next command); pg_clear_actuator_sets first";
-struct RolloutArgs { const char* who; int32_t steps; double dt; int32_t human_mode; const void* human_u; const char* coupled_only; bool node; const uint8_t* pre_flag; };
+struct RolloutArgs { const char* who; int32_t steps; double dt; int32_t human_mode; const void* human_u; const char* coupled_only; bool node; const uint8_t* pre_flag; bool other_car; };
 template <class Records, class Finish>
 static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish finish) {
     const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};
     const ActHist ah = h ? actuator_take_history(h) : ActHist{nullptr, nullptr, 0, 0};
     const DistHist dh = h ? disturbance_take_history(h) : DistHist{nullptr, 0};
     const EstHist eh = h ? estimator_take_history(h) : EstHist{nullptr, 0};
+    const HumanHist hh = h ? human_take_history(h) : HumanHist{nullptr, 0};
     int rc = check_ready(h); if (rc) return rc;
     if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
     if (a.node && actuator_lib_on(h)) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
-    if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u)) || (rc = rollout_ready(h)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
+    const bool human = a.other_car && human_lib_on(h);           // (pg_simulate_dev has no other car: it never reads the human library)
+    if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u, human)) || (rc = rollout_ready(h, human)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
     // Under an actuator library the handle's control pointer names, while the launches are QUEUED: d_plant_u (= a_k) for the records and the plant launch, d_seen for the
     // compute calls when some set has feedback == 1 -- k_nodes*, the QP's u_curr and the steering-rate rows all take the pointer from the handle --, and its own allocation
     // (the command) everywhere else and whenever this function returns.  The plant kernel leaves the next command in d_plant_u: one copy moves it to the control buffer
@@ -1958,7 +2099,7 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
         if (act) h->d_control = h->act_feedback ? h->d_seen : command;
         if (!rc) rc = rollout_compute(h, step, k, a.dt, mh, eh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
         h->d_control = command;
-        if (rc || (rc = launch_track(h, step))) return rc;
+        if (rc || (rc = launch_track(h, step)) || (human && (rc = launch_human(h, step, k, a.dt, a.human_u, hh)))) return rc;
         h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)
         if (act) h->d_control = h->d_plant_u;
         finish(k, step);
@@ -1976,7 +2117,7 @@ static int no_records(int) { return PG_OK; }
 template <class T> static T* hist_at(T* hist, int k, int B, int width) { return hist ? hist + (size_t)k * B * width : nullptr; }
 extern "C" {
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev, void* control_hist_dev) {
-    return rollout(h, RolloutArgs{"pg_simulate_dev", steps, dt, 0, nullptr, nullptr, false, nullptr},
+    return rollout(h, RolloutArgs{"pg_simulate_dev", steps, dt, 0, nullptr, nullptr, false, nullptr, false},
         [&](int k) -> int {
             const int B = h->B;
             if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)state_hist_dev, k, B, 6), h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));          // push!(qs, state) :88
@@ -1991,14 +2132,16 @@ int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev
 int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev,
                            void* state_hist_dev, void* control_hist_dev, void* other_hist_dev, void* human_hist_dev, void* V_hist_dev, int32_t* source_hist_dev) {
     return rollout(h, RolloutArgs{"pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev,
-                                  "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row", false, nullptr},
+                                  "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row", false, nullptr, true},
         no_records,
         [&](int k, int step) {
             const int B = h->B;
-            SafetyIO io{human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr, hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
+            const bool lib = human_lib_on(h);                    // (under a human library the kernel is handed this step's d_human_u as its script: it records and integrates that)
+            const int hmode = lib ? 2 : (int)human_mode;
+            SafetyIO io{lib ? (const real*)h->d_human_u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr), hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
                         hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
                         h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)h->has_hji, (int)h->sum_fresh, step,
+            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)h->has_hji, (int)h->sum_fresh, step,
                               h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
             h->sum_fresh = false;
         });
@@ -2106,16 +2249,18 @@ static int node_start(pg_handle* h, double dt) {
 int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji_policy, int32_t human_mode, const void* human_u_dev, const uint8_t* pre_flag_dev,
                          void* state_hist_dev, void* applied_hist_dev, int32_t* event_hist_dev, void* V_hist_dev) {
     return rollout(h, RolloutArgs{"pg_simulate_node_dev", steps, dt, human_mode, human_u_dev,
-                                  use_hji_policy ? "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)" : nullptr, true, pre_flag_dev},
+                                  use_hji_policy ? "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)" : nullptr, true, pre_flag_dev, true},
         no_records,
         [&](int k, int step) {
             const int B = h->B;
             NodeIO io = node_io(h);
-            io.human_u = human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr;
+            const bool lib = human_lib_on(h);                    // (as pg_simulate_safety_dev: d_human_u of this step is the script)
+            const int hmode = lib ? 2 : (int)human_mode;
+            io.human_u = lib ? (const real*)h->d_human_u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr);
             io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
             io.event_h = hist_at(event_hist_dev, k, B, 1);
             io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), (int)human_mode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
                               (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
                               h->sim_idx, h->kv, io);
             h->sum_fresh = false;

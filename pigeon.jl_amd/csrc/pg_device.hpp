@@ -792,4 +792,52 @@ PG_DEV void estimator_correct(const DevEstimator& E, const real p[6], const real
     }
 }
 
+// ---- human of the safety rollouts (pg_set_human_sets; build-defined: the reference only receives the other car from ROS) ----
+// one set of a human library in the arithmetic type of the build: the driver model, how many steps a decision is kept, the window in clock steps, the factor on the decided
+// (omega, a), the limits, and the random driver's standard deviations and correlation time
+struct DevHuman { int mode, hold_steps, step_on, step_off; real gain[2], omega_max, a_min, a_max, sigma[2], tau; };
+// The law for one instance and one clock step.  x7 / vg8: the step's relative state and HJI lookup of the instance (read by mode 1 with a grid only); script: the caller's
+// (omega, a) of the step (read by mode 2 only); n (in: n_{k-1}, out: n_k) the normalised state of the random driver, u (in: u_{k-1}, out: u_k) the driver's control.
+// `fresh`: no state of step k - 1 exists.
+//   mode 3 advances n at every step: (z_w, z_a) = Box-Muller of words (x0, x1) of Philox block j = 3 on (seed; step, 3, stream) -- blocks 0 and 1 are the sensor's, block 2
+//   the gust's --, n_k as disturbance_advance forms it
+//   outside the window u = (0, 0);  inside it and not deciding u is left as it is;  deciding:
+//   raw = (0, 0) | optimal_disturbance (as human_control applies it: (0, 0) without a grid or where the other car's speed is <= 0) | script | (sigma_w n_w, sigma_a n_a)
+//   u[c] = gain[c] raw[c], then the limits
+// gain == 1 COPIES, a sigma of 0 gives 0 without a multiply, and the limits are compare-and-select: a value inside them (and NaN) keeps its bits.  No contraction: every
+// product and sum of the law is rounded once, as the numpy twin rounds it (optimal_disturbance keeps the code it has in the plant kernels)
+PG_DEV void human_advance(const DevVehicle& P, const DevHuman& H, int has_hji, uint64_t seed, uint64_t stream, uint32_t step, bool fresh, real dt,
+                          const real* __restrict__ x7, const real* __restrict__ vg8, const real* __restrict__ script, real n[2], real u[2]) {
+#pragma clang fp contract(off)
+    if (H.mode == 3) {
+        const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+        const uint32_t ctr[4] = {step, 3u, (uint32_t)stream, (uint32_t)(stream >> 32)};
+        uint32_t x[4];
+        philox4x32_10(ctr, key, x);
+        real z[2]; box_muller(x[0], x[1], z[0], z[1]);
+        if (fresh || H.tau == real(0.0)) { n[0] = z[0]; n[1] = z[1]; }
+        else {
+            const real rho = pg_exp(-dt / H.tau), g = sqrt(-pg_expm1(real(-2.0) * dt / H.tau));
+            n[0] = rho * n[0] + g * z[0]; n[1] = rho * n[1] + g * z[1];
+        }
+    }
+    const bool active = (int)step >= H.step_on && (H.step_off < 0 || (int)step < H.step_off);
+    if (!active) { u[0] = real(0.0); u[1] = real(0.0); return; }
+    if (!fresh && ((int)step - H.step_on) % H.hold_steps != 0) return;
+    real w = real(0.0), a = real(0.0);
+    if (H.mode == 1) { if (has_hji && x7[5] > real(0.0)) optimal_disturbance(P, x7, vg8 + 1, w, a); }
+    else if (H.mode == 2) { w = script[0]; a = script[1]; }
+    else if (H.mode == 3) {
+        if (H.sigma[0] != real(0.0)) w = H.sigma[0] * n[0];
+        if (H.sigma[1] != real(0.0)) a = H.sigma[1] * n[1];
+    }
+    if (H.gain[0] != real(1.0)) w = H.gain[0] * w;
+    if (H.gain[1] != real(1.0)) a = H.gain[1] * a;
+    if (w > H.omega_max) w = H.omega_max;
+    if (w < -H.omega_max) w = -H.omega_max;
+    if (a < H.a_min) a = H.a_min;
+    if (a > H.a_max) a = H.a_max;
+    u[0] = w; u[1] = a;
+}
+
 }  // namespace pg

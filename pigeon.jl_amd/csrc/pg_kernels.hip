@@ -1269,6 +1269,44 @@ __global__ __launch_bounds__(64) void k_estimator_response(DevCfg C, int B, int 
     }
 }
 
+// Human library (pg_set_human_sets), lane = instance, one wavefront per block: (omega, a) of the other car's driver for this rollout step (human_advance, pg_device.hpp).
+// Queued behind the step's compute calls and tracking summary -- mode 1 reads the step's x7 [B][7] and vg8 [B][8] -- and ahead of the launch that moves the plants, which
+// takes `u` as the script of its human mode 2.  Reads the instance's record (copied into registers once), its stream id, the script row of the step (nullptr when no
+// installed set has mode 2) and, unless `fresh`, u [cap][2] and the random driver's state n [cap][2]; writes u, n and the step's row of the history when one is registered.
+// The draw is a function of (seed, stream id, clock step) alone, not of b or B.  idx == nullptr: a library of one.  `fresh`: no state of the previous step exists.
+// P: the controller's vehicle (the one human_control hands optimal_disturbance)
+struct HumanLib { const DevHuman* sets; const int* idx; const unsigned long long* stream; unsigned long long seed; real* n; real* u; };
+__global__ __launch_bounds__(64) void k_human(DevVehicle P, int B, int step, int fresh, int has_hji, real dt, HumanLib lib, const real* __restrict__ x7,
+                                              const real* __restrict__ vg8, const real* __restrict__ script, real* __restrict__ hist) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevHuman H = lib.sets[lib.idx ? lib.idx[b] : 0];
+    real n[2] = {real(0.0), real(0.0)}, u[2] = {real(0.0), real(0.0)};
+    if (!fresh) { n[0] = lib.n[(size_t)b * 2]; n[1] = lib.n[(size_t)b * 2 + 1]; u[0] = lib.u[(size_t)b * 2]; u[1] = lib.u[(size_t)b * 2 + 1]; }
+    human_advance(P, H, has_hji, lib.seed, lib.stream[b], (uint32_t)step, fresh != 0, dt, x7 + (size_t)b * 7, vg8 + (size_t)b * 8, script ? script + (size_t)b * 2 : nullptr, n, u);
+    for (int j = 0; j < 2; j++) {
+        lib.n[(size_t)b * 2 + j] = n[j];
+        lib.u[(size_t)b * 2 + j] = u[j];
+        if (hist) hist[(size_t)b * 2 + j] = u[j];
+    }
+}
+// pg_human_response: u [steps][B][2] of the clock steps [step0, step0 + steps) over a caller's x7 [steps][B][7], vg8 [steps][B][8] and script [steps][B][2] (nullptr: none)
+// through the function k_human calls, from a fresh state at step0 kept in registers (lane = instance; the steps in order)
+__global__ __launch_bounds__(64) void k_human_response(DevVehicle P, int B, int step0, int steps, int has_hji, real dt, const DevHuman* __restrict__ sets, const int* __restrict__ idx,
+                                                       const unsigned long long* __restrict__ stream, unsigned long long seed, const real* __restrict__ x7,
+                                                       const real* __restrict__ vg8, const real* __restrict__ script, real* __restrict__ u_out) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const DevHuman H = sets[idx ? idx[b] : 0];
+    const unsigned long long id = stream[b];
+    real n[2] = {real(0.0), real(0.0)}, u[2] = {real(0.0), real(0.0)};
+    for (int k = 0; k < steps; k++) {
+        const size_t at = (size_t)k * B + b;
+        human_advance(P, H, has_hji, seed, id, (uint32_t)step0 + (uint32_t)k, k == 0, dt, x7 + at * 7, vg8 + at * 8, script ? script + at * 2 : nullptr, n, u);
+        for (int j = 0; j < 2; j++) u_out[at * 2 + j] = u[j];
+    }
+}
+
 // ==================================================================================================================
 // Decoupled (lateral) formulation: decoupled_lat_long.jl.  The lateral QP (state (Uy, r, dpsi, e), input delta) is EMBEDDED in the
 // 8-state stage structure k_solve works on: x = (0, Ux_dummy, Uy, r, dpsi, e, delta, 0) with identity dynamics, zero cost and

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -468,6 +468,75 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_set_estimated_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_estimated_history_dev")
         return buf
 
+    # ---- the HUMAN of the safety and node rollouts, per instance (the other car's driver): a library of pg_human, a per-instance selection, a seed and stream ids ----
+    @classmethod
+    def pack_humans(cls, sets):
+        """human dicts (vehicles.human(**overrides); missing fields: the identity's) or pg_human structures -> a ctypes array of pg_human."""
+        def fill(rec, v):
+            d = _identity_human(**v)
+            for name in ("mode", "hold_steps", "step_on", "step_off"):
+                if int(d[name]) != d[name]:
+                    raise ValueError(f"{name} = {d[name]} is not a whole number")
+                setattr(rec, name, int(d[name]))
+            rec.gain[:] = d["gain"]; rec.sigma[:] = d["sigma"]
+            for name in ("omega_max", "a_min", "a_max", "tau"):
+                setattr(rec, name, float(d[name]))
+        return cls._pack(_lib.pg_human, sets, fill)
+
+    def set_humans(self, sets, index=None, seed=0, streams=None):
+        """Who drives the other car of simulate_safety_ / simulate_node_ (pg_set_human_sets): per instance hold (mode 0), the worst case (1), the caller's script (2) or a
+        seeded random driver (3), inside the window [step_on, step_off), decided every hold_steps steps, scaled by gain and limited to omega_max, [a_min, a_max].  One set
+        (dict / structure) for the whole batch, or a list of sets selected per instance with `index`; `seed` and the 64-bit `streams` [B] (None: stream[b] = b) fix the
+        random driver (pg_set_human_seed).  Under a library the rollouts' `human` argument no longer decides; pass human_u when a set has mode 2.  Resets nothing.  As
+        set_disturbances, EVERY call here installs seed and streams too."""
+        self._set_sets("human", _lib.pg_human, self.pack_humans, sets, index)
+        self.set_human_seed(seed, streams)
+
+    def set_human_index(self, index):
+        self._set_index("human", index)
+
+    def set_human_seed(self, seed=0, streams=None):
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
+        self._chk(self.lib.pg_set_human_seed(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), "pg_set_human_seed")
+
+    def clear_humans(self):
+        self._chk(self.lib.pg_clear_human_sets(self.h), "pg_clear_human_sets")
+
+    def humans(self):
+        """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        return self._get_sets("human", _lib.pg_human, lambda r: {name: (list(getattr(r, name)) if name in ("gain", "sigma") else getattr(r, name)) for name, _ in r._fields_})
+
+    def human_response(self, step0, x7, vg8, dt, script=None):
+        """The law alone, on the device through the function the rollouts call (pg_human_response): relative states x7 [steps][B][7], lookups vg8 [steps][B][8] (V, then the
+        gradient) and script [steps][B][2] (None unless a set has mode 2) -> (omega, a) [steps][B][2] of the clock steps [step0, step0 + steps) under the installed library,
+        index, seed and streams, from a fresh state at step0.  B is the batch of the inputs last installed."""
+        x7 = _f64(x7).reshape(-1, self.B, 7); vg8 = _f64(vg8).reshape(-1, self.B, 8)
+        if vg8.shape[0] != x7.shape[0]:
+            raise ValueError(f"x7 has {x7.shape[0]} steps and vg8 has {vg8.shape[0]}")
+        sc = None if script is None else _f64(script).reshape(x7.shape[0], self.B, 2)
+        out = np.zeros((x7.shape[0], self.B, 2))
+        self._chk(self.lib.pg_human_response(self.h, int(step0), x7.shape[0], C.c_double(dt), _p(x7), _p(vg8), _p(sc), _p(out)), "pg_human_response")
+        return out
+
+    def human_state(self):
+        """[B][2]: (omega, a) of the last rollout step under a human library (pg_get_human_state)."""
+        u = np.zeros((self.B, 2))
+        self._chk(self.lib.pg_get_human_state(self.h, _p(u)), "pg_get_human_state")
+        return u
+
+    def _human_hist(self, record, steps):
+        """registers a [steps][B][2] device record of the library's (omega, a) with the next rollout call; {} unless record and a library is installed"""
+        if not record:
+            return {}
+        n = C.c_int32(0)
+        self._chk(self.lib.pg_get_human_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_human_sets")
+        if n.value == 0:
+            return {}
+        torch, tdt, dev = self._torch()
+        buf = torch.empty(int(steps), self.B, 2, dtype=tdt, device=dev)
+        self._chk(self.lib.pg_set_human_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_human_history_dev")
+        return {"human_u": buf}
+
     def _torch(self):
         """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""
         import torch
@@ -565,14 +634,15 @@ class BatchedTrajectoryTrackingMPC:
     def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True, estimated=False):
         """The rollouts' shared plumbing.  Device records [steps][B] + shapes[name] in the library's element type and one int32 record `int_record` (record=True), the scripted
         human [steps][B][2], the measured history, under an actuator library the applied / command histories [steps][B][3] (record=True; they join the records as "applied"
-        and "command"), under a disturbance library the history of w [steps][B][4] (record=True; "disturbance"); call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
+        and "command"), under a disturbance library the history of w [steps][B][4] (record=True; "disturbance"), under a human library (rollouts with another car) the
+        history of the library's (omega, a) [steps][B][2] (record=True; "human_u"); call(ptr, hu, hist) makes the library call (ptr: tensor or None -> c_void_p); then the state is read back.  Returns
         ((state, control, t[, other]), the records as fp64 / int32 numpy arrays or None, (measured history,) or () followed by (estimated history,) or () -- estimated=True
         registers the [steps][B][6] record of the estimate, as measured=True registers the measured one)."""
         assert human in self.HUMAN_MODES, human
         hu = None; hist = {}
-        if human == "script":
-            if human_u is None:
-                raise ValueError('human="script" needs human_u [steps][B][2]')
+        if human == "script" and human_u is None:
+            raise ValueError('human="script" needs human_u [steps][B][2]')
+        if human_u is not None and other:                       # (the script of human="script", or of the mode-2 sets of a human library)
             torch, tdt, dev = self._torch()
             hu = torch.as_tensor(np.ascontiguousarray(human_u, dtype=np.float64).reshape(steps, self.B, 2)).to(device=dev, dtype=tdt).contiguous()
         if record:
@@ -584,6 +654,8 @@ class BatchedTrajectoryTrackingMPC:
         ebuf = self._estimated_hist(estimated, steps)
         abuf = self._actuator_hists(record, steps)
         abuf.update(self._disturbance_hist(record, steps))
+        if other:
+            abuf.update(self._human_hist(record, steps))
         call(lambda t: C.c_void_p(t.data_ptr()) if t is not None else None, hu, hist)
         s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")
@@ -616,7 +688,9 @@ class BatchedTrajectoryTrackingMPC:
         source [steps][B] (0 MPC / 1 HJI policy / 2 V <= eps with the policy off) -- the values at the start of each step, and the human control and V of that step.
         measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned, estimated=True (an estimator library is installed) the
         estimated history [steps][B][6] behind it.  Under an actuator library "control" is the APPLIED
-        control and the dict also holds "command" and "applied" [steps][B][3]; under a disturbance library it holds "disturbance": w [steps][B][4]."""
+        control and the dict also holds "command" and "applied" [steps][B][3]; under a disturbance library it holds "disturbance": w [steps][B][4].  Under a
+        human library (set_humans) the sets decide the other car's driver, human_u is the script of their mode-2 sets, and the dict also holds "human_u" [steps][B][2], what
+        k_human handed the plant (equal to "human")."""
         def call(ptr, hu, hist):
             self._chk(self.lib.pg_simulate_safety_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu),
                                                       *(ptr(hist.get(k)) for k in ("state", "control", "other", "human", "V", "source"))), "pg_simulate_safety_dev")
@@ -658,7 +732,7 @@ class BatchedTrajectoryTrackingMPC:
         steps and, with record=True, a dict of histories: state [steps][B][6], applied [steps][B][3], V [steps][B], event [steps][B] (pg_node_event).
         measured=True (a sensor library is installed) appends the measured history [steps][B][6] to what is returned, estimated=True (an estimator library is installed) the
         estimated history [steps][B][6] behind it.  Under a disturbance library the dict also holds
-        "disturbance": w [steps][B][4]."""
+        "disturbance": w [steps][B][4], and under a human library (set_humans: the sets decide the driver, human_u is the script of their mode-2 sets) "human_u" [steps][B][2]."""
         def call(ptr, hu, hist):
             pf = self._pre_flag_dev(pre_flag, (steps, self.B))
             self._chk(self.lib.pg_simulate_node_dev(self.h, int(steps), C.c_double(dt), int(bool(use_HJI_policy)), self.HUMAN_MODES[human], ptr(hu), ptr(pf),

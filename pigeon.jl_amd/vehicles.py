@@ -119,3 +119,32 @@ def estimator(**overrides):
         if len(e["gain"]) != 6:
             raise ValueError(f"gain has {len(e['gain'])} entries, not one per channel of {ESTIMATOR_CHANNELS}")
     return e
+
+
+HUMAN_FIELDS = ("mode", "hold_steps", "step_on", "step_off", "gain", "omega_max", "a_min", "a_max", "sigma", "tau")
+HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2, "random": 3}
+
+
+def human(**overrides):
+    """One human set for set_humans (pg_human): the driver of the other car in the safety and node rollouts.  human() is the identity of mode 0 -- always active, a decision
+    at every step, gain 1, no limits --, and human(mode=m) for m in (0, 1, 2) or ("hold", "worst", "script") reproduces a rollout called with that human mode on a handle
+    without a library bit for bit; human(mode="worst", hold_steps=30, gain=0.6, step_on=40) overrides fields; mode 3 / "random" is the seeded driver (sigma, tau).
+    gain and sigma take one number for both of (omega, a) or a pair.  Build-defined: the reference only receives the other car from ROS."""
+    h = dict(mode=0, hold_steps=1, step_on=0, step_off=-1, gain=[1.0, 1.0], omega_max=math.inf, a_min=-math.inf, a_max=math.inf, sigma=[0.0, 0.0], tau=0.0)
+    for k, v in overrides.items():
+        if k not in h:
+            raise KeyError(f"{k} is not a field of a human set: {HUMAN_FIELDS}")
+        h[k] = v
+    if isinstance(h["mode"], str):
+        if h["mode"] not in HUMAN_MODES:
+            raise KeyError(f"{h['mode']} is not a human mode: {tuple(HUMAN_MODES)}")
+        h["mode"] = HUMAN_MODES[h["mode"]]
+    for name in ("gain", "sigma"):
+        v = h[name]
+        if isinstance(v, numbers.Real):                    # (numpy scalars included)
+            h[name] = [float(v)] * 2
+        else:
+            h[name] = [float(x) for x in v]
+            if len(h[name]) != 2:
+                raise ValueError(f"{name} has {len(h[name])} entries, not one per channel of (omega, a)")
+    return h
