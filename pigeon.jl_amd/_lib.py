@@ -47,21 +47,24 @@ SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_defaul
            "pg_get_solve_info", "pg_get_polish_info", "pg_get_multipliers", "pg_get_phase_ms", "pg_hji_lookup", "pg_hji_lookup_dev", "pg_hji_lookup8_dev", "pg_hji_grid_dims", "pg_hji_slice", "pg_get_hji_constraint", "pg_get_walls"]
 
 
+def _set_prototypes(name, ctype, seed=False):
+    """the prototypes every per-instance library has (pg_set_<name>_sets / _index, pg_clear_<name>_sets, pg_get_<name>_sets), and pg_set_<name>_seed of a seeded one"""
+    p = {f"pg_set_{name}_sets": [C.c_void_p, C.c_int32, C.POINTER(ctype)],
+         f"pg_set_{name}_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]}
+    if seed:
+        p[f"pg_set_{name}_seed"] = [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]
+    p[f"pg_clear_{name}_sets"] = [C.c_void_p]
+    p[f"pg_get_{name}_sets"] = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ctype), C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    return p
+
+
 # control-parameter library (include/pigeon_mpc.h: pg_set_control_param_sets and its companions)
-CONTROL_PARAM_SET_PROTOTYPES = {
-    "pg_set_control_param_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_control_params)],
-    "pg_set_control_param_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_clear_control_param_sets": [C.c_void_p],
-    "pg_get_control_param_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_control_params), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
-}
+CONTROL_PARAM_SET_PROTOTYPES = _set_prototypes("control_param", pg_control_params)
 
 
 # plant library and tracking summary (include/pigeon_mpc.h: pg_set_plant_sets and its companions, pg_get_tracking_state)
 PLANT_SET_PROTOTYPES = {
-    "pg_set_plant_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_vehicle)],
-    "pg_set_plant_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_clear_plant_sets": [C.c_void_p],
-    "pg_get_plant_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_vehicle), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    **_set_prototypes("plant", pg_vehicle),
     "pg_get_tracking_state": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
 }
 
@@ -73,11 +76,7 @@ class pg_sensor(C.Structure):
 
 # sensor library (include/pigeon_mpc.h: pg_set_sensor_sets and its companions)
 SENSOR_SET_PROTOTYPES = {
-    "pg_set_sensor_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_sensor)],
-    "pg_set_sensor_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_set_sensor_seed": [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)],
-    "pg_clear_sensor_sets": [C.c_void_p],
-    "pg_get_sensor_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_sensor), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    **_set_prototypes("sensor", pg_sensor, seed=True),
     "pg_sensor_draws": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)],
     "pg_get_measured_state": [C.c_void_p, C.POINTER(C.c_double)],
     "pg_set_measured_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
@@ -95,10 +94,7 @@ class pg_actuator_set(C.Structure):
 
 # actuator library (include/pigeon_mpc.h: pg_set_actuator_sets and its companions)
 ACTUATOR_SET_PROTOTYPES = {
-    "pg_set_actuator_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_actuator_set)],
-    "pg_set_actuator_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_clear_actuator_sets": [C.c_void_p],
-    "pg_get_actuator_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_actuator_set), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    **_set_prototypes("actuator", pg_actuator_set),
     "pg_set_applied_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
     "pg_set_command_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
     "pg_get_actuator_state": [C.c_void_p, C.POINTER(C.c_double)],
@@ -115,11 +111,7 @@ class pg_disturbance(C.Structure):
 
 # disturbance library (include/pigeon_mpc.h: pg_set_disturbance_sets and its companions)
 DISTURBANCE_SET_PROTOTYPES = {
-    "pg_set_disturbance_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_disturbance)],
-    "pg_set_disturbance_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_set_disturbance_seed": [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)],
-    "pg_clear_disturbance_sets": [C.c_void_p],
-    "pg_get_disturbance_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_disturbance), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    **_set_prototypes("disturbance", pg_disturbance, seed=True),
     "pg_disturbance_response": [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double)],
     "pg_get_disturbance_state": [C.c_void_p, C.POINTER(C.c_double)],
     "pg_set_disturbance_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
@@ -134,10 +126,7 @@ class pg_estimator(C.Structure):
 
 # estimator library (include/pigeon_mpc.h: pg_set_estimator_sets and its companions)
 ESTIMATOR_SET_PROTOTYPES = {
-    "pg_set_estimator_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_estimator)],
-    "pg_set_estimator_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_clear_estimator_sets": [C.c_void_p],
-    "pg_get_estimator_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_estimator), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    **_set_prototypes("estimator", pg_estimator),
     "pg_get_estimated_state": [C.c_void_p, C.POINTER(C.c_double)],
     "pg_set_estimated_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
     "pg_estimator_response": [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
@@ -152,11 +141,7 @@ class pg_human(C.Structure):
 
 # human library (include/pigeon_mpc.h: pg_set_human_sets and its companions)
 HUMAN_SET_PROTOTYPES = {
-    "pg_set_human_sets": [C.c_void_p, C.c_int32, C.POINTER(pg_human)],
-    "pg_set_human_index": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)],
-    "pg_set_human_seed": [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)],
-    "pg_clear_human_sets": [C.c_void_p],
-    "pg_get_human_sets": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(pg_human), C.c_int32, C.POINTER(C.c_int32), C.c_int32],
+    **_set_prototypes("human", pg_human, seed=True),
     "pg_get_human_state": [C.c_void_p, C.POINTER(C.c_double)],
     "pg_set_human_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
     "pg_human_response": [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
@@ -183,9 +168,11 @@ def load_library(precision="f64"):
     lib.pg_last_error.argtypes = [C.c_void_p]
     for s in SYMBOLS:
         getattr(lib, s)
-    for name, argtypes in list(CONTROL_PARAM_SET_PROTOTYPES.items()) + list(PLANT_SET_PROTOTYPES.items()) + list(SENSOR_SET_PROTOTYPES.items()) + list(ACTUATOR_SET_PROTOTYPES.items()) + list(DISTURBANCE_SET_PROTOTYPES.items()) + list(ESTIMATOR_SET_PROTOTYPES.items()) + list(HUMAN_SET_PROTOTYPES.items()):
-        getattr(lib, name).argtypes = argtypes
-        getattr(lib, name).restype = C.c_int
+    for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
+                       HUMAN_SET_PROTOTYPES):
+        for name, argtypes in prototypes.items():
+            getattr(lib, name).argtypes = argtypes
+            getattr(lib, name).restype = C.c_int
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)
     check_layout(lib)
     _libs[precision] = lib

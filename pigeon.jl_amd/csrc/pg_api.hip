@@ -23,7 +23,23 @@ struct IndexArray {
 // One library of per-instance sets: the sets as the caller installed them, their device records, the selection (setlib_install / setlib_clear / setlib_get below)
 template <class Host, class Dev> struct SetLib {
     IndexArray idx; std::vector<Host> sets; Dev* d = nullptr;
+    bool on() const { return !sets.empty(); }                                             // the host knows whether a library is installed: that alone adds its kernel to a rollout step
+    const int* index() const { return sets.size() > 1 ? idx.d : (const int*)nullptr; }    // what the kernels are handed: a library of at most one set needs no index
     void release() { if (d) (void)hipFree(d); d = nullptr; sets.clear(); idx.release(); }
+};
+template <class... P> static void dev_release(P*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+// One history registration (pg_set_*_history_dev): a device record [steps][B][width] of the caller's.  One-shot: the next rollout call takes it, whether it succeeds or not
+struct HistSlot {
+    real* buf = nullptr; int steps = 0;
+    void clear() { buf = nullptr; steps = 0; }
+    HistSlot take() { const HistSlot s = *this; clear(); return s; }
+    real* at(int k, int B, int width) const { return (buf && k < steps) ? buf + (size_t)k * B * width : (real*)nullptr; }      // record k; nullptr: not recorded
+};
+// The streams of a seeded library: the ids as installed (instances they do not cover: stream[b] = b), their device copy [capacity] (sync: uploaded when a rollout or a
+// *_response / pg_sensor_draws call first needs it and whenever the ids changed) and the seed, a launch argument
+struct SeedStreams {
+    unsigned long long* d = nullptr; bool dirty = true; std::vector<uint64_t> host; uint64_t seed = 0;
+    int sync(pg_handle* h);
 };
 
 struct pg_handle {
@@ -57,55 +73,59 @@ struct pg_handle {
     // tracking summary (option "tracking_summary"; pg_get_tracking_state): [cap][6] sums, steps [cap] then first_exit [cap] (k_track), allocated when the option is first used
     int tracking = 0; real* d_track = nullptr; int* d_track_i = nullptr;
     bool track_fresh = true;                                  // the tracking summary restarts at the next rollout step (the clock restarted since it was last written)
+    // ---- the five rollout libraries that keep state beside their sets: one record each.  lib: the sets and the selection; streams: a seeded library's; hist: the one-shot
+    // history registration(s); fresh: no state of the previous step exists, the law restarts at the next step under the library (restart_on_clock lists them); valid: the
+    // record the getter reads was written by a rollout step since the inputs were installed (restart_on_inputs); steps_stat: read-only option "stat_<library>_steps";
+    // cleared(): what pg_clear_*_sets resets beside the sets; release(): pg_destroy ----
     // sensor library (pg_set_sensor_sets / pg_set_sensor_index / pg_set_sensor_seed): what the controller of a rollout step is handed in place of the true state.  Beside the
-    // sets: the stream ids [cap] (host as installed; uploaded when a rollout or pg_sensor_draws first needs them and whenever they changed), the seed, the measured state
-    // d_meas [cap][6] and, with the tracking summary, the projection of the TRUE state d_sep_true [cap][4].  Nothing is allocated without a library
-    SetLib<pg_sensor, DevSensor> sens{{"sensor", "pg_set_sensor_index"}};
-    unsigned long long* d_sens_stream = nullptr; bool sens_stream_dirty = true; std::vector<uint64_t> sens_stream; uint64_t sens_seed = 0;
-    real *d_meas = nullptr, *d_sep_true = nullptr; bool meas_valid = false;
-    real* meas_hist = nullptr; int meas_hist_steps = 0;          // pg_set_measured_history_dev: one-shot, consumed by the next rollout call
-    int64_t stat_sensor_steps = 0;                                // read-only option "stat_sensor_steps"
+    // sets: the streams and the seed, the measured state meas [cap][6] and, with the tracking summary, the projection of the TRUE state sep_true [cap][4].  Nothing is
+    // allocated without a library.  No `fresh`: the law has no state.  Clearing the sets leaves seed and streams as they are
+    struct Sensor {
+        SetLib<pg_sensor, DevSensor> lib{{"sensor", "pg_set_sensor_index"}}; SeedStreams streams; HistSlot hist;      // hist: pg_set_measured_history_dev
+        real *meas = nullptr, *sep_true = nullptr; bool valid = false; int64_t steps_stat = 0;
+        void cleared() { valid = false; hist.clear(); }
+        void release() { lib.release(); dev_release(streams.d, meas, sep_true); }
+    } sensor;
     // actuator library (pg_set_actuator_sets / pg_set_actuator_index): what the plant of a rollout step is handed in place of the command.  Beside the sets, allocated when a
-    // rollout first runs under a library: the actuator's position d_act [cap][3], the command ring d_act_ring [PG_ACT_MAX_DELAY][cap][3], d_plant_u [cap][3] (the plant
-    // kernel's `control`: a_k going in, the next command coming out) and, while some installed set has feedback == 1, d_seen [cap][3] (the compute kernels' current_control)
-    SetLib<pg_actuator_set, DevActuator> acts{{"actuator", "pg_set_actuator_index"}};
-    real *d_act = nullptr, *d_act_ring = nullptr, *d_plant_u = nullptr, *d_seen = nullptr;
-    bool act_feedback = false;                                    // some installed set has feedback == 1
-    bool act_fresh = true;                                        // the actuator state restarts at the next step under a library (the clock restarted, or no step ran under one since)
-    real *applied_hist = nullptr, *command_hist = nullptr; int applied_hist_steps = 0, command_hist_steps = 0;      // pg_set_applied_history_dev / pg_set_command_history_dev: one-shot
-    int64_t stat_actuator_steps = 0;                              // read-only option "stat_actuator_steps"
+    // rollout first runs under a library: the actuator's position pos [cap][3], the command ring [PG_ACT_MAX_DELAY][cap][3], plant_u [cap][3] (the plant kernel's
+    // `control`: a_k going in, the next command coming out) and, while some installed set has feedback == 1, seen [cap][3] (the compute kernels' current_control).
+    // No `valid`: before the first step since the clock restarted the position is the command (pg_get_actuator_state)
+    struct Actuator {
+        SetLib<pg_actuator_set, DevActuator> lib{{"actuator", "pg_set_actuator_index"}}; HistSlot applied_hist, command_hist;      // pg_set_applied_history_dev / pg_set_command_history_dev
+        real *pos = nullptr, *ring = nullptr, *plant_u = nullptr, *seen = nullptr;
+        bool feedback = false;                                    // some installed set has feedback == 1
+        bool fresh = true; int64_t steps_stat = 0;
+        void cleared() { feedback = false; fresh = true; applied_hist.clear(); command_hist.clear(); }      // (a library installed later starts from the command it finds)
+        void release() { lib.release(); dev_release(pos, ring, plant_u, seen); }
+    } actuator;
     // disturbance library (pg_set_disturbance_sets / pg_set_disturbance_index / pg_set_disturbance_seed): what acts on the ego plant of a rollout step from outside.  Beside
-    // the sets: the stream ids [cap] and the seed (as the sensor library keeps its own), and, allocated when a rollout first runs under a library: the gust state
-    // d_dist_n [cap][2], this step's w d_dist_w [cap][4] (k_disturb writes it, the library kernel's <DistW> instantiation reads it) and d_dist_veh, ONE record holding the handle's own vehicle:
+    // the sets: the streams and the seed (its own, as the sensor library keeps its own), and, allocated when a rollout first runs under a library: the gust state
+    // n [cap][2], this step's w [cap][4] (k_disturb writes it, the library kernel's <DistW> instantiation reads it) and veh, ONE record holding the handle's own vehicle:
     // the library of one that instantiation is handed when no plant library is installed
-    SetLib<pg_disturbance, DevDisturbance> dists{{"disturbance", "pg_set_disturbance_index"}};
-    unsigned long long* d_dist_stream = nullptr; bool dist_stream_dirty = true; std::vector<uint64_t> dist_stream; uint64_t dist_seed = 0;
-    real *d_dist_n = nullptr, *d_dist_w = nullptr; DevVehicle* d_dist_veh = nullptr;
-    bool dist_fresh = true;                                       // no gust state of the previous step exists (the clock restarted, or no step ran under a library since one was installed)
-    bool dist_valid = false;                                      // d_dist_w holds w of a rollout step since the inputs were installed
-    real* dist_hist = nullptr; int dist_hist_steps = 0;           // pg_set_disturbance_history_dev: one-shot, consumed by the next rollout call
-    int64_t stat_disturbance_steps = 0;                           // read-only option "stat_disturbance_steps"
+    struct Disturbance {
+        SetLib<pg_disturbance, DevDisturbance> lib{{"disturbance", "pg_set_disturbance_index"}}; SeedStreams streams; HistSlot hist;      // hist: pg_set_disturbance_history_dev
+        real *n = nullptr, *w = nullptr; DevVehicle* veh = nullptr; bool fresh = true, valid = false; int64_t steps_stat = 0;
+        void cleared() { fresh = true; valid = false; hist.clear(); }      // (a library installed later starts a gust of its own)
+        void release() { lib.release(); dev_release(streams.d, n, w, veh); }
+    } disturbance;
     // estimator library (pg_set_estimator_sets / pg_set_estimator_index): a fixed-gain observer between the sensor and the controller of a rollout step.  Beside the sets,
-    // allocated at the first install: the estimate d_est [cap][6] (what the gate and the compute calls of a step are handed as the state) and d_est_u [cap][3], the control
+    // allocated at the first install: the estimate x [cap][6] (what the gate and the compute calls of a step are handed as the state) and u [cap][3], the control
     // the controller was handed at the previous step (it drives the prior).  Nothing is allocated without a library
-    SetLib<pg_estimator, DevEstimator> ests{{"estimator", "pg_set_estimator_index"}};
-    real *d_est = nullptr, *d_est_u = nullptr;
-    bool est_fresh = true;                                        // no estimate of the previous step exists (new inputs, the clock restarted, or the library was cleared)
-    bool est_valid = false;                                       // d_est holds the estimate of a rollout step since the inputs were installed
-    real* est_hist = nullptr; int est_hist_steps = 0;             // pg_set_estimated_history_dev: one-shot, consumed by the next rollout call
-    int64_t stat_estimator_steps = 0;                             // read-only option "stat_estimator_steps"
-    // human library (pg_set_human_sets / pg_set_human_index / pg_set_human_seed): the driver of the other car in the safety and node rollouts.  Beside the sets: the stream
-    // ids [cap] and the seed (its own, as the disturbance library keeps its own), and, allocated when a rollout first runs under a library: the driver's control
-    // d_human_u [cap][2] (k_human writes it, the step's plant launch reads it as the script of its human mode 2) and the random driver's state d_human_n [cap][2].
-    // human_script: some installed set has mode 2 (the rollouts then want human_u_dev)
-    SetLib<pg_human, DevHuman> humans{{"human", "pg_set_human_index"}};
-    unsigned long long* d_human_stream = nullptr; bool human_stream_dirty = true; std::vector<uint64_t> human_stream; uint64_t human_seed = 0;
-    real *d_human_u = nullptr, *d_human_n = nullptr;
-    bool human_script = false;
-    bool human_fresh = true;                                      // no u / n of the previous step exists (the clock restarted, or no step ran under a library since one was installed)
-    bool human_valid = false;                                     // d_human_u holds u of a rollout step since the inputs were installed
-    real* human_hist = nullptr; int human_hist_steps = 0;         // pg_set_human_history_dev: one-shot, consumed by the next rollout call
-    int64_t stat_human_steps = 0;                                 // read-only option "stat_human_steps"
+    struct Estimator {
+        SetLib<pg_estimator, DevEstimator> lib{{"estimator", "pg_set_estimator_index"}}; HistSlot hist;      // hist: pg_set_estimated_history_dev
+        real *x = nullptr, *u = nullptr; bool fresh = true, valid = false; int64_t steps_stat = 0;
+        void cleared() { fresh = true; valid = false; hist.clear(); }      // (a library installed later starts from its first measurement)
+        void release() { lib.release(); dev_release(x, u); }
+    } estimator;
+    // human library (pg_set_human_sets / pg_set_human_index / pg_set_human_seed): the driver of the other car in the safety and node rollouts.  Beside the sets: the streams
+    // and the seed (its own), and, allocated when a rollout first runs under a library: the driver's control u [cap][2] (k_human writes it, the step's plant launch reads
+    // it as the script of its human mode 2) and the random driver's state n [cap][2].  script: some installed set has mode 2 (the rollouts then want human_u_dev)
+    struct Human {
+        SetLib<pg_human, DevHuman> lib{{"human", "pg_set_human_index"}}; SeedStreams streams; HistSlot hist;      // hist: pg_set_human_history_dev
+        real *u = nullptr, *n = nullptr; bool script = false, fresh = true, valid = false; int64_t steps_stat = 0;
+        void cleared() { script = false; fresh = true; valid = false; hist.clear(); }      // (a library installed later starts a driver of its own)
+        void release() { lib.release(); dev_release(streams.d, u, n); }
+    } human;
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -171,6 +191,24 @@ struct pg_handle {
 #define REQUIRE(h, cond, msg) do { if (!(cond)) { if (h) (h)->err = (msg); return PG_ERR_INVALID; } } while (0)
 
 static std::string g_create_error;
+
+// the stream ids of a seeded library on the device, [capacity]: the installed ones, then stream[b] = b
+int SeedStreams::sync(pg_handle* h) {
+    if (d && !dirty) return PG_OK;
+    const size_t cap = (size_t)h->cfg.batch_capacity;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!d) HIPCHK(h, hipMalloc((void**)&d, cap * sizeof(unsigned long long)));
+    std::vector<unsigned long long> full(cap);
+    for (size_t b = 0; b < cap; b++) full[b] = b < host.size() ? (unsigned long long)host[b] : (unsigned long long)b;
+    HIPCHK(h, hipMemcpy(d, full.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    dirty = false;
+    return PG_OK;
+}
+// a device buffer of `count` elements that is allocated when it is first needed
+template <class T> static int ensure(pg_handle* h, T*& p, size_t count) {
+    if (!p) HIPCHK(h, hipMalloc((void**)&p, count * sizeof(T)));
+    return PG_OK;
+}
 
 // ---- The device words the launches share: each layout is defined HERE only -- the allocations take their sizes from it, every launch its addresses. ----
 // d_todo [cap + CTL_WORDS] (the words zeroed by pg_create): the to-do list [cap] one solve launch files for the next, then the control words of the solve launches
@@ -358,9 +396,9 @@ int pg_default_config_decoupled(pg_config* c) {
 
 static void free_all(pg_handle* h) {
     void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i, h->d_sens_stream, h->d_meas, h->d_sep_true, h->d_act, h->d_act_ring, h->d_plant_u, h->d_seen, h->d_dist_stream, h->d_dist_n, h->d_dist_w, h->d_dist_veh, h->d_est, h->d_est_u, h->d_human_stream, h->d_human_u, h->d_human_n};
+                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sens.release(); h->acts.release(); h->dists.release(); h->ests.release(); h->humans.release();
+    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sensor.release(); h->actuator.release(); h->disturbance.release(); h->estimator.release(); h->human.release();
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
     if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
@@ -577,11 +615,11 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "lat_wtau") return R(&C.lat_wtau, 1e-300, 1e300);
     // read-only launch statistics of this handle
     if (n == "stat_pipelined_launches") return S(&h->stat_pipelined);
-    if (n == "stat_sensor_steps") return S(&h->stat_sensor_steps);
-    if (n == "stat_actuator_steps") return S(&h->stat_actuator_steps);
-    if (n == "stat_disturbance_steps") return S(&h->stat_disturbance_steps);
-    if (n == "stat_estimator_steps") return S(&h->stat_estimator_steps);
-    if (n == "stat_human_steps") return S(&h->stat_human_steps);
+    if (n == "stat_sensor_steps") return S(&h->sensor.steps_stat);
+    if (n == "stat_actuator_steps") return S(&h->actuator.steps_stat);
+    if (n == "stat_disturbance_steps") return S(&h->disturbance.steps_stat);
+    if (n == "stat_estimator_steps") return S(&h->estimator.steps_stat);
+    if (n == "stat_human_steps") return S(&h->human.steps_stat);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -720,6 +758,69 @@ static int setlib_get(pg_handle* h, const char* who, const SetLib<Host, Dev>& L,
     if (out) for (int k = 0; k < n && k < max_sets; k++) out[k] = L.sets[(size_t)k];
     if (index) for (int b = 0; b < B; b++) index[b] = b < L.idx.covered() ? L.idx.host[(size_t)b] : -1;
     return PG_OK;
+}
+template <class Host, class Dev> static int index_covers(pg_handle* h, const SetLib<Host, Dev>& L) { return index_covers(h, L.sets.size(), L.idx); }
+// field_problem(set) names the field that is wrong; the refusal of the install names the set as well: "set k: field" (`why` keeps the text while setlib_install reads it)
+template <class Host, class FieldProblem>
+static auto numbered_problem(FieldProblem field_problem, const Host* sets, std::string& why) {
+    return [field_problem, sets, &why](const Host& s) -> const char* {
+        const char* f = field_problem(s);
+        if (!f) return nullptr;
+        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
+        return why.c_str();
+    };
+}
+// ---- what the rollout libraries keep beside their sets (pg_handle: one record per library) ----
+// pg_set_*_history_dev: registers buf [steps][B][width] with the next rollout call (nullptr: drops the registration).  hint: what to record without the library
+template <class Host, class Dev>
+static int history_register(pg_handle* h, const char* who_, const SetLib<Host, Dev>& L, const char* hint, HistSlot& slot, pg_real_dev* buf, int32_t steps) {
+    if (!buf) { slot.clear(); return PG_OK; }
+    const std::string who(who_);
+    REQUIRE(h, steps >= 1, who + ": steps >= 1 required");
+    if (!L.on()) { h->err = who + ": no " + L.idx.what + " library installed " + hint; return PG_ERR_STATE; }
+    slot = HistSlot{(real*)buf, steps};
+    return PG_OK;
+}
+// pg_set_*_seed: the seed and the stream ids of the first B instances (nullptr: stream[b] = b for all)
+static int seed_install(pg_handle* h, const char* who, SeedStreams& S, uint64_t seed, int32_t B, const uint64_t* stream) {
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, std::string(who) + ": need 1 <= B <= batch_capacity");
+    S.seed = seed;                                              // (a launch argument: a rollout already queued keeps the seed it was launched with)
+    if (stream) S.host.assign(stream, stream + B); else S.host.clear();      // instances the array does not cover: stream[b] = b
+    S.dirty = true;
+    return PG_OK;
+}
+// The only two places that list what restarts.  The rollouts' clock restarted (clock_start; new inputs restart it too): every law starts from no previous step, and
+// the safety summary, the node counts and the tracking summary with it.  New inputs (set_inputs) also void what the *_state getters read.  The sensor's law has no
+// state, and the actuator's getter falls back to the command
+static void restart_on_clock(pg_handle* h) {
+    h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true;
+    h->actuator.fresh = true; h->disturbance.fresh = true; h->estimator.fresh = true; h->human.fresh = true;
+}
+static void restart_on_inputs(pg_handle* h) {
+    restart_on_clock(h);
+    h->sensor.valid = false; h->disturbance.valid = false; h->estimator.valid = false; h->human.valid = false;
+}
+// The scaffold of the four pg_*_response calls (the law of one library alone, on scratch memory of the call).  The shared preconditions in their order: inputs, a library,
+// `refuse` (the entry point's own reason for PG_ERR_INVALID, or nullptr), an index that covers the batch.  Then the streams of a seeded library (S, or nullptr) and
+// `scratch` reals; body(d, result) uploads, launches and names the n_out reals to download.  A failure is waited out before the scratch memory is freed
+template <class Host, class Dev, class Body>
+static int response_call(pg_handle* h, const char* who_, const SetLib<Host, Dev>& L, const char* refuse, SeedStreams* S, size_t scratch, double* out, size_t n_out, Body body) {
+    const std::string who(who_);
+    if (h->B <= 0) { h->err = who + ": no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
+    if (!L.on()) { h->err = who + ": no " + L.idx.what + " library installed"; return PG_ERR_STATE; }
+    REQUIRE(h, !refuse, refuse);
+    if (index_covers(h, L)) return PG_ERR_STATE;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = S ? S->sync(h) : PG_OK; if (rc) return rc;
+    real* d = nullptr;
+    HIPCHK(h, hipMalloc((void**)&d, scratch * sizeof(real)));
+    const real* result = nullptr;
+    rc = body(d, result);
+    if (!rc) { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { h->err = who + ": " + hipGetErrorString(e); rc = PG_ERR_HIP; } }
+    if (!rc) rc = down(h, out, result, n_out);
+    else (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    return rc;
 }
 extern "C" {
 
@@ -878,53 +979,36 @@ static const char* sensor_set_problem(const pg_sensor& s) {
 static void fill_dev_sensor(DevSensor& S, const pg_sensor& s) { for (int c = 0; c < 6; c++) { S.sigma[c] = (real)s.sigma[c]; S.bias[c] = (real)s.bias[c]; } }
 int pg_set_sensor_sets(pg_handle* h, int32_t n_sets, const pg_sensor* sets) {
     if (!h) return PG_ERR_INVALID;
-    return setlib_install(h, "pg_set_sensor_sets", h->sens, n_sets, sets, sensor_set_problem, fill_dev_sensor);      // (seed and streams persist)
+    return setlib_install(h, "pg_set_sensor_sets", h->sensor.lib, n_sets, sets, sensor_set_problem, fill_dev_sensor);      // (seed and streams persist)
 }
 int pg_set_sensor_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    return index_install(h, (int)h->sens.sets.size(), h->sens.idx, B, index);
+    return index_install(h, (int)h->sensor.lib.sets.size(), h->sensor.lib.idx, B, index);
 }
 int pg_set_sensor_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_set_sensor_seed: need 1 <= B <= batch_capacity");
-    h->sens_seed = seed;                                        // (a launch argument: a rollout already queued keeps the seed it was launched with)
-    if (stream) h->sens_stream.assign(stream, stream + B); else h->sens_stream.clear();      // instances the array does not cover: stream[b] = b
-    h->sens_stream_dirty = true;
-    return PG_OK;
+    return seed_install(h, "pg_set_sensor_seed", h->sensor.streams, seed, B, stream);
 }
 int pg_clear_sensor_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    const int rc = setlib_clear(h, h->sens); if (rc) return rc;
-    h->meas_valid = false; h->meas_hist = nullptr; h->meas_hist_steps = 0;
+    const int rc = setlib_clear(h, h->sensor.lib); if (rc) return rc;
+    h->sensor.cleared();
     return PG_OK;
 }
 int pg_get_sensor_sets(pg_handle* h, int32_t* n_sets, pg_sensor* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    return setlib_get(h, "pg_get_sensor_sets", h->sens, n_sets, out, max_sets, index, B);
+    return setlib_get(h, "pg_get_sensor_sets", h->sensor.lib, n_sets, out, max_sets, index, B);
 }
-// the stream ids of a seeded library on the device, [capacity]: the installed ones, then stream[b] = b
-static int streams_sync(pg_handle* h, unsigned long long*& d, bool& dirty, const std::vector<uint64_t>& installed) {
-    if (d && !dirty) return PG_OK;
-    const size_t cap = (size_t)h->cfg.batch_capacity;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!d) HIPCHK(h, hipMalloc((void**)&d, cap * sizeof(unsigned long long)));
-    std::vector<unsigned long long> full(cap);
-    for (size_t b = 0; b < cap; b++) full[b] = b < installed.size() ? (unsigned long long)installed[b] : (unsigned long long)b;
-    HIPCHK(h, hipMemcpy(d, full.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    dirty = false;
-    return PG_OK;
-}
-static int sensor_streams_sync(pg_handle* h) { return streams_sync(h, h->d_sens_stream, h->sens_stream_dirty, h->sens_stream); }
 int pg_sensor_draws(pg_handle* h, int32_t step0, int32_t steps, int32_t B, double* z) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, step0 >= 0 && steps >= 1 && z, "pg_sensor_draws: need step0 >= 0, steps >= 1 and the output array");
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_sensor_draws: need 1 <= B <= batch_capacity");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = sensor_streams_sync(h); if (rc) return rc;
+    int rc = h->sensor.streams.sync(h); if (rc) return rc;
     const size_t n = (size_t)steps * (size_t)B * 6;
     real* d = nullptr;
     HIPCHK(h, hipMalloc((void**)&d, n * sizeof(real)));
-    hipLaunchKernelGGL(k_sensor_draws, dim3((unsigned)(((size_t)steps * B + 63) / 64)), dim3(64), 0, h->stream, (int)B, (int)step0, (int)steps, h->d_sens_stream, (unsigned long long)h->sens_seed, d);
+    hipLaunchKernelGGL(k_sensor_draws, dim3((unsigned)(((size_t)steps * B + 63) / 64)), dim3(64), 0, h->stream, (int)B, (int)step0, (int)steps, h->sensor.streams.d, (unsigned long long)h->sensor.streams.seed, d);
     std::vector<real> tmp(n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), d, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
@@ -936,17 +1020,13 @@ int pg_sensor_draws(pg_handle* h, int32_t step0, int32_t steps, int32_t B, doubl
 }
 int pg_set_measured_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
     if (!h) return PG_ERR_INVALID;
-    if (!buf) { h->meas_hist = nullptr; h->meas_hist_steps = 0; return PG_OK; }
-    REQUIRE(h, steps >= 1, "pg_set_measured_history_dev: steps >= 1 required");
-    if (h->sens.sets.empty()) { h->err = "pg_set_measured_history_dev: no sensor library installed (the measured state is the true one: record state_hist)"; return PG_ERR_STATE; }
-    h->meas_hist = (real*)buf; h->meas_hist_steps = steps;
-    return PG_OK;
+    return history_register(h, "pg_set_measured_history_dev", h->sensor.lib, "(the measured state is the true one: record state_hist)", h->sensor.hist, buf, steps);
 }
 static int check_ready(pg_handle* h);
 int pg_get_measured_state(pg_handle* h, double* measured) {
     int rc = check_ready(h); if (rc) return rc;
-    if (!h->meas_valid || !h->d_meas) { h->err = "pg_get_measured_state: no rollout step under a sensor library since the inputs were installed"; return PG_ERR_STATE; }
-    return down(h, measured, h->d_meas, (size_t)h->B * 6);
+    if (!h->sensor.valid || !h->sensor.meas) { h->err = "pg_get_measured_state: no rollout step under a sensor library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, measured, h->sensor.meas, (size_t)h->B * 6);
 }
 
 // ---- actuator library: the control the PLANT of a rollout step integrates, a_k = actuator(c_{k - delay}, a_{k-1}) per channel (k_actuate).  Build-defined (the reference
@@ -966,72 +1046,51 @@ static void fill_dev_actuator(DevActuator& A, const pg_actuator_set& s) {
 int pg_set_actuator_sets(pg_handle* h, int32_t n_sets, const pg_actuator_set* sets) {
     if (!h) return PG_ERR_INVALID;
     std::string why;                                            // (the message names the field and the set)
-    const int rc = setlib_install(h, "pg_set_actuator_sets", h->acts, n_sets, sets, [&](const pg_actuator_set& s) -> const char* {
-        const char* f = actuator_field_problem(s);
-        if (!f) return nullptr;
-        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
-        return why.c_str();
-    }, fill_dev_actuator);
+    const int rc = setlib_install(h, "pg_set_actuator_sets", h->actuator.lib, n_sets, sets, numbered_problem(actuator_field_problem, sets, why), fill_dev_actuator);
     if (rc) return rc;
-    h->act_feedback = false;
-    for (const pg_actuator_set& s : h->acts.sets) h->act_feedback = h->act_feedback || s.feedback == 1;
+    h->actuator.feedback = false;
+    for (const pg_actuator_set& s : h->actuator.lib.sets) h->actuator.feedback = h->actuator.feedback || s.feedback == 1;
     return PG_OK;
 }
 int pg_set_actuator_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    return index_install(h, (int)h->acts.sets.size(), h->acts.idx, B, index);
+    return index_install(h, (int)h->actuator.lib.sets.size(), h->actuator.lib.idx, B, index);
 }
 int pg_clear_actuator_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    const int rc = setlib_clear(h, h->acts); if (rc) return rc;
-    h->act_feedback = false; h->act_fresh = true;               // (a library installed later starts from the command it finds)
-    h->applied_hist = nullptr; h->command_hist = nullptr; h->applied_hist_steps = 0; h->command_hist_steps = 0;
+    const int rc = setlib_clear(h, h->actuator.lib); if (rc) return rc;
+    h->actuator.cleared();
     return PG_OK;
 }
 int pg_get_actuator_sets(pg_handle* h, int32_t* n_sets, pg_actuator_set* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    return setlib_get(h, "pg_get_actuator_sets", h->acts, n_sets, out, max_sets, index, B);
-}
-static int actuator_set_history(pg_handle* h, const char* who, real*& slot, int& slot_steps, pg_real_dev* buf, int32_t steps) {
-    if (!h) return PG_ERR_INVALID;
-    if (!buf) { slot = nullptr; slot_steps = 0; return PG_OK; }
-    REQUIRE(h, steps >= 1, std::string(who) + ": steps >= 1 required");
-    if (h->acts.sets.empty()) { h->err = std::string(who) + ": no actuator library installed (applied = command: record control_hist)"; return PG_ERR_STATE; }
-    slot = (real*)buf; slot_steps = steps;
-    return PG_OK;
+    return setlib_get(h, "pg_get_actuator_sets", h->actuator.lib, n_sets, out, max_sets, index, B);
 }
 int pg_set_applied_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
-    return h ? actuator_set_history(h, "pg_set_applied_history_dev", h->applied_hist, h->applied_hist_steps, buf, steps) : PG_ERR_INVALID;
+    if (!h) return PG_ERR_INVALID;
+    return history_register(h, "pg_set_applied_history_dev", h->actuator.lib, "(applied = command: record control_hist)", h->actuator.applied_hist, buf, steps);
 }
 int pg_set_command_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
-    return h ? actuator_set_history(h, "pg_set_command_history_dev", h->command_hist, h->command_hist_steps, buf, steps) : PG_ERR_INVALID;
+    if (!h) return PG_ERR_INVALID;
+    return history_register(h, "pg_set_command_history_dev", h->actuator.lib, "(applied = command: record control_hist)", h->actuator.command_hist, buf, steps);
 }
 int pg_get_actuator_state(pg_handle* h, double* applied) {
     int rc = check_ready(h); if (rc) return rc;
-    const bool stepped = !h->acts.sets.empty() && !h->act_fresh && h->d_act;      // (else: no step under a library since the clock restarted -- the position is the command)
-    return down(h, applied, stepped ? h->d_act : h->d_control, (size_t)h->B * 3);
+    const bool stepped = h->actuator.lib.on() && !h->actuator.fresh && h->actuator.pos;      // (else: no step under a library since the clock restarted -- the position is the command)
+    return down(h, applied, stepped ? h->actuator.pos : h->d_control, (size_t)h->B * 3);
 }
 int pg_actuator_response(pg_handle* h, int32_t steps, double dt, const double* commands, double* applied) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, steps >= 1 && dt > 0.0 && commands && applied, "pg_actuator_response: steps >= 1, dt > 0 and both arrays required");
-    if (h->B <= 0) { h->err = "pg_actuator_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
-    if (h->acts.sets.empty()) { h->err = "pg_actuator_response: no actuator library installed"; return PG_ERR_STATE; }
-    if (index_covers(h, h->acts.sets.size(), h->acts.idx)) return PG_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B;
     const size_t n = (size_t)steps * (size_t)B * 3;
-    real* d = nullptr;                                           // scratch of the call: commands, applied, ring
-    HIPCHK(h, hipMalloc((void**)&d, (2 * n + (size_t)PG_ACT_MAX_DELAY * B * 3) * sizeof(real)));
-    int rc = up(h, d, commands, n);
-    if (!rc) {
-        hipLaunchKernelGGL(k_actuator_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, (int)steps, (real)dt, h->acts.d,
-                           h->acts.sets.size() > 1 ? h->acts.idx.d : (const int*)nullptr, d + 2 * n, d, d + n);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("pg_actuator_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
-    }
-    if (!rc) rc = down(h, applied, d + n, n);
-    (void)hipFree(d);
-    return rc;
+    // scratch of the call: commands, applied, ring
+    return response_call(h, "pg_actuator_response", h->actuator.lib, nullptr, nullptr, 2 * n + (size_t)PG_ACT_MAX_DELAY * B * 3, applied, n, [&](real* d, const real*& result) -> int {
+        const int rc = up(h, d, commands, n); if (rc) return rc;
+        hipLaunchKernelGGL(k_actuator_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, (int)steps, (real)dt, h->actuator.lib.d, h->actuator.lib.index(), d + 2 * n, d, d + n);
+        result = d + n;
+        return PG_OK;
+    });
 }
 
 // ---- disturbance library: what acts on the EGO PLANT of a rollout step from outside, w = (wFx, wFy, wMz, wmu) per instance (k_disturb; the <DistW> instantiations of the library kernels).
@@ -1055,68 +1114,47 @@ static void fill_dev_disturbance(DevDisturbance& D, const pg_disturbance& s) {
 int pg_set_disturbance_sets(pg_handle* h, int32_t n_sets, const pg_disturbance* sets) {
     if (!h) return PG_ERR_INVALID;
     std::string why;                                            // (the message names the field and the set; seed, streams and the gust state persist)
-    return setlib_install(h, "pg_set_disturbance_sets", h->dists, n_sets, sets, [&](const pg_disturbance& s) -> const char* {
-        const char* f = disturbance_field_problem(s);
-        if (!f) return nullptr;
-        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
-        return why.c_str();
-    }, fill_dev_disturbance);
+    return setlib_install(h, "pg_set_disturbance_sets", h->disturbance.lib, n_sets, sets, numbered_problem(disturbance_field_problem, sets, why), fill_dev_disturbance);
 }
 int pg_set_disturbance_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    return index_install(h, (int)h->dists.sets.size(), h->dists.idx, B, index);
+    return index_install(h, (int)h->disturbance.lib.sets.size(), h->disturbance.lib.idx, B, index);
 }
 int pg_set_disturbance_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_set_disturbance_seed: need 1 <= B <= batch_capacity");
-    h->dist_seed = seed;                                        // (a launch argument: a rollout already queued keeps the seed it was launched with)
-    if (stream) h->dist_stream.assign(stream, stream + B); else h->dist_stream.clear();      // instances the array does not cover: stream[b] = b
-    h->dist_stream_dirty = true;
-    return PG_OK;
+    return seed_install(h, "pg_set_disturbance_seed", h->disturbance.streams, seed, B, stream);
 }
 int pg_clear_disturbance_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    const int rc = setlib_clear(h, h->dists); if (rc) return rc;
-    h->dist_fresh = true; h->dist_valid = false; h->dist_hist = nullptr; h->dist_hist_steps = 0;      // (a library installed later starts a gust of its own)
+    const int rc = setlib_clear(h, h->disturbance.lib); if (rc) return rc;
+    h->disturbance.cleared();
     return PG_OK;
 }
 int pg_get_disturbance_sets(pg_handle* h, int32_t* n_sets, pg_disturbance* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    return setlib_get(h, "pg_get_disturbance_sets", h->dists, n_sets, out, max_sets, index, B);
+    return setlib_get(h, "pg_get_disturbance_sets", h->disturbance.lib, n_sets, out, max_sets, index, B);
 }
 int pg_set_disturbance_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
     if (!h) return PG_ERR_INVALID;
-    if (!buf) { h->dist_hist = nullptr; h->dist_hist_steps = 0; return PG_OK; }
-    REQUIRE(h, steps >= 1, "pg_set_disturbance_history_dev: steps >= 1 required");
-    if (h->dists.sets.empty()) { h->err = "pg_set_disturbance_history_dev: no disturbance library installed (w = (0, 0, 0, 1) at every step)"; return PG_ERR_STATE; }
-    h->dist_hist = (real*)buf; h->dist_hist_steps = steps;
-    return PG_OK;
+    return history_register(h, "pg_set_disturbance_history_dev", h->disturbance.lib, "(w = (0, 0, 0, 1) at every step)", h->disturbance.hist, buf, steps);
 }
 int pg_get_disturbance_state(pg_handle* h, double* w) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->dists.sets.empty() || !h->dist_valid || !h->d_dist_w) { h->err = "pg_get_disturbance_state: no rollout step under a disturbance library since the inputs were installed"; return PG_ERR_STATE; }
-    return down(h, w, h->d_dist_w, (size_t)h->B * 4);
+    if (!h->disturbance.lib.on() || !h->disturbance.valid || !h->disturbance.w) { h->err = "pg_get_disturbance_state: no rollout step under a disturbance library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, w, h->disturbance.w, (size_t)h->B * 4);
 }
 int pg_disturbance_response(pg_handle* h, int32_t step0, int32_t steps, double dt, double* w_out) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, step0 >= 0 && steps >= 1 && dt > 0.0 && w_out, "pg_disturbance_response: step0 >= 0, steps >= 1, dt > 0 and the output array required");
-    if (h->B <= 0) { h->err = "pg_disturbance_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
-    if (h->dists.sets.empty()) { h->err = "pg_disturbance_response: no disturbance library installed"; return PG_ERR_STATE; }
-    if (index_covers(h, h->dists.sets.size(), h->dists.idx)) return PG_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = streams_sync(h, h->d_dist_stream, h->dist_stream_dirty, h->dist_stream); if (rc) return rc;
     const int B = h->B;
     const size_t n = (size_t)steps * (size_t)B * 4;
-    real* d = nullptr;                                           // scratch of the call (the gust state lives in the lanes' registers)
-    HIPCHK(h, hipMalloc((void**)&d, n * sizeof(real)));
-    hipLaunchKernelGGL(k_disturbance_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, (int)step0, (int)steps, (real)dt, h->dists.d,
-                       h->dists.sets.size() > 1 ? h->dists.idx.d : (const int*)nullptr, h->d_dist_stream, (unsigned long long)h->dist_seed, d);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("pg_disturbance_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
-    if (!rc) rc = down(h, w_out, d, n);
-    else (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
+    // scratch of the call: w (the gust state lives in the lanes' registers)
+    return response_call(h, "pg_disturbance_response", h->disturbance.lib, nullptr, &h->disturbance.streams, n, w_out, n, [&](real* d, const real*& result) -> int {
+        hipLaunchKernelGGL(k_disturbance_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, (int)step0, (int)steps, (real)dt, h->disturbance.lib.d, h->disturbance.lib.index(),
+                           h->disturbance.streams.d, (unsigned long long)h->disturbance.streams.seed, d);
+        result = d;
+        return PG_OK;
+    });
 }
 
 // ---- estimator library: the state the CONTROLLER of a rollout step reads, a fixed-gain observer on the sensor's output, xh = p + gain (y - p) per channel with p one step
@@ -1135,67 +1173,48 @@ int pg_set_estimator_sets(pg_handle* h, int32_t n_sets, const pg_estimator* sets
     if (!h) return PG_ERR_INVALID;
     // the buffers first: a library is never installed without them (a failed allocation leaves the handle as it was)
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t cap = (size_t)h->cfg.batch_capacity;
-    if (!h->d_est) HIPCHK(h, hipMalloc((void**)&h->d_est, cap * 6 * sizeof(real)));
-    if (!h->d_est_u) HIPCHK(h, hipMalloc((void**)&h->d_est_u, cap * 3 * sizeof(real)));
+    int rc;
+    if ((rc = ensure(h, h->estimator.x, cap_of(h) * 6)) || (rc = ensure(h, h->estimator.u, cap_of(h) * 3))) return rc;
     std::string why;                                            // (the message names the set and the field; the estimate persists)
-    return setlib_install(h, "pg_set_estimator_sets", h->ests, n_sets, sets, [&](const pg_estimator& s) -> const char* {
-        const char* f = estimator_set_problem(s);
-        if (!f) return nullptr;
-        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
-        return why.c_str();
-    }, fill_dev_estimator);
+    return setlib_install(h, "pg_set_estimator_sets", h->estimator.lib, n_sets, sets, numbered_problem(estimator_set_problem, sets, why), fill_dev_estimator);
 }
 int pg_set_estimator_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    return index_install(h, (int)h->ests.sets.size(), h->ests.idx, B, index);
+    return index_install(h, (int)h->estimator.lib.sets.size(), h->estimator.lib.idx, B, index);
 }
 int pg_clear_estimator_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    const int rc = setlib_clear(h, h->ests); if (rc) return rc;
-    h->est_fresh = true; h->est_valid = false; h->est_hist = nullptr; h->est_hist_steps = 0;      // (a library installed later starts from its first measurement)
+    const int rc = setlib_clear(h, h->estimator.lib); if (rc) return rc;
+    h->estimator.cleared();
     return PG_OK;
 }
 int pg_get_estimator_sets(pg_handle* h, int32_t* n_sets, pg_estimator* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    return setlib_get(h, "pg_get_estimator_sets", h->ests, n_sets, out, max_sets, index, B);
+    return setlib_get(h, "pg_get_estimator_sets", h->estimator.lib, n_sets, out, max_sets, index, B);
 }
 int pg_set_estimated_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
     if (!h) return PG_ERR_INVALID;
-    if (!buf) { h->est_hist = nullptr; h->est_hist_steps = 0; return PG_OK; }
-    REQUIRE(h, steps >= 1, "pg_set_estimated_history_dev: steps >= 1 required");
-    if (h->ests.sets.empty()) { h->err = "pg_set_estimated_history_dev: no estimator library installed (the controller reads the sensor's output: record that)"; return PG_ERR_STATE; }
-    h->est_hist = (real*)buf; h->est_hist_steps = steps;
-    return PG_OK;
+    return history_register(h, "pg_set_estimated_history_dev", h->estimator.lib, "(the controller reads the sensor's output: record that)", h->estimator.hist, buf, steps);
 }
 int pg_get_estimated_state(pg_handle* h, double* estimated) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->ests.sets.empty() || !h->est_valid || !h->d_est) { h->err = "pg_get_estimated_state: no rollout step under an estimator library since the inputs were installed"; return PG_ERR_STATE; }
-    return down(h, estimated, h->d_est, (size_t)h->B * 6);
+    if (!h->estimator.lib.on() || !h->estimator.valid || !h->estimator.x) { h->err = "pg_get_estimated_state: no rollout step under an estimator library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, estimated, h->estimator.x, (size_t)h->B * 6);
 }
 int pg_estimator_response(pg_handle* h, int32_t steps, double dt, const double* y, const double* u, double* xhat) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, steps >= 1 && dt > 0.0 && y && u && xhat, "pg_estimator_response: steps >= 1, dt > 0, the measurements, the controls and the output array required");
-    if (h->B <= 0) { h->err = "pg_estimator_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
-    if (h->ests.sets.empty()) { h->err = "pg_estimator_response: no estimator library installed"; return PG_ERR_STATE; }
-    if (index_covers(h, h->ests.sets.size(), h->ests.idx)) return PG_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B;
     const size_t ny = (size_t)steps * (size_t)B * 6, nu = (size_t)steps * (size_t)B * 3;
-    real* d = nullptr;                                           // scratch of the call: y, xhat [steps][B][6], u [steps][B][3] (the estimate lives in the lanes' registers)
-    HIPCHK(h, hipMalloc((void**)&d, (2 * ny + nu) * sizeof(real)));
-    int rc = up(h, d, y, ny);
-    if (!rc) rc = up(h, d + 2 * ny, u, nu);
-    if (!rc) {
-        hipLaunchKernelGGL(k_estimator_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)steps, (real)(dt / h->dc.nsub), h->ests.d,
-                           h->ests.sets.size() > 1 ? h->ests.idx.d : (const int*)nullptr, (const real*)d, (const real*)(d + 2 * ny), d + ny);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("pg_estimator_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
-    }
-    if (!rc) rc = down(h, xhat, d + ny, ny);
-    else (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
+    // scratch of the call: y, xhat [steps][B][6], u [steps][B][3] (the estimate lives in the lanes' registers)
+    return response_call(h, "pg_estimator_response", h->estimator.lib, nullptr, nullptr, 2 * ny + nu, xhat, ny, [&](real* d, const real*& result) -> int {
+        int rc;
+        if ((rc = up(h, d, y, ny)) || (rc = up(h, d + 2 * ny, u, nu))) return rc;
+        hipLaunchKernelGGL(k_estimator_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)steps, (real)(dt / h->dc.nsub), h->estimator.lib.d, h->estimator.lib.index(),
+                           (const real*)d, (const real*)(d + 2 * ny), d + ny);
+        result = d + ny;
+        return PG_OK;
+    });
 }
 
 // ---- human library: the driver of the OTHER CAR in the safety and node rollouts, (omega, a) per instance (k_human; the plant kernels take it through their scripted mode).
@@ -1221,82 +1240,58 @@ static void fill_dev_human(DevHuman& H, const pg_human& s) {
 int pg_set_human_sets(pg_handle* h, int32_t n_sets, const pg_human* sets) {
     if (!h) return PG_ERR_INVALID;
     std::string why;                                            // (the message names the set and the field; seed, streams and the driver's state persist)
-    const int rc = setlib_install(h, "pg_set_human_sets", h->humans, n_sets, sets, [&](const pg_human& s) -> const char* {
-        const char* f = human_field_problem(s);
-        if (!f) return nullptr;
-        why = "set " + std::to_string((int)(&s - sets)) + ": " + f;
-        return why.c_str();
-    }, fill_dev_human);
+    const int rc = setlib_install(h, "pg_set_human_sets", h->human.lib, n_sets, sets, numbered_problem(human_field_problem, sets, why), fill_dev_human);
     if (rc) return rc;
-    h->human_script = false;
-    for (const pg_human& s : h->humans.sets) h->human_script = h->human_script || s.mode == 2;
+    h->human.script = false;
+    for (const pg_human& s : h->human.lib.sets) h->human.script = h->human.script || s.mode == 2;
     return PG_OK;
 }
 int pg_set_human_index(pg_handle* h, int32_t B, const int32_t* index) {
     if (!h) return PG_ERR_INVALID;
-    return index_install(h, (int)h->humans.sets.size(), h->humans.idx, B, index);
+    return index_install(h, (int)h->human.lib.sets.size(), h->human.lib.idx, B, index);
 }
 int pg_set_human_seed(pg_handle* h, uint64_t seed, int32_t B, const uint64_t* stream) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_set_human_seed: need 1 <= B <= batch_capacity");
-    h->human_seed = seed;                                       // (a launch argument: a rollout already queued keeps the seed it was launched with)
-    if (stream) h->human_stream.assign(stream, stream + B); else h->human_stream.clear();      // instances the array does not cover: stream[b] = b
-    h->human_stream_dirty = true;
-    return PG_OK;
+    return seed_install(h, "pg_set_human_seed", h->human.streams, seed, B, stream);
 }
 int pg_clear_human_sets(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
-    const int rc = setlib_clear(h, h->humans); if (rc) return rc;
-    h->human_script = false; h->human_fresh = true; h->human_valid = false; h->human_hist = nullptr; h->human_hist_steps = 0;      // (a library installed later starts a driver of its own)
+    const int rc = setlib_clear(h, h->human.lib); if (rc) return rc;
+    h->human.cleared();
     return PG_OK;
 }
 int pg_get_human_sets(pg_handle* h, int32_t* n_sets, pg_human* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
-    return setlib_get(h, "pg_get_human_sets", h->humans, n_sets, out, max_sets, index, B);
+    return setlib_get(h, "pg_get_human_sets", h->human.lib, n_sets, out, max_sets, index, B);
 }
 int pg_set_human_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps) {
     if (!h) return PG_ERR_INVALID;
-    if (!buf) { h->human_hist = nullptr; h->human_hist_steps = 0; return PG_OK; }
-    REQUIRE(h, steps >= 1, "pg_set_human_history_dev: steps >= 1 required");
-    if (h->humans.sets.empty()) { h->err = "pg_set_human_history_dev: no human library installed (the rollouts' human_mode decides: human_hist_dev of pg_simulate_safety_dev records that)"; return PG_ERR_STATE; }
-    h->human_hist = (real*)buf; h->human_hist_steps = steps;
-    return PG_OK;
+    return history_register(h, "pg_set_human_history_dev", h->human.lib, "(the rollouts' human_mode decides: human_hist_dev of pg_simulate_safety_dev records that)", h->human.hist, buf, steps);
 }
 int pg_get_human_state(pg_handle* h, double* u) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->humans.sets.empty() || !h->human_valid || !h->d_human_u) { h->err = "pg_get_human_state: no rollout step under a human library since the inputs were installed"; return PG_ERR_STATE; }
-    return down(h, u, h->d_human_u, (size_t)h->B * 2);
+    if (!h->human.lib.on() || !h->human.valid || !h->human.u) { h->err = "pg_get_human_state: no rollout step under a human library since the inputs were installed"; return PG_ERR_STATE; }
+    return down(h, u, h->human.u, (size_t)h->B * 2);
 }
 // what mode 1 is handed as has_hji: a grid on a coupled handle (the safety rollout is coupled only; the node rollout passes its plant kernel the same word)
 static int human_has_hji(const pg_handle* h) { return (int)(h->has_hji && h->dc.formulation == PG_COUPLED); }
 int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, step0 >= 0 && steps >= 1 && dt > 0.0 && x7 && vg8 && u_out, "pg_human_response: step0 >= 0, steps >= 1, dt > 0, x7, vg8 and the output array required");
-    if (h->B <= 0) { h->err = "pg_human_response: no inputs installed (the batch size is the one of pg_set_inputs)"; return PG_ERR_STATE; }
-    if (h->humans.sets.empty()) { h->err = "pg_human_response: no human library installed"; return PG_ERR_STATE; }
-    REQUIRE(h, !h->human_script || script, "pg_human_response: an installed set has mode 2 and needs script [steps][B][2]");
-    if (index_covers(h, h->humans.sets.size(), h->humans.idx)) return PG_ERR_STATE;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = streams_sync(h, h->d_human_stream, h->human_stream_dirty, h->human_stream); if (rc) return rc;
+    const char* const refuse = (h->human.script && !script) ? "pg_human_response: an installed set has mode 2 and needs script [steps][B][2]" : nullptr;
     const int B = h->B;
     const size_t sb = (size_t)steps * (size_t)B, nx = sb * 7, nv = sb * 8, nu = sb * 2;
-    real* d = nullptr;                                           // scratch of the call: x7, vg8, script, u (the driver's state lives in the lanes' registers)
-    HIPCHK(h, hipMalloc((void**)&d, (nx + nv + 2 * nu) * sizeof(real)));
-    real *dx = d, *dv = d + nx, *ds = dv + nv, *du = ds + nu;
-    rc = up(h, dx, x7, nx);
-    if (!rc) rc = up(h, dv, vg8, nv);
-    if (!rc && script) rc = up(h, ds, script, nu);
-    if (!rc) {
-        hipLaunchKernelGGL(k_human_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, (int)step0, (int)steps, human_has_hji(h), (real)dt, h->humans.d,
-                           h->humans.sets.size() > 1 ? h->humans.idx.d : (const int*)nullptr, h->d_human_stream, (unsigned long long)h->human_seed, (const real*)dx, (const real*)dv,
+    // scratch of the call: x7, vg8, script, u (the driver's state lives in the lanes' registers)
+    return response_call(h, "pg_human_response", h->human.lib, refuse, &h->human.streams, nx + nv + 2 * nu, u_out, nu, [&](real* d, const real*& result) -> int {
+        real *dx = d, *dv = d + nx, *ds = dv + nv, *du = ds + nu;
+        int rc;
+        if ((rc = up(h, dx, x7, nx)) || (rc = up(h, dv, vg8, nv)) || (script && (rc = up(h, ds, script, nu)))) return rc;
+        hipLaunchKernelGGL(k_human_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, (int)step0, (int)steps, human_has_hji(h), (real)dt, h->human.lib.d,
+                           h->human.lib.index(), h->human.streams.d, (unsigned long long)h->human.streams.seed, (const real*)dx, (const real*)dv,
                            script ? (const real*)ds : (const real*)nullptr, du);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("pg_human_response: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
-    }
-    if (!rc) rc = down(h, u_out, du, nu);
-    else (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    return rc;
+        result = du;
+        return PG_OK;
+    });
 }
 
 int pg_clear_hji_grid(pg_handle* h) {
@@ -1370,7 +1365,7 @@ static int set_inputs(pg_handle* h, int32_t B, const void* state, const void* co
     REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "batch size outside [1, batch_capacity]");
     REQUIRE(h, state && control && t0, "state, control and t0 are required");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->B = B; h->sim_idx = 0; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->meas_valid = false; h->act_fresh = true; h->dist_fresh = true; h->dist_valid = false; h->est_fresh = true; h->est_valid = false; h->human_fresh = true; h->human_valid = false;      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
+    h->B = B; h->sim_idx = 0; restart_on_inputs(h);      // (new times: the clock of pg_simulate_dev restarts from them, and the safety summary and node counts with it)
     const hipMemcpyKind kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     if (host) {
         // the caller's arrays are converted / copied into the pinned staging buffer here and now (so they may be reused as soon as this returns) and travel
@@ -1884,142 +1879,109 @@ static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, doub
     const std::string w(who);
     REQUIRE(h, steps >= 1 && dt > 0.0, w + ": steps >= 1 and dt > 0 required");
     REQUIRE(h, human_mode >= 0 && human_mode <= 2, w + ": human_mode is 0 (hold), 1 (worst case) or 2 (scripted)");
-    if (human_lib) REQUIRE(h, !h->human_script || human_u_dev, w + ": a set of the human library has mode 2 and needs human_u_dev [steps][B][2]");
+    if (human_lib) REQUIRE(h, !h->human.script || human_u_dev, w + ": a set of the human library has mode 2 and needs human_u_dev [steps][B][2]");
     else REQUIRE(h, human_mode != 2 || human_u_dev, w + ": human_mode 2 needs human_u_dev [steps][B][2]");
     return PG_OK;
 }
 // what a rollout needs beyond check_ready: a plant library of several sets wants an index that covers the batch; the tracking summary its buffers
 static int rollout_ready(pg_handle* h, bool human_lib) {
-    if (index_covers(h, h->plants.sets.size(), h->plants.idx)) return PG_ERR_STATE;
+    int rc;
+    const size_t cap = cap_of(h);
+    if (index_covers(h, h->plants)) return PG_ERR_STATE;
     if (human_lib) {                                             // (a rollout with another car, under a human library)
-        if (index_covers(h, h->humans.sets.size(), h->humans.idx)) return PG_ERR_STATE;
-        const size_t cap = cap_of(h);
-        if (!h->d_human_u) HIPCHK(h, hipMalloc((void**)&h->d_human_u, cap * 2 * sizeof(real)));
-        if (!h->d_human_n) HIPCHK(h, hipMalloc((void**)&h->d_human_n, cap * 2 * sizeof(real)));
-        const int rc = streams_sync(h, h->d_human_stream, h->human_stream_dirty, h->human_stream); if (rc) return rc;
+        auto& U = h->human;
+        if (index_covers(h, U.lib)) return PG_ERR_STATE;
+        if ((rc = ensure(h, U.u, cap * 2)) || (rc = ensure(h, U.n, cap * 2)) || (rc = U.streams.sync(h))) return rc;
     }
-    if (h->tracking && !h->d_track) {
-        const size_t cap = cap_of(h);
-        HIPCHK(h, hipMalloc((void**)&h->d_track, cap * 6 * sizeof(real)));
-        HIPCHK(h, hipMalloc((void**)&h->d_track_i, cap * 2 * sizeof(int)));
+    if (h->tracking && ((rc = ensure(h, h->d_track, cap * 6)) || (rc = ensure(h, h->d_track_i, cap * 2)))) return rc;
+    if (h->sensor.lib.on()) {
+        if (index_covers(h, h->sensor.lib)) return PG_ERR_STATE;
+        if ((rc = ensure(h, h->sensor.meas, cap * 6)) || (rc = h->sensor.streams.sync(h))) return rc;
     }
-    if (!h->sens.sets.empty()) {
-        if (index_covers(h, h->sens.sets.size(), h->sens.idx)) return PG_ERR_STATE;
-        const size_t cap = cap_of(h);
-        if (!h->d_meas) HIPCHK(h, hipMalloc((void**)&h->d_meas, cap * 6 * sizeof(real)));
-        const int rc = sensor_streams_sync(h); if (rc) return rc;
-    }
-    if (!h->ests.sets.empty() && index_covers(h, h->ests.sets.size(), h->ests.idx)) return PG_ERR_STATE;
+    if (index_covers(h, h->estimator.lib)) return PG_ERR_STATE;
     // (under either of the two the controller's (s, e) is not the truth's: launch_track projects the true state once more)
-    if (h->tracking && !h->d_sep_true && (!h->sens.sets.empty() || !h->ests.sets.empty())) HIPCHK(h, hipMalloc((void**)&h->d_sep_true, cap_of(h) * 4 * sizeof(real)));
-    if (!h->acts.sets.empty()) {
-        if (index_covers(h, h->acts.sets.size(), h->acts.idx)) return PG_ERR_STATE;
-        const size_t cap = cap_of(h);
-        if (!h->d_act) HIPCHK(h, hipMalloc((void**)&h->d_act, cap * 3 * sizeof(real)));
-        if (!h->d_act_ring) HIPCHK(h, hipMalloc((void**)&h->d_act_ring, (size_t)PG_ACT_MAX_DELAY * cap * 3 * sizeof(real)));
-        if (!h->d_plant_u) HIPCHK(h, hipMalloc((void**)&h->d_plant_u, cap * 3 * sizeof(real)));
-        if (h->act_feedback && !h->d_seen) HIPCHK(h, hipMalloc((void**)&h->d_seen, cap * 3 * sizeof(real)));
+    if (h->tracking && (h->sensor.lib.on() || h->estimator.lib.on()) && (rc = ensure(h, h->sensor.sep_true, cap * 4))) return rc;
+    if (h->actuator.lib.on()) {
+        auto& A = h->actuator;
+        if (index_covers(h, A.lib)) return PG_ERR_STATE;
+        if ((rc = ensure(h, A.pos, cap * 3)) || (rc = ensure(h, A.ring, (size_t)PG_ACT_MAX_DELAY * cap * 3)) || (rc = ensure(h, A.plant_u, cap * 3)) || (A.feedback && (rc = ensure(h, A.seen, cap * 3)))) return rc;
     }
-    if (!h->dists.sets.empty()) {
-        if (index_covers(h, h->dists.sets.size(), h->dists.idx)) return PG_ERR_STATE;
-        const size_t cap = cap_of(h);
-        if (!h->d_dist_n) HIPCHK(h, hipMalloc((void**)&h->d_dist_n, cap * 2 * sizeof(real)));
-        if (!h->d_dist_w) HIPCHK(h, hipMalloc((void**)&h->d_dist_w, cap * 4 * sizeof(real)));
-        if (!h->d_dist_veh) {                                    // (the controller's vehicle as the kernels hold it: DevCfg's record, bit for bit)
-            HIPCHK(h, hipMalloc((void**)&h->d_dist_veh, sizeof(DevVehicle)));
-            HIPCHK(h, hipMemcpy(h->d_dist_veh, &h->dc.veh, sizeof(DevVehicle), hipMemcpyHostToDevice));
+    if (h->disturbance.lib.on()) {
+        auto& D = h->disturbance;
+        if (index_covers(h, D.lib)) return PG_ERR_STATE;
+        if ((rc = ensure(h, D.n, cap * 2)) || (rc = ensure(h, D.w, cap * 4))) return rc;
+        if (!D.veh) {                                            // (the controller's vehicle as the kernels hold it: DevCfg's record, bit for bit)
+            if ((rc = ensure(h, D.veh, 1))) return rc;
+            HIPCHK(h, hipMemcpy(D.veh, &h->dc.veh, sizeof(DevVehicle), hipMemcpyHostToDevice));
         }
-        const int rc = streams_sync(h, h->d_dist_stream, h->dist_stream_dirty, h->dist_stream); if (rc) return rc;
+        if ((rc = D.streams.sync(h))) return rc;
     }
     return PG_OK;
 }
-// the disturbance library (the host knows whether one is installed: that alone adds k_disturb to a rollout step and picks the <DistW> instantiation of the library kernel).
-// disturbance_take_history: the one-shot registration of pg_set_disturbance_history_dev, consumed by the rollout call that starts now
-static bool disturbance_lib_on(const pg_handle* h) { return !h->dists.sets.empty(); }
-struct DistHist { real* buf; int steps; };
-static DistHist disturbance_take_history(pg_handle* h) { const DistHist d{h->dist_hist, h->dist_hist_steps}; h->dist_hist = nullptr; h->dist_hist_steps = 0; return d; }
-// the top of a rollout step under a library: w of clock step `step` into d_dist_w, the gust state advanced (fresh: the host knows that no state of step - 1 exists)
-static int launch_disturb(pg_handle* h, int step, int k, double dt, const DistHist& dh) {
-    const int B = h->B;
-    const DisturbanceLib lib{h->dists.d, h->dists.sets.size() > 1 ? h->dists.idx.d : (const int*)nullptr, h->d_dist_stream, (unsigned long long)h->dist_seed, h->d_dist_n, h->d_dist_w};
-    hipLaunchKernelGGL(k_disturb, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, (int)h->dist_fresh, (real)dt, lib,
-                       (dh.buf && k < dh.steps) ? dh.buf + (size_t)k * B * 4 : (real*)nullptr);
+// The one-shot history registrations a rollout call consumes (pg_set_*_history_dev), taken from the handle when the call starts
+struct RolloutHist { HistSlot measured, applied, command, disturbance, estimated, human; };
+static RolloutHist take_histories(pg_handle* h) {
+    return RolloutHist{h->sensor.hist.take(), h->actuator.applied_hist.take(), h->actuator.command_hist.take(), h->disturbance.hist.take(), h->estimator.hist.take(), h->human.hist.take()};
+}
+// the disturbance library (installed: k_disturb joins a rollout step, and the step's last launch is the <DistW> instantiation of the library kernel).
+// The top of a rollout step under a library: w of clock step `step` into disturbance.w, the gust state advanced (fresh: the host knows that no state of step - 1 exists)
+static int launch_disturb(pg_handle* h, int step, int k, double dt, const HistSlot& hist) {
+    const int B = h->B; auto& D = h->disturbance;
+    const DisturbanceLib lib{D.lib.d, D.lib.index(), D.streams.d, (unsigned long long)D.streams.seed, D.n, D.w};
+    hipLaunchKernelGGL(k_disturb, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, (int)D.fresh, (real)dt, lib, hist.at(k, B, 4));
     LAUNCH_CHECK(h);
-    h->dist_fresh = false; h->dist_valid = true; h->stat_disturbance_steps++;
+    D.fresh = false; D.valid = true; D.steps_stat++;
     return PG_OK;
 }
-// the human library (installed: k_human joins a step of the rollouts that have another car, ahead of the plant launch, which is handed d_human_u as the script of its human
-// mode 2).  human_take_history: the one-shot registration of pg_set_human_history_dev, consumed by the rollout call that starts now
-static bool human_lib_on(const pg_handle* h) { return !h->humans.sets.empty(); }
-struct HumanHist { real* buf; int steps; };
-static HumanHist human_take_history(pg_handle* h) { const HumanHist u{h->human_hist, h->human_hist_steps}; h->human_hist = nullptr; h->human_hist_steps = 0; return u; }
-// behind the compute calls of a rollout step under a library (mode 1 reads the step's d_x7, d_vg8): (omega, a) of clock step `step` into d_human_u, the driver's state
+// the human library (installed: k_human joins a step of the rollouts that have another car, ahead of the plant launch, which is handed human.u as the script of its human
+// mode 2).  Behind the compute calls of a rollout step under a library (mode 1 reads the step's d_x7, d_vg8): (omega, a) of clock step `step` into human.u, the driver's state
 // advanced (fresh: the host knows that no state of step - 1 exists).  script: human_u_dev of the call, [steps][B][2] or nullptr
-static int launch_human(pg_handle* h, int step, int k, double dt, const void* script, const HumanHist& hh) {
-    const int B = h->B;
-    const HumanLib lib{h->humans.d, h->humans.sets.size() > 1 ? h->humans.idx.d : (const int*)nullptr, h->d_human_stream, (unsigned long long)h->human_seed, h->d_human_n, h->d_human_u};
-    hipLaunchKernelGGL(k_human, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, step, (int)h->human_fresh, human_has_hji(h), (real)dt, lib, (const real*)h->d_x7,
-                       (const real*)h->d_vg8, script ? (const real*)script + (size_t)k * B * 2 : (const real*)nullptr, (hh.buf && k < hh.steps) ? hh.buf + (size_t)k * B * 2 : (real*)nullptr);
+static int launch_human(pg_handle* h, int step, int k, double dt, const void* script, const HistSlot& hist) {
+    const int B = h->B; auto& U = h->human;
+    const HumanLib lib{U.lib.d, U.lib.index(), U.streams.d, (unsigned long long)U.streams.seed, U.n, U.u};
+    hipLaunchKernelGGL(k_human, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, step, (int)U.fresh, human_has_hji(h), (real)dt, lib, (const real*)h->d_x7,
+                       (const real*)h->d_vg8, script ? (const real*)script + (size_t)k * B * 2 : (const real*)nullptr, hist.at(k, B, 2));
     LAUNCH_CHECK(h);
-    h->human_fresh = false; h->human_valid = true; h->stat_human_steps++;
+    U.fresh = false; U.valid = true; U.steps_stat++;
     return PG_OK;
 }
-// the actuator library (the host knows whether one is installed: that alone adds k_actuate and the copy-back to a rollout step).  actuator_take_history: the one-shot
-// registrations of pg_set_applied_history_dev / pg_set_command_history_dev, consumed by the rollout call that starts now
-static bool actuator_lib_on(const pg_handle* h) { return !h->acts.sets.empty(); }
-struct ActHist { real *applied, *command; int applied_steps, command_steps; };
-static ActHist actuator_take_history(pg_handle* h) {
-    const ActHist a{h->applied_hist, h->command_hist, h->applied_hist_steps, h->command_hist_steps};
-    h->applied_hist = nullptr; h->command_hist = nullptr; h->applied_hist_steps = 0; h->command_hist_steps = 0;
-    return a;
-}
-// the top of a rollout step under a library: a_k of clock step `step` from the command the handle's control buffer holds, into d_act, d_plant_u (and d_seen)
-static int launch_actuate(pg_handle* h, int step, int k, double dt, const ActHist& ah) {
-    const int B = h->B;
-    const ActuatorLib lib{h->acts.d, h->acts.sets.size() > 1 ? h->acts.idx.d : (const int*)nullptr, h->d_act, h->d_act_ring, h->d_plant_u,
-                          h->act_feedback ? h->d_seen : (real*)nullptr, (int)cap_of(h)};
-    hipLaunchKernelGGL(k_actuate, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, (int)h->act_fresh, (real)dt, lib, h->d_control,
-                       (ah.applied && k < ah.applied_steps) ? ah.applied + (size_t)k * B * 3 : (real*)nullptr,
-                       (ah.command && k < ah.command_steps) ? ah.command + (size_t)k * B * 3 : (real*)nullptr);
+// the actuator library (installed: k_actuate and the copy-back join a rollout step).  The top of a rollout step under a library: a_k of clock step `step` from the command
+// the handle's control buffer holds, into actuator.pos, plant_u (and seen)
+static int launch_actuate(pg_handle* h, int step, int k, double dt, const HistSlot& applied, const HistSlot& command) {
+    const int B = h->B; auto& A = h->actuator;
+    const ActuatorLib lib{A.lib.d, A.lib.index(), A.pos, A.ring, A.plant_u, A.feedback ? A.seen : (real*)nullptr, (int)cap_of(h)};
+    hipLaunchKernelGGL(k_actuate, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, (int)A.fresh, (real)dt, lib, h->d_control, applied.at(k, B, 3), command.at(k, B, 3));
     LAUNCH_CHECK(h);
-    h->act_fresh = false;
+    A.fresh = false;
     return PG_OK;
 }
-// the sensor library (the host knows whether one is installed: that alone adds k_measure to a rollout step).  sensor_take_history: the one-shot registration of
-// pg_set_measured_history_dev, consumed by the rollout call that starts now
-static bool sensor_lib_on(const pg_handle* h) { return !h->sens.sets.empty(); }
-// the estimator library (installed: k_estimate joins a rollout step, behind k_measure).  estimator_take_history: the one-shot registration of pg_set_estimated_history_dev
-static bool estimator_lib_on(const pg_handle* h) { return !h->ests.sets.empty(); }
-struct EstHist { real* buf; int steps; };
-static EstHist estimator_take_history(pg_handle* h) { const EstHist e{h->est_hist, h->est_hist_steps}; h->est_hist = nullptr; h->est_hist_steps = 0; return e; }
-struct MeasHist { real* buf; int steps; };
-static MeasHist sensor_take_history(pg_handle* h) { const MeasHist m{h->meas_hist, h->meas_hist_steps}; h->meas_hist = nullptr; h->meas_hist_steps = 0; return m; }
 // the controller's side of one rollout step: the node gate (node rollout) and the compute calls.  Under a sensor library k_measure writes the measured state of clock step
 // `step` first, and the handle's state pointer names THAT buffer while the gate and the compute kernels are queued -- they all take the state from the handle --, then the true
 // one again for the summary, the records and the plant: no copy, no restore launch, no kernel changed.  Under an estimator library k_estimate follows (on the measured state, or on the true one without a sensor library) and
-// the pointer names d_est in the same way: the gates, the projection, the nodes, the QP's q_curr, the HJI relative state and the policy selection all follow the estimate.
+// the pointer names estimator.x in the same way: the gates, the projection, the nodes, the QP's q_curr, the HJI relative state and the policy selection all follow the estimate.
 // Without either library: the gate and the compute calls, nothing else
 static int node_gate(pg_handle* h, const uint8_t* pre_flag);
-static int rollout_compute(pg_handle* h, int step, int k, double dt, const MeasHist& mh, const EstHist& eh, bool gate, const uint8_t* pre_flag) {
+static int rollout_compute(pg_handle* h, int step, int k, double dt, const HistSlot& measured, const HistSlot& estimated, bool gate, const uint8_t* pre_flag) {
     int rc;
-    if (!sensor_lib_on(h) && !estimator_lib_on(h)) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
+    auto& S = h->sensor; auto& E = h->estimator;
+    if (!S.lib.on() && !E.lib.on()) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
     const int B = h->B;
     real* const true_state = h->d_state;
     real* seen = true_state;                                     // what the gate and the compute calls read: the sensor's output, or the estimator's on top of it
-    if (sensor_lib_on(h)) {
-        const SensorLib lib{h->sens.d, h->sens.sets.size() > 1 ? h->sens.idx.d : (const int*)nullptr, h->d_sens_stream, (unsigned long long)h->sens_seed};
-        hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, h->d_meas, (mh.buf && k < mh.steps) ? mh.buf + (size_t)k * B * 6 : (real*)nullptr);
+    if (S.lib.on()) {
+        const SensorLib lib{S.lib.d, S.lib.index(), S.streams.d, (unsigned long long)S.streams.seed};
+        hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, S.meas, measured.at(k, B, 6));
         LAUNCH_CHECK(h);
-        h->meas_valid = true; h->stat_sensor_steps++;
-        seen = h->d_meas;
+        S.valid = true; S.steps_stat++;
+        seen = S.meas;
     }
-    if (estimator_lib_on(h)) {      // (h->d_control: what the compute calls below are handed as current_control -- the command, or d_seen under an actuator library with feedback)
-        const EstimatorLib lib{h->ests.d, h->ests.sets.size() > 1 ? h->ests.idx.d : (const int*)nullptr, h->d_est, h->d_est_u};
-        hipLaunchKernelGGL(k_estimate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)h->est_fresh, (real)(dt / h->dc.nsub), lib, (const real*)seen,
-                           (const real*)h->d_control, (eh.buf && k < eh.steps) ? eh.buf + (size_t)k * B * 6 : (real*)nullptr);
+    if (E.lib.on()) {      // (h->d_control: what the compute calls below are handed as current_control -- the command, or actuator.seen under an actuator library with feedback)
+        const EstimatorLib lib{E.lib.d, E.lib.index(), E.x, E.u};
+        hipLaunchKernelGGL(k_estimate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)E.fresh, (real)(dt / h->dc.nsub), lib, (const real*)seen,
+                           (const real*)h->d_control, estimated.at(k, B, 6));
         LAUNCH_CHECK(h);
-        h->est_fresh = false; h->est_valid = true; h->stat_estimator_steps++;
-        seen = h->d_est;
+        E.fresh = false; E.valid = true; E.steps_stat++;
+        seen = E.x;
     }
     h->d_state = seen;
     rc = gate ? node_gate(h, pre_flag) : PG_OK;
@@ -2028,18 +1990,17 @@ static int rollout_compute(pg_handle* h, int step, int k, double dt, const MeasH
     return rc;
 }
 // the plant library as the library kernels (k_*_lib) take it (the host knows whether one is installed: that alone picks the kernel)
-static bool plant_lib_on(const pg_handle* h) { return !h->plants.sets.empty(); }
-static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->plants.d, h->plants.sets.size() > 1 ? h->plants.idx.d : (const int*)nullptr}; }
+static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->plants.d, h->plants.index()}; }
 // the step's tracking summary (option "tracking_summary"): behind the projection of this step (step_compute), ahead of the kernel that moves the plant
 static int launch_track(pg_handle* h, int step) {
     if (!h->tracking) { h->track_fresh = true; return PG_OK; }      // (off: no launch; steps that went unseen must not be continued when it comes back on)
     const int B = h->B;
     const real* sep = h->d_sep;
-    if (sensor_lib_on(h) || estimator_lib_on(h)) {      // d_sep holds the projection of the MEASURED / ESTIMATED state (the node publishes its (s, e)): the summary describes the true one, projected once more
-        hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep_true, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
+    if (h->sensor.lib.on() || h->estimator.lib.on()) {      // d_sep holds the projection of the MEASURED / ESTIMATED state (the node publishes its (s, e)): the summary describes the true one, projected once more
+        hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->sensor.sep_true, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
                            (double*)nullptr, (int*)nullptr, 0, (int*)nullptr, (int*)nullptr, 0);
         LAUNCH_CHECK(h);
-        sep = h->d_sep_true;
+        sep = h->sensor.sep_true;
     }
     hipLaunchKernelGGL(k_track, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)h->track_fresh, step, h->d_state, sep, h->d_track, h->d_track_i, h->d_track_i + cap_of(h));
     LAUNCH_CHECK(h);
@@ -2049,7 +2010,7 @@ static int launch_track(pg_handle* h, int step) {
 static int clock_start(pg_handle* h, double dt) {
     if (h->sim_idx == 0 || h->sim_dt != dt || h->sim_tend != h->traj_t_end) {
         HIPCHK(h, hipMemcpyAsync(h->d_tstart, h->d_t0, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true; h->act_fresh = true; h->dist_fresh = true; h->est_fresh = true; h->human_fresh = true;
+        h->sim_clk = jl_colon(0.0, dt, h->traj_t_end); h->sim_idx = 1; h->sim_dt = dt; h->sim_tend = h->traj_t_end; restart_on_clock(h);
     }
     return PG_OK;
 }
@@ -2061,8 +2022,8 @@ static int node_start(pg_handle* h, double dt);
 template <class K, class KP, class KD, class... A>
 static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_dist, const A&... args) {
     const dim3 grid((h->B + 63) / 64), block(64);
-    if (disturbance_lib_on(h)) hipLaunchKernelGGL(with_dist, grid, block, 0, h->stream, args..., plant_lib_on(h) ? plant_lib(h) : PlantLib{h->d_dist_veh, nullptr}, (const real*)h->d_dist_w);
-    else if (plant_lib_on(h)) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
+    if (h->disturbance.lib.on()) hipLaunchKernelGGL(with_dist, grid, block, 0, h->stream, args..., h->plants.on() ? plant_lib(h) : PlantLib{h->disturbance.veh, nullptr}, (const real*)h->disturbance.w);
+    else if (h->plants.on()) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
     else hipLaunchKernelGGL(uniform, grid, block, 0, h->stream, args...);
 }
 // The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated, human) are taken (THIS call consumes them, also when it fails below), check_ready,
@@ -2075,39 +2036,36 @@ static const char* const ACTUATOR_NODE_REFUSAL = "an actuator library is install
 struct RolloutArgs { const char* who; int32_t steps; double dt; int32_t human_mode; const void* human_u; const char* coupled_only; bool node; const uint8_t* pre_flag; bool other_car; };
 template <class Records, class Finish>
 static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish finish) {
-    const MeasHist mh = h ? sensor_take_history(h) : MeasHist{nullptr, 0};
-    const ActHist ah = h ? actuator_take_history(h) : ActHist{nullptr, nullptr, 0, 0};
-    const DistHist dh = h ? disturbance_take_history(h) : DistHist{nullptr, 0};
-    const EstHist eh = h ? estimator_take_history(h) : EstHist{nullptr, 0};
-    const HumanHist hh = h ? human_take_history(h) : HumanHist{nullptr, 0};
+    const RolloutHist hist = h ? take_histories(h) : RolloutHist{};
     int rc = check_ready(h); if (rc) return rc;
     if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
-    if (a.node && actuator_lib_on(h)) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
-    const bool human = a.other_car && human_lib_on(h);           // (pg_simulate_dev has no other car: it never reads the human library)
+    if (a.node && h->actuator.lib.on()) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
+    const bool human = a.other_car && h->human.lib.on();         // (pg_simulate_dev has no other car: it never reads the human library)
     if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u, human)) || (rc = rollout_ready(h, human)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
-    // Under an actuator library the handle's control pointer names, while the launches are QUEUED: d_plant_u (= a_k) for the records and the plant launch, d_seen for the
+    // Under an actuator library the handle's control pointer names, while the launches are QUEUED: actuator.plant_u (= a_k) for the records and the plant launch, actuator.seen for the
     // compute calls when some set has feedback == 1 -- k_nodes*, the QP's u_curr and the steering-rate rows all take the pointer from the handle --, and its own allocation
-    // (the command) everywhere else and whenever this function returns.  The plant kernel leaves the next command in d_plant_u: one copy moves it to the control buffer
-    const bool act = actuator_lib_on(h), dist = disturbance_lib_on(h);
+    // (the command) everywhere else and whenever this function returns.  The plant kernel leaves the next command in plant_u: one copy moves it to the control buffer
+    auto& A = h->actuator;
+    const bool act = A.lib.on(), dist = h->disturbance.lib.on();
     real* const command = h->d_control;
     for (int k = 0; k < a.steps; k++) {
         const int step = h->sim_idx - 1;
-        if (act && (rc = launch_actuate(h, step, k, a.dt, ah))) return rc;
-        if (dist && (rc = launch_disturb(h, step, k, a.dt, dh))) return rc;      // (w of this step: read by the step's last launch only)
-        if (act) h->d_control = h->d_plant_u;
+        if (act && (rc = launch_actuate(h, step, k, a.dt, hist.applied, hist.command))) return rc;
+        if (dist && (rc = launch_disturb(h, step, k, a.dt, hist.disturbance))) return rc;      // (w of this step: read by the step's last launch only)
+        if (act) h->d_control = A.plant_u;
         rc = records(k);
-        if (act) h->d_control = h->act_feedback ? h->d_seen : command;
-        if (!rc) rc = rollout_compute(h, step, k, a.dt, mh, eh, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
+        if (act) h->d_control = A.feedback ? A.seen : command;
+        if (!rc) rc = rollout_compute(h, step, k, a.dt, hist.measured, hist.estimated, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
         h->d_control = command;
-        if (rc || (rc = launch_track(h, step)) || (human && (rc = launch_human(h, step, k, a.dt, a.human_u, hh)))) return rc;
+        if (rc || (rc = launch_track(h, step)) || (human && (rc = launch_human(h, step, k, a.dt, a.human_u, hist.human)))) return rc;
         h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)
-        if (act) h->d_control = h->d_plant_u;
+        if (act) h->d_control = A.plant_u;
         finish(k, step);
         h->d_control = command;
         LAUNCH_CHECK(h);
         if (act) {
-            HIPCHK(h, hipMemcpyAsync(command, h->d_plant_u, (size_t)h->B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
-            h->stat_actuator_steps++;
+            HIPCHK(h, hipMemcpyAsync(command, A.plant_u, (size_t)h->B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
+            A.steps_stat++;
         }
     }
     return PG_OK;
@@ -2136,9 +2094,9 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
         no_records,
         [&](int k, int step) {
             const int B = h->B;
-            const bool lib = human_lib_on(h);                    // (under a human library the kernel is handed this step's d_human_u as its script: it records and integrates that)
+            const bool lib = h->human.lib.on();                  // (under a human library the kernel is handed this step's human.u as its script: it records and integrates that)
             const int hmode = lib ? 2 : (int)human_mode;
-            SafetyIO io{lib ? (const real*)h->d_human_u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr), hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
+            SafetyIO io{lib ? (const real*)h->human.u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr), hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
                         hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
                         h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
             launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)h->has_hji, (int)h->sum_fresh, step,
@@ -2227,7 +2185,7 @@ static void node_done(pg_handle* h) { h->node_parity ^= 1; h->node_recheck = tru
 int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_flag_dev, void* cmd_out_dev, void* se_out_dev, int32_t* event_dev) {
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_node_step_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
-    if (!h->acts.sets.empty()) { h->err = std::string("pg_node_step_dev: ") + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
+    if (h->actuator.lib.on()) { h->err = std::string("pg_node_step_dev: ") + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
     if ((rc = node_prepare(h)) || (rc = node_gate(h, pre_flag_dev)) || (rc = step_compute(h))) return rc;
     NodeIO io = node_io(h);
     io.cmd_out = (real*)cmd_out_dev; io.se_out = (real*)se_out_dev; io.event = event_dev;
@@ -2254,9 +2212,9 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
         [&](int k, int step) {
             const int B = h->B;
             NodeIO io = node_io(h);
-            const bool lib = human_lib_on(h);                    // (as pg_simulate_safety_dev: d_human_u of this step is the script)
+            const bool lib = h->human.lib.on();                  // (as pg_simulate_safety_dev: human.u of this step is the script)
             const int hmode = lib ? 2 : (int)human_mode;
-            io.human_u = lib ? (const real*)h->d_human_u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr);
+            io.human_u = lib ? (const real*)h->human.u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr);
             io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
             io.event_h = hist_at(event_hist_dev, k, B, 1);
             io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;

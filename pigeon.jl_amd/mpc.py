@@ -188,6 +188,31 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(get(self.h, C.byref(n), arr, n.value, _p(index, c_i32p), self.B), f"pg_get_{name}_sets")
         return [as_dict(arr[k]) for k in range(n.value)], index
 
+    def _set_seed(self, name, seed, streams):
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
+        self._chk(getattr(self.lib, f"pg_set_{name}_seed")(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), f"pg_set_{name}_seed")
+
+    def _clear(self, name):
+        self._chk(getattr(self.lib, f"pg_clear_{name}_sets")(self.h), f"pg_clear_{name}_sets")
+
+    def _state(self, name, width):
+        """[B][width]: what pg_get_<name>_state reads"""
+        out = np.zeros((self.B, width))
+        self._chk(getattr(self.lib, f"pg_get_{name}_state")(self.h, _p(out)), f"pg_get_{name}_state")
+        return out
+
+    def _hist(self, setter, width, steps, library=None):
+        """registers a [steps][B][width] device record with the next rollout call through `setter` and returns it; None when `library` is given and none is installed"""
+        if library is not None:
+            n = C.c_int32(0)
+            self._chk(getattr(self.lib, f"pg_get_{library}_sets")(self.h, C.byref(n), None, 0, None, 0), f"pg_get_{library}_sets")
+            if n.value == 0:
+                return None
+        torch, tdt, dev = self._torch()
+        buf = torch.empty(int(steps), self.B, width, dtype=tdt, device=dev)
+        self._chk(getattr(self.lib, setter)(self.h, C.c_void_p(buf.data_ptr()), int(steps)), setter)
+        return buf
+
     # ---- one controller per (x0, control_params) pair: a library of parameter sets and a per-instance selection (a tuning sweep in one batch) ----
     def pack_control_params(self, sets):
         """dicts (missing fields: the handle's own control_params) or pg_control_params structures -> a ctypes array of pg_control_params."""
@@ -206,7 +231,7 @@ class BatchedTrajectoryTrackingMPC:
         self._set_index("control_param", index)
 
     def clear_control_params(self):
-        self._chk(self.lib.pg_clear_control_param_sets(self.h), "pg_clear_control_param_sets")
+        self._clear("control_param")
 
     def control_param_sets(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -229,7 +254,7 @@ class BatchedTrajectoryTrackingMPC:
         self._set_index("plant", index)
 
     def clear_plants(self):
-        self._chk(self.lib.pg_clear_plant_sets(self.h), "pg_clear_plant_sets")
+        self._clear("plant")
 
     def plant_sets(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -268,11 +293,10 @@ class BatchedTrajectoryTrackingMPC:
         self.set_sensor_seed(seed, streams)
 
     def set_sensor_seed(self, seed=0, streams=None):
-        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
-        self._chk(self.lib.pg_set_sensor_seed(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), "pg_set_sensor_seed")
+        self._set_seed("sensor", seed, streams)
 
     def clear_sensors(self):
-        self._chk(self.lib.pg_clear_sensor_sets(self.h), "pg_clear_sensor_sets")
+        self._clear("sensor")
 
     def sensors(self):
         """(list of {"sigma": [6], "bias": [6]}, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -287,9 +311,7 @@ class BatchedTrajectoryTrackingMPC:
 
     def measured_state(self):
         """[B][6]: what the controller read at the last rollout step under a sensor library (pg_get_measured_state)."""
-        m = np.zeros((self.B, 6))
-        self._chk(self.lib.pg_get_measured_state(self.h, _p(m)), "pg_get_measured_state")
-        return m
+        return self._state("measured", 6)
 
     # ---- the ACTUATOR of the rollouts, per instance (command delay, lag, slew): a library of pg_actuator_set and a per-instance selection ----
     @classmethod
@@ -315,7 +337,7 @@ class BatchedTrajectoryTrackingMPC:
         self._set_index("actuator", idx)
 
     def clear_actuators(self):
-        self._chk(self.lib.pg_clear_actuator_sets(self.h), "pg_clear_actuator_sets")
+        self._clear("actuator")
 
     def get_actuators(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -323,9 +345,7 @@ class BatchedTrajectoryTrackingMPC:
 
     def actuator_state(self):
         """[B][3]: the applied control a of the last rollout step under a library; the handle's control before the first one since the clock restarted (pg_get_actuator_state)."""
-        a = np.zeros((self.B, 3))
-        self._chk(self.lib.pg_get_actuator_state(self.h, _p(a)), "pg_get_actuator_state")
-        return a
+        return self._state("actuator", 3)
 
     def actuator_response(self, commands, dt):
         """The law alone, on the device through the function the rollouts call (pg_actuator_response): commands [steps][B][3] -> applied [steps][B][3] under the installed
@@ -334,20 +354,6 @@ class BatchedTrajectoryTrackingMPC:
         out = np.zeros_like(c)
         self._chk(self.lib.pg_actuator_response(self.h, c.shape[0], C.c_double(dt), _p(c), _p(out)), "pg_actuator_response")
         return out
-
-    def _actuator_hists(self, record, steps):
-        """registers [steps][B][3] device records of the applied control and of the command with the next rollout call; {} unless record and a library is installed"""
-        if not record:
-            return {}
-        n = C.c_int32(0)
-        self._chk(self.lib.pg_get_actuator_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_actuator_sets")
-        if n.value == 0:
-            return {}
-        torch, tdt, dev = self._torch()
-        bufs = {k: torch.empty(int(steps), self.B, 3, dtype=tdt, device=dev) for k in ("applied", "command")}
-        for k, buf in bufs.items():
-            self._chk(getattr(self.lib, f"pg_set_{k}_history_dev")(self.h, C.c_void_p(buf.data_ptr()), int(steps)), f"pg_set_{k}_history_dev")
-        return bufs
 
     # ---- the DISTURBANCE of the rollouts, per instance (forces, gusts, low-friction windows): a library of pg_disturbance, a per-instance selection, a seed and stream ids ----
     @classmethod
@@ -376,11 +382,10 @@ class BatchedTrajectoryTrackingMPC:
         self._set_index("disturbance", index)
 
     def set_disturbance_seed(self, seed=0, streams=None):
-        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
-        self._chk(self.lib.pg_set_disturbance_seed(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), "pg_set_disturbance_seed")
+        self._set_seed("disturbance", seed, streams)
 
     def clear_disturbances(self):
-        self._chk(self.lib.pg_clear_disturbance_sets(self.h), "pg_clear_disturbance_sets")
+        self._clear("disturbance")
 
     def disturbances(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -395,22 +400,7 @@ class BatchedTrajectoryTrackingMPC:
 
     def disturbance_state(self):
         """[B][4]: w of the last rollout step under a disturbance library (pg_get_disturbance_state)."""
-        w = np.zeros((self.B, 4))
-        self._chk(self.lib.pg_get_disturbance_state(self.h, _p(w)), "pg_get_disturbance_state")
-        return w
-
-    def _disturbance_hist(self, record, steps):
-        """registers a [steps][B][4] device record of w with the next rollout call; {} unless record and a library is installed"""
-        if not record:
-            return {}
-        n = C.c_int32(0)
-        self._chk(self.lib.pg_get_disturbance_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_disturbance_sets")
-        if n.value == 0:
-            return {}
-        torch, tdt, dev = self._torch()
-        buf = torch.empty(int(steps), self.B, 4, dtype=tdt, device=dev)
-        self._chk(self.lib.pg_set_disturbance_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_disturbance_history_dev")
-        return {"disturbance": buf}
+        return self._state("disturbance", 4)
 
     # ---- the ESTIMATOR of the rollouts, per instance (a fixed-gain observer between the sensor and the controller): a library of pg_estimator and a per-instance selection ----
     @classmethod
@@ -436,7 +426,7 @@ class BatchedTrajectoryTrackingMPC:
         self._set_index("estimator", index)
 
     def clear_estimators(self):
-        self._chk(self.lib.pg_clear_estimator_sets(self.h), "pg_clear_estimator_sets")
+        self._clear("estimator")
 
     def get_estimators(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -444,9 +434,7 @@ class BatchedTrajectoryTrackingMPC:
 
     def estimated_state(self):
         """[B][6]: what the controller read at the last rollout step under an estimator library (pg_get_estimated_state)."""
-        e = np.zeros((self.B, 6))
-        self._chk(self.lib.pg_get_estimated_state(self.h, _p(e)), "pg_get_estimated_state")
-        return e
+        return self._state("estimated", 6)
 
     def estimator_response(self, y, u, dt):
         """The law alone, on the device through the function the rollouts call (pg_estimator_response): measurements y [steps][B][6] and controls u [steps][B][3] (u[k]: what
@@ -458,15 +446,6 @@ class BatchedTrajectoryTrackingMPC:
         out = np.zeros_like(y)
         self._chk(self.lib.pg_estimator_response(self.h, y.shape[0], C.c_double(dt), _p(y), _p(u), _p(out)), "pg_estimator_response")
         return out
-
-    def _estimated_hist(self, estimated, steps):
-        """registers a [steps][B][6] device record of the estimate with the next rollout call (pg_set_estimated_history_dev); None unless asked for"""
-        if not estimated:
-            return None
-        torch, tdt, dev = self._torch()
-        buf = torch.empty(int(steps), self.B, 6, dtype=tdt, device=dev)
-        self._chk(self.lib.pg_set_estimated_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_estimated_history_dev")
-        return buf
 
     # ---- the HUMAN of the safety and node rollouts, per instance (the other car's driver): a library of pg_human, a per-instance selection, a seed and stream ids ----
     @classmethod
@@ -496,11 +475,10 @@ class BatchedTrajectoryTrackingMPC:
         self._set_index("human", index)
 
     def set_human_seed(self, seed=0, streams=None):
-        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64)
-        self._chk(self.lib.pg_set_human_seed(self.h, C.c_uint64(int(seed)), max(self.B, 1) if st is None else len(st), _p(st, C.POINTER(C.c_uint64))), "pg_set_human_seed")
+        self._set_seed("human", seed, streams)
 
     def clear_humans(self):
-        self._chk(self.lib.pg_clear_human_sets(self.h), "pg_clear_human_sets")
+        self._clear("human")
 
     def humans(self):
         """(list of dicts, index array over the current batch; -1 where no index covers an instance) as installed; ([], ...) without a library."""
@@ -520,36 +498,12 @@ class BatchedTrajectoryTrackingMPC:
 
     def human_state(self):
         """[B][2]: (omega, a) of the last rollout step under a human library (pg_get_human_state)."""
-        u = np.zeros((self.B, 2))
-        self._chk(self.lib.pg_get_human_state(self.h, _p(u)), "pg_get_human_state")
-        return u
-
-    def _human_hist(self, record, steps):
-        """registers a [steps][B][2] device record of the library's (omega, a) with the next rollout call; {} unless record and a library is installed"""
-        if not record:
-            return {}
-        n = C.c_int32(0)
-        self._chk(self.lib.pg_get_human_sets(self.h, C.byref(n), None, 0, None, 0), "pg_get_human_sets")
-        if n.value == 0:
-            return {}
-        torch, tdt, dev = self._torch()
-        buf = torch.empty(int(steps), self.B, 2, dtype=tdt, device=dev)
-        self._chk(self.lib.pg_set_human_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_human_history_dev")
-        return {"human_u": buf}
+        return self._state("human", 2)
 
     def _torch(self):
         """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""
         import torch
         return torch, torch.float32 if self.precision == "f32" else torch.float64, f"cuda:{self.cfg.device}"
-
-    def _measured_hist(self, measured, steps):
-        """registers a [steps][B][6] device record of the measured state with the next rollout call (pg_set_measured_history_dev); None unless asked for"""
-        if not measured:
-            return None
-        torch, tdt, dev = self._torch()
-        buf = torch.empty(int(steps), self.B, 6, dtype=tdt, device=dev)
-        self._chk(self.lib.pg_set_measured_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_measured_history_dev")
-        return buf
 
     # ---- mpc.HJI_cache = HJICache(...) (Pigeon.jl:40) ----
     def set_hji_cache(self, grid_knots, V_raw, gradV_raw):
@@ -630,6 +584,9 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_step_dev(self.h, C.c_void_p(u_out_ptr) if u_out_ptr else None), "pg_step_dev")
 
     HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
+    # the records a library adds to those of a rollout with record=True: (key, history setter, library, width)
+    LIBRARY_RECORDS = (("applied", "pg_set_applied_history_dev", "actuator", 3), ("command", "pg_set_command_history_dev", "actuator", 3),
+                       ("disturbance", "pg_set_disturbance_history_dev", "disturbance", 4), ("human_u", "pg_set_human_history_dev", "human", 2))
 
     def _rollout(self, steps, record, measured, shapes, int_record, call, human="hold", human_u=None, other=True, estimated=False):
         """The rollouts' shared plumbing.  Device records [steps][B] + shapes[name] in the library's element type and one int32 record `int_record` (record=True), the scripted
@@ -650,12 +607,13 @@ class BatchedTrajectoryTrackingMPC:
             hist = {k: torch.empty((steps, self.B) + s, dtype=tdt, device=dev) for k, s in shapes.items()}
             if int_record:
                 hist[int_record] = torch.empty((steps, self.B), dtype=torch.int32, device=dev)
-        mbuf = self._measured_hist(measured, steps)
-        ebuf = self._estimated_hist(estimated, steps)
-        abuf = self._actuator_hists(record, steps)
-        abuf.update(self._disturbance_hist(record, steps))
-        if other:
-            abuf.update(self._human_hist(record, steps))
+        mbuf = self._hist("pg_set_measured_history_dev", 6, steps) if measured else None
+        ebuf = self._hist("pg_set_estimated_history_dev", 6, steps) if estimated else None
+        abuf = {}
+        for key, setter, library, width in self.LIBRARY_RECORDS if record else ():
+            buf = self._hist(setter, width, steps, library) if other or library != "human" else None
+            if buf is not None:
+                abuf[key] = buf
         call(lambda t: C.c_void_p(t.data_ptr()) if t is not None else None, hu, hist)
         s = np.zeros((self.B, 6)); c = np.zeros((self.B, 3)); t = np.zeros(self.B); o = np.zeros((self.B, 4))
         self._chk(self.lib.pg_get_state(self.h, _p(s), _p(c), _p(t)), "pg_get_state")

@@ -1,4 +1,4 @@
-"""One index rule for the four per-instance libraries (trajectories, control parameters, plants, sensors): pg_set_*_index writes the WHOLE [capacity] device array,
+"""One index rule for the eight per-instance libraries (trajectories, control parameters, plants, sensors; below them actuators, disturbances, estimators, humans): pg_set_*_index writes the WHOLE [capacity] device array,
 entries beyond the indexed batch as 0, and a library of several sets wants an index that covers the batch.
 
 Per library, on a handle of capacity 80: a library of four sets with an index over 80 instances that uses set 3; then a library of two sets with an index over 70
@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 
 import plant_numpy
+import rollout_libs as rl
 import sensor_numpy
+from test_gpu_human_sets import grid  # noqa: F401  (the fixture: the grid of the human library's tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -62,3 +64,27 @@ def test_a_smaller_library_and_a_shorter_index_leave_nothing_of_the_earlier_ones
     fresh.close()
     for g, w in zip(got, want):
         assert g.tobytes() == w.tobytes()
+
+
+RESPONSE = {"actuator": lambda m: m.actuator_response(np.zeros((3, rl.B, 3)), DT),
+            "disturbance": lambda m: m.disturbance_response(0, 3, DT),
+            "estimator": lambda m: m.estimator_response(np.zeros((3, rl.B, 6)), np.zeros((3, rl.B, 3)), DT),
+            "human": lambda m: m.human_response(0, np.zeros((3, rl.B, 7)), np.zeros((3, rl.B, 8)), DT)}
+
+
+@pytest.mark.parametrize("library", ["actuator", "disturbance", "estimator", "human"])
+def test_the_other_four_libraries_want_an_index_that_covers_the_batch(pkg, skidpad, grid, library):
+    """The same rule for the libraries of the rollouts' actuator, disturbance, estimator and human: two sets and an index over B - 1 of the B = 5 instances.  The rollout
+    (three steps asked for) and the library's *_response call both refuse with PG_ERR_STATE and the index rule's one message."""
+    _, identity, setter, _ = rl.LIBRARIES[library]
+    refusal = f"a {library} library is installed but {setter} does not cover the batch"
+    m = rl.make(pkg, skidpad, grid)
+    state, control, t0, other, toff = rl.inputs(pkg, skidpad)
+    m.set_inputs(state, control, t0, other, toff)
+    rl.install(m, library, [identity, identity], np.array([0, 1, 0, 1], dtype=np.int32))
+    assert rl.rollout(m, library, 3) == rl.STATE
+    assert rl.last_error(m) == refusal
+    with pytest.raises(pkg.PigeonError) as e:
+        RESPONSE[library](m)
+    assert str(e.value) == f"pg_{library}_response failed with status {rl.STATE}: {refusal}"
+    m.close()
