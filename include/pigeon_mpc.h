@@ -453,6 +453,53 @@ int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, con
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
 int pg_clear_hji_grid(pg_handle* h);
 
+/* Making a grid: the backward reachable tube of the relative system, computed on the device for the handle's vehicle or for any pg_vehicle.  Stands in for the external
+ * level-set toolbox run whose result the reference downloads (deps/build.jl:1-4: BicycleCAvoid.jld2); the reference itself holds no solver, so the scheme is
+ * build-defined (tests/hji_solve_numpy.py is its numpy twin).  The roles are those of src/HJI_computation.jl:74-158: the robot maximises with
+ * optimal_control(X, x, p, :max, N = 50) (:133-158), the human minimises with optimal_disturbance(X, x, p, :min) (:90-131; (0, 0) at a knot V <= 0, where the
+ * reference divides by zero), f = relative_dynamics(X, x, uR, uH) (:74-88).  V <= 0 is unsafe.
+ *   Tube      V(0) = l0, dV/dtau = min(0, H), H(x, p) = p . f(x, uR*(p), uH*(p)), over tau in [0, horizon].
+ *   One sweep at node i, dimension d: p-_d = (V_i - V_{i-e_d}) / (x_d[i_d] - x_d[i_d-1]), p+_d the forward counterpart (actual spacings); at a low face p- := p+, at a
+ *             high face p+ := p-; pbar = (p+ + p-) / 2; Hhat = H(x_i, pbar) + sum_d alpha_d (p+_d - p-_d) / 2 with alpha_d = max over all nodes of |f_d| at this
+ *             sweep's pbar; V_i <- float32(V_i + dt min(0, Hhat)).  dt = min(cfl / sum_d (alpha_d / min spacing_d), horizon - tau), or min(fixed_dt, horizon - tau)
+ *             with fixed_dt > 0 (alpha is reduced all the same).  Arithmetic in the library's element type; V is float32 after every sweep in both libraries.
+ *   PG_HJI_PERIODIC_PSI  dimension 3 wraps: first and last knot are the same angle (at least 3 knots).  The low neighbour of node 0 is node n-2 at spacing
+ *             x[n-1] - x[n-2], the high neighbour of node n-1 is node 1 at spacing x[1] - x[0]; the last node's dynamics are evaluated at the first knot's angle, so the
+ *             two end nodes, each computed on its own, stay bit-identical whenever l0 is.
+ *   gradV     pbar of the final V, same face and wrap rules, 7 floats per node in node order.
+ * max_sweeps bounds the loop; reaching it is reported (reached_horizon = 0), not an error.  A NaN or Inf in V after a sweep ends the solve with PG_ERR_INVALID and
+ * the sweep's index in bad_sweep (-1 otherwise; the other fields describe the sweeps taken); nothing is installed. */
+enum pg_hji_solve_flags { PG_HJI_PERIODIC_PSI = 1 };
+typedef struct pg_hji_solve_opts {
+    double horizon;                 /* s, >= 0 (0: no sweep, V = l0) */
+    double cfl;                     /* in (0, 1]; default 0.8 */
+    double fixed_dt;                /* > 0: replaces the CFL rule; 0 (default): the CFL rule */
+    int32_t max_sweeps;             /* >= 0; default 100000 */
+    int32_t flags;                  /* pg_hji_solve_flags */
+} pg_hji_solve_opts;                /* 32 bytes */
+typedef struct pg_hji_solve_stats {
+    int32_t sweeps;                 /* sweeps taken */
+    int32_t reached_horizon;        /* 1: tau == horizon; 0: max_sweeps ended the loop */
+    int32_t bad_sweep;              /* index of the sweep after which V held a NaN or Inf (0-based; 0 too when l0 itself holds one), -1: none */
+    int32_t reserved;
+    double tau;                     /* time covered */
+    double last_dt;                 /* step of the last sweep (0 without one) */
+    double alpha[7];                /* the dissipation coefficients of the last sweep */
+    double v_min, v_max;            /* over the nodes of the result */
+} pg_hji_solve_stats;               /* 104 bytes */
+/* { horizon 3, cfl 0.8, fixed_dt 0, max_sweeps 100000, flags 0 } */
+pg_hji_solve_opts pg_default_hji_solve_opts(void);
+/* dims, knots_concat as pg_set_hji_grid takes them; l0 [prod dims] the target, column-major.  vehicle NULL: pg_config.vehicle; opts NULL: the defaults.  V_out [prod dims]
+ * and gradV_out [prod dims][7] (either may be NULL) are what pg_set_hji_grid takes.  install != 0 builds the handle's lookup table (the cell records of the current
+ * "hji_cell_dims") from the device buffers, with no host round trip: the handle is then exactly as after pg_set_hji_grid(h, dims, knots_concat, V_out, gradV_out).
+ * stats may be NULL.  Synchronous.  A handle that never calls this launches what it launched before.
+ * PG_ERR_INVALID (the handle and its installed grid are left unchanged): a null dims, knots_concat or l0; a dimension below 2; knots that do not increase strictly; a
+ * knot of dimension 4 (Ux) <= 0; PG_HJI_PERIODIC_PSI with fewer than 3 knots in dimension 3 or a span that is not 2 pi to float32 rounding (one ulp of 2 pi);
+ * unknown flags; horizon < 0 or not finite; cfl outside (0, 1]; fixed_dt < 0; max_sweeps < 0; a vehicle pg_set_plant_sets would refuse.
+ * PG_ERR_STATE: install on a decoupled handle (the safety row belongs to the coupled formulation). */
+int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* l0, const pg_vehicle* vehicle, const pg_hji_solve_opts* opts,
+                 int32_t install, float* V_out, float* gradV_out, pg_hji_solve_stats* stats);
+
 /* mpc.solved = false (src/ros_integration.jl:34,41,147): mask[b] != 0 resets instance b; mask == NULL resets all */
 int pg_reset(pg_handle* h, const uint8_t* mask);
 

@@ -464,6 +464,46 @@ function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,
                             mpc.handle, dims, vcat(grid_knots...), V_raw, ∇V_raw), "pg_set_hji_grid")
 end
 
+# Making a grid (pg_hji_solve): the avoid set computed on the device.  NOT EXECUTED in the build container, like the rest of this file.
+const PG_HJI_PERIODIC_PSI = Int32(1)
+"pg_hji_solve_opts (32 bytes): horizon (s), CFL number in (0, 1], a fixed step (0: the CFL rule), the bound on the sweeps, the flags"
+struct PgHjiSolveOpts
+    horizon::Float64
+    cfl::Float64
+    fixed_dt::Float64
+    max_sweeps::Int32
+    flags::Int32
+end
+PgHjiSolveOpts(; horizon=3.0, cfl=0.8, fixed_dt=0.0, max_sweeps=100000, periodic_psi=false) =
+    PgHjiSolveOpts(Float64(horizon), Float64(cfl), Float64(fixed_dt), Int32(max_sweeps), periodic_psi ? PG_HJI_PERIODIC_PSI : Int32(0))
+"pg_hji_solve_stats (104 bytes)"
+struct PgHjiSolveStats
+    sweeps::Int32
+    reached_horizon::Int32
+    bad_sweep::Int32
+    reserved::Int32
+    tau::Float64
+    last_dt::Float64
+    alpha::NTuple{7,Float64}
+    v_min::Float64
+    v_max::Float64
+end
+"The reachable tube of the target l0 over opts.horizon for `vehicle` (nothing: the handle's own): (V_raw, ∇V_raw, stats) as set_hji_cache! takes them; install = true leaves the handle as set_hji_cache! would, without a host round trip (stands in for the toolbox run behind deps/build.jl:1-4)"
+function solve_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, l0::Array{Float32,7}, opts::PgHjiSolveOpts=PgHjiSolveOpts();
+                          vehicle::Union{Nothing,PgVehicle}=nothing, install::Bool=true)
+    (sizeof(PgHjiSolveOpts), sizeof(PgHjiSolveStats)) == (32, 104) || error("PigeonMI355X.jl: PgHjiSolveOpts / PgHjiSolveStats differ from include/pigeon_mpc.h")
+    dims = Int32[length(k) for k in grid_knots]
+    V = zeros(Float32, size(l0)); g = zeros(Float32, 7, size(l0)...)
+    stats = Ref{PgHjiSolveStats}()
+    veh = vehicle === nothing ? Ptr{PgVehicle}(C_NULL) : Ref(vehicle)
+    check(mpc, ccall(sym(mpc, :pg_hji_solve), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{PgVehicle}, Ref{PgHjiSolveOpts}, Int32, Ptr{Float32}, Ptr{Float32}, Ref{PgHjiSolveStats}),
+                     mpc.handle, dims, vcat(grid_knots...), l0, veh, Ref(opts), Int32(install), V, g, stats), "pg_hji_solve")
+    V, g, stats[]
+end
+
+"{ horizon 3, cfl 0.8, fixed_dt 0, max_sweeps 100000, flags 0 } as the library states them (pg_default_hji_solve_opts)"
+default_hji_solve_opts(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_hji_solve_opts), PgHjiSolveOpts, ())
+
 "mpc.solved = false (src/ros_integration.jl:34,41,147)"
 reset!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_reset), Cint, (Ptr{Cvoid}, Ptr{UInt8}), mpc.handle, C_NULL), "pg_reset")
 

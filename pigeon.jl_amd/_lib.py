@@ -41,7 +41,7 @@ SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_defaul
            "pg_set_disturbance_sets", "pg_set_disturbance_index", "pg_set_disturbance_seed", "pg_clear_disturbance_sets", "pg_get_disturbance_sets", "pg_disturbance_response", "pg_get_disturbance_state", "pg_set_disturbance_history_dev",
            "pg_set_estimator_sets", "pg_set_estimator_index", "pg_clear_estimator_sets", "pg_get_estimator_sets", "pg_get_estimated_state", "pg_set_estimated_history_dev", "pg_estimator_response",
            "pg_set_human_sets", "pg_set_human_index", "pg_set_human_seed", "pg_clear_human_sets", "pg_get_human_sets", "pg_get_human_state", "pg_set_human_history_dev", "pg_human_response",
-           "pg_set_hji_grid", "pg_clear_hji_grid", "pg_reset", "pg_set_inputs", "pg_set_inputs_dev", "pg_compute_time_steps",
+           "pg_set_hji_grid", "pg_clear_hji_grid", "pg_default_hji_solve_opts", "pg_hji_solve", "pg_reset", "pg_set_inputs", "pg_set_inputs_dev", "pg_compute_time_steps",
            "pg_compute_linearization_nodes", "pg_update_qp", "pg_solve", "pg_get_next_control", "pg_get_next_control_dev", "pg_get_next_control_hji", "pg_get_next_control_hji_dev", "pg_step", "pg_step_dev", "pg_simulate_dev", "pg_simulate_clock", "pg_get_state", "pg_simulate_safety_dev", "pg_get_safety_state", "pg_node_step_dev", "pg_simulate_node_dev", "pg_get_node_state",
            "pg_set_stream", "pg_set_fusion", "pg_set_pipeline", "pg_set_option", "pg_get_option", "pg_get_pipeline_fallbacks", "pg_synchronize", "pg_get_time_steps", "pg_get_nodes", "pg_get_path_coordinates", "pg_qp_len", "pg_get_qp", "pg_set_qp", "pg_get_solution",
            "pg_get_solve_info", "pg_get_polish_info", "pg_get_multipliers", "pg_get_phase_ms", "pg_hji_lookup", "pg_hji_lookup_dev", "pg_hji_lookup8_dev", "pg_hji_grid_dims", "pg_hji_slice", "pg_get_hji_constraint", "pg_get_walls"]
@@ -148,6 +148,27 @@ HUMAN_SET_PROTOTYPES = {
 }
 
 
+PG_HJI_PERIODIC_PSI = 1
+
+
+class pg_hji_solve_opts(C.Structure):
+    """include/pigeon_mpc.h pg_hji_solve_opts: horizon (s), CFL number, a fixed step (0: the CFL rule), the bound on the sweeps, the flags (PG_HJI_PERIODIC_PSI)."""
+    _fields_ = [("horizon", C.c_double), ("cfl", C.c_double), ("fixed_dt", C.c_double), ("max_sweeps", C.c_int32), ("flags", C.c_int32)]
+
+
+class pg_hji_solve_stats(C.Structure):
+    """include/pigeon_mpc.h pg_hji_solve_stats."""
+    _fields_ = [("sweeps", C.c_int32), ("reached_horizon", C.c_int32), ("bad_sweep", C.c_int32), ("reserved", C.c_int32), ("tau", C.c_double), ("last_dt", C.c_double),
+                ("alpha", C.c_double * 7), ("v_min", C.c_double), ("v_max", C.c_double)]
+
+
+# grid solver (include/pigeon_mpc.h: pg_hji_solve)
+HJI_SOLVE_PROTOTYPES = {
+    "pg_hji_solve": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(pg_vehicle), C.POINTER(pg_hji_solve_opts), C.c_int32,
+                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(pg_hji_solve_stats)],
+}
+
+
 def load_library(precision="f64"):
     """Loads the HIP library of the requested arithmetic type.  PyTorch-ROCm is imported first so that both share ONE HIP runtime in this process."""
     assert precision in ("f64", "f32", "f64-diag")
@@ -169,10 +190,12 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
+    lib.pg_default_hji_solve_opts.argtypes = []
+    lib.pg_default_hji_solve_opts.restype = pg_hji_solve_opts
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)
     check_layout(lib)
     _libs[precision] = lib

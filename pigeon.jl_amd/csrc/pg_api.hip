@@ -1304,6 +1304,7 @@ int pg_clear_hji_grid(pg_handle* h) {
     return PG_OK;
 }
 
+static int hji_install_nodes(pg_handle* h, const int32_t dims[7]);
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, dims && knots_concat && V && gradV, "pg_set_hji_grid: null argument");
@@ -1319,6 +1320,11 @@ int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_conc
     HIPCHK(h, hipMalloc((void**)&h->d_knots, (size_t)nk * sizeof(float)));
     HIPCHK(h, hipMemcpy(h->d_hnodes, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_knots, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice));
+    return hji_install_nodes(h, dims);
+}
+// the lookup table of the handle from the node records h->d_hnodes and the knots h->d_knots (both on the device, owned by the handle): what pg_set_hji_grid does after
+// its upload and pg_hji_solve after its last sweep
+static int hji_install_nodes(pg_handle* h, const int32_t dims[7]) {
     long st = 1; int ko = 0;
     for (int d = 0; d < 7; d++) { h->hv.dims[d] = dims[d]; h->hv.koff[d] = ko; h->hv.stride[d] = st; st *= dims[d]; ko += dims[d]; }
     h->hv.knots = h->d_knots; h->hv.nodes = h->d_hnodes;
@@ -1342,6 +1348,127 @@ int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_conc
     HIPCHK(h, hipStreamSynchronize(h->stream));
     (void)hipFree(h->d_hnodes); h->d_hnodes = nullptr; h->hv.nodes = nullptr;
     h->has_hji = true; h->dc.has_hji = 1;
+    return PG_OK;
+}
+
+// ---- pg_hji_solve: the reachable-tube sweeps (pg_hji_solve.hip).  The host owns the only loop over sweeps: eval -> alpha to the host -> dt -> update ----
+pg_hji_solve_opts pg_default_hji_solve_opts(void) {
+    pg_hji_solve_opts o; o.horizon = 3.0; o.cfl = 0.8; o.fixed_dt = 0.0; o.max_sweeps = 100000; o.flags = 0;
+    return o;
+}
+namespace {
+struct HjiSolveBufs {                                   // device memory of one solve: released on every way out, except what an install hands to the handle
+    float *kn = nullptr, *V[2] = {nullptr, nullptr}, *rec = nullptr; real *Hc = nullptr, *alpha = nullptr; int* bad = nullptr; unsigned int* vkeys = nullptr;
+    ~HjiSolveBufs() { for (void* p : {(void*)kn, (void*)V[0], (void*)V[1], (void*)rec, (void*)Hc, (void*)alpha, (void*)bad, (void*)vkeys}) if (p) (void)hipFree(p); }
+};
+float hji_key_float(unsigned int k) { unsigned int b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &b, 4); return f; }
+}  // namespace
+int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* l0, const pg_vehicle* vehicle, const pg_hji_solve_opts* opts,
+                 int32_t install, float* V_out, float* gradV_out, pg_hji_solve_stats* stats) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, dims && knots_concat && l0, "pg_hji_solve: null argument");
+    const pg_hji_solve_opts O = opts ? *opts : pg_default_hji_solve_opts();
+    size_t n = 1; int nk = 0;
+    for (int d = 0; d < 7; d++) { REQUIRE(h, dims[d] >= 2, "pg_hji_solve: every dimension needs >= 2 knots"); n *= dims[d]; nk += dims[d]; }
+    double minsp[7];
+    {
+        const float* k = knots_concat;
+        for (int d = 0; d < 7; d++) {
+            minsp[d] = INFINITY;
+            for (int i = 0; i < dims[d]; i++) REQUIRE(h, std::isfinite(k[i]), "pg_hji_solve: a knot is not finite");
+            for (int i = 1; i < dims[d]; i++) {
+                REQUIRE(h, k[i] > k[i - 1], "pg_hji_solve: knots must increase strictly");
+                minsp[d] = std::min(minsp[d], (double)k[i] - (double)k[i - 1]);
+            }
+            if (d == 3) REQUIRE(h, k[0] > 0.0f, "pg_hji_solve: the knots of dimension 4 (Ux) must be positive");
+            if (d == 2 && (O.flags & PG_HJI_PERIODIC_PSI)) {
+                REQUIRE(h, dims[d] >= 3, "pg_hji_solve: a periodic dimension 3 needs >= 3 knots");
+                REQUIRE(h, fabs(((double)k[dims[d] - 1] - (double)k[0]) - 2.0 * M_PI) <= 4.76837158203125e-07, "pg_hji_solve: a periodic dimension 3 spans 2 pi");
+            }
+            k += dims[d];
+        }
+    }
+    REQUIRE(h, (O.flags & ~(int32_t)PG_HJI_PERIODIC_PSI) == 0, "pg_hji_solve: unknown flags");
+    REQUIRE(h, std::isfinite(O.horizon) && O.horizon >= 0.0, "pg_hji_solve: horizon must be finite and >= 0");
+    REQUIRE(h, O.cfl > 0.0 && O.cfl <= 1.0, "pg_hji_solve: cfl must lie in (0, 1]");
+    REQUIRE(h, std::isfinite(O.fixed_dt) && O.fixed_dt >= 0.0, "pg_hji_solve: fixed_dt must be finite and >= 0");
+    REQUIRE(h, O.max_sweeps >= 0, "pg_hji_solve: max_sweeps must be >= 0");
+    if (vehicle) { const char* why = plant_set_problem(*vehicle); REQUIRE(h, !why, std::string("pg_hji_solve: the vehicle: ") + (why ? why : "")); }
+    if (install && h->dc.formulation != PG_COUPLED) { h->err = "pg_hji_solve: install: the HJI safety row belongs to the coupled formulation only (coupled_lat_long.jl:341-346)"; return PG_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    HjiSolveGrid G; long st = 1; int ko = 0;
+    for (int d = 0; d < 7; d++) { G.dims[d] = dims[d]; G.koff[d] = ko; G.stride[d] = st; st *= dims[d]; ko += dims[d]; }
+    G.n = (long)n; G.periodic = (O.flags & PG_HJI_PERIODIC_PSI) ? 1 : 0;
+    DevVehicle P; fill_dev_vehicle(P, vehicle ? *vehicle : h->cfg.vehicle);
+    HjiSolveBufs D;
+    HIPCHK(h, hipMalloc((void**)&D.kn, (size_t)nk * sizeof(float)));
+    HIPCHK(h, hipMalloc((void**)&D.V[0], n * sizeof(float)));
+    HIPCHK(h, hipMalloc((void**)&D.V[1], n * sizeof(float)));
+    HIPCHK(h, hipMalloc((void**)&D.Hc, n * sizeof(real)));
+    HIPCHK(h, hipMalloc((void**)&D.rec, n * 8 * sizeof(float)));
+    HIPCHK(h, hipMalloc((void**)&D.alpha, 7 * sizeof(real)));
+    HIPCHK(h, hipMalloc((void**)&D.bad, sizeof(int)));
+    HIPCHK(h, hipMalloc((void**)&D.vkeys, 2 * sizeof(unsigned int)));
+    G.knots = D.kn;
+    HIPCHK(h, hipMemcpyAsync(D.kn, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(D.V[0], l0, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(D.bad, 0, sizeof(int), h->stream));
+    const unsigned int keys0[2] = {0xffffffffu, 0u};
+    HIPCHK(h, hipMemcpyAsync(D.vkeys, keys0, sizeof(keys0), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (the host arrays have been consumed)
+
+    pg_hji_solve_stats S; memset(&S, 0, sizeof(S)); S.bad_sweep = -1;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    int cur = 0, bad = 0;
+    bool reached = !(O.horizon > 0.0);
+    while (!reached && S.sweeps < O.max_sweeps) {
+        real a[7];
+        HIPCHK(h, hipMemsetAsync(D.alpha, 0, 7 * sizeof(real), h->stream));
+        hipLaunchKernelGGL(k_hji_sweep_eval, grid, block, 0, h->stream, G, P, (const float*)D.V[cur], D.Hc, D.alpha);
+        LAUNCH_CHECK(h);
+        HIPCHK(h, hipMemcpyAsync(a, D.alpha, sizeof(a), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&bad, D.bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));      // (the flag of the previous sweep's update)
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (bad) break;
+        double sum = 0.0;
+        for (int d = 0; d < 7; d++) { S.alpha[d] = (double)a[d]; sum += (double)a[d] / minsp[d]; }
+        double dt = O.fixed_dt > 0.0 ? O.fixed_dt : O.cfl / sum;          // (sum = 0: nothing moves, dt = +Inf and the step below is the whole remainder)
+        const double rem = O.horizon - S.tau;
+        const bool last = !(dt < rem);
+        if (last) dt = rem;
+        hipLaunchKernelGGL(k_hji_sweep_update, grid, block, 0, h->stream, G, (const float*)D.V[cur], (const real*)D.Hc, (const real*)D.alpha, (real)dt, D.V[cur ^ 1], D.bad);
+        LAUNCH_CHECK(h);
+        cur ^= 1; S.sweeps++; S.last_dt = dt; S.tau = last ? O.horizon : S.tau + dt; reached = last;
+    }
+    if (!bad) {
+        hipLaunchKernelGGL(k_hji_finish, grid, block, 0, h->stream, G, (const float*)D.V[cur], D.rec, D.vkeys, D.bad);
+        LAUNCH_CHECK(h);
+        unsigned int keys[2];
+        HIPCHK(h, hipMemcpyAsync(keys, D.vkeys, sizeof(keys), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&bad, D.bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        S.v_min = (double)hji_key_float(keys[0]); S.v_max = (double)hji_key_float(keys[1]);
+    }
+    S.reached_horizon = (int32_t)(reached && !bad);
+    if (bad) {
+        S.bad_sweep = S.sweeps > 0 ? S.sweeps - 1 : 0;
+        if (stats) *stats = S;
+        h->err = "pg_hji_solve: V holds a NaN or Inf after sweep " + std::to_string(S.bad_sweep) + " (nothing was installed)";
+        return PG_ERR_INVALID;
+    }
+    if (V_out) HIPCHK(h, hipMemcpy(V_out, D.V[cur], n * sizeof(float), hipMemcpyDeviceToHost));
+    if (gradV_out) {                                    // the records hold (V, gradV[7]): 28 of every 32 bytes
+        std::vector<float> rec(n * 8);
+        HIPCHK(h, hipMemcpy(rec.data(), D.rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) for (int k = 0; k < 7; k++) gradV_out[7 * i + k] = rec[8 * i + 1 + k];
+    }
+    if (stats) *stats = S;
+    if (install) {
+        pg_clear_hji_grid(h);
+        h->d_hnodes = D.rec; h->d_knots = D.kn; D.rec = nullptr; D.kn = nullptr;
+        return hji_install_nodes(h, dims);
+    }
     return PG_OK;
 }
 

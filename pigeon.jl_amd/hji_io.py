@@ -53,6 +53,20 @@ def load_hji_grid(path):
     return knots, V.copy(), g.reshape(n, 7).copy()
 
 
+def collision_target(knots, half_length, half_width):
+    """The target of the avoid set: the signed distance of (dE, dN) -- the other car's position in the ego frame, dE along the ego's heading -- to the rectangle
+    |dE| <= half_length, |dN| <= half_width (negative inside), the same for every value of the other five dimensions.  Returns l0 [prod dims] float32, column-major
+    (dimension 1 fastest), as BatchedTrajectoryTrackingMPC.solve_hji_cache takes it."""
+    dims = [len(k) for k in knots]
+    if len(dims) != 7:
+        raise ValueError("collision_target: 7 knot vectors expected")
+    qx = np.abs(np.asarray(knots[0], dtype=np.float64))[:, None] - float(half_length)
+    qy = np.abs(np.asarray(knots[1], dtype=np.float64))[None, :] - float(half_width)
+    sd = np.hypot(np.maximum(qx, 0.0), np.maximum(qy, 0.0)) + np.minimum(np.maximum(qx, qy), 0.0)
+    full = np.broadcast_to(sd.reshape(dims[0], dims[1], 1, 1, 1, 1, 1), dims)
+    return np.asarray(full, dtype=np.float32).reshape(-1, order="F")
+
+
 def trace_zero_contour(X, Y, cross_x, cross_y):
     """First zero-level line of one slice as an ordered vertex list [(x, y), ...] -- what update_HJI_contour_marker! publishes (rviz.jl:63-68: c.lines[1]).
     cross_x [n1-1, n2], cross_y [n1, n2-1] from hji_value_slice.  Marching squares over the cells, walking from edge to edge; saddle cells (four crossings)

@@ -518,6 +518,38 @@ class BatchedTrajectoryTrackingMPC:
     def clear_hji_cache(self):
         self._chk(self.lib.pg_clear_hji_grid(self.h), "pg_clear_hji_grid")
 
+    def solve_hji_cache(self, grid_knots, l0, horizon, vehicle=None, install=True, **opts):
+        """Computes the avoid-set grid on the device (pg_hji_solve): the reachable tube of the target l0 [prod dims] (column-major, e.g. hji_io.collision_target) over
+        `horizon` seconds for `vehicle` (a vehicles.X1(**overrides) dict or a pg_vehicle; None: the handle's own).  opts: cfl, fixed_dt, max_sweeps, periodic_psi.
+        Returns (V [prod dims] float32, gradV [prod dims, 7] float32, stats dict) -- what set_hji_cache takes; install=True leaves the handle as set_hji_cache would.
+        A refused argument or a NaN in V raises PigeonError; its `stats` attribute then holds the stats of the sweeps taken."""
+        dims = np.array([len(k) for k in grid_knots], dtype=np.int32)
+        kc = np.ascontiguousarray(np.concatenate([np.asarray(k, dtype=np.float32) for k in grid_knots]))
+        l0 = np.ascontiguousarray(l0, dtype=np.float32).reshape(-1)
+        n = int(np.prod(dims.astype(np.int64)))
+        assert len(dims) == 7 and l0.size == n
+        o = self.lib.pg_default_hji_solve_opts()
+        o.horizon = float(horizon)
+        periodic = bool(opts.pop("periodic_psi", False))
+        o.flags = _lib.PG_HJI_PERIODIC_PSI if periodic else 0
+        for k in list(opts):
+            if k not in ("cfl", "fixed_dt", "max_sweeps"):
+                raise KeyError(f"{k} is not an option of solve_hji_cache: cfl, fixed_dt, max_sweeps, periodic_psi")
+            setattr(o, k, int(opts[k]) if k == "max_sweeps" else float(opts[k]))
+        veh = None if vehicle is None else self.pack_vehicles([vehicle])
+        V = np.zeros(n, dtype=np.float32); g = np.zeros((n, 7), dtype=np.float32)
+        st = _lib.pg_hji_solve_stats()
+        fp = C.POINTER(C.c_float)
+        rc = self.lib.pg_hji_solve(self.h, _p(dims, c_i32p), _p(kc, fp), _p(l0, fp), veh, C.byref(o), int(bool(install)), _p(V, fp), _p(g, fp), C.byref(st))
+        stats = {"sweeps": st.sweeps, "reached_horizon": st.reached_horizon, "bad_sweep": st.bad_sweep, "tau": st.tau, "last_dt": st.last_dt,
+                 "alpha": np.array(list(st.alpha)), "v_min": st.v_min, "v_max": st.v_max}
+        try:
+            self._chk(rc, "pg_hji_solve")
+        except _lib.PigeonError as e:
+            e.stats = stats; e.status = rc
+            raise
+        return V, g, stats
+
     # ---- mpc.solved = false (ros_integration.jl:34,41,147) ----
     def reset(self, mask=None):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
