@@ -163,6 +163,52 @@ int pg_set_trajectories(pg_handle* h, int32_t n_traj, int32_t Lmax, const int32_
  * With n_traj > 1 the phase calls return PG_ERR_STATE until an index covering the current batch is installed. */
 int pg_set_trajectory_index(pg_handle* h, int32_t B, const int32_t* index);
 
+/* Making the speed profile: friction-limited V, A and t of every (path, plan set) pair of a path library and a library of plan sets, computed on the device in the
+ * layout pg_set_trajectories takes.  The reference takes UxDes / AxDes as its path message gives them (src/ros_integration.jl:13-16) from a planner outside its tree, so
+ * the scheme is build-defined (tests/speed_plan_numpy.py is its numpy twin).  It works on W = V^2, all arithmetic in the library's element type, every operation rounded
+ * on its own; only t is accumulated in double and rounded on store.  No grade force, as the plant applies none (src/vehicle_dynamics.jl:122).
+ *   Limits    a_lim = mu_scale vehicle.mu vehicle.G, ay = min(a_lim, ay_max);  cap_i = max(V_floor^2, min(V_max^2, ay / |kappa_i|)), V_max^2 where kappa_i = 0;
+ *             along(W, kappa) = sqrt(max(a_lim^2 - (W kappa)^2, 0));  Fd(V) = Cd0 + V (Cd1 + Cd2 V), V = sqrt(W);
+ *             acc(W, kappa) = min((min(m along, Fx_max, Px_max / V) - Fd) / m, ax_max);  dec(W, kappa) = max(min((min(m along, -Fx_min) + Fd) / m, -ax_min), 0).
+ *   Open      W_i = cap_i, the first / last knot lowered to max(V_start, V_floor)^2 / max(V_end, V_floor)^2 when given (never above the cap).
+ *             Backward, i = L-2 .. 0: W_i = min(W_i, W_{i+1} + 2 ds_i dec(W_{i+1}, kappa_{i+1})), ds_i = s_{i+1} - s_i.
+ *             Forward, i = 0 .. L-2: W_{i+1} = min(W_{i+1}, max(W_i + 2 ds_i acc(W_i, kappa_i), V_floor^2)).
+ *   Closed    knot L-1 is knot 0 again.  Both passes start at i0, the first knot of largest |kappa| among knots 0 .. L-2 (the smallest cap: W = cap stays there), and
+ *             go once around modulo L-1 in L-2 steps -- knot i0 itself is not revisited --, the wrap interval being s_{L-1} - s_{L-2}.  W_{L-1} = W_0 at the end.
+ *             V_start / V_end are ignored.
+ *   Result    V = sqrt(W);  A_i = (W_{i+1} - W_i) / (2 ds_i), A_{L-1} = 0 (open) or A_0 (closed);  t_0 = 0, t_{i+1} = t_i + 2 ds_i / (V_i + V_{i+1}) (math.jl:2).
+ *             The limiter of a knot is the last pass that lowered it, else the cap (knot L-1 of a closed path: that of knot 0).
+ * The scheme is explicit -- dec and acc are evaluated at the knot the pass comes from --, so the result may use slightly more than a_lim between two knots of different
+ * curvature: usage_max reports it -- measured at V_max 20: 1.05-1.08 on the committed ovals and vail (knots 0.10-0.24 m apart), 1.19 on variable_speed (28 knots about
+ * 2 m apart) at mu_scale 0.5, 0 on the straight lines (EXPERIMENTS 27) --; no implicit solve hides it. */
+typedef struct pg_speed_plan {
+    double mu_scale;        /* a_lim = mu_scale * vehicle.mu * vehicle.G; > 0, finite */
+    double V_max;           /* > 0, finite */
+    double V_floor;         /* > 0, <= V_max: no knot is planned slower (keeps t finite); default 1.0 = control V_min */
+    double V_start, V_end;  /* open path: speed at the first / last knot (finite, >= 0); NaN: free.  Ignored on a closed path */
+    double ax_max, ax_min;  /* extra caps on the tangential acceleration, ax_min <= 0 <= ax_max; +Inf / -Inf: none */
+    double ay_max;          /* extra cap on V^2 |kappa|, > 0; +Inf: none */
+} pg_speed_plan;            /* 64 bytes */
+typedef struct pg_speed_plan_stats {   /* one per output trajectory */
+    double t_end, v_min, v_max;
+    double usage_max;       /* max over knots of sqrt(A^2 + (V^2 kappa)^2) / a_lim of the RESULT */
+    int32_t n_cap, n_accel, n_brake, reserved;   /* knots whose speed is set by the cap, the forward pass, the backward pass; they sum to L */
+} pg_speed_plan_stats;      /* 48 bytes */
+/* { 1, 30, 1, NaN, NaN, +Inf, -Inf, +Inf } */
+pg_speed_plan pg_default_speed_plan(void);
+/* channels_in [n_path][10][Lmax] in the layout and channel order of pg_set_trajectories; its t, V and A channels are ignored, so a library in use can be re-planned as it
+ * stands.  closed[k] != 0: knot L[k]-1 of path k is the same point as knot 0 (the caller's statement; NULL: every path is open).  vehicles NULL: pg_config.vehicle for
+ * every set; else [n_sets], one vehicle per set.  Output trajectory k = path * n_sets + set: channels_out [n_path * n_sets][10][Lmax] and stats [n_path * n_sets]
+ * (either may be NULL).  The seven geometry channels of the valid knots are copied bit for bit (as the library's element type holds them); every channel is 0 at and
+ * past L[k].  install != 0 replaces the handle's trajectory library from the device buffers, with no host round trip: the handle is then exactly as after
+ * pg_set_trajectories(h, n_path * n_sets, Lmax, L repeated, channels_out) -- the fp64 end times, the dropped index.  Synchronous.  A handle that never calls this
+ * launches what it launched before.
+ * PG_ERR_INVALID (the handle and its installed library are left unchanged): a null L, channels_in or sets; n_path or n_sets < 1; Lmax < 2; L[k] outside [2, Lmax]; a
+ * closed path of fewer than 3 knots; s that does not increase strictly over the valid knots (in the library's element type); a non-finite geometry value in a valid
+ * knot; a set outside the ranges above; a vehicle pg_set_plant_sets would refuse; more than 65535 x 16 sets. */
+int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in, int32_t n_sets,
+                   const pg_speed_plan* sets, const pg_vehicle* vehicles, int32_t install, double* channels_out, pg_speed_plan_stats* stats);
+
 /* control_params of one controller per instance (src/coupled_lat_long.jl:42-60, src/decoupled_lat_long.jl:32-50): a library of control-parameter sets and a per-instance
  * selection, the counterpart of pg_set_trajectories / pg_set_trajectory_index for the controller's tuning -- a tuning sweep or robustness study (the same starts and paths
  * under many weightings, speed bounds and steering-rate limits) runs as ONE batch.  With no library the handle behaves as pg_config.control says.  A library of ONE set
@@ -667,6 +713,8 @@ int pg_synchronize(pg_handle* h);
  *     "pipe_pub_short" (3), "pipe_pub_long" (5)   the recurrence of that launch publishes its progress after every n-th node of the short / long horizon (a publication is a
  *                                device-scope release, ~3 us on the serial chain: every node of the short horizon 0.317 -> 0.345 ms)
  *     "lin_lanes" 1/2 (1)        lanes per (instance, interval) of the large-batch linearisation
+ *     "speed_plan_lanes" 0/16/32/64 (0)  sets per wavefront of pg_plan_speeds' kernel; 0 = by the size of the call (64, halved while the launch has fewer than 256
+ *                                wavefronts).  The result does not depend on it
  *     "phase_timing" 0/1 (0)     1 = pg_step_dev records the HIP events pg_get_phase_ms reads (four event records per step on the handle's stream: measured 13-25 us per step, 2-4 % of a
  *                                4096-instance step); 0 = no instrumentation, pg_get_phase_ms returns PG_ERR_STATE
  *     "graph" 0/1 (0)            pg_step of a small warm batch as one hipGraph launch (see pg_step)

@@ -504,6 +504,48 @@ end
 "{ horizon 3, cfl 0.8, fixed_dt 0, max_sweeps 100000, flags 0 } as the library states them (pg_default_hji_solve_opts)"
 default_hji_solve_opts(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_hji_solve_opts), PgHjiSolveOpts, ())
 
+# Making the speed profile (pg_plan_speeds): friction-limited V, A, t of every (path, plan set) pair on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_speed_plan (64 bytes): the share of the friction, the speed cap and floor, the end speeds of an open path (NaN: free), the extra caps on the tangential and lateral acceleration (Inf: none)"
+struct PgSpeedPlan
+    mu_scale::Float64
+    V_max::Float64
+    V_floor::Float64
+    V_start::Float64
+    V_end::Float64
+    ax_max::Float64
+    ax_min::Float64
+    ay_max::Float64
+end
+PgSpeedPlan(; mu_scale=1.0, V_max=30.0, V_floor=1.0, V_start=NaN, V_end=NaN, ax_max=Inf, ax_min=-Inf, ay_max=Inf) =
+    PgSpeedPlan(Float64(mu_scale), Float64(V_max), Float64(V_floor), Float64(V_start), Float64(V_end), Float64(ax_max), Float64(ax_min), Float64(ay_max))
+"pg_speed_plan_stats (48 bytes), one per output trajectory"
+struct PgSpeedPlanStats
+    t_end::Float64
+    v_min::Float64
+    v_max::Float64
+    usage_max::Float64
+    n_cap::Int32
+    n_accel::Int32
+    n_brake::Int32
+    reserved::Int32
+end
+"channels [Lmax, 10, n_path] (column-major: the C layout [n_path][10][Lmax]; t, V, A ignored), L the knot counts, sets the plan sets -> (channels_out [Lmax, 10, n_path * n_sets], stats); output k = path * n_sets + set (0-based).  closed[k]: knot L[k] is knot 1 again; vehicles: nothing (the handle's) or one per set; install = true leaves the handle as pg_set_trajectories with channels_out would"
+function plan_speeds!(mpc::BatchedTrajectoryTrackingMPC, channels::Array{Float64,3}, L::Vector{Int32}, sets::Vector{PgSpeedPlan};
+                      closed::Union{Nothing,Vector{Int32}}=nothing, vehicles::Union{Nothing,Vector{PgVehicle}}=nothing, install::Bool=false)
+    (sizeof(PgSpeedPlan), sizeof(PgSpeedPlanStats)) == (64, 48) || error("PigeonMI355X.jl: PgSpeedPlan / PgSpeedPlanStats differ from include/pigeon_mpc.h")
+    Lmax, ten, n_path = size(channels)
+    ten == 10 && length(L) == n_path || error("plan_speeds!: channels is [Lmax, 10, n_path], L has n_path entries")
+    vehicles === nothing || length(vehicles) == length(sets) || error("plan_speeds!: one vehicle per set")
+    n = n_path * length(sets)
+    out = zeros(Float64, Lmax, 10, n); stats = Vector{PgSpeedPlanStats}(undef, n)
+    check(mpc, ccall(sym(mpc, :pg_plan_speeds), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{PgSpeedPlan}, Ptr{PgVehicle}, Int32, Ptr{Float64}, Ptr{PgSpeedPlanStats}),
+                     mpc.handle, Int32(n_path), Int32(Lmax), L, closed === nothing ? Ptr{Int32}(C_NULL) : closed, channels, Int32(length(sets)), sets,
+                     vehicles === nothing ? Ptr{PgVehicle}(C_NULL) : vehicles, Int32(install), out, stats), "pg_plan_speeds")
+    out, stats
+end
+"{ 1, 30, 1, NaN, NaN, +Inf, -Inf, +Inf } as the library states them (pg_default_speed_plan)"
+default_speed_plan(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_speed_plan), PgSpeedPlan, ())
+
 "mpc.solved = false (src/ros_integration.jl:34,41,147)"
 reset!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_reset), Cint, (Ptr{Cvoid}, Ptr{UInt8}), mpc.handle, C_NULL), "pg_reset")
 

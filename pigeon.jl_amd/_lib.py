@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -169,6 +169,25 @@ HJI_SOLVE_PROTOTYPES = {
 }
 
 
+class pg_speed_plan(C.Structure):
+    """include/pigeon_mpc.h pg_speed_plan: the share of the friction to use, the speed cap and floor, the end speeds of an open path (NaN: free), the extra caps on the
+    tangential (ax_min <= 0 <= ax_max) and lateral acceleration (Inf: none)."""
+    _fields_ = [(n, C.c_double) for n in ["mu_scale", "V_max", "V_floor", "V_start", "V_end", "ax_max", "ax_min", "ay_max"]]
+
+
+class pg_speed_plan_stats(C.Structure):
+    """include/pigeon_mpc.h pg_speed_plan_stats: one per output trajectory."""
+    _fields_ = [("t_end", C.c_double), ("v_min", C.c_double), ("v_max", C.c_double), ("usage_max", C.c_double),
+                ("n_cap", C.c_int32), ("n_accel", C.c_int32), ("n_brake", C.c_int32), ("reserved", C.c_int32)]
+
+
+# speed planner (include/pigeon_mpc.h: pg_plan_speeds)
+SPEED_PLAN_PROTOTYPES = {
+    "pg_plan_speeds": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.POINTER(pg_speed_plan),
+                       C.POINTER(pg_vehicle), C.c_int32, C.POINTER(C.c_double), C.POINTER(pg_speed_plan_stats)],
+}
+
+
 def load_library(precision="f64"):
     """Loads the HIP library of the requested arithmetic type.  PyTorch-ROCm is imported first so that both share ONE HIP runtime in this process."""
     assert precision in ("f64", "f32", "f64-diag")
@@ -190,12 +209,14 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
     lib.pg_default_hji_solve_opts.argtypes = []
     lib.pg_default_hji_solve_opts.restype = pg_hji_solve_opts
+    lib.pg_default_speed_plan.argtypes = []
+    lib.pg_default_speed_plan.restype = pg_speed_plan
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)
     check_layout(lib)
     _libs[precision] = lib

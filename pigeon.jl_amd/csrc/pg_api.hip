@@ -51,6 +51,7 @@ struct pg_handle {
     int pipeline = 1;                                         // pg_set_pipeline: 1 = nodes + update_QP of a large batch with cold instances as one pipelined launch (k_nodes_linearize), 0 = never
     bool pipe_fault = false;                                  // -DPG_DIAG builds only (option "diag_pipe_fault"): fault injection for the pipelined launch (its nodes blocks never publish)
     int lin_groups = 0;                                       // -DPG_DIAG builds only (option "diag_lin_groups"): force the lane arrangement of launch_linearize (1, 2, 4, 8 lanes per interval)
+    int speed_lanes = 0;                                      // option "speed_plan_lanes": sets per wavefront of k_speed_plan (64, 32, 16; 0 = by the size of the call: speed_plan_spw)
     int debug_timeline = 0;                                   // -DPG_DIAG builds only (option "diag_timeline"): pg_debug_solve_cycles records the timeline of the product's kernel
     int lateral_solver = 0;                                   // option "lateral_solver": 0 = by horizon (k_solve_lat beyond 20 intervals or with the polish off), 1 = k_solve_lat, 2 = the embedding in k_solve
     int hji_cell_dims = 3;                                    // option "hji_cell_dims": corners per cell record of the next pg_set_hji_grid = 2^3 (256 B, default), 2^5, 2^7
@@ -588,6 +589,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "hji_cell_dims") return I(&h->hji_cell_dims, 3, 7);
     if (n == "time_grid_naive") return I(&C.time_grid_naive, 0, 1);
     if (n == "tracking_summary") return I(&h->tracking, 0, 1);
+    if (n == "speed_plan_lanes") return I(&h->speed_lanes, 0, 64);
     // k_solve_lat (lateral QP)
     if (n == "lateral_solver") return I(&h->lateral_solver, 0, 2);
     if (n == "lat_split") return I(&h->split_lat, 0, 1);
@@ -663,6 +665,7 @@ int pg_set_option(pg_handle* h, const char* name, double value) {
     if (o.stat) { h->err = std::string("pg_set_option: '") + name + "' is read-only"; return PG_ERR_INVALID; }
     if (!(value >= o.lo && value <= o.hi) || (o.integer && value != (double)(long long)value)) { h->err = std::string("pg_set_option: value out of range for '") + name + "'"; return PG_ERR_INVALID; }
     if (strcmp(name, "hji_cell_dims") == 0 && !(value == 3 || value == 5 || value == 7)) { h->err = "pg_set_option: hji_cell_dims is 3, 5 or 7"; return PG_ERR_INVALID; }
+    if (strcmp(name, "speed_plan_lanes") == 0 && !(value == 0 || value == 16 || value == 32 || value == 64)) { h->err = "pg_set_option: speed_plan_lanes is 0, 16, 32 or 64"; return PG_ERR_INVALID; }
     if (o.i) *o.i = (int)value; else *o.r = (real)value;
     return PG_OK;
 }
@@ -824,6 +827,19 @@ static int response_call(pg_handle* h, const char* who_, const SetLib<Host, Dev>
 }
 extern "C" {
 
+// The handle's view of the library in h->d_traj [n_traj][10][Lmax] / h->d_traj_len (both on the device, owned by the handle), with trajectory.t[end] of every trajectory in
+// fp64: what pg_set_trajectories does after its upload and pg_plan_speeds after its kernels.  Drops the index
+static void adopt_trajectories(pg_handle* h, int n_traj, int Lmax, int L0, std::vector<double>&& t_ends) {
+    h->traj_idx.host.clear();
+    const size_t stride = (size_t)10 * Lmax;
+    h->traj_t_end = t_ends[0];                           // trajectory.t[end] of trajectory 0 (channel 0 = t): the stop of pg_simulate_dev's clock range
+    h->traj_ends = std::move(t_ends); h->tend_dirty = true;      // ... and of every trajectory, fp64 (the window gate of the node callback)
+    TrajView& T = h->dc.traj; T.L = L0;
+    const real* p = h->d_traj; const size_t c = (size_t)Lmax;
+    T.t = p; T.s = p + c; T.V = p + 2 * c; T.A = p + 3 * c; T.E = p + 4 * c; T.N = p + 5 * c; T.psi = p + 6 * c; T.kappa = p + 7 * c; T.edge_L = p + 8 * c; T.edge_R = p + 9 * c;
+    h->dc.n_traj = n_traj; h->dc.traj_stride = (long)stride; h->dc.traj_len = h->d_traj_len; h->dc.traj_idx = nullptr;
+    h->traj_L = L0;
+}
 // install a trajectory library: channels[n_traj][10][Lmax] (t, s, V, A, E, N, psi, kappa, edge_L, edge_R), L[k] valid nodes of trajectory k
 static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_t* L, const double* channels) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -836,14 +852,9 @@ static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_
     { int rc = up(h, h->d_traj, channels, (size_t)n_traj * stride); if (rc) return rc; }
     HIPCHK(h, hipMalloc((void**)&h->d_traj_len, (size_t)n_traj * sizeof(int)));
     HIPCHK(h, hipMemcpy(h->d_traj_len, L, (size_t)n_traj * sizeof(int), hipMemcpyHostToDevice));
-    h->traj_t_end = channels[(size_t)L[0] - 1];          // trajectory.t[end] of trajectory 0 (channel 0 = t): the stop of pg_simulate_dev's clock range
-    h->traj_ends.assign((size_t)n_traj, 0.0); h->tend_dirty = true;      // ... and of every trajectory, fp64 (the window gate of the node callback)
-    for (int k = 0; k < n_traj; k++) h->traj_ends[(size_t)k] = channels[(size_t)k * stride + (size_t)L[k] - 1];
-    TrajView& T = h->dc.traj; T.L = L[0];
-    const real* p = h->d_traj; const size_t c = (size_t)Lmax;
-    T.t = p; T.s = p + c; T.V = p + 2 * c; T.A = p + 3 * c; T.E = p + 4 * c; T.N = p + 5 * c; T.psi = p + 6 * c; T.kappa = p + 7 * c; T.edge_L = p + 8 * c; T.edge_R = p + 9 * c;
-    h->dc.n_traj = n_traj; h->dc.traj_stride = (long)stride; h->dc.traj_len = h->d_traj_len; h->dc.traj_idx = nullptr;
-    h->traj_L = L[0];
+    std::vector<double> ends((size_t)n_traj);
+    for (int k = 0; k < n_traj; k++) ends[(size_t)k] = channels[(size_t)k * stride + (size_t)L[k] - 1];
+    adopt_trajectories(h, n_traj, Lmax, L[0], std::move(ends));
     return PG_OK;
 }
 
@@ -965,6 +976,122 @@ int pg_clear_plant_sets(pg_handle* h) {
 int pg_get_plant_sets(pg_handle* h, int32_t* n_sets, pg_vehicle* out, int32_t max_sets, int32_t* index, int32_t B) {
     if (!h) return PG_ERR_INVALID;
     return setlib_get(h, "pg_get_plant_sets", h->plants, n_sets, out, max_sets, index, B);
+}
+
+// ---- pg_plan_speeds: friction-limited speed profiles of a path library x a plan-set library (pg_speed_plan.hip).  Two launches (copy, plan); no loop on the host ----
+pg_speed_plan pg_default_speed_plan(void) {
+    pg_speed_plan p; p.mu_scale = 1.0; p.V_max = 30.0; p.V_floor = 1.0; p.V_start = NAN; p.V_end = NAN; p.ax_max = INFINITY; p.ax_min = -INFINITY; p.ay_max = INFINITY;
+    return p;
+}
+static const char* speed_plan_problem(const pg_speed_plan& p) {
+    if (!(std::isfinite(p.mu_scale) && p.mu_scale > 0.0)) return "a set needs a finite mu_scale > 0";
+    if (!(std::isfinite(p.V_max) && p.V_max > 0.0)) return "a set needs a finite V_max > 0";
+    if (!(p.V_floor > 0.0 && p.V_floor <= p.V_max)) return "a set needs 0 < V_floor <= V_max";
+    for (double v : {p.V_start, p.V_end}) if (!std::isnan(v) && !(std::isfinite(v) && v >= 0.0)) return "V_start / V_end of a set are NaN (free) or finite and >= 0";
+    if (!(p.ax_min <= 0.0 && p.ax_max >= 0.0)) return "a set needs ax_min <= 0 <= ax_max";
+    if (!(p.ay_max > 0.0)) return "a set needs ay_max > 0";
+    return nullptr;
+}
+// the constants of one (set, vehicle) as the kernel reads them: every product rounded on its own in the library's element type, as the scheme states it
+static void fill_speed_set(SpeedSet& S, const pg_speed_plan& p, const pg_vehicle& v) {
+#pragma clang fp contract(off)
+    const real mu_scale = (real)p.mu_scale, mu = (real)v.mu, G = (real)v.G, V_max = (real)p.V_max, V_floor = (real)p.V_floor;
+    const real mm = mu_scale * mu;
+    S.a_lim = mm * G;
+    const real ay_max = (real)p.ay_max;
+    S.ay = ay_max < S.a_lim ? ay_max : S.a_lim;
+    S.Wmax = V_max * V_max; S.Wfloor = V_floor * V_floor;
+    auto end = [&](double x) -> real { if (std::isnan(x)) return (real)NAN; real e = (real)x; if (V_floor > e) e = V_floor; return e * e; };
+    S.Wstart = end(p.V_start); S.Wend = end(p.V_end);
+    S.ax_max = (real)p.ax_max; S.nax_min = -(real)p.ax_min;
+    S.m = (real)v.m; S.Fx_max = (real)v.Fx_max; S.nFx_min = -(real)v.Fx_min; S.Px_max = (real)v.Px_max;
+    S.Cd0 = (real)v.Cd0; S.Cd1 = (real)v.Cd1; S.Cd2 = (real)v.Cd2; S.pad = real(0.0);
+}
+// sets per wavefront of k_speed_plan: option "speed_plan_lanes" (64, 32, 16), or 0 = the fewest wavefronts that still give every CU one (the passes are latency-bound and
+// a lane's stores are strided: fewer live lanes per wavefront cost nothing while CUs are idle, EXPERIMENTS 27).  The result does not depend on it: a lane owns its trajectory
+static int speed_plan_spw(const pg_handle* h, int n_path, int n_sets) {
+    if (h->speed_lanes) return h->speed_lanes;
+    int spw = 64;
+    while (spw > 16 && (long)n_path * ((n_sets + spw - 1) / spw) < 256) spw /= 2;
+    return spw;
+}
+namespace {
+struct SpeedPlanBufs {                                  // device memory of one call: released on every way out, except what an install hands to the handle
+    real *in = nullptr, *out = nullptr; int *L = nullptr, *i0 = nullptr, *len = nullptr; SpeedSet* sets = nullptr; pg_speed_plan_stats* stats = nullptr;
+    ~SpeedPlanBufs() { for (void* p : {(void*)in, (void*)out, (void*)L, (void*)i0, (void*)len, (void*)sets, (void*)stats}) if (p) (void)hipFree(p); }
+};
+}  // namespace
+int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in, int32_t n_sets,
+                   const pg_speed_plan* sets, const pg_vehicle* vehicles, int32_t install, double* channels_out, pg_speed_plan_stats* stats) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, L && channels_in && sets, "pg_plan_speeds: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && Lmax >= 2, "pg_plan_speeds: need n_path >= 1, n_sets >= 1 and Lmax >= 2");
+    REQUIRE(h, (n_sets + 15) / 16 <= 65535, "pg_plan_speeds: at most 65535 x 16 sets");
+    REQUIRE(h, (double)n_path * (double)n_sets <= 2147483647.0, "pg_plan_speeds: n_path * n_sets must fit 31 bits");
+    const size_t stride = (size_t)10 * Lmax;
+    std::vector<int> i0((size_t)n_path, -1);
+    for (int k = 0; k < n_path; k++) {
+        REQUIRE(h, L[k] >= 2 && L[k] <= Lmax, "pg_plan_speeds: every path needs 2 <= L[k] <= Lmax");
+        const bool cl = closed && closed[k] != 0;
+        REQUIRE(h, !cl || L[k] >= 3, "pg_plan_speeds: a closed path needs >= 3 knots");
+        const double* c = channels_in + (size_t)k * stride;
+        for (int ch = 0; ch < 10; ch++) {
+            if (ch == SP_T || ch == SP_V || ch == SP_A) continue;
+            for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(c[(size_t)ch * Lmax + i]), "pg_plan_speeds: a geometry value of a valid knot is not finite");
+        }
+        const double* s = c + (size_t)SP_S * Lmax; const double* kap = c + (size_t)SP_KAPPA * Lmax;
+        for (int i = 1; i < L[k]; i++) REQUIRE(h, (real)s[i] > (real)s[i - 1], "pg_plan_speeds: s must increase strictly over the valid knots");
+        if (cl) {                                          // i0: the first knot of largest |kappa| among knots 0 .. L-2, as the library's element type holds them
+            int best = 0;
+            for (int i = 1; i < L[k] - 1; i++) if (fabs((real)kap[i]) > fabs((real)kap[best])) best = i;
+            i0[(size_t)k] = best;
+        }
+    }
+    for (int j = 0; j < n_sets; j++) {
+        const char* why = speed_plan_problem(sets[j]); REQUIRE(h, !why, std::string("pg_plan_speeds: ") + (why ? why : ""));
+        if (vehicles) { const char* vw = plant_set_problem(vehicles[j]); REQUIRE(h, !vw, std::string("pg_plan_speeds: the vehicle: ") + (vw ? vw : "")); }
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t n_traj = (size_t)n_path * n_sets, total = n_traj * stride;
+    std::vector<SpeedSet> recs((size_t)n_sets);
+    for (int j = 0; j < n_sets; j++) fill_speed_set(recs[(size_t)j], sets[j], vehicles ? vehicles[j] : h->cfg.vehicle);
+    std::vector<int> lens(n_traj);
+    for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
+    SpeedPlanBufs D;
+    HIPCHK(h, hipMalloc((void**)&D.in, (size_t)n_path * stride * sizeof(real)));
+    HIPCHK(h, hipMalloc((void**)&D.out, total * sizeof(real)));
+    HIPCHK(h, hipMalloc((void**)&D.L, (size_t)n_path * sizeof(int)));
+    HIPCHK(h, hipMalloc((void**)&D.i0, (size_t)n_path * sizeof(int)));
+    HIPCHK(h, hipMalloc((void**)&D.len, n_traj * sizeof(int)));
+    HIPCHK(h, hipMalloc((void**)&D.sets, (size_t)n_sets * sizeof(SpeedSet)));
+    HIPCHK(h, hipMalloc((void**)&D.stats, n_traj * sizeof(pg_speed_plan_stats)));
+    { int rc = up(h, D.in, channels_in, (size_t)n_path * stride); if (rc) return rc; }
+    // (plain copies, as install_trajectories uses: the host vectors are consumed when each returns, on every way out)
+    HIPCHK(h, hipMemcpy(D.L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(D.i0, i0.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(D.len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(D.sets, recs.data(), (size_t)n_sets * sizeof(SpeedSet), hipMemcpyHostToDevice));
+    SpeedPlanArgs A; A.n_path = n_path; A.n_sets = n_sets; A.Lmax = Lmax; A.spw = speed_plan_spw(h, n_path, n_sets); A.L = D.L; A.i0 = D.i0; A.in = D.in; A.sets = D.sets; A.out = D.out; A.stats = D.stats;
+    hipLaunchKernelGGL(k_speed_plan_copy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, A, total);
+    LAUNCH_CHECK(h);
+    const dim3 grid((unsigned)n_path, (unsigned)((n_sets + A.spw - 1) / A.spw));
+    hipLaunchKernelGGL(k_speed_plan, grid, dim3(64), 0, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_speed_plan_stats> st(n_traj);
+    HIPCHK(h, hipMemcpyAsync(st.data(), D.stats, n_traj * sizeof(pg_speed_plan_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the host arrays have been consumed, the kernels have run)
+    { int rc = down(h, channels_out, D.out, total); if (rc) return rc; }
+    if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_speed_plan_stats));
+    if (install) {
+        if (h->d_traj) (void)hipFree(h->d_traj);
+        if (h->d_traj_len) (void)hipFree(h->d_traj_len);
+        h->d_traj = D.out; h->d_traj_len = D.len; D.out = nullptr; D.len = nullptr;
+        std::vector<double> ends(n_traj);
+        for (size_t k = 0; k < n_traj; k++) ends[k] = st[k].t_end;      // (the rounded t of the last knot, as a double: what pg_set_trajectories reads from channels_out)
+        adopt_trajectories(h, (int)n_traj, Lmax, L[0], std::move(ends));
+    }
+    return PG_OK;
 }
 
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no

@@ -12,12 +12,13 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
 
 SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
+SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
 
 
 def is_solved(status):
@@ -152,6 +153,98 @@ class BatchedTrajectoryTrackingMPC:
 
     def set_trajectory_index(self, index):
         self.trajectory_index = self._set_index("trajectory", index)
+
+    # ---- making the speed profile (pg_plan_speeds): every (path, plan set) tube of a path library x a library of plan sets, computed on the device ----
+    _CH_ROWS = [0, 1, 2, 3, 4, 5, 6, 7, 10, 11]                       # t, s, V, A, E, N, psi, kappa, edge_L, edge_R of the 12-channel tube
+
+    @classmethod
+    def pack_speed_plans(cls, sets):
+        """dicts (vehicles.speed_plan(**overrides); missing fields: the defaults) or pg_speed_plan structures -> a ctypes array of pg_speed_plan.  Raises ValueError for
+        a set outside the ranges of include/pigeon_mpc.h (the library refuses the same sets with PG_ERR_INVALID)."""
+        def fill(rec, p):
+            full = _default_speed_plan(**p)
+            for name, _ in _lib.pg_speed_plan._fields_:
+                setattr(rec, name, float(full[name]))
+        arr = cls._pack(_lib.pg_speed_plan, [sets] if isinstance(sets, (dict, _lib.pg_speed_plan)) else sets, fill)
+        if len(arr) < 1:
+            raise ValueError("plan_speeds: at least one plan set")
+        for k, r in enumerate(arr):
+            ok = (math.isfinite(r.mu_scale) and r.mu_scale > 0 and math.isfinite(r.V_max) and r.V_max > 0 and 0 < r.V_floor <= r.V_max
+                  and all(math.isnan(v) or (math.isfinite(v) and v >= 0) for v in (r.V_start, r.V_end)) and r.ax_min <= 0 <= r.ax_max and r.ay_max > 0)
+            if not ok:
+                raise ValueError(f"plan_speeds: set {k} is outside the ranges of pg_speed_plan (mu_scale, V_max > 0 and finite; 0 < V_floor <= V_max; V_start / V_end NaN or "
+                                 "finite and >= 0; ax_min <= 0 <= ax_max; ay_max > 0)")
+        return arr
+
+    @classmethod
+    def pack_paths(cls, paths, closed=None):
+        """TrajectoryTubes (a list, or one) or the channel array [n_path][10][Lmax] with every knot valid -> (L int32 [n_path], channels float64 [n_path][10][Lmax],
+        closed int32 [n_path]).  closed: None (all open), one flag for every path, or one per path.  Raises ValueError for what the library refuses on the path side:
+        fewer than 2 knots (3 on a closed path), s that does not increase strictly, a non-finite geometry value."""
+        if isinstance(paths, np.ndarray):
+            ch = _f64(paths)
+            if ch.ndim != 3 or ch.shape[1] != 10:
+                raise ValueError("plan_speeds: the channel array is [n_path][10][Lmax]")
+            L = np.full(ch.shape[0], ch.shape[2], dtype=np.int32)
+        else:
+            paths = [paths] if isinstance(paths, TrajectoryTube) else list(paths)
+            if not paths:
+                raise ValueError("plan_speeds: at least one path")
+            L = np.array([len(t) for t in paths], dtype=np.int32)
+            ch = np.zeros((len(paths), 10, int(L.max())))
+            for k, t in enumerate(paths):
+                ch[k, :, :len(t)] = t.data[cls._CH_ROWS]
+        cl = np.zeros(len(L), dtype=np.int32)
+        if closed is not None:
+            c = np.atleast_1d(np.asarray(closed)).astype(bool)
+            if c.shape not in ((1,), (len(L),)):
+                raise ValueError(f"plan_speeds: closed has {c.size} entries for {len(L)} paths")
+            cl[:] = c
+        for k in range(len(L)):
+            n = int(L[k])
+            if n < 2 or (cl[k] and n < 3):
+                raise ValueError(f"plan_speeds: path {k} has {n} knots (an open path needs 2, a closed one 3)")
+            geo = ch[k][[1, 4, 5, 6, 7, 8, 9], :n]
+            if not np.isfinite(geo).all():
+                raise ValueError(f"plan_speeds: path {k} has a non-finite geometry value")
+            if not (np.diff(ch[k, 1, :n]) > 0).all():
+                raise ValueError(f"plan_speeds: s of path {k} does not increase strictly")
+        return L, ch, cl
+
+    @classmethod
+    def tubes_from_channels(cls, channels, L, n_sets=1):
+        """channels [n_path * n_sets][10][Lmax] as pg_plan_speeds returns them, L [n_path] -> the TrajectoryTubes in the order k = path * n_sets + set (theta, phi zero,
+        as TrajectoryTube.from_path)."""
+        out = []
+        for k in range(channels.shape[0]):
+            n = int(L[k // n_sets]); c = channels[k, :, :n]
+            out.append(TrajectoryTube(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], np.zeros(n), np.zeros(n), c[8], c[9]))
+        return out
+
+    def plan_speeds(self, paths, sets, vehicles=None, closed=None, install=False):
+        """Friction-limited speed profiles on the device (pg_plan_speeds; the scheme is stated in include/pigeon_mpc.h): paths = TrajectoryTubes or the channel array
+        (their t, V, A are ignored), sets = vehicles.speed_plan(**overrides) dicts, vehicles = None (the handle's) or one vehicle per set, closed = None / one flag /
+        one per path.  Returns (tubes, stats): the n_path * n_sets TrajectoryTubes in the order k = path * n_sets + set, and a structured array with the fields of
+        pg_speed_plan_stats.  install=True makes them the handle's trajectory library (as set_trajectories(tubes) would, without the host round trip; select with
+        set_trajectory_index)."""
+        L, ch, cl = self.pack_paths(paths, closed)
+        arr = self.pack_speed_plans(sets)
+        veh = None
+        if vehicles is not None:
+            veh = self.pack_vehicles([vehicles] if isinstance(vehicles, (dict, _lib.pg_vehicle)) else vehicles)
+            if len(veh) != len(arr):
+                raise ValueError(f"plan_speeds: {len(veh)} vehicles for {len(arr)} sets")
+        n_traj = len(L) * len(arr)
+        out = np.zeros((n_traj, 10, ch.shape[2]))
+        st = (_lib.pg_speed_plan_stats * n_traj)()
+        self._chk(self.lib.pg_plan_speeds(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, veh, int(bool(install)), _p(out), st),
+                  "pg_plan_speeds")
+        tubes = self.tubes_from_channels(out, L, len(arr))
+        if install:
+            self.trajectories = tubes
+            self.trajectory = tubes[0]
+        stats = np.frombuffer(st, dtype=SPEED_PLAN_STATS_DTYPE).copy()
+        return tubes, stats
 
     # ---- the per-instance libraries share one protocol (pg_set_<name>_sets / pg_set_<name>_index / pg_clear_<name>_sets / pg_get_<name>_sets): the four routines below ----
     @staticmethod

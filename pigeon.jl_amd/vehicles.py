@@ -148,3 +148,18 @@ def human(**overrides):
             if len(h[name]) != 2:
                 raise ValueError(f"{name} has {len(h[name])} entries, not one per channel of (omega, a)")
     return h
+
+
+SPEED_PLAN_FIELDS = ("mu_scale", "V_max", "V_floor", "V_start", "V_end", "ax_max", "ax_min", "ay_max")
+
+
+def speed_plan(**overrides):
+    """One plan set for plan_speeds (pg_speed_plan).  speed_plan() is the library's default (pg_default_speed_plan) -- all of the friction, V_max 30, V_floor 1 = the
+    controller's V_min, free end speeds, no extra caps --; speed_plan(mu_scale=0.5, V_max=10.0, V_end=0.0) overrides fields (V_start / V_end: NaN = free, read on an open
+    path only; ax_min <= 0 <= ax_max and ay_max > 0, +-Inf = none).  Build-defined: the reference receives its speed profile from a planner outside its tree."""
+    p = dict(mu_scale=1.0, V_max=30.0, V_floor=1.0, V_start=math.nan, V_end=math.nan, ax_max=math.inf, ax_min=-math.inf, ay_max=math.inf)
+    for k, v in overrides.items():
+        if k not in p:
+            raise KeyError(f"{k} is not a field of a speed plan: {SPEED_PLAN_FIELDS}")
+        p[k] = float(v)
+    return p
