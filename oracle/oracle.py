@@ -201,6 +201,14 @@ class Oracle:
         V = self.L.po_hji_optimal_control(self.h, _d(_arr(state6, 6)), _d(_arr(other4, 4)), _d(u2))
         return float(V), u2
 
+    def hji_optimal_control_detail(self, state6, other4):
+        """(V, (delta_opt, Fx_opt), Bc, scores [50]): hji_optimal_control with the lateral co-state Bc whose sign is the steer sign and the objective of every
+        candidate of the line search (index n is Fx = n/49 Fx_max + (1 - n/49) Fx_min)"""
+        u2 = np.zeros(2); Bc = C.c_double(); sc = np.zeros(50)
+        self.L.po_hji_optimal_control_detail.restype = C.c_double
+        V = self.L.po_hji_optimal_control_detail(self.h, _d(_arr(state6, 6)), _d(_arr(other4, 4)), _d(u2), C.byref(Bc), _d(sc))
+        return float(V), u2, Bc.value, sc
+
     def hji_constraint(self, state6, other4, control3):
         M = np.zeros(2); b = C.c_double(); V = C.c_double()
         self.L.po_hji_constraint(self.h, _d(_arr(state6, 6)), _d(_arr(other4, 4)), _d(_arr(control3, 3)), _d(M), C.byref(b), C.byref(V))

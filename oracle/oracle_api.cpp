@@ -136,6 +136,13 @@ double po_hji_optimal_control(void* hv, const double* state6, const double* othe
     optimal_control(h->mpc.veh, x7, g, u2);
     return V;
 }
+// the same call with what decides it: Bc (its sign is the steer sign) and the objective of the 50 line-search candidates
+double po_hji_optimal_control_detail(void* hv, const double* state6, const double* other4, double* u2, double* Bc, double* scores50) {
+    Handle* h = (Handle*)hv; double x7[7], g[7], V; hji_relative_state(state6, other4, x7);
+    h->mpc.hji.lookup(x7, V, g);
+    optimal_control(h->mpc.veh, x7, g, u2, 50, Bc, scores50);
+    return V;
+}
 void po_hji_constraint(void* hv, const double* state6, const double* other4, const double* control3, double* M2, double* b, double* V) {
     Handle* h = (Handle*)hv; double x7[7]; hji_relative_state(state6, other4, x7);
     double uR[2] = {control3[0], control3[1] + control3[2]};

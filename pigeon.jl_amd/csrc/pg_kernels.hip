@@ -1763,6 +1763,13 @@ __global__ __launch_bounds__(64) void k_hji_constraint(DevCfg C, int B, const re
     o[2] = Hm.v - (M0 * uR0 + M1 * uR1);                                           // :168
 }
 
+// candidate n of optimal_control's line search (:147-148).  The winner is handed out as Fx_opt: the reference's two rounded products and their sum, not a fused
+// multiply-add (one ulp apart for some 0 < n < 49)
+PG_DEV real hji_fx_candidate(const DevVehicle& P, int n) {
+#pragma clang fp contract(off)
+    const real frac = (real)n / real(49.0);
+    return frac * P.Fx_max + (real(1.0) - frac) * P.Fx_min;
+}
 // optimal_control (uMode=:max, N=50) HJI_computation.jl:133-158 at relative state x and gradient g = gradV[0..6]: (delta_opt, Fx_opt).  The line search keeps the FIRST
 // strict maximum of the 50 candidates (NaN never wins), one lane per instance
 PG_DEV void hji_optimal_control(const DevVehicle& P, const real* x, const real* g, real& d_opt_out, real& Fx_opt_out) {
@@ -1775,8 +1782,7 @@ PG_DEV void hji_optimal_control(const DevVehicle& P, const real* x, const real* 
     real V_opt = -INFINITY, Fx_opt = real(0.0);
 #pragma unroll 1
     for (int n = 0; n < 50; n++) {
-        real frac = (real)n / real(49.0);
-        real Fx = frac * P.Fx_max + (real(1.0) - frac) * P.Fx_min;
+        real Fx = hji_fx_candidate(P, n);
         real Fxf = Fx > real(0.0) ? Fx * P.fwd_frac : Fx * P.fwb_frac, Fxr = Fx > real(0.0) ? Fx * P.rwd_frac : Fx * P.rwb_frac;       // longitudinal_tire_forces, no limits (:148)
         real Fyf, Fyr;
         lateral_forces<real>(P, taf, tar, Fxf, Fxr, sd, cd, Fyf, Fyr);

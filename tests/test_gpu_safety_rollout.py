@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import make_oracle
+import hji_live_cases as lc
 import safety_numpy as sn
 
 pytestmark = pytest.mark.gpu
@@ -28,11 +29,42 @@ def _policy_control(X, u2):
     return [u2[0], Fx * (X["fwd_frac"] if Fx > 0 else X["fwb_frac"]), Fx * (X["rwd_frac"] if Fx > 0 else X["rwb_frac"])]
 
 
-@pytest.mark.parametrize("human", ["hold", "worst"])
-def test_rollout_matches_an_oracle_loop(pkg, oracle_mod, skidpad, grid, human):
-    """40 steps x 32 instances against a host loop built from the oracle (exact solver with the safety row, HJI lookup, optimal_control, RK4 plant, the loop's clock) and
-    the numpy other car.  The selection is discontinuous at V = eps and the breach at V = 0: instances whose oracle V comes within 1e-3 of either are left out, and so are
-    instances that either solver did not end at a verified optimum at some step (PG_SOLVED; an unverified interior-point answer is 1e-5-close, not 1e-9-close)."""
+def oracle_loop(pkg, oracle_mod, skidpad, grid, human, state, control, t0, toff, other, steps, eps, margin):
+    """The host loop the rollout is compared with: the oracle's exact solver with the safety row, HJI lookup, optimal_control, RK4 plant and the loop's clock, and the numpy
+    other car.  Returns the histories, the final (q, u, other), the clock, the source of every step's control, keep (instances that stay `margin` away from V = eps and
+    V = 0 and whose solves all end verified), and for the steps the policy drove its steer sign and whether optimal_control was within rounding of another answer
+    (hji_live_cases.is_tie)."""
+    B = state.shape[0]
+    X = pkg.vehicles.X1()                                                    # the vehicle of the handle (mpc.vehicle)
+    orc = make_oracle(oracle_mod, skidpad); orc.set_hji_grid(*grid); orc.set_hji_eps(eps)
+    clock = np.stack([orc.simulate_times(DT, float(skidpad.t[-1]), steps + 1, t_start=float(t0[b])) for b in range(B)], axis=1)
+    q, u, ob, tt = state.copy(), control.copy(), other.copy(), t0.copy()
+    keep = np.ones(B, bool)
+    hist = {k: [] for k in ("state", "control", "other", "V")}
+    src = np.zeros((steps, B), dtype=np.int32)
+    steer = np.zeros((steps, B)); tie = np.zeros((steps, B), bool)
+    for k in range(steps):
+        hist["state"].append(q); hist["control"].append(u); hist["other"].append(ob)
+        unext, _, it, st, _ = orc.step_batch(q, u, tt, others4=ob, time_offsets=toff, solver=0)
+        x7 = np.stack([orc.hji_relative_state(q[b], ob[b]) for b in range(B)])
+        look = [orc.hji_lookup(x7[b]) for b in range(B)]
+        V = np.array([l[0] for l in look]); G = np.stack([l[1] for l in look])
+        hist["V"].append(V)
+        keep &= ~((np.abs(V - eps) < margin) | (np.abs(V) < margin)) & (st == pkg.SOLVED)
+        for b in np.nonzero(V <= eps)[0]:                                    # trajectory mode, policy on
+            _, u2, Bc, scores = orc.hji_optimal_control_detail(q[b], ob[b])
+            unext[b] = _policy_control(X, u2); src[k, b] = 1
+            steer[k, b] = np.sign(u2[0]); tie[k, b] = lc.is_tie(X, G[b], Bc, scores)
+        hu = sn.optimal_disturbance(X, x7, G) if human == "worst" else np.zeros((B, 2))
+        q = np.stack([orc.plant_step(q[b], u[b], DT) for b in range(B)])
+        ob = sn.other_car_step(ob, hu, DT)
+        u = unext; tt = clock[k + 1]
+    un = np.array([orc.u_norm[0], orc.u_norm[1], orc.u_norm[1]])
+    return dict(hist=hist, final=(q, u, ob), clock=clock, src=src, keep=keep, steer=steer, tie=tie, un=un)
+
+
+def _rollout_against_the_oracle_loop(pkg, oracle_mod, skidpad, grid, human, last_step=None):
+    """The body of test_rollout_matches_an_oracle_loop.  last_step(oracle loop) -> the last step index that is compared (None: all steps and the final state)."""
     B, steps, eps, margin = 32, 40, 1.0, 1e-3
     state, control, t0, toff = pkg.synthetic.config2_inputs(skidpad, B, seed=41)
     other = pkg.synthetic.other_cars(state, seed=43)
@@ -46,34 +78,15 @@ def test_rollout_matches_an_oracle_loop(pkg, oracle_mod, skidpad, grid, human):
     s, c, t, o = parts[-1][:4]
     H = {key: np.concatenate([p[4][key] for p in parts]) for key in parts[0][4]}
     dev_st = np.array(dev_st)
-    X = mpc.vehicle
-    orc = make_oracle(oracle_mod, skidpad); orc.set_hji_grid(*grid); orc.set_hji_eps(eps)
-    un = np.array([orc.u_norm[0], orc.u_norm[1], orc.u_norm[1]])
-    clock = np.stack([orc.simulate_times(DT, float(skidpad.t[-1]), steps + 1, t_start=float(t0[b])) for b in range(B)], axis=1)
-    q, u, ob, tt = state.copy(), control.copy(), other.copy(), t0.copy()
-    keep = np.ones(B, bool)
-    hist = {k: [] for k in ("state", "control", "other", "V")}
-    src = np.zeros((steps, B), dtype=np.int32)
-    for k in range(steps):
-        hist["state"].append(q); hist["control"].append(u); hist["other"].append(ob)
-        unext, _, it, st, _ = orc.step_batch(q, u, tt, others4=ob, time_offsets=toff, solver=0)
-        x7 = np.stack([orc.hji_relative_state(q[b], ob[b]) for b in range(B)])
-        look = [orc.hji_lookup(x7[b]) for b in range(B)]
-        V = np.array([l[0] for l in look]); G = np.stack([l[1] for l in look])
-        hist["V"].append(V)
-        keep &= ~((np.abs(V - eps) < margin) | (np.abs(V) < margin)) & (st == pkg.SOLVED)
-        for b in np.nonzero(V <= eps)[0]:                                    # trajectory mode, policy on
-            unext[b] = _policy_control(X, orc.hji_optimal_control(q[b], ob[b])[1]); src[k, b] = 1
-        hu = sn.optimal_disturbance(X, x7, G) if human == "worst" else np.zeros((B, 2))
-        q = np.stack([orc.plant_step(q[b], u[b], DT) for b in range(B)])
-        ob = sn.other_car_step(ob, hu, DT)
-        u = unext; tt = clock[k + 1]
+    L = oracle_loop(pkg, oracle_mod, skidpad, grid, human, state, control, t0, toff, other, steps, eps, margin)
+    hist, (q, u, ob), clock, src, keep, un = L["hist"], L["final"], L["clock"], L["src"], L["keep"], L["un"]
+    last = steps if last_step is None else last_step(L)
     keep &= np.all(dev_st == pkg.SOLVED, axis=0)
     assert keep.sum() >= B * 3 // 4, (keep.sum(), dev_st)
     # per instance, the largest deviation from the oracle loop over all steps (states, other car, V: relative; controls: normalised)
     rel = lambda a, b: np.abs(a - b) / np.maximum(1.0, np.abs(b))
     dev = np.zeros(B)
-    for k in range(steps + 1):
+    for k in range(last + 1):
         if k < steps:
             dq, du = H["state"][k], H["control"][k]; do = H["other"][k]
             Vd, Vo = H["V"][k], hist["V"][k]
@@ -100,6 +113,37 @@ def test_rollout_matches_an_oracle_loop(pkg, oracle_mod, skidpad, grid, human):
         assert np.any(H["human"] != 0.0)
     else:
         assert np.all(H["human"] == 0.0)
+    return H, L, keep, last
+
+
+@pytest.mark.parametrize("human", ["hold", "worst"])
+def test_rollout_matches_an_oracle_loop(pkg, oracle_mod, skidpad, grid, human):
+    """40 steps x 32 instances against a host loop built from the oracle (exact solver with the safety row, HJI lookup, optimal_control, RK4 plant, the loop's clock) and
+    the numpy other car.  The selection is discontinuous at V = eps and the breach at V = 0: instances whose oracle V comes within 1e-3 of either are left out, and so are
+    instances that either solver did not end at a verified optimum at some step (PG_SOLVED; an unverified interior-point answer is 1e-5-close, not 1e-9-close)."""
+    _rollout_against_the_oracle_loop(pkg, oracle_mod, skidpad, grid, human)
+
+
+def live_last_step(L):
+    """The last step of the live-grid rollout that is compared: the first one at which the policy drives an instance whose optimal_control is within rounding of another
+    answer (the tie set of test_gpu_hji_live.test_fallback_policy_on_the_live_grid: a bang-bang steer that flips there sends the two loops apart for good); all of them when
+    there is none.  It must not come before step 3."""
+    hit = np.nonzero((L["tie"] & (L["src"] == 1)).any(axis=1))[0]
+    last = int(hit[0]) if len(hit) else L["src"].shape[0]
+    assert last >= 3, last
+    return last
+
+
+def test_rollout_matches_an_oracle_loop_on_the_live_grid(pkg, oracle_mod, skidpad):
+    """The same comparison, same batch, steps and bars, worst-case human, on hji_live_cases.live_grid: dV/dUy and dV/dr are live, so the policy's steer takes both signs
+    (one instance changes sign on the way, at the same step on both sides); the human's optimal_disturbance sees a gradient that depends on every coordinate.  Compared
+    up to live_last_step (here: every step, no policy-driven step of the oracle loop is in the tie set)."""
+    H, L, keep, last = _rollout_against_the_oracle_loop(pkg, oracle_mod, skidpad, lc.live_grid(), "worst", last_step=live_last_step)
+    # the steer the policy handed over at step k is the control at the start of step k + 1
+    drove = (H["source"][:last - 1] == 1) & keep[None]
+    steer = H["control"][1:last][..., 0][drove]
+    assert np.sum(steer > 0) >= 3 and np.sum(steer < 0) >= 3, (np.sum(steer > 0), np.sum(steer < 0))
+    assert np.array_equal(np.sign(steer), L["steer"][:last - 1][drove])
 
 
 def test_reduces_to_the_existing_loop_bit_for_bit(pkg, skidpad):
