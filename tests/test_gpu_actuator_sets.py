@@ -16,6 +16,7 @@ import pytest
 
 import actuator_numpy
 import plant_numpy
+from rollout_libs import inputs, join, make, rel, rollout, same, start
 
 pytestmark = pytest.mark.gpu
 
@@ -29,15 +30,7 @@ SETS = actuator_numpy.six_sets()
 IDX = (np.arange(B) % 6).astype(np.int32)
 PURE = np.array([actuator_numpy.is_pure_delay(s) for s in SETS])
 DTYPE = {"f64": np.float64, "f32": np.float32}
-
-
-def rel(got, ref):
-    return np.abs(np.asarray(got) - np.asarray(ref)) / np.maximum(1.0, np.abs(ref))
-
-
-def same_bits(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+KEYS = ("state", "control", "command", "applied", "final_state", "final_control")          # what two runs are compared on
 
 
 def law_bar(commands, precision):
@@ -70,41 +63,11 @@ def law_shares(sets, idx, c):
     return slew, lag
 
 
-def make(pkg, traj, cap=B, formulation="coupled", precision="f64", **kw):
-    return pkg.BatchedTrajectoryTrackingMPC(traj, cap, formulation=formulation, precision=precision, **kw)
-
-
-def start(pkg, m, traj, n=B, others=False):
-    state, control, t0, toff = pkg.synthetic.config2_inputs(traj, n, seed=SEED)
-    m.set_inputs(state, control, t0, pkg.synthetic.other_cars(state) if others else None, toff)
-    return state, control, t0, toff
-
-
-def rollout(m, kind, steps):
-    """dict: state [steps][B][6], control [steps][B][3] (the control record), final (state), final_control, and under a library command / applied [steps][B][3]"""
-    if kind == "simulate":
-        out = m.simulate_(steps, DT, record=True)
-        r = dict(state=out[3], control=out[4], final=out[0], final_control=out[1])
-        if isinstance(out[-1], dict):
-            r.update(out[-1])
-        return r
-    out = m.simulate_safety_(steps, DT, use_HJI_policy=False, record=True)
-    r = dict(state=out[4]["state"], control=out[4]["control"], final=out[0], final_control=out[1])
-    r.update({k: out[4][k] for k in ("command", "applied") if k in out[4]})
-    return r
-
-
-def join(parts):
-    r = {k: np.concatenate([p[k] for p in parts]) for k in parts[0] if k not in ("final", "final_control")}
-    r["final"] = parts[-1]["final"]; r["final_control"] = parts[-1]["final_control"]
-    return r
-
-
 def check_law(applied, commands, precision, sets=SETS, idx=IDX, what=""):
     """applied == twin(commands): bit for bit where the set only delays, within the bar elsewhere; returns the worst difference in units of eps x max |command|"""
     want = actuator_numpy.actuator_response(sets, idx, commands, DT, DTYPE[precision])
     pure = np.array([actuator_numpy.is_pure_delay(s) for s in sets])[idx]
-    assert same_bits(applied[:, pure], want[:, pure]), what
+    assert same(applied[:, pure], want[:, pure]), what
     fin = np.where(np.isfinite(commands), commands, 0.0)
     unit = law_bar(fin, precision) / UNITS
     with np.errstate(invalid="ignore"):
@@ -121,8 +84,8 @@ def test_the_law_equals_the_twin(pkg, skidpad, precision):
     slew, lag = law_shares(SETS, idx, c)
     print(f"command sequence: slew limit of set 4 binds on {slew:.0%} of its steps, lag of set 3 apart from its input by > 100 bars on {lag:.0%}")
     assert slew >= 0.25 and lag >= 0.5
-    m = make(pkg, skidpad, precision=precision)
-    start(pkg, m, skidpad)
+    m = make(pkg, skidpad, B, precision=precision)
+    start(m, inputs(pkg, skidpad, B))
     m.set_actuators(SETS, idx)
     got = m.actuator_response(c, DT)
     c_real = c.astype(DTYPE[precision]).astype(np.float64)
@@ -133,7 +96,7 @@ def test_the_law_equals_the_twin(pkg, skidpad, precision):
     m.set_actuators(SETS[5])
     one = m.actuator_response(c, DT)
     check_law(one, c_real, precision, [SETS[5]], np.zeros(B, dtype=int), what="library of one")
-    assert same_bits(m.actuator_state(), start(pkg, m, skidpad)[1].astype(DTYPE[precision]))
+    assert same(m.actuator_state(), start(m, inputs(pkg, skidpad, B))[1].astype(DTYPE[precision]))
     m.close()
 
 
@@ -141,12 +104,12 @@ def test_the_law_equals_the_twin(pkg, skidpad, precision):
 def check_replay(r, precision, plants, what):
     """2 (a): applied = twin(command); 2 (b): every step replays through the numpy plant with the APPLIED control; 2 (c): ... and not with the command"""
     check_law(r["applied"], r["command"], precision, what=what)
-    assert same_bits(r["control"], r["applied"]), what           # the control record under a library is the applied control
+    assert same(r["control"], r["applied"]), what           # the control record under a library is the applied control
     bar = BAR[precision]
     steps = r["state"].shape[0]
     worst = 0.0; apart = np.zeros(r["state"].shape[1])
     for k in range(steps):
-        nxt = r["state"][k + 1] if k + 1 < steps else r["final"]
+        nxt = r["state"][k + 1] if k + 1 < steps else r["final_state"]
         pred = plant_numpy.plant_step_vec(plants, r["state"][k], r["applied"][k], DT)
         err = rel(nxt, pred)
         worst = max(worst, float(err.max()))
@@ -158,15 +121,15 @@ def check_replay(r, precision, plants, what):
 @pytest.mark.parametrize("kind,formulation,precision", [("simulate", "coupled", "f64"), ("simulate", "decoupled", "f64"), ("safety", "coupled", "f64"),
                                                         ("simulate", "coupled", "f32"), ("safety", "coupled", "f32")])
 def test_every_step_replays_with_the_applied_control(pkg, skidpad, kind, formulation, precision):
-    m = make(pkg, skidpad, formulation=formulation, precision=precision)
+    m = make(pkg, skidpad, B, formulation=formulation, precision=precision)
     m.set_actuators(SETS, IDX)
-    start(pkg, m, skidpad, others=kind == "safety")
+    start(m, inputs(pkg, skidpad, B), others=kind == "safety")
     # 20 steps in one call, then four calls of one step: behind each of those the control the step computed can be read back (2 (d))
-    parts = [rollout(m, kind, STEPS - 4)]
+    parts = [rollout(m, kind, STEPS - 4, DT)]
     computed = []
     for _ in range(4):
         computed.append(m.get_next_control())
-        parts.append(rollout(m, kind, 1))
+        parts.append(rollout(m, kind, 1, DT))
     computed.append(m.get_next_control())
     r = join(parts)
     what = f"{kind} {formulation}"
@@ -178,20 +141,20 @@ def test_every_step_replays_with_the_applied_control(pkg, skidpad, kind, formula
     # (d) the command of the next step is the control the step computed; the last one is the handle's control now
     real = DTYPE[precision]
     for i in range(4):
-        assert same_bits(r["command"][STEPS - 4 + i], computed[i].astype(real)), i
-    assert same_bits(r["final_control"], computed[4].astype(real))
-    assert same_bits(m.actuator_state(), r["applied"][-1])
+        assert same(r["command"][STEPS - 4 + i], computed[i].astype(real)), i
+    assert same(r["final_control"], computed[4].astype(real))
+    assert same(m.actuator_state(), r["applied"][-1])
     assert m.get_option("stat_actuator_steps") == STEPS
     m.close()
 
 
 # ---- 3: identity = no library, bit for bit -------------------------------------------------------------------------------------------------------------------------------
 def histories(pkg, traj, kind, sets, idx, formulation="coupled", steps=STEPS):
-    m = make(pkg, traj, formulation=formulation)
+    m = make(pkg, traj, B, formulation=formulation)
     if sets is not None:
         m.set_actuators(sets, idx)
-    start(pkg, m, traj, others=kind == "safety")
-    r = rollout(m, kind, steps)
+    start(m, inputs(pkg, traj, B), others=kind == "safety")
+    r = rollout(m, kind, steps, DT)
     m.close()
     return r
 
@@ -199,17 +162,17 @@ def histories(pkg, traj, kind, sets, idx, formulation="coupled", steps=STEPS):
 @pytest.mark.parametrize("kind,formulation", [("simulate", "coupled"), ("simulate", "decoupled"), ("safety", "coupled")])
 def test_the_identity_set_equals_no_library_bit_for_bit(pkg, skidpad, kind, formulation):
     none = histories(pkg, skidpad, kind, None, None, formulation)
-    assert "applied" not in none
+    assert none["applied"] is None
     for fb in (0, 1):
         one = histories(pkg, skidpad, kind, [actuator_numpy.identity(feedback=fb)], None, formulation)
-        for k in ("state", "control", "final", "final_control"):
-            assert same_bits(none[k], one[k]), (kind, formulation, fb, k)
-        assert same_bits(one["applied"], one["command"]) and same_bits(one["applied"], none["control"])
+        for k in ("state", "control", "final_state", "final_control"):
+            assert same(none[k], one[k]), (kind, formulation, fb, k)
+        assert same(one["applied"], one["command"]) and same(one["applied"], none["control"])
     mixed = histories(pkg, skidpad, kind, SETS, IDX, formulation)
     sel = IDX == 0
     for k in ("state", "control"):
-        assert same_bits(none[k][:, sel], mixed[k][:, sel]), (kind, formulation, k)
-    assert same_bits(none["final"][sel], mixed["final"][sel]) and same_bits(none["final_control"][sel], mixed["final_control"][sel])
+        assert same(none[k][:, sel], mixed[k][:, sel]), (kind, formulation, k)
+    assert same(none["final_state"][sel], mixed["final_state"][sel]) and same(none["final_control"][sel], mixed["final_control"][sel])
 
 
 def test_mixed_library_equals_libraries_of_one_bit_for_bit(pkg, skidpad):
@@ -219,26 +182,26 @@ def test_mixed_library_equals_libraries_of_one_bit_for_bit(pkg, skidpad):
         one = histories(pkg, skidpad, "simulate", [SETS[j]], None)
         sel = IDX == j
         for k in ("state", "control", "command", "applied"):
-            assert same_bits(mixed[k][:, sel], one[k][:, sel]), (j, k)
-        assert same_bits(mixed["final"][sel], one["final"][sel]), j
+            assert same(mixed[k][:, sel], one[k][:, sel]), (j, k)
+        assert same(mixed["final_state"][sel], one["final_state"][sel]), j
         if j == 0:
-            base = one["final"]
+            base = one["final_state"]
         else:
-            assert np.max(np.abs(one["final"] - base)) > 1e-5, j          # the sets are not cosmetic
+            assert np.max(np.abs(one["final_state"] - base)) > 1e-5, j          # the sets are not cosmetic
 
 
 # ---- 4: what the controller sees -----------------------------------------------------------------------------------------------------------------------------------------
 def test_the_controller_sees_the_command_or_the_position(pkg, skidpad):
-    m = make(pkg, skidpad)
+    m = make(pkg, skidpad, B)
     m.set_actuators(SETS, IDX)
-    start(pkg, m, skidpad)
-    r = rollout(m, "simulate", STEPS)
+    start(m, inputs(pkg, skidpad, B))
+    r = rollout(m, "simulate", STEPS, DT)
     fb = np.array([s["feedback"] for s in SETS])[IDX] == 1
     seen = np.where(fb[:, None], r["applied"][-1], r["command"][-1])
     un = m.u_normalization
     want = np.stack([seen[:, 0] / un[0], (seen[:, 1] + seen[:, 2]) / un[1]], axis=1)
     u_curr = m.qp_data()[:, -5:-3]
-    assert same_bits(u_curr, want)
+    assert same(u_curr, want)
     gap = np.max(np.abs(r["applied"][-1] - r["command"][-1])[fb], axis=1)
     print(f"feedback = 1 set at the last step: |applied - command| between {gap.min():.2e} and {gap.max():.2e}")
     assert np.all(gap > 1e-6)
@@ -248,32 +211,32 @@ def test_the_controller_sees_the_command_or_the_position(pkg, skidpad):
 # ---- 5: continuation and restart -----------------------------------------------------------------------------------------------------------------------------------------
 def test_continuation_and_restart(pkg, skidpad):
     whole = histories(pkg, skidpad, "simulate", SETS, IDX)
-    m = make(pkg, skidpad)
+    m = make(pkg, skidpad, B)
     m.set_actuators(SETS, IDX)
-    start(pkg, m, skidpad)
-    split = join([rollout(m, "simulate", 10), rollout(m, "simulate", 14)])
-    for k in whole:
-        assert same_bits(whole[k], split[k]), k                  # ring and position continue across calls
-    m.reset(); start(pkg, m, skidpad)                            # the clock restarts: the same 24 steps again
-    assert same_bits(m.actuator_state(), split["command"][0])
-    again = rollout(m, "simulate", STEPS)
-    for k in whole:
-        assert same_bits(whole[k], again[k]), k
+    start(m, inputs(pkg, skidpad, B))
+    split = join([rollout(m, "simulate", 10, DT), rollout(m, "simulate", 14, DT)])
+    for k in KEYS:
+        assert same(whole[k], split[k]), k                  # ring and position continue across calls
+    m.reset(); start(m, inputs(pkg, skidpad, B))                            # the clock restarts: the same 24 steps again
+    assert same(m.actuator_state(), split["command"][0])
+    again = rollout(m, "simulate", STEPS, DT)
+    for k in KEYS:
+        assert same(whole[k], again[k]), k
     # a new index between two calls resets nothing: instances that keep their set stay bit-identical, the others change from the next step on
     idx2 = np.where(np.arange(B) % 7 == 3, (IDX + 1) % 6, IDX).astype(np.int32)
-    m.reset(); start(pkg, m, skidpad)
-    first = rollout(m, "simulate", 10)
+    m.reset(); start(m, inputs(pkg, skidpad, B))
+    first = rollout(m, "simulate", 10, DT)
     m.set_actuator_index(idx2)
-    swapped = join([first, rollout(m, "simulate", 14)])
+    swapped = join([first, rollout(m, "simulate", 14, DT)])
     keep = idx2 == IDX
     for k in ("state", "control", "command", "applied"):
-        assert same_bits(swapped[k][:, keep], whole[k][:, keep]), k
-        assert same_bits(swapped[k][:10], whole[k][:10]), k
-    assert not same_bits(swapped["applied"][10:, ~keep], whole["applied"][10:, ~keep])
+        assert same(swapped[k][:, keep], whole[k][:, keep]), k
+        assert same(swapped[k][:10], whole[k][:10]), k
+    assert not same(swapped["applied"][10:, ~keep], whole["applied"][10:, ~keep])
     # ... an instance whose delay grew reads commands that were already in the ring: the twin over the whole command history with the new sets from step 10 on
     grew = np.flatnonzero((IDX == 0) & (idx2 == 1))              # identity -> delay 3
     assert grew.size >= 1
-    assert same_bits(swapped["applied"][10:, grew], swapped["command"][7:21, grew])
+    assert same(swapped["applied"][10:, grew], swapped["command"][7:21, grew])
     m.close()
 
 
@@ -282,15 +245,15 @@ def test_composition_with_plants_sensors_tunings_and_the_summary(pkg, skidpad):
     import sensor_numpy
     plants = plant_numpy.four_plants(pkg.X1)
     pidx = (np.arange(B) % 4).astype(np.int32)
-    m = make(pkg, skidpad)
+    m = make(pkg, skidpad, B)
     cp = pkg.CoupledControlParams()
     m.set_control_params([cp, dict(cp, Q_e=2.0, R_ddelta=0.2)], ((np.arange(B) // 2) % 2).astype(np.int32))
     m.set_plants(plants, pidx)
     m.set_sensors(sensor_numpy.four_sensors(), ((np.arange(B) // 3) % 4).astype(np.int32), seed=7)
     m.set_actuators(SETS, IDX)
     m.set_option("tracking_summary", 1)
-    start(pkg, m, skidpad)
-    r = rollout(m, "simulate", STEPS)
+    start(m, inputs(pkg, skidpad, B))
+    r = rollout(m, "simulate", STEPS, DT)
     own = plant_numpy.stack_vehicles([plants[i] for i in pidx], B)
     worst, apart = check_replay(r, "f64", own, "composition")
     share = float(np.mean(apart[IDX != 0] > 100 * BAR["f64"]))
@@ -306,13 +269,13 @@ def test_large_batch_takes_the_pipelined_launch_under_a_library(pkg, skidpad):
     n, steps = 2341, 3
     idx = (np.arange(n) % 6).astype(np.int32)
     m = make(pkg, skidpad, n, options={"pipe_min": 2341})
-    start(pkg, m, skidpad, n)
+    start(m, inputs(pkg, skidpad, n))
     m.set_actuators(SETS, idx)
-    r = rollout(m, "simulate", steps)
+    r = rollout(m, "simulate", steps, DT)
     assert m.get_option("stat_pipelined_launches") >= 1 and m.get_option("stat_actuator_steps") == steps
     check_law(r["applied"], r["command"], "f64", idx=idx, what="B = 2341")
     for k in range(steps):
-        nxt = r["state"][k + 1] if k + 1 < steps else r["final"]
+        nxt = r["state"][k + 1] if k + 1 < steps else r["final_state"]
         assert rel(nxt, plant_numpy.plant_step_vec(pkg.X1(), r["state"][k], r["applied"][k], DT)).max() < BAR["f64"], k
     m.close()
 
@@ -323,11 +286,11 @@ def test_contract(pkg, skidpad):
     from pigeon_jl_amd import _lib
     cap = 80
     m = make(pkg, skidpad, cap)
-    start(pkg, m, skidpad, others=True)
+    start(m, inputs(pkg, skidpad, B), others=True)
     # a handle that never installed a library: the launch counter stays at zero, the state call returns the control, the histories are refused
-    none = rollout(m, "simulate", 3)
+    none = rollout(m, "simulate", 3, DT)
     assert m.get_option("stat_actuator_steps") == 0 and m.get_actuators()[0] == []
-    assert same_bits(m.actuator_state(), none["final_control"])
+    assert same(m.actuator_state(), none["final_control"])
     buf = torch.full((2, B, 3), -7.0, dtype=torch.float64, device=f"cuda:{m.cfg.device}")
     assert m.lib.pg_set_applied_history_dev(m.h, C.c_void_p(buf.data_ptr()), 2) == -4 and m.lib.pg_set_command_history_dev(m.h, C.c_void_p(buf.data_ptr()), 2) == -4
     with pytest.raises(pkg.PigeonError):
@@ -387,7 +350,7 @@ def test_contract(pkg, skidpad):
     assert all(np.array_equal(a, b) for a, b in zip(u0, u1))
     plain.close()
     # a rollout call that FAILS consumes the one-shot histories: the successful call behind it writes nothing to those buffers
-    start(pkg, m, skidpad, others=True)
+    start(m, inputs(pkg, skidpad, B), others=True)
     m.set_actuators(SETS)                                        # (installing a library drops the index)
     assert np.all(m.get_actuators()[1] == -1)
     cbuf = torch.full((2, B, 3), -7.0, dtype=torch.float64, device=f"cuda:{m.cfg.device}")
@@ -399,10 +362,10 @@ def test_contract(pkg, skidpad):
     assert m.get_option("stat_actuator_steps") == 2
     m.clear_actuators()
     assert m.get_actuators()[0] == []
-    m.reset(); start(pkg, m, skidpad, others=True)
-    again = rollout(m, "simulate", 3)                            # the no-library bits are back, and the counter stands
-    for k in none:
-        assert same_bits(none[k], again[k]), k
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
+    again = rollout(m, "simulate", 3, DT)                            # the no-library bits are back, and the counter stands
+    for k in KEYS:
+        assert same(none[k], again[k]), k
     assert m.get_option("stat_actuator_steps") == 2
     m.simulate_node_(2, DT); m.node_step_()                      # ... and the node callback runs again
     m.close()

@@ -19,6 +19,7 @@ import pytest
 
 import disturbance_numpy as dn
 import plant_numpy
+from rollout_libs import check_summary, inputs, join, make, numpy_summary, rel, rollout, start
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +32,8 @@ B = 70
 STEPS = 12
 SETS = dn.four_disturbances()
 IDX = (np.arange(B) % 4).astype(np.int32)
+KEYS = ("state", "control", "disturbance", "final_state")          # what two runs are compared on
 OUTSIDE = dn.identity(Fx=-3000.0, Fy=4000.0, Mz=500.0, sigma_Fx=100.0, sigma_Fy=900.0, x_cp=1.0, tau_gust=0.2, mu_scale=0.3, step_on=1000, step_off=2000)
-
-
-def rel(got, ref):
-    return np.abs(np.asarray(got) - np.asarray(ref)) / np.maximum(1.0, np.abs(ref))
 
 
 def active(sets, idx, step0, steps):
@@ -67,41 +65,6 @@ def replay_share_on_the_starts(pkg, traj):
     return float(np.mean(far[live])), per_set, float(np.mean(far_rel[live]))
 
 
-def make(pkg, traj, cap=B, formulation="coupled", precision="f64", **kw):
-    return pkg.BatchedTrajectoryTrackingMPC(traj, cap, formulation=formulation, precision=precision, **kw)
-
-
-def start(pkg, m, traj, n=B, others=False):
-    state, control, t0, toff = pkg.synthetic.config2_inputs(traj, n, seed=SEED)
-    m.set_inputs(state, control, t0, pkg.synthetic.other_cars(state) if others else None, toff)
-    return state, control, t0, toff
-
-
-def rollout(m, kind, steps):
-    """dict: state [steps][B][6], control [steps][B][3] (what the plant integrated), final (state) and, under a library, disturbance [steps][B][4]"""
-    if kind == "simulate":
-        out = m.simulate_(steps, DT, record=True)
-        r = dict(state=out[3], control=out[4], final=out[0])
-        if isinstance(out[-1], dict):
-            r.update({k: v for k, v in out[-1].items() if k == "disturbance"})
-        return r
-    if kind == "safety":
-        out = m.simulate_safety_(steps, DT, use_HJI_policy=False, record=True)
-        h = out[4]; r = dict(state=h["state"], control=h["control"], final=out[0])
-    else:
-        out = m.simulate_node_(steps, DT, record=True)
-        h = out[5]; r = dict(state=h["state"], control=h["applied"], final=out[0])
-    if "disturbance" in h:
-        r["disturbance"] = h["disturbance"]
-    return r
-
-
-def join(parts):
-    r = {k: np.concatenate([p[k] for p in parts]) for k in parts[0] if k != "final"}
-    r["final"] = parts[-1]["final"]
-    return r
-
-
 def check_law(got, precision, sets, idx, streams, step0, what, seed=GUST_SEED):
     """got [steps][B][4] against the twin from a fresh state at step0: within steps x DRAW_BAR, and bit-equal to (0, 0, 0, 1) outside the window"""
     steps = got.shape[0]
@@ -118,8 +81,8 @@ def check_law(got, precision, sets, idx, streams, step0, what, seed=GUST_SEED):
 # ---- 1: the law, no controller ------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_the_law_equals_the_twin(pkg, skidpad, precision):
-    m = make(pkg, skidpad, precision=precision)
-    start(pkg, m, skidpad)
+    m = make(pkg, skidpad, B, precision=precision)
+    start(m, inputs(pkg, skidpad, B))
     m.set_disturbances(SETS, IDX, seed=GUST_SEED)
     check_law(m.disturbance_response(0, 40, DT), precision, SETS, IDX, np.arange(B), 0, "pg_disturbance_response")
     check_law(m.disturbance_response(7, 40, DT), precision, SETS, IDX, np.arange(B), 7, "pg_disturbance_response")
@@ -139,7 +102,7 @@ def check_replay(r, precision, plants, sets, idx, what, step0=0):
     worst = 0.0; apart = np.zeros((steps, n), dtype=bool)
     ident = np.tile(dn.IDENTITY_W, (n, 1))
     for k in range(steps):
-        nxt = r["state"][k + 1] if k + 1 < steps else r["final"]
+        nxt = r["state"][k + 1] if k + 1 < steps else r["final_state"]
         pred = dn.plant_step_vec_dist(plants, r["state"][k], r["control"][k], r["disturbance"][k], DT)
         err = rel(nxt, pred)
         worst = max(worst, float(err.max()))
@@ -152,10 +115,10 @@ def check_replay(r, precision, plants, sets, idx, what, step0=0):
 @pytest.mark.parametrize("kind,formulation,precision", [("simulate", "coupled", "f64"), ("simulate", "decoupled", "f64"), ("safety", "coupled", "f64"), ("node", "coupled", "f64"),
                                                         ("node", "decoupled", "f64"), ("simulate", "coupled", "f32"), ("safety", "coupled", "f32"), ("node", "coupled", "f32")])
 def test_every_step_replays_through_the_disturbed_numpy_plant(pkg, skidpad, kind, formulation, precision):
-    m = make(pkg, skidpad, formulation=formulation, precision=precision)
+    m = make(pkg, skidpad, B, formulation=formulation, precision=precision)
     m.set_disturbances(SETS, IDX, seed=GUST_SEED)
-    start(pkg, m, skidpad, others=kind != "simulate")
-    r = rollout(m, kind, STEPS)
+    start(m, inputs(pkg, skidpad, B), others=kind != "simulate")
+    r = rollout(m, kind, STEPS, DT)
     what = f"{kind} {formulation}"
     check_law(r["disturbance"], precision, SETS, IDX, np.arange(B), 0, what + " record")
     worst, share = check_replay(r, precision, pkg.X1(), SETS, IDX, what)
@@ -172,8 +135,8 @@ def histories(pkg, traj, kind, sets, idx, n=256, steps=8, precision="f64", **kw)
     m = make(pkg, traj, n, precision=precision, **kw)
     if sets is not None:
         m.set_disturbances(sets, idx, seed=GUST_SEED)
-    start(pkg, m, traj, n, others=kind != "simulate")
-    r = rollout(m, kind, steps)
+    start(m, inputs(pkg, traj, n), others=kind != "simulate")
+    r = rollout(m, kind, steps, DT)
     r["stat"] = m.get_option("stat_disturbance_steps"); r["pipelined"] = m.get_option("stat_pipelined_launches")
     m.close()
     return r
@@ -181,9 +144,9 @@ def histories(pkg, traj, kind, sets, idx, n=256, steps=8, precision="f64", **kw)
 
 @pytest.mark.parametrize("kind", ["simulate", "safety", "node"])
 def test_the_identity_set_and_a_closed_window_equal_no_library(pkg, skidpad, kind):
-    keys = ("state", "control", "final")
+    keys = ("state", "control", "final_state")
     none = histories(pkg, skidpad, kind, None, None)
-    assert none["stat"] == 0 and "disturbance" not in none
+    assert none["stat"] == 0 and none["disturbance"] is None
     for name, s in (("identity", dn.identity()), ("closed window", OUTSIDE)):
         one = histories(pkg, skidpad, kind, [s], None)
         assert one["stat"] == 8
@@ -207,17 +170,17 @@ def test_mixed_library_equals_libraries_of_one_bit_for_bit(pkg, skidpad):
         sel = idx == j
         for k in ("state", "control", "disturbance"):
             assert np.array_equal(mixed[k][:, sel], one[k][:, sel]), (j, k)
-        assert np.array_equal(mixed["final"][sel], one["final"][sel]), j
+        assert np.array_equal(mixed["final_state"][sel], one["final_state"][sel]), j
         if j == 0:
-            base = one["final"]
+            base = one["final_state"]
         else:
-            assert np.max(np.abs(one["final"] - base)) > 1e-5, j          # the sets are not cosmetic
+            assert np.max(np.abs(one["final_state"] - base)) > 1e-5, j          # the sets are not cosmetic
 
 
 # ---- 5: the controller does not see it -------------------------------------------------------------------------------------------------------------------------------------
 def test_the_controller_does_not_see_the_disturbance(pkg, skidpad):
     state, control, t0, toff = pkg.synthetic.config2_inputs(skidpad, B, seed=SEED)
-    plain = make(pkg, skidpad); lib = make(pkg, skidpad)
+    plain = make(pkg, skidpad, B); lib = make(pkg, skidpad, B)
     lib.set_disturbances(SETS)                               # four sets and NO index: pg_step does not care
     u0, st0, it0 = plain.step_(state, control, t0, time_offset=toff)
     u1, st1, it1 = lib.step_(state, control, t0, time_offset=toff)
@@ -226,19 +189,19 @@ def test_the_controller_does_not_see_the_disturbance(pkg, skidpad):
     assert all(np.array_equal(a, b) for a, b in zip(plain.nodes(), lib.nodes()))
     assert lib.get_option("stat_disturbance_steps") == 0
     # in a rollout: the nodes and the QP of step 0 are those of the handle without a library (the headwind set is active there); the states part company one step after a set's window opens
-    fresh = make(pkg, skidpad); roll = make(pkg, skidpad)
+    fresh = make(pkg, skidpad, B); roll = make(pkg, skidpad, B)
     roll.set_disturbances(SETS, IDX, seed=GUST_SEED)
     for m in (fresh, roll):
         m.set_inputs(state, control, t0, None, toff)
-    f0 = rollout(fresh, "simulate", 1); r0 = rollout(roll, "simulate", 1)
+    f0 = rollout(fresh, "simulate", 1, DT); r0 = rollout(roll, "simulate", 1, DT)
     assert np.array_equal(fresh.qp_data(), roll.qp_data()) and all(np.array_equal(a, b) for a, b in zip(fresh.nodes(), roll.nodes()))
     assert np.any(r0["disturbance"][0, IDX == 3, 0] != 0.0)
-    f = join([f0, rollout(fresh, "simulate", STEPS - 1)]); r = join([r0, rollout(roll, "simulate", STEPS - 1)])
+    f = join([f0, rollout(fresh, "simulate", STEPS - 1, DT)]); r = join([r0, rollout(roll, "simulate", STEPS - 1, DT)])
     for j in range(4):
         sel = IDX == j
         on = SETS[j]["step_on"]
         if j == 0:
-            assert np.array_equal(f["state"][:, sel], r["state"][:, sel]) and np.array_equal(f["final"][sel], r["final"][sel])
+            assert np.array_equal(f["state"][:, sel], r["state"][:, sel]) and np.array_equal(f["final_state"][sel], r["final_state"][sel])
             continue
         assert np.array_equal(f["state"][:on + 1, sel], r["state"][:on + 1, sel]) and np.array_equal(f["control"][:on + 1, sel], r["control"][:on + 1, sel]), j
         assert np.all(np.any(f["state"][on + 1, sel] != r["state"][on + 1, sel], axis=1)), j
@@ -249,24 +212,24 @@ def test_the_controller_does_not_see_the_disturbance(pkg, skidpad):
 # ---- 6: determinism --------------------------------------------------------------------------------------------------------------------------------------------------------
 def test_determinism(pkg, skidpad):
     streams = (1000 + np.arange(B)).astype(np.uint64)
-    m = make(pkg, skidpad)
-    start(pkg, m, skidpad)
+    m = make(pkg, skidpad, B)
+    start(m, inputs(pkg, skidpad, B))
     m.set_disturbances(SETS, IDX, seed=GUST_SEED, streams=streams)
     w70 = m.disturbance_response(0, STEPS, DT)
     check_law(w70, "f64", SETS, IDX, streams, 0, "streams 1000 + b")
     # (a) a function of the stream id, not of b or B
     pick = np.array([1, 2, 3, 13, 34, 67, 69])
     small = make(pkg, skidpad, 7)
-    start(pkg, small, skidpad, 7)
+    start(small, inputs(pkg, skidpad, 7))
     small.set_disturbances(SETS, IDX[pick], seed=GUST_SEED, streams=streams[pick])
     assert np.array_equal(small.disturbance_response(0, STEPS, DT), w70[:, pick])
     small.close()
     # (b) 6 + 6 steps in two calls are 12 in one; (c) set_inputs replays them
-    whole = rollout(m, "simulate", STEPS)
+    whole = rollout(m, "simulate", STEPS, DT)
     assert np.array_equal(whole["disturbance"], w70)
-    m.reset(); start(pkg, m, skidpad)
-    split = join([rollout(m, "simulate", 6), rollout(m, "simulate", 6)])
-    for k in whole:
+    m.reset(); start(m, inputs(pkg, skidpad, B))
+    split = join([rollout(m, "simulate", 6, DT), rollout(m, "simulate", 6, DT)])
+    for k in KEYS:
         assert np.array_equal(whole[k], split[k]), k
     assert m.get_option("stat_disturbance_steps") == 2 * STEPS
     # (d) another seed: w changes wherever a sigma is positive and the window open, and nowhere else
@@ -285,14 +248,13 @@ def test_composition_with_plants_sensors_actuators_tunings_and_the_summary(pkg, 
     import actuator_numpy
     import sensor_numpy
     from conftest import make_oracle
-    from test_gpu_plant_sets import numpy_summary, check_summary
     plants = plant_numpy.four_plants(pkg.X1)
     pidx = ((np.arange(B) // 4) % 4).astype(np.int32)           # every (plant, disturbance) pair occurs
     asets = actuator_numpy.six_sets()
     orc = make_oracle(oracle_mod, skidpad)
 
     def run(disturbed):
-        m = make(pkg, skidpad)
+        m = make(pkg, skidpad, B)
         cp = pkg.CoupledControlParams()
         m.set_control_params([cp, dict(cp, Q_e=2.0, R_ddelta=0.2)], ((np.arange(B) // 2) % 2).astype(np.int32))
         m.set_plants(plants, pidx)
@@ -301,8 +263,8 @@ def test_composition_with_plants_sensors_actuators_tunings_and_the_summary(pkg, 
         if disturbed:
             m.set_disturbances(SETS, IDX, seed=GUST_SEED)
         m.set_option("tracking_summary", 1)
-        start(pkg, m, skidpad)
-        r = rollout(m, "simulate", STEPS)
+        start(m, inputs(pkg, skidpad, B))
+        r = rollout(m, "simulate", STEPS, DT)
         got = m.tracking_summary()
         stats = [m.get_option(f"stat_{n}_steps") for n in ("disturbance", "actuator", "sensor")]
         m.close()
@@ -314,8 +276,8 @@ def test_composition_with_plants_sensors_actuators_tunings_and_the_summary(pkg, 
     worst, share = check_replay(r, "f64", own, SETS, IDX, "composition")      # (the control record under an actuator library is the applied control)
     print(f"composition: worst |state - disturbed numpy plant of the instance's own set (applied control)| = {worst:.2e}; undisturbed replay apart on {share:.0%}")
     assert share >= 0.5
-    want, _ = numpy_summary([orc], np.zeros(B, dtype=int), r["state"])
-    check_summary(got, want, BAR["f64"], B)
+    want, _, _ = numpy_summary([orc], None, r["state"])
+    check_summary(got, want, BAR["f64"])
     r0, got0, stats0 = run(False)
     assert stats0[0] == 0
     slick = IDX == 2
@@ -329,8 +291,8 @@ def test_contract(pkg, skidpad):
     import torch
     cap = 80
     m = make(pkg, skidpad, cap)
-    start(pkg, m, skidpad, others=True)
-    none = rollout(m, "simulate", 3)
+    start(m, inputs(pkg, skidpad, B), others=True)
+    none = rollout(m, "simulate", 3, DT)
     assert m.get_option("stat_disturbance_steps") == 0 and m.disturbances()[0] == []
     buf = torch.full((2, B, 4), -7.0, dtype=torch.float64, device=f"cuda:{m.cfg.device}")
     assert m.lib.pg_set_disturbance_history_dev(m.h, C.c_void_p(buf.data_ptr()), 2) == -4          # no library
@@ -387,7 +349,7 @@ def test_contract(pkg, skidpad):
     m.node_step_()
     assert m.get_option("stat_disturbance_steps") == 0
     # a rollout call that FAILS consumes the one-shot history: the successful call behind it writes nothing to that buffer
-    m.reset(); start(pkg, m, skidpad, others=True)
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
     m.set_disturbances(SETS, seed=GUST_SEED)                     # (installing a library drops the index)
     assert np.all(m.disturbances()[1] == -1)
     assert m.lib.pg_set_disturbance_history_dev(m.h, C.c_void_p(buf.data_ptr()), 2) == 0
@@ -400,9 +362,9 @@ def test_contract(pkg, skidpad):
     # clearing: the launches and the bits of before; seed and streams persist across it
     m.clear_disturbances()
     assert m.disturbances()[0] == []
-    m.reset(); start(pkg, m, skidpad, others=True)
-    again = rollout(m, "simulate", 3)
-    for k in none:
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
+    again = rollout(m, "simulate", 3, DT)
+    for k in KEYS:
         assert np.array_equal(none[k], again[k]), k
     assert m.get_option("stat_disturbance_steps") == 2
     arr = m.pack_disturbances(SETS)

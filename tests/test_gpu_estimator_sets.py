@@ -16,8 +16,8 @@ import estimator_numpy as en
 import node_numpy as nn
 import plant_numpy
 import sensor_numpy
-import test_gpu_sensor_sets as gs
 from conftest import make_oracle
+from rollout_libs import NOISE_SEED, inputs, join, make, narrowed, numpy_summary, rel, rollout, start, stream_ids
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +25,8 @@ BAR = {"f64": 1e-9, "f32": 2e-5}
 DT = 0.01
 SETS = en.four_estimators()
 SENSORS = sensor_numpy.four_sensors()
-NOISE_SEED = gs.NOISE_SEED
 KINDS = [("simulate", "coupled"), ("simulate", "decoupled"), ("safety", "coupled"), ("node", "coupled"), ("node", "decoupled")]
 DTYPE = {"f64": np.float64, "f32": np.float32}
-make, inputs, start, rel, stream_ids = gs.make, gs.inputs, gs.start, gs.rel, gs.stream_ids
-
-
-def rollout(m, kind, steps, measured=False, estimated=True, **kw):
-    """dict(state [steps][B][6], control = the control the plant integrates [steps][B][3], final [B][6], measured / estimated [steps][B][6] or None)"""
-    if kind == "simulate":
-        out = m.simulate_(steps, DT, record=True, measured=measured, estimated=estimated)
-        r = dict(state=out[3], control=out[4], final=out[0]); tail = out[5:]
-    elif kind == "safety":
-        out = m.simulate_safety_(steps, DT, use_HJI_policy=False, record=True, measured=measured, estimated=estimated)
-        r = dict(state=out[4]["state"], control=out[4]["control"], final=out[0]); tail = out[5:]
-    else:
-        out = m.simulate_node_(steps, DT, record=True, measured=measured, estimated=estimated, **kw)
-        r = dict(state=out[5]["state"], control=out[5]["applied"], final=out[0], event=out[5]["event"]); tail = out[6:]
-    tail = [x for x in tail if not isinstance(x, dict)]
-    r["measured"] = tail.pop(0) if measured else None
-    r["estimated"] = tail.pop(0) if estimated else None
-    assert not tail
-    return r
-
-
-def join(a, b):
-    return {k: (b[k] if k == "final" else None if a[k] is None else np.concatenate([a[k], b[k]])) for k in a}
 
 
 def check_estimates(r, precision, idx, P, what="", moved_min=0.9):
@@ -81,7 +57,7 @@ def test_the_response_equals_the_twin(pkg, skidpad, precision):
     B, steps = 70, 12
     idx = (np.arange(B) % 4).astype(np.int32)
     m = make(pkg, skidpad, B, precision=precision)
-    st = start(pkg, m, skidpad, B)
+    st = start(m, inputs(pkg, skidpad, B))
     m.set_estimators(SETS, idx)
     P = pkg.X1()
     x = np.empty((steps, B, 6)); x[0] = st[0]
@@ -117,23 +93,23 @@ def filtered_run(pkg, traj, kind, formulation, precision, sensor=True):
         B = 70
         idx = (np.arange(B) % 4).astype(np.int32)
         m = make(pkg, traj, B, formulation, precision)
-        st = start(pkg, m, traj, B, others=kind != "simulate")
+        st = start(m, inputs(pkg, traj, B), others=kind != "simulate")
         if sensor:
             m.set_sensors([SENSORS[1]], None, seed=NOISE_SEED, streams=stream_ids(B))
         m.set_estimators(SETS, idx)
-        a = rollout(m, kind, 5, measured=sensor)
+        a = rollout(m, kind, 5, DT, measured=sensor, estimated=True)
         last5 = m.estimated_state()
-        b = rollout(m, kind, 7, measured=sensor)
-        r = join(a, b)
+        b = rollout(m, kind, 7, DT, measured=sensor, estimated=True)
+        r = join([a, b])
         r.update(idx=idx, last5=last5, last=m.estimated_state(), est_steps=m.get_option("stat_estimator_steps"), clock=m.simulate_clock(12, st[2], DT), inputs=st)
         m.close()
         # the same twelve steps in one call
         m = make(pkg, traj, B, formulation, precision)
-        start(pkg, m, traj, B, others=kind != "simulate")
+        start(m, inputs(pkg, traj, B), others=kind != "simulate")
         if sensor:
             m.set_sensors([SENSORS[1]], None, seed=NOISE_SEED, streams=stream_ids(B))
         m.set_estimators(SETS, idx)
-        r["whole"] = rollout(m, kind, 12, measured=sensor)
+        r["whole"] = rollout(m, kind, 12, DT, measured=sensor, estimated=True)
         m.close()
         _runs[key] = r
     return _runs[key]
@@ -147,7 +123,7 @@ def test_the_estimate_is_one_twin_step_from_the_histories(pkg, skidpad, kind, fo
     # (node rollout: the applied command of the history is the message the compute calls read -- k_node_finish writes both, and leaves both alone for a gated-out instance)
     check_estimates(r, precision, r["idx"], pkg.X1(), f"{kind} {formulation}")
     assert np.array_equal(r["last5"], r["estimated"][4]) and np.array_equal(r["last"], r["estimated"][11])      # pg_get_estimated_state: the last row of each call
-    for k in ("state", "control", "final", "measured", "estimated"):
+    for k in ("state", "control", "final_state", "measured", "estimated"):
         assert np.array_equal(r[k], r["whole"][k]), k         # 5 + 7 = 12, bit for bit
 
 
@@ -169,7 +145,7 @@ def test_the_plant_moves_the_true_state(pkg, skidpad, kind, formulation, precisi
     qh, uh, eh = r["state"], r["control"], r["estimated"]
     worst = 0.0; apart = np.zeros(70)
     for k in range(12):
-        nxt = qh[k + 1] if k + 1 < 12 else r["final"]
+        nxt = qh[k + 1] if k + 1 < 12 else r["final_state"]
         err = rel(nxt, plant_numpy.plant_step_vec(P, qh[k], uh[k], DT))
         worst = max(worst, float(err.max()))
         assert err.max() < bar, (kind, formulation, precision, k, int(np.argmax(err.max(axis=1))), float(err.max()))
@@ -213,7 +189,7 @@ def histories(pkg, traj, kind, precision, est, others, B=256, steps=8):
     idx = (np.arange(B) % 4).astype(np.int32)
     m = make(pkg, traj, B, precision=precision)
     m.set_option("tracking_summary", 1)
-    start(pkg, m, traj, B, others=kind != "simulate")
+    start(m, inputs(pkg, traj, B), others=kind != "simulate")
     if others:
         m.set_sensors(SENSORS, idx, seed=NOISE_SEED, streams=stream_ids(B))
         m.set_disturbances(disturbance_numpy.four_disturbances(), idx, seed=NOISE_SEED + 1)
@@ -222,8 +198,8 @@ def histories(pkg, traj, kind, precision, est, others, B=256, steps=8):
             m.set_actuators(acts, (np.arange(B) % len(acts)).astype(np.int32))
     if est is not None:
         m.set_estimators(est, None)
-    r = rollout(m, kind, steps, measured=others, estimated=est is not None)
-    out = [r["state"], r["control"], r["final"]] + [np.asarray(x) for x in m.solve_info()[:3]] + [np.asarray(x) for x in m.tracking_summary()]
+    r = rollout(m, kind, steps, DT, measured=others, estimated=est is not None)
+    out = [r["state"], r["control"], r["final_state"]] + [np.asarray(x) for x in m.solve_info()[:3]] + [np.asarray(x) for x in m.tracking_summary()]
     if others:
         out.append(r["measured"])
     if kind != "simulate":
@@ -261,17 +237,17 @@ def test_the_summaries_describe_the_truth(pkg, oracle_mod, skidpad, kind, precis
     bar = BAR[precision]
     idx = (np.arange(B) % 4).astype(np.int32)
     pidx = ((np.arange(B) // 4) % 4).astype(np.int32)
-    tube = gs.narrowed(pkg, skidpad)
+    tube = narrowed(pkg, skidpad)
     orc = make_oracle(oracle_mod, tube if precision == "f64" else pkg.TrajectoryTube(*tube.data.astype(np.float32).astype(np.float64)))
     m = make(pkg, tube, B, precision=precision)
     m.set_option("tracking_summary", 1)
-    start(pkg, m, tube, B, others=kind != "simulate")
+    start(m, inputs(pkg, tube, B), others=kind != "simulate")
     m.set_plants(plant_numpy.four_plants(pkg.X1), pidx)
     m.set_estimators(SETS, idx)
-    a = rollout(m, kind, 5); b = rollout(m, kind, 7)
-    r = join(a, b)
+    a = rollout(m, kind, 5, DT, estimated=True); b = rollout(m, kind, 7, DT, estimated=True)
+    r = join([a, b])
     sm, n, fx = m.tracking_summary()
-    (wsm, wn, wfx, margin), _, _ = gs.numpy_summary(orc, r["state"])
+    (wsm, wn, wfx, margin), _, _ = numpy_summary([orc], None, r["state"])
     assert np.array_equal(n, wn) and np.all(n == steps)
     err = rel(sm, wsm)
     print(f"{kind} {precision}: tracking summary vs numpy on the TRUE history: {err.max():.2e} (bar {bar:g})")
@@ -279,7 +255,7 @@ def test_the_summaries_describe_the_truth(pkg, oracle_mod, skidpad, kind, precis
     decided = margin > 1e-6
     assert np.mean(~decided) <= 1 / 8 and np.array_equal(fx[decided], wfx[decided])
     # the estimate really left the truth: the low-pass set (gain 0.5, no model) trails the car by v dt (1 - g) / g, a decimetre at 10 m/s
-    (msm, _, _, _), ms, me = gs.numpy_summary(orc, r["estimated"])
+    (msm, _, _, _), ms, me = numpy_summary([orc], None, r["estimated"])
     off = rel(sm, msm).max(axis=1)
     lag = np.linalg.norm(r["estimated"][-1, :, :2] - r["state"][-1, :, :2], axis=1)
     print(f"{kind} {precision}: the summary of the ESTIMATED history is off by > 100 bars on {np.mean(off[idx == 2] > 100 * bar):.0%} of the low-pass instances; "
@@ -313,11 +289,11 @@ def test_the_gates_read_the_estimate(pkg, skidpad):
         m.set_sensors(biased, sidx, seed=NOISE_SEED)
         if lib:
             m.set_estimators(est, eidx)
-        first = rollout(m, "node", 1, measured=True, estimated=lib)
+        first = rollout(m, "node", 1, DT, measured=True, estimated=lib)
         assert first["measured"][0, slow, 3] < 1.0 and first["event"][0, slow] == nn.LOW_SPEED
         m.set_sensors([SENSORS[0]], None, seed=NOISE_SEED)
         x0 = [np.asarray(a)[slow].copy() for a in list(m.solution()) + list(m.solve_info())]
-        r = rollout(m, "node", steps, measured=True, estimated=lib)
+        r = rollout(m, "node", steps, DT, measured=True, estimated=lib)
         assert np.all(r["measured"][:, slow, 3] >= 1.0) and np.all(r["state"][:, slow, 3] >= 1.0)
         if lib:
             assert np.all(r["estimated"][:, slow, 3] < 1.0) and np.all(r["estimated"][:, slow, 3] > 0.9)
@@ -340,10 +316,10 @@ def test_the_observer_filters_in_the_closed_loop(pkg, skidpad):
     B, steps = 70, 200
     idx = (np.arange(B) % 2 == 0).astype(np.int32)            # set 1 for even b, set 0 (the identity) for odd b
     m = make(pkg, skidpad, B)
-    start(pkg, m, skidpad, B)
+    start(m, inputs(pkg, skidpad, B))
     m.set_sensors([SENSORS[1]], None, seed=NOISE_SEED, streams=stream_ids(B))
     m.set_estimators([SETS[0], SETS[1]], idx)
-    r = rollout(m, "simulate", steps, measured=True)
+    r = rollout(m, "simulate", steps, DT, measured=True, estimated=True)
     m.close()
     x, y, xh = r["state"][50:], r["measured"][50:], r["estimated"][50:]
     rms = lambda a, sel: np.sqrt(np.mean(a[:, sel] ** 2, axis=(0, 1)))
@@ -364,7 +340,7 @@ def test_contract(pkg, skidpad):
 
     def fresh():
         m = make(pkg, skidpad, cap)
-        start(pkg, m, skidpad, B, others=True)
+        start(m, inputs(pkg, skidpad, B), others=True)
         return m
     m = fresh()
     with pytest.raises(pkg.PigeonError):
@@ -420,7 +396,7 @@ def test_contract(pkg, skidpad):
     m.simulate_(2, DT); m.synchronize()
     assert bool((buf == -7.0).all()) and m.get_option("stat_estimator_steps") == 2
     assert m.estimated_state().shape == (B, 6)
-    m.reset(); start(pkg, m, skidpad, B, others=True)
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
     with pytest.raises(pkg.PigeonError):
         m.estimated_state()                                  # forgotten with the inputs
     m.clear_estimators()
@@ -462,22 +438,22 @@ def test_installing_resets_nothing_and_clearing_restarts_the_estimate(pkg, skidp
 
     def run(between):
         m = make(pkg, skidpad, B)
-        st = start(pkg, m, skidpad, B)
+        st = start(m, inputs(pkg, skidpad, B))
         m.set_sensors([SENSORS[1]], None, seed=NOISE_SEED, streams=stream_ids(B))
         m.set_estimators(SETS, idx)
-        rollout(m, "simulate", 4, measured=True)
+        rollout(m, "simulate", 4, DT, measured=True, estimated=True)
         if between == "restore":
             m.set_estimators([SETS[3]], None); m.set_estimators(SETS, idx)
         elif between == "clear":
             m.clear_estimators(); m.set_estimators(SETS, idx)
-        r = rollout(m, "simulate", 4, measured=True)
+        r = rollout(m, "simulate", 4, DT, measured=True, estimated=True)
         r["t"] = m.simulate_(1, DT)[2]
         clock = m.simulate_clock(10, st[2], DT)
         m.close()
         return r, clock
     twin, clock = run(None)
     back, _ = run("restore")
-    for k in ("state", "control", "final", "measured", "estimated", "t"):
+    for k in ("state", "control", "final_state", "measured", "estimated", "t"):
         assert np.array_equal(twin[k], back[k]), k
     assert np.array_equal(twin["t"], clock[9])               # nine steps of ONE clock
     assert not np.array_equal(twin["estimated"][0, idx != 0], twin["measured"][0, idx != 0])      # the fifth step filters on
@@ -493,10 +469,10 @@ def test_large_batch_takes_the_pipelined_launch_under_a_library(pkg, skidpad):
     idx = (np.arange(B) % 4).astype(np.int32)
     ids = stream_ids(B)
     m = make(pkg, skidpad, B, options={"pipe_min": 2341})
-    start(pkg, m, skidpad, B)
+    start(m, inputs(pkg, skidpad, B))
     m.set_sensors([SENSORS[1]], None, seed=NOISE_SEED, streams=ids)
     m.set_estimators(SETS, idx)
-    r = rollout(m, "simulate", steps, measured=True)
+    r = rollout(m, "simulate", steps, DT, measured=True, estimated=True)
     assert m.get_option("stat_pipelined_launches") >= 1 and m.get_option("stat_estimator_steps") == steps
     check_estimates(r, "f64", idx, pkg.X1(), "B = 2341")
     assert np.array_equal(m.estimated_state(), r["estimated"][-1])

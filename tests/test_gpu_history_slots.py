@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import rollout_libs as rl
-from test_gpu_human_sets import grid  # noqa: F401  (the fixture: the grid of the human library's tests)
+from rollout_libs import grid  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,8 +26,8 @@ def records(m, buf):
 
 
 def started(pkg, skidpad, grid, library=None):
-    m = rl.make(pkg, skidpad, grid)
-    m.set_inputs(*rl.inputs(pkg, skidpad))
+    m = rl.make_small(pkg, skidpad, grid)
+    m.set_inputs(*rl.small_inputs(pkg, skidpad))
     if library:
         rl.install(m, library)
     return m
@@ -50,13 +50,13 @@ def test_what_a_history_setter_refuses_and_what_clears_its_slot(pkg, skidpad, gr
     # a null buffer: PG_OK, and a pending registration is gone
     assert rl.register(m, setter, buf, 3) == rl.OK
     assert rl.register(m, setter, None, 3) == rl.OK
-    assert rl.rollout(m, library) == rl.OK
+    assert rl.rollout_status(m, library) == rl.OK
     assert np.all(records(m, buf) == SENTINEL)
     # pg_clear_*_sets drops a pending registration
     assert rl.register(m, setter, buf, 3) == rl.OK
     rl.clear(m, library)
     rl.install(m, library)
-    assert rl.rollout(m, library) == rl.OK
+    assert rl.rollout_status(m, library) == rl.OK
     assert np.all(records(m, buf) == SENTINEL)
     m.close()
 
@@ -68,17 +68,17 @@ def test_a_registration_serves_the_next_rollout_call_and_no_step_beyond_it(pkg, 
     buf = sentinel_buffer(m, width)
     # 2 steps registered, 3 run: records 0 and 1 are written, record 2 is not
     assert rl.register(m, setter, buf, 2) == rl.OK
-    assert rl.rollout(m, library, 3) == rl.OK
+    assert rl.rollout_status(m, library, 3) == rl.OK
     first = records(m, buf)
     assert np.all(np.isfinite(first[:2])) and not np.any(first[:2] == SENTINEL)
     assert np.all(first[2] == SENTINEL)
     # one-shot: a second rollout without registering again writes nothing
-    assert rl.rollout(m, library, 3) == rl.OK
+    assert rl.rollout_status(m, library, 3) == rl.OK
     assert records(m, buf).tobytes() == first.tobytes()
     # a rollout call that fails its argument check (dt = 0) has consumed the registration all the same
     fresh = sentinel_buffer(m, width)
     assert rl.register(m, setter, fresh, 3) == rl.OK
-    assert rl.rollout(m, library, 3, dt=0.0) == rl.INVALID
-    assert rl.rollout(m, library, 3) == rl.OK
+    assert rl.rollout_status(m, library, 3, dt=0.0) == rl.INVALID
+    assert rl.rollout_status(m, library, 3) == rl.OK
     assert np.all(records(m, fresh) == SENTINEL)
     m.close()

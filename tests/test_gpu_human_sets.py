@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 
 import human_numpy as hn
+import rollout_libs as rl
 import safety_numpy as sn
+from rollout_libs import grid  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,82 +31,27 @@ SETS = hn.four_humans()
 IDX = (np.arange(B) % 4).astype(np.int32)
 MIXED = [hn.identity(0), hn.identity(1), hn.identity(2)]
 MODE_NAME = ("hold", "worst", "script")
-
-
-def rel(got, ref):
-    return np.abs(np.asarray(got) - np.asarray(ref)) / np.maximum(1.0, np.abs(ref))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    """two device results, bit for bit (-0.0 is not 0.0, a NaN equals itself)"""
-    a = np.asarray(a); b = np.asarray(b)
-    return a.shape == b.shape and (np.array_equal(bits(a), bits(b)) if a.dtype.kind == "f" else np.array_equal(a, b))
-
-
-def stream_ids(n):
-    b = np.arange(n, dtype=np.uint64)
-    return b * np.uint64(0x100000001) + np.uint64(7) + (b % np.uint64(3)) * np.uint64(1 << 40)
-
-
-@pytest.fixture(scope="module")
-def grid(pkg):
-    return pkg.synthetic.hji_grid(dims=(7, 6, 5, 4, 4, 5, 4), seed=11)
+RUN = dict(use_HJI_policy=True, summary=True)          # of every rollout here but the decoupled one: the policy on, the safety summary read
 
 
 @pytest.fixture(scope="module")
 def inputs(pkg, skidpad):
     """state, control, t0, toff, other of the 96 instances and the script [STEPS][B][2]"""
-    state, control, t0, toff = pkg.synthetic.config2_inputs(skidpad, B, seed=SEED)
-    other = pkg.synthetic.other_cars(state, seed=OTHER_SEED)
     rng = np.random.default_rng(3)
     script = np.stack([rng.uniform(-0.5, 0.5, (STEPS, B)), rng.uniform(-3.0, 3.0, (STEPS, B))], axis=2)
-    return state, control, t0, toff, other, script
-
-
-def make(pkg, traj, grid, cap=B, formulation="coupled", precision="f64", **kw):
-    m = pkg.BatchedTrajectoryTrackingMPC(traj, cap, formulation=formulation, precision=precision, hji_eps=1.0, **kw)
-    if grid is not None:
-        m.set_hji_cache(*grid)
-    return m
-
-
-def start(m, inp, n=B):
-    state, control, t0, toff, other, _ = inp
-    m.set_inputs(state[:n], control[:n], t0[:n], other[:n], toff[:n])
-
-
-def rollout(m, kind, steps, human="hold", script=None, policy=True):
-    """every history and the state after the call: a dict of arrays"""
-    if kind == "safety":
-        out = m.simulate_safety_(steps, DT, use_HJI_policy=policy, human=human, human_u=script, record=True)
-        r = dict(out[4]); r.update(f_state=out[0], f_control=out[1], f_t=out[2], f_other=out[3])
-    else:
-        out = m.simulate_node_(steps, DT, use_HJI_policy=policy, human=human, human_u=script, record=True)
-        r = dict(out[5]); r.update(f_state=out[0], f_control=out[1], f_t=out[2], f_other=out[3], f_applied=out[4])
-    vmin, fb, ps = m.safety_summary()
-    r.update(f_vmin=vmin, f_breach=fb, f_policy=ps)
-    return r
-
-
-def join(parts):
-    r = {k: (np.concatenate([p[k] for p in parts]) if not k.startswith("f_") else parts[-1][k]) for k in parts[0]}
-    return r
+    return rl.inputs(pkg, skidpad, B, SEED, OTHER_SEED) + (script,)
 
 
 def assert_same_run(a, b, what, cols=None, skip=("human_u",)):
     """two runs, every history and final state bit for bit (cols: the instances compared, as (columns of a, columns of b))"""
-    keys = [k for k in a if k not in skip]
-    assert sorted(keys) == sorted(k for k in b if k not in skip), (what, sorted(a), sorted(b))
+    keys = [k for k in a if k not in skip and a[k] is not None]
+    assert keys == [k for k in b if k not in skip and b[k] is not None], (what, keys)          # both runs produced the same records
     for k in keys:
         x, y = np.asarray(a[k]), np.asarray(b[k])
         if cols is not None:
-            ax = 0 if k.startswith("f_") else 1
+            ax = 1 if k in rl.RECORDS else 0
             x = np.take(x, cols[0], axis=ax); y = np.take(y, cols[1], axis=ax)
-        assert same(x, y), (what, k)
+        assert rl.same(x, y), (what, k)
 
 
 def other_libraries(pkg, m, kind):
@@ -150,16 +97,16 @@ def check_law(pkg, got, precision, sets, idx, streams, step0, x7, vg8, script, w
     for j in range(steps):
         for b in np.nonzero(lanes)[0]:
             if held[j, b]:
-                assert same(got[j, b], got[decided[j, b] - step0, b]), (what, "held", j, b)
+                assert rl.same(got[j, b], got[decided[j, b] - step0, b]), (what, "held", j, b)
                 count["held"] += 1
                 continue
             for c in range(2):
                 h = int(how[j, b, c])
                 count[h] += 1
                 if h == hn.EXACT:
-                    assert same(got[j, b, c], want[j, b, c]), (what, "copy", j, b, c, got[j, b, c], want[j, b, c])
+                    assert rl.same(got[j, b, c], want[j, b, c]), (what, "copy", j, b, c, got[j, b, c], want[j, b, c])
                 else:
-                    worst[h] = max(worst[h], float(rel(got[j, b, c], want[j, b, c])))
+                    worst[h] = max(worst[h], float(rl.rel(got[j, b, c], want[j, b, c])))
     bar3 = steps * DRAW_BAR[precision]
     print(f"{what} {precision}: {count[hn.EXACT]} copies and {count['held']} held steps bit for bit; mode 1 arithmetic ({count[hn.FROM_WORST]} values) worst "
           f"{worst[hn.FROM_WORST]:.3g} (bar {WORST_BAR:.3g}); mode 3 arithmetic ({count[hn.FROM_RANDOM]} values) worst {worst[hn.FROM_RANDOM]:.3g} (bar {bar3:.3g})")
@@ -171,8 +118,8 @@ def check_law(pkg, got, precision, sets, idx, streams, step0, x7, vg8, script, w
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_the_response_equals_the_twin(pkg, skidpad, grid, inputs, precision):
     state, control, t0, toff, other, script = inputs
-    m = make(pkg, skidpad, grid, precision=precision)
-    start(m, inputs)
+    m = rl.make(pkg, skidpad, B, grid=grid, precision=precision)
+    rl.start(m, inputs, others=True)
     # the other car drives on at its speed while the ego stands: twelve different relative states per instance
     others = [other]
     for _ in range(STEPS - 1):
@@ -183,10 +130,10 @@ def test_the_response_equals_the_twin(pkg, skidpad, grid, inputs, precision):
     live = int(np.count_nonzero(np.any(w0 != 0.0, axis=1)))
     print(f"worst case non-zero at step 0 on {live} of {B} instances")
     assert live >= B // 2
-    m.set_humans(SETS, IDX, seed=DRIVER_SEED, streams=stream_ids(B))
+    m.set_humans(SETS, IDX, seed=DRIVER_SEED, streams=rl.stream_ids(B))
     for step0 in (0, 4):
         got = m.human_response(step0, x7, vg8, DT, script)
-        count = check_law(pkg, got, precision, SETS, IDX, stream_ids(B), step0, x7, vg8, script, f"pg_human_response from step {step0}")
+        count = check_law(pkg, got, precision, SETS, IDX, rl.stream_ids(B), step0, x7, vg8, script, f"pg_human_response from step {step0}")
         assert count[hn.FROM_WORST] > 0 and count[hn.FROM_RANDOM] > 0 and count["held"] > 0
     # the call leaves the handle's driver state and the clock alone: no step has run
     with pytest.raises(pkg.PigeonError):
@@ -204,27 +151,27 @@ def test_the_identity_set_reproduces_the_human_mode(pkg, skidpad, grid, inputs, 
     for mode in (0, 1, 2):
         runs = []
         for lib in (False, True):
-            m = make(pkg, skidpad, grid, precision=precision)
+            m = rl.make(pkg, skidpad, B, grid=grid, precision=precision)
             if with_others:
                 other_libraries(pkg, m, kind)
             if lib:
                 m.set_humans(hn.identity(mode), seed=DRIVER_SEED)
-            start(m, inputs)
+            rl.start(m, inputs, others=True)
             # (under the library the argument no longer decides: the call asks for another mode, the set's is what runs)
             human = MODE_NAME[(mode + 1) % 2] if lib else MODE_NAME[mode]
-            runs.append(rollout(m, kind, STEPS, human=human, script=script if mode == 2 else None))
+            runs.append(rl.rollout(m, kind, STEPS, DT, human=human, human_u=script if mode == 2 else None, **RUN))
             if lib:
-                assert m.get_option("stat_human_steps") == STEPS and same(m.human_state(), runs[1]["human_u"][-1])
+                assert m.get_option("stat_human_steps") == STEPS and rl.same(m.human_state(), runs[1]["human_u"][-1])
             else:
                 assert m.get_option("stat_human_steps") == 0
             m.close()
         assert_same_run(runs[0], runs[1], (kind, precision, mode))
         if kind == "safety":
-            assert same(runs[1]["human_u"], runs[1]["human"])
+            assert rl.same(runs[1]["human_u"], runs[1]["human"])
             if mode == 1:
                 assert np.count_nonzero(runs[0]["human"]) > 0
             if mode == 2:
-                assert same(runs[1]["human"], script.astype(DTYPE[precision]))
+                assert rl.same(runs[1]["human"], script.astype(DTYPE[precision]))
 
 
 # ---- 3: a mixed library is the per-instance composition -----------------------------------------------------------------------------------------------------------------
@@ -233,15 +180,15 @@ def test_the_identity_set_reproduces_the_human_mode(pkg, skidpad, grid, inputs, 
 def test_a_mixed_library_is_the_composition_per_instance(pkg, skidpad, grid, inputs, kind, precision):
     script = inputs[5]
     idx = (np.arange(B) % 3).astype(np.int32)
-    m = make(pkg, skidpad, grid, precision=precision)
+    m = rl.make(pkg, skidpad, B, grid=grid, precision=precision)
     m.set_humans(MIXED, idx)
-    start(m, inputs)
-    mixed = rollout(m, kind, STEPS, script=script)
+    rl.start(m, inputs, others=True)
+    mixed = rl.rollout(m, kind, STEPS, DT, human_u=script, **RUN)
     m.close()
     for mode in (0, 1, 2):
-        u = make(pkg, skidpad, grid, precision=precision)
-        start(u, inputs)
-        uniform = rollout(u, kind, STEPS, human=MODE_NAME[mode], script=script if mode == 2 else None)
+        u = rl.make(pkg, skidpad, B, grid=grid, precision=precision)
+        rl.start(u, inputs, others=True)
+        uniform = rl.rollout(u, kind, STEPS, DT, human=MODE_NAME[mode], human_u=script if mode == 2 else None, **RUN)
         u.close()
         cols = np.nonzero(idx == mode)[0]
         assert_same_run(mixed, uniform, (kind, precision, mode), cols=(cols, cols))
@@ -250,35 +197,35 @@ def test_a_mixed_library_is_the_composition_per_instance(pkg, skidpad, grid, inp
 # ---- 4: the window ------------------------------------------------------------------------------------------------------------------------------------------------------
 def test_a_window_is_the_script_zeroed_outside_it(pkg, skidpad, grid, inputs):
     script = inputs[5]
-    m = make(pkg, skidpad, grid)
+    m = rl.make(pkg, skidpad, B, grid=grid)
     m.set_humans(hn.identity(2, step_on=3, step_off=6))
-    start(m, inputs)
-    lib = rollout(m, "safety", STEPS, script=script)
+    rl.start(m, inputs, others=True)
+    lib = rl.rollout(m, "safety", STEPS, DT, human_u=script, **RUN)
     m.close()
     cut = script.copy(); cut[:3] = 0.0; cut[6:] = 0.0
-    u = make(pkg, skidpad, grid)
-    start(u, inputs)
-    ref = rollout(u, "safety", STEPS, human="script", script=cut)
+    u = rl.make(pkg, skidpad, B, grid=grid)
+    rl.start(u, inputs, others=True)
+    ref = rl.rollout(u, "safety", STEPS, DT, human="script", human_u=cut, **RUN)
     u.close()
     assert_same_run(lib, ref, "window")
-    assert same(lib["human_u"], cut)
+    assert rl.same(lib["human_u"], cut)
 
 
 # ---- 5: hold ------------------------------------------------------------------------------------------------------------------------------------------------------------
 def test_a_held_worst_case(pkg, skidpad, grid, inputs):
-    m = make(pkg, skidpad, grid)
+    m = rl.make(pkg, skidpad, B, grid=grid)
     held = hn.identity(1, hold_steps=3)
     m.set_humans(held)
-    start(m, inputs)
-    r = rollout(m, "safety", STEPS)
+    rl.start(m, inputs, others=True)
+    r = rl.rollout(m, "safety", STEPS, DT, **RUN)
     H = r["human"]
     for k in range(STEPS):
-        assert same(H[k], H[k - k % 3]), k
+        assert rl.same(H[k], H[k - k % 3]), k
     decisions = H[[0, 3, 6, 9]]
     assert np.any(np.any(decisions != decisions[:1], axis=(0, 2)))
     x7, vg8 = lookups(m, r["state"], r["other"])
     got = m.human_response(0, x7, vg8, DT)
-    err = float(rel(H, got).max())
+    err = float(rl.rel(H, got).max())
     print(f"held worst case: the rollout's history against pg_human_response on the reconstructed x7 / vg8: worst {err:.3g} (bar {WORST_BAR:.3g})")
     assert err <= WORST_BAR
     check_law(pkg, H, "f64", [held], None, np.arange(B), 0, x7, vg8, None, "held worst case, rollout history")
@@ -289,24 +236,24 @@ def test_a_held_worst_case(pkg, skidpad, grid, inputs):
 @pytest.mark.parametrize("kind", ["safety", "node"])
 def test_clock_rules(pkg, skidpad, grid, inputs, kind):
     script = inputs[5]
-    ids = stream_ids(B)
+    ids = rl.stream_ids(B)
 
     def run(split, between=None):
-        m = make(pkg, skidpad, grid)
+        m = rl.make(pkg, skidpad, B, grid=grid)
         m.set_humans(SETS, IDX, seed=DRIVER_SEED, streams=ids)
-        start(m, inputs)
+        rl.start(m, inputs, others=True)
         parts = []; k0 = 0
         for i, n in enumerate(split):
             if i and between == "reinstall":
                 m.set_humans([SETS[0]], None); m.set_humans(SETS, IDX, seed=1); m.set_human_index(IDX); m.set_human_seed(DRIVER_SEED, ids)
             if i and between == "clear":
                 m.clear_humans(); m.set_humans(SETS, IDX, seed=DRIVER_SEED, streams=ids)
-            parts.append(rollout(m, kind, n, script=script[k0:k0 + n])); k0 += n
-        return m, join(parts)
+            parts.append(rl.rollout(m, kind, n, DT, human_u=script[k0:k0 + n], **RUN)); k0 += n
+        return m, rl.join(parts)
     m, whole = run([STEPS])
     assert m.get_option("stat_human_steps") == STEPS
-    m.reset(); start(m, inputs)                               # pg_set_inputs: the clock restarts and the run replays (pg_reset: from cold solvers, as the first run)
-    again = rollout(m, kind, STEPS, script=script)
+    m.reset(); rl.start(m, inputs, others=True)                               # pg_set_inputs: the clock restarts and the run replays (pg_reset: from cold solvers, as the first run)
+    again = rl.rollout(m, kind, STEPS, DT, human_u=script, **RUN)
     assert_same_run(whole, again, "replay", skip=())
     m.close()
     for between in (None, "reinstall"):
@@ -315,42 +262,42 @@ def test_clock_rules(pkg, skidpad, grid, inputs, kind):
         m.close()
     # the hold phase and the AR state did continue: the random lanes decide at even steps only, and step 5 holds step 4
     rnd = IDX == 3
-    assert same(whole["human_u"][5][rnd], whole["human_u"][4][rnd]) and not same(whole["human_u"][6][rnd], whole["human_u"][4][rnd])
+    assert rl.same(whole["human_u"][5][rnd], whole["human_u"][4][rnd]) and not rl.same(whole["human_u"][6][rnd], whole["human_u"][4][rnd])
     # after a clear the next install starts fresh: a decision at step 5, and the law from a fresh state there (the worst-case lanes need x7: left out)
     m, cleared = run([5, 7], "clear")
     m.close()
-    assert same(cleared["human_u"][:5], whole["human_u"][:5]) and not same(cleared["human_u"][5][rnd], cleared["human_u"][4][rnd])
+    assert rl.same(cleared["human_u"][:5], whole["human_u"][:5]) and not rl.same(cleared["human_u"][5][rnd], cleared["human_u"][4][rnd])
     check_law(pkg, cleared["human_u"][5:], "f64", SETS, IDX, ids, 5, None, None, script[5:], "after a clear", has_hji=False, lanes=IDX != 1)
 
 
 def test_a_stream_draws_the_same_sequence_in_any_batch(pkg, skidpad, grid, inputs):
-    ids = stream_ids(B)
+    ids = rl.stream_ids(B)
     rnd = hn.identity(3, sigma=[0.2, 1.5], tau=0.05)
     z7 = np.zeros((STEPS, B, 7)); z8 = np.zeros((STEPS, B, 8))
-    big = make(pkg, skidpad, grid)
-    start(big, inputs)
+    big = rl.make(pkg, skidpad, B, grid=grid)
+    rl.start(big, inputs, others=True)
     big.set_humans(rnd, seed=DRIVER_SEED, streams=ids)
     u96 = big.human_response(0, z7, z8, DT)
-    r96 = rollout(big, "safety", STEPS)
+    r96 = rl.rollout(big, "safety", STEPS, DT, **RUN)
     big.close()
     slots = np.arange(B - 1, B - 33, -1)                      # the last 32 instances, in reverse order
-    small = make(pkg, skidpad, grid)
-    start(small, [a[slots] for a in inputs[:5]] + [None], n=32)
+    small = rl.make(pkg, skidpad, B, grid=grid)
+    rl.start(small, [a[slots] for a in inputs[:5]] + [None], 32, others=True)
     small.set_humans(rnd, seed=DRIVER_SEED, streams=ids[slots])
     u32 = small.human_response(0, z7[:, :32], z8[:, :32], DT)
-    r32 = rollout(small, "safety", STEPS)
+    r32 = rl.rollout(small, "safety", STEPS, DT, **RUN)
     small.close()
-    assert same(u32, u96[:, slots]) and np.count_nonzero(u96) == u96.size
-    assert same(r32["human_u"], r96["human_u"][:, slots]) and same(r32["human"], r96["human"][:, slots])
-    assert same(r96["human_u"], u96)
+    assert rl.same(u32, u96[:, slots]) and np.count_nonzero(u96) == u96.size
+    assert rl.same(r32["human_u"], r96["human_u"][:, slots]) and rl.same(r32["human"], r96["human"][:, slots])
+    assert rl.same(r96["human_u"], u96)
 
 
 # ---- 7: contract --------------------------------------------------------------------------------------------------------------------------------------------------------
 def test_contract(pkg, skidpad, grid, inputs):
     import torch
     script = inputs[5]
-    m = make(pkg, skidpad, grid)
-    start(m, inputs)
+    m = rl.make(pkg, skidpad, B, grid=grid)
+    rl.start(m, inputs, others=True)
     m.set_humans(SETS, IDX, seed=DRIVER_SEED)
     before = m.humans()
     bad = [dict(mode=4), dict(mode=-1), dict(hold_steps=0), dict(step_on=-1), dict(gain=[1.5, 1.0]), dict(gain=[1.0, -0.1]), dict(gain=[np.nan, 1.0]),
@@ -385,7 +332,7 @@ def test_contract(pkg, skidpad, grid, inputs):
     # pg_simulate_dev never reads the library: no script wanted, nothing counted
     m.simulate_(2, DT)
     assert m.get_option("stat_human_steps") == 2
-    start(m, inputs)
+    rl.start(m, inputs, others=True)
     with pytest.raises(pkg.PigeonError):
         m.human_state()                                       # forgotten with the inputs
     m.clear_humans()
@@ -399,7 +346,7 @@ def test_the_other_entry_points_never_read_the_library(pkg, skidpad, grid, input
     state, control, t0, toff, other, _ = inputs
     outs = []
     for lib in (False, True):
-        m = make(pkg, skidpad, grid)
+        m = rl.make(pkg, skidpad, B, grid=grid)
         if lib:
             m.set_humans(SETS, None, seed=DRIVER_SEED)        # four sets, a script set among them, and NO index: none of these calls cares
         u = m.step_(state, control, t0, other_car_state=other, time_offset=toff)
@@ -423,14 +370,14 @@ def test_the_other_entry_points_never_read_the_library(pkg, skidpad, grid, input
 def test_the_decoupled_node_rollout_has_no_worst_case(pkg, skidpad, inputs):
     runs = []
     for lib in (False, True):
-        m = make(pkg, skidpad, None, formulation="decoupled")        # (a lateral handle takes no grid: there is no safety row)
+        m = rl.make(pkg, skidpad, B, formulation="decoupled", hji_eps=1.0)        # (a lateral handle takes no grid: there is no safety row)
         if lib:
             m.set_humans(hn.identity(1))
-        start(m, inputs)
-        runs.append(rollout(m, "node", STEPS, human="worst", policy=False))
+        rl.start(m, inputs, others=True)
+        runs.append(rl.rollout(m, "node", STEPS, DT, human="worst", summary=True))
         m.close()
     assert_same_run(runs[0], runs[1], "decoupled node")
-    assert same(runs[1]["human_u"], np.zeros((STEPS, B, 2)))
+    assert rl.same(runs[1]["human_u"], np.zeros((STEPS, B, 2)))
 
 
 # ---- 9: one large batch -------------------------------------------------------------------------------------------------------------------------------------------------
@@ -442,18 +389,18 @@ def test_large_batch_takes_the_pipelined_launch_under_a_library(pkg, skidpad, gr
     script = np.stack([rng.uniform(-0.5, 0.5, (steps, n)), rng.uniform(-3.0, 3.0, (steps, n))], axis=2)
     inp = (state, control, t0, toff, other, script)
     idx = (np.arange(n) % 3).astype(np.int32)
-    big = make(pkg, skidpad, grid, cap=n, options={"pipe_min": n})
+    big = rl.make(pkg, skidpad, n, grid=grid, options={"pipe_min": n})
     big.set_humans(MIXED, idx)
-    start(big, inp, n)
-    rb = rollout(big, "safety", steps, script=script)
+    rl.start(big, inp, n, others=True)
+    rb = rl.rollout(big, "safety", steps, DT, human_u=script, **RUN)
     assert big.get_option("stat_pipelined_launches") >= 1 and big.get_option("stat_human_steps") == steps
-    assert same(big.human_state(), rb["human_u"][-1])
+    assert rl.same(big.human_state(), rb["human_u"][-1])
     big.close()
-    small = make(pkg, skidpad, grid)
+    small = rl.make(pkg, skidpad, B, grid=grid)
     small.set_humans(MIXED, idx[:B])
-    start(small, inp, B)
-    rs = rollout(small, "safety", steps, script=script[:, :B])
+    rl.start(small, inp, B, others=True)
+    rs = rl.rollout(small, "safety", steps, DT, human_u=script[:, :B], **RUN)
     small.close()
     assert_same_run(rb, rs, "B = 2341 against B = 96", cols=(np.arange(B), np.arange(B)), skip=())
-    assert same(rb["human_u"][:, idx == 0], np.zeros((steps, int(np.sum(idx == 0)), 2))) and same(rb["human_u"][:, idx == 2], script[:, idx == 2])
+    assert rl.same(rb["human_u"][:, idx == 0], np.zeros((steps, int(np.sum(idx == 0)), 2))) and rl.same(rb["human_u"][:, idx == 2], script[:, idx == 2])
     assert np.count_nonzero(rb["human_u"][:, idx == 1]) > 0

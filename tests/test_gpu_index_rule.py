@@ -12,7 +12,7 @@ import pytest
 import plant_numpy
 import rollout_libs as rl
 import sensor_numpy
-from test_gpu_human_sets import grid  # noqa: F401  (the fixture: the grid of the human library's tests)
+from rollout_libs import grid  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -78,11 +78,11 @@ def test_the_other_four_libraries_want_an_index_that_covers_the_batch(pkg, skidp
     (three steps asked for) and the library's *_response call both refuse with PG_ERR_STATE and the index rule's one message."""
     _, identity, setter, _ = rl.LIBRARIES[library]
     refusal = f"a {library} library is installed but {setter} does not cover the batch"
-    m = rl.make(pkg, skidpad, grid)
-    state, control, t0, other, toff = rl.inputs(pkg, skidpad)
+    m = rl.make_small(pkg, skidpad, grid)
+    state, control, t0, other, toff = rl.small_inputs(pkg, skidpad)
     m.set_inputs(state, control, t0, other, toff)
     rl.install(m, library, [identity, identity], np.array([0, 1, 0, 1], dtype=np.int32))
-    assert rl.rollout(m, library, 3) == rl.STATE
+    assert rl.rollout_status(m, library, 3) == rl.STATE
     assert rl.last_error(m) == refusal
     with pytest.raises(pkg.PigeonError) as e:
         RESPONSE[library](m)

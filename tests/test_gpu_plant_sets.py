@@ -12,6 +12,7 @@ import pytest
 
 import plant_numpy
 from conftest import make_oracle
+from rollout_libs import check_summary, inputs, make, narrowed, numpy_summary, rel, rollout, start
 
 pytestmark = pytest.mark.gpu
 
@@ -20,36 +21,9 @@ BAR = {"f64": 1e-9, "f32": 2e-5}
 DT = 0.01
 
 
-def rel(got, ref):
-    return np.abs(np.asarray(got) - np.asarray(ref)) / np.maximum(1.0, np.abs(ref))
-
-
 @pytest.fixture(scope="module")
 def plants(pkg):
     return plant_numpy.four_plants(pkg.X1)
-
-
-def make(pkg, traj, B, formulation="coupled", precision="f64", **kw):
-    return pkg.BatchedTrajectoryTrackingMPC(traj, B, formulation=formulation, precision=precision, **kw)
-
-
-def start(pkg, m, traj, B, others=False):
-    state, control, t0, toff = pkg.synthetic.config2_inputs(traj, B, seed=SEED)
-    other = pkg.synthetic.other_cars(state) if others else None
-    m.set_inputs(state, control, t0, other, toff)
-    return state, control, t0, toff
-
-
-def rollout(m, kind, steps, **kw):
-    """(state history [steps][B][6], applied control history [steps][B][3], final state [B][6]) of one of the three rollouts"""
-    if kind == "simulate":
-        s, c, t, qh, uh = m.simulate_(steps, DT, record=True)
-        return qh, uh, s
-    if kind == "safety":
-        out = m.simulate_safety_(steps, DT, use_HJI_policy=False, record=True)
-        return out[4]["state"], out[4]["control"], out[0]
-    out = m.simulate_node_(steps, DT, record=True, **kw)
-    return out[5]["state"], out[5]["applied"], out[0]
 
 
 # ---- 1 / 7: replay of every recorded step against the numpy plant ----------------------------------------------------------------------------------------------------
@@ -60,8 +34,9 @@ def test_every_step_replays_through_the_numpy_plant_of_its_own_set(pkg, skidpad,
     idx = (np.arange(B) % 4).astype(np.int32)
     m = make(pkg, skidpad, B, formulation, precision)
     m.set_plants(plants, idx)
-    start(pkg, m, skidpad, B, others=kind != "simulate")
-    qh, uh, final = rollout(m, kind, steps)
+    start(m, inputs(pkg, skidpad, B), others=kind != "simulate")
+    r = rollout(m, kind, steps, DT)
+    qh, uh, final = r["state"], r["control"], r["final_state"]
     own = plant_numpy.stack_vehicles([plants[i] for i in idx], B)
     bar = BAR[precision]
     worst = 0.0; apart = np.zeros(B)
@@ -84,11 +59,11 @@ def histories(pkg, traj, B, steps, sets, idx, kind="simulate", precision="f64", 
     m = make(pkg, traj, B, precision=precision, **kw)
     if sets is not None:
         m.set_plants(sets, idx)
-    start(pkg, m, traj, B, others=kind != "simulate")
-    qh, uh, final = rollout(m, kind, steps)
+    start(m, inputs(pkg, traj, B), others=kind != "simulate")
+    r = rollout(m, kind, steps, DT)
     stat = m.get_option("stat_pipelined_launches")
     m.close()
-    return qh, uh, final, stat
+    return r["state"], r["control"], r["final_state"], stat
 
 
 def test_mixed_library_equals_libraries_of_one_bit_for_bit(pkg, skidpad, plants):
@@ -211,7 +186,7 @@ def test_installing_an_index_between_rollouts_resets_nothing(pkg, skidpad, plant
     def run(between):
         m = make(pkg, skidpad, B)
         m.set_hji_cache(*grid)
-        st = start(pkg, m, skidpad, B, others=True)
+        st = start(m, inputs(pkg, skidpad, B), others=True)
         m.set_plants(plants, idx)
         m.simulate_safety_(4, DT, use_HJI_policy=True, human="worst")
         if between == "restore":
@@ -253,37 +228,6 @@ def test_large_batch_takes_the_pipelined_launch_under_a_library(pkg, skidpad, pl
 
 
 # ---- 6 / 7: tracking summary -----------------------------------------------------------------------------------------------------------------------------------------
-def narrowed(pkg, traj, half=0.25, shift=0.0):
-    d = traj.data.copy()
-    d[10] = half + shift; d[11] = -half + shift
-    return pkg.TrajectoryTube(*d)
-
-
-def numpy_summary(orcs, tidx, qh, step0=0):
-    """the numpy tracking summary of a recorded state history [steps][B][6]; orcs: one oracle per trajectory, tidx [B]"""
-    K, B = qh.shape[:2]
-    s = np.zeros((K, B)); e = np.zeros((K, B))
-    for k in range(K):
-        for b in range(B):
-            s[k, b], e[k, b] = orcs[tidx[b]].path_coordinates(qh[k, b, 0], qh[k, b, 1])[:2]
-    eL = np.zeros((K, B)); eR = np.zeros((K, B))
-    for j, o in enumerate(orcs):
-        sel = tidx == j
-        eL[:, sel], eR[:, sel] = plant_numpy.tube_edges(o.traj, s[:, sel])
-    return plant_numpy.tracking_summary(s, e, qh[..., 3], qh[..., 4], qh[..., 5], eL, eR, step0), e
-
-
-def check_summary(got, want, bar, B):
-    (sm, n, fx), (wsm, wn, wfx, margin) = got, want
-    assert np.array_equal(n, wn)
-    err = rel(sm, wsm)
-    assert err.max() < bar, (err.max(axis=0), bar)
-    decided = margin > 1e-6
-    assert np.mean(~decided) <= 1 / 8, float(np.mean(~decided))
-    assert np.array_equal(fx[decided], wfx[decided]), np.flatnonzero(decided & (fx != wfx))
-    return float(err.max())
-
-
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_tracking_summary_equals_numpy_on_the_recorded_history(pkg, oracle_mod, skidpad, plants, precision):
     B, steps = 96, 30
@@ -295,35 +239,35 @@ def test_tracking_summary_equals_numpy_on_the_recorded_history(pkg, oracle_mod, 
     tidx = np.zeros(B, dtype=int)
     m = make(pkg, tube, B, precision=precision)
     m.set_plants(plants, idx)
-    start(pkg, m, tube, B)
+    start(m, inputs(pkg, tube, B))
     with pytest.raises(pkg.PigeonError):
         m.tracking_summary()                                 # option off: PG_ERR_STATE
     m.set_option("tracking_summary", 1)
     sm0, n0, fx0 = m.tracking_summary()
     assert np.all(n0 == 0) and np.all(fx0 == -1)              # nothing counted yet
     qh = m.simulate_(steps, DT, record=True)[3]
-    want, e = numpy_summary([orc], tidx, qh)
+    want, _, e = numpy_summary([orc], tidx, qh)
     out = (e > 0.25) | (e < -0.25)
     n_start, n_leave, n_never = int(out[0].sum()), int((~out[0] & out.any(axis=0)).sum()), int((~out.any(axis=0)).sum())
     print(f"{precision}: start outside {n_start}, leave {n_leave}, never {n_never}")
     assert min(n_start, n_leave, n_never) >= 8
-    worst = check_summary(m.tracking_summary(), want, bar, B)
+    worst = check_summary(m.tracking_summary(), want, bar)
     # a second call with the same dt continues the sums and the step indices
     qh2 = m.simulate_(10, DT, record=True)[3]
     both = np.concatenate([qh, qh2])
-    want2, _ = numpy_summary([orc], tidx, both)
-    worst = max(worst, check_summary(m.tracking_summary(), want2, bar, B))
+    want2, _, _ = numpy_summary([orc], tidx, both)
+    worst = max(worst, check_summary(m.tracking_summary(), want2, bar))
     assert np.all(m.tracking_summary()[1] == 40)
     # another dt restarts them (and the clock)
     qh3 = m.simulate_(5, 0.02, record=True)[3]
-    want3, _ = numpy_summary([orc], tidx, qh3)
-    worst = max(worst, check_summary(m.tracking_summary(), want3, bar, B))
+    want3, _, _ = numpy_summary([orc], tidx, qh3)
+    worst = max(worst, check_summary(m.tracking_summary(), want3, bar))
     # set_inputs restarts them
-    start(pkg, m, tube, B)
+    start(m, inputs(pkg, tube, B))
     assert np.all(m.tracking_summary()[1] == 0)
     qh4 = m.simulate_(3, 0.02, record=True)[3]
-    want4, _ = numpy_summary([orc], tidx, qh4)
-    worst = max(worst, check_summary(m.tracking_summary(), want4, bar, B))
+    want4, _, _ = numpy_summary([orc], tidx, qh4)
+    worst = max(worst, check_summary(m.tracking_summary(), want4, bar))
     print(f"{precision}: tracking summary vs numpy, worst relative difference {worst:.2e} (bar {bar:g})")
     m.close()
 
@@ -335,7 +279,7 @@ def test_tracking_summary_off_adds_no_launch_and_changes_no_bit(pkg, skidpad):
         m = make(pkg, skidpad, B)
         if on:
             m.set_option("tracking_summary", 1)
-        start(pkg, m, skidpad, B)
+        start(m, inputs(pkg, skidpad, B))
         r = m.simulate_(steps, DT, record=True)
         stats = [m.get_option(n) for n in ("stat_pipelined_launches", "stat_split_solve_launches", "stat_single_solve_launches", "stat_whole_batch_solves")]
         outs.append((r, stats))
@@ -356,24 +300,24 @@ def test_tracking_summary_with_a_trajectory_library_and_in_the_node_rollout(pkg,
     m.set_trajectories(tubes, tidx)
     m.set_plants(plants, idx)
     m.set_option("tracking_summary", 1)
-    start(pkg, m, tubes[0], B, others=True)
+    start(m, inputs(pkg, tubes[0], B), others=True)
     qh = m.simulate_(steps, DT, record=True)[3]
-    want, _ = numpy_summary(orcs, tidx, qh)
-    check_summary(m.tracking_summary(), want, BAR["f64"], B)
+    want, _, _ = numpy_summary(orcs, tidx, qh)
+    check_summary(m.tracking_summary(), want, BAR["f64"])
     assert len(set(want[2][tidx == 0]) | set(want[2][tidx == 1])) > 2
     # node rollout, pre_flag off on a third of the steps (for every other instance): the steps still count, the summaries still match
-    start(pkg, m, tubes[0], B, others=True)
+    start(m, inputs(pkg, tubes[0], B), others=True)
     pre = np.ones((steps, B), dtype=np.uint8); pre[::3, ::2] = 0
     out = m.simulate_node_(steps, DT, pre_flag=pre, record=True)
     hist = out[5]
     assert np.all(hist["event"][::3, ::2] == m.NODE_EVENTS["pre_flag_off"])
-    want, _ = numpy_summary(orcs, tidx, hist["state"])
+    want, _, _ = numpy_summary(orcs, tidx, hist["state"])
     got = m.tracking_summary()
     assert np.all(got[1] == steps)
-    check_summary(got, want, BAR["f64"], B)
+    check_summary(got, want, BAR["f64"])
     # ... and in the safety rollout
-    start(pkg, m, tubes[0], B, others=True)
+    start(m, inputs(pkg, tubes[0], B), others=True)
     sh = m.simulate_safety_(8, DT, use_HJI_policy=False, record=True)[4]["state"]
-    want, _ = numpy_summary(orcs, tidx, sh)
-    check_summary(m.tracking_summary(), want, BAR["f64"], B)
+    want, _, _ = numpy_summary(orcs, tidx, sh)
+    check_summary(m.tracking_summary(), want, BAR["f64"])
     m.close()

@@ -13,7 +13,7 @@ import disturbance_numpy
 import estimator_numpy
 import human_numpy
 import rollout_libs as rl
-from test_gpu_human_sets import grid  # noqa: F401  (the fixture: the grid of the human library's tests)
+from rollout_libs import grid  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +33,7 @@ def first_record(m, library, setter, dt):
     torch, tdt, dev = m._torch()
     buf = torch.zeros((3, rl.B, rl.HISTORIES[setter][1]), dtype=tdt, device=dev)
     assert rl.register(m, setter, buf, 3) == rl.OK
-    assert rl.rollout(m, library, 3, dt) == rl.OK
+    assert rl.rollout_status(m, library, 3, dt) == rl.OK
     m.synchronize()
     return buf.cpu().numpy().astype(np.float64)[0]
 
@@ -41,12 +41,12 @@ def first_record(m, library, setter, dt):
 @pytest.mark.parametrize("library", sorted(CASES))
 def test_new_inputs_void_the_state_and_another_dt_restarts_the_law(pkg, skidpad, grid, library):
     one_set, seed, getter, article, setter = CASES[library]
-    state, control, t0, other, toff = rl.inputs(pkg, skidpad)
-    m = rl.make(pkg, skidpad, grid)
+    state, control, t0, other, toff = rl.small_inputs(pkg, skidpad)
+    m = rl.make_small(pkg, skidpad, grid)
     rl.install(m, library, [one_set], **seed)
     m.set_inputs(state, control, t0, other, toff)
     # after a rollout step the getter answers
-    assert rl.rollout(m, library) == rl.OK
+    assert rl.rollout_status(m, library) == rl.OK
     assert getattr(m, getter)().shape[0] == rl.B
     # after new inputs it refuses
     m.set_inputs(state, control, t0, other, toff)
@@ -55,14 +55,14 @@ def test_new_inputs_void_the_state_and_another_dt_restarts_the_law(pkg, skidpad,
     name = {"disturbance_state": "pg_get_disturbance_state", "estimated_state": "pg_get_estimated_state", "human_state": "pg_get_human_state"}[getter]
     assert str(e.value) == f"{name} failed with status {rl.STATE}: {name}: no rollout step under {article} library since the inputs were installed"
     # three steps at DT, then a call at 2 DT: the clock restarts.  Its first record against a fresh handle's, started from the state the second call found
-    assert rl.rollout(m, library) == rl.OK
+    assert rl.rollout_status(m, library) == rl.OK
     s = np.zeros((rl.B, 6)); c = np.zeros((rl.B, 3)); t = np.zeros(rl.B); o = np.zeros((rl.B, 4))
     m._chk(m.lib.pg_get_state(m.h, s.ctypes.data_as(DP), c.ctypes.data_as(DP), t.ctypes.data_as(DP)), "pg_get_state")
     m._chk(m.lib.pg_get_safety_state(m.h, o.ctypes.data_as(DP), None, None, None), "pg_get_safety_state")
     got = first_record(m, library, setter, 2 * rl.DT)
     m.close()
 
-    fresh = rl.make(pkg, skidpad, grid)
+    fresh = rl.make_small(pkg, skidpad, grid)
     rl.install(fresh, library, [one_set], **seed)
     fresh.set_inputs(s, c, t, o, toff)
     want = first_record(fresh, library, setter, 2 * rl.DT)

@@ -13,61 +13,16 @@ import node_numpy as nn
 import plant_numpy
 import sensor_numpy
 from conftest import make_oracle
+from rollout_libs import NOISE_SEED, inputs, join, make, narrowed, numpy_summary, rel, rollout, start, stream_ids
 
 pytestmark = pytest.mark.gpu
 
-SEED = 4                                  # of the synthetic inputs
-NOISE_SEED = 0x9E3779B97F4A7C15           # of the draws: high word non-zero
 BAR = {"f64": 1e-9, "f32": 2e-5}          # node bars
 MEAS_BAR = {"f64": 1e-12, "f32": 2e-5}    # measured = true + bias + sigma z: three roundings + the draw's 1e-13 / the fp32 draw's 2e-6
 DRAW_BAR = {"f64": 1e-13, "f32": 2e-5}
 DT = 0.01
 SETS = sensor_numpy.four_sensors()
 KINDS = [("simulate", "coupled"), ("simulate", "decoupled"), ("safety", "coupled"), ("node", "coupled")]
-
-
-def rel(got, ref):
-    return np.abs(np.asarray(got) - np.asarray(ref)) / np.maximum(1.0, np.abs(ref))
-
-
-def stream_ids(B):
-    """64-bit ids, all but the first above 2^32, no two alike in either word"""
-    b = np.arange(B, dtype=np.uint64)
-    return b * np.uint64(0x100000001) + np.uint64(7) + (b % np.uint64(3)) * np.uint64(1 << 40)
-
-
-def make(pkg, traj, B, formulation="coupled", precision="f64", **kw):
-    return pkg.BatchedTrajectoryTrackingMPC(traj, B, formulation=formulation, precision=precision, **kw)
-
-
-def inputs(pkg, traj, B):
-    state, control, t0, toff = pkg.synthetic.config2_inputs(traj, B, seed=SEED)
-    return state, control, t0, toff, pkg.synthetic.other_cars(state)
-
-
-def start(pkg, m, traj, B, others=False):
-    st, control, t0, toff, other = inputs(pkg, traj, B)
-    m.set_inputs(st, control, t0, other if others else None, toff)
-    return st, control, t0, toff
-
-
-def rollout(m, kind, steps, measured=False, **kw):
-    """dict(state [steps][B][6], control = the control the plant integrates [steps][B][3], final [B][6], measured [steps][B][6] or None) of one of the three rollouts"""
-    if kind == "simulate":
-        out = m.simulate_(steps, DT, record=True, measured=measured)
-        r = dict(state=out[3], control=out[4], final=out[0])
-    elif kind == "safety":
-        out = m.simulate_safety_(steps, DT, use_HJI_policy=False, record=True, measured=measured)
-        r = dict(state=out[4]["state"], control=out[4]["control"], final=out[0])
-    else:
-        out = m.simulate_node_(steps, DT, record=True, measured=measured, **kw)
-        r = dict(state=out[5]["state"], control=out[5]["applied"], final=out[0], event=out[5]["event"])
-    r["measured"] = out[-1] if measured else None
-    return r
-
-
-def join(a, b):
-    return {k: (b[k] if k == "final" else None if a[k] is None else np.concatenate([a[k], b[k]])) for k in a}
 
 
 _noisy = {}
@@ -80,12 +35,12 @@ def noisy_run(pkg, traj, kind, formulation, precision):
         B = 70
         idx = (np.arange(B) % 4).astype(np.int32)
         m = make(pkg, traj, B, formulation, precision)
-        st = start(pkg, m, traj, B, others=kind != "simulate")
+        st = start(m, inputs(pkg, traj, B), others=kind != "simulate")
         m.set_sensors(SETS, idx, seed=NOISE_SEED, streams=stream_ids(B))
-        a = rollout(m, kind, 5, measured=True)
+        a = rollout(m, kind, 5, DT, measured=True)
         last5 = m.measured_state()
-        b = rollout(m, kind, 7, measured=True)
-        r = join(a, b)
+        b = rollout(m, kind, 7, DT, measured=True)
+        r = join([a, b])
         r.update(idx=idx, last5=last5, last=m.measured_state(), sensor_steps=m.get_option("stat_sensor_steps"), clock=m.simulate_clock(12, st[2], DT), inputs=st)
         m.close()
         _noisy[key] = r
@@ -113,10 +68,10 @@ def test_draws_equal_the_twin(pkg, skidpad, precision):
     B = 70
     ids = stream_ids(B)
     m = make(pkg, skidpad, B, precision=precision)
-    start(pkg, m, skidpad, B)
+    start(m, inputs(pkg, skidpad, B))
     m.set_sensor_seed(NOISE_SEED, ids)
     small = make(pkg, skidpad, 7, precision=precision)
-    start(pkg, small, skidpad, 7)
+    start(small, inputs(pkg, skidpad, 7))
     ids7 = np.array([11, 12, ids[5], 1 << 50, 3, 4, 5], dtype=np.uint64)
     small.set_sensor_seed(NOISE_SEED, ids7)
     for step0 in (0, 1000):
@@ -155,7 +110,7 @@ def test_the_plant_moves_the_true_state(pkg, skidpad, kind, formulation, precisi
     qh, uh, mh = r["state"], r["control"], r["measured"]
     worst = 0.0; apart = np.zeros(70)
     for k in range(12):
-        nxt = qh[k + 1] if k + 1 < 12 else r["final"]
+        nxt = qh[k + 1] if k + 1 < 12 else r["final_state"]
         err = rel(nxt, plant_numpy.plant_step_vec(P, qh[k], uh[k], DT))
         worst = max(worst, float(err.max()))
         assert err.max() < bar, (kind, formulation, precision, k, int(np.argmax(err.max(axis=1))), float(err.max()))
@@ -182,9 +137,9 @@ def test_the_controller_sees_the_measured_state(pkg, skidpad, formulation):
         h.close()
         return np.stack(us)
     plain = make(pkg, skidpad, B, formulation)
-    st = start(pkg, plain, skidpad, B)
+    st = start(plain, inputs(pkg, skidpad, B))
     clock = plain.simulate_clock(steps, st[2], DT)
-    p = rollout(plain, "simulate", steps)
+    p = rollout(plain, "simulate", steps, DT)
     assert plain.get_option("stat_sensor_steps") == 0
     plain.close()
     up = replay(p["state"], p["control"], clock, st[3])
@@ -210,11 +165,11 @@ def test_the_controller_sees_the_measured_state(pkg, skidpad, formulation):
 # ---- 5: nothing changes without noise --------------------------------------------------------------------------------------------------------------------------------
 def histories(pkg, traj, B, steps, sets, idx, kind, precision, **kw):
     m = make(pkg, traj, B, precision=precision, **kw)
-    start(pkg, m, traj, B, others=kind != "simulate")
+    start(m, inputs(pkg, traj, B), others=kind != "simulate")
     if sets is not None:
         m.set_sensors(sets, idx, seed=NOISE_SEED, streams=stream_ids(B))
-    r = rollout(m, kind, steps)
-    out = [r["state"], r["control"], r["final"]] + [np.asarray(x) for x in m.solve_info()[:3]]
+    r = rollout(m, kind, steps, DT)
+    out = [r["state"], r["control"], r["final_state"]] + [np.asarray(x) for x in m.solve_info()[:3]]
     stats = (m.get_option("stat_pipelined_launches"), m.get_option("stat_sensor_steps"))
     m.close()
     return out, stats
@@ -285,7 +240,7 @@ def test_the_gates_read_the_measurement(pkg, skidpad):
         if lib:
             m.set_sensors(sets, idx, seed=NOISE_SEED)
         x0 = [np.asarray(a)[[slow, fast]].copy() for a in list(m.solution()) + list(m.solve_info())]
-        r = rollout(m, "node", steps, measured=lib)
+        r = rollout(m, "node", steps, DT, measured=lib)
         seen = r["measured"] if lib else r["state"]                                                        # what the gate read: on the intended side of 1 m/s at every step
         assert (np.all(seen[:, slow, 3] < 1.0) and np.all(seen[:, fast, 3] >= 1.0)) if lib else (np.all(seen[:, slow, 3] >= 1.0) and np.all(seen[:, fast, 3] < 1.0))
         if lib:
@@ -306,22 +261,6 @@ def test_the_gates_read_the_measurement(pkg, skidpad):
 
 
 # ---- 7: the summaries describe the truth -----------------------------------------------------------------------------------------------------------------------------
-def narrowed(pkg, traj, half=0.25):
-    d = traj.data.copy()
-    d[10] = half; d[11] = -half
-    return pkg.TrajectoryTube(*d)
-
-
-def numpy_summary(orc, qh):
-    K, B = qh.shape[:2]
-    s = np.zeros((K, B)); e = np.zeros((K, B))
-    for k in range(K):
-        for b in range(B):
-            s[k, b], e[k, b] = orc.path_coordinates(qh[k, b, 0], qh[k, b, 1])[:2]
-    eL, eR = plant_numpy.tube_edges(orc.traj, s)
-    return plant_numpy.tracking_summary(s, e, qh[..., 3], qh[..., 4], qh[..., 5], eL, eR, 0), s, e
-
-
 @pytest.mark.parametrize("kind,precision", [("simulate", "f64"), ("simulate", "f32"), ("node", "f64")])
 def test_the_summaries_describe_the_truth(pkg, oracle_mod, skidpad, kind, precision):
     B, steps = 70, 12
@@ -331,19 +270,19 @@ def test_the_summaries_describe_the_truth(pkg, oracle_mod, skidpad, kind, precis
     orc = make_oracle(oracle_mod, tube if precision == "f64" else pkg.TrajectoryTube(*tube.data.astype(np.float32).astype(np.float64)))
     m = make(pkg, tube, B, precision=precision)
     m.set_option("tracking_summary", 1)
-    start(pkg, m, tube, B, others=kind != "simulate")
+    start(m, inputs(pkg, tube, B), others=kind != "simulate")
     m.set_sensors(SETS, idx, seed=NOISE_SEED, streams=stream_ids(B))
-    a = rollout(m, kind, 5, measured=True); b = rollout(m, kind, 7, measured=True)
-    r = join(a, b)
+    a = rollout(m, kind, 5, DT, measured=True); b = rollout(m, kind, 7, DT, measured=True)
+    r = join([a, b])
     sm, n, fx = m.tracking_summary()
-    (wsm, wn, wfx, margin), _, _ = numpy_summary(orc, r["state"])
+    (wsm, wn, wfx, margin), _, _ = numpy_summary([orc], None, r["state"])
     assert np.array_equal(n, wn) and np.all(n == steps)
     err = rel(sm, wsm)
     print(f"{kind} {precision}: tracking summary vs numpy on the TRUE history: {err.max():.2e} (bar {bar:g})")
     assert err.max() < bar, (err.max(axis=0), bar)
     decided = margin > 1e-6
     assert np.mean(~decided) <= 1 / 8 and np.array_equal(fx[decided], wfx[decided])
-    (msm, _, _, _), ms, me = numpy_summary(orc, r["measured"])
+    (msm, _, _, _), ms, me = numpy_summary([orc], None, r["measured"])
     off = rel(sm, msm).max(axis=1)
     share = float(np.mean(off[idx != 0] > 100 * bar))
     print(f"{kind} {precision}: the summary of the MEASURED history is off by > 100 bars on {share:.0%} of the instances of sets 2-4")
@@ -352,7 +291,7 @@ def test_the_summaries_describe_the_truth(pkg, oracle_mod, skidpad, kind, precis
     # NodeIO::sep, which node_io() points at the handle's sep buffer, the one path_coordinates() reads (a node_step_ here would not do: the one-shot call never reads the library)
     sep = m.path_coordinates(); s_dev, e_dev = sep[:, 0], sep[:, 1]
     assert rel(s_dev, ms[-1]).max() < max(bar, 1e-7) and np.abs(e_dev - me[-1]).max() < (1e-7 if precision == "f64" else 1e-3)
-    (_, ts_, te) = numpy_summary(orc, r["state"][-1:])
+    (_, ts_, te) = numpy_summary([orc], None, r["state"][-1:])
     assert np.mean(np.abs(e_dev - te[0])[idx != 0] > 1e-3) >= 0.8
     m.close()
 
@@ -365,11 +304,11 @@ def test_contract(pkg, skidpad):
 
     def fresh():
         m = make(pkg, skidpad, cap)
-        start(pkg, m, skidpad, B, others=True)
+        start(m, inputs(pkg, skidpad, B), others=True)
         return m
     twin = fresh()
     twin.set_sensors(SETS, idx, seed=NOISE_SEED, streams=ids)
-    want = rollout(twin, "simulate", 4, measured=True)
+    want = rollout(twin, "simulate", 4, DT, measured=True)
     twin.close()
     m = fresh()
     with pytest.raises(pkg.PigeonError):
@@ -414,19 +353,19 @@ def test_contract(pkg, skidpad):
     for args in ((0, 1, 0), (0, 1, cap + 1), (-1, 1, B), (0, 0, B)):
         rejected(m.lib.pg_sensor_draws(m.h, *args, z.ctypes.data_as(C.POINTER(C.c_double))))
     # ... and the histories after all those refusals are the twin's, bit for bit (seed and streams included)
-    got = rollout(m, "simulate", 4, measured=True)
-    for k in ("state", "control", "final", "measured"):
+    got = rollout(m, "simulate", 4, DT, measured=True)
+    for k in ("state", "control", "final_state", "measured"):
         assert np.array_equal(got[k], want[k]), k
     # pg_set_inputs restarts the sequence: the same four steps again, the same bits; another seed, other bits
-    m.reset(); start(pkg, m, skidpad, B, others=True)
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
     with pytest.raises(pkg.PigeonError):
         m.measured_state()                                   # forgotten with the inputs
-    again = rollout(m, "simulate", 4, measured=True)
-    for k in ("state", "control", "final", "measured"):
+    again = rollout(m, "simulate", 4, DT, measured=True)
+    for k in ("state", "control", "final_state", "measured"):
         assert np.array_equal(again[k], want[k]), k
-    m.reset(); start(pkg, m, skidpad, B, others=True)
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
     m.set_sensor_seed(NOISE_SEED + 1, ids)
-    other = rollout(m, "simulate", 4, measured=True)
+    other = rollout(m, "simulate", 4, DT, measured=True)
     assert np.array_equal(other["state"][0], want["state"][0]) and not np.array_equal(other["measured"][0], want["measured"][0])
     assert np.array_equal(other["measured"][:, idx == 0], other["state"][:, idx == 0])
     # installing a library drops the index, keeps seed and streams; clearing restores the no-library launches
@@ -435,8 +374,8 @@ def test_contract(pkg, skidpad):
     assert np.all(m.sensors()[1] == -1)
     rollouts_refuse()
     assert m.lib.pg_set_sensor_index(m.h, B, i32(idx)) == 0
-    m.reset(); start(pkg, m, skidpad, B, others=True)
-    third = rollout(m, "simulate", 4, measured=True)
+    m.reset(); start(m, inputs(pkg, skidpad, B), others=True)
+    third = rollout(m, "simulate", 4, DT, measured=True)
     assert np.array_equal(third["measured"], want["measured"])
     m.clear_sensors()
     assert m.sensors()[0] == [] and m.lib.pg_set_sensor_index(m.h, B, i32(idx)) == -2
@@ -466,7 +405,7 @@ def test_installing_a_library_between_rollouts_resets_nothing(pkg, skidpad):
     def run(between):
         m = make(pkg, skidpad, B)
         m.set_hji_cache(*grid)
-        st = start(pkg, m, skidpad, B, others=True)
+        st = start(m, inputs(pkg, skidpad, B), others=True)
         m.set_sensors(SETS, idx, seed=NOISE_SEED, streams=ids)
         m.simulate_safety_(4, DT, use_HJI_policy=True, human="worst")
         if between == "restore":
@@ -502,9 +441,9 @@ def test_large_batch_takes_the_pipelined_launch_under_a_library(pkg, skidpad):
     idx = (np.arange(B) % 4).astype(np.int32)
     ids = stream_ids(B)
     m = make(pkg, skidpad, B, options={"pipe_min": 2341})
-    start(pkg, m, skidpad, B)
+    start(m, inputs(pkg, skidpad, B))
     m.set_sensors(SETS, idx, seed=NOISE_SEED, streams=ids)
-    r = rollout(m, "simulate", steps, measured=True)
+    r = rollout(m, "simulate", steps, DT, measured=True)
     assert m.get_option("stat_pipelined_launches") >= 1 and m.get_option("stat_sensor_steps") == steps
     check_measured(r, "f64", idx, ids, steps)
     assert np.array_equal(m.measured_state(), r["measured"][-1])
