@@ -209,6 +209,65 @@ pg_speed_plan pg_default_speed_plan(void);
 int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in, int32_t n_sets,
                    const pg_speed_plan* sets, const pg_vehicle* vehicles, int32_t install, double* channels_out, pg_speed_plan_stats* stats);
 
+/* Making the path: a library of paths from line, arc and clothoid segments -- the curvature is linear in the arc length inside a segment --, computed on the device in the
+ * layout pg_set_trajectories takes.  The reference generates straight lines only (src/trajectories.jl:46-58) and reads every other path from a file, so the scheme is
+ * build-defined (tests/path_make_numpy.py is its numpy twin).  ALL arithmetic is double in both libraries, every operation rounded on its own (no contraction), and the
+ * result is rounded to the library's element type on store: the fp32 library's output is exactly the fp64 library's rounded to float, and the stats are the same doubles.
+ *   Bounds    (host) b_0 = 0, b_{j+1} = b_j + length_j;  psib_0 = psi0, psib_{j+1} = psib_j + (0.5 (kappa0_j + kappa1_j)) length_j;  total = b_{n_seg}.
+ *   Knots     ds = total / (n_knots - 1);  s_i = i ds for i < n_knots - 1, s_last = total.  Knot i lies in the segment of the largest j with b_j <= s_i (b_j <= s_i < b_{j+1});
+ *             the last knot lies at the end of the last segment.  With u = s_i - b_j (the last knot: u = length of the last segment, what total - b_j is before the
+ *             roundings of the sums -- the heading of a path that ends on an arc then closes to the last bit):  kappa_i = kappa0 + ((kappa1 - kappa0) u) / length;
+ *             psi_i = psi(j, u) = psib_j + u (kappa0 + ((0.5 (kappa1 - kappa0)) u) / length);  the edges as kappa;  t_i = s_i / V_ref, V_i = V_ref, A_i = 0.
+ *             s, psi, kappa, the edges, t, V and A therefore reproduce the twin bit for bit.
+ *   Position  dE/ds = -sin psi, dN/ds = cos psi (the committed paths' convention).  The interval [s_i, s_{i+1}] starts as the piece (j, u) of knot i; while b_{j+1} <
+ *             s_{i+1} and a segment follows, the piece [u, length_j] of segment j is closed and the next starts at (j + 1, 0); the last piece is [u, s_{i+1} - b_j].
+ *             A piece [ua, ub] of segment j: half = 0.5 (ub - ua), mid = 0.5 (ua + ub), nodes u_k = mid + half x_k over the four Gauss-Legendre points in ascending
+ *             order (x = -+0.8611363115940526 with weight 0.3478548451374538, -+0.3399810435848563 with 0.6521451548625461);  dE = -(half sum_k w_k sin psi(j, u_k)),
+ *             dN = half sum_k w_k cos psi(j, u_k), the sums from 0 in the order of the nodes.  The pieces of an interval are added in order from 0.
+ *   Prefix    With c = ceil((n_knots - 1) / 256), block b holds the intervals b c .. b c + c - 1.  r_i (i >= 1) is the sum, in order from 0, of the increments of the
+ *             intervals of block (i - 1) / c up to and including interval i - 1; T_b is the sum over all of block b (0 for an empty block).  The 256 totals are combined
+ *             in groups of 64: inside a group by doubling -- for d = 1, 2, 4, 8, 16, 32 in turn, every T_b with b mod 64 >= d becomes T_b + T_{b-d}, all b of a step
+ *             from the values before it --, which leaves the inclusive sums I_b;  G_0 = 0, G_{g+1} = G_g + I_{64 g + 63};  P_b = G_{b / 64} + (I_{b-1} if b mod 64 > 0,
+ *             else 0).  E_0 = E0 and E_i = E0 + (P_{(i-1)/c} + r_i); N alike.  The order depends on the path's own n_knots alone: not on n_path, on the path's place
+ *             in the library or on Lmax.  Against a serial sum the difference stays within 4 (n_knots + 64) 2^-53 total.
+ * The accuracy is that of the 4-point rule per piece: against the Fresnel integrals 4.5e-14 m on a 20 m clothoid to 0.2 1/m at ds 1 m and 1.2e-11 m at ds 2 m (tests/test_path_make_host.py).
+ * No repair of a path that does not close: closure_pos / closure_psi report the gap. */
+typedef struct pg_path_segment {
+    double length;          /* > 0, finite */
+    double kappa0, kappa1;  /* curvature at the segment's start and end, linear in between: line (0, 0), arc (k, k), clothoid (k0 != k1); finite, either sign */
+    double edge_L0, edge_L1;   /* tube edges at start / end, linear in between; finite, edge_L > edge_R at both ends */
+    double edge_R0, edge_R1;
+    double reserved;        /* 0 */
+} pg_path_segment;          /* 64 bytes */
+typedef struct pg_path_spec {
+    double E0, N0, psi0;    /* pose of knot 0; finite */
+    double V_ref;           /* > 0, finite: fills V = V_ref, A = 0, t = s / V_ref (the committed paths are constant-speed profiles of this kind) */
+    int32_t seg0, n_seg;    /* this path's segments: segments[seg0 .. seg0 + n_seg), n_seg >= 1, inside [0, n_seg_total) */
+    int32_t n_knots;        /* 2 <= n_knots <= Lmax; a closed path needs >= 3 */
+    int32_t closed;         /* the caller's statement, passed through to closed_out (what pg_plan_speeds takes as closed[]) */
+} pg_path_spec;             /* 48 bytes */
+typedef struct pg_path_stats {   /* one per path; computed in double in both libraries */
+    double length;          /* sum of the segment lengths = s of the last knot */
+    double turn;            /* psi(last knot) - psi0 */
+    double closure_pos;     /* hypot(E, N of the last knot - E, N of knot 0) */
+    double closure_psi;     /* turn reduced to (-pi, pi] (the IEEE remainder by 6.283185307179586, -pi mapped to +pi) */
+    double kappa_abs_max;   /* over the knots */
+    double ds;              /* length / (n_knots - 1) */
+} pg_path_stats;            /* 48 bytes */
+/* { 1, 0, 0, 4, 4, -4, -4, 0 }: a 1 m line with the edge defaults of src/trajectories.jl:43-44 */
+pg_path_segment pg_default_path_segment(void);
+/* Output [n_path][10][Lmax] in the layout and channel order of pg_set_trajectories (t, s, V, A, E, N, psi, kappa, edge_L, edge_R), 0 at and past n_knots, as
+ * pg_plan_speeds writes its tails.  L_out [n_path] (= n_knots), closed_out [n_path] (= closed), channels_out and stats [n_path] may each be NULL.  Segment ranges of
+ * different paths may overlap (one oval at several poses).  install != 0 hands the device buffer to the handle, with no host round trip: the handle is then exactly as
+ * after pg_set_trajectories(h, n_path, Lmax, L_out, channels_out) -- the fp64 end times (total / V_ref as the library's element type holds it), the dropped index, the
+ * PG_ERR_STATE of the phase calls until an index is set when n_path > 1.  Synchronous.  A handle that never calls this launches what it launched before.
+ * PG_ERR_INVALID, everything validated before the first allocation (the handle and its installed library are left unchanged): a null specs or segments; n_path < 1;
+ * n_seg_total < 1; Lmax < 2; n_knots outside [2, Lmax]; a closed path of fewer than 3 knots; n_seg < 1 or a segment range outside [0, n_seg_total); a length that is not
+ * finite and > 0; a non-finite kappa, edge or pose; edge_L <= edge_R at either end of a segment; V_ref not finite or <= 0; reserved != 0 (segments no path refers to are
+ * not looked at); knots so dense that s does not increase strictly in the library's element type; n_path * 10 * Lmax elements beyond the allocation arithmetic. */
+int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32_t n_seg_total, const pg_path_segment* segments, int32_t Lmax,
+                  int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_path_stats* stats);
+
 /* control_params of one controller per instance (src/coupled_lat_long.jl:42-60, src/decoupled_lat_long.jl:32-50): a library of control-parameter sets and a per-instance
  * selection, the counterpart of pg_set_trajectories / pg_set_trajectory_index for the controller's tuning -- a tuning sweep or robustness study (the same starts and paths
  * under many weightings, speed bounds and steering-rate limits) runs as ONE batch.  With no library the handle behaves as pg_config.control says.  A library of ONE set

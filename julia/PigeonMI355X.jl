@@ -546,6 +546,52 @@ end
 "{ 1, 30, 1, NaN, NaN, +Inf, -Inf, +Inf } as the library states them (pg_default_speed_plan)"
 default_speed_plan(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_speed_plan), PgSpeedPlan, ())
 
+# Making the path (pg_make_paths): a library of paths from line, arc and clothoid segments on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_path_segment (64 bytes): length, the curvature at the start and the end (linear in between: line, arc, clothoid), the tube edges at the start and the end, a reserved 0"
+struct PgPathSegment
+    length::Float64
+    kappa0::Float64
+    kappa1::Float64
+    edge_L0::Float64
+    edge_L1::Float64
+    edge_R0::Float64
+    edge_R1::Float64
+    reserved::Float64
+end
+PgPathSegment(; length=1.0, kappa0=0.0, kappa1=0.0, edge_L0=4.0, edge_L1=4.0, edge_R0=-4.0, edge_R1=-4.0) =
+    PgPathSegment(Float64(length), Float64(kappa0), Float64(kappa1), Float64(edge_L0), Float64(edge_L1), Float64(edge_R0), Float64(edge_R1), 0.0)
+"pg_path_spec (48 bytes): the pose of knot 0, the constant speed, the path's segments segments[seg0 + 1 : seg0 + n_seg] (seg0 is 0-based, as in C), its knot count, the caller's `closed`"
+struct PgPathSpec
+    E0::Float64
+    N0::Float64
+    psi0::Float64
+    V_ref::Float64
+    seg0::Int32
+    n_seg::Int32
+    n_knots::Int32
+    closed::Int32
+end
+"pg_path_stats (48 bytes), one per path"
+struct PgPathStats
+    length::Float64
+    turn::Float64
+    closure_pos::Float64
+    closure_psi::Float64
+    kappa_abs_max::Float64
+    ds::Float64
+end
+"specs and segments as pg_make_paths takes them -> (channels_out [Lmax, 10, n_path] (column-major: the C layout [n_path][10][Lmax]), L, closed, stats); install = true leaves the handle as pg_set_trajectories with channels_out would"
+function make_paths!(mpc::BatchedTrajectoryTrackingMPC, specs::Vector{PgPathSpec}, segments::Vector{PgPathSegment}; Lmax::Integer=maximum(s.n_knots for s in specs), install::Bool=false)
+    (sizeof(PgPathSegment), sizeof(PgPathSpec), sizeof(PgPathStats)) == (64, 48, 48) || error("PigeonMI355X.jl: PgPathSegment / PgPathSpec / PgPathStats differ from include/pigeon_mpc.h")
+    n = length(specs)
+    out = zeros(Float64, Lmax, 10, n); L = zeros(Int32, n); closed = zeros(Int32, n); stats = Vector{PgPathStats}(undef, n)
+    check(mpc, ccall(sym(mpc, :pg_make_paths), Cint, (Ptr{Cvoid}, Int32, Ptr{PgPathSpec}, Int32, Ptr{PgPathSegment}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{PgPathStats}),
+                     mpc.handle, Int32(n), specs, Int32(length(segments)), segments, Int32(Lmax), Int32(install), L, closed, out, stats), "pg_make_paths")
+    out, L, closed, stats
+end
+"{ 1, 0, 0, 4, 4, -4, -4, 0 } as the library states them (pg_default_path_segment)"
+default_path_segment(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_path_segment), PgPathSegment, ())
+
 "mpc.solved = false (src/ros_integration.jl:34,41,147)"
 reset!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_reset), Cint, (Ptr{Cvoid}, Ptr{UInt8}), mpc.handle, C_NULL), "pg_reset")
 

@@ -1094,6 +1094,132 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
     return PG_OK;
 }
 
+// ---- pg_make_paths: a path library from line, arc and clothoid segments (pg_path_make.hip).  One launch, one workgroup per path; no loop on the host ----
+static_assert(sizeof(pg_path_segment) == 64 && sizeof(pg_path_spec) == 48 && sizeof(pg_path_stats) == 48, "the sizes include/pigeon_mpc.h states");
+pg_path_segment pg_default_path_segment(void) {
+    pg_path_segment s; s.length = 1.0; s.kappa0 = 0.0; s.kappa1 = 0.0; s.edge_L0 = 4.0; s.edge_L1 = 4.0; s.edge_R0 = -4.0; s.edge_R1 = -4.0; s.reserved = 0.0;
+    return s;
+}
+static const char* path_segment_problem(const pg_path_segment& g) {
+    if (!(std::isfinite(g.length) && g.length > 0.0)) return "a segment needs a finite length > 0";
+    for (double v : {g.kappa0, g.kappa1, g.edge_L0, g.edge_L1, g.edge_R0, g.edge_R1}) if (!std::isfinite(v)) return "a curvature or an edge of a segment is not finite";
+    if (!(g.edge_L0 > g.edge_R0 && g.edge_L1 > g.edge_R1)) return "a segment needs edge_L > edge_R at both ends";
+    if (g.reserved != 0.0) return "reserved of a segment must be 0";
+    return nullptr;
+}
+// the segment bounds of one path as the scheme states them: b_0 = 0, b_{j+1} = b_j + length_j; psib_0 = psi0, psib_{j+1} = psib_j + 0.5 (kappa0_j + kappa1_j) length_j,
+// every operation rounded once.  Returns total = b_{n_seg}
+static double path_bounds(const pg_path_spec& p, const pg_path_segment* seg, PathSeg* out) {
+#pragma clang fp contract(off)
+    double b = 0.0, psib = p.psi0;
+    for (int j = 0; j < p.n_seg; j++) {
+        const pg_path_segment& g = seg[p.seg0 + j];
+        PathSeg& o = out[j];
+        o.b = b; o.psib = psib; o.length = g.length; o.kappa0 = g.kappa0; o.kappa1 = g.kappa1; o.eL0 = g.edge_L0; o.eL1 = g.edge_L1; o.eR0 = g.edge_R0; o.eR1 = g.edge_R1; o.pad = 0.0;
+        const double ksum = g.kappa0 + g.kappa1;
+        const double kmid = 0.5 * ksum;
+        const double dpsi = kmid * g.length;
+        b = b + g.length; psib = psib + dpsi;
+    }
+    return b;
+}
+// s_i = i (total / (n_knots - 1)), s_last = total, as the library's element type holds them: do they increase strictly?  Two neighbours are ds apart before the two
+// roundings (to double, to real), each of which moves a value by at most half an ulp at `total`: with ds >= 4 eps total they cannot meet, and only denser knots are walked
+static bool path_s_increases(double total, int n_knots) {
+#pragma clang fp contract(off)
+    const double ds = total / (double)(n_knots - 1);
+    if (!(std::isfinite(total) && ds > 0.0)) return false;
+    const double eps = sizeof(real) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
+    if (ds >= 4.0 * eps * total) return true;
+    real prev = (real)0.0;
+    for (int i = 1; i < n_knots; i++) {
+        const real s = (real)(i == n_knots - 1 ? total : (double)i * ds);
+        if (!(s > prev)) return false;
+        prev = s;
+    }
+    return true;
+}
+namespace {
+struct PathMakeBufs {                                   // device memory of one call: released on every way out, except what an install hands to the handle
+    real* out = nullptr; int* len = nullptr; PathSpec* specs = nullptr; PathSeg* segs = nullptr; double* scratch = nullptr; pg_path_stats* stats = nullptr;
+    ~PathMakeBufs() { for (void* p : {(void*)out, (void*)len, (void*)specs, (void*)segs, (void*)scratch, (void*)stats}) if (p) (void)hipFree(p); }
+};
+}  // namespace
+int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32_t n_seg_total, const pg_path_segment* segments, int32_t Lmax,
+                  int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_path_stats* stats) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, specs && segments, "pg_make_paths: null argument");
+    REQUIRE(h, n_path >= 1 && n_seg_total >= 1 && Lmax >= 2, "pg_make_paths: need n_path >= 1, n_seg_total >= 1 and Lmax >= 2");
+    // (the largest buffer of the call holds n_path * 10 * Lmax doubles: its size in bytes has to fit the size arithmetic, with room for the sums around it)
+    REQUIRE(h, (double)n_path * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0, "pg_make_paths: n_path * 10 * Lmax elements are more than the allocation arithmetic holds");
+    size_t n_rows = 0;
+    for (int k = 0; k < n_path; k++) {
+        const pg_path_spec& p = specs[k];
+        REQUIRE(h, p.n_knots >= 2 && p.n_knots <= Lmax, "pg_make_paths: every path needs 2 <= n_knots <= Lmax");
+        REQUIRE(h, !p.closed || p.n_knots >= 3, "pg_make_paths: a closed path needs >= 3 knots");
+        REQUIRE(h, p.n_seg >= 1 && p.seg0 >= 0 && p.seg0 < n_seg_total && p.n_seg <= n_seg_total - p.seg0, "pg_make_paths: the segments of a path must lie inside [0, n_seg_total)");
+        REQUIRE(h, std::isfinite(p.E0) && std::isfinite(p.N0) && std::isfinite(p.psi0), "pg_make_paths: the pose of a path is not finite");
+        REQUIRE(h, std::isfinite(p.V_ref) && p.V_ref > 0.0, "pg_make_paths: a path needs a finite V_ref > 0");
+        for (int j = 0; j < p.n_seg; j++) { const char* why = path_segment_problem(segments[p.seg0 + j]); REQUIRE(h, !why, std::string("pg_make_paths: ") + (why ? why : "")); }
+        n_rows += (size_t)p.n_seg;
+    }
+    std::vector<PathSeg> rows(n_rows);
+    std::vector<PathSpec> recs((size_t)n_path);
+    std::vector<int> lens((size_t)n_path);
+    {
+        size_t at = 0;
+        for (int k = 0; k < n_path; k++) {
+            const pg_path_spec& p = specs[k];
+            REQUIRE(h, at + (size_t)p.n_seg <= 2147483647u, "pg_make_paths: the segments of all paths together must fit 31 bits");
+            PathSpec& r = recs[(size_t)k];
+            r.E0 = p.E0; r.N0 = p.N0; r.psi0 = p.psi0; r.V_ref = p.V_ref; r.seg0 = (int)at; r.n_seg = p.n_seg; r.n_knots = p.n_knots; r.pad = 0;
+            r.total = path_bounds(p, segments, rows.data() + at);
+            REQUIRE(h, path_s_increases(r.total, p.n_knots), "pg_make_paths: the knots are so dense that s does not increase strictly in the library's element type");
+            lens[(size_t)k] = p.n_knots;
+            at += (size_t)p.n_seg;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t stride = (size_t)10 * Lmax, total = (size_t)n_path * stride;
+    PathMakeBufs D;
+    HIPCHK(h, hipMalloc((void**)&D.out, total * sizeof(real)));
+    HIPCHK(h, hipMalloc((void**)&D.len, (size_t)n_path * sizeof(int)));
+    HIPCHK(h, hipMalloc((void**)&D.specs, (size_t)n_path * sizeof(PathSpec)));
+    HIPCHK(h, hipMalloc((void**)&D.segs, n_rows * sizeof(PathSeg)));
+    HIPCHK(h, hipMalloc((void**)&D.scratch, (size_t)n_path * 2 * (size_t)Lmax * sizeof(double)));
+    HIPCHK(h, hipMalloc((void**)&D.stats, (size_t)n_path * sizeof(pg_path_stats)));
+    // (plain copies, as install_trajectories uses: the host vectors are consumed when each returns, on every way out)
+    HIPCHK(h, hipMemcpy(D.len, lens.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(D.specs, recs.data(), (size_t)n_path * sizeof(PathSpec), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(D.segs, rows.data(), n_rows * sizeof(PathSeg), hipMemcpyHostToDevice));
+    PathMakeArgs A; A.Lmax = Lmax; A.specs = D.specs; A.segs = D.segs; A.out = D.out; A.scratch = D.scratch; A.stats = D.stats;
+    hipLaunchKernelGGL(k_path_make, dim3((unsigned)n_path), dim3(PM_THREADS), 0, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_path_stats> st((size_t)n_path);
+    HIPCHK(h, hipMemcpyAsync(st.data(), D.stats, (size_t)n_path * sizeof(pg_path_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    { int rc = down(h, channels_out, D.out, total); if (rc) return rc; }
+    const double pi = 3.141592653589793, two_pi = 6.283185307179586;
+    for (int k = 0; k < n_path; k++) {                        // the turn reduced to (-pi, pi]: the IEEE remainder is exact
+        double r = std::remainder(st[(size_t)k].turn, two_pi);
+        if (r <= -pi) r = r + two_pi;
+        st[(size_t)k].closure_psi = r;
+        if (L_out) L_out[k] = specs[k].n_knots;
+        if (closed_out) closed_out[k] = specs[k].closed;
+    }
+    if (stats) memcpy(stats, st.data(), (size_t)n_path * sizeof(pg_path_stats));
+    if (install) {
+        if (h->d_traj) (void)hipFree(h->d_traj);
+        if (h->d_traj_len) (void)hipFree(h->d_traj_len);
+        h->d_traj = D.out; h->d_traj_len = D.len; D.out = nullptr; D.len = nullptr;
+        std::vector<double> ends((size_t)n_path);
+        for (int k = 0; k < n_path; k++) ends[(size_t)k] = (double)(real)(recs[(size_t)k].total / recs[(size_t)k].V_ref);   // (t of the last knot as stored: what pg_set_trajectories reads from channels_out)
+        adopt_trajectories(h, n_path, Lmax, lens[0], std::move(ends));
+    }
+    return PG_OK;
+}
+
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
 // solver state: nothing is reset ----
 static const char* sensor_set_problem(const pg_sensor& s) {

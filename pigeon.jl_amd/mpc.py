@@ -12,13 +12,14 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan, path_segment as _default_path_segment
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
 
 SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
+PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
 
 
 def is_solved(status):
@@ -245,6 +246,92 @@ class BatchedTrajectoryTrackingMPC:
             self.trajectory = tubes[0]
         stats = np.frombuffer(st, dtype=SPEED_PLAN_STATS_DTYPE).copy()
         return tubes, stats
+
+    # ---- making the path (pg_make_paths): a library of paths from line, arc and clothoid segments, computed on the device ----
+    @classmethod
+    def pack_path_specs(cls, paths, n_knots, V_ref=6.0, pose=(0.0, 0.0, 0.0), closed=False):
+        """paths: a list of segment lists (vehicles.path_segment(**overrides) dicts, as the builders of vehicles.py return them; or pg_path_segment structures); n_knots,
+        V_ref, closed: one value for every path or one per path; pose: one (E0, N0, psi0) or one per path -> (specs, segments): ctypes arrays of pg_path_spec [n_path] and
+        pg_path_segment [all segments, path after path].  Raises ValueError for what the library refuses with PG_ERR_INVALID (include/pigeon_mpc.h)."""
+        paths = [list(p) for p in paths]
+        if not paths:
+            raise ValueError("make_paths: at least one path")
+        n = len(paths)
+
+        def per_path(x, what, width=None):
+            a = np.asarray(x, dtype=np.float64)
+            if a.shape == (() if width is None else (width,)):
+                a = np.broadcast_to(a, (n,) + a.shape)
+            if a.shape != ((n,) if width is None else (n, width)):
+                raise ValueError(f"make_paths: {what} is one value for every path or one per path ({n} paths)")
+            return a
+
+        knots, V, cl, poses = per_path(n_knots, "n_knots"), per_path(V_ref, "V_ref"), per_path(closed, "closed"), per_path(pose, "pose", 3)
+
+        def fill(rec, g):
+            full = _default_path_segment(**g)
+            for name, _ in _lib.pg_path_segment._fields_:
+                setattr(rec, name, float(full[name]))
+        for k, p in enumerate(paths):
+            if not p:
+                raise ValueError(f"make_paths: path {k} has no segment")
+        segs = cls._pack(_lib.pg_path_segment, [g for p in paths for g in p], fill)
+        for j, g in enumerate(segs):
+            if not (math.isfinite(g.length) and g.length > 0):
+                raise ValueError(f"make_paths: segment {j} needs a finite length > 0")
+            if not all(math.isfinite(v) for v in (g.kappa0, g.kappa1, g.edge_L0, g.edge_L1, g.edge_R0, g.edge_R1)):
+                raise ValueError(f"make_paths: segment {j} has a non-finite curvature or edge")
+            if not (g.edge_L0 > g.edge_R0 and g.edge_L1 > g.edge_R1):
+                raise ValueError(f"make_paths: segment {j} needs edge_L > edge_R at both ends")
+            if g.reserved != 0:
+                raise ValueError(f"make_paths: reserved of segment {j} must be 0")
+        specs = (_lib.pg_path_spec * n)()
+        at = 0
+        for k, p in enumerate(paths):
+            if not np.isfinite(poses[k]).all():
+                raise ValueError(f"make_paths: the pose of path {k} is not finite")
+            if not (math.isfinite(V[k]) and V[k] > 0):
+                raise ValueError(f"make_paths: path {k} needs a finite V_ref > 0")
+            if not (knots[k] == int(knots[k]) and 2 <= knots[k] <= 2**31 - 1):
+                raise ValueError(f"make_paths: path {k} needs an integer n_knots >= 2")
+            if cl[k] and knots[k] < 3:
+                raise ValueError(f"make_paths: path {k} is closed and has {int(knots[k])} knots (a closed path needs 3)")
+            s = specs[k]
+            s.E0, s.N0, s.psi0, s.V_ref = (float(x) for x in (*poses[k], V[k]))
+            s.seg0, s.n_seg, s.n_knots, s.closed = at, len(p), int(knots[k]), int(bool(cl[k]))
+            at += len(p)
+        return specs, segs
+
+    def make_paths(self, paths, ds=None, n_knots=None, V_ref=6.0, pose=(0.0, 0.0, 0.0), closed=False, install=False):
+        """A path library on the device (pg_make_paths; the scheme is stated in include/pigeon_mpc.h): paths = a list of segment lists (vehicles.line_segments,
+        circle_segments, oval_segments, lane_change_segments, or path_segment dicts of your own).  Give the knots as n_knots (one value or one per path) or as a spacing
+        ds (n_knots = max(2, ceil(total / ds) + 1) per path).  V_ref fills the constant-speed profile (V = V_ref, A = 0, t = s / V_ref), pose = (E0, N0, psi0) of knot 0,
+        closed = the caller's statement for plan_speeds (each one value or one per path).  Returns (tubes, stats): the TrajectoryTubes and a structured array with the
+        fields of pg_path_stats (length, turn, closure_pos, closure_psi, kappa_abs_max, ds).  install=True makes them the handle's trajectory library (as
+        set_trajectories(tubes) would, without the host round trip; select with set_trajectory_index)."""
+        paths = [list(p) for p in paths]
+        if (ds is None) == (n_knots is None):
+            raise ValueError("make_paths: give ds or n_knots (one of them)")
+        if n_knots is None:
+            if not (np.all(np.isfinite(ds)) and np.all(np.asarray(ds) > 0)):
+                raise ValueError("make_paths: ds must be finite and > 0")
+            dss = np.broadcast_to(np.asarray(ds, dtype=np.float64), (len(paths),))
+            totals = [sum(float(g["length"] if isinstance(g, dict) else g.length) for g in p) for p in paths]
+            if not np.all(np.isfinite(totals)):
+                raise ValueError("make_paths: a segment's length is not finite")
+            n_knots = [max(2, math.ceil(t / d) + 1) for t, d in zip(totals, dss)]
+        specs, segs = self.pack_path_specs(paths, n_knots, V_ref=V_ref, pose=pose, closed=closed)
+        n = len(specs)
+        Lmax = max(s.n_knots for s in specs)
+        out = np.zeros((n, 10, Lmax))
+        L = np.zeros(n, dtype=np.int32)
+        st = (_lib.pg_path_stats * n)()
+        self._chk(self.lib.pg_make_paths(self.h, n, specs, len(segs), segs, Lmax, int(bool(install)), _p(L, c_i32p), None, _p(out), st), "pg_make_paths")
+        tubes = self.tubes_from_channels(out, L)
+        if install:
+            self.trajectories = tubes
+            self.trajectory = tubes[0]
+        return tubes, np.frombuffer(st, dtype=PATH_STATS_DTYPE).copy()
 
     # ---- the per-instance libraries share one protocol (pg_set_<name>_sets / pg_set_<name>_index / pg_clear_<name>_sets / pg_get_<name>_sets): the four routines below ----
     @staticmethod

@@ -163,3 +163,109 @@ def speed_plan(**overrides):
             raise KeyError(f"{k} is not a field of a speed plan: {SPEED_PLAN_FIELDS}")
         p[k] = float(v)
     return p
+
+
+PATH_SEGMENT_FIELDS = ("length", "kappa0", "kappa1", "edge_L0", "edge_L1", "edge_R0", "edge_R1", "reserved")
+
+
+def path_segment(**overrides):
+    """One segment for make_paths (pg_path_segment).  path_segment() is the library's default (pg_default_path_segment): a 1 m line with the edges at +4 / -4 m
+    (trajectories.jl:43-44); path_segment(length=15.0, kappa1=1 / 14.5) is a clothoid from a straight into a left turn of radius 14.5 m.  The curvature and the edges are
+    linear in the arc length between the two ends.  edge_L=3.0 / edge_R=-2.0 set both ends of an edge at once.  Build-defined: the reference generates straight lines only."""
+    g = dict(length=1.0, kappa0=0.0, kappa1=0.0, edge_L0=4.0, edge_L1=4.0, edge_R0=-4.0, edge_R1=-4.0, reserved=0.0)
+    for k, v in overrides.items():
+        if k in ("edge_L", "edge_R"):
+            g[k + "0"] = g[k + "1"] = float(v)
+        elif k in g:
+            g[k] = float(v)
+        else:
+            raise KeyError(f"{k} is not a field of a path segment: {PATH_SEGMENT_FIELDS} (edge_L / edge_R set both ends)")
+    return g
+
+
+def line_segments(length, **edges):
+    """A straight of `length` m: one segment.  **edges: the edge fields of path_segment, applied to every segment (as in the other builders)."""
+    return [path_segment(length=length, **edges)]
+
+
+def circle_segments(radius, turns=1, **edges):
+    """`turns` laps of a circle: one arc of curvature 1 / radius (radius < 0: a right turn) and length 2 pi |radius| turns."""
+    if radius == 0 or not turns > 0:
+        raise ValueError("circle_segments: radius != 0 and turns > 0")
+    k = 1.0 / float(radius)
+    return [path_segment(length=2.0 * math.pi * abs(float(radius)) * turns, kappa0=k, kappa1=k, **edges)]
+
+
+def oval_segments(straight, radius, clothoid, **edges):
+    """An oval from the start of a straight, once around (left turns; radius < 0: right turns): two halves of line, clothoid in, arc, clothoid out.  The clothoids take
+    clothoid / |radius| of each half turn, the arc the angle pi - clothoid / |radius| that is left -- it has to be positive.  clothoid = 0 drops the clothoids.  The path
+    closes by symmetry; make_paths reports what the arithmetic leaves (closure_pos, closure_psi)."""
+    straight, radius, clothoid = float(straight), float(radius), float(clothoid)
+    if not (straight > 0 and radius != 0 and clothoid >= 0):
+        raise ValueError("oval_segments: straight > 0, radius != 0, clothoid >= 0")
+    r = abs(radius)
+    angle = math.pi - clothoid / r
+    if not angle > 0:
+        raise ValueError(f"oval_segments: clothoids of {clothoid} m take the whole half turn at radius {r} m (the arc's angle pi - clothoid / radius = {angle} must be positive)")
+    k = 1.0 / radius
+    arc = angle * r
+    for _ in range(4):                                       # 1 / radius is rounded: take the neighbour of angle * radius at which |k| * length rounds to the angle, if one does
+        got = abs(k) * arc
+        if got == angle:
+            break
+        arc = math.nextafter(arc, math.inf if got < angle else 0.0)
+    else:
+        arc = angle * r
+    half = [path_segment(length=straight, **edges)]
+    if clothoid > 0:
+        half.append(path_segment(length=clothoid, kappa0=0.0, kappa1=k, **edges))
+    half.append(path_segment(length=arc, kappa0=k, kappa1=k, **edges))
+    if clothoid > 0:
+        half.append(path_segment(length=clothoid, kappa0=k, kappa1=0.0, **edges))
+    return [dict(g) for g in half + half]
+
+
+LANE_CHANGE_TOL = 1e-11      # m: what lane_change_segments leaves between the offset asked for and the one its segments integrate to
+
+
+def _lateral_shift(segs, pieces=16):
+    """the shift to the left of a path that starts with psi = 0, over its segments: the integral of sin psi by the 4-point Gauss-Legendre rule of pg_make_paths
+    (include/pigeon_mpc.h) on `pieces` pieces per segment"""
+    X = (-0.8611363115940526, -0.3399810435848563, 0.3399810435848563, 0.8611363115940526)
+    W = (0.3478548451374538, 0.6521451548625461, 0.6521451548625461, 0.3478548451374538)
+    psib, shift = 0.0, 0.0
+    for g in segs:
+        h = g["length"] / pieces
+        for p in range(pieces):
+            for x, w in zip(X, W):
+                u = (p + 0.5 + 0.5 * x) * h
+                shift += 0.5 * h * w * math.sin(psib + u * (g["kappa0"] + 0.5 * (g["kappa1"] - g["kappa0"]) * u / g["length"]))
+        psib += 0.5 * (g["kappa0"] + g["kappa1"]) * g["length"]
+    return shift
+
+
+def lane_change_segments(offset, length, **edges):
+    """A lane change of `offset` m (> 0: to the left, the side of edge_L) over `length` m of arc: four clothoids of length / 4 with the curvature 0 -> k -> 0 -> -k -> 0,
+    so the heading ends where it started.  The peak curvature k is solved by bisection on the path's own integral (_lateral_shift: the quadrature of pg_make_paths) until
+    the shift is within LANE_CHANGE_TOL = 1e-11 m of the offset; the heading peaks at k length / 4, and an offset that would need more than a quarter turn is refused."""
+    offset, length = float(offset), float(length)
+    if not (length > 0 and math.isfinite(offset)):
+        raise ValueError("lane_change_segments: length > 0 and a finite offset")
+    q = length / 4.0
+
+    def segs(k):
+        return [path_segment(length=q, kappa0=a, kappa1=b, **edges) for a, b in ((0.0, k), (k, 0.0), (0.0, -k), (-k, 0.0))]
+
+    if offset == 0:
+        return segs(0.0)
+    sign, want = math.copysign(1.0, offset), abs(offset)
+    lo, hi = 0.0, 2.0 * math.pi / length                     # (the heading peaks at a quarter turn at hi: the shift grows with k up to there)
+    if _lateral_shift(segs(hi)) < want:
+        raise ValueError(f"lane_change_segments: {want} m cannot be reached in {length} m without turning past a quarter turn")
+    for _ in range(200):
+        k = 0.5 * (lo + hi)
+        d = _lateral_shift(segs(k)) - want
+        if abs(d) <= 0.1 * LANE_CHANGE_TOL or k in (lo, hi):
+            break
+        lo, hi = (k, hi) if d < 0 else (lo, k)
+    return segs(sign * k)
