@@ -190,6 +190,8 @@ struct pg_handle {
 #define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(e_); return PG_ERR_HIP; } } while (0)
 #define LAUNCH_CHECK(h) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { (h)->err = std::string("kernel launch: ") + hipGetErrorString(e_); return PG_ERR_HIP; } } while (0)
 #define REQUIRE(h, cond, msg) do { if (!(cond)) { if (h) (h)->err = (msg); return PG_ERR_INVALID; } } while (0)
+// a *_problem check (why: its text, or nullptr when nothing is wrong) refuses with "<who><why>"; `who` carries its own ": "
+#define REQUIRE_NO(h, who, why) do { const char* why_ = (why); if (why_) { (h)->err = std::string(who) + why_; return PG_ERR_INVALID; } } while (0)
 
 static std::string g_create_error;
 
@@ -208,6 +210,26 @@ int SeedStreams::sync(pg_handle* h) {
 // a device buffer of `count` elements that is allocated when it is first needed
 template <class T> static int ensure(pg_handle* h, T*& p, size_t count) {
     if (!p) HIPCHK(h, hipMalloc((void**)&p, count * sizeof(T)));
+    return PG_OK;
+}
+// The device memory of one call (the makers, install_trajectories): alloc() remembers what it allocated, and what the call still holds is freed on every way out.
+// give() is the one way a buffer leaves: to the handle, which owns it from then on (the caller's pointer is nulled: nothing in the call reads the buffer afterwards)
+struct CallBufs {
+    std::vector<void*> held;
+    CallBufs() = default; CallBufs(const CallBufs&) = delete; CallBufs& operator=(const CallBufs&) = delete;
+    ~CallBufs() { for (void* p : held) if (p) (void)hipFree(p); }
+    template <class T> hipError_t alloc(T*& p, size_t count) { p = nullptr; const hipError_t e = hipMalloc((void**)&p, count * sizeof(T)); if (e == hipSuccess) held.push_back(p); return e; }
+    template <class T> T* give(T*& p) { for (void*& q : held) if (q == (void*)p) q = nullptr; T* const out = p; p = nullptr; return out; }
+};
+// The walk over the seven dimensions of an HJI grid, written here only (pg_set_hji_grid, pg_hji_solve; hji_install_nodes reads its result): nodes n, knots nk and, per
+// dimension, the stride of its node index and the offset of its knots.  Refuses in the name of `who` fewer than 2 knots.  fill(): into a device view (HjiView, HjiSolveGrid)
+struct HjiWalk {
+    int dims[7], koff[7]; long stride[7]; size_t n; int nk;
+    template <class Grid> void fill(Grid& G) const { for (int d = 0; d < 7; d++) { G.dims[d] = dims[d]; G.koff[d] = koff[d]; G.stride[d] = stride[d]; } }
+};
+static int hji_walk(pg_handle* h, const char* who, const int32_t dims[7], HjiWalk& W) {
+    W.n = 1; W.nk = 0;
+    for (int d = 0; d < 7; d++) { REQUIRE(h, dims[d] >= 2, std::string(who) + ": every dimension needs >= 2 knots"); W.dims[d] = dims[d]; W.koff[d] = W.nk; W.stride[d] = (long)W.n; W.n *= dims[d]; W.nk += dims[d]; }
     return PG_OK;
 }
 
@@ -731,7 +753,7 @@ template <class Host, class Dev, class Problem, class Fill>
 static int setlib_install(pg_handle* h, const char* who_, SetLib<Host, Dev>& L, int32_t n_sets, const Host* sets, Problem problem, Fill fill, bool on_device = true) {
     const std::string who(who_);
     REQUIRE(h, n_sets >= 1 && sets, who + ": need n_sets >= 1 and the sets");
-    for (int k = 0; k < n_sets; k++) { const char* why = problem(sets[k]); REQUIRE(h, !why, who + ": " + why); }
+    for (int k = 0; k < n_sets; k++) REQUIRE_NO(h, who + ": ", problem(sets[k]));
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
     Dev* d_new = nullptr;
@@ -815,47 +837,51 @@ static int response_call(pg_handle* h, const char* who_, const SetLib<Host, Dev>
     if (index_covers(h, L)) return PG_ERR_STATE;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = S ? S->sync(h) : PG_OK; if (rc) return rc;
-    real* d = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, scratch * sizeof(real)));
+    CallBufs D; real* d = nullptr;
+    HIPCHK(h, D.alloc(d, scratch));
     const real* result = nullptr;
     rc = body(d, result);
     if (!rc) { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { h->err = who + ": " + hipGetErrorString(e); rc = PG_ERR_HIP; } }
     if (!rc) rc = down(h, out, result, n_out);
     else (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
     return rc;
 }
 extern "C" {
 
-// The handle's view of the library in h->d_traj [n_traj][10][Lmax] / h->d_traj_len (both on the device, owned by the handle), with trajectory.t[end] of every trajectory in
-// fp64: what pg_set_trajectories does after its upload and pg_plan_speeds after its kernels.  Drops the index
-static void adopt_trajectories(pg_handle* h, int n_traj, int Lmax, int L0, std::vector<double>&& t_ends) {
-    h->traj_idx.host.clear();
+// The ONE routine that replaces the handle's trajectory library (pg_set_trajectory / pg_set_trajectories after their upload, pg_plan_speeds and pg_make_paths after their
+// kernels).  The rule: h->d_traj [n_traj][10][Lmax] and h->d_traj_len [n_traj] are device memory the handle owns, and h->dc.traj / traj_len / n_traj / traj_stride
+// describe exactly that pair.  The caller hands in a FINISHED library held by its CallBufs, with trajectory.t[end] of every trajectory in fp64; no call touches the
+// handle's library before this point, so one that fails earlier leaves it whole.  In this order: wait for the stream (a launch still queued reads the old pair), free
+// the old pair, take the new one (the caller's pointers are nulled), fill the view, drop the index
+static int replace_trajectories(pg_handle* h, CallBufs& D, real*& traj, int*& len, int n_traj, int Lmax, int L0, std::vector<double>&& t_ends) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_traj) (void)hipFree(h->d_traj);
+    if (h->d_traj_len) (void)hipFree(h->d_traj_len);
+    h->d_traj = D.give(traj); h->d_traj_len = D.give(len);
     const size_t stride = (size_t)10 * Lmax;
     h->traj_t_end = t_ends[0];                           // trajectory.t[end] of trajectory 0 (channel 0 = t): the stop of pg_simulate_dev's clock range
     h->traj_ends = std::move(t_ends); h->tend_dirty = true;      // ... and of every trajectory, fp64 (the window gate of the node callback)
     TrajView& T = h->dc.traj; T.L = L0;
     const real* p = h->d_traj; const size_t c = (size_t)Lmax;
     T.t = p; T.s = p + c; T.V = p + 2 * c; T.A = p + 3 * c; T.E = p + 4 * c; T.N = p + 5 * c; T.psi = p + 6 * c; T.kappa = p + 7 * c; T.edge_L = p + 8 * c; T.edge_R = p + 9 * c;
-    h->dc.n_traj = n_traj; h->dc.traj_stride = (long)stride; h->dc.traj_len = h->d_traj_len; h->dc.traj_idx = nullptr;
+    h->dc.n_traj = n_traj; h->dc.traj_stride = (long)stride; h->dc.traj_len = h->d_traj_len;
     h->traj_L = L0;
+    h->traj_idx.host.clear(); h->dc.traj_idx = nullptr;
+    return PG_OK;
 }
-// install a trajectory library: channels[n_traj][10][Lmax] (t, s, V, A, E, N, psi, kappa, edge_L, edge_R), L[k] valid nodes of trajectory k
+// install a trajectory library: channels[n_traj][10][Lmax] (t, s, V, A, E, N, psi, kappa, edge_L, edge_R), L[k] valid nodes of trajectory k.  Built in fresh buffers
+// beside the installed library, which stays whole and in place until both uploads have succeeded
 static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_t* L, const double* channels) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_traj) { (void)hipFree(h->d_traj); h->d_traj = nullptr; }
-    if (h->d_traj_len) { (void)hipFree(h->d_traj_len); h->d_traj_len = nullptr; }
-    h->traj_idx.host.clear();
     const size_t stride = (size_t)10 * Lmax;
-    HIPCHK(h, hipMalloc((void**)&h->d_traj, (size_t)n_traj * stride * sizeof(real)));
-    { int rc = up(h, h->d_traj, channels, (size_t)n_traj * stride); if (rc) return rc; }
-    HIPCHK(h, hipMalloc((void**)&h->d_traj_len, (size_t)n_traj * sizeof(int)));
-    HIPCHK(h, hipMemcpy(h->d_traj_len, L, (size_t)n_traj * sizeof(int), hipMemcpyHostToDevice));
+    CallBufs D; real* traj = nullptr; int* len = nullptr;
+    HIPCHK(h, D.alloc(traj, (size_t)n_traj * stride));
+    { int rc = up(h, traj, channels, (size_t)n_traj * stride); if (rc) return rc; }
+    HIPCHK(h, D.alloc(len, (size_t)n_traj));
+    HIPCHK(h, hipMemcpy(len, L, (size_t)n_traj * sizeof(int), hipMemcpyHostToDevice));
     std::vector<double> ends((size_t)n_traj);
     for (int k = 0; k < n_traj; k++) ends[(size_t)k] = channels[(size_t)k * stride + (size_t)L[k] - 1];
-    adopt_trajectories(h, n_traj, Lmax, L[0], std::move(ends));
-    return PG_OK;
+    return replace_trajectories(h, D, traj, len, n_traj, Lmax, L[0], std::move(ends));
 }
 
 int pg_set_trajectory(pg_handle* h, int32_t L, const double* t, const double* s, const double* V, const double* A, const double* E, const double* N,
@@ -1015,12 +1041,6 @@ static int speed_plan_spw(const pg_handle* h, int n_path, int n_sets) {
     while (spw > 16 && (long)n_path * ((n_sets + spw - 1) / spw) < 256) spw /= 2;
     return spw;
 }
-namespace {
-struct SpeedPlanBufs {                                  // device memory of one call: released on every way out, except what an install hands to the handle
-    real *in = nullptr, *out = nullptr; int *L = nullptr, *i0 = nullptr, *len = nullptr; SpeedSet* sets = nullptr; pg_speed_plan_stats* stats = nullptr;
-    ~SpeedPlanBufs() { for (void* p : {(void*)in, (void*)out, (void*)L, (void*)i0, (void*)len, (void*)sets, (void*)stats}) if (p) (void)hipFree(p); }
-};
-}  // namespace
 int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in, int32_t n_sets,
                    const pg_speed_plan* sets, const pg_vehicle* vehicles, int32_t install, double* channels_out, pg_speed_plan_stats* stats) {
     if (!h) return PG_ERR_INVALID;
@@ -1048,8 +1068,8 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
         }
     }
     for (int j = 0; j < n_sets; j++) {
-        const char* why = speed_plan_problem(sets[j]); REQUIRE(h, !why, std::string("pg_plan_speeds: ") + (why ? why : ""));
-        if (vehicles) { const char* vw = plant_set_problem(vehicles[j]); REQUIRE(h, !vw, std::string("pg_plan_speeds: the vehicle: ") + (vw ? vw : "")); }
+        REQUIRE_NO(h, "pg_plan_speeds: ", speed_plan_problem(sets[j]));
+        if (vehicles) REQUIRE_NO(h, "pg_plan_speeds: the vehicle: ", plant_set_problem(vehicles[j]));
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
 
@@ -1058,40 +1078,35 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
     for (int j = 0; j < n_sets; j++) fill_speed_set(recs[(size_t)j], sets[j], vehicles ? vehicles[j] : h->cfg.vehicle);
     std::vector<int> lens(n_traj);
     for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
-    SpeedPlanBufs D;
-    HIPCHK(h, hipMalloc((void**)&D.in, (size_t)n_path * stride * sizeof(real)));
-    HIPCHK(h, hipMalloc((void**)&D.out, total * sizeof(real)));
-    HIPCHK(h, hipMalloc((void**)&D.L, (size_t)n_path * sizeof(int)));
-    HIPCHK(h, hipMalloc((void**)&D.i0, (size_t)n_path * sizeof(int)));
-    HIPCHK(h, hipMalloc((void**)&D.len, n_traj * sizeof(int)));
-    HIPCHK(h, hipMalloc((void**)&D.sets, (size_t)n_sets * sizeof(SpeedSet)));
-    HIPCHK(h, hipMalloc((void**)&D.stats, n_traj * sizeof(pg_speed_plan_stats)));
-    { int rc = up(h, D.in, channels_in, (size_t)n_path * stride); if (rc) return rc; }
+    CallBufs D; real *d_in = nullptr, *d_out = nullptr; int *d_L = nullptr, *d_i0 = nullptr, *d_len = nullptr; SpeedSet* d_sets = nullptr; pg_speed_plan_stats* d_stats = nullptr;
+    HIPCHK(h, D.alloc(d_in, (size_t)n_path * stride));
+    HIPCHK(h, D.alloc(d_out, total));
+    HIPCHK(h, D.alloc(d_L, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_i0, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_len, n_traj));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_stats, n_traj));
+    { int rc = up(h, d_in, channels_in, (size_t)n_path * stride); if (rc) return rc; }
     // (plain copies, as install_trajectories uses: the host vectors are consumed when each returns, on every way out)
-    HIPCHK(h, hipMemcpy(D.L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.i0, i0.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.sets, recs.data(), (size_t)n_sets * sizeof(SpeedSet), hipMemcpyHostToDevice));
-    SpeedPlanArgs A; A.n_path = n_path; A.n_sets = n_sets; A.Lmax = Lmax; A.spw = speed_plan_spw(h, n_path, n_sets); A.L = D.L; A.i0 = D.i0; A.in = D.in; A.sets = D.sets; A.out = D.out; A.stats = D.stats;
+    HIPCHK(h, hipMemcpy(d_L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_i0, i0.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_sets, recs.data(), (size_t)n_sets * sizeof(SpeedSet), hipMemcpyHostToDevice));
+    SpeedPlanArgs A; A.n_path = n_path; A.n_sets = n_sets; A.Lmax = Lmax; A.spw = speed_plan_spw(h, n_path, n_sets); A.L = d_L; A.i0 = d_i0; A.in = d_in; A.sets = d_sets; A.out = d_out; A.stats = d_stats;
     hipLaunchKernelGGL(k_speed_plan_copy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, A, total);
     LAUNCH_CHECK(h);
     const dim3 grid((unsigned)n_path, (unsigned)((n_sets + A.spw - 1) / A.spw));
     hipLaunchKernelGGL(k_speed_plan, grid, dim3(64), 0, h->stream, A);
     LAUNCH_CHECK(h);
     std::vector<pg_speed_plan_stats> st(n_traj);
-    HIPCHK(h, hipMemcpyAsync(st.data(), D.stats, n_traj * sizeof(pg_speed_plan_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_traj * sizeof(pg_speed_plan_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the host arrays have been consumed, the kernels have run)
-    { int rc = down(h, channels_out, D.out, total); if (rc) return rc; }
+    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
     if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_speed_plan_stats));
-    if (install) {
-        if (h->d_traj) (void)hipFree(h->d_traj);
-        if (h->d_traj_len) (void)hipFree(h->d_traj_len);
-        h->d_traj = D.out; h->d_traj_len = D.len; D.out = nullptr; D.len = nullptr;
-        std::vector<double> ends(n_traj);
-        for (size_t k = 0; k < n_traj; k++) ends[k] = st[k].t_end;      // (the rounded t of the last knot, as a double: what pg_set_trajectories reads from channels_out)
-        adopt_trajectories(h, (int)n_traj, Lmax, L[0], std::move(ends));
-    }
-    return PG_OK;
+    if (!install) return PG_OK;
+    std::vector<double> ends(n_traj);
+    for (size_t k = 0; k < n_traj; k++) ends[k] = st[k].t_end;      // (the rounded t of the last knot, as a double: what pg_set_trajectories reads from channels_out)
+    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));
 }
 
 // ---- pg_make_paths: a path library from line, arc and clothoid segments (pg_path_make.hip).  One launch, one workgroup per path; no loop on the host ----
@@ -1139,12 +1154,6 @@ static bool path_s_increases(double total, int n_knots) {
     }
     return true;
 }
-namespace {
-struct PathMakeBufs {                                   // device memory of one call: released on every way out, except what an install hands to the handle
-    real* out = nullptr; int* len = nullptr; PathSpec* specs = nullptr; PathSeg* segs = nullptr; double* scratch = nullptr; pg_path_stats* stats = nullptr;
-    ~PathMakeBufs() { for (void* p : {(void*)out, (void*)len, (void*)specs, (void*)segs, (void*)scratch, (void*)stats}) if (p) (void)hipFree(p); }
-};
-}  // namespace
 int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32_t n_seg_total, const pg_path_segment* segments, int32_t Lmax,
                   int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_path_stats* stats) {
     if (!h) return PG_ERR_INVALID;
@@ -1160,7 +1169,7 @@ int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32
         REQUIRE(h, p.n_seg >= 1 && p.seg0 >= 0 && p.seg0 < n_seg_total && p.n_seg <= n_seg_total - p.seg0, "pg_make_paths: the segments of a path must lie inside [0, n_seg_total)");
         REQUIRE(h, std::isfinite(p.E0) && std::isfinite(p.N0) && std::isfinite(p.psi0), "pg_make_paths: the pose of a path is not finite");
         REQUIRE(h, std::isfinite(p.V_ref) && p.V_ref > 0.0, "pg_make_paths: a path needs a finite V_ref > 0");
-        for (int j = 0; j < p.n_seg; j++) { const char* why = path_segment_problem(segments[p.seg0 + j]); REQUIRE(h, !why, std::string("pg_make_paths: ") + (why ? why : "")); }
+        for (int j = 0; j < p.n_seg; j++) REQUIRE_NO(h, "pg_make_paths: ", path_segment_problem(segments[p.seg0 + j]));
         n_rows += (size_t)p.n_seg;
     }
     std::vector<PathSeg> rows(n_rows);
@@ -1182,24 +1191,24 @@ int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32
     HIPCHK(h, hipSetDevice(h->cfg.device));
 
     const size_t stride = (size_t)10 * Lmax, total = (size_t)n_path * stride;
-    PathMakeBufs D;
-    HIPCHK(h, hipMalloc((void**)&D.out, total * sizeof(real)));
-    HIPCHK(h, hipMalloc((void**)&D.len, (size_t)n_path * sizeof(int)));
-    HIPCHK(h, hipMalloc((void**)&D.specs, (size_t)n_path * sizeof(PathSpec)));
-    HIPCHK(h, hipMalloc((void**)&D.segs, n_rows * sizeof(PathSeg)));
-    HIPCHK(h, hipMalloc((void**)&D.scratch, (size_t)n_path * 2 * (size_t)Lmax * sizeof(double)));
-    HIPCHK(h, hipMalloc((void**)&D.stats, (size_t)n_path * sizeof(pg_path_stats)));
+    CallBufs D; real* d_out = nullptr; int* d_len = nullptr; PathSpec* d_specs = nullptr; PathSeg* d_segs = nullptr; double* d_scratch = nullptr; pg_path_stats* d_stats = nullptr;
+    HIPCHK(h, D.alloc(d_out, total));
+    HIPCHK(h, D.alloc(d_len, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_specs, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_segs, n_rows));
+    HIPCHK(h, D.alloc(d_scratch, (size_t)n_path * 2 * (size_t)Lmax));
+    HIPCHK(h, D.alloc(d_stats, (size_t)n_path));
     // (plain copies, as install_trajectories uses: the host vectors are consumed when each returns, on every way out)
-    HIPCHK(h, hipMemcpy(D.len, lens.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.specs, recs.data(), (size_t)n_path * sizeof(PathSpec), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.segs, rows.data(), n_rows * sizeof(PathSeg), hipMemcpyHostToDevice));
-    PathMakeArgs A; A.Lmax = Lmax; A.specs = D.specs; A.segs = D.segs; A.out = D.out; A.scratch = D.scratch; A.stats = D.stats;
+    HIPCHK(h, hipMemcpy(d_len, lens.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_specs, recs.data(), (size_t)n_path * sizeof(PathSpec), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_segs, rows.data(), n_rows * sizeof(PathSeg), hipMemcpyHostToDevice));
+    PathMakeArgs A; A.Lmax = Lmax; A.specs = d_specs; A.segs = d_segs; A.out = d_out; A.scratch = d_scratch; A.stats = d_stats;
     hipLaunchKernelGGL(k_path_make, dim3((unsigned)n_path), dim3(PM_THREADS), 0, h->stream, A);
     LAUNCH_CHECK(h);
     std::vector<pg_path_stats> st((size_t)n_path);
-    HIPCHK(h, hipMemcpyAsync(st.data(), D.stats, (size_t)n_path * sizeof(pg_path_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, (size_t)n_path * sizeof(pg_path_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
-    { int rc = down(h, channels_out, D.out, total); if (rc) return rc; }
+    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
     const double pi = 3.141592653589793, two_pi = 6.283185307179586;
     for (int k = 0; k < n_path; k++) {                        // the turn reduced to (-pi, pi]: the IEEE remainder is exact
         double r = std::remainder(st[(size_t)k].turn, two_pi);
@@ -1209,15 +1218,10 @@ int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32
         if (closed_out) closed_out[k] = specs[k].closed;
     }
     if (stats) memcpy(stats, st.data(), (size_t)n_path * sizeof(pg_path_stats));
-    if (install) {
-        if (h->d_traj) (void)hipFree(h->d_traj);
-        if (h->d_traj_len) (void)hipFree(h->d_traj_len);
-        h->d_traj = D.out; h->d_traj_len = D.len; D.out = nullptr; D.len = nullptr;
-        std::vector<double> ends((size_t)n_path);
-        for (int k = 0; k < n_path; k++) ends[(size_t)k] = (double)(real)(recs[(size_t)k].total / recs[(size_t)k].V_ref);   // (t of the last knot as stored: what pg_set_trajectories reads from channels_out)
-        adopt_trajectories(h, n_path, Lmax, lens[0], std::move(ends));
-    }
-    return PG_OK;
+    if (!install) return PG_OK;
+    std::vector<double> ends((size_t)n_path);
+    for (int k = 0; k < n_path; k++) ends[(size_t)k] = (double)(real)(recs[(size_t)k].total / recs[(size_t)k].V_ref);   // (t of the last knot as stored: what pg_set_trajectories reads from channels_out)
+    return replace_trajectories(h, D, d_out, d_len, n_path, Lmax, lens[0], std::move(ends));
 }
 
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
@@ -1557,13 +1561,13 @@ int pg_clear_hji_grid(pg_handle* h) {
     return PG_OK;
 }
 
-static int hji_install_nodes(pg_handle* h, const int32_t dims[7]);
+static int hji_install_nodes(pg_handle* h, const HjiWalk& W);
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, dims && knots_concat && V && gradV, "pg_set_hji_grid: null argument");
     REQUIRE(h, h->dc.formulation == PG_COUPLED, "the HJI safety row belongs to the coupled formulation only (coupled_lat_long.jl:341-346)");
-    size_t n = 1; int nk = 0;
-    for (int d = 0; d < 7; d++) { REQUIRE(h, dims[d] >= 2, "pg_set_hji_grid: every dimension needs >= 2 knots"); n *= dims[d]; nk += dims[d]; }
+    HjiWalk W; { const int rc = hji_walk(h, "pg_set_hji_grid", dims, W); if (rc) return rc; }
+    const size_t n = W.n; const int nk = W.nk;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     pg_clear_hji_grid(h);
     // interleave (V, gradV[7]) into 8-float node records: one 32 B aligned read per corner instead of a 4 B + a 28 B unaligned one
@@ -1573,13 +1577,13 @@ int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_conc
     HIPCHK(h, hipMalloc((void**)&h->d_knots, (size_t)nk * sizeof(float)));
     HIPCHK(h, hipMemcpy(h->d_hnodes, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_knots, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice));
-    return hji_install_nodes(h, dims);
+    return hji_install_nodes(h, W);
 }
 // the lookup table of the handle from the node records h->d_hnodes and the knots h->d_knots (both on the device, owned by the handle): what pg_set_hji_grid does after
 // its upload and pg_hji_solve after its last sweep
-static int hji_install_nodes(pg_handle* h, const int32_t dims[7]) {
-    long st = 1; int ko = 0;
-    for (int d = 0; d < 7; d++) { h->hv.dims[d] = dims[d]; h->hv.koff[d] = ko; h->hv.stride[d] = st; st *= dims[d]; ko += dims[d]; }
+static int hji_install_nodes(pg_handle* h, const HjiWalk& W) {
+    const int* dims = W.dims;
+    W.fill(h->hv);
     h->hv.knots = h->d_knots; h->hv.nodes = h->d_hnodes;
     // cell records (8 corners of dims 1..3 contiguous): built on the device from the compact node records, which are then released
     size_t free_b = 0, total_b = 0;
@@ -1610,10 +1614,6 @@ pg_hji_solve_opts pg_default_hji_solve_opts(void) {
     return o;
 }
 namespace {
-struct HjiSolveBufs {                                   // device memory of one solve: released on every way out, except what an install hands to the handle
-    float *kn = nullptr, *V[2] = {nullptr, nullptr}, *rec = nullptr; real *Hc = nullptr, *alpha = nullptr; int* bad = nullptr; unsigned int* vkeys = nullptr;
-    ~HjiSolveBufs() { for (void* p : {(void*)kn, (void*)V[0], (void*)V[1], (void*)rec, (void*)Hc, (void*)alpha, (void*)bad, (void*)vkeys}) if (p) (void)hipFree(p); }
-};
 float hji_key_float(unsigned int k) { unsigned int b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &b, 4); return f; }
 }  // namespace
 int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* l0, const pg_vehicle* vehicle, const pg_hji_solve_opts* opts,
@@ -1621,8 +1621,8 @@ int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat,
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, dims && knots_concat && l0, "pg_hji_solve: null argument");
     const pg_hji_solve_opts O = opts ? *opts : pg_default_hji_solve_opts();
-    size_t n = 1; int nk = 0;
-    for (int d = 0; d < 7; d++) { REQUIRE(h, dims[d] >= 2, "pg_hji_solve: every dimension needs >= 2 knots"); n *= dims[d]; nk += dims[d]; }
+    HjiWalk W; { const int rc = hji_walk(h, "pg_hji_solve", dims, W); if (rc) return rc; }
+    const size_t n = W.n; const int nk = W.nk;
     double minsp[7];
     {
         const float* k = knots_concat;
@@ -1646,29 +1646,28 @@ int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat,
     REQUIRE(h, O.cfl > 0.0 && O.cfl <= 1.0, "pg_hji_solve: cfl must lie in (0, 1]");
     REQUIRE(h, std::isfinite(O.fixed_dt) && O.fixed_dt >= 0.0, "pg_hji_solve: fixed_dt must be finite and >= 0");
     REQUIRE(h, O.max_sweeps >= 0, "pg_hji_solve: max_sweeps must be >= 0");
-    if (vehicle) { const char* why = plant_set_problem(*vehicle); REQUIRE(h, !why, std::string("pg_hji_solve: the vehicle: ") + (why ? why : "")); }
+    if (vehicle) REQUIRE_NO(h, "pg_hji_solve: the vehicle: ", plant_set_problem(*vehicle));
     if (install && h->dc.formulation != PG_COUPLED) { h->err = "pg_hji_solve: install: the HJI safety row belongs to the coupled formulation only (coupled_lat_long.jl:341-346)"; return PG_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
 
-    HjiSolveGrid G; long st = 1; int ko = 0;
-    for (int d = 0; d < 7; d++) { G.dims[d] = dims[d]; G.koff[d] = ko; G.stride[d] = st; st *= dims[d]; ko += dims[d]; }
+    HjiSolveGrid G; W.fill(G);
     G.n = (long)n; G.periodic = (O.flags & PG_HJI_PERIODIC_PSI) ? 1 : 0;
     DevVehicle P; fill_dev_vehicle(P, vehicle ? *vehicle : h->cfg.vehicle);
-    HjiSolveBufs D;
-    HIPCHK(h, hipMalloc((void**)&D.kn, (size_t)nk * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&D.V[0], n * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&D.V[1], n * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&D.Hc, n * sizeof(real)));
-    HIPCHK(h, hipMalloc((void**)&D.rec, n * 8 * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&D.alpha, 7 * sizeof(real)));
-    HIPCHK(h, hipMalloc((void**)&D.bad, sizeof(int)));
-    HIPCHK(h, hipMalloc((void**)&D.vkeys, 2 * sizeof(unsigned int)));
-    G.knots = D.kn;
-    HIPCHK(h, hipMemcpyAsync(D.kn, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(D.V[0], l0, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(D.bad, 0, sizeof(int), h->stream));
+    CallBufs D; float *d_kn = nullptr, *d_V[2] = {nullptr, nullptr}, *d_rec = nullptr; real *d_Hc = nullptr, *d_alpha = nullptr; int* d_bad = nullptr; unsigned int* d_vkeys = nullptr;
+    HIPCHK(h, D.alloc(d_kn, (size_t)nk));
+    HIPCHK(h, D.alloc(d_V[0], n));
+    HIPCHK(h, D.alloc(d_V[1], n));
+    HIPCHK(h, D.alloc(d_Hc, n));
+    HIPCHK(h, D.alloc(d_rec, n * 8));
+    HIPCHK(h, D.alloc(d_alpha, 7));
+    HIPCHK(h, D.alloc(d_bad, 1));
+    HIPCHK(h, D.alloc(d_vkeys, 2));
+    G.knots = d_kn;
+    HIPCHK(h, hipMemcpyAsync(d_kn, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_V[0], l0, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_bad, 0, sizeof(int), h->stream));
     const unsigned int keys0[2] = {0xffffffffu, 0u};
-    HIPCHK(h, hipMemcpyAsync(D.vkeys, keys0, sizeof(keys0), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_vkeys, keys0, sizeof(keys0), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));                 // (the host arrays have been consumed)
 
     pg_hji_solve_stats S; memset(&S, 0, sizeof(S)); S.bad_sweep = -1;
@@ -1677,11 +1676,11 @@ int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat,
     bool reached = !(O.horizon > 0.0);
     while (!reached && S.sweeps < O.max_sweeps) {
         real a[7];
-        HIPCHK(h, hipMemsetAsync(D.alpha, 0, 7 * sizeof(real), h->stream));
-        hipLaunchKernelGGL(k_hji_sweep_eval, grid, block, 0, h->stream, G, P, (const float*)D.V[cur], D.Hc, D.alpha);
+        HIPCHK(h, hipMemsetAsync(d_alpha, 0, 7 * sizeof(real), h->stream));
+        hipLaunchKernelGGL(k_hji_sweep_eval, grid, block, 0, h->stream, G, P, (const float*)d_V[cur], d_Hc, d_alpha);
         LAUNCH_CHECK(h);
-        HIPCHK(h, hipMemcpyAsync(a, D.alpha, sizeof(a), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&bad, D.bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));      // (the flag of the previous sweep's update)
+        HIPCHK(h, hipMemcpyAsync(a, d_alpha, sizeof(a), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));      // (the flag of the previous sweep's update)
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (bad) break;
         double sum = 0.0;
@@ -1690,16 +1689,16 @@ int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat,
         const double rem = O.horizon - S.tau;
         const bool last = !(dt < rem);
         if (last) dt = rem;
-        hipLaunchKernelGGL(k_hji_sweep_update, grid, block, 0, h->stream, G, (const float*)D.V[cur], (const real*)D.Hc, (const real*)D.alpha, (real)dt, D.V[cur ^ 1], D.bad);
+        hipLaunchKernelGGL(k_hji_sweep_update, grid, block, 0, h->stream, G, (const float*)d_V[cur], (const real*)d_Hc, (const real*)d_alpha, (real)dt, d_V[cur ^ 1], d_bad);
         LAUNCH_CHECK(h);
         cur ^= 1; S.sweeps++; S.last_dt = dt; S.tau = last ? O.horizon : S.tau + dt; reached = last;
     }
     if (!bad) {
-        hipLaunchKernelGGL(k_hji_finish, grid, block, 0, h->stream, G, (const float*)D.V[cur], D.rec, D.vkeys, D.bad);
+        hipLaunchKernelGGL(k_hji_finish, grid, block, 0, h->stream, G, (const float*)d_V[cur], d_rec, d_vkeys, d_bad);
         LAUNCH_CHECK(h);
         unsigned int keys[2];
-        HIPCHK(h, hipMemcpyAsync(keys, D.vkeys, sizeof(keys), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&bad, D.bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(keys, d_vkeys, sizeof(keys), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         S.v_min = (double)hji_key_float(keys[0]); S.v_max = (double)hji_key_float(keys[1]);
     }
@@ -1710,17 +1709,17 @@ int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat,
         h->err = "pg_hji_solve: V holds a NaN or Inf after sweep " + std::to_string(S.bad_sweep) + " (nothing was installed)";
         return PG_ERR_INVALID;
     }
-    if (V_out) HIPCHK(h, hipMemcpy(V_out, D.V[cur], n * sizeof(float), hipMemcpyDeviceToHost));
+    if (V_out) HIPCHK(h, hipMemcpy(V_out, d_V[cur], n * sizeof(float), hipMemcpyDeviceToHost));
     if (gradV_out) {                                    // the records hold (V, gradV[7]): 28 of every 32 bytes
         std::vector<float> rec(n * 8);
-        HIPCHK(h, hipMemcpy(rec.data(), D.rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(rec.data(), d_rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; i++) for (int k = 0; k < 7; k++) gradV_out[7 * i + k] = rec[8 * i + 1 + k];
     }
     if (stats) *stats = S;
     if (install) {
         pg_clear_hji_grid(h);
-        h->d_hnodes = D.rec; h->d_knots = D.kn; D.rec = nullptr; D.kn = nullptr;
-        return hji_install_nodes(h, dims);
+        h->d_hnodes = D.give(d_rec); h->d_knots = D.give(d_kn);
+        return hji_install_nodes(h, W);
     }
     return PG_OK;
 }

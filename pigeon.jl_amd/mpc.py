@@ -137,15 +137,16 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_set_trajectory(self.h, len(traj), *[_p(c) for c in cols]), "pg_set_trajectory")
 
     # ---- one controller per (x0, reference trajectory) pair: the batch carries a library of tubes and a per-instance selection ----
+    _CH_ROWS = [0, 1, 2, 3, 4, 5, 6, 7, 10, 11]                       # t, s, V, A, E, N, psi, kappa, edge_L, edge_R of the 12-channel tube
+
     def set_trajectories(self, trajs, index=None):
         trajs = list(trajs)
         Lmax = max(len(t) for t in trajs)
         L = np.array([len(t) for t in trajs], dtype=np.int32)
         pack = np.zeros((len(trajs), 10, Lmax))
-        rows = [0, 1, 2, 3, 4, 5, 6, 7, 10, 11]                     # t, s, V, A, E, N, psi, kappa, edge_L, edge_R of the 12-channel tube
         for k, t in enumerate(trajs):
-            pack[k, :, :len(t)] = t.data[rows]
-            pack[k, :, len(t):] = t.data[rows][:, -1:]              # padding is never read (L[k] bounds every search)
+            pack[k, :, :len(t)] = t.data[self._CH_ROWS]
+            pack[k, :, len(t):] = t.data[self._CH_ROWS][:, -1:]     # padding is never read (L[k] bounds every search)
         self._chk(self.lib.pg_set_trajectories(self.h, len(trajs), Lmax, _p(L, C.POINTER(C.c_int32)), _p(pack)), "pg_set_trajectories")
         self.trajectories = trajs
         self.trajectory = trajs[0]
@@ -156,8 +157,6 @@ class BatchedTrajectoryTrackingMPC:
         self.trajectory_index = self._set_index("trajectory", index)
 
     # ---- making the speed profile (pg_plan_speeds): every (path, plan set) tube of a path library x a library of plan sets, computed on the device ----
-    _CH_ROWS = [0, 1, 2, 3, 4, 5, 6, 7, 10, 11]                       # t, s, V, A, E, N, psi, kappa, edge_L, edge_R of the 12-channel tube
-
     @classmethod
     def pack_speed_plans(cls, sets):
         """dicts (vehicles.speed_plan(**overrides); missing fields: the defaults) or pg_speed_plan structures -> a ctypes array of pg_speed_plan.  Raises ValueError for
@@ -222,6 +221,14 @@ class BatchedTrajectoryTrackingMPC:
             out.append(TrajectoryTube(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], np.zeros(n), np.zeros(n), c[8], c[9]))
         return out
 
+    def _made_tubes(self, channels, L, n_sets, install):
+        """the tubes a maker returns; with install they are the handle's library from here on, as the library already holds them"""
+        tubes = self.tubes_from_channels(channels, L, n_sets)
+        if install:
+            self.trajectories = tubes
+            self.trajectory = tubes[0]
+        return tubes
+
     def plan_speeds(self, paths, sets, vehicles=None, closed=None, install=False):
         """Friction-limited speed profiles on the device (pg_plan_speeds; the scheme is stated in include/pigeon_mpc.h): paths = TrajectoryTubes or the channel array
         (their t, V, A are ignored), sets = vehicles.speed_plan(**overrides) dicts, vehicles = None (the handle's) or one vehicle per set, closed = None / one flag /
@@ -240,12 +247,7 @@ class BatchedTrajectoryTrackingMPC:
         st = (_lib.pg_speed_plan_stats * n_traj)()
         self._chk(self.lib.pg_plan_speeds(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, veh, int(bool(install)), _p(out), st),
                   "pg_plan_speeds")
-        tubes = self.tubes_from_channels(out, L, len(arr))
-        if install:
-            self.trajectories = tubes
-            self.trajectory = tubes[0]
-        stats = np.frombuffer(st, dtype=SPEED_PLAN_STATS_DTYPE).copy()
-        return tubes, stats
+        return self._made_tubes(out, L, len(arr), install), np.frombuffer(st, dtype=SPEED_PLAN_STATS_DTYPE).copy()
 
     # ---- making the path (pg_make_paths): a library of paths from line, arc and clothoid segments, computed on the device ----
     @classmethod
@@ -327,11 +329,7 @@ class BatchedTrajectoryTrackingMPC:
         L = np.zeros(n, dtype=np.int32)
         st = (_lib.pg_path_stats * n)()
         self._chk(self.lib.pg_make_paths(self.h, n, specs, len(segs), segs, Lmax, int(bool(install)), _p(L, c_i32p), None, _p(out), st), "pg_make_paths")
-        tubes = self.tubes_from_channels(out, L)
-        if install:
-            self.trajectories = tubes
-            self.trajectory = tubes[0]
-        return tubes, np.frombuffer(st, dtype=PATH_STATS_DTYPE).copy()
+        return self._made_tubes(out, L, 1, install), np.frombuffer(st, dtype=PATH_STATS_DTYPE).copy()
 
     # ---- the per-instance libraries share one protocol (pg_set_<name>_sets / pg_set_<name>_index / pg_clear_<name>_sets / pg_get_<name>_sets): the four routines below ----
     @staticmethod

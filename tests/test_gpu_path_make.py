@@ -5,29 +5,16 @@ pg_set_trajectories, the chain into pg_plan_speeds, every refusal, and one close
 fp64 library: s, psi, kappa, the edges, t, V and A are closed forms whose every operation is rounded once in both places: bit for bit.  E and N: the library sums the
 interval increments in blocks, the twin serially; the bar 4 (n_knots + 64) 2^-53 total is derived (path_make_cases.bar), 3.3e-11 m for the oval of 201.1 m.
 Measured on the MI355X: see EXPERIMENTS 30."""
-import ctypes as C
-import sys
-
 import numpy as np
 import pytest
 
 import path_make_cases as cases
+from path_libs import INVALID, OK, c_dp, c_i32p, drive, handle, install_equals_set_trajectories, lib, refusals, step_bits
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID, STATE = 0, -2, -4
-c_i32p = C.POINTER(C.c_int32)
-c_dp = C.POINTER(C.c_double)
 GEOMETRY = (1, 4, 5, 6, 7, 8, 9)
 N_PATH = 5
-
-
-def lib_mod():
-    return sys.modules["pigeon_jl_amd._lib"]
-
-
-def handle(pkg, precision="f64", cap=8, **kw):
-    return pkg.BatchedTrajectoryTrackingMPC(pkg.load_path_fixture("skidpadoval"), cap, N_short=1, N_long=0, precision=precision, **kw)
 
 
 def packed(m, which=range(N_PATH)):
@@ -41,7 +28,7 @@ def raw_make(m, specs, segs, Lmax=cases.LMAX, install=False):
     n = len(specs)
     out = np.full((n, 10, Lmax), np.nan)
     L = np.full(n, -1, dtype=np.int32); cl = np.full(n, -1, dtype=np.int32)
-    st = (lib_mod().pg_path_stats * n)()
+    st = (lib().pg_path_stats * n)()
     rc = m.lib.pg_make_paths(m.h, n, specs, len(segs), segs, Lmax, int(install), L.ctypes.data_as(c_i32p), cl.ctypes.data_as(c_i32p), out.ctypes.data_as(c_dp), st)
     assert rc == OK, m.lib.pg_last_error(m.h)
     return out, st, L, cl
@@ -109,37 +96,13 @@ def test_determinism_and_independence_of_the_batch(pkg, made):
     m.close()
 
 
-def get_state(m, B):
-    q = np.zeros((B, 6)); u = np.zeros((B, 3)); t = np.zeros(B)
-    assert m.lib.pg_get_state(m.h, q.ctypes.data_as(c_dp), u.ctypes.data_as(c_dp), t.ctypes.data_as(c_dp)) == OK, m.lib.pg_last_error(m.h)
-    return np.concatenate([q, t[:, None]], axis=1), u
-
-
 def test_install_equals_set_trajectories_with_the_returned_channels(pkg, made):
     out, st, L, cl = made
     a, b = handle(pkg), handle(pkg)
     raw_make(a, *packed(a), install=True)
     oval = a.tubes_from_channels(out, L)[1]
-    state, control, t0, toff = pkg.synthetic.config2_inputs(oval, 5, seed=4, s_range=(2.0, 20.0))
-    a.set_inputs(state, control, t0, time_offset=toff)
-    # a library of several needs an index, as after pg_set_trajectories: the phase calls return PG_ERR_STATE until one is installed
-    assert a.lib.pg_compute_time_steps(a.h) == STATE and a.lib.pg_compute_linearization_nodes(a.h) == STATE
-    assert a.lib.pg_step_dev(a.h, None) == STATE
-    assert b.lib.pg_set_trajectories(b.h, N_PATH, cases.LMAX, L.ctypes.data_as(c_i32p), np.ascontiguousarray(out).ctypes.data_as(c_dp)) == OK
-    b.set_inputs(state, control, t0, time_offset=toff)
     index = np.full(5, 1, dtype=np.int32)                           # the starts lie on the oval
-    res = []
-    for m in (a, b):
-        m.set_trajectory_index(index)
-        rc = m.lib.pg_simulate_dev(m.h, 6, C.c_double(0.01), None, None)
-        assert rc == OK, m.lib.pg_last_error(m.h)
-        res.append(get_state(m, 5))
-    assert res[0][0].tobytes() == res[1][0].tobytes() and res[0][1].tobytes() == res[1][1].tobytes()
-    assert np.all(np.isfinite(res[0][0]))
-    # the clock of pg_simulate_dev reads trajectory.t[end] of trajectory 0: the same times on both handles, for a step that has an exact rational and one that has not
-    for dt in (0.01, 0.37):
-        ca, cb = a.simulate_clock(7, t0, dt=dt), b.simulate_clock(7, t0, dt=dt)
-        assert ca.tobytes() == cb.tobytes() and np.all(np.isfinite(ca)), dt
+    install_equals_set_trajectories(pkg, a, b, out, L, cases.LMAX, index, oval)
     a.close(); b.close()
 
 
@@ -151,7 +114,7 @@ def test_the_chain_into_plan_speeds(pkg, made):
     arr = m.pack_speed_plans(sets)
     ch = np.ascontiguousarray(out[pick]); Lp = np.ascontiguousarray(L[pick]); clp = np.ascontiguousarray(cl[pick])
     planned = np.full((4, 10, cases.LMAX), np.nan)
-    ps = (lib_mod().pg_speed_plan_stats * 4)()
+    ps = (lib().pg_speed_plan_stats * 4)()
     rc = m.lib.pg_plan_speeds(m.h, 2, cases.LMAX, Lp.ctypes.data_as(c_i32p), clp.ctypes.data_as(c_i32p), ch.ctypes.data_as(c_dp), 2, arr, None, 0, planned.ctypes.data_as(c_dp), ps)
     assert rc == OK, m.lib.pg_last_error(m.h)
     for i, k in enumerate(pick):
@@ -165,16 +128,10 @@ def test_the_chain_into_plan_speeds(pkg, made):
     m.close()
 
 
-def step_bits(m, pkg):
-    state, control, t0, toff = pkg.synthetic.config2_inputs(m.trajectories[0], 5, seed=4)
-    u, status, _ = m.step_(state, control, t0, time_offset=toff)
-    return u.tobytes() + status.tobytes()
-
-
 def test_every_refusal_leaves_the_installed_library_alone(pkg):
     m = handle(pkg)
     before = step_bits(m, pkg)
-    L = lib_mod()
+    L = lib()
 
     def call(n_path=N_PATH, Lmax=cases.LMAX, spec=None, seg=None, null_specs=False, null_segs=False, n_seg_total=None):
         """the shared case with one edit: spec = (path, field, value), seg = (segment, field, value)"""
@@ -189,7 +146,7 @@ def test_every_refusal_leaves_the_installed_library_alone(pkg):
     n_segs = len(packed(m)[1])
     assert n_segs == 19
     big = 2**31 - 1
-    refusals = {
+    refused = {
         "null specs": dict(null_specs=True), "null segments": dict(null_segs=True), "n_path 0": dict(n_path=0), "n_seg_total 0": dict(n_seg_total=0), "Lmax 1": dict(Lmax=1),
         "n_knots 1": dict(spec=(2, "n_knots", 1)), "n_knots above Lmax": dict(spec=(1, "n_knots", 301)), "Lmax below n_knots": dict(Lmax=299),
         "closed with 2 knots": dict(spec=(0, "closed", 1)), "n_seg 0": dict(spec=(3, "n_seg", 0)), "seg0 negative": dict(spec=(3, "seg0", -1)),
@@ -206,10 +163,7 @@ def test_every_refusal_leaves_the_installed_library_alone(pkg):
     assert call() == OK                                             # the unedited call is accepted (and installs: put the first library back)
     m.set_trajectory(pkg.load_path_fixture("skidpadoval"))
     assert step_bits(m, pkg) == before
-    for name, kw in refusals.items():
-        assert call(**kw) == INVALID, name
-        assert m.lib.pg_last_error(m.h).decode().startswith("pg_make_paths"), name
-        assert step_bits(m, pkg) == before, name
+    refusals(m, pkg, call, refused, "pg_make_paths", before)
     # knots so dense that s does not increase strictly in the library's element type.  In double, i ds is at least an ulp of the total apart for any n_knots an int32
     # holds, except where ds itself is lost:
     specs = (L.pg_path_spec * 1)(); segs = (L.pg_path_segment * 1)()
@@ -250,16 +204,7 @@ def test_a_made_path_is_drivable(pkg, made):
     b = np.cumsum([0.0] + [g["length"] for g in p[1]])             # straight [b0, b1], clothoid in [b1, b2], arc [b2, b3], clothoid out [b3, b4]
     at = [0.5 * (b[0] + b[1]), 0.5 * (b[1] + b[2]), 0.5 * (b[2] + b[3]), 0.5 * (b[3] + b[4])]
     knots = [int(np.argmin(np.abs(tube.s - s))) for s in at]
-    state = np.zeros((4, 6)); control = np.zeros((4, 3)); t0 = np.zeros(4)
-    for i, k in enumerate(knots):
-        state[i] = [tube.E[k], tube.N[k], tube.psi[k], tube.V[k], 0.0, tube.V[k] * tube.kappa[k]]
-        t0[i] = tube.t[k]
-    m.set_inputs(state, control, t0, time_offset=np.zeros(4))
-    status = np.zeros((100, 4), dtype=np.int32)
-    for k in range(100):                                            # (one step per call: consecutive calls continue the clock, and the step's statuses can be read)
-        m.simulate_(1, dt=0.01)
-        status[k] = m.solve_info()[0]
-    summary, steps, first_exit = m.tracking_summary()
+    status, summary, first_exit = drive(m, tube, knots, 100)
     print("made oval: starts at knots", knots, "kappa", tube.kappa[knots], "max |e|", summary[:, 0], "min Ux", summary[:, 4], "first_exit", first_exit, "statuses", np.unique(status))
     assert np.all(pkg.is_solved(status)), np.unique(status)
     assert np.all(first_exit == -1), first_exit

@@ -5,25 +5,17 @@ ragged library, both closures in one call.  Then determinism, the install path a
 fp64 library: every operation of the scheme is correctly rounded in both places, so the expected difference is zero: MEASURED_F64 = 0 on the MI355X, asserted as 8 x 0.
 fp32 library against the float64 twin: MEASURED_F32 (largest relative difference of V over the valid knots, and of t_end), asserted at 8 x measured -- the factor of the
 HJI solve's fp32 bound: it covers the change of rounding order between batch shapes, not more."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import speed_plan_cases as cases
 import speed_plan_numpy as twin
+from path_libs import OK, c_dp, c_i32p, drive, handle, install_equals_set_trajectories, lib, refusals, step_bits
 
 pytestmark = pytest.mark.gpu
 
 MEASURED_F64 = {"V": 0.0, "A": 0.0, "t": 0.0, "stats": 0.0}
 MEASURED_F32 = {"V": 7.72e-5, "t_end": 1.04e-5}                 # measured on the MI355X (EXPERIMENTS 27); the loss sits in along = sqrt(a_lim^2 - (W kappa)^2) near the cap
-OK, INVALID, STATE = 0, -2, -4
-c_i32p = C.POINTER(C.c_int32)
-c_dp = C.POINTER(C.c_double)
-
-
-def handle(pkg, precision="f64", cap=8):
-    return pkg.BatchedTrajectoryTrackingMPC(pkg.load_path_fixture("skidpadoval"), cap, N_short=1, N_long=0, precision=precision)
 
 
 @pytest.fixture(scope="module")
@@ -42,16 +34,11 @@ def raw_plan(m, paths, closed, sets, vehs=None, install=False):
     veh = None if vehs is None else m.pack_vehicles(vehs)
     n = len(L) * len(arr)
     out = np.full((n, 10, ch.shape[2]), np.nan)
-    st = (pkg_lib(m).pg_speed_plan_stats * n)()
+    st = (lib().pg_speed_plan_stats * n)()
     rc = m.lib.pg_plan_speeds(m.h, len(L), ch.shape[2], L.ctypes.data_as(c_i32p), cl.ctypes.data_as(c_i32p), ch.ctypes.data_as(c_dp), len(arr), arr, veh, int(install),
                               out.ctypes.data_as(c_dp), st)
     assert rc == OK, m.lib.pg_last_error(m.h)
     return out, st
-
-
-def pkg_lib(m):
-    import sys
-    return sys.modules["pigeon_jl_amd"]._lib
 
 
 def compare(out, st, single=np.float64):
@@ -132,46 +119,16 @@ def test_determinism_and_independence_of_the_batch(pkg, planned):
     m.close()
 
 
-def get_state(m, B):
-    q = np.zeros((B, 6)); u = np.zeros((B, 3)); t = np.zeros(B)
-    assert m.lib.pg_get_state(m.h, q.ctypes.data_as(c_dp), u.ctypes.data_as(c_dp), t.ctypes.data_as(c_dp)) == OK, m.lib.pg_last_error(m.h)
-    return np.concatenate([q, t[:, None]], axis=1), u
-
-
 def test_install_equals_set_trajectories_with_the_returned_channels(pkg, planned):
     p, closed, sets, vehs, _ = cases.reference()
     out, st = planned
     a, b = handle(pkg), handle(pkg)
-    tubes_a, _ = a.plan_speeds(p, sets, vehicles=vehs, closed=closed, install=True)
-    state, control, t0, toff = pkg.synthetic.config2_inputs(p[0], 5, seed=4, s_range=(2.0, 20.0))
-    a.set_inputs(state, control, t0, time_offset=toff)
-    # a library of several needs an index, as after pg_set_trajectories: the phase calls return PG_ERR_STATE until one is installed
-    assert a.lib.pg_compute_time_steps(a.h) == STATE and a.lib.pg_compute_linearization_nodes(a.h) == STATE
-    assert a.lib.pg_step_dev(a.h, None) == STATE
+    a.plan_speeds(p, sets, vehicles=vehs, closed=closed, install=True)
     # handle B: pg_set_trajectories with A's channels_out, L repeated
     L = np.repeat(np.array([len(t) for t in p], dtype=np.int32), cases.N_SETS)
-    assert b.lib.pg_set_trajectories(b.h, len(L), cases.LMAX, L.ctypes.data_as(c_i32p), np.ascontiguousarray(out).ctypes.data_as(c_dp)) == OK
-    b.set_inputs(state, control, t0, time_offset=toff)
     index = np.array([0, 7, 64, 3, 40], dtype=np.int32)              # path 0 (the starts lie on it) under five sets
-    res = []
-    for m in (a, b):
-        m.set_trajectory_index(index)
-        rc = m.lib.pg_simulate_dev(m.h, 6, C.c_double(0.01), None, None)
-        assert rc == OK, m.lib.pg_last_error(m.h)
-        res.append(get_state(m, 5))
-    assert res[0][0].tobytes() == res[1][0].tobytes() and res[0][1].tobytes() == res[1][1].tobytes()
-    assert np.all(np.isfinite(res[0][0]))
-    # the clock of pg_simulate_dev reads trajectory.t[end] of trajectory 0: the same times on both handles, for a step that has an exact rational and one that has not
-    for dt in (0.01, 0.37):
-        ca, cb = a.simulate_clock(7, t0, dt=dt), b.simulate_clock(7, t0, dt=dt)
-        assert ca.tobytes() == cb.tobytes() and np.all(np.isfinite(ca)), dt
+    install_equals_set_trajectories(pkg, a, b, out, L, cases.LMAX, index, p[0])
     a.close(); b.close()
-
-
-def step_bits(m, pkg):
-    state, control, t0, toff = pkg.synthetic.config2_inputs(m.trajectories[0], 5, seed=4)
-    u, status, _ = m.step_(state, control, t0, time_offset=toff)
-    return u.tobytes() + status.tobytes()
 
 
 def test_every_refusal_leaves_the_installed_library_alone(pkg):
@@ -201,7 +158,7 @@ def test_every_refusal_leaves_the_installed_library_alone(pkg):
             setattr(v[1], k, x)
         return v
 
-    refusals = {
+    refused = {
         "null L": dict(L_=None), "null channels": dict(ch_=None), "null sets": dict(arr_=None),
         "n_path 0": dict(n_path=0), "n_sets 0": dict(n_sets=0), "Lmax 1": dict(Lmax=1),
         "L below 2": dict(L_=np.array([130, 1, 65], dtype=np.int32)), "L above Lmax": dict(L_=np.array([131, 28, 65], dtype=np.int32)),
@@ -217,10 +174,7 @@ def test_every_refusal_leaves_the_installed_library_alone(pkg):
     assert call(veh_=veh) == OK                                     # the unedited call is accepted (and installs: put the first library back)
     m.set_trajectory(pkg.load_path_fixture("skidpadoval"))
     assert step_bits(m, pkg) == before
-    for name, kw in refusals.items():
-        assert call(**kw) == INVALID, name
-        assert m.lib.pg_last_error(m.h).decode().startswith("pg_plan_speeds"), name
-        assert step_bits(m, pkg) == before, name
+    refusals(m, pkg, call, refused, "pg_plan_speeds", before)
     # a geometry value past L[k] is not looked at
     assert call(ch_=edited(lambda c: c[1, 8].__setitem__(28, np.nan))) == OK
     m.close()
@@ -250,16 +204,7 @@ def test_the_plan_is_drivable(pkg):
             m.set_trajectory(path)
         else:
             m.plan_speeds(path, pkg.vehicles.speed_plan(mu_scale=0.5, V_max=10.0), closed=True, install=True)
-        state = np.zeros((4, 6)); control = np.zeros((4, 3)); t0 = np.zeros(4)
-        for b, k in enumerate(knots):
-            state[b] = [tube.E[k], tube.N[k], tube.psi[k], tube.V[k], 0.0, tube.V[k] * tube.kappa[k]]
-            t0[b] = tube.t[k]
-        m.set_inputs(state, control, t0, time_offset=np.zeros(4))
-        status = np.zeros((200, 4), dtype=np.int32)
-        for k in range(200):                                        # (one step per call: consecutive calls continue the clock, and the step's statuses can be read)
-            m.simulate_(1, dt=0.01)
-            status[k] = m.solve_info()[0]
-        summary, steps, first_exit = m.tracking_summary()
+        status, summary, first_exit = drive(m, tube, knots, 200)
         print(name, "profile: max |e|", summary[:, 0], "min Ux", summary[:, 4], "first_exit", first_exit, "statuses", np.unique(status))
         assert np.all(pkg.is_solved(status)), (name, np.unique(status))
         assert np.all(first_exit == -1), (name, first_exit)

@@ -4,7 +4,9 @@ Also covers the un-staged nodes kernel (a tube longer than the LDS staging limit
 import numpy as np
 import pytest
 
+import path_make_cases as cases
 from conftest import make_oracle
+from path_libs import handle, install_equals_set_trajectories, step_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +74,35 @@ def test_library_step_matches_single_trajectory_oracles(pkg, oracle_mod, library
         assert np.array_equal(u1, u[sel]), k
         one.close()
     mpc.close()
+
+
+def test_the_ways_a_library_arrives_replace_each_other(pkg, skidpad):
+    """One handle, the three ways its trajectory library arrives in turn: pg_set_trajectory, pg_make_paths with install, pg_plan_speeds with install, pg_set_trajectories,
+    pg_set_trajectory again.  After each library of several the handle computes, bit for bit, what a fresh handle computes that was given the same channels by
+    pg_set_trajectories (and wants an index first: the previous one is dropped); the single trajectory it ends with gives the step it began with."""
+    p, _ = cases.reference()
+    m = handle(pkg)
+    m.set_trajectory(skidpad)
+    first = step_bits(m, pkg)
+
+    def check(tubes, index, start_tube):
+        L, ch, _ = m.pack_paths(tubes)                              # the channels the tubes were cut from, as pg_set_trajectories takes them
+        b = handle(pkg)
+        install_equals_set_trajectories(pkg, m, b, ch, L, ch.shape[2], np.array(index, dtype=np.int32), start_tube)
+        b.close()
+
+    made, _ = m.make_paths(p, n_knots=cases.N_KNOTS, V_ref=cases.V_REFS, pose=cases.POSES, closed=cases.CLOSED, install=True)
+    assert len(made) == 5 and max(len(t) for t in made) == cases.LMAX
+    check(made, [1, 1, 1, 1, 1], made[1])                           # the starts lie on the oval
+    sets = [pkg.vehicles.speed_plan(mu_scale=0.5, V_max=12.0), pkg.vehicles.speed_plan(mu_scale=0.9, V_max=20.0, V_end=2.0)]
+    planned, _ = m.plan_speeds([made[1], made[3]], sets, closed=[cases.CLOSED[1], cases.CLOSED[3]], install=True)
+    assert len(planned) == 4
+    check(planned, [0, 1, 0, 1, 1], planned[0])                     # the oval under both sets
+    m.set_trajectories(planned)
+    check(planned, [1, 0, 1, 0, 0], planned[0])
+    m.set_trajectory(skidpad)
+    assert step_bits(m, pkg) == first
+    m.close()
 
 
 def test_long_tube_unstaged_nodes_kernel(pkg, oracle_mod, library):
