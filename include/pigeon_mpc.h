@@ -268,6 +268,77 @@ pg_path_segment pg_default_path_segment(void);
 int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32_t n_seg_total, const pg_path_segment* segments, int32_t Lmax,
                   int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_path_stats* stats);
 
+/* Fitting the path: a library of paths through waypoints -- surveyed or recorded (E, N) points with their tube edges --, computed on the device in the layout
+ * pg_set_trajectories takes: an interpolating cubic spline of E and of N over the chord-length parameter, natural on an open path and periodic on a closed one, resampled
+ * at n_knots knots equally spaced in arc length.  The reference reads its paths from files (src/ros_integration.jl:13-16), so the scheme is build-defined
+ * (tests/path_fit_numpy.py is its numpy twin).  ALL arithmetic is double in both libraries, every operation rounded on its own (no contraction), and the result is rounded
+ * to the library's element type on store: the fp32 library's output is exactly the fp64 library's rounded to float, and the stats are the same doubles.  Below, a
+ * parenthesis is one rounded operation and a sum or product without one is taken from the left.
+ *   Spans     An open path has the spans j = 0 .. n_wp - 2, a closed one n_wp spans, the last from waypoint n_wp - 1 back to waypoint 0 (the caller does not repeat the
+ *             first point).  Span j runs from waypoint j to waypoint jn = (j + 1) mod n_wp:  h_j = sqrt((dE dE) + (dN dN)) with dE = E_jn - E_j, dN = N_jn - N_j (no hypot);
+ *             the slopes d_j = dE / h_j and dN / h_j.
+ *   Spline    Per coordinate y, in the second-derivative form:  h_{i-1} M_{i-1} + b_i M_i + h_i M_{i+1} = g_i with b_i = 2 (h_{i-1} + h_i), g_i = 6 (d_i - d_{i-1}).
+ *             Open: M_0 = M_{n_wp-1} = 0 and the rows lo = 1 .. hi = n_wp - 2 (none for two waypoints: a straight line).  Closed: the rows lo = 0 .. hi = n_wp - 1 with the
+ *             indices modulo n_wp, a cyclic system solved by Sherman-Morrison with gamma = -b_0, that is the correction vector u = (-b_0, 0, .., 0, hl) with hl =
+ *             h_{n_wp-1}, b_0 = 2 (hl + h_0), against v = (1, 0, .., 0, -hl / b_0): the tridiagonal part keeps its rows but for bb_0 = 2 b_0 and bb_hi = b_hi + ((hl hl) / b_0), and has a third right-hand
+ *             side g = u.  With three waypoints every off-diagonal place of the 3 x 3 matrix is taken -- band and corners still do not share a place --, and the same
+ *             steps apply.  The Thomas recurrences, without pivoting (strictly diagonally dominant), per right-hand side; the pivots depend on h alone:
+ *             beta_lo = bb_lo;  for i = lo + 1 .. hi: w = h_{i-1} / beta_{i-1}, beta_i = bb_i - (w h_{i-1}), g_i = g_i - (w g_{i-1});
+ *             x_hi = g_hi / beta_hi;  for i = hi - 1 .. lo: x_i = (g_i - (h_i x_{i+1})) / beta_i.
+ *             Open: M = x.  Closed, with z the solution for u:  den = (1 + z_0) - ((hl z_hi) / b_0);  fact = (x_0 - ((hl x_hi) / b_0)) / den;  M_i = x_i - (fact z_i).
+ *   Cubic     In span j, u in [0, h_j]:  c1 = d_j - ((h_j ((2 M_j) + M_jn)) / 6), c3 = (M_jn - M_j) / (6 h_j);
+ *             y(u) = y_j + (u (c1 + (u ((0.5 M_j) + (u c3))))),  y'(u) = c1 + (u (M_j + (u (3 c3)))),  y''(u) = M_j + (u (6 c3)).
+ *   Lengths   v(u) = sqrt((E' E') + (N' N')).  A piece [ua, ub]: half = 0.5 (ub - ua), mid = 0.5 (ua + ub), the four Gauss-Legendre nodes u_k = mid + (half x_k) and
+ *             weights of pg_make_paths in ascending order, piece = half sum_k (w_k v(u_k)), the sum from 0 in the order of the nodes.  l_j(u) = piece [0, 0.5 u] + piece
+ *             [0.5 u, u];  l_j = l_j(h_j).  S_0 = 0 and S_{j+1} = P_{j / c} + r_{j+1} in the blocked prefix order of pg_make_paths (Prefix) over the l_j, with c =
+ *             ceil(n_span / 256): the order depends on the path's own span count alone.  total = S_{n_span}.
+ *   Knots     ds = total / (n_knots - 1);  s_i = i ds for i < n_knots - 1, s_last = total.  Knot i lies in the span of the largest j with S_j <= s_i; target = s_i - S_j;
+ *             u_0 = clamp((target h_j) / l_j), then exactly three Newton steps u <- clamp(u - ((l_j(u) - target) / v(u))), clamp(u) = 0 unless u >= 0, h_j where u > h_j.
+ *             The count is fixed, so the bits depend on no convergence test; s_err_max reports what is left.  The last knot lies in the last span at u = h_j, and its E
+ *             and N are those of the waypoint the span ends on (waypoint 0 of a closed path), not y(h_j).
+ *   Channels  E = E(u), N = N(u);  v2 = (E' E') + (N' N'), kappa = ((E' N'') - (E'' N')) / (v2 sqrt(v2)): with dE/ds = -sin psi, dN/ds = cos psi (the committed paths'
+ *             convention) a left turn is positive, a counter-clockwise circle gives +1 / R;  psi_raw = atan2(-E', N');  an edge = edge_j + (((edge_jn - edge_j) u) / h_j);
+ *             t = s / V_ref, V = V_ref, A = 0.
+ *   Unwrap    k_0 = 0;  k_i = k_{i-1} - 1 where psi_raw_i - psi_raw_{i-1} > 3.141592653589793, k_{i-1} + 1 where it is < -3.141592653589793, else k_{i-1};
+ *             psi_i = psi_raw_i + (k_i 6.283185307179586).  The prefix is over integers: its order cannot show.
+ * Everything but atan2 reproduces the twin bit for bit; psi, turn and closure_psi are within 8 * 2^-52 * max(pi, |psi|) of it.  Interpolation, not smoothing: the curvature of
+ * noisy waypoints is the caller's to judge (kappa_abs_max). */
+typedef struct pg_waypoint {
+    double E, N;            /* finite; two neighbouring waypoints of a path must not coincide */
+    double edge_L, edge_R;  /* the tube edges at the waypoint, linear in u across a span; finite, edge_L > edge_R */
+} pg_waypoint;              /* 32 bytes */
+typedef struct pg_fit_spec {
+    double V_ref;           /* > 0, finite: fills V = V_ref, A = 0, t = s / V_ref */
+    int32_t wp0, n_wp;      /* this path's waypoints: waypoints[wp0 .. wp0 + n_wp), inside [0, n_wp_total); n_wp >= 2, a closed path >= 3 */
+    int32_t n_knots;        /* 2 <= n_knots <= Lmax; a closed path needs >= 3 */
+    int32_t closed;         /* != 0: periodic, the last span returns to waypoint 0 and the last knot is knot 0 again; passed through to closed_out */
+} pg_fit_spec;              /* 24 bytes */
+typedef struct pg_fit_stats {    /* one per path; computed in double in both libraries */
+    double length;          /* total = s of the last knot */
+    double turn;            /* psi(last knot) - psi(knot 0) */
+    double closure_pos;     /* sqrt(dE dE + dN dN) between the last knot and knot 0: 0 on a closed path by construction, the gap of an open one */
+    double closure_psi;     /* turn reduced to (-pi, pi] (the IEEE remainder by 6.283185307179586, -pi mapped to +pi) */
+    double kappa_abs_max;   /* over the knots */
+    double ds;              /* length / (n_knots - 1) */
+    double chord_min, chord_max;   /* over the spans */
+    double s_err_max;       /* largest |l_j(u) - target| left by the inversion, over the knots */
+    double reserved;        /* 0 */
+} pg_fit_stats;             /* 80 bytes */
+/* { 0, 0, 4, -4 }: the edge defaults of src/trajectories.jl:43-44 */
+pg_waypoint pg_default_waypoint(void);
+/* Output [n_path][10][Lmax] in the channel order and with the tail rule of pg_make_paths.  L_out [n_path] (= n_knots), closed_out [n_path] (= closed, what pg_plan_speeds
+ * takes as closed[]), channels_out and stats [n_path] may each be NULL.  Waypoint ranges of different paths may overlap (one survey fitted at several knot counts).
+ * install != 0 hands the device buffer to the handle, with no host round trip: the handle is then exactly as after pg_set_trajectories(h, n_path, Lmax, L_out,
+ * channels_out).  Synchronous.  A handle that never calls this launches what it launched before.
+ * PG_ERR_INVALID, everything validated before the first allocation (the handle and its installed library are left unchanged): a null specs or waypoints; n_path < 1;
+ * n_wp_total < 1; Lmax < 2; n_knots outside [2, Lmax]; an open path with n_wp < 2; a closed path with n_wp < 3 or n_knots < 3; a waypoint range outside [0, n_wp_total);
+ * a non-finite waypoint field; edge_L <= edge_R; a span whose chord is not finite and > 0 (two neighbouring waypoints at the same point, last-to-first on a closed path
+ * included); V_ref not finite or <= 0 (waypoints no path refers to are not looked at); knots so dense that s cannot be shown to increase strictly in the library's
+ * element type -- decided before the spline exists, from the sum C of the chords: refused unless n_knots - 1 <= 1 / (4 eps) (2^21 in the fp32 library; every int32 in the
+ * fp64 library) and 2^-100 <= C / (n_knots - 1), C <= 2^100 --; n_path * 10 * Lmax elements or the scratch of all spans beyond the allocation arithmetic. */
+int pg_fit_paths(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints, int32_t Lmax,
+                 int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_fit_stats* stats);
+
 /* control_params of one controller per instance (src/coupled_lat_long.jl:42-60, src/decoupled_lat_long.jl:32-50): a library of control-parameter sets and a per-instance
  * selection, the counterpart of pg_set_trajectories / pg_set_trajectory_index for the controller's tuning -- a tuning sweep or robustness study (the same starts and paths
  * under many weightings, speed bounds and steering-rate limits) runs as ONE batch.  With no library the handle behaves as pg_config.control says.  A library of ONE set

@@ -592,6 +592,48 @@ end
 "{ 1, 0, 0, 4, 4, -4, -4, 0 } as the library states them (pg_default_path_segment)"
 default_path_segment(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_path_segment), PgPathSegment, ())
 
+# Fitting the path (pg_fit_paths): a library of paths through waypoints on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_waypoint (32 bytes): a surveyed point and the tube edges at it"
+struct PgWaypoint
+    E::Float64
+    N::Float64
+    edge_L::Float64
+    edge_R::Float64
+end
+PgWaypoint(; E=0.0, N=0.0, edge_L=4.0, edge_R=-4.0) = PgWaypoint(Float64(E), Float64(N), Float64(edge_L), Float64(edge_R))
+"pg_fit_spec (24 bytes): the constant speed, the path's waypoints waypoints[wp0 + 1 : wp0 + n_wp] (wp0 is 0-based, as in C), its knot count, closed (periodic; the first point is not repeated)"
+struct PgFitSpec
+    V_ref::Float64
+    wp0::Int32
+    n_wp::Int32
+    n_knots::Int32
+    closed::Int32
+end
+"pg_fit_stats (80 bytes), one per path: the six fields of pg_path_stats, then the shortest and the longest chord, what the inversion left, a reserved 0"
+struct PgFitStats
+    length::Float64
+    turn::Float64
+    closure_pos::Float64
+    closure_psi::Float64
+    kappa_abs_max::Float64
+    ds::Float64
+    chord_min::Float64
+    chord_max::Float64
+    s_err_max::Float64
+    reserved::Float64
+end
+"specs and waypoints as pg_fit_paths takes them -> (channels_out [Lmax, 10, n_path] (column-major: the C layout [n_path][10][Lmax]), L, closed, stats); install = true leaves the handle as pg_set_trajectories with channels_out would"
+function fit_paths!(mpc::BatchedTrajectoryTrackingMPC, specs::Vector{PgFitSpec}, waypoints::Vector{PgWaypoint}; Lmax::Integer=maximum(s.n_knots for s in specs), install::Bool=false)
+    (sizeof(PgWaypoint), sizeof(PgFitSpec), sizeof(PgFitStats)) == (32, 24, 80) || error("PigeonMI355X.jl: PgWaypoint / PgFitSpec / PgFitStats differ from include/pigeon_mpc.h")
+    n = length(specs)
+    out = zeros(Float64, Lmax, 10, n); L = zeros(Int32, n); closed = zeros(Int32, n); stats = Vector{PgFitStats}(undef, n)
+    check(mpc, ccall(sym(mpc, :pg_fit_paths), Cint, (Ptr{Cvoid}, Int32, Ptr{PgFitSpec}, Int32, Ptr{PgWaypoint}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{PgFitStats}),
+                     mpc.handle, Int32(n), specs, Int32(length(waypoints)), waypoints, Int32(Lmax), Int32(install), L, closed, out, stats), "pg_fit_paths")
+    out, L, closed, stats
+end
+"{ 0, 0, 4, -4 } as the library states them (pg_default_waypoint)"
+default_waypoint(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_waypoint), PgWaypoint, ())
+
 "mpc.solved = false (src/ros_integration.jl:34,41,147)"
 reset!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_reset), Cint, (Ptr{Cvoid}, Ptr{UInt8}), mpc.handle, C_NULL), "pg_reset")
 

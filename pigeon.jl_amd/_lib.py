@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -211,6 +211,28 @@ PATH_MAKE_PROTOTYPES = {
 }
 
 
+class pg_waypoint(C.Structure):
+    """include/pigeon_mpc.h pg_waypoint: a surveyed point (E, N) and the tube edges at it."""
+    _fields_ = [(n, C.c_double) for n in ["E", "N", "edge_L", "edge_R"]]
+
+
+class pg_fit_spec(C.Structure):
+    """include/pigeon_mpc.h pg_fit_spec: the constant speed of the profile, the path's range of waypoints, its knot count and whether it is closed (periodic)."""
+    _fields_ = [("V_ref", C.c_double), ("wp0", C.c_int32), ("n_wp", C.c_int32), ("n_knots", C.c_int32), ("closed", C.c_int32)]
+
+
+class pg_fit_stats(C.Structure):
+    """include/pigeon_mpc.h pg_fit_stats: one per path -- the six fields of pg_path_stats, the shortest and the longest chord, what the inversion left, a reserved 0."""
+    _fields_ = [(n, C.c_double) for n in ["length", "turn", "closure_pos", "closure_psi", "kappa_abs_max", "ds", "chord_min", "chord_max", "s_err_max", "reserved"]]
+
+
+# path fitter (include/pigeon_mpc.h: pg_fit_paths)
+PATH_FIT_PROTOTYPES = {
+    "pg_fit_paths": [C.c_void_p, C.c_int32, C.POINTER(pg_fit_spec), C.c_int32, C.POINTER(pg_waypoint), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                     C.POINTER(C.c_double), C.POINTER(pg_fit_stats)],
+}
+
+
 def load_library(precision="f64"):
     """Loads the HIP library of the requested arithmetic type.  PyTorch-ROCm is imported first so that both share ONE HIP runtime in this process."""
     assert precision in ("f64", "f32", "f64-diag")
@@ -232,7 +254,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -242,6 +264,8 @@ def load_library(precision="f64"):
     lib.pg_default_speed_plan.restype = pg_speed_plan
     lib.pg_default_path_segment.argtypes = []
     lib.pg_default_path_segment.restype = pg_path_segment
+    lib.pg_default_waypoint.argtypes = []
+    lib.pg_default_waypoint.restype = pg_waypoint
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)
     check_layout(lib)
     _libs[precision] = lib

@@ -1224,6 +1224,104 @@ int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32
     return replace_trajectories(h, D, d_out, d_len, n_path, Lmax, lens[0], std::move(ends));
 }
 
+// ---- pg_fit_paths: a path library fitted to waypoints (pg_path_fit.hip).  One launch, one workgroup per path; no loop on the host ----
+static_assert(sizeof(pg_waypoint) == 32 && sizeof(pg_fit_spec) == 24 && sizeof(pg_fit_stats) == 80, "the sizes include/pigeon_mpc.h states");
+pg_waypoint pg_default_waypoint(void) {
+    pg_waypoint w; w.E = 0.0; w.N = 0.0; w.edge_L = 4.0; w.edge_R = -4.0;
+    return w;
+}
+// the waypoints of one path: what is wrong with them (nullptr: nothing); C = the sum of the chords as the scheme rounds each of them
+static const char* fit_waypoints_problem(const pg_fit_spec& p, const pg_waypoint* wp, double& C) {
+#pragma clang fp contract(off)
+    const pg_waypoint* w = wp + p.wp0;
+    for (int i = 0; i < p.n_wp; i++) {
+        for (double v : {w[i].E, w[i].N, w[i].edge_L, w[i].edge_R}) if (!std::isfinite(v)) return "a field of a waypoint is not finite";
+        if (!(w[i].edge_L > w[i].edge_R)) return "a waypoint needs edge_L > edge_R";
+    }
+    C = 0.0;
+    const int n_span = p.closed ? p.n_wp : p.n_wp - 1;
+    for (int j = 0; j < n_span; j++) {
+        const pg_waypoint &a = w[j], &b = w[j + 1 == p.n_wp ? 0 : j + 1];
+        const double dE = b.E - a.E, dN = b.N - a.N;
+        const double ee = dE * dE, nn = dN * dN;
+        const double h = sqrt(ee + nn);
+        if (!(std::isfinite(h) && h > 0.0)) return "two neighbouring waypoints of a path lie at the same point (a chord must be finite and > 0)";
+        C += h;
+    }
+    return nullptr;
+}
+int pg_fit_paths(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints, int32_t Lmax,
+                 int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_fit_stats* stats) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, specs && waypoints, "pg_fit_paths: null argument");
+    REQUIRE(h, n_path >= 1 && n_wp_total >= 1 && Lmax >= 2, "pg_fit_paths: need n_path >= 1, n_wp_total >= 1 and Lmax >= 2");
+    REQUIRE(h, (double)n_path * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0, "pg_fit_paths: n_path * 10 * Lmax elements are more than the allocation arithmetic holds");
+    const double eps = sizeof(real) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16, range = 1.2676506002282294e30;      // 2^100
+    double span_doubles = 0.0;
+    for (int k = 0; k < n_path; k++) {
+        const pg_fit_spec& p = specs[k];
+        REQUIRE(h, p.n_knots >= 2 && p.n_knots <= Lmax, "pg_fit_paths: every path needs 2 <= n_knots <= Lmax");
+        REQUIRE(h, p.closed ? (p.n_wp >= 3 && p.n_knots >= 3) : p.n_wp >= 2, "pg_fit_paths: an open path needs >= 2 waypoints, a closed one >= 3 waypoints and >= 3 knots");
+        REQUIRE(h, p.wp0 >= 0 && p.wp0 < n_wp_total && p.n_wp <= n_wp_total - p.wp0, "pg_fit_paths: the waypoints of a path must lie inside [0, n_wp_total)");
+        REQUIRE(h, std::isfinite(p.V_ref) && p.V_ref > 0.0, "pg_fit_paths: a path needs a finite V_ref > 0");
+        double C = 0.0;
+        REQUIRE_NO(h, "pg_fit_paths: ", fit_waypoints_problem(p, waypoints, C));
+        const double per = (double)(p.n_knots - 1);
+        REQUIRE(h, per <= 1.0 / (4.0 * eps) && C / per >= 1.0 / range && C <= range,
+                "pg_fit_paths: the knots are so dense that s cannot be shown to increase strictly in the library's element type");
+        span_doubles += (double)PF_ARRAYS * ((double)p.n_wp + 1.0);
+    }
+    REQUIRE(h, span_doubles * 8.0 < 4611686018427387904.0, "pg_fit_paths: the spans of all paths together are more than the allocation arithmetic holds");
+    std::vector<FitSpec> recs((size_t)n_path);
+    std::vector<int> lens((size_t)n_path);
+    size_t n_span_doubles = 0;
+    for (int k = 0; k < n_path; k++) {
+        const pg_fit_spec& p = specs[k];
+        FitSpec& r = recs[(size_t)k];
+        r.V_ref = p.V_ref; r.soff = (long long)n_span_doubles; r.wp0 = p.wp0; r.n_wp = p.n_wp; r.n_knots = p.n_knots; r.closed = p.closed ? 1 : 0;
+        n_span_doubles += (size_t)PF_ARRAYS * ((size_t)p.n_wp + 1);
+        lens[(size_t)k] = p.n_knots;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t stride = (size_t)10 * Lmax, total = (size_t)n_path * stride, n_knot_slots = (size_t)n_path * (size_t)Lmax;
+    CallBufs D; real* d_out = nullptr; int* d_len = nullptr; FitSpec* d_specs = nullptr; pg_waypoint* d_wps = nullptr; double* d_span = nullptr; double* d_raw = nullptr;
+    int* d_runk = nullptr; pg_fit_stats* d_stats = nullptr;
+    HIPCHK(h, D.alloc(d_out, total));
+    HIPCHK(h, D.alloc(d_len, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_specs, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_wps, (size_t)n_wp_total));
+    HIPCHK(h, D.alloc(d_span, n_span_doubles));
+    HIPCHK(h, D.alloc(d_raw, n_knot_slots));
+    HIPCHK(h, D.alloc(d_runk, n_knot_slots));
+    HIPCHK(h, D.alloc(d_stats, (size_t)n_path));
+    // (plain copies, as install_trajectories uses: the host arrays are consumed when each returns, on every way out.  Waypoints no path refers to travel with the rest
+    // and are read by no thread)
+    HIPCHK(h, hipMemcpy(d_len, lens.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_specs, recs.data(), (size_t)n_path * sizeof(FitSpec), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_wps, waypoints, (size_t)n_wp_total * sizeof(pg_waypoint), hipMemcpyHostToDevice));
+    PathFitArgs A; A.Lmax = Lmax; A.specs = d_specs; A.wps = d_wps; A.out = d_out; A.span = d_span; A.psi_raw = d_raw; A.runk = d_runk; A.stats = d_stats;
+    hipLaunchKernelGGL(k_path_fit, dim3((unsigned)n_path), dim3(PF_THREADS), 0, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_fit_stats> st((size_t)n_path);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, (size_t)n_path * sizeof(pg_fit_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
+    const double pi = 3.141592653589793, two_pi = 6.283185307179586;
+    for (int k = 0; k < n_path; k++) {                        // the turn reduced to (-pi, pi]: the IEEE remainder is exact
+        double r = std::remainder(st[(size_t)k].turn, two_pi);
+        if (r <= -pi) r = r + two_pi;
+        st[(size_t)k].closure_psi = r;
+        if (L_out) L_out[k] = specs[k].n_knots;
+        if (closed_out) closed_out[k] = specs[k].closed;
+    }
+    if (stats) memcpy(stats, st.data(), (size_t)n_path * sizeof(pg_fit_stats));
+    if (!install) return PG_OK;
+    std::vector<double> ends((size_t)n_path);
+    for (int k = 0; k < n_path; k++) ends[(size_t)k] = (double)(real)(st[(size_t)k].length / recs[(size_t)k].V_ref);   // (t of the last knot as stored: what pg_set_trajectories reads from channels_out)
+    return replace_trajectories(h, D, d_out, d_len, n_path, Lmax, lens[0], std::move(ends));
+}
+
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
 // solver state: nothing is reset ----
 static const char* sensor_set_problem(const pg_sensor& s) {

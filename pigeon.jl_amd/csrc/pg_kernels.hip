@@ -3408,5 +3408,6 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
 #include "pg_hji_solve.hip"         // pg_hji_solve: the reachable-tube sweeps that make an HJI grid (thread = node)
 #include "pg_speed_plan.hip"        // pg_plan_speeds: friction-limited speed profiles of a path library x plan-set library (lane = set)
 #include "pg_path_make.hip"         // pg_make_paths: a path library from line, arc and clothoid segments (workgroup = path)
+#include "pg_path_fit.hip"          // pg_fit_paths: a path library fitted to waypoints, cubic splines resampled in arc length (workgroup = path)
 
 }  // namespace pg

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan, path_segment as _default_path_segment
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -20,6 +20,7 @@ c_i32p = C.POINTER(C.c_int32)
 SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
 PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
+FIT_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_fit_stats._fields_])      # 80 bytes, the layout of pg_fit_stats
 
 
 def is_solved(status):
@@ -330,6 +331,82 @@ class BatchedTrajectoryTrackingMPC:
         st = (_lib.pg_path_stats * n)()
         self._chk(self.lib.pg_make_paths(self.h, n, specs, len(segs), segs, Lmax, int(bool(install)), _p(L, c_i32p), None, _p(out), st), "pg_make_paths")
         return self._made_tubes(out, L, 1, install), np.frombuffer(st, dtype=PATH_STATS_DTYPE).copy()
+
+    # ---- fitting the path (pg_fit_paths): a library of paths through waypoints, cubic splines resampled in arc length on the device ----
+    @classmethod
+    def pack_fit_specs(cls, paths, Lmax=None, precision="f64"):
+        """paths: a list of dict(waypoints=[vehicles.waypoint(**overrides) dicts or pg_waypoint structures], n_knots=.., V_ref=6.0, closed=False) -> (specs, waypoints,
+        Lmax): ctypes arrays of pg_fit_spec [n_path] and pg_waypoint [all waypoints, path after path], and Lmax (None: the largest n_knots).  Raises ValueError for what the
+        library refuses with PG_ERR_INVALID (include/pigeon_mpc.h); precision names the library's element type for the "dense" refusal."""
+        paths = list(paths)
+        if not paths:
+            raise ValueError("fit_paths: at least one path")
+
+        def fill(rec, w):
+            full = _default_waypoint(**w)
+            for name, _ in _lib.pg_waypoint._fields_:
+                setattr(rec, name, float(full[name]))
+        lists = []
+        for k, p in enumerate(paths):
+            unknown = set(p) - {"waypoints", "n_knots", "V_ref", "closed"}
+            if unknown or "waypoints" not in p or "n_knots" not in p:
+                raise ValueError(f"fit_paths: path {k} is dict(waypoints=, n_knots=, V_ref=6.0, closed=False); got {sorted(p)}")
+            lists.append(list(p["waypoints"]))
+        wps = cls._pack(_lib.pg_waypoint, [w for l in lists for w in l], fill)
+        specs = (_lib.pg_fit_spec * len(paths))()
+        eps = 2.0 ** -23 if precision == "f32" else 2.0 ** -52
+        at = 0
+        for k, (p, l) in enumerate(zip(paths, lists)):
+            n_knots, V, cl, n = p["n_knots"], float(p.get("V_ref", 6.0)), bool(p.get("closed", False)), len(l)
+            if not (n_knots == int(n_knots) and 2 <= n_knots <= 2**31 - 1):
+                raise ValueError(f"fit_paths: path {k} needs an integer n_knots >= 2")
+            if n < (3 if cl else 2) or (cl and n_knots < 3):
+                raise ValueError(f"fit_paths: path {k} has {n} waypoints and {int(n_knots)} knots (an open path needs 2 waypoints, a closed one 3 waypoints and 3 knots)")
+            if not (math.isfinite(V) and V > 0):
+                raise ValueError(f"fit_paths: path {k} needs a finite V_ref > 0")
+            C_sum = 0.0
+            for i in range(n):
+                w = wps[at + i]
+                if not all(math.isfinite(v) for v in (w.E, w.N, w.edge_L, w.edge_R)):
+                    raise ValueError(f"fit_paths: waypoint {i} of path {k} has a non-finite field")
+                if not w.edge_L > w.edge_R:
+                    raise ValueError(f"fit_paths: waypoint {i} of path {k} needs edge_L > edge_R")
+            for j in range(n if cl else n - 1):
+                a, b = wps[at + j], wps[at + (j + 1) % n]
+                dE = b.E - a.E; dN = b.N - a.N
+                h = math.sqrt(dE * dE + dN * dN)
+                if not (math.isfinite(h) and h > 0):
+                    raise ValueError(f"fit_paths: waypoints {j} and {(j + 1) % n} of path {k} lie at the same point (a chord must be finite and > 0)")
+                C_sum += h
+            per = float(int(n_knots) - 1)
+            if not (per <= 1.0 / (4.0 * eps) and C_sum / per >= 2.0 ** -100 and C_sum <= 2.0 ** 100):
+                raise ValueError(f"fit_paths: the knots of path {k} are so dense that s cannot be shown to increase strictly in the library's element type")
+            s = specs[k]
+            s.V_ref, s.wp0, s.n_wp, s.n_knots, s.closed = V, at, n, int(n_knots), int(cl)
+            at += n
+        most = max(s.n_knots for s in specs)
+        if Lmax is None:
+            Lmax = most
+        if not (Lmax == int(Lmax) and max(2, most) <= Lmax <= 2**31 - 1):
+            raise ValueError(f"fit_paths: Lmax is an integer >= the largest n_knots ({most})")
+        if len(paths) * 10.0 * Lmax * 8.0 >= 2.0 ** 62:
+            raise ValueError("fit_paths: n_path * 10 * Lmax elements are more than the allocation arithmetic holds")
+        return specs, wps, int(Lmax)
+
+    def fit_paths(self, paths, Lmax=None, install=False):
+        """A path library through waypoints on the device (pg_fit_paths; the scheme is stated in include/pigeon_mpc.h): paths = a list of dict(waypoints=[vehicles.waypoint
+        dicts, e.g. vehicles.waypoints_from_tube(tube, every=4, closed=True)], n_knots=.., V_ref=6.0, closed=False).  An interpolating cubic spline over the chord length,
+        natural (open) or periodic (closed: do not repeat the first point), resampled at n_knots knots equally spaced in arc length; V = V_ref, A = 0, t = s / V_ref.
+        Returns (tubes, closed, stats): the TrajectoryTubes, the int32 flags plan_speeds takes as closed=, and a structured array with the fields of pg_fit_stats (length,
+        turn, closure_pos, closure_psi, kappa_abs_max, ds, chord_min, chord_max, s_err_max).  install=True makes the tubes the handle's trajectory library (as
+        set_trajectories(tubes) would, without the host round trip; select with set_trajectory_index)."""
+        specs, wps, Lmax = self.pack_fit_specs(paths, Lmax, "f32" if self.precision == "f32" else "f64")
+        n = len(specs)
+        out = np.zeros((n, 10, Lmax))
+        L = np.zeros(n, dtype=np.int32); cl = np.zeros(n, dtype=np.int32)
+        st = (_lib.pg_fit_stats * n)()
+        self._chk(self.lib.pg_fit_paths(self.h, n, specs, len(wps), wps, Lmax, int(bool(install)), _p(L, c_i32p), _p(cl, c_i32p), _p(out), st), "pg_fit_paths")
+        return self._made_tubes(out, L, 1, install), cl, np.frombuffer(st, dtype=FIT_STATS_DTYPE).copy()
 
     # ---- the per-instance libraries share one protocol (pg_set_<name>_sets / pg_set_<name>_index / pg_clear_<name>_sets / pg_get_<name>_sets): the four routines below ----
     @staticmethod

@@ -183,6 +183,37 @@ def path_segment(**overrides):
     return g
 
 
+WAYPOINT_FIELDS = ("E", "N", "edge_L", "edge_R")
+
+
+def waypoint(**overrides):
+    """One waypoint for fit_paths (pg_waypoint).  waypoint() is the library's default (pg_default_waypoint): the origin with the edges at +4 / -4 m (trajectories.jl:43-44);
+    waypoint(E=12.0, N=-3.5, edge_L=3.0) is a surveyed point with its own left edge.  The edges are linear in the chord parameter between two waypoints."""
+    w = dict(E=0.0, N=0.0, edge_L=4.0, edge_R=-4.0)
+    for k, v in overrides.items():
+        if k not in w:
+            raise KeyError(f"{k} is not a field of a waypoint: {WAYPOINT_FIELDS}")
+        w[k] = float(v)
+    return w
+
+
+def waypoints_from_tube(tube, every=1, closed=False):
+    """The knots 0, every, 2 every, .. of a TrajectoryTube -- or of a committed path as its file holds it (the keys posE_m, posN_m, edgeL_m, edgeR_m) -- as a waypoint list
+    for fit_paths: "the same track thinned to every n-th point".  closed=True: the file repeats knot 0 as its last knot, which is dropped (fit_paths closes the path itself);
+    closed=False: the last knot is kept whatever `every` is, so the path ends where the tube ends."""
+    if not (every == int(every) and every >= 1):
+        raise ValueError("waypoints_from_tube: every is an integer >= 1")
+    if isinstance(tube, dict) or hasattr(tube, "files"):
+        E, N, eL, eR = (tube[k] for k in ("posE_m", "posN_m", "edgeL_m", "edgeR_m"))
+    else:
+        E, N, eL, eR = tube.E, tube.N, tube.edge_L, tube.edge_R
+    n = len(E) - 1 if closed else len(E)
+    idx = list(range(0, n, int(every)))
+    if not closed and idx[-1] != n - 1:
+        idx.append(n - 1)
+    return [waypoint(E=E[i], N=N[i], edge_L=eL[i], edge_R=eR[i]) for i in idx]
+
+
 def line_segments(length, **edges):
     """A straight of `length` m: one segment.  **edges: the edge fields of path_segment, applied to every segment (as in the other builders)."""
     return [path_segment(length=length, **edges)]
