@@ -625,7 +625,10 @@ int pg_set_human_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
 int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out);
 
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
- * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1). */
+ * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1).
+ * An install first drops the installed grid and then builds the new table (never two tables side by side: the cell records of the real grid take 1.9 to 19 GB).
+ * After an install that fails past the argument checks (PG_ERR_HIP: an allocation, a copy, the build launch) the handle has NO HJI grid, no device memory of the call
+ * remains, and pg_last_error says why.  The same holds for pg_hji_solve with install != 0 once its sweeps have succeeded. */
 int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV);
 int pg_clear_hji_grid(pg_handle* h);
 

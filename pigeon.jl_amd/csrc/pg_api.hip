@@ -7,9 +7,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include "pg_kernels.hip"
+#include "pg_own.hpp"
 
 using namespace pg;
 
@@ -18,16 +20,13 @@ using namespace pg;
 struct IndexArray {
     const char *what, *setter; int* d = nullptr; std::vector<int32_t> host;
     int covered() const { return (int)host.size(); }
-    void release() { if (d) (void)hipFree(d); d = nullptr; host.clear(); }
 };
 // One library of per-instance sets: the sets as the caller installed them, their device records, the selection (setlib_install / setlib_clear / setlib_get below)
 template <class Host, class Dev> struct SetLib {
     IndexArray idx; std::vector<Host> sets; Dev* d = nullptr;
     bool on() const { return !sets.empty(); }                                             // the host knows whether a library is installed: that alone adds its kernel to a rollout step
     const int* index() const { return sets.size() > 1 ? idx.d : (const int*)nullptr; }    // what the kernels are handed: a library of at most one set needs no index
-    void release() { if (d) (void)hipFree(d); d = nullptr; sets.clear(); idx.release(); }
 };
-template <class... P> static void dev_release(P*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
 // One history registration (pg_set_*_history_dev): a device record [steps][B][width] of the caller's.  One-shot: the next rollout call takes it, whether it succeeds or not
 struct HistSlot {
     real* buf = nullptr; int steps = 0;
@@ -77,7 +76,7 @@ struct pg_handle {
     // ---- the five rollout libraries that keep state beside their sets: one record each.  lib: the sets and the selection; streams: a seeded library's; hist: the one-shot
     // history registration(s); fresh: no state of the previous step exists, the law restarts at the next step under the library (restart_on_clock lists them); valid: the
     // record the getter reads was written by a rollout step since the inputs were installed (restart_on_inputs); steps_stat: read-only option "stat_<library>_steps";
-    // cleared(): what pg_clear_*_sets resets beside the sets; release(): pg_destroy ----
+    // cleared(): what pg_clear_*_sets resets beside the sets (the device buffers stay, and die with the handle: pg_handle::mem) ----
     // sensor library (pg_set_sensor_sets / pg_set_sensor_index / pg_set_sensor_seed): what the controller of a rollout step is handed in place of the true state.  Beside the
     // sets: the streams and the seed, the measured state meas [cap][6] and, with the tracking summary, the projection of the TRUE state sep_true [cap][4].  Nothing is
     // allocated without a library.  No `fresh`: the law has no state.  Clearing the sets leaves seed and streams as they are
@@ -85,7 +84,6 @@ struct pg_handle {
         SetLib<pg_sensor, DevSensor> lib{{"sensor", "pg_set_sensor_index"}}; SeedStreams streams; HistSlot hist;      // hist: pg_set_measured_history_dev
         real *meas = nullptr, *sep_true = nullptr; bool valid = false; int64_t steps_stat = 0;
         void cleared() { valid = false; hist.clear(); }
-        void release() { lib.release(); dev_release(streams.d, meas, sep_true); }
     } sensor;
     // actuator library (pg_set_actuator_sets / pg_set_actuator_index): what the plant of a rollout step is handed in place of the command.  Beside the sets, allocated when a
     // rollout first runs under a library: the actuator's position pos [cap][3], the command ring [PG_ACT_MAX_DELAY][cap][3], plant_u [cap][3] (the plant kernel's
@@ -97,7 +95,6 @@ struct pg_handle {
         bool feedback = false;                                    // some installed set has feedback == 1
         bool fresh = true; int64_t steps_stat = 0;
         void cleared() { feedback = false; fresh = true; applied_hist.clear(); command_hist.clear(); }      // (a library installed later starts from the command it finds)
-        void release() { lib.release(); dev_release(pos, ring, plant_u, seen); }
     } actuator;
     // disturbance library (pg_set_disturbance_sets / pg_set_disturbance_index / pg_set_disturbance_seed): what acts on the ego plant of a rollout step from outside.  Beside
     // the sets: the streams and the seed (its own, as the sensor library keeps its own), and, allocated when a rollout first runs under a library: the gust state
@@ -107,7 +104,6 @@ struct pg_handle {
         SetLib<pg_disturbance, DevDisturbance> lib{{"disturbance", "pg_set_disturbance_index"}}; SeedStreams streams; HistSlot hist;      // hist: pg_set_disturbance_history_dev
         real *n = nullptr, *w = nullptr; DevVehicle* veh = nullptr; bool fresh = true, valid = false; int64_t steps_stat = 0;
         void cleared() { fresh = true; valid = false; hist.clear(); }      // (a library installed later starts a gust of its own)
-        void release() { lib.release(); dev_release(streams.d, n, w, veh); }
     } disturbance;
     // estimator library (pg_set_estimator_sets / pg_set_estimator_index): a fixed-gain observer between the sensor and the controller of a rollout step.  Beside the sets,
     // allocated at the first install: the estimate x [cap][6] (what the gate and the compute calls of a step are handed as the state) and u [cap][3], the control
@@ -116,7 +112,6 @@ struct pg_handle {
         SetLib<pg_estimator, DevEstimator> lib{{"estimator", "pg_set_estimator_index"}}; HistSlot hist;      // hist: pg_set_estimated_history_dev
         real *x = nullptr, *u = nullptr; bool fresh = true, valid = false; int64_t steps_stat = 0;
         void cleared() { fresh = true; valid = false; hist.clear(); }      // (a library installed later starts from its first measurement)
-        void release() { lib.release(); dev_release(x, u); }
     } estimator;
     // human library (pg_set_human_sets / pg_set_human_index / pg_set_human_seed): the driver of the other car in the safety and node rollouts.  Beside the sets: the streams
     // and the seed (its own), and, allocated when a rollout first runs under a library: the driver's control u [cap][2] (k_human writes it, the step's plant launch reads
@@ -125,7 +120,6 @@ struct pg_handle {
         SetLib<pg_human, DevHuman> lib{{"human", "pg_set_human_index"}}; SeedStreams streams; HistSlot hist;      // hist: pg_set_human_history_dev
         real *u = nullptr, *n = nullptr; bool script = false, fresh = true, valid = false; int64_t steps_stat = 0;
         void cleared() { script = false; fresh = true; valid = false; hist.clear(); }      // (a library installed later starts a driver of its own)
-        void release() { lib.release(); dev_release(streams.d, u, n); }
     } human;
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
@@ -159,8 +153,9 @@ struct pg_handle {
     int node_parity = 0; bool node_recheck = false;           // node_recheck: the last step was a node step (some instance may have no solution: launch_nodes queues k_nodes_recheck)
     bool node_fresh = true;                                   // the node counts restart at the next node step (the clock restarted since they were last written)
     int *d_status = nullptr, *d_iters = nullptr, *d_polish = nullptr; uint16_t* d_active = nullptr;
-    // HJI grid
-    HjiView hv; float *d_knots = nullptr, *d_hnodes = nullptr, *d_hcells = nullptr; bool has_hji = false;
+    // HJI grid: the view the kernels are handed (knots and cells point into the two buffers, nodes is null: the node records die with the call that installs), the two
+    // buffers, and whether a grid is installed (dc.has_hji mirrors `on` for the kernels).  Written by hji_table_clear and hji_table_build only
+    struct HjiTable { HjiView hv; float *knots = nullptr, *cells = nullptr; bool on = false; HjiTable() { memset(&hv, 0, sizeof(hv)); } } hji;
     hipEvent_t ev[4]; bool ev_ok = false; float phase_ms[3] = {0, 0, 0}; bool timing_valid = false;
     size_t solve_lds = 0; bool solve_ring = false;
     real* d_walls = nullptr;                                    // [cap][N][2] wall extension
@@ -185,9 +180,17 @@ struct pg_handle {
     bool qp_embedded = true; int lat_pack_only = 1;            // lateral formulation: the embedded QP block is current (k_qp_dec wrote it) / option "lat_pack_only": steps write the packed records only
     bool qp_stale = false;                                    // the lateral solver was switched (option "lateral_solver") after the last update_QP!: pg_solve returns PG_ERR_STATE until the QP data are rebuilt
     bool solve_lat = false; size_t lat_lds = 0;               // lateral formulation: its own kernel k_solve_lat (option "lateral_solver" = 2 keeps the embedding in k_solve)
+    pg_handle() = default; pg_handle(const pg_handle&) = delete; pg_handle& operator=(const pg_handle&) = delete;      // (never copied or moved: `mem` holds addresses of members)
+    // what is not device memory; the device is current (pg_create set it, pg_destroy sets it)
+    ~pg_handle() {
+        if (h_stage) (void)hipHostFree(h_stage); if (sg.x) (void)hipGraphExecDestroy(sg.x); if (sg.g) (void)hipGraphDestroy(sg.g); if (sg.own) (void)hipStreamDestroy(sg.own);
+        if (ev_ok) for (int i = 0; i < 4; i++) (void)hipEventDestroy(ev[i]);
+    }
+    // Every device buffer above is allocated through mem (ensure / adopt below) and freed by it, here or in a drop.  LAST member: destroyed first
+    HandleBufs mem;
 };
 
-#define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(e_); return PG_ERR_HIP; } } while (0)
+#define HIPCHK(h, call) do { const hipError_t e_ = (hipError_t)(call); if (e_ != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(e_); return PG_ERR_HIP; } } while (0)
 #define LAUNCH_CHECK(h) do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { (h)->err = std::string("kernel launch: ") + hipGetErrorString(e_); return PG_ERR_HIP; } } while (0)
 #define REQUIRE(h, cond, msg) do { if (!(cond)) { if (h) (h)->err = (msg); return PG_ERR_INVALID; } } while (0)
 // a *_problem check (why: its text, or nullptr when nothing is wrong) refuses with "<who><why>"; `who` carries its own ": "
@@ -195,33 +198,28 @@ struct pg_handle {
 
 static std::string g_create_error;
 
+// what the two owners of pg_own.hpp allocate and free with: the library's only calls of either
+int pg_dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+void pg_dev_free(void* p) { (void)hipFree(p); }
+// The one way a buffer of the handle comes to be: `count` elements for member p, allocated when it is first needed and owned by h->mem from then on
+template <class T> static int ensure(pg_handle* h, T*& p, size_t count) {
+    const int e = h->mem.get(p, count);
+    if (e) { h->err = "device allocation of " + std::to_string(count * sizeof(T)) + " bytes failed: " + hipGetErrorString((hipError_t)e); return PG_ERR_HIP; }
+    return PG_OK;
+}
 // the stream ids of a seeded library on the device, [capacity]: the installed ones, then stream[b] = b
 int SeedStreams::sync(pg_handle* h) {
     if (d && !dirty) return PG_OK;
     const size_t cap = (size_t)h->cfg.batch_capacity;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!d) HIPCHK(h, hipMalloc((void**)&d, cap * sizeof(unsigned long long)));
+    { const int rc = ensure(h, d, cap); if (rc) return rc; }
     std::vector<unsigned long long> full(cap);
     for (size_t b = 0; b < cap; b++) full[b] = b < host.size() ? (unsigned long long)host[b] : (unsigned long long)b;
     HIPCHK(h, hipMemcpy(d, full.data(), cap * sizeof(unsigned long long), hipMemcpyHostToDevice));
     dirty = false;
     return PG_OK;
 }
-// a device buffer of `count` elements that is allocated when it is first needed
-template <class T> static int ensure(pg_handle* h, T*& p, size_t count) {
-    if (!p) HIPCHK(h, hipMalloc((void**)&p, count * sizeof(T)));
-    return PG_OK;
-}
-// The device memory of one call (the makers, install_trajectories): alloc() remembers what it allocated, and what the call still holds is freed on every way out.
-// give() is the one way a buffer leaves: to the handle, which owns it from then on (the caller's pointer is nulled: nothing in the call reads the buffer afterwards)
-struct CallBufs {
-    std::vector<void*> held;
-    CallBufs() = default; CallBufs(const CallBufs&) = delete; CallBufs& operator=(const CallBufs&) = delete;
-    ~CallBufs() { for (void* p : held) if (p) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T*& p, size_t count) { p = nullptr; const hipError_t e = hipMalloc((void**)&p, count * sizeof(T)); if (e == hipSuccess) held.push_back(p); return e; }
-    template <class T> T* give(T*& p) { for (void*& q : held) if (q == (void*)p) q = nullptr; T* const out = p; p = nullptr; return out; }
-};
-// The walk over the seven dimensions of an HJI grid, written here only (pg_set_hji_grid, pg_hji_solve; hji_install_nodes reads its result): nodes n, knots nk and, per
+// The walk over the seven dimensions of an HJI grid, written here only (pg_set_hji_grid, pg_hji_solve; hji_table_build reads its result): nodes n, knots nk and, per
 // dimension, the stride of its node index and the offset of its knots.  Refuses in the name of `who` fewer than 2 knots.  fill(): into a device view (HjiView, HjiSolveGrid)
 struct HjiWalk {
     int dims[7], koff[7]; long stride[7]; size_t n; int nk;
@@ -339,17 +337,19 @@ static DevControlRec make_control_rec(int formulation, const pg_control_params& 
 }
 
 // Lateral formulation: which kernel solves it, and the buffers that kernel needs.  Called by pg_create and by pg_set_option("lateral_solver" / "lat_workspace").
-static int configure_lateral(pg_handle* h, std::string* why) {
+// A failure says why in h->err
+static int configure_lateral(pg_handle* h) {
     DevCfg& C = h->dc; const pg_config* cfg = &h->cfg; const int N = C.N; const size_t cap = (size_t)cfg->batch_capacity;
     const bool want = h->lateral_solver == 1 || (h->lateral_solver != 2 && !(cfg->polish && N <= 20));
     h->solve_lat = cfg->formulation == PG_DECOUPLED && want;
     if (!h->solve_lat) { C.lat_pack = nullptr; return PG_OK; }
-    if (!h->d_lat && hipMalloc((void**)&h->d_lat, cap * N * LATP * sizeof(real)) != hipSuccess) { *why = "hipMalloc failed for the packed lateral stage records"; return PG_ERR_HIP; }
+    int rc;
+    if ((rc = ensure(h, h->d_lat, cap * N * LATP))) return rc;                          // the packed lateral stage records
     C.lat_pack = h->d_lat;
-    if (!h->d_lat_aux && hipMalloc((void**)&h->d_lat_aux, ((cap + 1) * 64 * LAT_AUX + 8) * sizeof(real)) != hipSuccess)      /* (+ 1: the spare block idle lane groups of a resumed launch write) */ { *why = "hipMalloc failed for k_solve_lat's multiplier block"; return PG_ERR_HIP; }
+    if ((rc = ensure(h, h->d_lat_aux, (cap + 1) * 64 * LAT_AUX + 8))) return rc;      // k_solve_lat's multiplier block (+ 1: the spare block idle lane groups of a resumed launch write)
     C.lat_aux = h->d_lat_aux;
     C.lat_zero = h->d_lat_aux + (cap + 1) * 64 * LAT_AUX;      // (+ 8 stored zeros: DevCfg::lat_zero)
-    if (hipMemset((void*)C.lat_zero, 0, 8 * sizeof(real)) != hipSuccess) { *why = "hipMemset failed"; return PG_ERR_HIP; }
+    if (hipMemset((void*)C.lat_zero, 0, 8 * sizeof(real)) != hipSuccess) { h->err = "hipMemset failed"; return PG_ERR_HIP; }
     // (round 4: with the wall rows the two-slot register variant spills 720 B per lane since the warm start was added -- 1.57 ms at N = 30 against 1.36 ms through the
     // workspace; without them the registers still win, 0.94 against 1.01 ms)
     // (round 6: horizons of 17..32 intervals WITHOUT the wall rows used the two-slot register instantiation, k_solve_lat<2, .., false> -- 512 registers + 300 B of scratch, the
@@ -358,12 +358,11 @@ static int configure_lateral(pg_handle* h, std::string* why) {
     // instantiation is retired, those horizons take the workspace variant like the longer ones -- and its straggler hand-over with it)
     h->lat_mem = N > 16 || h->lat_mem_forced;
     if (h->lat_mem) {
-        if (!h->d_lat_ws && hipMalloc((void**)&h->d_lat_ws, lat_ws_bytes(cap)) != hipSuccess) { *why = "hipMalloc failed for k_solve_lat's workspace"; return PG_ERR_HIP; }
+        if ((rc = ensure(h, h->d_lat_ws, lat_ws_bytes(cap)))) return rc;                              // k_solve_lat's workspace
         C.lat_ws = h->d_lat_ws;
-        if (!h->d_lat_spc && hipMalloc((void**)&h->d_lat_spc, lat_spc_bytes((int)cap, N)) != hipSuccess) { *why = "hipMalloc failed for k_solve_lat's stage constants"; return PG_ERR_HIP; }
+        if ((rc = ensure(h, h->d_lat_spc, lat_spc_bytes((int)cap, N) / sizeof(real)))) return rc;      // ... its stage constants
         C.lat_spc = h->d_lat_spc;
-        if (!h->d_hand_r && hipMalloc((void**)&h->d_hand_r, cap * LAT_HAND_R * sizeof(real)) != hipSuccess) { *why = "hipMalloc failed for k_solve_lat's hand-over records"; return PG_ERR_HIP; }
-        if (!h->d_hand_i && hipMalloc((void**)&h->d_hand_i, cap * LAT_HAND_I * sizeof(int)) != hipSuccess) { *why = "hipMalloc failed for k_solve_lat's hand-over records"; return PG_ERR_HIP; }
+        if ((rc = ensure(h, h->d_hand_r, cap * LAT_HAND_R)) || (rc = ensure(h, h->d_hand_i, cap * LAT_HAND_I))) return rc;      // ... its hand-over records
     } else C.lat_ws = nullptr;
     return PG_OK;
 }
@@ -417,18 +416,6 @@ int pg_default_config_decoupled(pg_config* c) {
     return PG_OK;
 }
 
-static void free_all(pg_handle* h) {
-    void* ptrs[] = {h->d_traj, h->d_traj_len, h->d_in, h->d_out, h->d_solved, h->d_ts, h->d_dt, h->d_prev_ts, h->d_sep, h->d_nodes,
-                    h->d_qp, h->d_x7, h->d_vg8, h->d_Mb, h->d_solx, h->d_sigma, h->d_mu, h->d_active, h->d_knots, h->d_hnodes, h->d_hcells, h->d_pol_u2, h->d_pol_u, h->d_pol_src, h->d_walls, h->d_mask, h->d_polish, h->d_lam, h->d_todo, h->d_order, h->d_naux, h->d_progress, h->d_lat, h->d_lat_aux, h->d_lat_ws, h->d_tstart, h->d_hand_r, h->d_hand_i, h->d_lat_spc, h->d_vmin, h->d_breach, h->d_keep, h->d_node, h->d_applied, h->d_tend, h->d_track, h->d_track_i};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->traj_idx.release(); h->cp.release(); h->plants.release(); h->sensor.release(); h->actuator.release(); h->disturbance.release(); h->estimator.release(); h->human.release();
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->sg.x) (void)hipGraphExecDestroy(h->sg.x);
-    if (h->sg.g) (void)hipGraphDestroy(h->sg.g);
-    if (h->sg.own) (void)hipStreamDestroy(h->sg.own);
-    if (h->ev_ok) for (int i = 0; i < 4; i++) (void)hipEventDestroy(h->ev[i]);
-}
-
 const char* pg_last_error(const pg_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int pg_create(const pg_config* cfg, pg_handle** out) {
@@ -452,7 +439,7 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
     }
 #endif
     if (hipSetDevice(cfg->device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return PG_ERR_HIP; }
-    pg_handle* h = new pg_handle();
+    std::unique_ptr<pg_handle> own(new pg_handle()); pg_handle* const h = own.get();      // (an exit below destroys the handle and, through h->mem, every buffer it has by then)
     h->cfg = *cfg;
     DevCfg& C = h->dc; memset(&C, 0, sizeof(C));
     fill_dev_params(C, cfg); C.Ns = cfg->N_short; C.Nl = cfg->N_long; C.N = C.Ns + C.Nl; C.NN = C.N + 1;
@@ -471,20 +458,18 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
     C.ipm_max_iter = cfg->ipm_max_iter; C.ipm_tol = (real)cfg->ipm_tol; C.ipm_mu0 = (real)cfg->ipm_mu0;
     C.polish = cfg->polish != 0; C.polish_rho = (real)cfg->polish_rho; C.polish_tol = (real)cfg->polish_tol; C.polish_ipm_tol = (real)cfg->polish_ipm_tol; C.warm_polish = cfg->warm_polish != 0; C.cold_guess = cfg->cold_guess > 0 ? cfg->cold_guess : 0;
     const size_t cap = (size_t)cfg->batch_capacity; const int N = C.N, NN = C.NN;
-#define ALLOC(ptr, count, type) do { if (hipMalloc((void**)&(ptr), (size_t)(count) * sizeof(type)) != hipSuccess) { g_create_error = "hipMalloc failed for " #ptr; free_all(h); delete h; return PG_ERR_HIP; } } while (0)
+#define ALLOC(ptr, count) do { if (ensure(h, ptr, (size_t)(count))) { g_create_error = h->err; return PG_ERR_HIP; } } while (0)
     h->in_dbl_off = (cap * 13 * sizeof(real) + 7) / 8 * 8; h->in_bytes = h->in_dbl_off + cap * 16; h->out_bytes = cap * (3 * sizeof(real) + 8);
-    ALLOC(h->d_in, h->in_bytes, char); ALLOC(h->d_out, h->out_bytes, char);
+    ALLOC(h->d_in, h->in_bytes); ALLOC(h->d_out, h->out_bytes);
     h->d_state = (real*)h->d_in; h->d_control = h->d_state + cap * 6; h->d_other = h->d_control + cap * 3; h->d_t0 = (double*)(h->d_in + h->in_dbl_off); h->d_toff = h->d_t0 + cap;
     h->d_u = (real*)h->d_out; h->d_status = (int*)(h->d_u + cap * 3); h->d_iters = h->d_status + cap;
-    ALLOC(h->d_tstart, cap, double);
-    ALLOC(h->d_solved, 2 * cap, int); h->d_wfail = h->d_solved + cap; ALLOC(h->d_mask, cap, uint8_t); ALLOC(h->d_ts, cap * NN, double); ALLOC(h->d_dt, cap * N, double); ALLOC(h->d_prev_ts, cap * NN, double);
-    ALLOC(h->d_sep, cap * 4, real); ALLOC(h->d_nodes, cap * NN * 10, real); ALLOC(h->d_qp, cap * C.qp_len, real);
-    ALLOC(h->d_x7, cap * 7, real); ALLOC(h->d_vg8, cap * 8, real); ALLOC(h->d_Mb, cap * 4, real);
-    ALLOC(h->d_solx, cap * NN * 8, real); ALLOC(h->d_sigma, cap * N * 3, real); ALLOC(h->d_mu, cap, real);
-    ALLOC(h->d_polish, cap, int); ALLOC(h->d_todo, cap + CTL_WORDS, int); ALLOC(h->d_lam, cap * N * 16, real); ALLOC(h->d_order, 2 * cap + ORDER_CNT_WORDS, int); ALLOC(h->d_naux, cap * NN * 4, real); ALLOC(h->d_progress, pipe_words(h), int); ALLOC(h->d_active, cap * N, uint16_t);
-    if (cfg->walls) { ALLOC(h->d_walls, cap * N * 2, real); C.walls = 1; C.wall_weight = (real)cfg->wall_weight; C.wall_edges = h->d_walls; }
-    ALLOC(h->d_pol_u2, cap * 2, real); ALLOC(h->d_pol_u, cap * 3, real); ALLOC(h->d_pol_src, cap, int);
-    ALLOC(h->d_vmin, cap, real); ALLOC(h->d_breach, 2 * cap, int);
+    ALLOC(h->d_tstart, cap); ALLOC(h->d_solved, 2 * cap); h->d_wfail = h->d_solved + cap; ALLOC(h->d_mask, cap); ALLOC(h->d_ts, cap * NN); ALLOC(h->d_dt, cap * N); ALLOC(h->d_prev_ts, cap * NN);
+    ALLOC(h->d_sep, cap * 4); ALLOC(h->d_nodes, cap * NN * 10); ALLOC(h->d_qp, cap * C.qp_len);
+    ALLOC(h->d_x7, cap * 7); ALLOC(h->d_vg8, cap * 8); ALLOC(h->d_Mb, cap * 4);
+    ALLOC(h->d_solx, cap * NN * 8); ALLOC(h->d_sigma, cap * N * 3); ALLOC(h->d_mu, cap);
+    ALLOC(h->d_polish, cap); ALLOC(h->d_todo, cap + CTL_WORDS); ALLOC(h->d_lam, cap * N * 16); ALLOC(h->d_order, 2 * cap + ORDER_CNT_WORDS); ALLOC(h->d_naux, cap * NN * 4); ALLOC(h->d_progress, pipe_words(h)); ALLOC(h->d_active, cap * N);
+    if (cfg->walls) { ALLOC(h->d_walls, cap * N * 2); C.walls = 1; C.wall_weight = (real)cfg->wall_weight; C.wall_edges = h->d_walls; }
+    ALLOC(h->d_pol_u2, cap * 2); ALLOC(h->d_pol_u, cap * 3); ALLOC(h->d_pol_src, cap); ALLOC(h->d_vmin, cap); ALLOC(h->d_breach, 2 * cap);
     // The lateral formulation has a solve kernel of its own (k_solve_lat, pg_solve_lat.hip) for horizons beyond 20 intervals.  Shorter ones -- the reference's on-vehicle
     // N_short = 5, N_long = 10 among them -- stay with the embedding in k_solve when the polish is on: its active-set rounds from the empty set serve a short lateral QP
     // without any interior-point iteration (N = 15, 4096 instances: 0.12 ms against 0.37), an advantage that is gone at N = 30 (2.4 against 1.5 ms) and reversed at
@@ -494,12 +479,11 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
         C.lat_mu0_cost = real(10.0); C.lat_pin = 1; C.lat_polish2 = 1; C.lat_far_cost = real(3e4); C.lat_rho_scale = sizeof(real) == 8 ? real(1e3) : real(1.0); C.lat_polish_rounds = 3; C.lat_settle = 0;
         C.lat_warm_rounds = 2;      /* (2 since the two-launch warm step: an attempt that needs a third working set is cheaper to hand to the cold list: 2.03 -> 1.95 ms, 2.9 -> 2.7 with walls) */
         C.lat_wipm = 0; C.lat_wmu = real(1e-2); C.lat_wtau = real(1e-4); C.lat_aux_gate = 1;
-        std::string why;
-        if (configure_lateral(h, &why) != PG_OK) { g_create_error = why; free_all(h); delete h; return PG_ERR_HIP; }
+        if (configure_lateral(h) != PG_OK) { g_create_error = h->err; return PG_ERR_HIP; }
     }
 #undef ALLOC
     h->stage_bytes = h->in_bytes > h->out_bytes ? h->in_bytes : h->out_bytes;          // inputs: state 6 + control 3 + other 4 (real) + t0 + time_offset (double); outputs reuse the front of it
-    if (hipHostMalloc((void**)&h->h_stage, h->stage_bytes, hipHostMallocDefault) != hipSuccess) { g_create_error = "hipHostMalloc failed for the staging buffer"; free_all(h); delete h; return PG_ERR_HIP; }
+    if (hipHostMalloc((void**)&h->h_stage, h->stage_bytes, hipHostMallocDefault) != hipSuccess) { g_create_error = "hipHostMalloc failed for the staging buffer"; return PG_ERR_HIP; }
     // initial ts = 1..NN (model_predictive_control.jl:13), solved = false
     {
         std::vector<double> ts(cap * NN), dt(cap * N, 1.0);
@@ -515,16 +499,16 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
         (void)hipMemset(h->d_lam, 0, cap * N * 16 * sizeof(real));          // pg_get_multipliers promises 0 off the working set: the kernels write only the rows they own
         (void)hipMemset(h->d_active, 0, cap * N * sizeof(uint16_t));
         (void)hipMemset(solve_ctl(h, 0), 0, CTL_WORDS * sizeof(int));
-        if (hipDeviceSynchronize() != hipSuccess) { g_create_error = "initial fills failed"; free_all(h); delete h; return PG_ERR_HIP; }   // hipMemset may return before the fill has run
+        if (hipDeviceSynchronize() != hipSuccess) { g_create_error = "initial fills failed"; return PG_ERR_HIP; }   // hipMemset may return before the fill has run
     }
-    for (int i = 0; i < 4; i++) if (hipEventCreate(&h->ev[i]) != hipSuccess) { g_create_error = "hipEventCreate failed"; free_all(h); delete h; return PG_ERR_HIP; }
+    for (int i = 0; i < 4; i++) if (hipEventCreate(&h->ev[i]) != hipSuccess) { g_create_error = "hipEventCreate failed"; return PG_ERR_HIP; }
     h->ev_ok = true;
     // defaults of the build-defined options (pg_set_option changes them per handle; nothing here reads the process environment)
     C.hji_seed = 0; C.clip_guess = 1; C.clip_stops = 0; C.ck_riccati = 1; C.warm_trivial_cold = 1; C.hji_rounds = 0;
     // horizons up to 32 intervals keep their dynamics blocks resident in LDS (one pass over the QP data); longer ones stream them through a 4-slot ring
     h->solve_ring = N > 32;
     h->solve_lds = (size_t)((h->solve_ring ? 4 : N) * SB + 10 * NN + 8 * NN + 2 * N + 2 * N + 16 * N + 4 * N + 8 * N + 2 * N + 8 * NN + 2 * N + 72 + 100 + 8 + 72 + 4 + 32 + 2 * N + 11 * N) * sizeof(real);
-    if (h->solve_lds > 160 * 1024) { g_create_error = "horizon too long for LDS staging"; free_all(h); delete h; return PG_ERR_INVALID; }
+    if (h->solve_lds > 160 * 1024) { g_create_error = "horizon too long for LDS staging"; return PG_ERR_INVALID; }
     // hipFuncSetAttribute applies to the CURRENT DEVICE's copy of a kernel, and a later handle with a shorter horizon must not lower the limit an earlier handle of the same
     // device relies on: the largest size asked for so far is kept per device ordinal
     static size_t lds_attr_max[64] = {0};
@@ -544,12 +528,12 @@ int pg_create(const pg_config* cfg, pg_handle** out) {
     }
     h->lat_lds = lat_lds_doubles(N) * sizeof(real);
     // (N + 1 <= 64 nodes: at most 4 x 63 x 24 doubles + 72 = 48,960 B, below the 64 KB a launch may ask for without raising the function attribute)
-    if (h->solve_lat && h->lat_lds > 64 * 1024) { g_create_error = "horizon too long for k_solve_lat's LDS staging"; free_all(h); delete h; return PG_ERR_INVALID; }
-    *out = h;
+    if (h->solve_lat && h->lat_lds > 64 * 1024) { g_create_error = "horizon too long for k_solve_lat's LDS staging"; return PG_ERR_INVALID; }
+    *out = own.release();
     return PG_OK;
 }
 
-int pg_destroy(pg_handle* h) { if (!h) return PG_ERR_INVALID; (void)hipSetDevice(h->cfg.device); free_all(h); delete h; return PG_OK; }
+int pg_destroy(pg_handle* h) { if (!h) return PG_ERR_INVALID; (void)hipSetDevice(h->cfg.device); delete h; return PG_OK; }
 int pg_get_config(const pg_handle* h, pg_config* out) { if (!h || !out) return PG_ERR_INVALID; *out = h->cfg; return PG_OK; }
 int pg_get_u_normalization(const pg_handle* h, double out[2]) {
     if (!h || !out) return PG_ERR_INVALID;
@@ -672,9 +656,9 @@ int pg_set_option(pg_handle* h, const char* name, double value) {
         if (which_solver && value == 1.0 && lat_lds_doubles(h->dc.N) * sizeof(real) > 64 * 1024) { h->err = "horizon too long for k_solve_lat's LDS staging"; return PG_ERR_INVALID; }
         const int old_solver = h->lateral_solver; const bool old_forced = h->lat_mem_forced, old_lat = h->solve_lat;
         if (which_solver) h->lateral_solver = (int)value; else h->lat_mem_forced = value != 0.0;
-        std::string why;
-        if (configure_lateral(h, &why) != PG_OK) {
-            h->lateral_solver = old_solver; h->lat_mem_forced = old_forced; std::string why2; (void)configure_lateral(h, &why2);
+        if (configure_lateral(h) != PG_OK) {
+            const std::string why = h->err;
+            h->lateral_solver = old_solver; h->lat_mem_forced = old_forced; (void)configure_lateral(h);
             h->err = why; return PG_ERR_HIP;
         }
         // the two solve kernels read different QP records (k_solve: the embedded block, k_solve_lat: the packed stage records) and the last update_QP! wrote what the OLD
@@ -733,7 +717,7 @@ static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, c
     for (int b = 0; b < B; b++) REQUIRE(h, index[b] >= 0 && index[b] < n_sets, who + ": index out of range of the installed library");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!arr.d) HIPCHK(h, hipMalloc((void**)&arr.d, cap_of(h) * sizeof(int)));
+    { const int rc = ensure(h, arr.d, cap_of(h)); if (rc) return rc; }
     std::vector<int> full(cap_of(h), 0);
     for (int b = 0; b < B; b++) full[(size_t)b] = index[b];
     HIPCHK(h, hipMemcpy(arr.d, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -756,22 +740,21 @@ static int setlib_install(pg_handle* h, const char* who_, SetLib<Host, Dev>& L, 
     for (int k = 0; k < n_sets; k++) REQUIRE_NO(h, who + ": ", problem(sets[k]));
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a rollout still queued reads the library it was launched with)
-    Dev* d_new = nullptr;
+    CallBufs D; Dev* d_new = nullptr;
     if (on_device) {
         std::vector<Dev> recs((size_t)n_sets);
         for (int k = 0; k < n_sets; k++) fill(recs[(size_t)k], sets[k]);
-        HIPCHK(h, hipMalloc((void**)&d_new, recs.size() * sizeof(Dev)));
-        if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(Dev), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); h->err = who + ": copy failed"; return PG_ERR_HIP; }
+        HIPCHK(h, D.alloc(d_new, recs.size()));
+        if (hipMemcpy(d_new, recs.data(), recs.size() * sizeof(Dev), hipMemcpyHostToDevice) != hipSuccess) { h->err = who + ": copy failed"; return PG_ERR_HIP; }
     }
-    if (L.d) (void)hipFree(L.d);
-    L.d = d_new; L.sets.assign(sets, sets + n_sets); L.idx.host.clear();
+    h->mem.adopt(L.d, D.give(d_new)); L.sets.assign(sets, sets + n_sets); L.idx.host.clear();
     return PG_OK;
 }
 template <class Host, class Dev>
 static int setlib_clear(pg_handle* h, SetLib<Host, Dev>& L) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    L.release();
+    h->mem.drop(L.d); L.sets.clear(); h->mem.drop(L.idx.d); L.idx.host.clear();
     return PG_OK;
 }
 // the sets and the index as installed: *n_sets always, up to max_sets sets, index[b] = -1 where no index covers instance b
@@ -852,12 +835,10 @@ extern "C" {
 // kernels).  The rule: h->d_traj [n_traj][10][Lmax] and h->d_traj_len [n_traj] are device memory the handle owns, and h->dc.traj / traj_len / n_traj / traj_stride
 // describe exactly that pair.  The caller hands in a FINISHED library held by its CallBufs, with trajectory.t[end] of every trajectory in fp64; no call touches the
 // handle's library before this point, so one that fails earlier leaves it whole.  In this order: wait for the stream (a launch still queued reads the old pair), free
-// the old pair, take the new one (the caller's pointers are nulled), fill the view, drop the index
+// the old pair and take the new one (HandleBufs::adopt; the caller's pointers are nulled), fill the view, drop the index
 static int replace_trajectories(pg_handle* h, CallBufs& D, real*& traj, int*& len, int n_traj, int Lmax, int L0, std::vector<double>&& t_ends) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_traj) (void)hipFree(h->d_traj);
-    if (h->d_traj_len) (void)hipFree(h->d_traj_len);
-    h->d_traj = D.give(traj); h->d_traj_len = D.give(len);
+    h->mem.adopt(h->d_traj, D.give(traj)); h->mem.adopt(h->d_traj_len, D.give(len));
     const size_t stride = (size_t)10 * Lmax;
     h->traj_t_end = t_ends[0];                           // trajectory.t[end] of trajectory 0 (channel 0 = t): the stop of pg_simulate_dev's clock range
     h->traj_ends = std::move(t_ends); h->tend_dirty = true;      // ... and of every trajectory, fp64 (the window gate of the node callback)
@@ -1361,14 +1342,13 @@ int pg_sensor_draws(pg_handle* h, int32_t step0, int32_t steps, int32_t B, doubl
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = h->sensor.streams.sync(h); if (rc) return rc;
     const size_t n = (size_t)steps * (size_t)B * 6;
-    real* d = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, n * sizeof(real)));
+    CallBufs D; real* d = nullptr;
+    HIPCHK(h, D.alloc(d, n));
     hipLaunchKernelGGL(k_sensor_draws, dim3((unsigned)(((size_t)steps * B + 63) / 64)), dim3(64), 0, h->stream, (int)B, (int)step0, (int)steps, h->sensor.streams.d, (unsigned long long)h->sensor.streams.seed, d);
     std::vector<real> tmp(n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), d, n * sizeof(real), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) { h->err = std::string("pg_sensor_draws: ") + hipGetErrorString(e); return PG_ERR_HIP; }
     for (size_t i = 0; i < n; i++) z[i] = (double)tmp[i];
     return PG_OK;
@@ -1629,7 +1609,7 @@ int pg_get_human_state(pg_handle* h, double* u) {
     return down(h, u, h->human.u, (size_t)h->B * 2);
 }
 // what mode 1 is handed as has_hji: a grid on a coupled handle (the safety rollout is coupled only; the node rollout passes its plant kernel the same word)
-static int human_has_hji(const pg_handle* h) { return (int)(h->has_hji && h->dc.formulation == PG_COUPLED); }
+static int human_has_hji(const pg_handle* h) { return (int)(h->hji.on && h->dc.formulation == PG_COUPLED); }
 int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, step0 >= 0 && steps >= 1 && dt > 0.0 && x7 && vg8 && u_out, "pg_human_response: step0 >= 0, steps >= 1, dt > 0, x7, vg8 and the output array required");
@@ -1649,41 +1629,18 @@ int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, con
     });
 }
 
-int pg_clear_hji_grid(pg_handle* h) {
-    if (!h) return PG_ERR_INVALID;
-    (void)hipStreamSynchronize(h->stream);
-    if (h->d_knots) (void)hipFree(h->d_knots);
-    if (h->d_hnodes) (void)hipFree(h->d_hnodes);
-    if (h->d_hcells) (void)hipFree(h->d_hcells);
-    h->d_knots = nullptr; h->d_hnodes = nullptr; h->d_hcells = nullptr; h->has_hji = false; h->dc.has_hji = 0;
-    return PG_OK;
+// ---- the handle's HJI table (pg_handle::hji, dc.has_hji): these two routines are the only code that writes it.  An install is "clear, then build": the old table is gone
+// before the new one is allocated (never two tables side by side: the cell records are 1.9 to 19 GB for the real grid), so AFTER A FAILED INSTALL the handle has no HJI
+// grid, no device memory of the call remains (the call's CallBufs held all of it), and pg_last_error says why ----
+static void hji_table_clear(pg_handle* h) {
+    (void)hipStreamSynchronize(h->stream);                      // (a launch still queued reads the old table)
+    h->mem.drop(h->hji.knots); h->mem.drop(h->hji.cells);
+    memset(&h->hji.hv, 0, sizeof(HjiView)); h->hji.on = false; h->dc.has_hji = 0;
 }
-
-static int hji_install_nodes(pg_handle* h, const HjiWalk& W);
-int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV) {
-    if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, dims && knots_concat && V && gradV, "pg_set_hji_grid: null argument");
-    REQUIRE(h, h->dc.formulation == PG_COUPLED, "the HJI safety row belongs to the coupled formulation only (coupled_lat_long.jl:341-346)");
-    HjiWalk W; { const int rc = hji_walk(h, "pg_set_hji_grid", dims, W); if (rc) return rc; }
-    const size_t n = W.n; const int nk = W.nk;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    pg_clear_hji_grid(h);
-    // interleave (V, gradV[7]) into 8-float node records: one 32 B aligned read per corner instead of a 4 B + a 28 B unaligned one
-    std::vector<float> rec(n * 8);
-    for (size_t i = 0; i < n; i++) { rec[8 * i] = V[i]; for (int k = 0; k < 7; k++) rec[8 * i + 1 + k] = gradV[7 * i + k]; }
-    HIPCHK(h, hipMalloc((void**)&h->d_hnodes, rec.size() * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&h->d_knots, (size_t)nk * sizeof(float)));
-    HIPCHK(h, hipMemcpy(h->d_hnodes, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_knots, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice));
-    return hji_install_nodes(h, W);
-}
-// the lookup table of the handle from the node records h->d_hnodes and the knots h->d_knots (both on the device, owned by the handle): what pg_set_hji_grid does after
-// its upload and pg_hji_solve after its last sweep
-static int hji_install_nodes(pg_handle* h, const HjiWalk& W) {
-    const int* dims = W.dims;
-    W.fill(h->hv);
-    h->hv.knots = h->d_knots; h->hv.nodes = h->d_hnodes;
-    // cell records (8 corners of dims 1..3 contiguous): built on the device from the compact node records, which are then released
+// The lookup table from the node records and the knots of walk W, both on the device and held by D.  The cell records (8 corners of dims 1..3 contiguous) are built in D
+// on a view of the call's; only after the kernel has run do knots and cells pass to the handle and the record is filled.  The node records stay in D and die with the call
+static int hji_table_build(pg_handle* h, const HjiWalk& W, CallBufs& D, float*& nodes, float*& knots) {
+    HjiView V; memset(&V, 0, sizeof(V)); W.fill(V); V.knots = knots; V.nodes = nodes;
     size_t free_b = 0, total_b = 0;
     HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
     // Device layout: 256 B cell records (cdims = 3: sixteen per lookup; 6 x the node table -- 1.9 GB for the 13 x 13 x 9^5 grid).  Since the lookup reads every record 256
@@ -1692,18 +1649,38 @@ static int hji_install_nodes(pg_handle* h, const HjiWalk& W) {
     int cd = h->hji_cell_dims; long ncell = 0;
     for (;; cd -= 2) {        // (a larger record asked for must fit a quarter of the free HBM)
         long cs = 1; ncell = 1;
-        for (int d = 0; d < 7; d++) { int ext = d < cd ? dims[d] - 1 : dims[d]; h->hv.cstride[d] = cs; cs *= ext; ncell *= ext; }
+        for (int d = 0; d < 7; d++) { int ext = d < cd ? W.dims[d] - 1 : W.dims[d]; V.cstride[d] = cs; cs *= ext; ncell *= ext; }
         if (cd == 3 || ((size_t)ncell << cd) * 32 <= free_b / 4) break;
     }
-    h->hv.cdims = cd;
-    HIPCHK(h, hipMalloc((void**)&h->d_hcells, ((size_t)ncell << cd) * 8 * sizeof(float)));
-    h->hv.cells = h->d_hcells;
-    hipLaunchKernelGGL(k_hji_build_cells, dim3((unsigned)((((size_t)ncell << cd) + 255) / 256)), dim3(256), 0, h->stream, h->hv, ncell, h->d_hcells);
+    float* cells = nullptr;
+    HIPCHK(h, D.alloc(cells, ((size_t)ncell << cd) * 8));
+    V.cdims = cd; V.cells = cells;
+    hipLaunchKernelGGL(k_hji_build_cells, dim3((unsigned)((((size_t)ncell << cd) + 255) / 256)), dim3(256), 0, h->stream, V, ncell, cells);
     LAUNCH_CHECK(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_hnodes); h->d_hnodes = nullptr; h->hv.nodes = nullptr;
-    h->has_hji = true; h->dc.has_hji = 1;
+    V.nodes = nullptr;
+    h->mem.adopt(h->hji.knots, D.give(knots)); h->mem.adopt(h->hji.cells, D.give(cells));
+    memcpy(&h->hji.hv, &V, sizeof(HjiView)); h->hji.on = true; h->dc.has_hji = 1;      // (a byte copy: the captured step compares the view with memcmp, padding included)
     return PG_OK;
+}
+
+int pg_clear_hji_grid(pg_handle* h) { if (!h) return PG_ERR_INVALID; hji_table_clear(h); return PG_OK; }
+int pg_set_hji_grid(pg_handle* h, const int32_t dims[7], const float* knots_concat, const float* V, const float* gradV) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, dims && knots_concat && V && gradV, "pg_set_hji_grid: null argument");
+    REQUIRE(h, h->dc.formulation == PG_COUPLED, "the HJI safety row belongs to the coupled formulation only (coupled_lat_long.jl:341-346)");
+    HjiWalk W; { const int rc = hji_walk(h, "pg_set_hji_grid", dims, W); if (rc) return rc; }
+    const size_t n = W.n; const int nk = W.nk;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hji_table_clear(h);
+    // interleave (V, gradV[7]) into 8-float node records: one 32 B aligned read per corner instead of a 4 B + a 28 B unaligned one
+    std::vector<float> rec(n * 8);
+    for (size_t i = 0; i < n; i++) { rec[8 * i] = V[i]; for (int k = 0; k < 7; k++) rec[8 * i + 1 + k] = gradV[7 * i + k]; }
+    CallBufs D; float *d_rec = nullptr, *d_kn = nullptr;
+    HIPCHK(h, D.alloc(d_rec, rec.size())); HIPCHK(h, D.alloc(d_kn, (size_t)nk));
+    HIPCHK(h, hipMemcpy(d_rec, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_kn, knots_concat, (size_t)nk * sizeof(float), hipMemcpyHostToDevice));
+    return hji_table_build(h, W, D, d_rec, d_kn);
 }
 
 // ---- pg_hji_solve: the reachable-tube sweeps (pg_hji_solve.hip).  The host owns the only loop over sweeps: eval -> alpha to the host -> dt -> update ----
@@ -1815,9 +1792,8 @@ int pg_hji_solve(pg_handle* h, const int32_t dims[7], const float* knots_concat,
     }
     if (stats) *stats = S;
     if (install) {
-        pg_clear_hji_grid(h);
-        h->d_hnodes = D.give(d_rec); h->d_knots = D.give(d_kn);
-        return hji_install_nodes(h, W);
+        hji_table_clear(h);
+        return hji_table_build(h, W, D, d_rec, d_kn);
     }
     return PG_OK;
 }
@@ -2035,9 +2011,9 @@ static int launch_nodes(pg_handle* h, bool with_time_grid) {
 }
 static int launch_hji_lookup(pg_handle* h, int B, const real* x7_dev, real* out8_dev) {
     dim3 grid((unsigned)(((size_t)B * 16 + 255) / 256));
-    if (h->hv.cdims == 7) hipLaunchKernelGGL(k_hji_lookup<7>, grid, dim3(256), 0, h->stream, h->hv, B, x7_dev, out8_dev);
-    else if (h->hv.cdims == 5) hipLaunchKernelGGL(k_hji_lookup<5>, grid, dim3(256), 0, h->stream, h->hv, B, x7_dev, out8_dev);
-    else hipLaunchKernelGGL(k_hji_lookup<3>, grid, dim3(256), 0, h->stream, h->hv, B, x7_dev, out8_dev);
+    if (h->hji.hv.cdims == 7) hipLaunchKernelGGL(k_hji_lookup<7>, grid, dim3(256), 0, h->stream, h->hji.hv, B, x7_dev, out8_dev);
+    else if (h->hji.hv.cdims == 5) hipLaunchKernelGGL(k_hji_lookup<5>, grid, dim3(256), 0, h->stream, h->hji.hv, B, x7_dev, out8_dev);
+    else hipLaunchKernelGGL(k_hji_lookup<3>, grid, dim3(256), 0, h->stream, h->hji.hv, B, x7_dev, out8_dev);
     LAUNCH_CHECK(h);
     return PG_OK;
 }
@@ -2045,7 +2021,7 @@ static int launch_hji_lookup(pg_handle* h, int B, const real* x7_dev, real* out8
 // (two halves: the rows themselves read the measured states only and may run before the nodes -- the pipelined launch needs (M, b) when it linearises interval 0 --,
 // the re-filed launch order needs the verdicts the nodes kernel filed)
 static int launch_hji_rows_compute(pg_handle* h) {
-    if (!h->has_hji) return PG_OK;
+    if (!h->hji.on) return PG_OK;
     const int B = h->B;
     hipLaunchKernelGGL(k_hji_relstate, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, h->d_state, h->d_other, h->d_x7);
     LAUNCH_CHECK(h);
@@ -2055,7 +2031,7 @@ static int launch_hji_rows_compute(pg_handle* h) {
     return PG_OK;
 }
 static int launch_hji_order(pg_handle* h) {
-    if (!h->has_hji) return PG_OK;
+    if (!h->hji.on) return PG_OK;
     const int B = h->B;
     if (h->dc.polish && h->order_B == B) {              // launch order again, now that the safety rows are known (k_order_hji)
         const OrderOut F = order_out(h, h->d_order);
@@ -2197,7 +2173,7 @@ static int launch_solve_coupled(pg_handle* h, hipStream_t st, const int* order, 
     SolveOut O = solve_out(h, order);
     if (h->u_direct) { O.u_out2 = h->u_direct; h->u_written = true; }      // (every k_solve instantiation below writes the caller's array itself)
     if (h->solve_ring) launch_k_solve<false, true, false>(h, st, n, O);
-    else if (h->split_solve && h->dc.polish && (h->dc.cold_guess > 0 || h->dc.warm_polish) && !h->has_hji && !h->sg.capturing) {
+    else if (h->split_solve && h->dc.polish && (h->dc.cold_guess > 0 || h->dc.warm_polish) && !h->hji.on && !h->sg.capturing) {
         // Two launches: the rounds-only instantiation (no scratch: the interior point's state and code are not in it) serves the instances an active-set attempt
         // verifies -- all of them on the tracking batches --; what it leaves (SolveOut::todo) goes through the full kernel in list mode, its blocks returning at once
         // when the list is empty.  Not with a safety row installed: there the instances whose row is violated NEED the interior point (9-17 % of config 3), and in one
@@ -2264,11 +2240,11 @@ static int update_and_solve(pg_handle* h, hipEvent_t after_update) {
 // cycles of one solve launch, out [B][6] = (stage assembly+step, sync, matrix pass, vector passes, forward passes, prologue); diagnostic build of the kernel, never timed
 int pg_debug_solve_cycles(pg_handle* h, unsigned long long* out) {
     int rc = check_ready(h); if (rc) return rc;
-    unsigned long long* d = nullptr;
-    HIPCHK(h, hipMalloc((void**)&d, ((size_t)h->B * 9 + 1024) * 8));
+    CallBufs D; unsigned long long* d = nullptr;
+    HIPCHK(h, D.alloc(d, (size_t)h->B * 9 + 1024));
     HIPCHK(h, hipMemset(d, 0, ((size_t)h->B * 9 + 1024) * 8));
     SolveOut O = solve_out(h, solve_order(h));            // (the launch order pg_solve would use: the timeline is the product's)
-    if (h->solve_lat) { if ((rc = launch_solve_lat(h, h->stream, d))) { (void)hipFree(d); return rc; } }
+    if (h->solve_lat) { if ((rc = launch_solve_lat(h, h->stream, d))) return rc; }
     else if (h->solve_ring) launch_k_solve<true, true, false>(h, h->stream, h->B, O, d);
     else if (h->debug_timeline) {      // the product's kernel (the rounds-only instantiation of the split launch): timeline only
         int* const cnt = solve_ctl(h, CTL_TIMELINE);
@@ -2279,7 +2255,6 @@ int pg_debug_solve_cycles(pg_handle* h, unsigned long long* out) {
     else launch_k_solve<true, false, false>(h, h->stream, h->B, O, d);
     LAUNCH_CHECK(h);
     HIPCHK(h, hipMemcpy(out, d, ((size_t)h->B * 9 + 1024) * 8, hipMemcpyDeviceToHost));      // out: [B][6] cycles + 1024-double trace of the "diag_instance" instance + [B][3] timeline (k_solve: entry, exit on the 100 MHz wall clock, HW_ID | XCC_ID << 32)
-    (void)hipFree(d);
     return PG_OK;
 }
 #endif
@@ -2306,7 +2281,7 @@ int pg_get_next_control(pg_handle* h, double* u_out) {
 static int launch_hji_policy(pg_handle* h, int use_policy) {
     const int B = h->B;
     if (h->dc.formulation != PG_COUPLED) { h->err = "the HJI policy belongs to the coupled controller (ros_integration.jl:56,114)"; return PG_ERR_STATE; }
-    if (!h->has_hji) {                      // no grid: V = +Inf everywhere, the MPC control always wins
+    if (!h->hji.on) {                      // no grid: V = +Inf everywhere, the MPC control always wins
         HIPCHK(h, hipMemcpyAsync(h->d_pol_u, h->d_u, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_pol_src, 0, (size_t)B * sizeof(int), h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_pol_u2, 0, (size_t)B * 2 * sizeof(real), h->stream));
@@ -2576,7 +2551,7 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
             SafetyIO io{lib ? (const real*)h->human.u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr), hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
                         hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
                         h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)h->has_hji, (int)h->sum_fresh, step,
+            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)h->hji.on, (int)h->sum_fresh, step,
                               h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
             h->sum_fresh = false;
         });
@@ -2614,28 +2589,30 @@ int pg_get_tracking_state(pg_handle* h, double* summary, int32_t* steps, int32_t
     return PG_OK;
 }
 // ---- node callback (from_autobox_callback, ros_integration.jl:48-151) --------------------------------------------
-// first call: the keep buffer at batch capacity (one carve-up of one allocation), the node words, the applied command (zeroed: heartbeat and counts start at 0)
+// first call: the keep buffer at batch capacity (one carve-up of one allocation), the node words, the applied command (zeroed: heartbeat and counts start at 0).
+// A call that failed here is not a first call that happened: the next one takes up whichever of the three buffers is missing and fills again
 static int node_prepare(pg_handle* h) {
     const size_t cap = (size_t)h->cfg.batch_capacity; const int N = h->dc.N, NN = h->dc.NN;
     const int naux_cap = h->dc.formulation == PG_DECOUPLED ? 64 * LAT_AUX : 0;
     KeepView& K = h->kv;
-    if (!h->d_keep) {
+    if (!h->d_applied) {                                      // (the last of the three)
         const size_t dbl = cap * (size_t)(NN + N + NN), rl = cap * (size_t)(NN * 8 + N * 3 + N * 16 + 3 + 1 + naux_cap), it = cap * 5, u16 = cap * (size_t)N;
         const size_t bytes = dbl * sizeof(double) + rl * sizeof(real) + it * sizeof(int) + u16 * sizeof(uint16_t);
-        HIPCHK(h, hipMalloc((void**)&h->d_keep, bytes));
+        int rc;
+        if ((rc = ensure(h, h->d_keep, bytes))) return rc;
         char* p = h->d_keep;
         auto take = [&](auto*& dst, size_t n) { dst = (std::remove_reference_t<decltype(dst)>)p; p += n * sizeof(*dst); };
         take(K.k_ts, cap * NN); take(K.k_dt, cap * N); take(K.k_prev_ts, cap * NN);
         take(K.k_solx, cap * NN * 8); take(K.k_sigma, cap * N * 3); take(K.k_lam, cap * N * 16); take(K.k_u, cap * 3); take(K.k_mu, cap); take(K.k_aux, cap * naux_cap);
         take(K.k_solved, cap); take(K.k_wfail, cap); take(K.k_status, cap); take(K.k_iters, cap); take(K.k_polish, cap); take(K.k_active, cap * N);
-        HIPCHK(h, hipMalloc((void**)&h->d_node, (cap * 6 + NODE_COLD_WORDS) * sizeof(int)));
+        if ((rc = ensure(h, h->d_node, cap * 6 + NODE_COLD_WORDS))) return rc;
         HIPCHK(h, hipMemset(h->d_node, 0, (cap * 6 + NODE_COLD_WORDS) * sizeof(int)));
-        HIPCHK(h, hipMalloc((void**)&h->d_applied, cap * 3 * sizeof(real)));
+        if ((rc = ensure(h, h->d_applied, cap * 3))) return rc;
         HIPCHK(h, hipMemset(h->d_applied, 0, cap * 3 * sizeof(real)));
     }
     if (h->tend_dirty) {
-        if (h->d_tend) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_tend); h->d_tend = nullptr; }
-        HIPCHK(h, hipMalloc((void**)&h->d_tend, h->traj_ends.size() * sizeof(double)));
+        if (h->d_tend) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->mem.drop(h->d_tend); }
+        { const int rc = ensure(h, h->d_tend, h->traj_ends.size()); if (rc) return rc; }
         HIPCHK(h, hipMemcpy(h->d_tend, h->traj_ends.data(), h->traj_ends.size() * sizeof(double), hipMemcpyHostToDevice));
         h->tend_dirty = false;
     }
@@ -2667,7 +2644,7 @@ int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_fl
     NodeIO io = node_io(h);
     io.cmd_out = (real*)cmd_out_dev; io.se_out = (real*)se_out_dev; io.event = event_dev;
     const int B = h->B;
-    hipLaunchKernelGGL(k_node_finish<false>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, 0.0, (int)(use_hji_policy != 0), 0, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+    hipLaunchKernelGGL(k_node_finish<false>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, 0.0, (int)(use_hji_policy != 0), 0, (int)(h->hji.on && h->dc.formulation == PG_COUPLED),
                        (int)h->node_fresh, 0, 0, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, 0, h->kv, io);
     LAUNCH_CHECK(h);
     node_done(h);
@@ -2695,7 +2672,7 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
             io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
             io.event_h = hist_at(event_hist_dev, k, B, 1);
             io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)(h->has_hji && h->dc.formulation == PG_COUPLED),
+            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)(h->hji.on && h->dc.formulation == PG_COUPLED),
                               (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
                               h->sim_idx, h->kv, io);
             h->sum_fresh = false;
@@ -2756,8 +2733,8 @@ static int step_by_graph(pg_handle* h, int32_t B, const double* state, const dou
     if (!h->graph_mode || G.disabled || B != h->cfg.batch_capacity || B > 256 || h->B != B || h->warm_B < B || h->fuse != 0 || !h->d_traj || h->node_recheck) return PG_OK;
     if (index_covers(h, (size_t)h->dc.n_traj, h->traj_idx) || index_covers(h, (size_t)h->dc.n_cp, h->cp.idx)) return PG_OK;      // (h->B == B; the ordinary path reports it)
     if (hipSetDevice(h->cfg.device) != hipSuccess) return PG_OK;
-    const bool same = G.x && G.B == B && G.user == h->stream && G.fuse == h->fuse && G.pipeline == h->pipeline && G.has_hji == (int)h->has_hji && G.traj_L == h->traj_L &&
-                      memcmp(&G.dc, &h->dc, sizeof(DevCfg)) == 0 && memcmp(&G.hv, &h->hv, sizeof(HjiView)) == 0;
+    const bool same = G.x && G.B == B && G.user == h->stream && G.fuse == h->fuse && G.pipeline == h->pipeline && G.has_hji == (int)h->hji.on && G.traj_L == h->traj_L &&
+                      memcmp(&G.dc, &h->dc, sizeof(DevCfg)) == 0 && memcmp(&G.hv, &h->hji.hv, sizeof(HjiView)) == 0;
     hipStream_t run = h->stream ? h->stream : G.own;
     if (!same) {
         if (G.x) { (void)hipGraphExecDestroy(G.x); G.x = nullptr; }
@@ -2784,8 +2761,8 @@ static int step_by_graph(pg_handle* h, int32_t B, const double* state, const dou
             G.disabled = true; (void)hipGetLastError();
             return PG_OK;
         }
-        memcpy(&G.dc, &h->dc, sizeof(DevCfg)); memcpy(&G.hv, &h->hv, sizeof(HjiView)); G.B = B;      // (byte copies: the signature is compared with memcmp, padding included)
-         G.user = user; G.fuse = h->fuse; G.pipeline = h->pipeline; G.has_hji = (int)h->has_hji; G.traj_L = h->traj_L;
+        memcpy(&G.dc, &h->dc, sizeof(DevCfg)); memcpy(&G.hv, &h->hji.hv, sizeof(HjiView)); G.B = B;      // (byte copies: the signature is compared with memcmp, padding included)
+         G.user = user; G.fuse = h->fuse; G.pipeline = h->pipeline; G.has_hji = (int)h->hji.on; G.traj_L = h->traj_L;
     } else if (hipStreamSynchronize(h->stream) != hipSuccess) return PG_OK;
     stage_block(h, B, state, control, t0, other, toff);
     HIPCHK(h, hipGraphLaunch(G.x, run));
@@ -2916,9 +2893,9 @@ int pg_get_hji_constraint(pg_handle* h, double* M, double* b, double* V) {
     int rc = check_ready(h); if (rc) return rc;
     const size_t B = h->B;
     std::vector<double> mb(B * 4);
-    if (h->has_hji && (rc = down(h, mb.data(), h->d_Mb, mb.size()))) return rc;
+    if (h->hji.on && (rc = down(h, mb.data(), h->d_Mb, mb.size()))) return rc;
     for (size_t i = 0; i < B; i++) {
-        if (!h->has_hji) { mb[4 * i] = 0; mb[4 * i + 1] = 0; mb[4 * i + 2] = 1; mb[4 * i + 3] = INFINITY; }
+        if (!h->hji.on) { mb[4 * i] = 0; mb[4 * i + 1] = 0; mb[4 * i + 2] = 1; mb[4 * i + 3] = INFINITY; }
         if (M) { M[2 * i] = mb[4 * i]; M[2 * i + 1] = mb[4 * i + 1]; }
         if (b) b[i] = mb[4 * i + 2];
         if (V) V[i] = mb[4 * i + 3];
@@ -2928,76 +2905,64 @@ int pg_get_hji_constraint(pg_handle* h, double* M, double* b, double* V) {
 
 int pg_hji_lookup_dev(pg_handle* h, int32_t B, const void* x7_dev, void* V_dev, void* gradV_dev) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, h->has_hji, "no HJI grid installed");
+    REQUIRE(h, h->hji.on, "no HJI grid installed");
     REQUIRE(h, B >= 1 && x7_dev, "pg_hji_lookup_dev: bad arguments");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    real* out8 = nullptr; const size_t R = sizeof(real);
-    HIPCHK(h, hipMalloc((void**)&out8, (size_t)B * 8 * R));
-    int rc = launch_hji_lookup(h, B, (const real*)x7_dev, out8);
-    if (!rc) {
-        if (V_dev) HIPCHK(h, hipMemcpy2DAsync(V_dev, R, out8, 8 * R, R, B, hipMemcpyDeviceToDevice, h->stream));
-        if (gradV_dev) HIPCHK(h, hipMemcpy2DAsync(gradV_dev, 7 * R, out8 + 1, 8 * R, 7 * R, B, hipMemcpyDeviceToDevice, h->stream));
-    }
+    CallBufs D; real* out8 = nullptr; const size_t R = sizeof(real);
+    HIPCHK(h, D.alloc(out8, (size_t)B * 8));
+    const int rc = launch_hji_lookup(h, B, (const real*)x7_dev, out8); if (rc) return rc;
+    if (V_dev) HIPCHK(h, hipMemcpy2DAsync(V_dev, R, out8, 8 * R, R, B, hipMemcpyDeviceToDevice, h->stream));
+    if (gradV_dev) HIPCHK(h, hipMemcpy2DAsync(gradV_dev, 7 * R, out8 + 1, 8 * R, 7 * R, B, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(out8);
-    return rc;
+    return PG_OK;
 }
 int pg_hji_lookup8_dev(pg_handle* h, int32_t B, const void* x7_dev, void* out8_dev) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, h->has_hji, "no HJI grid installed");
+    REQUIRE(h, h->hji.on, "no HJI grid installed");
     REQUIRE(h, B >= 1 && x7_dev && out8_dev, "pg_hji_lookup8_dev: bad arguments");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return launch_hji_lookup(h, B, (const real*)x7_dev, (real*)out8_dev);
 }
 int pg_hji_grid_dims(pg_handle* h, int32_t dims[7]) {
     if (!h || !dims) return PG_ERR_INVALID;
-    REQUIRE(h, h->has_hji, "no HJI grid installed");
-    for (int d = 0; d < 7; d++) dims[d] = h->hv.dims[d];
+    REQUIRE(h, h->hji.on, "no HJI grid installed");
+    for (int d = 0; d < 7; d++) dims[d] = h->hji.hv.dims[d];
     return PG_OK;
 }
 int pg_hji_slice(pg_handle* h, int32_t B, const double* q7, double* V_out, double* rgb_out, double* cross_x, double* cross_y) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, h->has_hji, "no HJI grid installed");
+    REQUIRE(h, h->hji.on, "no HJI grid installed");
     REQUIRE(h, B >= 1 && q7 && V_out, "pg_hji_slice: need B >= 1, the relative states and V_out");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int n1 = h->hv.dims[0], n2 = h->hv.dims[1]; const size_t npt = (size_t)B * n1 * n2;
-    real *dq = nullptr, *dx = nullptr, *dv = nullptr, *dV = nullptr, *drgb = nullptr, *dcx = nullptr, *dcy = nullptr;
-    int rc = PG_OK;
-    auto cleanup = [&]() { for (void* p : {(void*)dq, (void*)dx, (void*)dv, (void*)dV, (void*)drgb, (void*)dcx, (void*)dcy}) if (p) (void)hipFree(p); };
-#define SL_ALLOC(ptr, count) do { if (hipMalloc((void**)&(ptr), (size_t)(count) * sizeof(real)) != hipSuccess) { h->err = "pg_hji_slice: hipMalloc failed"; cleanup(); return PG_ERR_HIP; } } while (0)
-    SL_ALLOC(dq, (size_t)B * 7); SL_ALLOC(dx, npt * 7); SL_ALLOC(dv, npt * 8); SL_ALLOC(dV, npt);
-    if (rgb_out) SL_ALLOC(drgb, npt * 3);
-    if (cross_x) SL_ALLOC(dcx, (size_t)B * (n1 - 1) * n2);
-    if (cross_y) SL_ALLOC(dcy, (size_t)B * n1 * (n2 - 1));
-#undef SL_ALLOC
-    if ((rc = up(h, dq, q7, (size_t)B * 7))) { cleanup(); return rc; }
+    const int n1 = h->hji.hv.dims[0], n2 = h->hji.hv.dims[1]; const size_t npt = (size_t)B * n1 * n2;
+    CallBufs D; real *dq = nullptr, *dx = nullptr, *dv = nullptr, *dV = nullptr, *drgb = nullptr, *dcx = nullptr, *dcy = nullptr; int rc = PG_OK;
+    HIPCHK(h, D.alloc(dq, (size_t)B * 7)); HIPCHK(h, D.alloc(dx, npt * 7)); HIPCHK(h, D.alloc(dv, npt * 8)); HIPCHK(h, D.alloc(dV, npt));
+    if (rgb_out) HIPCHK(h, D.alloc(drgb, npt * 3));
+    if (cross_x) HIPCHK(h, D.alloc(dcx, (size_t)B * (n1 - 1) * n2));
+    if (cross_y) HIPCHK(h, D.alloc(dcy, (size_t)B * n1 * (n2 - 1)));
+    if ((rc = up(h, dq, q7, (size_t)B * 7))) return rc;
     const dim3 grid((unsigned)((npt + 255) / 256));
-    hipLaunchKernelGGL(k_hji_slice_queries, grid, dim3(256), 0, h->stream, h->hv, B, dq, dx);
-    if ((rc = launch_hji_lookup(h, (int)npt, dx, dv))) { cleanup(); return rc; }
-    hipLaunchKernelGGL(k_hji_slice_post, grid, dim3(256), 0, h->stream, h->hv, B, dv, dV, drgb, dcx, dcy);
-    if (hipGetLastError() != hipSuccess) { h->err = "pg_hji_slice: kernel launch failed"; cleanup(); return PG_ERR_HIP; }
+    hipLaunchKernelGGL(k_hji_slice_queries, grid, dim3(256), 0, h->stream, h->hji.hv, B, dq, dx);
+    if ((rc = launch_hji_lookup(h, (int)npt, dx, dv))) return rc;
+    hipLaunchKernelGGL(k_hji_slice_post, grid, dim3(256), 0, h->stream, h->hji.hv, B, dv, dV, drgb, dcx, dcy);
+    if (hipGetLastError() != hipSuccess) { h->err = "pg_hji_slice: kernel launch failed"; return PG_ERR_HIP; }
     if ((rc = down(h, V_out, dV, npt)) || (rc = down(h, rgb_out, drgb, npt * 3)) || (rc = down(h, cross_x, dcx, (size_t)B * (n1 - 1) * n2)) ||
-        (rc = down(h, cross_y, dcy, (size_t)B * n1 * (n2 - 1)))) { cleanup(); return rc; }
-    cleanup();
+        (rc = down(h, cross_y, dcy, (size_t)B * n1 * (n2 - 1)))) return rc;
     return PG_OK;
 }
 int pg_hji_lookup(pg_handle* h, int32_t B, const double* x7, double* V, double* gradV) {
     if (!h) return PG_ERR_INVALID;
-    REQUIRE(h, h->has_hji, "no HJI grid installed");
+    REQUIRE(h, h->hji.on, "no HJI grid installed");
     REQUIRE(h, B >= 1 && x7, "pg_hji_lookup: bad arguments");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    real *dx = nullptr, *dout = nullptr;
-    HIPCHK(h, hipMalloc((void**)&dx, (size_t)B * 7 * sizeof(real)));
-    HIPCHK(h, hipMalloc((void**)&dout, (size_t)B * 8 * sizeof(real)));
-    int rc = up(h, dx, x7, (size_t)B * 7);
-    if (!rc) rc = launch_hji_lookup(h, B, dx, dout);
+    CallBufs D; real *dx = nullptr, *dout = nullptr;
+    HIPCHK(h, D.alloc(dx, (size_t)B * 7));
+    HIPCHK(h, D.alloc(dout, (size_t)B * 8));
     std::vector<double> out((size_t)B * 8);
-    if (!rc) rc = down(h, out.data(), dout, out.size());
-    if (!rc) {
-        for (int i = 0; i < B; i++) { if (V) V[i] = out[8 * (size_t)i]; if (gradV) for (int k = 0; k < 7; k++) gradV[7 * (size_t)i + k] = out[8 * (size_t)i + 1 + k]; }
-    }
-    (void)hipFree(dx); (void)hipFree(dout);
-    return rc;
+    int rc;
+    if ((rc = up(h, dx, x7, (size_t)B * 7)) || (rc = launch_hji_lookup(h, B, dx, dout)) || (rc = down(h, out.data(), dout, out.size()))) return rc;
+    for (int i = 0; i < B; i++) { if (V) V[i] = out[8 * (size_t)i]; if (gradV) for (int k = 0; k < 7; k++) gradV[7 * (size_t)i + k] = out[8 * (size_t)i + 1 + k]; }
+    return PG_OK;
 }
 
 }  // extern "C"

@@ -264,3 +264,12 @@ def test_tools_option_names_exist_in_the_header():
     listed = set(re.findall(r'"([a-z0-9_]+)"', header))
     missing = sorted(n for n in set(mod._MAP.values()) | {"lateral_solver"} if n not in listed)
     assert not missing, missing
+
+
+def test_device_memory_is_allocated_and_freed_in_one_place():
+    """pg_api.hip allocates and frees device memory through the two owners of pg_own.hpp only: hipMalloc and hipFree each occur once (inside pg_dev_alloc / pg_dev_free,
+    comments and strings included), and no exit of pg_create frees by hand."""
+    src = open(os.path.join(ROOT, "pigeon.jl_amd", "csrc", "pg_api.hip")).read()
+    assert src.count("hipFree(") == 1
+    assert src.count("hipMalloc(") == 1
+    assert "free_all(h); delete h" not in src

@@ -4,6 +4,8 @@ Also covers the un-staged nodes kernel (a tube longer than the LDS staging limit
 import numpy as np
 import pytest
 
+import hji_live_cases as lc
+import hji_solve_cases as solve_cases
 import path_make_cases as cases
 from conftest import make_oracle
 from path_libs import handle, install_equals_set_trajectories, step_bits
@@ -103,6 +105,45 @@ def test_the_ways_a_library_arrives_replace_each_other(pkg, skidpad):
     m.set_trajectory(skidpad)
     assert step_bits(m, pkg) == first
     m.close()
+
+
+@pytest.mark.parametrize("cell_dims", [3, 7])
+def test_the_ways_an_hji_grid_arrives_replace_each_other(pkg, skidpad, cell_dims):
+    """One coupled handle, its HJI table in turn: pg_set_hji_grid (the live grid), pg_hji_solve with install (the smallest grid of the solve tests), pg_clear_hji_grid,
+    pg_set_hji_grid again.  After each the handle answers, bit for bit, as a fresh handle that received only that grid: the lookup at lookup_queries of the grid's knots,
+    and the safety row after one cold step.  After the clear the lookup refuses and the row is the one of a handle that never had a grid."""
+    live = lc.live_grid()
+    knots_a, l0 = solve_cases.grid("A", False)
+    solve = dict(install=True, fixed_dt=solve_cases.FIXED_DT, max_sweeps=solve_cases.SWEEPS)
+    state, control, t0, toff, other = (a[:8] for a in lc.constraint_inputs(pkg, skidpad))
+
+    def answers(m, knots):
+        m.reset()
+        m.step_(state, control, t0, other_car_state=other, time_offset=toff)
+        out = b"".join(a.tobytes() for a in m.hji_constraint())
+        if knots is None:
+            with pytest.raises(pkg.PigeonError, match="no HJI grid installed"):
+                m.hji_lookup(lc.lookup_queries(live[0])[0])
+            return out
+        V, g = m.hji_lookup(lc.lookup_queries(knots)[0])
+        assert np.isfinite(V).sum() >= 50
+        return out + V.tobytes() + g.tobytes()
+
+    installs = [(live[0], lambda m: m.set_hji_cache(*live)), (knots_a, lambda m: m.solve_hji_cache(knots_a, l0, 1e9, **solve)), (None, lambda m: m.clear_hji_cache()),
+                (live[0], lambda m: m.set_hji_cache(*live))]
+    one = pkg.BatchedTrajectoryTrackingMPC(skidpad, 8, hji_eps=10.0, options={"hji_cell_dims": cell_dims})
+    got, want = [], []
+    for knots, install in installs:
+        install(one)
+        got.append(answers(one, knots))
+        fresh = pkg.BatchedTrajectoryTrackingMPC(skidpad, 8, hji_eps=10.0, options={"hji_cell_dims": cell_dims})
+        if knots is not None:
+            install(fresh)
+        want.append(answers(fresh, knots))
+        fresh.close()
+    one.close()
+    assert got == want, [a == b for a, b in zip(got, want)]
+    assert got[0] == got[3] and len({got[0], got[1], got[2]}) == 3          # (the three tables answer differently: none of the comparisons is of a handle with itself)
 
 
 def test_long_tube_unstaged_nodes_kernel(pkg, oracle_mod, library):
