@@ -339,6 +339,61 @@ pg_waypoint pg_default_waypoint(void);
 int pg_fit_paths(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints, int32_t Lmax,
                  int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_fit_stats* stats);
 
+/* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
+ * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car
+ * (src/ros_integration.jl:48-99), so the feature is build-defined (tests/start_make_numpy.py is its numpy twin).  After pg_make_paths / pg_fit_paths / pg_plan_speeds
+ * with install != 0 the host holds no tube to interpolate; this call needs none.  "Starts" joins the sweep axes sensors x plants x tunings x tracks: a library of
+ * start sets, a per-instance set index, a seed and 64-bit stream ids; every draw is a pure function of (seed, stream id, channel), never of the batch.
+ *   Draws     26 uniform ranges (lo, hi) in the order of the structure = 13 channels c: s, e, dpsi, v, uy, dr, delta, fx, dt0, other_dx, other_dy, other_dpsi, other_v.
+ *             Channel c takes word c % 4 of Philox4x32-10 block 4 + c / 4: key (seed_lo, seed_hi), counter (0, 4 + c / 4, stream_lo, stream_hi) -- blocks 0-3 belong to
+ *             the sensor, the disturbance and the human.  u = (x + 0.5) 2^-32 in double; value = lo + (u (hi - lo)), so lo == hi gives lo exactly.
+ *   s         s_first + value (s_mode 0) or s_first + (value (s_last - s_first)) (s_mode 1), clamped to [s_first, s_last] of the instance's own tube (trajectory
+ *             index[b] of the installed library).  No wrap on a closed path.
+ *   Lookup    the controller's own, in DOUBLE in both libraries on the channels as the library holds them (the fp32 library: every channel rounded to float):
+ *             i from the count of knots < s, A = (V_i+1 - V_i) / (t_i+1 - t_i), ds = s - s_i, dt = ds / V_i where |A| < 1e-3, else (sqrt((2 A ds) + (V_i V_i)) - V_i) / A;
+ *             V = V_i + (A dt), t(s) = t_i + dt (src/trajectories.jl:55-68 as written: in double the cancellation of the root costs at most 2^-52 V_i / |A| s, and this
+ *             form equals the numpy statement of the reference bit for bit; the controller's own traj[s] rationalises the root, one rounding apart);  j from the count of
+ *             knots <= s, w = (s - s_j) / (s_j+1 - s_j), c = c_j + (w (c_j+1 - c_j)) for psi, kappa, E, N, edge_L, edge_R (:32-35).  Every operation rounded once.
+ *   Place     e = value (e_mode 0) or (0.5 (edge_L + edge_R)) + (value (0.5 (edge_L - edge_R))) (e_mode 1).  psi is measured from North, the left normal is
+ *             (-cos psi, -sin psi):  E = E_p - (e cos psi_p), N = N_p - (e sin psi_p), psi = psi_p + dpsi.
+ *   Body      steady 0: Ux = v V, Uy = 0, r = kappa Ux, delta = Fx = 0.  steady 1: steady_state_estimates(pg_config.vehicle, v V, A, kappa) with the reference's defaults
+ *             (src/vehicle_dynamics.jl:319: 4 iterations, r = (v V) kappa, the other estimates 0), in the library's element type -- the function that seeds the cold nodes;
+ *             Ux, Uy, r, delta and Fx = Fxf + Fxr are taken from it.  Then Uy += uy, r += dr, delta += delta, Fx += fx, and (Fxf, Fxr) = longitudinal_tire_forces(Fx)
+ *             (:279-283).  No control limits are applied.
+ *   Other     other_mode 1: in the frame of the MADE ego heading, forward (-sin psi, cos psi), left (-cos psi, -sin psi): E_o = (E + (dx (-sin psi))) + (dy (-cos psi)),
+ *             N_o = (N + (dx cos psi)) + (dy (-sin psi)), psi_o = psi + dpsi_o, V_o = value.  other_mode 0: zeros.
+ *   Store     state, control and other car rounded ONCE to the library's element type; t0 = t(s) + dt0, time_offset (0, or NaN with time_mode 1) and placed in double.  The
+ *             host outputs are the stored values widened to double.
+ * Everything but sincos (and, with steady 1, steady_state) reproduces the twin bit for bit. */
+typedef struct pg_start_set {
+    double s_lo, s_hi;           /* arclength: metres from the tube's first knot (s_mode 0) or fraction of its length (s_mode 1) */
+    double e_lo, e_hi;           /* lateral offset, left positive: metres (e_mode 0) or fraction of the local tube (e_mode 1: e = mid + f half, mid/half from edge_L, edge_R at s) */
+    double dpsi_lo, dpsi_hi;     /* heading minus path heading */
+    double v_lo, v_hi;           /* factor on the tube's V(s); > 0 */
+    double uy_lo, uy_hi, dr_lo, dr_hi;           /* added to Uy and r */
+    double delta_lo, delta_hi, fx_lo, fx_hi;     /* added to delta and total Fx */
+    double dt0_lo, dt0_hi;       /* t0 = t(s) + this */
+    double other_dx_lo, other_dx_hi, other_dy_lo, other_dy_hi, other_dpsi_lo, other_dpsi_hi, other_v_lo, other_v_hi;  /* ego frame: forward, left */
+    int32_t s_mode, e_mode;
+    int32_t steady;              /* 0: Ux = v V(s), Uy = 0, r = kappa Ux, delta = Fx = 0;  1: steady_state_estimates(vehicle, v V(s), A(s), kappa(s)) */
+    int32_t time_mode;           /* 0: time_offset = 0 (trajectory mode); 1: NaN (path mode) */
+    int32_t other_mode;          /* 0: other car zeros; 1: placed relative to the ego from the other_* ranges */
+    int32_t reserved[3];         /* must be 0 */
+} pg_start_set;                  /* 240 bytes */
+/* every range [0,0] except v = [1,1]; every mode 0: "on the profile, at the first knot" */
+pg_start_set pg_default_start_set(void);
+/* sets [n_sets]; set_index [B] (NULL: set 0 for every instance); stream [B] (NULL: stream[b] = b).  state_out [B][6], control_out [B][3], t0_out [B], other_out [B][4],
+ * time_offset_out [B], placed_out [B][4] = (s, e, dpsi, V(s) of the tube); each may be NULL.
+ * install != 0: the handle is exactly as after pg_set_inputs(h, B, state_out, control_out, t0_out, other_out, time_offset_out) -- the same buffers, the restarted rollout
+ * clock, the restart of every library state --, with no host round trip.  install == 0 leaves the handle's inputs untouched.  Synchronous.  A handle that never calls this
+ * launches what it launched before.
+ * PG_ERR_INVALID, everything validated before the first allocation (the handle's inputs and clock are left untouched): a null sets; n_sets < 1 (the set libraries have no
+ * upper bound, nor has this); B outside [1, batch_capacity]; an index outside [0, n_sets); a non-finite range field; lo > hi; v_lo <= 0; a mode outside {0, 1};
+ * reserved != 0.  pg_set_inputs accepts an other car and time_offset = 0 under both formulations, so neither other_mode nor time_mode is refused under the decoupled one.
+ * PG_ERR_STATE: no trajectory library installed; a library of several tubes without a trajectory index that covers B (an instance reads its own tube through it). */
+int pg_make_starts(pg_handle* h, int32_t B, int32_t n_sets, const pg_start_set* sets, const int32_t* set_index, uint64_t seed, const uint64_t* stream, int32_t install,
+                   double* state_out, double* control_out, double* t0_out, double* other_out, double* time_offset_out, double* placed_out);
+
 /* control_params of one controller per instance (src/coupled_lat_long.jl:42-60, src/decoupled_lat_long.jl:32-50): a library of control-parameter sets and a per-instance
  * selection, the counterpart of pg_set_trajectories / pg_set_trajectory_index for the controller's tuning -- a tuning sweep or robustness study (the same starts and paths
  * under many weightings, speed bounds and steering-rate limits) runs as ONE batch.  With no library the handle behaves as pg_config.control says.  A library of ONE set

@@ -634,6 +634,43 @@ end
 "{ 0, 0, 4, -4 } as the library states them (pg_default_waypoint)"
 default_waypoint(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_waypoint), PgWaypoint, ())
 
+# Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
+struct PgStartSet
+    s_lo::Float64; s_hi::Float64
+    e_lo::Float64; e_hi::Float64
+    dpsi_lo::Float64; dpsi_hi::Float64
+    v_lo::Float64; v_hi::Float64
+    uy_lo::Float64; uy_hi::Float64
+    dr_lo::Float64; dr_hi::Float64
+    delta_lo::Float64; delta_hi::Float64
+    fx_lo::Float64; fx_hi::Float64
+    dt0_lo::Float64; dt0_hi::Float64
+    other_dx_lo::Float64; other_dx_hi::Float64
+    other_dy_lo::Float64; other_dy_hi::Float64
+    other_dpsi_lo::Float64; other_dpsi_hi::Float64
+    other_v_lo::Float64; other_v_hi::Float64
+    s_mode::Int32
+    e_mode::Int32
+    steady::Int32
+    time_mode::Int32
+    other_mode::Int32
+    reserved::NTuple{3,Int32}
+end
+"every range [0, 0] except v = [1, 1], every mode 0, as the library states them (pg_default_start_set)"
+default_start_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_start_set), PgStartSet, ())
+"sets, the set of every instance (0-based, as in C; nothing: set 0), a seed and the stream id of every instance (nothing: its position) -> (state [6, B], control [3, B], t0 [B], other [4, B], time_offset [B], placed [4, B] = s, e, dpsi, V(s)); install = true leaves the handle as pg_set_inputs with these arrays would"
+function make_starts!(mpc::BatchedTrajectoryTrackingMPC, B::Integer, sets::Vector{PgStartSet}; index::Union{Nothing,Vector{Int32}}=nothing, seed::Integer=0,
+                      streams::Union{Nothing,Vector{UInt64}}=nothing, install::Bool=true)
+    (sizeof(PgStartSet), fieldoffset(PgStartSet, 27)) == (240, 208) || error("PigeonMI355X.jl: PgStartSet differs from pg_start_set of include/pigeon_mpc.h")
+    (index === nothing || length(index) == B) && (streams === nothing || length(streams) == B) || error("make_starts!: index and streams have B entries")
+    state = zeros(Float64, 6, B); control = zeros(Float64, 3, B); t0 = zeros(Float64, B); other = zeros(Float64, 4, B); toff = zeros(Float64, B); placed = zeros(Float64, 4, B)
+    check(mpc, ccall(sym(mpc, :pg_make_starts), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{PgStartSet}, Ptr{Int32}, UInt64, Ptr{UInt64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     mpc.handle, Int32(B), Int32(length(sets)), sets, index === nothing ? Ptr{Int32}(C_NULL) : index, UInt64(seed), streams === nothing ? Ptr{UInt64}(C_NULL) : streams,
+                     Int32(install), state, control, t0, other, toff, placed), "pg_make_starts")
+    state, control, t0, other, toff, placed
+end
+
 "mpc.solved = false (src/ros_integration.jl:34,41,147)"
 reset!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_reset), Cint, (Ptr{Cvoid}, Ptr{UInt8}), mpc.handle, C_NULL), "pg_reset")
 

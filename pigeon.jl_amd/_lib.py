@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_start_set", "pg_make_starts",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -233,6 +233,22 @@ PATH_FIT_PROTOTYPES = {
 }
 
 
+START_RANGES = ["s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v"]      # the 13 channels of the draws, in their order
+START_MODES = ["s_mode", "e_mode", "steady", "time_mode", "other_mode"]
+
+
+class pg_start_set(C.Structure):
+    """include/pigeon_mpc.h pg_start_set: 13 uniform ranges (lo, hi) -- arclength, lateral offset, heading offset, factor on V(s), offsets on Uy, r, delta, Fx and t0, the
+    other car in the ego frame -- and the modes (s as a fraction, e as a fraction of the tube, steady-state body state, path mode, other car on), three reserved zeros."""
+    _fields_ = [(f"{n}_{end}", C.c_double) for n in START_RANGES for end in ("lo", "hi")] + [(n, C.c_int32) for n in START_MODES] + [("reserved", C.c_int32 * 3)]
+
+
+# start maker (include/pigeon_mpc.h: pg_make_starts)
+START_MAKE_PROTOTYPES = {
+    "pg_make_starts": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(pg_start_set), C.POINTER(C.c_int32), C.c_uint64, C.POINTER(C.c_uint64), C.c_int32] + [C.POINTER(C.c_double)] * 6,
+}
+
+
 def load_library(precision="f64"):
     """Loads the HIP library of the requested arithmetic type.  PyTorch-ROCm is imported first so that both share ONE HIP runtime in this process."""
     assert precision in ("f64", "f32", "f64-diag")
@@ -254,7 +270,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, START_MAKE_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -266,6 +282,8 @@ def load_library(precision="f64"):
     lib.pg_default_path_segment.restype = pg_path_segment
     lib.pg_default_waypoint.argtypes = []
     lib.pg_default_waypoint.restype = pg_waypoint
+    lib.pg_default_start_set.argtypes = []
+    lib.pg_default_start_set.restype = pg_start_set
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)
     check_layout(lib)
     _libs[precision] = lib

@@ -1857,6 +1857,62 @@ int pg_set_inputs_dev(pg_handle* h, int32_t B, const void* state, const void* co
     return set_inputs(h, B, state, control, t0, other, toff, false);
 }
 
+// ---- pg_make_starts: the inputs of a batch placed on the installed trajectory library under a library of start sets (pg_start_make.hip).  One launch, one lane per
+// instance; the install is pg_set_inputs_dev from the call's own buffers ----
+static_assert(sizeof(pg_start_set) == 240 && offsetof(pg_start_set, s_mode) == 208, "the size include/pigeon_mpc.h states; the 26 range fields lead the structure");
+pg_start_set pg_default_start_set(void) {
+    pg_start_set s; memset(&s, 0, sizeof(s)); s.v_lo = 1.0; s.v_hi = 1.0;
+    return s;
+}
+static const char* start_set_problem(const pg_start_set& s) {
+    const double* r = &s.s_lo;
+    for (int c = 0; c < ST_CHANNELS; c++) {
+        if (!(std::isfinite(r[2 * c]) && std::isfinite(r[2 * c + 1]))) return "a range field is not finite";
+        if (r[2 * c] > r[2 * c + 1]) return "a range needs lo <= hi";
+    }
+    if (!(s.v_lo > 0.0)) return "the speed factor needs v_lo > 0";
+    for (int32_t m : {s.s_mode, s.e_mode, s.steady, s.time_mode, s.other_mode}) if (m != 0 && m != 1) return "a mode is 0 or 1";
+    for (int32_t z : s.reserved) if (z != 0) return "reserved must be 0";
+    return nullptr;
+}
+int pg_make_starts(pg_handle* h, int32_t B, int32_t n_sets, const pg_start_set* sets, const int32_t* set_index, uint64_t seed, const uint64_t* stream, int32_t install,
+                   double* state_out, double* control_out, double* t0_out, double* other_out, double* time_offset_out, double* placed_out) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, sets, "pg_make_starts: null argument");
+    REQUIRE(h, n_sets >= 1, "pg_make_starts: need n_sets >= 1");
+    REQUIRE(h, B >= 1 && B <= h->cfg.batch_capacity, "pg_make_starts: batch size outside [1, batch_capacity]");
+    std::string why;
+    auto problem = numbered_problem(start_set_problem, sets, why);
+    for (int k = 0; k < n_sets; k++) REQUIRE_NO(h, "pg_make_starts: ", problem(sets[k]));
+    if (set_index) for (int b = 0; b < B; b++) REQUIRE(h, set_index[b] >= 0 && set_index[b] < n_sets, "pg_make_starts: index out of range of the start sets");
+    if (!h->d_traj) { h->err = "pg_make_starts: no trajectory installed (the starts are placed on the installed library)"; return PG_ERR_STATE; }
+    if (h->dc.n_traj > 1 && h->traj_idx.covered() < B) { h->err = "pg_make_starts: a trajectory library is installed but pg_set_trajectory_index does not cover B (an instance is placed on its own tube)"; return PG_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t nb = (size_t)B;
+    CallBufs D; StartMakeArgs A{}; pg_start_set* d_sets = nullptr; int* d_idx = nullptr; unsigned long long* d_stream = nullptr;
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(A.state, nb * 6)); HIPCHK(h, D.alloc(A.control, nb * 3)); HIPCHK(h, D.alloc(A.other, nb * 4));
+    HIPCHK(h, D.alloc(A.t0, nb)); HIPCHK(h, D.alloc(A.toff, nb)); HIPCHK(h, D.alloc(A.placed, nb * 4));
+    // (plain copies: the caller's arrays are consumed when each returns, on every way out)
+    HIPCHK(h, hipMemcpy(d_sets, sets, (size_t)n_sets * sizeof(pg_start_set), hipMemcpyHostToDevice));
+    if (set_index && n_sets > 1) { HIPCHK(h, D.alloc(d_idx, nb)); HIPCHK(h, hipMemcpy(d_idx, set_index, nb * sizeof(int), hipMemcpyHostToDevice)); }
+    if (stream) { HIPCHK(h, D.alloc(d_stream, nb)); HIPCHK(h, hipMemcpy(d_stream, stream, nb * sizeof(unsigned long long), hipMemcpyHostToDevice)); }
+    A.B = B; A.n_sets = n_sets; A.sets = d_sets; A.set_index = d_idx; A.stream = d_stream; A.seed = (unsigned long long)seed;
+    hipLaunchKernelGGL(k_make_starts, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, h->dc, A);
+    LAUNCH_CHECK(h);
+    int rc = down(h, state_out, A.state, nb * 6);                  // (each waits for the stream: the kernel has run)
+    if (!rc) rc = down(h, control_out, A.control, nb * 3);
+    if (!rc) rc = down(h, other_out, A.other, nb * 4);
+    if (!rc) rc = down_raw(h, t0_out, A.t0, nb * 8);
+    if (!rc) rc = down_raw(h, time_offset_out, A.toff, nb * 8);
+    if (!rc) rc = down_raw(h, placed_out, A.placed, nb * 4 * 8);
+    if (!rc && install) rc = set_inputs(h, B, A.state, A.control, A.t0, A.other, A.toff, false);      // pg_set_inputs_dev: the same buffers, the restarted clock, the restart of every library state
+    const hipError_t e = hipStreamSynchronize(h->stream);          // the copies out of the call's buffers have landed before they are freed, on every way out
+    if (!rc && e != hipSuccess) { h->err = std::string("pg_make_starts: ") + hipGetErrorString(e); rc = PG_ERR_HIP; }
+    return rc;
+}
+
 static int check_ready(pg_handle* h) {
     if (!h) return PG_ERR_INVALID;
     if (h->B <= 0) { h->err = "no inputs installed (call pg_set_inputs first)"; return PG_ERR_STATE; }

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -407,6 +407,57 @@ class BatchedTrajectoryTrackingMPC:
         st = (_lib.pg_fit_stats * n)()
         self._chk(self.lib.pg_fit_paths(self.h, n, specs, len(wps), wps, Lmax, int(bool(install)), _p(L, c_i32p), _p(cl, c_i32p), _p(out), st), "pg_fit_paths")
         return self._made_tubes(out, L, 1, install), cl, np.frombuffer(st, dtype=FIT_STATS_DTYPE).copy()
+
+    # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
+    @classmethod
+    def pack_starts(cls, sets):
+        """dicts (vehicles.start(**overrides); missing fields: the defaults) or pg_start_set structures -> a ctypes array of pg_start_set.  Raises ValueError for what the
+        library refuses with PG_ERR_INVALID (include/pigeon_mpc.h)."""
+        def fill(rec, p):
+            full = _default_start(**p)
+            for name, ctype in _lib.pg_start_set._fields_:
+                if name != "reserved":
+                    setattr(rec, name, int(full[name]) if ctype is C.c_int32 else float(full[name]))
+        arr = cls._pack(_lib.pg_start_set, [sets] if isinstance(sets, (dict, _lib.pg_start_set)) else sets, fill)
+        if len(arr) == 0:
+            raise ValueError("make_starts: at least one start set")
+        for k, p in enumerate(arr):
+            for n in _lib.START_RANGES:
+                lo, hi = getattr(p, n + "_lo"), getattr(p, n + "_hi")
+                if not (math.isfinite(lo) and math.isfinite(hi)):
+                    raise ValueError(f"make_starts: set {k}: the range {n} is not finite")
+                if lo > hi:
+                    raise ValueError(f"make_starts: set {k}: the range {n} needs lo <= hi")
+            if not p.v_lo > 0:
+                raise ValueError(f"make_starts: set {k}: the speed factor needs v_lo > 0")
+            if any(getattr(p, m) not in (0, 1) for m in _lib.START_MODES):
+                raise ValueError(f"make_starts: set {k}: a mode is 0 or 1")
+            if any(p.reserved):
+                raise ValueError(f"make_starts: set {k}: reserved must be 0")
+        return arr
+
+    def make_starts(self, sets, index=None, seed=0, streams=None, B=None, install=True):
+        """The inputs of a batch placed on the INSTALLED trajectory library on the device (pg_make_starts; the scheme is stated in include/pigeon_mpc.h): sets = one
+        vehicles.start(**overrides) dict or a list of them, index = the set of every instance (None: set 0), seed and streams = the 64-bit stream id of every instance
+        (None: its position in the batch); a start is a function of (seed, stream id, set, tube) alone.  B = the batch size (None: the length of index or of streams, else
+        the current batch).  With several tubes installed an instance is placed on its own (set_trajectory_index first).  install=True makes them the handle's inputs, as
+        set_inputs with the returned arrays would, without the host round trip.  Returns a dict of arrays: state [B][6], control [B][3], t0 [B], other [B][4],
+        time_offset [B], placed [B][4] = (s, e, dpsi, V(s))."""
+        arr = self.pack_starts(sets)
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint64).reshape(-1)
+        if B is None:
+            B = len(idx) if idx is not None else len(st) if st is not None else self.B
+        B = int(B)
+        for what, a in (("index", idx), ("streams", st)):
+            if a is not None and len(a) != B:
+                raise ValueError(f"make_starts: {what} has {len(a)} entries for B = {B}")
+        out = dict(state=np.zeros((B, 6)), control=np.zeros((B, 3)), t0=np.zeros(B), other=np.zeros((B, 4)), time_offset=np.zeros(B), placed=np.zeros((B, 4)))
+        self._chk(self.lib.pg_make_starts(self.h, B, len(arr), arr, _p(idx, c_i32p), C.c_uint64(int(seed)), _p(st, C.POINTER(C.c_uint64)), int(bool(install)),
+                                          *(_p(out[k]) for k in ("state", "control", "t0", "other", "time_offset", "placed"))), "pg_make_starts")
+        if install:
+            self.B = B
+        return out
 
     # ---- the per-instance libraries share one protocol (pg_set_<name>_sets / pg_set_<name>_index / pg_clear_<name>_sets / pg_get_<name>_sets): the four routines below ----
     @staticmethod

@@ -165,6 +165,41 @@ def speed_plan(**overrides):
     return p
 
 
+START_RANGES = ("s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v")
+START_MODES = ("s_mode", "e_mode", "steady", "time_mode", "other_mode")
+
+
+def start(**overrides):
+    """One start set for make_starts (pg_start_set).  start() is the library's default (pg_default_start_set): every range [0, 0] except the speed factor v = [1, 1],
+    every mode 0 -- on the profile, at the first knot.  A range is given as one value or a pair: start(s=(5.0, 120.0), e=(-0.5, 0.5), v=1.05) or by its ends
+    (s_lo=5.0, s_hi=120.0); the modes by name (s_mode=1: s as a fraction of the tube's length; e_mode=1: e as a fraction of the local tube, -1 = edge_R, +1 = edge_L;
+    steady=1: the body state and control of steady_state_estimates; time_mode=1: path mode, time_offset = NaN; other_mode=1: the other car from the other_* ranges, ego
+    frame).  Build-defined: the reference receives its state from the car."""
+    p = {f"{n}_{end}": (1.0 if n == "v" else 0.0) for n in START_RANGES for end in ("lo", "hi")}
+    p.update({m: 0 for m in START_MODES})
+    for k, v in overrides.items():
+        if k in START_RANGES:
+            lo, hi = (v, v) if isinstance(v, numbers.Real) else v
+            p[k + "_lo"], p[k + "_hi"] = float(lo), float(hi)
+        elif k in START_MODES:
+            p[k] = int(v)
+        elif k in p:
+            p[k] = float(v)
+        else:
+            raise KeyError(f"{k} is not a field of a start set: the ranges {START_RANGES} (or <range>_lo / <range>_hi) and the modes {START_MODES}")
+    return p
+
+
+def start_config2(s_range=None, traj_mode=True):
+    """The start set whose ranges are those of synthetic.config2_inputs: e +-0.5 m, heading +-0.1 rad, V(s) x [0.9, 1.1], Uy +-0.2, r +-0.05, delta +-0.05, Fx +-500 N,
+    t0 +-0.2 s.  The same distribution, different numbers: the draws come from Philox per (seed, stream), not from a PCG64 stream over the batch, and V and t are the
+    controller's own lookup instead of a linear interpolation.  s_range = (lo, hi) in metres from the first knot; None takes the whole tube (s_mode 1, [0, 1]) --
+    config2_inputs' default window [5, s_end - 60] m needs the tube's length, which after an install only the device holds."""
+    s = dict(s=(0.0, 1.0), s_mode=1) if s_range is None else dict(s=tuple(s_range))
+    return start(e=(-0.5, 0.5), dpsi=(-0.1, 0.1), v=(0.9, 1.1), uy=(-0.2, 0.2), dr=(-0.05, 0.05), delta=(-0.05, 0.05), fx=(-500.0, 500.0), dt0=(-0.2, 0.2),
+                 time_mode=0 if traj_mode else 1, **s)
+
+
 PATH_SEGMENT_FIELDS = ("length", "kappa0", "kappa1", "edge_L0", "edge_L1", "edge_R0", "edge_R1", "reserved")
 
 
