@@ -27,12 +27,14 @@ template <class Host, class Dev> struct SetLib {
     bool on() const { return !sets.empty(); }                                             // the host knows whether a library is installed: that alone adds its kernel to a rollout step
     const int* index() const { return sets.size() > 1 ? idx.d : (const int*)nullptr; }    // what the kernels are handed: a library of at most one set needs no index
 };
+// record k of a [steps][B][width] history on the device (nullptr: not recorded)
+template <class T> static T* hist_at(T* hist, int k, int B, int width) { return hist ? hist + (size_t)k * B * width : nullptr; }
 // One history registration (pg_set_*_history_dev): a device record [steps][B][width] of the caller's.  One-shot: the next rollout call takes it, whether it succeeds or not
 struct HistSlot {
     real* buf = nullptr; int steps = 0;
     void clear() { buf = nullptr; steps = 0; }
     HistSlot take() { const HistSlot s = *this; clear(); return s; }
-    real* at(int k, int B, int width) const { return (buf && k < steps) ? buf + (size_t)k * B * width : (real*)nullptr; }      // record k; nullptr: not recorded
+    real* at(int k, int B, int width) const { return k < steps ? hist_at(buf, k, B, width) : (real*)nullptr; }      // record k; nullptr: not recorded
 };
 // The streams of a seeded library: the ids as installed (instances they do not cover: stream[b] = b), their device copy [capacity] (sync: uploaded when a rollout or a
 // *_response / pg_sensor_draws call first needs it and whenever the ids changed) and the seed, a launch argument
@@ -55,9 +57,9 @@ struct pg_handle {
     int lateral_solver = 0;                                   // option "lateral_solver": 0 = by horizon (k_solve_lat beyond 20 intervals or with the polish off), 1 = k_solve_lat, 2 = the embedding in k_solve
     int hji_cell_dims = 3;                                    // option "hji_cell_dims": corners per cell record of the next pg_set_hji_grid = 2^3 (256 B, default), 2^5, 2^7
     int64_t stat_pipelined = 0, stat_split = 0, stat_single = 0, stat_lat_two = 0;      // read-only options "stat_*": launches that took the pipelined nodes + update_QP path / the split solve / the single solve kernel / the two-launch lateral solve
+    // (these two are handle state, not arguments in disguise: pg_compute_linearization_nodes followed by a separate pg_solve relies on them across public calls)
     int solve_parity = 0;                                     // which of the two to-do counters the next solve launch counts into (the other one holds the previous launch's count: see launch_solve)
     bool cnt_cleared = false;                                 // this step's projection kernel has zeroed the counter launch_solve is about to use
-    bool lin_done = false;                                    // this step's launch_nodes already linearised (update_and_solve skips update_QP)
     int* d_progress = nullptr;                                // progress and fault words of the pipelined launch (k_nodes_linearize): layout below (pipe_fault_word)
     int64_t fallback_total = 0; int fallback_seen = 0;        // pg_get_pipeline_fallbacks: 64-bit total kept on the host, last value of the device's 32-bit word
     int fuse = 0;                                             // pg_step_dev / pg_simulate_dev: linearisation fused into the solve kernel (pg_set_fusion): 0 never (default), 1 always, 2 for all-warm batches
@@ -121,6 +123,7 @@ struct pg_handle {
         real *u = nullptr, *n = nullptr; bool script = false, fresh = true, valid = false; int64_t steps_stat = 0;
         void cleared() { script = false; fresh = true; valid = false; hist.clear(); }      // (a library installed later starts a driver of its own)
     } human;
+    // the inputs: the true state and the command, always -- assigned once, by pg_create.  What a step's controller is handed instead travels as a Seen (below)
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
     // clock of pg_simulate_dev (model_predictive_control.jl:87, `for t in 0:dt:trajectory.t[end]`): start time per instance, the range, and the index of the element t0 holds.
@@ -140,7 +143,6 @@ struct pg_handle {
                                                               // directions (option "lin_lanes" = 2: the lane pair of rounds 1-3, for A/B runs; same bits in fp64, rounding-level differences in fp32)
     int* d_todo = nullptr; int split_solve = 1, split_lat = 1;      // d_todo: instances one solve launch leaves to the next; behind them the control words of the solve launches: layout below (solve_ctl)
     int phase_timing = 0;                                           // option "phase_timing": 1 = pg_step_dev records the four HIP events pg_get_phase_ms reads (13-25 us of stream time per step at B = 4096: 2-4 %); 0 (default) = no instrumentation on the stream
-    real* u_direct = nullptr; bool u_written = false;               // pg_step_dev: the caller's control array for k_solve to write (SolveOut::u_out2), and whether the launch did
     int* d_order = nullptr; int order_B = 0;  // launch order filed by the nodes kernels of the current step (likely slow instances first): layout below (order_cnt); order_B = batch it is valid for
     real *d_pol_u2 = nullptr, *d_pol_u = nullptr; int* d_pol_src = nullptr;   // HJI fallback policy (HJI_computation.jl:133-158)
     real* d_vmin = nullptr; int* d_breach = nullptr;          // summary of pg_simulate_safety_dev: V_min [cap]; first_breach [cap] then policy_steps [cap] (k_advance_safety)
@@ -264,6 +266,13 @@ static SolveOut solve_out(const pg_handle* h, const int* order) {
     O.solved = h->d_solved; O.polish = h->d_polish; O.lam = h->d_lam; O.order_in = order; O.wfail = h->d_wfail;
     return O;
 }
+// pg_step_dev's control array (SolveOut::u_out2; nullptr: none) and whether a launch took it: every k_solve instantiation writes it itself, the lateral kernel does not
+struct DirectOut { real* u = nullptr; bool written = false; };
+static void take_direct(SolveOut& O, DirectOut& D) { if (D.u) { O.u_out2 = D.u; D.written = true; } }
+// What the controller's side of a step is handed as current state and current control: the handle's own pair, except in a rollout step under a sensor, estimator or
+// actuator library (rollout_compute).  Every launch on that side takes the two from here, never from the handle
+struct Seen { const real* state; const real* control; };
+static Seen seen_own(const pg_handle* h) { return Seen{h->d_state, h->d_control}; }
 // one k_solve launch, one wavefront per instance, `n` blocks
 template <bool PROF, bool RING, bool FUSE, bool IPM = true>
 static void launch_k_solve(pg_handle* h, hipStream_t st, int n, const SolveOut& O, unsigned long long* prof = nullptr) {
@@ -1609,7 +1618,7 @@ int pg_get_human_state(pg_handle* h, double* u) {
     return down(h, u, h->human.u, (size_t)h->B * 2);
 }
 // what mode 1 is handed as has_hji: a grid on a coupled handle (the safety rollout is coupled only; the node rollout passes its plant kernel the same word)
-static int human_has_hji(const pg_handle* h) { return (int)(h->hji.on && h->dc.formulation == PG_COUPLED); }
+static int has_hji_row(const pg_handle* h) { return (int)(h->hji.on && h->dc.formulation == PG_COUPLED); }
 int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out) {
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, step0 >= 0 && steps >= 1 && dt > 0.0 && x7 && vg8 && u_out, "pg_human_response: step0 >= 0, steps >= 1, dt > 0, x7, vg8 and the output array required");
@@ -1621,7 +1630,7 @@ int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, con
         real *dx = d, *dv = d + nx, *ds = dv + nv, *du = ds + nu;
         int rc;
         if ((rc = up(h, dx, x7, nx)) || (rc = up(h, dv, vg8, nv)) || (script && (rc = up(h, ds, script, nu)))) return rc;
-        hipLaunchKernelGGL(k_human_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, (int)step0, (int)steps, human_has_hji(h), (real)dt, h->human.lib.d,
+        hipLaunchKernelGGL(k_human_response, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, (int)step0, (int)steps, has_hji_row(h), (real)dt, h->human.lib.d,
                            h->human.lib.index(), h->human.streams.d, (unsigned long long)h->human.streams.seed, (const real*)dx, (const real*)dv,
                            script ? (const real*)ds : (const real*)nullptr, du);
         result = du;
@@ -1929,10 +1938,11 @@ int pg_compute_time_steps(pg_handle* h) {
     LAUNCH_CHECK(h);
     return PG_OK;
 }
-static int launch_nodes(pg_handle* h, bool with_time_grid);
+static int launch_nodes(pg_handle* h, const Seen& seen, bool with_time_grid, bool& lin_done);
 int pg_compute_linearization_nodes(pg_handle* h) {
     int rc = check_ready(h); if (rc) return rc;
-    return launch_nodes(h, false);
+    bool lin_done;      // (false: without the time grid the pipelined launch never applies)
+    return launch_nodes(h, seen_own(h), false, lin_done);
 }
 // compute_time_steps! + compute_linearization_nodes! of pg_step_dev / pg_simulate_dev: the time grid rides in the projection kernel (one launch fewer)
 // the pipelined nodes + update_QP launch (k_nodes_linearize) serves the steps of pg_step_dev / pg_simulate_dev when: coupled formulation, some instance is cold (an
@@ -1941,8 +1951,8 @@ int pg_compute_linearization_nodes(pg_handle* h) {
 // wavefronts to be resident at once (<= 16384 instances = 256 of the 1024 SIMD slots; measured with the one-lane linearisation: 12288: 0.72 against 0.86 ms, 16384: 1.02 against 1.07), and the
 // linearisation is not fused into the solve kernel.  With a safety row, its (M, b) -- functions of the measured states only -- are computed BEFORE the launch and the
 // launch order is re-filed after it (k_order_hji needs the verdicts the recurrence files).
-static int launch_hji_rows_compute(pg_handle* h);
-static int launch_hji_order(pg_handle* h);
+static int launch_hji_rows_compute(pg_handle* h, const Seen& seen);
+static int launch_hji_order(pg_handle* h, const Seen& seen);
 static bool pipeline_applies(const pg_handle* h) {
     const DevCfg& C = h->dc;
     const bool fuse_wanted = h->fuse == 1;
@@ -1954,10 +1964,10 @@ static OrderOut order_out(const pg_handle* h, int* order) {
     return F;
 }
 // The four branches of launch_nodes behind the projection.  staged / traj_lds: the trajectory travels through LDS; F: where the launch order of the step is filed.
-static int launch_nodes_decoupled(pg_handle* h, bool staged, size_t traj_lds) {
+static int launch_nodes_decoupled(pg_handle* h, const Seen& seen, bool staged, size_t traj_lds) {
     const int B = h->B;
     auto kern = staged ? k_nodes_dec<true> : k_nodes_dec<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((B + NODES_DEC_IPB - 1) / NODES_DEC_IPB)), dim3(64), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_toff, h->d_sep, h->d_ts, h->d_dt, h->d_nodes, h->d_naux);      // (NODES_DEC_LPN lanes per instance)
+    hipLaunchKernelGGL(kern, dim3((unsigned)((B + NODES_DEC_IPB - 1) / NODES_DEC_IPB)), dim3(64), traj_lds, h->stream, h->dc, B, seen.state, seen.control, h->d_toff, h->d_sep, h->d_ts, h->d_dt, h->d_nodes, h->d_naux);      // (NODES_DEC_LPN lanes per instance)
     LAUNCH_CHECK(h);
     const long nn = (long)B * h->dc.NN;
     hipLaunchKernelGGL(k_nodes_angles, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, (const int*)nullptr);
@@ -1965,18 +1975,18 @@ static int launch_nodes_decoupled(pg_handle* h, bool staged, size_t traj_lds) {
     return PG_OK;
 }
 // every instance takes the warm branch: lane = (instance, node)
-static int launch_nodes_warm(pg_handle* h, bool staged, size_t traj_lds, const OrderOut& F, bool recheck) {
+static int launch_nodes_warm(pg_handle* h, const Seen& seen, bool staged, size_t traj_lds, const OrderOut& F, bool recheck) {
     const int B = h->B;
     auto kern = staged ? k_nodes_warm<true> : k_nodes_warm<false>;
     const long nth = (long)B * h->dc.NN;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((nth + 255) / 256)), dim3(256), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_sep, h->d_ts, h->d_prev_ts, h->d_solx,
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nth + 255) / 256)), dim3(256), traj_lds, h->stream, h->dc, B, seen.state, seen.control, h->d_sep, h->d_ts, h->d_prev_ts, h->d_solx,
                        h->d_nodes, F);
     if (recheck) {          // behind a node step: instances without a solution are known on the device only (k_nodes_recheck, predicated on the word k_node_finish filed)
         LAUNCH_CHECK(h);
         const int* cold = node_cold(h, h->node_parity);
         OrderOut Fr = order_out(h, nullptr); Fr.cnt = nullptr; Fr.slow = nullptr;      // (the launch order stays as k_nodes_warm filed it)
         auto rk = staged ? k_nodes_recheck<true> : k_nodes_recheck<false>;
-        hipLaunchKernelGGL(rk, dim3((B + NODES_IPB - 1) / NODES_IPB), dim3(64), traj_lds, h->stream, h->dc, B, cold, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep,
+        hipLaunchKernelGGL(rk, dim3((B + NODES_IPB - 1) / NODES_IPB), dim3(64), traj_lds, h->stream, h->dc, B, cold, seen.state, seen.control, h->d_toff, h->d_solved, h->d_sep,
                            h->d_ts, h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, Fr, h->d_naux);
         LAUNCH_CHECK(h);
         hipLaunchKernelGGL(k_nodes_angles, dim3(64), dim3(256), 0, h->stream, h->dc, B, h->d_naux, h->d_nodes, cold);
@@ -1985,9 +1995,9 @@ static int launch_nodes_warm(pg_handle* h, bool staged, size_t traj_lds, const O
     return PG_OK;
 }
 // nodes + update_QP! as one pipelined launch (k_nodes_linearize), its predicated repair, and the rate rows of a control-parameter library
-static int launch_nodes_pipelined(pg_handle* h, bool staged, size_t traj_lds, const OrderOut& F) {
+static int launch_nodes_pipelined(pg_handle* h, const Seen& seen, bool staged, size_t traj_lds, const OrderOut& F) {
     const int B = h->B;
-    { int rc = launch_hji_rows_compute(h); if (rc) return rc; }      // (M, b) of the safety row: read by the lanes that linearise interval 0
+    { int rc = launch_hji_rows_compute(h, seen); if (rc) return rc; }      // (M, b) of the safety row: read by the lanes that linearise interval 0
     const int lpi = h->lin_lpi, ipb = 64 / lpi;
     const int nbn = (B + NODES_IPB - 1) / NODES_IPB, nbt = (B + ipb - 1) / ipb;
     const size_t lds = traj_lds > 64 * 20 * sizeof(real) ? traj_lds : 64 * 20 * sizeof(real);
@@ -2005,7 +2015,7 @@ static int launch_nodes_pipelined(pg_handle* h, bool staged, size_t traj_lds, co
     for (int i = 1; i < h->dc.N - 2 && i < 63; i++)
         if (i <= h->dc.Ns ? i % h->pipe_pub_short == 0 : (i - h->dc.Ns) % h->pipe_pub_long == h->pipe_pub_long - 1) pub |= 1ull << i;
     if (h->pipe_fault) pub = 1ull << 63;                  // test hook: nothing is ever published (tests/test_gpu_api_contract.py)
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nbn + nbt * h->dc.N)), dim3(64), lds, h->stream, h->dc, B, nbn, nzf, pub, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nbn + nbt * h->dc.N)), dim3(64), lds, h->stream, h->dc, B, nbn, nzf, pub, seen.state, seen.control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
                        h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, F, h->d_naux, h->d_progress, h->d_Mb, h->d_qp, pipe_fault_word(h, nbn), pipe_fallbacks(h));
     LAUNCH_CHECK(h);
     // repair, queued unconditionally and predicated on the device: if any waiting wavefront of the launch above gave up (its fault word, zeroed by the
@@ -2026,15 +2036,15 @@ static int launch_nodes_pipelined(pg_handle* h, bool staged, size_t traj_lds, co
         const long nt = (long)B * h->dc.N;
         hipLaunchKernelGGL(k_rate_limits, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, h->dc, B, h->d_qp);
     }
-    h->lin_done = true; h->stat_pipelined++;
+    h->stat_pipelined++;
     LAUNCH_CHECK(h);
     return PG_OK;
 }
 // some instance is cold: the recurrence, one lane group per instance, then the deferred angles
-static int launch_nodes_cold(pg_handle* h, bool staged, size_t traj_lds, const OrderOut& F) {
+static int launch_nodes_cold(pg_handle* h, const Seen& seen, bool staged, size_t traj_lds, const OrderOut& F) {
     const int B = h->B;
     auto kern = staged ? k_nodes<true> : k_nodes<false>;
-    hipLaunchKernelGGL(kern, dim3((B + NODES_IPB - 1) / NODES_IPB), dim3(64), traj_lds, h->stream, h->dc, B, h->d_state, h->d_control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
+    hipLaunchKernelGGL(kern, dim3((B + NODES_IPB - 1) / NODES_IPB), dim3(64), traj_lds, h->stream, h->dc, B, seen.state, seen.control, h->d_toff, h->d_solved, h->d_sep, h->d_ts,
                        h->d_dt, h->d_prev_ts, h->d_solx, h->d_nodes, F, h->d_naux);
     LAUNCH_CHECK(h);
     const long nn = (long)B * h->dc.NN;
@@ -2042,28 +2052,28 @@ static int launch_nodes_cold(pg_handle* h, bool staged, size_t traj_lds, const O
     LAUNCH_CHECK(h);
     return PG_OK;
 }
-static int launch_nodes(pg_handle* h, bool with_time_grid) {
+static int launch_nodes(pg_handle* h, const Seen& seen, bool with_time_grid, bool& lin_done) {
     const int B = h->B;
     const bool recheck = h->node_recheck && !h->sg.capturing; h->node_recheck = false;
     const bool pipelined = with_time_grid && pipeline_applies(h);
-    h->lin_done = false;
+    lin_done = pipelined;      // the pipelined branch (taken whenever pipeline_applies: coupled, some instance cold) writes this step's QP data too: update_and_solve skips update_QP!
     const bool file = h->dc.formulation != PG_DECOUPLED && h->dc.polish;
     int* const cnt = file ? order_cnt(h) : (int*)nullptr;                      // the two counters of the launch order start from zero: the projection kernel clears them (no memset of its own)
     int* const ctl = solve_ctl(h, CTL_TODO0);                                  // ... and the control words of this step's solve launches (launch_solve_coupled): the to-do counter it counts into
     h->cnt_cleared = !h->sg.capturing;
-    if (with_time_grid) hipLaunchKernelGGL(k_project<true>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep, h->d_t0, h->d_ts, h->d_dt, h->d_prev_ts,
+    if (with_time_grid) hipLaunchKernelGGL(k_project<true>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, seen.state, h->d_sep, h->d_t0, h->d_ts, h->d_dt, h->d_prev_ts,
                                            pipelined ? h->d_progress : (int*)nullptr, (B + NODES_IPB - 1) / NODES_IPB + 1, cnt, ctl, h->solve_parity);      // (+ 1: the fault word of the pipelined launch)
-    else hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_state, h->d_sep, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
+    else hipLaunchKernelGGL(k_project<false>, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, seen.state, h->d_sep, (const double*)nullptr, (double*)nullptr, (double*)nullptr,
                             (double*)nullptr, (int*)nullptr, 0, cnt, ctl, h->solve_parity);
     LAUNCH_CHECK(h);
     const bool staged = h->dc.n_traj == 1 && h->traj_L <= 2048;
     const size_t traj_lds = staged ? (size_t)2 * h->traj_L * sizeof(real) : 0;
     const OrderOut F = order_out(h, file ? h->d_order : nullptr);
     h->order_B = file ? B : 0;
-    if (h->dc.formulation == PG_DECOUPLED) return launch_nodes_decoupled(h, staged, traj_lds);
-    if (h->warm_B >= B) return launch_nodes_warm(h, staged, traj_lds, F, recheck);
-    if (pipelined) return launch_nodes_pipelined(h, staged, traj_lds, F);
-    return launch_nodes_cold(h, staged, traj_lds, F);
+    if (h->dc.formulation == PG_DECOUPLED) return launch_nodes_decoupled(h, seen, staged, traj_lds);
+    if (h->warm_B >= B) return launch_nodes_warm(h, seen, staged, traj_lds, F, recheck);
+    if (pipelined) return launch_nodes_pipelined(h, seen, staged, traj_lds, F);
+    return launch_nodes_cold(h, seen, staged, traj_lds, F);
 }
 static int launch_hji_lookup(pg_handle* h, int B, const real* x7_dev, real* out8_dev) {
     dim3 grid((unsigned)(((size_t)B * 16 + 255) / 256));
@@ -2076,30 +2086,30 @@ static int launch_hji_lookup(pg_handle* h, int B, const real* x7_dev, real* out8
 // the safety row of update_QP! (coupled_lat_long.jl:345-346): relative state, value / gradient look-up, (M, b) per instance
 // (two halves: the rows themselves read the measured states only and may run before the nodes -- the pipelined launch needs (M, b) when it linearises interval 0 --,
 // the re-filed launch order needs the verdicts the nodes kernel filed)
-static int launch_hji_rows_compute(pg_handle* h) {
+static int launch_hji_rows_compute(pg_handle* h, const Seen& seen) {
     if (!h->hji.on) return PG_OK;
     const int B = h->B;
-    hipLaunchKernelGGL(k_hji_relstate, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, h->d_state, h->d_other, h->d_x7);
+    hipLaunchKernelGGL(k_hji_relstate, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, seen.state, h->d_other, h->d_x7);
     LAUNCH_CHECK(h);
     int rc = launch_hji_lookup(h, B, h->d_x7, h->d_vg8); if (rc) return rc;
-    hipLaunchKernelGGL(k_hji_constraint, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, h->d_x7, h->d_vg8, h->d_control, h->d_Mb);
+    hipLaunchKernelGGL(k_hji_constraint, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, h->d_x7, h->d_vg8, seen.control, h->d_Mb);
     LAUNCH_CHECK(h);
     return PG_OK;
 }
-static int launch_hji_order(pg_handle* h) {
+static int launch_hji_order(pg_handle* h, const Seen& seen) {
     if (!h->hji.on) return PG_OK;
     const int B = h->B;
     if (h->dc.polish && h->order_B == B) {              // launch order again, now that the safety rows are known (k_order_hji)
         const OrderOut F = order_out(h, h->d_order);
         HIPCHK(h, hipMemsetAsync(order_cnt(h), 0, ORDER_CNT_WORDS * sizeof(int), h->stream));
-        hipLaunchKernelGGL(k_order_hji, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->dc, B, h->d_control, h->d_Mb, F);
+        hipLaunchKernelGGL(k_order_hji, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->dc, B, seen.control, h->d_Mb, F);
         LAUNCH_CHECK(h);
     }
     return PG_OK;
 }
-static int launch_hji_rows(pg_handle* h) {
-    int rc = launch_hji_rows_compute(h); if (rc) return rc;
-    return launch_hji_order(h);
+static int launch_hji_rows(pg_handle* h, const Seen& seen) {
+    int rc = launch_hji_rows_compute(h, seen); if (rc) return rc;
+    return launch_hji_order(h, seen);
 }
 #define PG_LIN_PAIR_MAX 1024
 static int launch_linearize(pg_handle* h, int n) {
@@ -2133,8 +2143,8 @@ static int launch_linearize(pg_handle* h, int n) {
     LAUNCH_CHECK(h);
     return PG_OK;
 }
-int pg_update_qp(pg_handle* h) {
-    int rc = check_ready(h); if (rc) return rc;
+static int update_qp(pg_handle* h, const Seen& seen) {
+    int rc;
     const int B = h->B; const DevCfg& C = h->dc;
     if (C.formulation == PG_DECOUPLED) {
         long nt = (long)B * C.N;
@@ -2145,9 +2155,10 @@ int pg_update_qp(pg_handle* h) {
         h->qp_embedded = embed != 0; h->qp_stale = false;
         return PG_OK;
     }
-    if ((rc = launch_hji_rows(h))) return rc;
+    if ((rc = launch_hji_rows(h, seen))) return rc;
     return launch_linearize(h, B);
 }
+int pg_update_qp(pg_handle* h) { const int rc = check_ready(h); return rc ? rc : update_qp(h, seen_own(h)); }
 static const int* solve_order(const pg_handle* h) { return (h->dc.polish && h->order_B == h->B) ? h->d_order : nullptr; }      // the launch order the nodes kernels of this step filed (likely slow instances first)
 static void mark_solved(pg_handle* h) { if (h->B > h->warm_B) h->warm_B = h->B; }      // model_predictive_control.jl:76: solved = true for every instance of the batch
 static dim3 lat_grid4(const pg_handle* h) { return dim3((unsigned)((h->B + 3) / 4)); }                              // four instances per wavefront
@@ -2225,9 +2236,9 @@ static int launch_solve_lat(pg_handle* h, hipStream_t st, unsigned long long* la
 }
 // coupled formulation (and the lateral one embedded in it), one wavefront per instance: `n` instances, the whole batch in index order (order == nullptr) or the
 // sub-range order[0..n) of the launch order
-static int launch_solve_coupled(pg_handle* h, hipStream_t st, const int* order, int n) {
+static int launch_solve_coupled(pg_handle* h, hipStream_t st, const int* order, int n, DirectOut& direct) {
     SolveOut O = solve_out(h, order);
-    if (h->u_direct) { O.u_out2 = h->u_direct; h->u_written = true; }      // (every k_solve instantiation below writes the caller's array itself)
+    take_direct(O, direct);
     if (h->solve_ring) launch_k_solve<false, true, false>(h, st, n, O);
     else if (h->split_solve && h->dc.polish && (h->dc.cold_guess > 0 || h->dc.warm_polish) && !h->hji.on && !h->sg.capturing) {
         // Two launches: the rounds-only instantiation (no scratch: the interior point's state and code are not in it) serves the instances an active-set attempt
@@ -2257,14 +2268,15 @@ static int launch_solve_coupled(pg_handle* h, hipStream_t st, const int* order, 
     LAUNCH_CHECK(h);
     return PG_OK;
 }
-static int launch_solve(pg_handle* h, hipStream_t st, const int* order, int n) { return h->solve_lat ? launch_solve_lat(h, st, nullptr) : launch_solve_coupled(h, st, order, n); }
-int pg_solve(pg_handle* h) {
-    int rc = check_ready(h); if (rc) return rc;
+static int launch_solve(pg_handle* h, hipStream_t st, const int* order, int n, DirectOut& direct) { return h->solve_lat ? launch_solve_lat(h, st, nullptr) : launch_solve_coupled(h, st, order, n, direct); }
+static int solve_qp(pg_handle* h, DirectOut& direct) {
+    int rc;
     if (h->qp_stale) { h->err = "pg_solve: the lateral solver was switched (pg_set_option \"lateral_solver\") after the last update_QP!: call pg_update_qp first"; return PG_ERR_STATE; }
-    if ((rc = launch_solve(h, h->stream, solve_order(h), h->B))) return rc;
+    if ((rc = launch_solve(h, h->stream, solve_order(h), h->B, direct))) return rc;
     mark_solved(h);
     return PG_OK;
 }
+int pg_solve(pg_handle* h) { DirectOut none; const int rc = check_ready(h); return rc ? rc : solve_qp(h, none); }
 // update_QP! + solve! of one step.  For the coupled formulation with N <= 32 both run in ONE kernel (k_solve<.., FUSE = true>): the wavefront that solves an instance
 // first linearises it (two lanes per interval = 60 of its 64 lanes), writes the QP data (still readable through pg_get_qp) and goes on to the solve.  k_solve ends
 // with its slowest wave -- an instance that needs the interior point takes 0.5 ms whatever the batch size -- and as a separate kernel it leaves part of the machine
@@ -2275,17 +2287,15 @@ int pg_solve(pg_handle* h) {
 // loops were 5-8 % faster fused as long as a few instances per step fell back to the interior point; with those stragglers gone (the polish rules of k_solve)
 // the two-kernel sequence wins there too (0.91 vs 0.99, 1.06 vs 1.11, 0.87 vs 0.98 ms per closed-loop step).  Hence OFF by default (pg_set_fusion:
 // 0 never, 1 always, 2 for all-warm batches of >= 1024 instances).
-static int update_and_solve(pg_handle* h, hipEvent_t after_update) {
+static int update_and_solve(pg_handle* h, const Seen& seen, bool lin_done, hipEvent_t after_update, DirectOut& direct) {
     const bool want = h->fuse == 1 || (h->fuse == 2 && h->warm_B >= h->B && h->B >= 1024);
-    const bool lin_done = h->lin_done;      // the QP data of this step are already there (k_nodes_linearize)
     const bool fused = !lin_done && want && h->dc.formulation != PG_DECOUPLED && !h->solve_ring && 2 * h->dc.N <= 64;
-    h->lin_done = false;
-    const int rc = lin_done ? launch_hji_order(h) : (fused ? launch_hji_rows(h) : pg_update_qp(h));
+    const int rc = lin_done ? launch_hji_order(h, seen) : (fused ? launch_hji_rows(h, seen) : update_qp(h, seen));
     if (rc) return rc;
     if (after_update) HIPCHK(h, hipEventRecord(after_update, h->stream));
-    if (!fused) return pg_solve(h);
+    if (!fused) return solve_qp(h, direct);
     SolveOut O = solve_out(h, solve_order(h));
-    if (h->u_direct) { O.u_out2 = h->u_direct; h->u_written = true; }
+    take_direct(O, direct);
     launch_k_solve<false, false, true>(h, h->stream, h->B, O);
     LAUNCH_CHECK(h);
     mark_solved(h);
@@ -2366,13 +2376,11 @@ int pg_step_dev(pg_handle* h, void* u_out_dev) {
     int rc = check_ready(h); if (rc) return rc;
     const bool ev = !h->sg.capturing && h->phase_timing != 0;     // (a step that is being captured into a graph carries no timing events; option "phase_timing" = 0: none at all)
     if (ev) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if ((rc = launch_nodes(h, true))) return rc;
+    const Seen seen = seen_own(h); bool lin_done; DirectOut direct{(real*)u_out_dev};
+    if ((rc = launch_nodes(h, seen, true, lin_done))) return rc;
     if (ev) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    h->u_direct = (real*)u_out_dev; h->u_written = false;
-    rc = update_and_solve(h, ev ? h->ev[2] : nullptr);       // (chunked: ev[2] marks the end of the LAST update_QP chunk; earlier solve chunks run under it)
-    h->u_direct = nullptr;
-    if (rc) return rc;
-    if (!h->u_written && (rc = pg_get_next_control_dev(h, u_out_dev))) return rc;      // (k_solve writes the caller's array itself; the lateral kernel's controls are copied)
+    if ((rc = update_and_solve(h, seen, lin_done, ev ? h->ev[2] : nullptr, direct))) return rc;       // (chunked: ev[2] marks the end of the LAST update_QP chunk; earlier solve chunks run under it)
+    if (!direct.written && (rc = pg_get_next_control_dev(h, u_out_dev))) return rc;      // (k_solve writes the caller's array itself; the lateral kernel's controls are copied)
     if (ev) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     h->timing_valid = ev;
     return PG_OK;
@@ -2380,7 +2388,11 @@ int pg_step_dev(pg_handle* h, void* u_out_dev) {
 // the loop's clock (:87): t takes the elements of 0:dt:trajectory.t[end], here shifted by each instance's start time.  A call continues the clock of the previous one
 // (same dt, same path end, no pg_set_inputs in between); otherwise it restarts from the times the inputs carry (and so does the safety summary)
 // the compute calls of one closed-loop step (model_predictive_control.jl:90-93; the time grid rides in the projection launch): fusion, pipelining and the split solve as pg_step_dev has them
-static int step_compute(pg_handle* h) { const int rc = launch_nodes(h, true); return rc ? rc : update_and_solve(h, nullptr); }
+static int step_compute(pg_handle* h, const Seen& seen) {
+    bool lin_done; DirectOut none;
+    const int rc = launch_nodes(h, seen, true, lin_done);
+    return rc ? rc : update_and_solve(h, seen, lin_done, nullptr, none);
+}
 // the arguments the rollouts share (`who`: the entry point, for the message; a rollout without a human passes mode 0)
 // human_lib: the rollout runs under a human library -- the sets decide, and the script is wanted exactly when one of them has mode 2
 static int check_rollout_args(pg_handle* h, const char* who, int32_t steps, double dt, int32_t human_mode, const void* human_u_dev, bool human_lib) {
@@ -2447,8 +2459,8 @@ static int launch_disturb(pg_handle* h, int step, int k, double dt, const HistSl
 static int launch_human(pg_handle* h, int step, int k, double dt, const void* script, const HistSlot& hist) {
     const int B = h->B; auto& U = h->human;
     const HumanLib lib{U.lib.d, U.lib.index(), U.streams.d, (unsigned long long)U.streams.seed, U.n, U.u};
-    hipLaunchKernelGGL(k_human, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, step, (int)U.fresh, human_has_hji(h), (real)dt, lib, (const real*)h->d_x7,
-                       (const real*)h->d_vg8, script ? (const real*)script + (size_t)k * B * 2 : (const real*)nullptr, hist.at(k, B, 2));
+    hipLaunchKernelGGL(k_human, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc.veh, B, step, (int)U.fresh, has_hji_row(h), (real)dt, lib, (const real*)h->d_x7,
+                       (const real*)h->d_vg8, hist_at((const real*)script, k, B, 2), hist.at(k, B, 2));
     LAUNCH_CHECK(h);
     U.fresh = false; U.valid = true; U.steps_stat++;
     return PG_OK;
@@ -2463,39 +2475,32 @@ static int launch_actuate(pg_handle* h, int step, int k, double dt, const HistSl
     A.fresh = false;
     return PG_OK;
 }
-// the controller's side of one rollout step: the node gate (node rollout) and the compute calls.  Under a sensor library k_measure writes the measured state of clock step
-// `step` first, and the handle's state pointer names THAT buffer while the gate and the compute kernels are queued -- they all take the state from the handle --, then the true
-// one again for the summary, the records and the plant: no copy, no restore launch, no kernel changed.  Under an estimator library k_estimate follows (on the measured state, or on the true one without a sensor library) and
-// the pointer names estimator.x in the same way: the gates, the projection, the nodes, the QP's q_curr, the HJI relative state and the policy selection all follow the estimate.
-// Without either library: the gate and the compute calls, nothing else
-static int node_gate(pg_handle* h, const uint8_t* pre_flag);
-static int rollout_compute(pg_handle* h, int step, int k, double dt, const HistSlot& measured, const HistSlot& estimated, bool gate, const uint8_t* pre_flag) {
+// the controller's side of one rollout step: the node gate (node rollout) and the compute calls, on the view built here.  State: under a sensor library k_measure writes the
+// measured state of clock step `step` and the view names that; under an estimator library k_estimate follows (on the measured state, or on the true one without a sensor
+// library) and the view names estimator.x -- the gates, the projection, the nodes, the QP's q_curr, the HJI relative state and the policy selection all follow it; without
+// either, the true state.  Control: `control`, as the rollout hands it in (the command, or actuator.seen).  The summary, the records and the plant never see the view
+static int node_gate(pg_handle* h, const Seen& seen, const uint8_t* pre_flag);
+static int rollout_compute(pg_handle* h, const real* control, int step, int k, double dt, const HistSlot& measured, const HistSlot& estimated, bool gate, const uint8_t* pre_flag) {
     int rc;
     auto& S = h->sensor; auto& E = h->estimator;
-    if (!S.lib.on() && !E.lib.on()) return (gate && (rc = node_gate(h, pre_flag))) ? rc : step_compute(h);
     const int B = h->B;
-    real* const true_state = h->d_state;
-    real* seen = true_state;                                     // what the gate and the compute calls read: the sensor's output, or the estimator's on top of it
+    Seen seen{h->d_state, control};
     if (S.lib.on()) {
         const SensorLib lib{S.lib.d, S.lib.index(), S.streams.d, (unsigned long long)S.streams.seed};
         hipLaunchKernelGGL(k_measure, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, step, lib, h->d_state, S.meas, measured.at(k, B, 6));
         LAUNCH_CHECK(h);
         S.valid = true; S.steps_stat++;
-        seen = S.meas;
+        seen.state = S.meas;
     }
-    if (E.lib.on()) {      // (h->d_control: what the compute calls below are handed as current_control -- the command, or actuator.seen under an actuator library with feedback)
+    if (E.lib.on()) {
         const EstimatorLib lib{E.lib.d, E.lib.index(), E.x, E.u};
-        hipLaunchKernelGGL(k_estimate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)E.fresh, (real)(dt / h->dc.nsub), lib, (const real*)seen,
-                           (const real*)h->d_control, estimated.at(k, B, 6));
+        hipLaunchKernelGGL(k_estimate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, (int)E.fresh, (real)(dt / h->dc.nsub), lib, seen.state, seen.control, estimated.at(k, B, 6));
         LAUNCH_CHECK(h);
         E.fresh = false; E.valid = true; E.steps_stat++;
-        seen = E.x;
+        seen.state = E.x;
     }
-    h->d_state = seen;
-    rc = gate ? node_gate(h, pre_flag) : PG_OK;
-    if (!rc) rc = step_compute(h);
-    h->d_state = true_state;
-    return rc;
+    if (gate && (rc = node_gate(h, seen, pre_flag))) return rc;
+    return step_compute(h, seen);
 }
 // the plant library as the library kernels (k_*_lib) take it (the host knows whether one is installed: that alone picks the kernel)
 static PlantLib plant_lib(const pg_handle* h) { return PlantLib{h->plants.d, h->plants.index()}; }
@@ -2536,11 +2541,12 @@ static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_di
 }
 // The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated, human) are taken (THIS call consumes them, also when it fails below), check_ready,
 // the entry point's own precondition (coupled_only: the message for a lateral handle, nullptr: none), the shared arguments, rollout_ready, the node's buffers (node: the
-// rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records(k) ahead of the compute calls, the
-// controller's side (:90-93, on the measured state under a sensor library), the tracking summary, the clock index, then finish(k, step): the step's last launch, which moves
-// the plant (step: index of the clock element t0 held -- steps continue across calls)
+// rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records ahead of the compute calls, the
+// controller's side (:90-93, rollout_compute), the tracking summary, the clock index, then finish: the step's last launch, which moves the plant
 static const char* const ACTUATOR_NODE_REFUSAL = "an actuator library is installed and the node callback is outside its scope (k_node_finish keeps message and applied command "
                                                  "apart and leaves `applied` unwritten for a gated-out instance: no plain hand-back of the next command); pg_clear_actuator_sets first";
+// one step as records and finish see it: k within the call, the clock step (index of the clock element t0 held -- steps continue across calls), the control they read
+struct RolloutStep { int k, step; real* control; };
 struct RolloutArgs { const char* who; int32_t steps; double dt; int32_t human_mode; const void* human_u; const char* coupled_only; bool node; const uint8_t* pre_flag; bool other_car; };
 template <class Records, class Finish>
 static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish finish) {
@@ -2550,47 +2556,41 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
     if (a.node && h->actuator.lib.on()) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
     const bool human = a.other_car && h->human.lib.on();         // (pg_simulate_dev has no other car: it never reads the human library)
     if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u, human)) || (rc = rollout_ready(h, human)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
-    // Under an actuator library the handle's control pointer names, while the launches are QUEUED: actuator.plant_u (= a_k) for the records and the plant launch, actuator.seen for the
-    // compute calls when some set has feedback == 1 -- k_nodes*, the QP's u_curr and the steering-rate rows all take the pointer from the handle --, and its own allocation
-    // (the command) everywhere else and whenever this function returns.  The plant kernel leaves the next command in plant_u: one copy moves it to the control buffer
+    // Who reads which control.  The records and the plant launch: actuator.plant_u (= a_k) under an actuator library, else the command.  The compute calls -- k_nodes*, the
+    // QP's u_curr, the steering-rate rows, k_estimate --: actuator.seen when some set has feedback == 1, else the command.  k_actuate: the command (the handle's own buffer).
+    // The plant kernel leaves the next command in plant_u: one copy moves it to the control buffer
     auto& A = h->actuator;
     const bool act = A.lib.on(), dist = h->disturbance.lib.on();
     real* const command = h->d_control;
+    real* const plant_u = act ? A.plant_u : command;
+    const real* const seen_u = act && A.feedback ? A.seen : command;
     for (int k = 0; k < a.steps; k++) {
-        const int step = h->sim_idx - 1;
-        if (act && (rc = launch_actuate(h, step, k, a.dt, hist.applied, hist.command))) return rc;
-        if (dist && (rc = launch_disturb(h, step, k, a.dt, hist.disturbance))) return rc;      // (w of this step: read by the step's last launch only)
-        if (act) h->d_control = A.plant_u;
-        rc = records(k);
-        if (act) h->d_control = A.feedback ? A.seen : command;
-        if (!rc) rc = rollout_compute(h, step, k, a.dt, hist.measured, hist.estimated, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr);
-        h->d_control = command;
-        if (rc || (rc = launch_track(h, step)) || (human && (rc = launch_human(h, step, k, a.dt, a.human_u, hist.human)))) return rc;
+        const RolloutStep s{k, h->sim_idx - 1, plant_u};
+        if (act && (rc = launch_actuate(h, s.step, k, a.dt, hist.applied, hist.command))) return rc;
+        if (dist && (rc = launch_disturb(h, s.step, k, a.dt, hist.disturbance))) return rc;      // (w of this step: read by the step's last launch only)
+        if ((rc = records(s)) || (rc = rollout_compute(h, seen_u, s.step, k, a.dt, hist.measured, hist.estimated, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr)) ||
+            (rc = launch_track(h, s.step)) || (human && (rc = launch_human(h, s.step, k, a.dt, a.human_u, hist.human)))) return rc;
         h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)
-        if (act) h->d_control = A.plant_u;
-        finish(k, step);
-        h->d_control = command;
+        finish(s);
         LAUNCH_CHECK(h);
         if (act) {
-            HIPCHK(h, hipMemcpyAsync(command, A.plant_u, (size_t)h->B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(command, plant_u, (size_t)h->B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));
             A.steps_stat++;
         }
     }
     return PG_OK;
 }
-static int no_records(int) { return PG_OK; }
-// record k of a [steps][B][width] history (nullptr: not recorded)
-template <class T> static T* hist_at(T* hist, int k, int B, int width) { return hist ? hist + (size_t)k * B * width : nullptr; }
+static int no_records(const RolloutStep&) { return PG_OK; }
 extern "C" {
 int pg_simulate_dev(pg_handle* h, int32_t steps, double dt, void* state_hist_dev, void* control_hist_dev) {
     return rollout(h, RolloutArgs{"pg_simulate_dev", steps, dt, 0, nullptr, nullptr, false, nullptr, false},
-        [&](int k) -> int {
-            const int B = h->B;
+        [&](const RolloutStep& s) -> int {
+            const int B = h->B, k = s.k;
             if (state_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)state_hist_dev, k, B, 6), h->d_state, (size_t)B * 6 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));          // push!(qs, state) :88
-            if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)control_hist_dev, k, B, 3), h->d_control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));  // push!(us, control) :89
+            if (control_hist_dev) HIPCHK(h, hipMemcpyAsync(hist_at((real*)control_hist_dev, k, B, 3), s.control, (size_t)B * 3 * sizeof(real), hipMemcpyDeviceToDevice, h->stream));  // push!(us, control) :89
             return PG_OK;
         },
-        [&](int, int) { launch_plant_step(h, k_advance, k_advance_lib<>, k_advance_lib<DistW>, h->dc, h->B, dt, h->d_state, h->d_control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
+        [&](const RolloutStep& s) { launch_plant_step(h, k_advance, k_advance_lib<>, k_advance_lib<DistW>, h->dc, h->B, dt, h->d_state, s.control, h->d_u, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx); });      // :94-95
 }
 // simulate (:80-100) with the control the ROS node sends (ros_integration.jl:114-124) fed back and the other car moving (k_advance_safety, pg_kernels.hip).  Per step: the four
 // compute calls exactly as pg_simulate_dev makes them (fusion, pipelining and the split solve unchanged; with a grid they leave the step's relative state d_x7 and its
@@ -2600,15 +2600,15 @@ int pg_simulate_safety_dev(pg_handle* h, int32_t steps, double dt, int32_t use_h
     return rollout(h, RolloutArgs{"pg_simulate_safety_dev", steps, dt, human_mode, human_u_dev,
                                   "the safety rollout belongs to the coupled controller (ros_integration.jl:56,114): the lateral formulation has no safety row", false, nullptr, true},
         no_records,
-        [&](int k, int step) {
-            const int B = h->B;
+        [&](const RolloutStep& s) {
+            const int B = h->B, k = s.k;
             const bool lib = h->human.lib.on();                  // (under a human library the kernel is handed this step's human.u as its script: it records and integrates that)
             const int hmode = lib ? 2 : (int)human_mode;
             SafetyIO io{lib ? (const real*)h->human.u : (human_mode == 2 ? hist_at((const real*)human_u_dev, k, B, 2) : nullptr), hist_at((real*)state_hist_dev, k, B, 6), hist_at((real*)control_hist_dev, k, B, 3),
                         hist_at((real*)other_hist_dev, k, B, 4), hist_at((real*)human_hist_dev, k, B, 2), hist_at((real*)V_hist_dev, k, B, 1), hist_at(source_hist_dev, k, B, 1),
                         h->d_vmin, h->d_breach, h->d_breach + h->cfg.batch_capacity};
-            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)h->hji.on, (int)h->sum_fresh, step,
-                              h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
+            launch_plant_step(h, k_advance_safety, k_advance_safety_lib<>, k_advance_safety_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)h->hji.on, (int)h->sum_fresh, s.step,
+                              h->d_state, s.control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, h->sim_idx, io);
             h->sum_fresh = false;
         });
 }
@@ -2678,9 +2678,9 @@ static int node_prepare(pg_handle* h) {
     K.solved = h->d_solved; K.wfail = h->d_wfail; K.status = h->d_status; K.iters = h->d_iters; K.polish = h->d_polish; K.active = h->d_active;
     return PG_OK;
 }
-static int node_gate(pg_handle* h, const uint8_t* pre_flag) {
+static int node_gate(pg_handle* h, const Seen& seen, const uint8_t* pre_flag) {
     const int B = h->B;
-    hipLaunchKernelGGL(k_node_gate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, h->d_state, h->d_t0, h->d_toff, h->d_tend, pre_flag, h->d_node,
+    hipLaunchKernelGGL(k_node_gate, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, seen.state, h->d_t0, h->d_toff, h->d_tend, pre_flag, h->d_node,
                        node_cold(h, h->node_parity ^ 1), h->kv);
     LAUNCH_CHECK(h);
     return PG_OK;
@@ -2696,11 +2696,11 @@ int pg_node_step_dev(pg_handle* h, int32_t use_hji_policy, const uint8_t* pre_fl
     int rc = check_ready(h); if (rc) return rc;
     if (h->dc.formulation != PG_COUPLED && use_hji_policy) { h->err = "pg_node_step_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)"; return PG_ERR_STATE; }
     if (h->actuator.lib.on()) { h->err = std::string("pg_node_step_dev: ") + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
-    if ((rc = node_prepare(h)) || (rc = node_gate(h, pre_flag_dev)) || (rc = step_compute(h))) return rc;
+    if ((rc = node_prepare(h)) || (rc = node_gate(h, seen_own(h), pre_flag_dev)) || (rc = step_compute(h, seen_own(h)))) return rc;
     NodeIO io = node_io(h);
     io.cmd_out = (real*)cmd_out_dev; io.se_out = (real*)se_out_dev; io.event = event_dev;
     const int B = h->B;
-    hipLaunchKernelGGL(k_node_finish<false>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, 0.0, (int)(use_hji_policy != 0), 0, (int)(h->hji.on && h->dc.formulation == PG_COUPLED),
+    hipLaunchKernelGGL(k_node_finish<false>, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->dc, B, 0.0, (int)(use_hji_policy != 0), 0, has_hji_row(h),
                        (int)h->node_fresh, 0, 0, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk, 0, h->kv, io);
     LAUNCH_CHECK(h);
     node_done(h);
@@ -2719,8 +2719,8 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
     return rollout(h, RolloutArgs{"pg_simulate_node_dev", steps, dt, human_mode, human_u_dev,
                                   use_hji_policy ? "pg_simulate_node_dev: the HJI policy belongs to the coupled controller (the lateral formulation has no safety row)" : nullptr, true, pre_flag_dev, true},
         no_records,
-        [&](int k, int step) {
-            const int B = h->B;
+        [&](const RolloutStep& s) {
+            const int B = h->B, k = s.k;
             NodeIO io = node_io(h);
             const bool lib = h->human.lib.on();                  // (as pg_simulate_safety_dev: human.u of this step is the script)
             const int hmode = lib ? 2 : (int)human_mode;
@@ -2728,8 +2728,8 @@ int pg_simulate_node_dev(pg_handle* h, int32_t steps, double dt, int32_t use_hji
             io.state_h = hist_at((real*)state_hist_dev, k, B, 6); io.applied_h = hist_at((real*)applied_hist_dev, k, B, 3); io.V_h = hist_at((real*)V_hist_dev, k, B, 1);
             io.event_h = hist_at(event_hist_dev, k, B, 1);
             io.V_min = h->d_vmin; io.first_breach = h->d_breach; io.policy_steps = h->d_breach + h->cfg.batch_capacity;
-            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, (int)(h->hji.on && h->dc.formulation == PG_COUPLED),
-                              (int)h->node_fresh, (int)h->sum_fresh, step, h->d_state, h->d_control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
+            launch_plant_step(h, k_node_finish<true>, k_node_finish_lib<>, k_node_finish_lib<DistW>, h->dc, B, dt, (int)(use_hji_policy != 0), hmode, has_hji_row(h),
+                              (int)h->node_fresh, (int)h->sum_fresh, s.step, h->d_state, s.control, h->d_other, h->d_u, h->d_x7, h->d_vg8, h->d_toff, h->d_t0, h->d_tstart, h->sim_clk,
                               h->sim_idx, h->kv, io);
             h->sum_fresh = false;
             node_done(h);

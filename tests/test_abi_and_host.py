@@ -273,3 +273,16 @@ def test_device_memory_is_allocated_and_freed_in_one_place():
     assert src.count("hipFree(") == 1
     assert src.count("hipMalloc(") == 1
     assert "free_all(h); delete h" not in src
+
+
+def test_the_handles_input_pointers_are_assigned_once_and_carry_no_parked_arguments():
+    """pg_api.hip assigns h->d_state and h->d_control once each (pg_create): they are the true state and the command, and what a step's controller is handed instead
+    travels as an argument.  Nor does pg_handle hold a call's arguments or return values: no u_direct, u_written or lin_done among its members or behind `h->`."""
+    src = open(os.path.join(ROOT, "pigeon.jl_amd", "csrc", "pg_api.hip")).read()
+    assert len(re.findall(r"h->d_state\s*=(?!=)", src)) == 1
+    assert len(re.findall(r"h->d_control\s*=(?!=)", src)) == 1
+    body = re.search(r"^struct pg_handle \{\n(.*?)^\};", src, re.S | re.M).group(1)
+    assert "d_state" in body and "d_control" in body           # (the right struct)
+    for name in ("u_direct", "u_written", "lin_done"):
+        assert not re.search(rf"\b{name}\b", body), name
+        assert not re.search(rf"(->|\.)\s*{name}\b", src), name
