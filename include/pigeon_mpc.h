@@ -679,6 +679,66 @@ int pg_set_human_history_dev(pg_handle* h, pg_real_dev* buf, int32_t steps);
  * does not cover the batch */
 int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, const double* x7, const double* vg8, const double* script, double* u_out);
 
+/* Route sets: the TRAJECTORY an instance tracks CHANGES DURING a rollout, per instance -- nominal_trajectory_callback of the node (src/ros_integration.jl:30-41: a /des_traj
+ * message brings a new tube and time_offset = its stamp, a /des_path message a new tube and time_offset = NaN, either one sets mpc.solved = false) as a ninth library
+ * beside the other eight axes: per instance a list of up to PG_ROUTE_EVENTS events "at clock step k, go to trajectory j of the installed library, anchored so".
+ * With a library installed pg_simulate_dev, pg_simulate_safety_dev and pg_simulate_node_dev queue one launch (k_route, one wavefront per instance) on the clock steps that
+ * carry an event in some installed set (and on every step of a call with a registered route history), behind the step's k_measure / k_estimate and ahead of the node gate
+ * and the compute calls.  An event of instance b fires when the clock step (the step index of first_breach, first_exit and the sensor draws) equals ev.step; with t0[b] the
+ * instance's clock time at that step it writes
+ *   the trajectory index of b, in place     target_mode PG_ROUTE_ABSOLUTE: target; PG_ROUTE_RELATIVE: (current + target) mod n_traj, target may be negative
+ *   time_offset[b]                          anchor PG_ROUTE_KEEP:    unchanged (the new trajectory shares the old one's time base: another plan set of the same path)
+ *                                                  PG_ROUTE_PATH:    NaN, path-tracking mode (the /des_path callback, :30-35)
+ *                                                  PG_ROUTE_STAMP:   t0[b] - t_join (t_join = 0: the /des_traj callback, :36-41 -- the new trajectory's t = 0 is now)
+ *                                                  PG_ROUTE_PROJECT: t0[b] - (t_proj + t_join), t_proj = the third path coordinate (pg_get_path_coordinates) of the state
+ *                                                                    the step's controller is handed (measured / estimated under those libraries) projected on the TARGET
+ *                                                                    trajectory -- a planner that hands over a trajectory already in progress.  BUILD-DEFINED.  A non-finite
+ *                                                                    pose gives time_offset = NaN; the index still switches
+ *   with cold = 1: solved = false           as the reference's callback; cold = 0 keeps the warm start (BUILD-DEFINED: the previous solution belongs to the old trajectory)
+ *   the route state (pg_get_route_state)    fired += 1, last_step = k, t_at, e_at
+ * time_offset arithmetic is double in both libraries, the projection is the library's element type (the statements of the step's own projection: t_at and e_at of a PROJECT
+ * event equal what pg_get_path_coordinates reports for that state on the target, bit for bit).  On a clock step that carries an event the host takes the launches of a batch
+ * with a cold instance (as after pg_reset with a mask); the nodes kernels read `solved` per instance.
+ * STATE.  The index pg_set_trajectory_index installed is the instance's HOME.  When the rollout clock restarts (new inputs, another dt) the next rollout under a library first
+ * puts every instance back on its home trajectory with fired = 0 (time_offset is whatever the inputs carry); consecutive calls continue.  After a rollout pg_step* and the
+ * phase calls run on the trajectory the instance switched to.  pg_set_trajectory_index installs home and current together; pg_clear_route_sets leaves the current index as
+ * it is.  The other libraries' states (gust, streams, actuator ring, estimate, driver), the clock and the summaries do not restart at a switch; the tracking summary follows
+ * the CURRENT trajectory (its "last s" and the tube test change trajectory with the instance).
+ * IDENTITY: pg_default_route() (no event).  A library whose sets hold no event queues the launches of a handle without one and reproduces it bit for bit (the read-only option
+ * "stat_route_steps" counts the k_route launches).
+ * A rollout under a library wants a trajectory library of at least two trajectories whose index covers the batch, every absolute target < n_traj (checked when the rollout
+ * starts: the trajectory library may be replaced after the route sets are installed), and with several sets pg_set_route_index covering the batch: PG_ERR_STATE otherwise.
+ * Lifetime, index rule and errors as pg_set_plant_sets.  PG_ERR_INVALID (the handle is left unchanged; the message names the set): a used slot (step >= 0) behind an unused
+ * one, steps of the used slots not strictly increasing, target_mode / anchor / cold out of range, t_join not finite or != 0 under KEEP / PATH, an absolute target < 0,
+ * reserved != 0.  pg_abi_layout is unchanged (sizeof(pg_route) = 128 is asserted where the library is compiled). */
+#define PG_ROUTE_EVENTS 4
+enum pg_route_target_mode { PG_ROUTE_ABSOLUTE = 0, PG_ROUTE_RELATIVE = 1 };
+enum pg_route_anchor { PG_ROUTE_KEEP = 0, PG_ROUTE_PATH = 1, PG_ROUTE_STAMP = 2, PG_ROUTE_PROJECT = 3 };
+typedef struct pg_route_event {
+    int32_t step;                  /* clock step at which it fires, ahead of that step's controller; < 0: unused slot */
+    int32_t target;                /* PG_ROUTE_ABSOLUTE: library index; PG_ROUTE_RELATIVE: (current + target) mod n_traj, target may be negative */
+    int32_t target_mode;           /* PG_ROUTE_ABSOLUTE 0 | PG_ROUTE_RELATIVE 1 */
+    int32_t anchor;                /* PG_ROUTE_KEEP 0 | PG_ROUTE_PATH 1 | PG_ROUTE_STAMP 2 | PG_ROUTE_PROJECT 3 */
+    int32_t cold;                  /* 1: solved = false, as the reference's callback (default); 0: keep the warm start */
+    int32_t reserved;              /* 0 */
+    double  t_join;                /* seconds, STAMP / PROJECT only (0 otherwise) */
+} pg_route_event;                  /* 32 bytes */
+typedef struct pg_route { pg_route_event ev[PG_ROUTE_EVENTS]; } pg_route;      /* 128 bytes */
+pg_route pg_default_route(void);                                                 /* no event: the identity set (every slot {-1, 0, 0, PG_ROUTE_STAMP, 1, 0, 0.0}) */
+int pg_set_route_sets(pg_handle* h, int32_t n_sets, const pg_route* sets);
+int pg_set_route_index(pg_handle* h, int32_t B, const int32_t* index);           /* index[b] in [0, n_sets) */
+int pg_clear_route_sets(pg_handle* h);                                           /* the current trajectory index stays as the events left it */
+/* the installed library, as pg_get_plant_sets */
+int pg_get_route_sets(pg_handle* h, int32_t* n_sets, pg_route* out, int32_t max_sets, int32_t* index, int32_t B);
+/* [B] each, any may be NULL: traj = the trajectory the instance is on now; fired = events since the clock last restarted; last_step = clock step of the last one (-1: none);
+ * t_at = where the new trajectory was joined at that event -- PROJECT: t_proj; STAMP: t_join; KEEP: t0 - time_offset; PATH: NaN --; e_at = the lateral offset of that
+ * projection (NaN unless PROJECT).  Before the first rollout step since the clock restarted: fired 0, last_step -1, t_at and e_at NaN, and traj still the trajectory the
+ * instance was left on -- the return home is applied when the next rollout starts, and until then pg_step* and the phase calls run on what traj reports.  PG_ERR_STATE without inputs or without a library */
+int pg_get_route_state(pg_handle* h, int32_t* traj, int32_t* fired, int32_t* last_step, double* t_at, double* e_at);
+/* the NEXT rollout call writes the trajectory the controller of its step k < steps ran on to buf[k][B] (int32, device memory); one-shot -- that call consumes the
+ * registration whether it succeeds or returns an error --; (NULL, 0) cancels, NULL with steps != 0 and steps < 1 are PG_ERR_INVALID.  PG_ERR_STATE without a library */
+int pg_set_route_history_dev(pg_handle* h, int32_t* buf, int32_t steps);
+
 /* mpc.HJI_cache = HJICache(grid_knots, V_raw, gradV_raw)  src/HJI_computation.jl:26-57.  V is column-major (dim 1 fastest),
  * gradV is 7 floats per node in the same node order.  Without a grid the safety row is inactive (M = 0, b = 1).
  * An install first drops the installed grid and then builds the new table (never two tables side by side: the cell records of the real grid take 1.9 to 19 GB).
@@ -911,6 +971,7 @@ int pg_synchronize(pg_handle* h);
  *     "stat_disturbance_steps"   (read-only) rollout steps that ran under a disturbance library (k_disturb launches) since pg_create
  *     "stat_estimator_steps"     (read-only) rollout steps that ran under an estimator library (k_estimate launches) since pg_create
  *     "stat_human_steps"         (read-only) rollout steps that ran under a human library (k_human launches) since pg_create
+ *     "stat_route_steps"         (read-only) k_route launches since pg_create: rollout steps that carried an event of an installed route set or recorded the route
  *     "tracking_summary" 0/1 (0) 1 = every rollout step runs k_track (pg_get_tracking_state); 0 = no such launch.  Switching it off and on again restarts the summary
  *     "time_grid_naive" 0/1 (0)  0 = the time axes as Julia's RANGES give them (src/model_predictive_control.jl:25-26: `t0 .+ dt_short*(0:N_short)`, `t0_long .+ dt_long*(1:N_long)`,
  *                                and :87, `for t in 0:dt:trajectory.t[end]` in pg_simulate_dev): reference value and step in twice the working precision, dt lifted to its exact

@@ -457,6 +457,61 @@ function human_response(mpc::BatchedTrajectoryTrackingMPC, step0::Integer, x7::A
     u
 end
 
+# Route sets (pg_set_route_sets ...): an instance changes trajectory during a rollout (nominal_trajectory_callback).  NOT EXECUTED in the build container, like the rest of this file.
+
+const PG_ROUTE_EVENTS = 4
+const ROUTE_ANCHORS = Dict(:keep => Int32(0), :path => Int32(1), :stamp => Int32(2), :project => Int32(3))
+"One event of a route set (pg_route_event): at clock step `step` (< 0: unused slot), ahead of that step's controller, go to trajectory `target` of the installed library (0-based; relative = true: `target` trajectories on from the current one, modulo the library), anchored :keep (time_offset stays), :path (NaN), :stamp (the new trajectory's t = t_join is now) or :project (the seen state projected on the target, t_join further on); cold = true sets solved = false as the reference's callback does."
+struct PgRouteEvent
+    step::Int32
+    target::Int32
+    target_mode::Int32
+    anchor::Int32
+    cold::Int32
+    reserved::Int32
+    t_join::Float64
+end
+PgRouteEvent(step, target; anchor::Symbol=:stamp, relative::Bool=false, cold::Bool=true, t_join=0.0) =
+    PgRouteEvent(Int32(step), Int32(target), Int32(relative), ROUTE_ANCHORS[anchor], Int32(cold), Int32(0), Float64(t_join))
+"One route set (pg_route): up to four events in the order of their steps; PgRoute() is the identity (no event)."
+struct PgRoute
+    ev::NTuple{4,PgRouteEvent}
+end
+PgRoute(events::PgRouteEvent...) = PgRoute(ntuple(k -> k <= length(events) ? events[k] : PgRouteEvent(-1, 0), PG_ROUTE_EVENTS))
+"the layout include/pigeon_mpc.h states (32 and 128 bytes): checked before the first install"
+function check_route_layout()
+    off(f) = Int(fieldoffset(PgRouteEvent, Base.fieldindex(PgRouteEvent, f)))
+    (sizeof(PgRoute), sizeof(PgRouteEvent), off(:step), off(:target), off(:target_mode), off(:anchor), off(:cold), off(:reserved), off(:t_join)) ==
+        (128, 32, 0, 4, 8, 12, 16, 20, 24) || error("PigeonMI355X.jl: PgRoute differs from pg_route of include/pigeon_mpc.h")
+end
+"the identity set as the library makes it"
+default_route(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_route), PgRoute, ())
+"Which trajectory of the installed library an instance tracks when: a library of route sets and the set each instance runs under (0-based; may be empty for a library of one).  The index set_trajectory_index! installed is every instance's home: a restarted rollout clock starts there again."
+function set_routes!(mpc::BatchedTrajectoryTrackingMPC, sets::Vector{PgRoute}, index::Vector{Int32}=Int32[])
+    check_route_layout()
+    check(mpc, ccall(sym(mpc, :pg_set_route_sets), Cint, (Ptr{Cvoid}, Int32, Ptr{PgRoute}), mpc.handle, length(sets), sets), "pg_set_route_sets")
+    isempty(index) || check(mpc, ccall(sym(mpc, :pg_set_route_index), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}), mpc.handle, length(index), index), "pg_set_route_index")
+    nothing
+end
+clear_routes!(mpc::BatchedTrajectoryTrackingMPC) = check(mpc, ccall(sym(mpc, :pg_clear_route_sets), Cint, (Ptr{Cvoid},), mpc.handle), "pg_clear_route_sets")
+"(sets, index over B instances; -1 where no index covers an instance) as installed"
+function routes(mpc::BatchedTrajectoryTrackingMPC, B::Integer)
+    n = Ref{Int32}(0)
+    check(mpc, ccall(sym(mpc, :pg_get_route_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgRoute}, Int32, Ptr{Int32}, Int32), mpc.handle, n, C_NULL, 0, C_NULL, 0), "pg_get_route_sets")
+    sets = Vector{PgRoute}(undef, n[]); index = fill(Int32(-1), B)
+    check(mpc, ccall(sym(mpc, :pg_get_route_sets), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{PgRoute}, Int32, Ptr{Int32}, Int32), mpc.handle, n, sets, n[], index, B), "pg_get_route_sets")
+    sets, index
+end
+"(traj (0-based), fired, last_step, t_at, e_at), B each: where every instance is now and what its last event did"
+function route_state(mpc::BatchedTrajectoryTrackingMPC)
+    traj = zeros(Int32, mpc.B); fired = zeros(Int32, mpc.B); last_step = zeros(Int32, mpc.B); t_at = zeros(mpc.B); e_at = zeros(mpc.B)
+    check(mpc, ccall(sym(mpc, :pg_get_route_state), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}), mpc.handle, traj, fired, last_step, t_at, e_at), "pg_get_route_state")
+    traj, fired, last_step, t_at, e_at
+end
+"The NEXT rollout call writes the trajectory the controller of its step k < steps ran on to a device array B x steps of Int32 (one-shot; (C_NULL, 0) cancels)"
+set_route_history!(mpc::BatchedTrajectoryTrackingMPC, buf::Ptr{Cvoid}, steps::Integer) =
+    check(mpc, ccall(sym(mpc, :pg_set_route_history_dev), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), mpc.handle, buf, steps), "pg_set_route_history_dev")
+
 "mpc.HJI_cache = HJICache(fname) (src/Pigeon.jl:40): hand over grid_knots, V_raw, ∇V_raw exactly as stored in the JLD2 file"
 function set_hji_cache!(mpc::BatchedTrajectoryTrackingMPC, grid_knots::NTuple{7,Vector{Float32}}, V_raw::Array{Float32,7}, ∇V_raw::Array{Float32})
     dims = Int32[length(k) for k in grid_knots]

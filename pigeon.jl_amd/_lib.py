@@ -41,6 +41,7 @@ SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_defaul
            "pg_set_disturbance_sets", "pg_set_disturbance_index", "pg_set_disturbance_seed", "pg_clear_disturbance_sets", "pg_get_disturbance_sets", "pg_disturbance_response", "pg_get_disturbance_state", "pg_set_disturbance_history_dev",
            "pg_set_estimator_sets", "pg_set_estimator_index", "pg_clear_estimator_sets", "pg_get_estimator_sets", "pg_get_estimated_state", "pg_set_estimated_history_dev", "pg_estimator_response",
            "pg_set_human_sets", "pg_set_human_index", "pg_set_human_seed", "pg_clear_human_sets", "pg_get_human_sets", "pg_get_human_state", "pg_set_human_history_dev", "pg_human_response",
+           "pg_default_route", "pg_set_route_sets", "pg_set_route_index", "pg_clear_route_sets", "pg_get_route_sets", "pg_get_route_state", "pg_set_route_history_dev",
            "pg_set_hji_grid", "pg_clear_hji_grid", "pg_default_hji_solve_opts", "pg_hji_solve", "pg_reset", "pg_set_inputs", "pg_set_inputs_dev", "pg_compute_time_steps",
            "pg_compute_linearization_nodes", "pg_update_qp", "pg_solve", "pg_get_next_control", "pg_get_next_control_dev", "pg_get_next_control_hji", "pg_get_next_control_hji_dev", "pg_step", "pg_step_dev", "pg_simulate_dev", "pg_simulate_clock", "pg_get_state", "pg_simulate_safety_dev", "pg_get_safety_state", "pg_node_step_dev", "pg_simulate_node_dev", "pg_get_node_state",
            "pg_set_stream", "pg_set_fusion", "pg_set_pipeline", "pg_set_option", "pg_get_option", "pg_get_pipeline_fallbacks", "pg_synchronize", "pg_get_time_steps", "pg_get_nodes", "pg_get_path_coordinates", "pg_qp_len", "pg_get_qp", "pg_set_qp", "pg_get_solution",
@@ -145,6 +146,30 @@ HUMAN_SET_PROTOTYPES = {
     "pg_get_human_state": [C.c_void_p, C.POINTER(C.c_double)],
     "pg_set_human_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
     "pg_human_response": [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+}
+
+
+PG_ROUTE_EVENTS = 4
+PG_ROUTE_ABSOLUTE, PG_ROUTE_RELATIVE = 0, 1
+PG_ROUTE_KEEP, PG_ROUTE_PATH, PG_ROUTE_STAMP, PG_ROUTE_PROJECT = 0, 1, 2, 3
+
+
+class pg_route_event(C.Structure):
+    """include/pigeon_mpc.h pg_route_event: the clock step at which it fires (< 0: unused slot), the target and how to read it (0 absolute, 1 relative to the current index),
+    the anchor of the new time offset (0 keep, 1 path, 2 stamp, 3 project), whether the instance starts cold, a reserved 0, the seconds into the new trajectory."""
+    _fields_ = [("step", C.c_int32), ("target", C.c_int32), ("target_mode", C.c_int32), ("anchor", C.c_int32), ("cold", C.c_int32), ("reserved", C.c_int32), ("t_join", C.c_double)]
+
+
+class pg_route(C.Structure):
+    """include/pigeon_mpc.h pg_route: PG_ROUTE_EVENTS events, the used slots first and in the order of their steps."""
+    _fields_ = [("ev", pg_route_event * PG_ROUTE_EVENTS)]
+
+
+# route library (include/pigeon_mpc.h: pg_set_route_sets and its companions)
+ROUTE_SET_PROTOTYPES = {
+    **_set_prototypes("route", pg_route),
+    "pg_get_route_state": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "pg_set_route_history_dev": [C.c_void_p, C.c_void_p, C.c_int32],
 }
 
 
@@ -270,7 +295,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, START_MAKE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, START_MAKE_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -284,6 +309,8 @@ def load_library(precision="f64"):
     lib.pg_default_waypoint.restype = pg_waypoint
     lib.pg_default_start_set.argtypes = []
     lib.pg_default_start_set.restype = pg_start_set
+    lib.pg_default_route.argtypes = []
+    lib.pg_default_route.restype = pg_route
     assert lib.pg_precision_bits() == (32 if precision == "f32" else 64)
     check_layout(lib)
     _libs[precision] = lib

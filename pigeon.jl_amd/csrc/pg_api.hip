@@ -123,6 +123,17 @@ struct pg_handle {
         real *u = nullptr, *n = nullptr; bool script = false, fresh = true, valid = false; int64_t steps_stat = 0;
         void cleared() { script = false; fresh = true; valid = false; hist.clear(); }      // (a library installed later starts a driver of its own)
     } human;
+    // route library (pg_set_route_sets / pg_set_route_index): an instance changes trajectory during a rollout (k_route).  Beside the sets (the device records ARE the
+    // caller's: no real in them): the clock steps that carry an event in some installed set (the host's branch choice and the launches follow them), and, allocated when a
+    // rollout first runs under a library: fired [cap] then last_step [cap], t_at [cap], e_at [cap].  The trajectory index the events write is traj_idx.d; HOME is
+    // traj_idx.host.  fresh: the clock restarted -- the next rollout under a library puts every instance back on its home trajectory with fired = 0 (route_start).
+    // hist: pg_set_route_history_dev, one-shot, int32 [steps][B]
+    struct Route {
+        SetLib<pg_route, pg_route> lib{{"route", "pg_set_route_index"}}; std::vector<int> event_steps;
+        int *fired = nullptr, *hist = nullptr; int hist_steps = 0; double* t_at = nullptr; real* e_at = nullptr; bool fresh = true; int64_t steps_stat = 0;
+        bool event_at(int step) const { for (int s : event_steps) if (s == step) return true; return false; }
+        void cleared() { event_steps.clear(); fresh = true; hist = nullptr; hist_steps = 0; }
+    } route;
     // the inputs: the true state and the command, always -- assigned once, by pg_create.  What a step's controller is handed instead travels as a Seen (below)
     real *d_state = nullptr, *d_control = nullptr, *d_other = nullptr;
     double *d_t0 = nullptr, *d_toff = nullptr;            // absolute time stays fp64 in both builds (tdouble)
@@ -637,6 +648,7 @@ static bool find_option(pg_handle* h, const char* name, OptRef* o) {
     if (n == "stat_disturbance_steps") return S(&h->disturbance.steps_stat);
     if (n == "stat_estimator_steps") return S(&h->estimator.steps_stat);
     if (n == "stat_human_steps") return S(&h->human.steps_stat);
+    if (n == "stat_route_steps") return S(&h->route.steps_stat);
     if (n == "stat_split_solve_launches") return S(&h->stat_split);
     if (n == "stat_single_solve_launches") return S(&h->stat_single);
     if (n == "stat_lat_two_launch_solves") return S(&h->stat_lat_two);
@@ -716,7 +728,7 @@ int pg_get_pipeline_fallbacks(pg_handle* h, int64_t* count) {
 }
 int pg_synchronize(pg_handle* h) { if (!h) return PG_ERR_INVALID; HIPCHK(h, hipStreamSynchronize(h->stream)); return PG_OK; }
 
-// ---- what the eight libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances, estimators, humans): one index rule and one install / clear / get protocol ----
+// ---- what the nine libraries share (trajectories, control parameters, plants, sensors, actuators, disturbances, estimators, humans, routes): one index rule and one install / clear / get protocol ----
 // Installs the selection of `B` instances into a library of `n_sets`.  The WHOLE [capacity] array is written, entries beyond B as 0: never an address outside the library,
 // whatever an earlier, larger library left there
 static int index_install(pg_handle* h, int n_sets, IndexArray& arr, int32_t B, const int32_t* index) {
@@ -811,7 +823,7 @@ static int seed_install(pg_handle* h, const char* who, SeedStreams& S, uint64_t 
 // state, and the actuator's getter falls back to the command
 static void restart_on_clock(pg_handle* h) {
     h->sum_fresh = true; h->node_fresh = true; h->track_fresh = true;
-    h->actuator.fresh = true; h->disturbance.fresh = true; h->estimator.fresh = true; h->human.fresh = true;
+    h->actuator.fresh = true; h->disturbance.fresh = true; h->estimator.fresh = true; h->human.fresh = true; h->route.fresh = true;
 }
 static void restart_on_inputs(pg_handle* h) {
     restart_on_clock(h);
@@ -1638,6 +1650,86 @@ int pg_human_response(pg_handle* h, int32_t step0, int32_t steps, double dt, con
     });
 }
 
+// ---- route library: the trajectory an instance tracks changes DURING a rollout (nominal_trajectory_callback, ros_integration.jl:30-41; k_route).  The events write the
+// device trajectory index in place; what pg_set_trajectory_index installed (IndexArray::host) is the instance's home ----
+static_assert(sizeof(pg_route_event) == 32 && sizeof(pg_route) == 128 && offsetof(pg_route_event, t_join) == 24, "the sizes include/pigeon_mpc.h states");
+pg_route pg_default_route(void) {
+    pg_route r; memset(&r, 0, sizeof(r));
+    for (pg_route_event& e : r.ev) { e.step = -1; e.anchor = PG_ROUTE_STAMP; e.cold = 1; }
+    return r;
+}
+static const char* route_set_problem(const pg_route& r) {
+    bool unused_seen = false; int last = -1;
+    for (const pg_route_event& e : r.ev) {
+        if (e.target_mode != PG_ROUTE_ABSOLUTE && e.target_mode != PG_ROUTE_RELATIVE) return "target_mode must be 0 (absolute) or 1 (relative)";
+        if (e.anchor < PG_ROUTE_KEEP || e.anchor > PG_ROUTE_PROJECT) return "anchor must be 0 (keep), 1 (path), 2 (stamp) or 3 (project)";
+        if (e.cold != 0 && e.cold != 1) return "cold must be 0 or 1";
+        if (e.reserved != 0) return "reserved must be 0";
+        if (!std::isfinite(e.t_join)) return "t_join must be finite";
+        if ((e.anchor == PG_ROUTE_KEEP || e.anchor == PG_ROUTE_PATH) && e.t_join != 0.0) return "t_join must be 0 under the anchors keep and path";
+        if (e.step < 0) { unused_seen = true; continue; }
+        if (unused_seen) return "a used slot (step >= 0) stands behind an unused one";
+        if (e.step <= last) return "the steps of the used slots must be strictly increasing";
+        last = e.step;
+        if (e.target_mode == PG_ROUTE_ABSOLUTE && e.target < 0) return "an absolute target must be >= 0";
+    }
+    return nullptr;
+}
+int pg_set_route_sets(pg_handle* h, int32_t n_sets, const pg_route* sets) {
+    if (!h) return PG_ERR_INVALID;
+    std::string why;                                            // (the message names the set; the route state persists: it restarts with the clock)
+    const int rc = setlib_install(h, "pg_set_route_sets", h->route.lib, n_sets, sets, numbered_problem(route_set_problem, sets, why), [](pg_route& d, const pg_route& s) { d = s; });
+    if (rc) return rc;
+    auto& steps = h->route.event_steps; steps.clear();
+    for (const pg_route& r : h->route.lib.sets) for (const pg_route_event& e : r.ev) if (e.step >= 0 && !h->route.event_at(e.step)) steps.push_back(e.step);
+    return PG_OK;
+}
+int pg_set_route_index(pg_handle* h, int32_t B, const int32_t* index) {
+    if (!h) return PG_ERR_INVALID;
+    return index_install(h, (int)h->route.lib.sets.size(), h->route.lib.idx, B, index);
+}
+int pg_clear_route_sets(pg_handle* h) {
+    if (!h) return PG_ERR_INVALID;
+    const int rc = setlib_clear(h, h->route.lib); if (rc) return rc;
+    h->route.cleared();
+    return PG_OK;
+}
+int pg_get_route_sets(pg_handle* h, int32_t* n_sets, pg_route* out, int32_t max_sets, int32_t* index, int32_t B) {
+    if (!h) return PG_ERR_INVALID;
+    return setlib_get(h, "pg_get_route_sets", h->route.lib, n_sets, out, max_sets, index, B);
+}
+int pg_set_route_history_dev(pg_handle* h, int32_t* buf, int32_t steps) {
+    if (!h) return PG_ERR_INVALID;
+    auto& U = h->route;
+    if (!buf && steps == 0) { U.hist = nullptr; U.hist_steps = 0; return PG_OK; }
+    REQUIRE(h, buf, "pg_set_route_history_dev: a device buffer [steps][B] of int32 is required ((NULL, 0) drops the registration)");
+    REQUIRE(h, steps >= 1, "pg_set_route_history_dev: steps >= 1 required");
+    if (!U.lib.on()) { h->err = "pg_set_route_history_dev: no route library installed (every instance stays on the trajectory pg_set_trajectory_index gave it)"; return PG_ERR_STATE; }
+    U.hist = buf; U.hist_steps = steps;
+    return PG_OK;
+}
+int pg_get_route_state(pg_handle* h, int32_t* traj, int32_t* fired, int32_t* last_step, double* t_at, double* e_at) {
+    int rc = check_ready(h); if (rc) return rc;
+    auto& U = h->route;
+    if (!U.lib.on()) { h->err = "pg_get_route_state: no route library installed"; return PG_ERR_STATE; }
+    const size_t B = (size_t)h->B, cap = cap_of(h);
+    if (U.fresh || !U.fired) {                                  // no rollout step under the library since the clock (re)started: nothing fired.  The return home is
+        // applied when the next rollout starts (route_start): until then pg_step* and the phase calls run on what the device index holds, and that is what is reported
+        if (h->dc.n_traj > 1 && h->traj_idx.d) { if ((rc = down_raw(h, traj, h->traj_idx.d, B * sizeof(int32_t)))) return rc; }
+        else if (traj) memset(traj, 0, B * sizeof(int32_t));
+        for (size_t b = 0; b < B; b++) {
+            if (fired) fired[b] = 0;
+            if (last_step) last_step[b] = -1;
+            if (t_at) t_at[b] = NAN;
+            if (e_at) e_at[b] = NAN;
+        }
+        return PG_OK;
+    }
+    if ((rc = down_raw(h, traj, h->traj_idx.d, B * sizeof(int32_t))) || (rc = down_raw(h, fired, U.fired, B * sizeof(int32_t))) ||
+        (rc = down_raw(h, last_step, U.fired + cap, B * sizeof(int32_t))) || (rc = down_raw(h, t_at, U.t_at, B * sizeof(double))) || (rc = down(h, e_at, U.e_at, B))) return rc;
+    return PG_OK;
+}
+
 // ---- the handle's HJI table (pg_handle::hji, dc.has_hji): these two routines are the only code that writes it.  An install is "clear, then build": the old table is gone
 // before the new one is allocated (never two tables side by side: the cell records are 1.9 to 19 GB for the real grid), so AFTER A FAILED INSTALL the handle has no HJI
 // grid, no device memory of the call remains (the call's CallBufs held all of it), and pg_last_error says why ----
@@ -2436,12 +2528,26 @@ static int rollout_ready(pg_handle* h, bool human_lib) {
         }
         if ((rc = D.streams.sync(h))) return rc;
     }
+    if (h->route.lib.on()) {
+        auto& U = h->route;
+        if (h->dc.n_traj < 2) { h->err = "a route library is installed but the handle has no trajectory library of at least two trajectories (pg_set_trajectories)"; return PG_ERR_STATE; }
+        if (h->traj_idx.covered() < h->B || !h->traj_idx.d) { h->err = "a route library is installed but pg_set_trajectory_index does not cover the batch (it is every instance's home)"; return PG_ERR_STATE; }
+        for (const pg_route& r : U.lib.sets) for (const pg_route_event& e : r.ev)      // (here, not at the install: the trajectory library may have been replaced since)
+            if (e.step >= 0 && e.target_mode == PG_ROUTE_ABSOLUTE && e.target >= h->dc.n_traj) {
+                h->err = "a route set has an absolute target " + std::to_string(e.target) + " outside the installed trajectory library of " + std::to_string(h->dc.n_traj); return PG_ERR_STATE;
+            }
+        if (index_covers(h, U.lib)) return PG_ERR_STATE;
+        if ((rc = ensure(h, U.fired, cap * 2)) || (rc = ensure(h, U.t_at, cap)) || (rc = ensure(h, U.e_at, cap))) return rc;
+    }
     return PG_OK;
 }
 // The one-shot history registrations a rollout call consumes (pg_set_*_history_dev), taken from the handle when the call starts
-struct RolloutHist { HistSlot measured, applied, command, disturbance, estimated, human; };
+struct RolloutHist { HistSlot measured, applied, command, disturbance, estimated, human; int* route = nullptr; int route_steps = 0; };
 static RolloutHist take_histories(pg_handle* h) {
-    return RolloutHist{h->sensor.hist.take(), h->actuator.applied_hist.take(), h->actuator.command_hist.take(), h->disturbance.hist.take(), h->estimator.hist.take(), h->human.hist.take()};
+    RolloutHist r{h->sensor.hist.take(), h->actuator.applied_hist.take(), h->actuator.command_hist.take(), h->disturbance.hist.take(), h->estimator.hist.take(), h->human.hist.take(),
+                  h->route.hist, h->route.hist_steps};
+    h->route.hist = nullptr; h->route.hist_steps = 0;
+    return r;
 }
 // the disturbance library (installed: k_disturb joins a rollout step, and the step's last launch is the <DistW> instantiation of the library kernel).
 // The top of a rollout step under a library: w of clock step `step` into disturbance.w, the gust state advanced (fresh: the host knows that no state of step - 1 exists)
@@ -2480,7 +2586,39 @@ static int launch_actuate(pg_handle* h, int step, int k, double dt, const HistSl
 // library) and the view names estimator.x -- the gates, the projection, the nodes, the QP's q_curr, the HJI relative state and the policy selection all follow it; without
 // either, the true state.  Control: `control`, as the rollout hands it in (the command, or actuator.seen).  The summary, the records and the plant never see the view
 static int node_gate(pg_handle* h, const Seen& seen, const uint8_t* pre_flag);
-static int rollout_compute(pg_handle* h, const real* control, int step, int k, double dt, const HistSlot& measured, const HistSlot& estimated, bool gate, const uint8_t* pre_flag) {
+// the route library (installed: k_route joins the rollout steps whose clock step carries an event in some installed set, and every step of a call that records the route).
+// Behind k_measure / k_estimate -- a PROJECT event projects the state the controller is handed -- and ahead of the gate and the compute calls, which then read the new
+// index, the new offset and the cleared solved flag.  On an event step the host takes the launches of a batch with a cold instance, exactly as control_sets_changed does
+// (k_nodes / k_nodes_linearize read solved[b] per instance); mark_solved makes the batch warm again behind the step's solve
+static int launch_route(pg_handle* h, const Seen& seen, int step, int* hist) {
+    auto& U = h->route;
+    const bool event = U.event_at(step);
+    if (!event && !hist) return PG_OK;
+    const int B = h->B;
+    const RouteLib lib{U.lib.d, U.lib.index(), h->traj_idx.d, U.fired, U.fired + cap_of(h), U.t_at, U.e_at};
+    hipLaunchKernelGGL(k_route, dim3((B * 64 + 255) / 256), dim3(256), 0, h->stream, h->dc, B, step, lib, seen.state, (const double*)h->d_t0, h->d_toff, h->d_solved, h->d_wfail, hist);
+    LAUNCH_CHECK(h);
+    U.steps_stat++;
+    if (event) { h->warm_B = 0; h->order_B = 0; }
+    return PG_OK;
+}
+// The clock restarted (route.fresh): every instance back on its home trajectory, nothing fired.  Once per restart, at the start of a rollout call: the copy waits for the stream
+static int route_start(pg_handle* h) {
+    auto& U = h->route;
+    if (!U.lib.on() || !U.fresh) return PG_OK;
+    const size_t cap = cap_of(h);
+    std::vector<int> home(cap, 0), last(cap, -1);
+    for (size_t b = 0; b < h->traj_idx.host.size(); b++) home[b] = h->traj_idx.host[b];
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(h->traj_idx.d, home.data(), cap * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(U.fired, 0, cap * sizeof(int)));
+    HIPCHK(h, hipMemcpy(U.fired + cap, last.data(), cap * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemset(U.t_at, 0xFF, cap * sizeof(double)));      // (all-ones: a NaN in either element type)
+    HIPCHK(h, hipMemset(U.e_at, 0xFF, cap * sizeof(real)));
+    U.fresh = false;
+    return PG_OK;
+}
+static int rollout_compute(pg_handle* h, const real* control, int step, int k, double dt, const HistSlot& measured, const HistSlot& estimated, int* route_hist, bool gate, const uint8_t* pre_flag) {
     int rc;
     auto& S = h->sensor; auto& E = h->estimator;
     const int B = h->B;
@@ -2499,6 +2637,7 @@ static int rollout_compute(pg_handle* h, const real* control, int step, int k, d
         E.fresh = false; E.valid = true; E.steps_stat++;
         seen.state = E.x;
     }
+    if (h->route.lib.on() && (rc = launch_route(h, seen, step, route_hist))) return rc;
     if (gate && (rc = node_gate(h, seen, pre_flag))) return rc;
     return step_compute(h, seen);
 }
@@ -2539,9 +2678,9 @@ static void launch_plant_step(pg_handle* h, K uniform, KP with_plant, KD with_di
     else if (h->plants.on()) hipLaunchKernelGGL(with_plant, grid, block, 0, h->stream, args..., plant_lib(h));
     else hipLaunchKernelGGL(uniform, grid, block, 0, h->stream, args...);
 }
-// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated, human) are taken (THIS call consumes them, also when it fails below), check_ready,
+// The rollouts' shared driver.  Prologue, in this order: the one-shot history registrations (measured, applied / command, disturbance, estimated, human, route) are taken (THIS call consumes them, also when it fails below), check_ready,
 // the entry point's own precondition (coupled_only: the message for a lateral handle, nullptr: none), the shared arguments, rollout_ready, the node's buffers (node: the
-// rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87).  Per step: records ahead of the compute calls, the
+// rollout of the node callback, its steps run behind the gate with pre_flag [steps][B]), the loop's clock (:87), the route library's return home when that clock restarted.  Per step: records ahead of the compute calls, the
 // controller's side (:90-93, rollout_compute), the tracking summary, the clock index, then finish: the step's last launch, which moves the plant
 static const char* const ACTUATOR_NODE_REFUSAL = "an actuator library is installed and the node callback is outside its scope (k_node_finish keeps message and applied command "
                                                  "apart and leaves `applied` unwritten for a gated-out instance: no plain hand-back of the next command); pg_clear_actuator_sets first";
@@ -2555,7 +2694,7 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
     if (a.coupled_only && h->dc.formulation != PG_COUPLED) { h->err = a.coupled_only; return PG_ERR_STATE; }
     if (a.node && h->actuator.lib.on()) { h->err = std::string(a.who) + ": " + ACTUATOR_NODE_REFUSAL; return PG_ERR_STATE; }
     const bool human = a.other_car && h->human.lib.on();         // (pg_simulate_dev has no other car: it never reads the human library)
-    if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u, human)) || (rc = rollout_ready(h, human)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt))) return rc;
+    if ((rc = check_rollout_args(h, a.who, a.steps, a.dt, a.human_mode, a.human_u, human)) || (rc = rollout_ready(h, human)) || (a.node && (rc = node_start(h, a.dt))) || (rc = clock_start(h, a.dt)) || (rc = route_start(h))) return rc;
     // Who reads which control.  The records and the plant launch: actuator.plant_u (= a_k) under an actuator library, else the command.  The compute calls -- k_nodes*, the
     // QP's u_curr, the steering-rate rows, k_estimate --: actuator.seen when some set has feedback == 1, else the command.  k_actuate: the command (the handle's own buffer).
     // The plant kernel leaves the next command in plant_u: one copy moves it to the control buffer
@@ -2568,7 +2707,7 @@ static int rollout(pg_handle* h, const RolloutArgs& a, Records records, Finish f
         const RolloutStep s{k, h->sim_idx - 1, plant_u};
         if (act && (rc = launch_actuate(h, s.step, k, a.dt, hist.applied, hist.command))) return rc;
         if (dist && (rc = launch_disturb(h, s.step, k, a.dt, hist.disturbance))) return rc;      // (w of this step: read by the step's last launch only)
-        if ((rc = records(s)) || (rc = rollout_compute(h, seen_u, s.step, k, a.dt, hist.measured, hist.estimated, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr)) ||
+        if ((rc = records(s)) || (rc = rollout_compute(h, seen_u, s.step, k, a.dt, hist.measured, hist.estimated, k < hist.route_steps ? hist_at(hist.route, k, h->B, 1) : (int*)nullptr, a.node, a.pre_flag ? a.pre_flag + (size_t)k * h->B : nullptr)) ||
             (rc = launch_track(h, s.step)) || (human && (rc = launch_human(h, s.step, k, a.dt, a.human_u, hist.human)))) return rc;
         h->sim_idx++;                                                     // (t0 now holds element sim_idx of the clock)
         finish(s);

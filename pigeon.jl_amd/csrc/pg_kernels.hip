@@ -3410,5 +3410,6 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
 #include "pg_path_make.hip"         // pg_make_paths: a path library from line, arc and clothoid segments (workgroup = path)
 #include "pg_path_fit.hip"          // pg_fit_paths: a path library fitted to waypoints, cubic splines resampled in arc length (workgroup = path)
 #include "pg_start_make.hip"        // pg_make_starts: the inputs of a batch placed on the installed trajectory library under a library of start sets (lane = instance)
+#include "pg_route.hip"             // route sets: an instance changes trajectory during a rollout (k_route: wave = instance)
 
 }  // namespace pg

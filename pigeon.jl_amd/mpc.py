@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -805,6 +805,52 @@ class BatchedTrajectoryTrackingMPC:
     def human_state(self):
         """[B][2]: (omega, a) of the last rollout step under a human library (pg_get_human_state)."""
         return self._state("human", 2)
+
+    # ---- the ROUTE of the rollouts, per instance (a trajectory change during the run: nominal_trajectory_callback): a library of pg_route and a per-instance selection ----
+    @classmethod
+    def pack_routes(cls, sets):
+        """route sets (vehicles.route(*events): a list of up to four event dicts; a shorter list is filled with unused slots) or pg_route structures -> a ctypes array of pg_route."""
+        def fill(rec, events):
+            events = list(events)
+            if len(events) > _lib.PG_ROUTE_EVENTS:
+                raise ValueError(f"a route set holds at most {_lib.PG_ROUTE_EVENTS} events, not {len(events)}")
+            for k, e in enumerate(events + _route()[len(events):]):
+                for name, _ in _lib.pg_route_event._fields_:
+                    setattr(rec.ev[k], name, float(e[name]) if name == "t_join" else int(e[name]))
+        return cls._pack(_lib.pg_route, sets, fill)
+
+    def set_routes(self, sets, index=None):
+        """Which trajectory of the installed library an instance tracks WHEN during simulate_ / simulate_safety_ / simulate_node_ (pg_set_route_sets): per instance up to four
+        events "at clock step k go to trajectory j, anchored so" (vehicles.route, vehicles.route_event).  One set (a list of events / structure) for the whole batch, or a
+        list of sets selected per instance with `index`.  The index set_trajectory_index installed is every instance's home: a restarted clock starts there again."""
+        if isinstance(sets, _lib.pg_route) or (isinstance(sets, (list, tuple)) and (not sets or isinstance(sets[0], dict))):
+            sets = [sets]                                        # (one set: a list of event dicts, possibly empty)
+        self._set_sets("route", _lib.pg_route, self.pack_routes, list(sets), index)
+
+    def set_route_index(self, index):
+        self._set_index("route", index)
+
+    def clear_routes(self):
+        self._clear("route")
+
+    def routes(self):
+        """(list of sets, each a list of four event dicts; index array over the current batch, -1 where no index covers an instance) as installed; ([], ...) without a library."""
+        return self._get_sets("route", _lib.pg_route, lambda r: [{name: getattr(e, name) for name, _ in e._fields_} for e in r.ev])
+
+    def route_state(self):
+        """dict of [B] arrays (pg_get_route_state): traj (the trajectory each instance is on now), fired (events since the clock last restarted), last_step (clock step of
+        the last one, -1: none), t_at (where the new trajectory was joined) and e_at (lateral offset of a "project" event's projection, NaN otherwise)."""
+        i32 = lambda: np.zeros(self.B, dtype=np.int32)
+        tr, fi, ls, ta, ea = i32(), i32(), i32(), np.zeros(self.B), np.zeros(self.B)
+        self._chk(self.lib.pg_get_route_state(self.h, _p(tr, c_i32p), _p(fi, c_i32p), _p(ls, c_i32p), _p(ta), _p(ea)), "pg_get_route_state")
+        return dict(traj=tr, fired=fi, last_step=ls, t_at=ta, e_at=ea)
+
+    def record_route(self, steps):
+        """Registers an int32 device tensor [steps][B] with the NEXT rollout call and returns it: the trajectory each step's controller ran on (pg_set_route_history_dev)."""
+        torch, _, dev = self._torch()
+        buf = torch.empty(int(steps), self.B, dtype=torch.int32, device=dev)
+        self._chk(self.lib.pg_set_route_history_dev(self.h, C.c_void_p(buf.data_ptr()), int(steps)), "pg_set_route_history_dev")
+        return buf
 
     def _torch(self):
         """(torch, the library's own element type: what device arrays handed to the *_dev entry points hold, the handle's device)"""

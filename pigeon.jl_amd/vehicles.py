@@ -150,6 +150,33 @@ def human(**overrides):
     return h
 
 
+ROUTE_EVENTS = 4
+ROUTE_EVENT_FIELDS = ("step", "target", "target_mode", "anchor", "cold", "reserved", "t_join")
+ROUTE_ANCHORS = {"keep": 0, "path": 1, "stamp": 2, "project": 3}
+
+
+def route_event(step, target, anchor="stamp", relative=False, cold=True, t_join=0.0):
+    """One event of a route set (pg_route_event): at clock step `step`, ahead of that step's controller, the instance goes to trajectory `target` of the installed library
+    (relative=True: `target` trajectories on from the one it is on, modulo the library, negative allowed).  anchor: "keep" (the time offset stays), "path" (NaN: path
+    tracking, the /des_path callback), "stamp" (the new trajectory's t = t_join is now; t_join = 0: the /des_traj callback), "project" (the state the controller sees is
+    projected on the target and joins it t_join seconds further on; build-defined).  cold=True sets solved = false as the reference's callback does."""
+    if isinstance(anchor, str):
+        if anchor not in ROUTE_ANCHORS:
+            raise KeyError(f"{anchor} is not an anchor: {tuple(ROUTE_ANCHORS)}")
+        anchor = ROUTE_ANCHORS[anchor]
+    for name, v in (("step", step), ("target", target), ("anchor", anchor)):
+        if int(v) != v:
+            raise ValueError(f"{name} = {v} is not a whole number")
+    return dict(step=int(step), target=int(target), target_mode=int(bool(relative)), anchor=int(anchor), cold=int(bool(cold)), reserved=0, t_join=float(t_join))
+
+
+def route(*events):
+    """One route set for set_routes (pg_route): up to four route_event(...) in the order of their steps; route() is the identity (no event: pg_default_route)."""
+    if len(events) > ROUTE_EVENTS:
+        raise ValueError(f"a route set holds at most {ROUTE_EVENTS} events, not {len(events)}")
+    return [dict(e) for e in events] + [route_event(-1, 0) for _ in range(ROUTE_EVENTS - len(events))]
+
+
 SPEED_PLAN_FIELDS = ("mu_scale", "V_max", "V_floor", "V_start", "V_end", "ax_max", "ax_min", "ay_max")
 
 
