@@ -339,6 +339,70 @@ pg_waypoint pg_default_waypoint(void);
 int pg_fit_paths(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints, int32_t Lmax,
                  int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_fit_stats* stats);
 
+/* Offsetting the path: every (path, offset set) pair of a path library and a library of offset sets as a trajectory, computed on the device in the layout
+ * pg_set_trajectories takes -- the same road d metres to the left (a lane), a lane change between two arc lengths, a pass-by that goes round something and comes back.
+ * The reference reads its paths from files (src/ros_integration.jl:13-16) or makes straight lines (src/trajectories.jl:46-58), so the scheme is build-defined
+ * (tests/path_offset_numpy.py is its numpy twin).  It is knot-wise: output knot i belongs to source knot i, nothing is resampled.  channels_in is read as the doubles
+ * given, ALL arithmetic is double in both libraries, every operation rounded on its own (no contraction), and the result is rounded to the library's element type once,
+ * on store: the fp32 library's output is exactly the fp64 library's rounded to float, and the stats are the same doubles.  Below, a parenthesis is one rounded operation
+ * and a sum or product without one is taken from the left.
+ *   Window    win(u; a, b) = (f, f', f'') of sigma(tau) = tau^3 (10 - 15 tau + 6 tau^2) and its derivatives in u (C2: the curvature stays continuous across a window's
+ *             ends):  a = +Inf: (0, 0, 0).  Else w = b - a, tau = (u - a) / w;  unless tau > 0: (0, 0, 0);  where tau >= 1: (1, 0, 0);  else with z = tau (1 - tau):
+ *             f = ((tau tau) tau) (10 + (tau ((6 tau) - 15))),  f' = (30 (z z)) / w,  f'' = ((60 z) (1 - (2 tau))) / (w w).
+ *   Offset    With u = s - s_first of the SOURCE, rise = win(u; s_a, s_b), fall = win(u; s_c, s_d) and dd = d1 - d0:
+ *             d = d0 + (dd (rise - fall)),  d' = dd (rise' - fall'),  d'' = dd (rise'' - fall'').
+ *   Arclength Interval i = [s_i, s_{i+1}]: diff = s_{i+1} - s_i, half = 0.5 diff, mid = 0.5 (s_i + s_{i+1}); the four Gauss-Legendre nodes u_k = mid + (half x_k) and
+ *             weights of pg_make_paths in ascending order.  At a node kappa = kappa_i + (((kappa_{i+1} - kappa_i) (u_k - s_i)) / diff) -- linear inside the interval, the
+ *             controller's own lookup --, d and d' are those of Offset at u_k - s_first, x = 1 - (kappa d), g = sqrt((x x) + (d' d'));
+ *             extra_i = half sum_k (w_k (g - 1)), the sum from 0 in the order of the nodes.  The g - 1 form is deliberate: the four weights sum to 1.9999999999999996, and
+ *             with it the identity set returns s' = s bit for bit.  X_0 = 0 and X_{i+1} = P_{i / c} + r_{i+1} in the blocked prefix order of pg_make_paths (Prefix) over
+ *             the extra_i, with c = ceil((L - 1) / 256): the order depends on the path's own knot count alone.  s'_i = s_i + X_i.
+ *   Frame     That of pg_make_starts: psi is measured from North, the left normal is (-cos psi, -sin psi), a left turn has kappa > 0.  At knot i, with d, d', d'' at
+ *             u = s_i - s_first:  x = 1 - (kappa_i d), y = d', g2 = (x x) + (y y), g = sqrt(g2);  E' = E_i - (d cos psi_i), N' = N_i - (d sin psi_i);
+ *             psi' = psi_i + atan2(y, x);  kappa' = (kappa_i + (((x d'') + (y ((ks d) + (kappa_i d')))) / g2)) / g.
+ *             ks is the source's d kappa / ds at the knot: (kappa_{i+1} - kappa_{i-1}) / (s_{i+1} - s_{i-1}) inside; at the ends of an open path the same with the
+ *             missing neighbour replaced by the knot itself (one-sided); at knot 0 and knot L-1 of a closed path (the same point)
+ *             (kappa_1 - kappa_{L-2}) / ((s_1 - s_0) + (s_{L-1} - s_{L-2})).
+ *   Speed     The Result rule of pg_plan_speeds on the new s:  V' = V;  ds'_i = s'_{i+1} - s'_i;  A'_i = ((V_{i+1} V_{i+1}) - (V_i V_i)) / (2 ds'_i), A'_{L-1} = 0 on an
+ *             open path and A'_0 on a closed one;  dt_i = (2 ds'_i) / (V_i + V_{i+1});  t'_0 = t_0 and t'_{i+1} = t_0 + (P_{i / c} + r_{i+1}), the same blocked prefix over
+ *             the dt_i.  A friction-limited profile for the new curvature -- the inner lane of a bend needs a slower one -- is pg_plan_speeds' job: hand it channels_out
+ *             and closed_out.
+ *   Edges     edge_mode 0, the same road: edge' = edge - d for both edges;  edge_mode 1, the tube travels with the path: the edges are copied.
+ *   Stats     length = s'_{L-1} - s'_0;  ds_min, ds_max over the ds'_i;  kappa_abs_max over |kappa'|;  x_min over the x of the knots;  d_abs_max over |d| of the knots;
+ *             closure_pos = sqrt((dE dE) + (dN dN)) between the last and the first output knot;  n_outside counts the knots where edge_R' < 0 < edge_L' does not hold
+ *             (reported, not refused).
+ * t, s, V, A, kappa, both edges and every stat but closure_pos reproduce the twin bit for bit (they carry no libm call but sqrt); psi is within 8 * 2^-52 * max(pi, |psi|)
+ * of it (atan2), E and N within 8 * 2^-52 * (|d| + |E or N|) (sin, cos and the last rounding). */
+typedef struct pg_offset_set {
+    double d0, d1;            /* lateral offset in metres, left positive: d0 outside the windows, d1 on the plateau; finite */
+    double s_a, s_b;          /* rise d0 -> d1 over [s_a, s_b], metres of the SOURCE arclength from its first knot; s_a = +Inf: no rise (d = d0 throughout) */
+    double s_c, s_d;          /* fall d1 -> d0 over [s_c, s_d]; s_c = +Inf: no fall (a single lane change) */
+    double x_min;             /* refuse a pair where 1 - kappa_i d_i < x_min at a valid knot (the offset reaches the centre of curvature); in (0, 1], default 0.1 */
+    int32_t edge_mode;        /* 0: the same road (edge' = edge - d); 1: the tube travels with the path (edges copied) */
+    int32_t reserved;         /* 0 */
+} pg_offset_set;              /* 64 bytes */
+typedef struct pg_offset_stats {   /* one per output trajectory; computed in double in both libraries */
+    double length, ds_min, ds_max, kappa_abs_max, x_min, d_abs_max, closure_pos;
+    int32_t n_outside, reserved;
+} pg_offset_stats;            /* 64 bytes */
+/* { 0, 0, +Inf, +Inf, +Inf, +Inf, 0.1, 0, 0 }: the identity */
+pg_offset_set pg_default_offset_set(void);
+/* channels_in [n_path][10][Lmax], L and closed are what pg_plan_speeds takes (closed NULL: every path is open); here V and t_0 of the valid knots are read as well.
+ * Output trajectory k = path * n_sets + set, as in pg_plan_speeds: channels_out [n_path * n_sets][10][Lmax], stats [n_path * n_sets], L_out [n_path * n_sets] (=
+ * L[path]) and closed_out [n_path * n_sets] (= closed[path]; 0 where closed is NULL); each may be NULL.  Every channel is 0 at and past L.  install != 0 hands the device buffer to the
+ * handle, with no host round trip: the handle is then exactly as after pg_set_trajectories(h, n_path * n_sets, Lmax, L_out, channels_out).  Synchronous.  A handle that
+ * never calls this launches what it launched before.
+ * PG_ERR_INVALID, everything the host can decide validated before the first allocation (the handle and its installed library are left unchanged): a null L, channels_in or
+ * sets; n_path or n_sets < 1; Lmax < 2; L[k] outside [2, Lmax]; a closed path of fewer than 3 knots; s that does not increase strictly over the valid knots (in the
+ * library's element type); a non-finite geometry value, a V that is not finite and > 0 or a non-finite t_0 in a valid knot; a non-finite d0 or d1; s_a or s_c that is
+ * neither finite nor +Inf; a window with a start whose end is not finite and beyond it (s_b <= s_a, s_d <= s_c, NaN); s_c < s_b when both windows exist; a fall without a
+ * rise; x_min outside (0, 1]; edge_mode outside {0, 1}; reserved != 0; a (path, set) pair with 1 - kappa_i d_i < x_min at a valid knot (the message names path, set
+ * and knot); a closed path whose first or last knot lies inside a window, or whose two ends lie on different plateaus (such an offset curve does not close);
+ * n_path * n_sets * 10 * Lmax elements beyond the allocation arithmetic.  After the launch and before any install: a pair whose s' does not increase strictly in the
+ * library's element type.  Windows that lie beyond a path's end are not an error: that path keeps d0. */
+int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
+                    int32_t n_sets, const pg_offset_set* sets, int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_offset_stats* stats);
+
 /* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
  * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car
  * (src/ros_integration.jl:48-99), so the feature is build-defined (tests/start_make_numpy.py is its numpy twin).  After pg_make_paths / pg_fit_paths / pg_plan_speeds

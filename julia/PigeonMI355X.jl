@@ -689,6 +689,49 @@ end
 "{ 0, 0, 4, -4 } as the library states them (pg_default_waypoint)"
 default_waypoint(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_waypoint), PgWaypoint, ())
 
+# Offsetting the path (pg_offset_paths): lanes, lane changes and pass-bys of a path library on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_offset_set (64 bytes): the offset outside the windows and on the plateau, the rise [s_a, s_b] and the fall [s_c, s_d] in the source's arc length (a start of Inf: none), x_min, edge_mode (0 the same road, 1 the tube travels with the path), a reserved 0"
+struct PgOffsetSet
+    d0::Float64
+    d1::Float64
+    s_a::Float64
+    s_b::Float64
+    s_c::Float64
+    s_d::Float64
+    x_min::Float64
+    edge_mode::Int32
+    reserved::Int32
+end
+PgOffsetSet(; d0=0.0, d1=0.0, s_a=Inf, s_b=Inf, s_c=Inf, s_d=Inf, x_min=0.1, edge_mode=0) =
+    PgOffsetSet(Float64(d0), Float64(d1), Float64(s_a), Float64(s_b), Float64(s_c), Float64(s_d), Float64(x_min), Int32(edge_mode), Int32(0))
+lane(d; kw...) = PgOffsetSet(; d0=d, d1=d, kw...)
+lane_change(d0, d1, s_a, s_b; kw...) = PgOffsetSet(; d0=d0, d1=d1, s_a=s_a, s_b=s_b, kw...)
+pass_by(d, s_a, s_b, s_c, s_d; kw...) = PgOffsetSet(; d1=d, s_a=s_a, s_b=s_b, s_c=s_c, s_d=s_d, kw...)
+"pg_offset_stats (64 bytes), one per output trajectory"
+struct PgOffsetStats
+    length::Float64
+    ds_min::Float64
+    ds_max::Float64
+    kappa_abs_max::Float64
+    x_min::Float64
+    d_abs_max::Float64
+    closure_pos::Float64
+    n_outside::Int32
+    reserved::Int32
+end
+"channels_in [Lmax, 10, n_path] (column-major: the C layout [n_path][10][Lmax]), L and closed as plan_speeds! takes them -> (channels_out [Lmax, 10, n_path * n_sets], L_out, closed_out, stats), trajectory k = path * n_sets + set (0-based); install = true leaves the handle as pg_set_trajectories with channels_out would"
+function offset_paths!(mpc::BatchedTrajectoryTrackingMPC, channels_in::Array{Float64,3}, L::Vector{Int32}, closed::Vector{Int32}, sets::Vector{PgOffsetSet}; install::Bool=false)
+    (sizeof(PgOffsetSet), sizeof(PgOffsetStats)) == (64, 64) || error("PigeonMI355X.jl: PgOffsetSet / PgOffsetStats differ from include/pigeon_mpc.h")
+    Lmax, _, n_path = size(channels_in)
+    n = n_path * length(sets)
+    out = zeros(Float64, Lmax, 10, n); L_out = zeros(Int32, n); closed_out = zeros(Int32, n); stats = Vector{PgOffsetStats}(undef, n)
+    check(mpc, ccall(sym(mpc, :pg_offset_paths), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{PgOffsetSet}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{PgOffsetStats}),
+                     mpc.handle, Int32(n_path), Int32(Lmax), L, closed, channels_in, Int32(length(sets)), sets, Int32(install), L_out, closed_out, out, stats), "pg_offset_paths")
+    out, L_out, closed_out, stats
+end
+"{ 0, 0, Inf, Inf, Inf, Inf, 0.1, 0, 0 } as the library states them (pg_default_offset_set): the identity"
+default_offset_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_offset_set), PgOffsetSet, ())
+
 # Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
 "pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
 struct PgStartSet

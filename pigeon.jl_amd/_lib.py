@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_start_set", "pg_make_starts",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_start_set", "pg_make_starts",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -258,6 +258,24 @@ PATH_FIT_PROTOTYPES = {
 }
 
 
+class pg_offset_set(C.Structure):
+    """include/pigeon_mpc.h pg_offset_set: the offset outside the windows and on the plateau (m, left positive), the rise and the fall window in the source's arc length
+    (a start of +Inf: no such window), the smallest 1 - kappa d a pair may reach, how the edges follow (0 the same road, 1 the tube travels with the path), a reserved 0."""
+    _fields_ = [(n, C.c_double) for n in ["d0", "d1", "s_a", "s_b", "s_c", "s_d", "x_min"]] + [("edge_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class pg_offset_stats(C.Structure):
+    """include/pigeon_mpc.h pg_offset_stats: one per output trajectory."""
+    _fields_ = [(n, C.c_double) for n in ["length", "ds_min", "ds_max", "kappa_abs_max", "x_min", "d_abs_max", "closure_pos"]] + [("n_outside", C.c_int32), ("reserved", C.c_int32)]
+
+
+# path offsetter (include/pigeon_mpc.h: pg_offset_paths)
+PATH_OFFSET_PROTOTYPES = {
+    "pg_offset_paths": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.POINTER(pg_offset_set), C.c_int32,
+                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(pg_offset_stats)],
+}
+
+
 START_RANGES = ["s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v"]      # the 13 channels of the draws, in their order
 START_MODES = ["s_mode", "e_mode", "steady", "time_mode", "other_mode"]
 
@@ -295,7 +313,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, START_MAKE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, START_MAKE_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -307,6 +325,8 @@ def load_library(precision="f64"):
     lib.pg_default_path_segment.restype = pg_path_segment
     lib.pg_default_waypoint.argtypes = []
     lib.pg_default_waypoint.restype = pg_waypoint
+    lib.pg_default_offset_set.argtypes = []
+    lib.pg_default_offset_set.restype = pg_offset_set
     lib.pg_default_start_set.argtypes = []
     lib.pg_default_start_set.restype = pg_start_set
     lib.pg_default_route.argtypes = []

@@ -1324,6 +1324,131 @@ int pg_fit_paths(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t
     return replace_trajectories(h, D, d_out, d_len, n_path, Lmax, lens[0], std::move(ends));
 }
 
+// ---- pg_offset_paths: every (path, offset set) pair of a path library x a library of offset sets (pg_path_offset.hip).  One launch, one workgroup per pair ----
+static_assert(sizeof(pg_offset_set) == 64 && sizeof(pg_offset_stats) == 64, "the sizes include/pigeon_mpc.h states");
+pg_offset_set pg_default_offset_set(void) {
+    pg_offset_set s; s.d0 = 0.0; s.d1 = 0.0; s.s_a = INFINITY; s.s_b = INFINITY; s.s_c = INFINITY; s.s_d = INFINITY; s.x_min = 0.1; s.edge_mode = 0; s.reserved = 0;
+    return s;
+}
+static const char* offset_set_problem(const pg_offset_set& s) {
+    if (!(std::isfinite(s.d0) && std::isfinite(s.d1))) return "d0 or d1 of a set is not finite";
+    const bool rise = std::isfinite(s.s_a), fall = std::isfinite(s.s_c);
+    if (!(rise || s.s_a == INFINITY) || !(fall || s.s_c == INFINITY)) return "s_a and s_c of a set are finite or +Inf";
+    if (rise && !(std::isfinite(s.s_b) && s.s_b > s.s_a)) return "a rise of a set needs a finite s_b > s_a";
+    if (fall && !(std::isfinite(s.s_d) && s.s_d > s.s_c)) return "a fall of a set needs a finite s_d > s_c";
+    if (!rise && std::isnan(s.s_b)) return "s_b of a set is NaN";
+    if (!fall && std::isnan(s.s_d)) return "s_d of a set is NaN";
+    if (fall && !rise) return "a set has a fall without a rise";
+    if (rise && fall && s.s_c < s.s_b) return "a set needs s_c >= s_b (the fall starts after the rise has ended)";
+    if (!(s.x_min > 0.0 && s.x_min <= 1.0)) return "a set needs x_min in (0, 1]";
+    if (s.edge_mode != 0 && s.edge_mode != 1) return "edge_mode of a set is 0 or 1";
+    if (s.reserved != 0) return "reserved of a set must be 0";
+    return nullptr;
+}
+int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
+                    int32_t n_sets, const pg_offset_set* sets, int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_offset_stats* stats) {
+#pragma clang fp contract(off)
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, L && channels_in && sets, "pg_offset_paths: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && Lmax >= 2, "pg_offset_paths: need n_path >= 1, n_sets >= 1 and Lmax >= 2");
+    REQUIRE(h, (double)n_path * (double)n_sets <= 2147483647.0, "pg_offset_paths: n_path * n_sets must fit 31 bits");
+    // (the largest buffer of the call holds n_path * n_sets * 10 * Lmax elements: its size in bytes has to fit the size arithmetic, with room for the sums around it)
+    REQUIRE(h, (double)n_path * (double)n_sets * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0,
+            "pg_offset_paths: n_path * n_sets * 10 * Lmax elements are more than the allocation arithmetic holds");
+    const size_t stride = (size_t)10 * Lmax;
+    for (int k = 0; k < n_path; k++) {
+        REQUIRE(h, L[k] >= 2 && L[k] <= Lmax, "pg_offset_paths: every path needs 2 <= L[k] <= Lmax");
+        const bool cl = closed && closed[k] != 0;
+        REQUIRE(h, !cl || L[k] >= 3, "pg_offset_paths: a closed path needs >= 3 knots");
+        const double* c = channels_in + (size_t)k * stride;
+        for (int ch = 0; ch < 10; ch++) {
+            if (ch == PO_T || ch == PO_V || ch == PO_A) continue;
+            for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(c[(size_t)ch * Lmax + i]), "pg_offset_paths: a geometry value of a valid knot is not finite");
+        }
+        const double* s = c + (size_t)PO_S * Lmax; const double* V = c + (size_t)PO_V * Lmax;
+        for (int i = 1; i < L[k]; i++) REQUIRE(h, (real)s[i] > (real)s[i - 1], "pg_offset_paths: s must increase strictly over the valid knots");
+        for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(V[i]) && V[i] > 0.0, "pg_offset_paths: V of a valid knot is not finite and > 0");
+        REQUIRE(h, std::isfinite(c[(size_t)PO_T * Lmax]), "pg_offset_paths: t of the first knot is not finite");
+    }
+    for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_offset_paths: ", offset_set_problem(sets[j]));
+    // the pairs: x = 1 - kappa_i d_i at every valid knot, in the kernel's own arithmetic (po_offset is one function for host and device); the ends of a closed path
+    for (int k = 0; k < n_path; k++) {
+        const double* c = channels_in + (size_t)k * stride;
+        const double* s = c + (size_t)PO_S * Lmax; const double* kap = c + (size_t)PO_KAPPA * Lmax;
+        const bool cl = closed && closed[k] != 0;
+        for (int j = 0; j < n_sets; j++) {
+            const pg_offset_set& S = sets[j];
+            if (cl) {
+                const OffsetEval a = po_offset(S, 0.0), z = po_offset(S, s[L[k] - 1] - s[0]);
+                if (!(a.d1 == 0.0 && a.d2 == 0.0 && z.d1 == 0.0 && z.d2 == 0.0 && a.d == z.d)) {
+                    h->err = "pg_offset_paths: path " + std::to_string(k) + " is closed and its first or last knot lies inside a window of set " + std::to_string(j) +
+                             ", or its two ends lie on different plateaus (the offset curve does not close)";
+                    return PG_ERR_INVALID;
+                }
+            }
+            if (S.d0 == 0.0 && S.d1 == 0.0) continue;         // (x = 1 at every knot)
+            for (int i = 0; i < L[k]; i++) {
+                const OffsetEval D = po_offset(S, s[i] - s[0]);
+                const double kd = kap[i] * D.d;
+                const double x = 1.0 - kd;
+                if (!(x >= S.x_min)) {
+                    h->err = "pg_offset_paths: path " + std::to_string(k) + ", set " + std::to_string(j) + ", knot " + std::to_string(i) + ": 1 - kappa d = " + std::to_string(x) +
+                             " is below x_min (the offset reaches the centre of curvature)";
+                    return PG_ERR_INVALID;
+                }
+            }
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t n_traj = (size_t)n_path * n_sets, total = n_traj * stride, n_in = (size_t)n_path * stride;
+    std::vector<int> lens(n_traj), cls((size_t)n_path);
+    for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
+    for (int k = 0; k < n_path; k++) cls[(size_t)k] = closed ? closed[k] : 0;
+    CallBufs D; double *d_in = nullptr, *d_sp = nullptr, *d_run = nullptr, *d_tend = nullptr; real* d_out = nullptr; int *d_L = nullptr, *d_cl = nullptr, *d_len = nullptr, *d_bad = nullptr;
+    pg_offset_set* d_sets = nullptr; pg_offset_stats* d_stats = nullptr;
+    HIPCHK(h, D.alloc(d_in, n_in));
+    HIPCHK(h, D.alloc(d_out, total));
+    HIPCHK(h, D.alloc(d_sp, n_traj * (size_t)Lmax));
+    HIPCHK(h, D.alloc(d_run, n_traj * (size_t)Lmax));
+    HIPCHK(h, D.alloc(d_tend, n_traj));
+    HIPCHK(h, D.alloc(d_L, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_cl, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_len, n_traj));
+    HIPCHK(h, D.alloc(d_bad, n_traj));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_stats, n_traj));
+    // (plain copies, as install_trajectories uses: the host arrays are consumed when each returns, on every way out.  The source travels as the doubles given)
+    HIPCHK(h, hipMemcpy(d_in, channels_in, n_in * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_cl, cls.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_sets, sets, (size_t)n_sets * sizeof(pg_offset_set), hipMemcpyHostToDevice));
+    PathOffsetArgs A; A.n_sets = n_sets; A.Lmax = Lmax; A.L = d_L; A.closed = d_cl; A.in = d_in; A.sets = d_sets; A.out = d_out; A.sp = d_sp; A.run = d_run; A.t_end = d_tend; A.stats = d_stats; A.bad = d_bad;
+    hipLaunchKernelGGL(k_path_offset, dim3((unsigned)n_traj), dim3(PO_THREADS), 0, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_offset_stats> st(n_traj);
+    std::vector<int> bad(n_traj);
+    std::vector<double> ends(n_traj);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_traj * sizeof(pg_offset_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ends.data(), d_tend, n_traj * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, n_traj * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    for (size_t k = 0; k < n_traj; k++) if (bad[k]) {
+        h->err = "pg_offset_paths: path " + std::to_string(k / (size_t)n_sets) + ", set " + std::to_string(k % (size_t)n_sets) +
+                 ": the offset knots are so dense that s does not increase strictly in the library's element type (ds_min " + std::to_string(st[k].ds_min) + ")";
+        return PG_ERR_INVALID;
+    }
+    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
+    for (size_t k = 0; k < n_traj; k++) {
+        if (L_out) L_out[k] = lens[k];
+        if (closed_out) closed_out[k] = cls[k / (size_t)n_sets];
+    }
+    if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_offset_stats));
+    if (!install) return PG_OK;
+    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));      // (ends: t of the last knot as stored, what pg_set_trajectories reads from channels_out)
+}
+
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
 // solver state: nothing is reset ----
 static const char* sensor_set_problem(const pg_sensor& s) {

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -20,6 +20,7 @@ c_i32p = C.POINTER(C.c_int32)
 SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
 PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
+OFFSET_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_offset_stats._fields_])      # 64 bytes, the layout of pg_offset_stats
 FIT_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_fit_stats._fields_])      # 80 bytes, the layout of pg_fit_stats
 
 
@@ -407,6 +408,54 @@ class BatchedTrajectoryTrackingMPC:
         st = (_lib.pg_fit_stats * n)()
         self._chk(self.lib.pg_fit_paths(self.h, n, specs, len(wps), wps, Lmax, int(bool(install)), _p(L, c_i32p), _p(cl, c_i32p), _p(out), st), "pg_fit_paths")
         return self._made_tubes(out, L, 1, install), cl, np.frombuffer(st, dtype=FIT_STATS_DTYPE).copy()
+
+    # ---- offsetting the path (pg_offset_paths): every (path, offset set) pair of a path library x a library of offset sets, computed on the device ----
+    @classmethod
+    def pack_offsets(cls, sets):
+        """dicts (vehicles.offset / lane / lane_change / pass_by; missing fields: the defaults) or pg_offset_set structures -> a ctypes array of pg_offset_set.  Raises
+        ValueError for a set outside the ranges of include/pigeon_mpc.h (the library refuses the same sets with PG_ERR_INVALID)."""
+        def fill(rec, p):
+            full = _default_offset(**p)
+            for name, ctype in _lib.pg_offset_set._fields_:
+                setattr(rec, name, int(full[name]) if ctype is C.c_int32 else float(full[name]))
+        arr = cls._pack(_lib.pg_offset_set, [sets] if isinstance(sets, (dict, _lib.pg_offset_set)) else sets, fill)
+        if len(arr) < 1:
+            raise ValueError("offset_paths: at least one offset set")
+        for k, r in enumerate(arr):
+            rise, fall = math.isfinite(r.s_a), math.isfinite(r.s_c)
+            if not (math.isfinite(r.d0) and math.isfinite(r.d1)):
+                raise ValueError(f"offset_paths: d0 or d1 of set {k} is not finite")
+            if not ((rise or r.s_a == math.inf) and (fall or r.s_c == math.inf)):
+                raise ValueError(f"offset_paths: s_a and s_c of set {k} are finite or +Inf")
+            if (rise and not (math.isfinite(r.s_b) and r.s_b > r.s_a)) or (fall and not (math.isfinite(r.s_d) and r.s_d > r.s_c)) or math.isnan(r.s_b) or math.isnan(r.s_d):
+                raise ValueError(f"offset_paths: a window of set {k} needs a finite end beyond its start (s_b > s_a, s_d > s_c)")
+            if fall and not rise:
+                raise ValueError(f"offset_paths: set {k} has a fall without a rise")
+            if rise and fall and r.s_c < r.s_b:
+                raise ValueError(f"offset_paths: set {k} needs s_c >= s_b (the fall starts after the rise has ended)")
+            if not 0.0 < r.x_min <= 1.0:
+                raise ValueError(f"offset_paths: set {k} needs x_min in (0, 1]")
+            if r.edge_mode not in (0, 1):
+                raise ValueError(f"offset_paths: edge_mode of set {k} is 0 or 1")
+            if r.reserved != 0:
+                raise ValueError(f"offset_paths: reserved of set {k} must be 0")
+        return arr
+
+    def offset_paths(self, paths, sets, closed=None, install=False):
+        """Lanes, lane changes and pass-bys of a path library on the device (pg_offset_paths; the scheme is stated in include/pigeon_mpc.h): paths = TrajectoryTubes or the
+        channel array, sets = vehicles.lane(3.5) / lane_change(0, 3.5, 40, 70) / pass_by(3.0, 120, 135, 145, 160) / offset(**overrides) dicts, closed = None / one flag /
+        one per path.  Output knot i belongs to source knot i; V is copied and t, A follow the new arc length -- hand the result to plan_speeds (closed=np.repeat(closed,
+        len(sets))) for a friction-limited profile on the new curvature.  Returns (tubes, stats): the n_path * n_sets TrajectoryTubes in the order k = path * n_sets + set,
+        and a structured array with the fields of pg_offset_stats.  install=True makes them the handle's trajectory library (as set_trajectories(tubes) would, without the
+        host round trip; select with set_trajectory_index, switch with route events)."""
+        L, ch, cl = self.pack_paths(paths, closed)
+        arr = self.pack_offsets(sets)
+        n_traj = len(L) * len(arr)
+        out = np.zeros((n_traj, 10, ch.shape[2]))
+        st = (_lib.pg_offset_stats * n_traj)()
+        self._chk(self.lib.pg_offset_paths(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, int(bool(install)), None, None, _p(out), st),
+                  "pg_offset_paths")
+        return self._made_tubes(out, L, len(arr), install), np.frombuffer(st, dtype=OFFSET_STATS_DTYPE).copy()
 
     # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
     @classmethod

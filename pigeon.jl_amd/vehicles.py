@@ -192,6 +192,37 @@ def speed_plan(**overrides):
     return p
 
 
+OFFSET_FIELDS = ("d0", "d1", "s_a", "s_b", "s_c", "s_d", "x_min", "edge_mode", "reserved")
+
+
+def offset(**overrides):
+    """One offset set for offset_paths (pg_offset_set).  offset() is the library's default (pg_default_offset_set), the identity: d0 = d1 = 0, no window (s_a = s_c =
+    +Inf), x_min 0.1, edge_mode 0.  d0 / d1: the offset in metres, left positive, outside the windows / on the plateau; the rise d0 -> d1 runs over [s_a, s_b] and the fall
+    d1 -> d0 over [s_c, s_d], metres of the source's arc length from its first knot; x_min: the smallest 1 - kappa d a pair may reach; edge_mode 0: the same road (the
+    edges move by -d), 1: the tube travels with the path.  lane, lane_change and pass_by build the usual three.  Build-defined: the reference has no path maker."""
+    p = dict(d0=0.0, d1=0.0, s_a=math.inf, s_b=math.inf, s_c=math.inf, s_d=math.inf, x_min=0.1, edge_mode=0, reserved=0)
+    for k, v in overrides.items():
+        if k not in p:
+            raise KeyError(f"{k} is not a field of an offset set: {OFFSET_FIELDS}")
+        p[k] = int(v) if k in ("edge_mode", "reserved") else float(v)
+    return p
+
+
+def lane(d, **overrides):
+    """The same road d metres to the left (d < 0: to the right): offset(d0=d, d1=d)."""
+    return offset(d0=d, d1=d, **overrides)
+
+
+def lane_change(d0, d1, s_a, s_b, **overrides):
+    """Leave the lane d0 at s_a and be on the lane d1 at s_b (metres of the source's arc length from its first knot): a single rise, no fall."""
+    return offset(d0=d0, d1=d1, s_a=s_a, s_b=s_b, **overrides)
+
+
+def pass_by(d, s_a, s_b, s_c, s_d, **overrides):
+    """Go round something: leave the source at s_a, be d metres to the left at s_b, start back at s_c and be on the source again at s_d."""
+    return offset(d0=0.0, d1=d, s_a=s_a, s_b=s_b, s_c=s_c, s_d=s_d, **overrides)
+
+
 START_RANGES = ("s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v")
 START_MODES = ("s_mode", "e_mode", "steady", "time_mode", "other_mode")
 
