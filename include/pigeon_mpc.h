@@ -403,6 +403,79 @@ pg_offset_set pg_default_offset_set(void);
 int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
                     int32_t n_sets, const pg_offset_set* sets, int32_t install, int32_t* L_out, int32_t* closed_out, double* channels_out, pg_offset_stats* stats);
 
+/* Clipping the tube: every (path, obstacle set) pair of a path library and a library of obstacle sets as a trajectory, computed on the device in the layout
+ * pg_set_trajectories takes -- the same path, its two edge channels narrowed around the discs of the set: the thing a pass-by of pg_offset_paths goes round.  Whatever
+ * reads the edges (the wall rows of the decoupled formulation, first_exit of the tracking summary, e_frac of pg_make_starts, n_outside of pg_offset_paths) then sees the
+ * obstacle.  The reference has no obstacles (src/trajectories.jl:8-44 only stores edge_L, edge_R), so the scheme is build-defined (tests/tube_clip_numpy.py is its numpy
+ * twin).  It is knot-wise.  channels_in is read as the doubles given, ALL arithmetic is double in both libraries, every operation rounded on its own (no contraction), and a
+ * value is rounded to the library's element type once, on store: the fp32 library's output is exactly the fp64 library's rounded to float, and the stats and reports are
+ * the same doubles.  Below, a parenthesis is one rounded operation; min, max and | | are exact.
+ *   Frame     That of pg_make_starts / pg_offset_paths: psi is measured from North, the tangent in (E, N) is (-sin psi, cos psi), the left normal is (-cos psi, -sin psi),
+ *             and edge_R < 0 < edge_L on an unobstructed road.  Knot i is a valid knot of the path; knot L-1 of a closed path is knot 0 again: it takes part in no
+ *             search and in no count, and its two output edges are those of knot 0.  Obstacle j is an obstacle of the set, R = (radius + margin).
+ *   Sight     wE = E_j - E_i, wN = N_j - N_i;  a = (wE (-cos psi_i)) + (wN (-sin psi_i)) (to the left),  b = (wE (-sin psi_i)) + (wN cos psi_i) (ahead),
+ *             q = (wE wE) + (wN wN).  Knot i SEES j when |b| < R and, with h = sqrt((R R) - (b b)), (a - h) < edge_L_i and (a + h) > edge_R_i: the chord the disc cuts
+ *             out of the knot's normal line reaches into the SOURCE tube.
+ *   Closest   k_at = the knot of smallest q, the lowest index on ties.  The report's values are those of this knot: dist_at = sqrt(q), a_at = a, u_at = s - s_first,
+ *             h_at = h (0 where |b| >= R there), free_right = (a_at - h_at) - edge_R, free_left = edge_L - (a_at + h_at).
+ *   Side      One decision per (pair, obstacle), taken at k_at, so a tube never splits.  PG_PASS_CENTRE: the obstacle is on the left when a_at > 0.  PG_PASS_WIDER: pass
+ *             on the side of the larger free_*, on equality the CENTRE rule.  PG_PASS_LEFT: the obstacle counts as on the right.  PG_PASS_RIGHT: as on the left.
+ *             side = +1: the left edge is clipped (we pass on the right); -1: the right edge; 0: no knot sees it (it is ignored; k_first = k_last = -1).
+ *   Hard clip cL_i and cR_i start from edge_L_i and edge_R_i.  At every knot that sees j: cL_i = min(cL_i, (a - h)) when side = +1, cR_i = max(cR_i, (a + h)) when
+ *             side = -1.  k_first / k_last are the lowest and the highest seeing knot.
+ *   Taper     dist(i, k) = |s_i - s_k| on an open path, min(|s_i - s_k|, ((s_{L-1} - s_0) - |s_i - s_k|)) on a closed one.  With m = taper finite:
+ *             edge_L'_i = min(cL_i, min over the knots k with cL_k < edge_L_k of (cL_k + (m dist(i, k)))),
+ *             edge_R'_i = max(cR_i, max over the knots k with cR_k > edge_R_k of (cR_k - (m dist(i, k)))).  With m = +Inf: edge' = c.
+ *             Every term is an expression of its own and min / max are exact, so the result does not depend on the order in which the k are visited.
+ *   Stats     Over the knots that take part, on the doubles before the store: width_min = min of (edge_L' - edge_R'), u_width_min = s - s_first there (the lowest knot
+ *             on ties);  n_clip_L / n_clip_R count the knots where edge_L' / edge_R' differs from the source;  n_blocked those where (edge_L' - edge_R') < min_width;
+ *             n_centre_out those where edge_R' < 0 < edge_L' fails;  n_seen / n_ignored the obstacles of the set with side != 0 / == 0.  Blocked and centre-out knots
+ *             are reported, never refused.
+ *   Output    The other eight channels are copied (as the element type holds them), L_out and closed_out as in pg_offset_paths.
+ * What the knots see: a disc that lies between two knots farther apart than its chord is seen by neither and comes back side = 0 -- on a line with knots 10 m apart a disc
+ * of R = 1.5 m at 215 m is such a one.  A tube wider than the distance to the opposite side of a loop is outside the scheme.  Choose the knots to the obstacle.
+ * The copied channels, every integer and every edge of a knot no obstacle touches reproduce the twin bit for bit; a touched edge and the report's doubles are within
+ * 8 * 2^-52 * (|wE| + |wN| + R) * (1 + |b| / h) of it (sin, cos, a two-term product sum, and the condition of sqrt((R R) - (b b))). */
+enum pg_pass_policy { PG_PASS_CENTRE = 0, PG_PASS_WIDER = 1, PG_PASS_LEFT = 2, PG_PASS_RIGHT = 3 };
+typedef struct pg_obstacle {
+    double E, N, radius;      /* a disc in the world frame; finite, radius >= 0 */
+    double reserved;          /* 0 */
+} pg_obstacle;                /* 32 bytes */
+typedef struct pg_obstacle_set {
+    int32_t first, count;     /* obstacles[first .. first+count) of the call's array; count in [0, 64]; sets may share and overlap ranges */
+    double margin;            /* added to every radius: half the car's width plus clearance; finite, >= 0 */
+    double taper;             /* metres of edge per metre of arclength by which a clip may relax; > 0, or +Inf: no taper, the hard clip only */
+    double min_width;         /* a knot whose clipped width is below this counts as blocked; finite, >= 0 */
+    int32_t policy, reserved; /* PG_PASS_CENTRE 0, PG_PASS_WIDER 1, PG_PASS_LEFT 2, PG_PASS_RIGHT 3; 0 */
+    double pad[3];            /* 0 */
+} pg_obstacle_set;            /* 64 bytes */
+typedef struct pg_clip_stats {     /* one per output trajectory; computed in double in both libraries */
+    double width_min, u_width_min;
+    double reserved_d[2];
+    int32_t n_clip_L, n_clip_R, n_blocked, n_centre_out, n_seen, n_ignored, reserved[2];
+} pg_clip_stats;              /* 64 bytes */
+typedef struct pg_obstacle_report {   /* one per (output trajectory, obstacle slot) */
+    double u_at, a_at, h_at, dist_at, free_left, free_right;
+    int32_t k_at, k_first, k_last, side;
+} pg_obstacle_report;         /* 64 bytes */
+/* { 0, 0, 0.0, +Inf, 0.0, 0, 0, {0, 0, 0} }: the identity */
+pg_obstacle_set pg_default_obstacle_set(void);
+/* channels_in [n_path][10][Lmax], L and closed are what pg_offset_paths takes (closed NULL: every path is open); V, A and t are copied, not read.  obstacles [n_obs] is
+ * shared by the sets.  Output trajectory k = path * n_sets + set: channels_out [n_path * n_sets][10][Lmax], stats [n_path * n_sets], L_out, closed_out as in
+ * pg_offset_paths, report [n_path * n_sets][max_count] with max_count the largest count of the call (slot j of a pair: obstacle first + j of its set; the unused slots are
+ * all zero with k_at = k_first = k_last = -1); each may be NULL.  Every channel is 0 at and past L.  install != 0 hands the device buffer to the handle, with no host round
+ * trip: the handle is then exactly as after pg_set_trajectories(h, n_path * n_sets, Lmax, L_out, channels_out).  Synchronous.  A handle that never calls this launches
+ * what it launched before.
+ * PG_ERR_INVALID, all of it validated before the first allocation (the handle and its installed library are left unchanged): a null L, channels_in or sets; n_path or
+ * n_sets < 1; Lmax < 2; L[k] outside [2, Lmax]; a closed path of fewer than 3 knots; s that does not increase strictly over the valid knots (in the library's element
+ * type); a non-finite geometry value (s, E, N, psi, kappa, either edge) in a valid knot; n_obs < 0, or obstacles NULL while some count > 0; first < 0, count outside
+ * [0, 64] or first + count > n_obs; a non-finite E, N or radius, a radius < 0 or a reserved != 0 of an obstacle some set uses; radius + margin not > 0; margin or
+ * min_width not finite and >= 0; taper not > 0 (NaN included); policy outside 0 .. 3; reserved or pad != 0; n_path * n_sets * 10 * Lmax elements beyond the allocation
+ * arithmetic. */
+int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
+                  int32_t n_sets, const pg_obstacle_set* sets, int32_t n_obs, const pg_obstacle* obstacles, int32_t install,
+                  int32_t* L_out, int32_t* closed_out, double* channels_out, pg_clip_stats* stats, pg_obstacle_report* report);
+
 /* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
  * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car
  * (src/ros_integration.jl:48-99), so the feature is build-defined (tests/start_make_numpy.py is its numpy twin).  After pg_make_paths / pg_fit_paths / pg_plan_speeds

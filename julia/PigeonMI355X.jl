@@ -732,6 +732,68 @@ end
 "{ 0, 0, Inf, Inf, Inf, Inf, 0.1, 0, 0 } as the library states them (pg_default_offset_set): the identity"
 default_offset_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_offset_set), PgOffsetSet, ())
 
+# Clipping the tube (pg_clip_tubes): the tubes of a path library narrowed around obstacle sets on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_obstacle (32 bytes): a disc in the world frame, a reserved 0"
+struct PgObstacle
+    E::Float64
+    N::Float64
+    radius::Float64
+    reserved::Float64
+end
+PgObstacle(E, N, radius) = PgObstacle(Float64(E), Float64(N), Float64(radius), 0.0)
+"pg_obstacle_set (64 bytes): obstacles[first+1 : first+count] of the call's array (first is 0-based, as in C), the margin added to every radius, the taper (Inf: none), the width below which a knot counts as blocked, the side policy (0 centre, 1 wider, 2 pass left, 3 pass right), zeros"
+struct PgObstacleSet
+    first::Int32
+    count::Int32
+    margin::Float64
+    taper::Float64
+    min_width::Float64
+    policy::Int32
+    reserved::Int32
+    pad::NTuple{3,Float64}
+end
+PgObstacleSet(; first=0, count=0, margin=0.0, taper=Inf, min_width=0.0, policy=0) =
+    PgObstacleSet(Int32(first), Int32(count), Float64(margin), Float64(taper), Float64(min_width), Int32(policy), Int32(0), (0.0, 0.0, 0.0))
+"pg_clip_stats (64 bytes), one per output trajectory"
+struct PgClipStats
+    width_min::Float64
+    u_width_min::Float64
+    reserved_d::NTuple{2,Float64}
+    n_clip_L::Int32
+    n_clip_R::Int32
+    n_blocked::Int32
+    n_centre_out::Int32
+    n_seen::Int32
+    n_ignored::Int32
+    reserved::NTuple{2,Int32}
+end
+"pg_obstacle_report (64 bytes), one per (output trajectory, obstacle slot); the knot indices are 0-based, as in C"
+struct PgObstacleReport
+    u_at::Float64
+    a_at::Float64
+    h_at::Float64
+    dist_at::Float64
+    free_left::Float64
+    free_right::Float64
+    k_at::Int32
+    k_first::Int32
+    k_last::Int32
+    side::Int32
+end
+"channels_in [Lmax, 10, n_path], L and closed as offset_paths! takes them -> (channels_out [Lmax, 10, n_path * n_sets], L_out, closed_out, stats, report [max_count, n_path * n_sets]), trajectory k = path * n_sets + set (0-based); install = true leaves the handle as pg_set_trajectories with channels_out would"
+function clip_tubes!(mpc::BatchedTrajectoryTrackingMPC, channels_in::Array{Float64,3}, L::Vector{Int32}, closed::Vector{Int32}, sets::Vector{PgObstacleSet}, obstacles::Vector{PgObstacle}; install::Bool=false)
+    (sizeof(PgObstacle), sizeof(PgObstacleSet), sizeof(PgClipStats), sizeof(PgObstacleReport)) == (32, 64, 64, 64) || error("PigeonMI355X.jl: the pg_clip_tubes structures differ from include/pigeon_mpc.h")
+    Lmax, _, n_path = size(channels_in)
+    n = n_path * length(sets)
+    max_count = maximum(Int(s.count) for s in sets)
+    out = zeros(Float64, Lmax, 10, n); L_out = zeros(Int32, n); closed_out = zeros(Int32, n); stats = Vector{PgClipStats}(undef, n); report = Matrix{PgObstacleReport}(undef, max_count, n)
+    check(mpc, ccall(sym(mpc, :pg_clip_tubes), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{PgObstacleSet}, Int32, Ptr{PgObstacle}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{PgClipStats}, Ptr{PgObstacleReport}),
+                     mpc.handle, Int32(n_path), Int32(Lmax), L, closed, channels_in, Int32(length(sets)), sets, Int32(length(obstacles)), obstacles, Int32(install), L_out, closed_out, out, stats, report), "pg_clip_tubes")
+    out, L_out, closed_out, stats, report
+end
+"{ 0, 0, 0.0, Inf, 0.0, 0, 0, (0, 0, 0) } as the library states them (pg_default_obstacle_set): the identity"
+default_obstacle_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_obstacle_set), PgObstacleSet, ())
+
 # Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
 "pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
 struct PgStartSet

@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_start_set", "pg_make_starts",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_start_set", "pg_make_starts",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -276,6 +276,35 @@ PATH_OFFSET_PROTOTYPES = {
 }
 
 
+class pg_obstacle(C.Structure):
+    """include/pigeon_mpc.h pg_obstacle: a disc in the world frame, a reserved 0."""
+    _fields_ = [(n, C.c_double) for n in ["E", "N", "radius", "reserved"]]
+
+
+class pg_obstacle_set(C.Structure):
+    """include/pigeon_mpc.h pg_obstacle_set: the range of the call's obstacle array, the margin added to every radius, the taper (m of edge per m of arc length; +Inf: none),
+    the width below which a knot counts as blocked, the side policy (0 centre, 1 wider, 2 pass left, 3 pass right), zeros."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("margin", C.c_double), ("taper", C.c_double), ("min_width", C.c_double), ("policy", C.c_int32), ("reserved", C.c_int32),
+                ("pad", C.c_double * 3)]
+
+
+class pg_clip_stats(C.Structure):
+    """include/pigeon_mpc.h pg_clip_stats: one per output trajectory."""
+    _fields_ = [("width_min", C.c_double), ("u_width_min", C.c_double), ("reserved_d", C.c_double * 2)] + [(n, C.c_int32) for n in ["n_clip_L", "n_clip_R", "n_blocked", "n_centre_out", "n_seen", "n_ignored"]] + [("reserved", C.c_int32 * 2)]
+
+
+class pg_obstacle_report(C.Structure):
+    """include/pigeon_mpc.h pg_obstacle_report: one per (output trajectory, obstacle slot)."""
+    _fields_ = [(n, C.c_double) for n in ["u_at", "a_at", "h_at", "dist_at", "free_left", "free_right"]] + [(n, C.c_int32) for n in ["k_at", "k_first", "k_last", "side"]]
+
+
+# tube clipper (include/pigeon_mpc.h: pg_clip_tubes)
+TUBE_CLIP_PROTOTYPES = {
+    "pg_clip_tubes": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.POINTER(pg_obstacle_set), C.c_int32,
+                      C.POINTER(pg_obstacle), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(pg_clip_stats), C.POINTER(pg_obstacle_report)],
+}
+
+
 START_RANGES = ["s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v"]      # the 13 channels of the draws, in their order
 START_MODES = ["s_mode", "e_mode", "steady", "time_mode", "other_mode"]
 
@@ -313,7 +342,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, START_MAKE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, START_MAKE_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -327,6 +356,8 @@ def load_library(precision="f64"):
     lib.pg_default_waypoint.restype = pg_waypoint
     lib.pg_default_offset_set.argtypes = []
     lib.pg_default_offset_set.restype = pg_offset_set
+    lib.pg_default_obstacle_set.argtypes = []
+    lib.pg_default_obstacle_set.restype = pg_obstacle_set
     lib.pg_default_start_set.argtypes = []
     lib.pg_default_start_set.restype = pg_start_set
     lib.pg_default_route.argtypes = []

@@ -1449,6 +1449,108 @@ int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
     return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));      // (ends: t of the last knot as stored, what pg_set_trajectories reads from channels_out)
 }
 
+// ---- pg_clip_tubes: every (path, obstacle set) pair of a path library x a library of obstacle sets (pg_tube_clip.hip).  One launch, one workgroup per pair ----
+static_assert(sizeof(pg_obstacle) == 32 && sizeof(pg_obstacle_set) == 64 && sizeof(pg_clip_stats) == 64 && sizeof(pg_obstacle_report) == 64, "the sizes include/pigeon_mpc.h states");
+pg_obstacle_set pg_default_obstacle_set(void) {
+    pg_obstacle_set s; s.first = 0; s.count = 0; s.margin = 0.0; s.taper = INFINITY; s.min_width = 0.0; s.policy = PG_PASS_CENTRE; s.reserved = 0; s.pad[0] = 0.0; s.pad[1] = 0.0; s.pad[2] = 0.0;
+    return s;
+}
+static const char* obstacle_set_problem(const pg_obstacle_set& s, int n_obs, const pg_obstacle* obs) {
+    if (!(s.count >= 0 && s.count <= 64)) return "count of a set is outside [0, 64]";
+    if (!(s.first >= 0 && (long long)s.first + s.count <= (long long)n_obs)) return "first .. first + count of a set lies outside the obstacle array";
+    if (s.count > 0 && !obs) return "a set has obstacles and the obstacle array is null";
+    if (!(std::isfinite(s.margin) && s.margin >= 0.0)) return "margin of a set is not finite and >= 0";
+    if (!(s.taper > 0.0)) return "taper of a set is not > 0 (+Inf: no taper)";
+    if (!(std::isfinite(s.min_width) && s.min_width >= 0.0)) return "min_width of a set is not finite and >= 0";
+    if (s.policy < 0 || s.policy > 3) return "policy of a set is outside 0 .. 3";
+    if (s.reserved != 0 || s.pad[0] != 0.0 || s.pad[1] != 0.0 || s.pad[2] != 0.0) return "reserved and pad of a set must be 0";
+    for (int j = 0; j < s.count; j++) {
+        const pg_obstacle& o = obs[s.first + j];
+        if (!(std::isfinite(o.E) && std::isfinite(o.N) && std::isfinite(o.radius))) return "E, N or radius of an obstacle is not finite";
+        if (!(o.radius >= 0.0)) return "radius of an obstacle is < 0";
+        if (o.reserved != 0.0) return "reserved of an obstacle must be 0";
+        const double R = o.radius + s.margin;
+        if (!(R > 0.0)) return "radius + margin of an obstacle is not > 0";
+    }
+    return nullptr;
+}
+int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
+                  int32_t n_sets, const pg_obstacle_set* sets, int32_t n_obs, const pg_obstacle* obstacles, int32_t install,
+                  int32_t* L_out, int32_t* closed_out, double* channels_out, pg_clip_stats* stats, pg_obstacle_report* report) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, L && channels_in && sets, "pg_clip_tubes: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && Lmax >= 2, "pg_clip_tubes: need n_path >= 1, n_sets >= 1 and Lmax >= 2");
+    REQUIRE(h, n_obs >= 0, "pg_clip_tubes: n_obs < 0");
+    REQUIRE(h, (double)n_path * (double)n_sets <= 2147483647.0, "pg_clip_tubes: n_path * n_sets must fit 31 bits");
+    // (the largest buffer of the call holds n_path * n_sets * 10 * Lmax elements: its size in bytes has to fit the size arithmetic, with room for the sums around it)
+    REQUIRE(h, (double)n_path * (double)n_sets * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0,
+            "pg_clip_tubes: n_path * n_sets * 10 * Lmax elements are more than the allocation arithmetic holds");
+    const size_t stride = (size_t)10 * Lmax;
+    for (int k = 0; k < n_path; k++) {
+        REQUIRE(h, L[k] >= 2 && L[k] <= Lmax, "pg_clip_tubes: every path needs 2 <= L[k] <= Lmax");
+        const bool cl = closed && closed[k] != 0;
+        REQUIRE(h, !cl || L[k] >= 3, "pg_clip_tubes: a closed path needs >= 3 knots");
+        const double* c = channels_in + (size_t)k * stride;
+        for (int ch = 0; ch < 10; ch++) {
+            if (ch == PO_T || ch == PO_V || ch == PO_A) continue;
+            for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(c[(size_t)ch * Lmax + i]), "pg_clip_tubes: a geometry value of a valid knot is not finite");
+        }
+        const double* s = c + (size_t)PO_S * Lmax;
+        for (int i = 1; i < L[k]; i++) REQUIRE(h, (real)s[i] > (real)s[i - 1], "pg_clip_tubes: s must increase strictly over the valid knots");
+    }
+    int max_count = 0;
+    for (int j = 0; j < n_sets; j++) {
+        REQUIRE_NO(h, "pg_clip_tubes: ", obstacle_set_problem(sets[j], n_obs, obstacles));
+        max_count = std::max(max_count, (int)sets[j].count);
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t n_traj = (size_t)n_path * n_sets, total = n_traj * stride, n_in = (size_t)n_path * stride, n_rep = n_traj * (size_t)max_count;
+    std::vector<int> lens(n_traj), cls((size_t)n_path);
+    for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
+    for (int k = 0; k < n_path; k++) cls[(size_t)k] = closed ? closed[k] : 0;
+    CallBufs D; double *d_in = nullptr, *d_scr = nullptr, *d_tend = nullptr; real* d_out = nullptr; int *d_L = nullptr, *d_cl = nullptr, *d_len = nullptr;
+    pg_obstacle_set* d_sets = nullptr; pg_obstacle* d_obs = nullptr; pg_clip_stats* d_stats = nullptr; pg_obstacle_report* d_rep = nullptr;
+    HIPCHK(h, D.alloc(d_in, n_in));
+    HIPCHK(h, D.alloc(d_out, total));
+    HIPCHK(h, D.alloc(d_scr, 6 * n_traj * (size_t)Lmax));
+    HIPCHK(h, D.alloc(d_tend, n_traj));
+    HIPCHK(h, D.alloc(d_L, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_cl, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_len, n_traj));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_obs, (size_t)std::max(n_obs, 1)));
+    HIPCHK(h, D.alloc(d_stats, n_traj));
+    HIPCHK(h, D.alloc(d_rep, std::max(n_rep, (size_t)1)));
+    // (plain copies, as install_trajectories uses: the host arrays are consumed when each returns, on every way out.  The source travels as the doubles given)
+    HIPCHK(h, hipMemcpy(d_in, channels_in, n_in * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_cl, cls.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_sets, sets, (size_t)n_sets * sizeof(pg_obstacle_set), hipMemcpyHostToDevice));
+    if (n_obs > 0 && obstacles) HIPCHK(h, hipMemcpy(d_obs, obstacles, (size_t)n_obs * sizeof(pg_obstacle), hipMemcpyHostToDevice));
+    TubeClipArgs A; A.n_sets = n_sets; A.Lmax = Lmax; A.max_count = max_count; A.L = d_L; A.closed = d_cl; A.in = d_in; A.sets = d_sets; A.obs = d_obs; A.out = d_out; A.scratch = d_scr;
+    A.t_end = d_tend; A.stats = d_stats; A.report = d_rep;
+    hipLaunchKernelGGL(k_tube_clip, dim3((unsigned)n_traj), dim3(TC_THREADS), 0, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_clip_stats> st(n_traj);
+    std::vector<pg_obstacle_report> rp(n_rep);
+    std::vector<double> ends(n_traj);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_traj * sizeof(pg_clip_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ends.data(), d_tend, n_traj * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (report && n_rep > 0) HIPCHK(h, hipMemcpyAsync(rp.data(), d_rep, n_rep * sizeof(pg_obstacle_report), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
+    for (size_t k = 0; k < n_traj; k++) {
+        if (L_out) L_out[k] = lens[k];
+        if (closed_out) closed_out[k] = cls[k / (size_t)n_sets];
+    }
+    if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_clip_stats));
+    if (report && n_rep > 0) memcpy(report, rp.data(), n_rep * sizeof(pg_obstacle_report));
+    if (!install) return PG_OK;
+    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));      // (ends: t of the last knot as stored, what pg_set_trajectories reads from channels_out)
+}
+
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
 // solver state: nothing is reset ----
 static const char* sensor_set_problem(const pg_sensor& s) {

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -21,6 +21,8 @@ SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
 PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
 OFFSET_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_offset_stats._fields_])      # 64 bytes, the layout of pg_offset_stats
+CLIP_STATS_DTYPE = np.dtype([("width_min", np.float64), ("u_width_min", np.float64), ("reserved_d", np.float64, (2,))] + [(n, np.int32) for n in ("n_clip_L", "n_clip_R", "n_blocked", "n_centre_out", "n_seen", "n_ignored")] + [("reserved", np.int32, (2,))])      # 64 bytes, the layout of pg_clip_stats
+OBSTACLE_REPORT_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_obstacle_report._fields_])      # 64 bytes, the layout of pg_obstacle_report
 FIT_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_fit_stats._fields_])      # 80 bytes, the layout of pg_fit_stats
 
 
@@ -456,6 +458,68 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_offset_paths(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, int(bool(install)), None, None, _p(out), st),
                   "pg_offset_paths")
         return self._made_tubes(out, L, len(arr), install), np.frombuffer(st, dtype=OFFSET_STATS_DTYPE).copy()
+
+    # ---- clipping the tube (pg_clip_tubes): every (path, obstacle set) pair of a path library x a library of obstacle sets, computed on the device ----
+    @classmethod
+    def pack_obstacle_sets(cls, sets):
+        """vehicles.obstacle_set(...) dicts (one, or a list) -> (a ctypes array of pg_obstacle_set, a ctypes array of pg_obstacle): the obstacles of the sets one after the
+        other in one array, `first` / `count` of each set pointing into it.  Raises ValueError for a set outside the ranges of include/pigeon_mpc.h (the library refuses the
+        same sets with PG_ERR_INVALID)."""
+        sets = [sets] if isinstance(sets, dict) else list(sets)
+        if len(sets) < 1:
+            raise ValueError("clip_tubes: at least one obstacle set")
+        n_obs = sum(len(s["obstacles"]) for s in sets)
+        arr = (_lib.pg_obstacle_set * len(sets))()
+        obs = (_lib.pg_obstacle * max(n_obs, 1))()
+        at = 0
+        for k, s in enumerate(sets):
+            extra = set(s) - {"obstacles", "margin", "taper", "min_width", "policy"}
+            if extra:
+                raise ValueError(f"clip_tubes: set {k} has fields an obstacle set does not have: {sorted(extra)}")
+            full = _default_obstacle_set(**s)
+            margin, taper, min_width, policy = full["margin"], full["taper"], full["min_width"], full["policy"]
+            if len(full["obstacles"]) > 64:
+                raise ValueError(f"clip_tubes: set {k} has {len(full['obstacles'])} obstacles (at most 64)")
+            if not (math.isfinite(margin) and margin >= 0.0):
+                raise ValueError(f"clip_tubes: margin of set {k} is not finite and >= 0")
+            if not taper > 0.0:
+                raise ValueError(f"clip_tubes: taper of set {k} is not > 0 (+Inf: no taper)")
+            if not (math.isfinite(min_width) and min_width >= 0.0):
+                raise ValueError(f"clip_tubes: min_width of set {k} is not finite and >= 0")
+            if policy not in (0, 1, 2, 3):
+                raise ValueError(f"clip_tubes: policy of set {k} is outside 0 .. 3")
+            arr[k].first, arr[k].count, arr[k].margin, arr[k].taper, arr[k].min_width, arr[k].policy = at, len(full["obstacles"]), margin, taper, min_width, policy
+            for o in full["obstacles"]:
+                E, N, radius, reserved = float(o["E"]), float(o["N"]), float(o["radius"]), float(o.get("reserved", 0.0))
+                if not (math.isfinite(E) and math.isfinite(N) and math.isfinite(radius)):
+                    raise ValueError(f"clip_tubes: E, N or radius of an obstacle of set {k} is not finite")
+                if radius < 0.0 or not radius + margin > 0.0:
+                    raise ValueError(f"clip_tubes: an obstacle of set {k} needs radius >= 0 and radius + margin > 0")
+                if reserved != 0.0:
+                    raise ValueError(f"clip_tubes: reserved of an obstacle of set {k} must be 0")
+                obs[at].E, obs[at].N, obs[at].radius = E, N, radius
+                at += 1
+        return arr, obs, n_obs
+
+    def clip_tubes(self, paths, sets, closed=None, install=False):
+        """The tubes of a path library narrowed around obstacle sets, on the device (pg_clip_tubes; the scheme is stated in include/pigeon_mpc.h): paths = TrajectoryTubes or
+        the channel array, sets = vehicles.obstacle_set([vehicles.obstacle(E, N, radius) or vehicles.obstacle_at(path, u, e, radius), ...], margin=, taper=, min_width=,
+        policy=) dicts, closed = None / one flag / one per path.  Only edge_L and edge_R change; whatever reads them (walls, first_exit, make_starts' e_frac, offset_paths'
+        n_outside) then sees the obstacles.  Returns (tubes, stats, reports): the n_path * n_sets TrajectoryTubes in the order k = path * n_sets + set, a structured array
+        with the fields of pg_clip_stats, and a structured array [n_path * n_sets][max_count] with the fields of pg_obstacle_report (slot j: obstacle j of the pair's set;
+        vehicles.pass_by_around turns a record into the pass-by that goes round it).  install=True makes the tubes the handle's trajectory library (as set_trajectories(tubes)
+        would, without the host round trip)."""
+        L, ch, cl = self.pack_paths(paths, closed)
+        arr, obs, n_obs = self.pack_obstacle_sets(sets)
+        n_traj = len(L) * len(arr)
+        max_count = max(s.count for s in arr)
+        out = np.zeros((n_traj, 10, ch.shape[2]))
+        st = (_lib.pg_clip_stats * n_traj)()
+        rp = (_lib.pg_obstacle_report * max(n_traj * max_count, 1))()
+        self._chk(self.lib.pg_clip_tubes(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, n_obs, obs, int(bool(install)), None, None, _p(out),
+                                         st, rp), "pg_clip_tubes")
+        reports = np.frombuffer(rp, dtype=OBSTACLE_REPORT_DTYPE)[:n_traj * max_count].reshape(n_traj, max_count).copy()
+        return self._made_tubes(out, L, len(arr), install), np.frombuffer(st, dtype=CLIP_STATS_DTYPE).copy(), reports
 
     # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
     @classmethod

@@ -223,6 +223,69 @@ def pass_by(d, s_a, s_b, s_c, s_d, **overrides):
     return offset(d0=0.0, d1=d, s_a=s_a, s_b=s_b, s_c=s_c, s_d=s_d, **overrides)
 
 
+PASS_POLICIES = {"centre": 0, "wider": 1, "left": 2, "right": 3}
+
+
+def obstacle(E, N, radius):
+    """One disc in the world frame for clip_tubes (pg_obstacle)."""
+    return dict(E=float(E), N=float(N), radius=float(radius), reserved=0.0)
+
+
+def obstacle_set(obstacles=(), margin=0.0, taper=math.inf, min_width=0.0, policy="centre"):
+    """One obstacle set for clip_tubes (pg_obstacle_set): a list of obstacle(...) dicts, the margin added to every radius (half the car's width plus clearance), the taper
+    (metres of edge per metre of arc length by which a clip may relax; +Inf: the hard clip only), the width below which a knot counts as blocked, and the side policy:
+    "centre" (an obstacle left of the centre line is passed on the right), "wider" (pass where more room is left), "left" / "right" (always pass on that side), or 0 .. 3.
+    obstacle_set() is the library's default (pg_default_obstacle_set), the identity.  Build-defined: the reference has no obstacles."""
+    p = PASS_POLICIES[policy] if isinstance(policy, str) else int(policy)
+    return dict(obstacles=[dict(o) for o in obstacles], margin=float(margin), taper=float(taper), min_width=float(min_width), policy=p)
+
+
+def _path_rows(path):
+    """(s, E, N, psi, edge_L, edge_R) of a TrajectoryTube or of a channel array [10][L]"""
+    if hasattr(path, "edge_L"):
+        return path.s, path.E, path.N, path.psi, path.edge_L, path.edge_R
+    return path[1], path[4], path[5], path[6], path[8], path[9]
+
+
+def obstacle_at(channels, u, e, radius):
+    """A disc beside a path, on the host: at the arc length u from the path's first knot and e metres to the left of it (the frame of make_starts: the left normal is
+    (-cos psi, -sin psi)); E, N and psi are taken linear between the two knots around u.  channels: a TrajectoryTube or the channel array [10][L] of one path."""
+    s, E, N, psi, _, _ = _path_rows(channels)
+    n = len(s)
+    x = float(s[0]) + float(u)
+    i = 0
+    while i < n - 2 and float(s[i + 1]) <= x:
+        i += 1
+    w = (x - float(s[i])) / (float(s[i + 1]) - float(s[i]))
+    lin = lambda c: float(c[i]) + w * (float(c[i + 1]) - float(c[i]))
+    p = lin(psi)
+    return obstacle(lin(E) - float(e) * math.cos(p), lin(N) - float(e) * math.sin(p), radius)
+
+
+def pass_by_around(report_row, edges_at, ramp, x_min=0.1):
+    """The pass-by that goes round one obstacle of clip_tubes: report_row is the obstacle's record of the reports (the fields of pg_obstacle_report), edges_at the SOURCE
+    path the tube was clipped from (a TrajectoryTube or its channel array [10][L]: its edges are read at k_at, its arc length at k_first and k_last).  The plateau lies in
+    the middle of what the disc leaves on the side it is passed on: side = +1 (the left edge was clipped) gives d1 = 0.5 ((a_at - h_at) + edge_R), side = -1 gives
+    d1 = 0.5 ((a_at + h_at) + edge_L); the rise ends at u(k_first), the fall starts at u(k_last), each over `ramp` metres.  side = 0 (no knot sees the obstacle) returns
+    the identity set.  Raises ValueError where the free side is narrower than 0.  Returns a pass_by(...) set for offset_paths."""
+    r = report_row
+    side = int(r["side"])
+    if side == 0:
+        return offset(x_min=x_min)
+    s, _, _, _, eL, eR = _path_rows(edges_at)
+    k = int(r["k_at"])
+    a, h = float(r["a_at"]), float(r["h_at"])
+    if side > 0:
+        lo, hi = float(eR[k]), a - h
+    else:
+        lo, hi = a + h, float(eL[k])
+    if hi - lo < 0.0:
+        raise ValueError(f"pass_by_around: the obstacle leaves {hi - lo:.3f} m on the side it is passed on (knot {k})")
+    u1 = float(s[int(r["k_first"])]) - float(s[0])
+    u2 = float(s[int(r["k_last"])]) - float(s[0])
+    return pass_by(0.5 * (hi + lo), u1 - float(ramp), u1, u2, u2 + float(ramp), x_min=x_min)
+
+
 START_RANGES = ("s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v")
 START_MODES = ("s_mode", "e_mode", "steady", "time_mode", "other_mode")
 
