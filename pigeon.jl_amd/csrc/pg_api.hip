@@ -324,6 +324,8 @@ static int down(pg_handle* h, double* dst, const real* src, size_t n) {         
 #endif
     return PG_OK;
 }
+// `count` elements of a host array to a buffer of the same element type, under HIPCHK.  A plain synchronous copy: the host array is consumed when it returns, on every way out
+template <class T> static hipError_t to_device(T* dst, const T* src, size_t count) { return hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice); }
 static int down_raw(pg_handle* h, void* dst, const void* src, size_t bytes) {      // integer / time buffers: same type on both sides
     if (!dst) return PG_OK;
     HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -852,8 +854,8 @@ static int response_call(pg_handle* h, const char* who_, const SetLib<Host, Dev>
 }
 extern "C" {
 
-// The ONE routine that replaces the handle's trajectory library (pg_set_trajectory / pg_set_trajectories after their upload, pg_plan_speeds and pg_make_paths after their
-// kernels).  The rule: h->d_traj [n_traj][10][Lmax] and h->d_traj_len [n_traj] are device memory the handle owns, and h->dc.traj / traj_len / n_traj / traj_stride
+// The ONE routine that replaces the handle's trajectory library (install_trajectories for pg_set_trajectory / pg_set_trajectories after their upload, finish_library for
+// the five makers -- pg_plan_speeds, pg_make_paths, pg_fit_paths, pg_offset_paths, pg_clip_tubes -- after their kernels).  The rule: h->d_traj [n_traj][10][Lmax] and h->d_traj_len [n_traj] are device memory the handle owns, and h->dc.traj / traj_len / n_traj / traj_stride
 // describe exactly that pair.  The caller hands in a FINISHED library held by its CallBufs, with trajectory.t[end] of every trajectory in fp64; no call touches the
 // handle's library before this point, so one that fails earlier leaves it whole.  In this order: wait for the stream (a launch still queued reads the old pair), free
 // the old pair and take the new one (HandleBufs::adopt; the caller's pointers are nulled), fill the view, drop the index
@@ -880,10 +882,58 @@ static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_
     HIPCHK(h, D.alloc(traj, (size_t)n_traj * stride));
     { int rc = up(h, traj, channels, (size_t)n_traj * stride); if (rc) return rc; }
     HIPCHK(h, D.alloc(len, (size_t)n_traj));
-    HIPCHK(h, hipMemcpy(len, L, (size_t)n_traj * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, to_device(len, L, (size_t)n_traj));
     std::vector<double> ends((size_t)n_traj);
     for (int k = 0; k < n_traj; k++) ends[(size_t)k] = channels[(size_t)k * stride + (size_t)L[k] - 1];
     return replace_trajectories(h, D, traj, len, n_traj, Lmax, L[0], std::move(ends));
+}
+
+// ---- what the five makers of a trajectory library share on the host (pg_plan_speeds, pg_make_paths, pg_fit_paths, pg_offset_paths, pg_clip_tubes below) ----
+// One path of a source library (the three pair makers): L valid knots of Lmax, c = its channels [10][Lmax].  What is wrong with it (nullptr: nothing), tested in this
+// order.  t, V and A are not geometry: each maker says after this what it needs of them
+static const char* source_path_problem(int L, int Lmax, bool closed, const double* c) {
+    if (!(L >= 2 && L <= Lmax)) return "every path needs 2 <= L[k] <= Lmax";
+    if (closed && L < 3) return "a closed path needs >= 3 knots";
+    for (int ch = 0; ch < 10; ch++) {
+        if (ch == CH_T || ch == CH_V || ch == CH_A) continue;
+        for (int i = 0; i < L; i++) if (!std::isfinite(c[(size_t)ch * Lmax + i])) return "a geometry value of a valid knot is not finite";
+    }
+    const double* s = c + (size_t)CH_S * Lmax;
+    for (int i = 1; i < L; i++) if (!((real)s[i] > (real)s[i - 1])) return "s must increase strictly over the valid knots";      // (as the library's element type holds s)
+    return nullptr;
+}
+// A pair is one (path, set) combination of a pair maker, numbered path * n_sets + set.  Its number has to fit an int, and the largest buffer of the call, n_path * n_sets *
+// 10 * Lmax elements, has a size in bytes that has to fit the size arithmetic with room for the sums around it
+static const char* pair_count_problem(int n_path, int n_sets, int Lmax) {
+    if (!((double)n_path * (double)n_sets <= 2147483647.0)) return "n_path * n_sets must fit 31 bits";
+    if (!((double)n_path * (double)n_sets * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0)) return "n_path * n_sets * 10 * Lmax elements are more than the allocation arithmetic holds";
+    return nullptr;
+}
+// lens[pair] = L[path] of every pair, cls[path] = closed[path] (no array: every path is open)
+static void pair_vectors(int n_path, int n_sets, const int32_t* L, const int32_t* closed, std::vector<int>& lens, std::vector<int>& cls) {
+    lens.resize((size_t)n_path * n_sets); cls.resize((size_t)n_path);
+    for (size_t k = 0; k < lens.size(); k++) lens[k] = L[k / (size_t)n_sets];
+    for (int k = 0; k < n_path; k++) cls[(size_t)k] = closed ? closed[k] : 0;
+}
+// a turn reduced to (-pi, pi]: the IEEE remainder is exact
+static double turn_in_pi(double turn) {
+    const double pi = 3.141592653589793, two_pi = 6.283185307179586;
+    const double r = std::remainder(turn, two_pi);
+    return r <= -pi ? r + two_pi : r;
+}
+// The end of every maker's call, after its one hipStreamSynchronize: the finished library d_out [lens.size()][10][Lmax] goes to the caller -- channels_out, L_out and
+// closed_out, each where given; cls holds one flag per n_sets trajectories (a spec maker: n_sets = 1) -- and, with install, to the handle together with d_len.
+// ends, read with install only: t of the last knot of every trajectory as stored, as a double (what pg_set_trajectories reads from channels_out)
+static int finish_library(pg_handle* h, CallBufs& D, real*& d_out, int*& d_len, const std::vector<int>& lens, const std::vector<int>& cls, int n_sets, int Lmax,
+                          int install, int32_t* L_out, int32_t* closed_out, double* channels_out, std::vector<double>&& ends) {
+    const size_t n_traj = lens.size();
+    { int rc = down(h, channels_out, d_out, n_traj * 10 * (size_t)Lmax); if (rc) return rc; }
+    for (size_t k = 0; k < n_traj; k++) {
+        if (L_out) L_out[k] = lens[k];
+        if (closed_out) closed_out[k] = cls[k / (size_t)n_sets];
+    }
+    if (!install) return PG_OK;
+    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, lens[0], std::move(ends));
 }
 
 int pg_set_trajectory(pg_handle* h, int32_t L, const double* t, const double* s, const double* V, const double* A, const double* E, const double* N,
@@ -1053,17 +1103,11 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
     const size_t stride = (size_t)10 * Lmax;
     std::vector<int> i0((size_t)n_path, -1);
     for (int k = 0; k < n_path; k++) {
-        REQUIRE(h, L[k] >= 2 && L[k] <= Lmax, "pg_plan_speeds: every path needs 2 <= L[k] <= Lmax");
         const bool cl = closed && closed[k] != 0;
-        REQUIRE(h, !cl || L[k] >= 3, "pg_plan_speeds: a closed path needs >= 3 knots");
         const double* c = channels_in + (size_t)k * stride;
-        for (int ch = 0; ch < 10; ch++) {
-            if (ch == SP_T || ch == SP_V || ch == SP_A) continue;
-            for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(c[(size_t)ch * Lmax + i]), "pg_plan_speeds: a geometry value of a valid knot is not finite");
-        }
-        const double* s = c + (size_t)SP_S * Lmax; const double* kap = c + (size_t)SP_KAPPA * Lmax;
-        for (int i = 1; i < L[k]; i++) REQUIRE(h, (real)s[i] > (real)s[i - 1], "pg_plan_speeds: s must increase strictly over the valid knots");
+        REQUIRE_NO(h, "pg_plan_speeds: ", source_path_problem(L[k], Lmax, cl, c));
         if (cl) {                                          // i0: the first knot of largest |kappa| among knots 0 .. L-2, as the library's element type holds them
+            const double* kap = c + (size_t)CH_KAPPA * Lmax;
             int best = 0;
             for (int i = 1; i < L[k] - 1; i++) if (fabs((real)kap[i]) > fabs((real)kap[best])) best = i;
             i0[(size_t)k] = best;
@@ -1078,8 +1122,8 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
     const size_t n_traj = (size_t)n_path * n_sets, total = n_traj * stride;
     std::vector<SpeedSet> recs((size_t)n_sets);
     for (int j = 0; j < n_sets; j++) fill_speed_set(recs[(size_t)j], sets[j], vehicles ? vehicles[j] : h->cfg.vehicle);
-    std::vector<int> lens(n_traj);
-    for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
+    std::vector<int> lens, cls;
+    pair_vectors(n_path, n_sets, L, closed, lens, cls);
     CallBufs D; real *d_in = nullptr, *d_out = nullptr; int *d_L = nullptr, *d_i0 = nullptr, *d_len = nullptr; SpeedSet* d_sets = nullptr; pg_speed_plan_stats* d_stats = nullptr;
     HIPCHK(h, D.alloc(d_in, (size_t)n_path * stride));
     HIPCHK(h, D.alloc(d_out, total));
@@ -1089,11 +1133,10 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
     HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
     HIPCHK(h, D.alloc(d_stats, n_traj));
     { int rc = up(h, d_in, channels_in, (size_t)n_path * stride); if (rc) return rc; }
-    // (plain copies, as install_trajectories uses: the host vectors are consumed when each returns, on every way out)
-    HIPCHK(h, hipMemcpy(d_L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_i0, i0.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_sets, recs.data(), (size_t)n_sets * sizeof(SpeedSet), hipMemcpyHostToDevice));
+    HIPCHK(h, to_device(d_L, L, (size_t)n_path));
+    HIPCHK(h, to_device(d_i0, i0.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_len, lens.data(), n_traj));
+    HIPCHK(h, to_device(d_sets, recs.data(), (size_t)n_sets));
     SpeedPlanArgs A; A.n_path = n_path; A.n_sets = n_sets; A.Lmax = Lmax; A.spw = speed_plan_spw(h, n_path, n_sets); A.L = d_L; A.i0 = d_i0; A.in = d_in; A.sets = d_sets; A.out = d_out; A.stats = d_stats;
     hipLaunchKernelGGL(k_speed_plan_copy, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, A, total);
     LAUNCH_CHECK(h);
@@ -1103,12 +1146,10 @@ int pg_plan_speeds(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L,
     std::vector<pg_speed_plan_stats> st(n_traj);
     HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_traj * sizeof(pg_speed_plan_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the host arrays have been consumed, the kernels have run)
-    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
     if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_speed_plan_stats));
-    if (!install) return PG_OK;
-    std::vector<double> ends(n_traj);
-    for (size_t k = 0; k < n_traj; k++) ends[k] = st[k].t_end;      // (the rounded t of the last knot, as a double: what pg_set_trajectories reads from channels_out)
-    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));
+    std::vector<double> ends(install ? n_traj : 0);
+    for (size_t k = 0; k < ends.size(); k++) ends[k] = st[k].t_end;      // (the rounded t of the last knot, as a double)
+    return finish_library(h, D, d_out, d_len, lens, cls, n_sets, Lmax, install, nullptr, nullptr, channels_out, std::move(ends));
 }
 
 // ---- pg_make_paths: a path library from line, arc and clothoid segments (pg_path_make.hip).  One launch, one workgroup per path; no loop on the host ----
@@ -1200,30 +1241,20 @@ int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32
     HIPCHK(h, D.alloc(d_segs, n_rows));
     HIPCHK(h, D.alloc(d_scratch, (size_t)n_path * 2 * (size_t)Lmax));
     HIPCHK(h, D.alloc(d_stats, (size_t)n_path));
-    // (plain copies, as install_trajectories uses: the host vectors are consumed when each returns, on every way out)
-    HIPCHK(h, hipMemcpy(d_len, lens.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_specs, recs.data(), (size_t)n_path * sizeof(PathSpec), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_segs, rows.data(), n_rows * sizeof(PathSeg), hipMemcpyHostToDevice));
+    HIPCHK(h, to_device(d_len, lens.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_specs, recs.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_segs, rows.data(), n_rows));
     PathMakeArgs A; A.Lmax = Lmax; A.specs = d_specs; A.segs = d_segs; A.out = d_out; A.scratch = d_scratch; A.stats = d_stats;
     hipLaunchKernelGGL(k_path_make, dim3((unsigned)n_path), dim3(PM_THREADS), 0, h->stream, A);
     LAUNCH_CHECK(h);
     std::vector<pg_path_stats> st((size_t)n_path);
     HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, (size_t)n_path * sizeof(pg_path_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
-    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
-    const double pi = 3.141592653589793, two_pi = 6.283185307179586;
-    for (int k = 0; k < n_path; k++) {                        // the turn reduced to (-pi, pi]: the IEEE remainder is exact
-        double r = std::remainder(st[(size_t)k].turn, two_pi);
-        if (r <= -pi) r = r + two_pi;
-        st[(size_t)k].closure_psi = r;
-        if (L_out) L_out[k] = specs[k].n_knots;
-        if (closed_out) closed_out[k] = specs[k].closed;
-    }
+    std::vector<int> cls((size_t)n_path); std::vector<double> ends(install ? (size_t)n_path : 0);
+    for (size_t k = 0; k < cls.size(); k++) { st[k].closure_psi = turn_in_pi(st[k].turn); cls[k] = specs[k].closed; }
+    for (size_t k = 0; k < ends.size(); k++) ends[k] = (double)(real)(recs[k].total / recs[k].V_ref);
     if (stats) memcpy(stats, st.data(), (size_t)n_path * sizeof(pg_path_stats));
-    if (!install) return PG_OK;
-    std::vector<double> ends((size_t)n_path);
-    for (int k = 0; k < n_path; k++) ends[(size_t)k] = (double)(real)(recs[(size_t)k].total / recs[(size_t)k].V_ref);   // (t of the last knot as stored: what pg_set_trajectories reads from channels_out)
-    return replace_trajectories(h, D, d_out, d_len, n_path, Lmax, lens[0], std::move(ends));
+    return finish_library(h, D, d_out, d_len, lens, cls, 1, Lmax, install, L_out, closed_out, channels_out, std::move(ends));
 }
 
 // ---- pg_fit_paths: a path library fitted to waypoints (pg_path_fit.hip).  One launch, one workgroup per path; no loop on the host ----
@@ -1297,31 +1328,20 @@ int pg_fit_paths(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t
     HIPCHK(h, D.alloc(d_raw, n_knot_slots));
     HIPCHK(h, D.alloc(d_runk, n_knot_slots));
     HIPCHK(h, D.alloc(d_stats, (size_t)n_path));
-    // (plain copies, as install_trajectories uses: the host arrays are consumed when each returns, on every way out.  Waypoints no path refers to travel with the rest
-    // and are read by no thread)
-    HIPCHK(h, hipMemcpy(d_len, lens.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_specs, recs.data(), (size_t)n_path * sizeof(FitSpec), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_wps, waypoints, (size_t)n_wp_total * sizeof(pg_waypoint), hipMemcpyHostToDevice));
+    HIPCHK(h, to_device(d_len, lens.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_specs, recs.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_wps, waypoints, (size_t)n_wp_total));      // (waypoints no path refers to travel with the rest and are read by no thread)
     PathFitArgs A; A.Lmax = Lmax; A.specs = d_specs; A.wps = d_wps; A.out = d_out; A.span = d_span; A.psi_raw = d_raw; A.runk = d_runk; A.stats = d_stats;
     hipLaunchKernelGGL(k_path_fit, dim3((unsigned)n_path), dim3(PF_THREADS), 0, h->stream, A);
     LAUNCH_CHECK(h);
     std::vector<pg_fit_stats> st((size_t)n_path);
     HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, (size_t)n_path * sizeof(pg_fit_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
-    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
-    const double pi = 3.141592653589793, two_pi = 6.283185307179586;
-    for (int k = 0; k < n_path; k++) {                        // the turn reduced to (-pi, pi]: the IEEE remainder is exact
-        double r = std::remainder(st[(size_t)k].turn, two_pi);
-        if (r <= -pi) r = r + two_pi;
-        st[(size_t)k].closure_psi = r;
-        if (L_out) L_out[k] = specs[k].n_knots;
-        if (closed_out) closed_out[k] = specs[k].closed;
-    }
+    std::vector<int> cls((size_t)n_path); std::vector<double> ends(install ? (size_t)n_path : 0);
+    for (size_t k = 0; k < cls.size(); k++) { st[k].closure_psi = turn_in_pi(st[k].turn); cls[k] = specs[k].closed; }
+    for (size_t k = 0; k < ends.size(); k++) ends[k] = (double)(real)(st[k].length / recs[k].V_ref);
     if (stats) memcpy(stats, st.data(), (size_t)n_path * sizeof(pg_fit_stats));
-    if (!install) return PG_OK;
-    std::vector<double> ends((size_t)n_path);
-    for (int k = 0; k < n_path; k++) ends[(size_t)k] = (double)(real)(st[(size_t)k].length / recs[(size_t)k].V_ref);   // (t of the last knot as stored: what pg_set_trajectories reads from channels_out)
-    return replace_trajectories(h, D, d_out, d_len, n_path, Lmax, lens[0], std::move(ends));
+    return finish_library(h, D, d_out, d_len, lens, cls, 1, Lmax, install, L_out, closed_out, channels_out, std::move(ends));
 }
 
 // ---- pg_offset_paths: every (path, offset set) pair of a path library x a library of offset sets (pg_path_offset.hip).  One launch, one workgroup per pair ----
@@ -1351,30 +1371,20 @@ int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
     if (!h) return PG_ERR_INVALID;
     REQUIRE(h, L && channels_in && sets, "pg_offset_paths: null argument");
     REQUIRE(h, n_path >= 1 && n_sets >= 1 && Lmax >= 2, "pg_offset_paths: need n_path >= 1, n_sets >= 1 and Lmax >= 2");
-    REQUIRE(h, (double)n_path * (double)n_sets <= 2147483647.0, "pg_offset_paths: n_path * n_sets must fit 31 bits");
-    // (the largest buffer of the call holds n_path * n_sets * 10 * Lmax elements: its size in bytes has to fit the size arithmetic, with room for the sums around it)
-    REQUIRE(h, (double)n_path * (double)n_sets * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0,
-            "pg_offset_paths: n_path * n_sets * 10 * Lmax elements are more than the allocation arithmetic holds");
+    REQUIRE_NO(h, "pg_offset_paths: ", pair_count_problem(n_path, n_sets, Lmax));
     const size_t stride = (size_t)10 * Lmax;
     for (int k = 0; k < n_path; k++) {
-        REQUIRE(h, L[k] >= 2 && L[k] <= Lmax, "pg_offset_paths: every path needs 2 <= L[k] <= Lmax");
-        const bool cl = closed && closed[k] != 0;
-        REQUIRE(h, !cl || L[k] >= 3, "pg_offset_paths: a closed path needs >= 3 knots");
         const double* c = channels_in + (size_t)k * stride;
-        for (int ch = 0; ch < 10; ch++) {
-            if (ch == PO_T || ch == PO_V || ch == PO_A) continue;
-            for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(c[(size_t)ch * Lmax + i]), "pg_offset_paths: a geometry value of a valid knot is not finite");
-        }
-        const double* s = c + (size_t)PO_S * Lmax; const double* V = c + (size_t)PO_V * Lmax;
-        for (int i = 1; i < L[k]; i++) REQUIRE(h, (real)s[i] > (real)s[i - 1], "pg_offset_paths: s must increase strictly over the valid knots");
+        REQUIRE_NO(h, "pg_offset_paths: ", source_path_problem(L[k], Lmax, closed && closed[k] != 0, c));
+        const double* V = c + (size_t)CH_V * Lmax;
         for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(V[i]) && V[i] > 0.0, "pg_offset_paths: V of a valid knot is not finite and > 0");
-        REQUIRE(h, std::isfinite(c[(size_t)PO_T * Lmax]), "pg_offset_paths: t of the first knot is not finite");
+        REQUIRE(h, std::isfinite(c[(size_t)CH_T * Lmax]), "pg_offset_paths: t of the first knot is not finite");
     }
     for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_offset_paths: ", offset_set_problem(sets[j]));
     // the pairs: x = 1 - kappa_i d_i at every valid knot, in the kernel's own arithmetic (po_offset is one function for host and device); the ends of a closed path
     for (int k = 0; k < n_path; k++) {
         const double* c = channels_in + (size_t)k * stride;
-        const double* s = c + (size_t)PO_S * Lmax; const double* kap = c + (size_t)PO_KAPPA * Lmax;
+        const double* s = c + (size_t)CH_S * Lmax; const double* kap = c + (size_t)CH_KAPPA * Lmax;
         const bool cl = closed && closed[k] != 0;
         for (int j = 0; j < n_sets; j++) {
             const pg_offset_set& S = sets[j];
@@ -1402,9 +1412,8 @@ int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
     HIPCHK(h, hipSetDevice(h->cfg.device));
 
     const size_t n_traj = (size_t)n_path * n_sets, total = n_traj * stride, n_in = (size_t)n_path * stride;
-    std::vector<int> lens(n_traj), cls((size_t)n_path);
-    for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
-    for (int k = 0; k < n_path; k++) cls[(size_t)k] = closed ? closed[k] : 0;
+    std::vector<int> lens, cls;
+    pair_vectors(n_path, n_sets, L, closed, lens, cls);
     CallBufs D; double *d_in = nullptr, *d_sp = nullptr, *d_run = nullptr, *d_tend = nullptr; real* d_out = nullptr; int *d_L = nullptr, *d_cl = nullptr, *d_len = nullptr, *d_bad = nullptr;
     pg_offset_set* d_sets = nullptr; pg_offset_stats* d_stats = nullptr;
     HIPCHK(h, D.alloc(d_in, n_in));
@@ -1418,12 +1427,11 @@ int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
     HIPCHK(h, D.alloc(d_bad, n_traj));
     HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
     HIPCHK(h, D.alloc(d_stats, n_traj));
-    // (plain copies, as install_trajectories uses: the host arrays are consumed when each returns, on every way out.  The source travels as the doubles given)
-    HIPCHK(h, hipMemcpy(d_in, channels_in, n_in * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_cl, cls.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_sets, sets, (size_t)n_sets * sizeof(pg_offset_set), hipMemcpyHostToDevice));
+    HIPCHK(h, to_device(d_in, channels_in, n_in));            // (the source travels as the doubles given)
+    HIPCHK(h, to_device(d_L, L, (size_t)n_path));
+    HIPCHK(h, to_device(d_cl, cls.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_len, lens.data(), n_traj));
+    HIPCHK(h, to_device(d_sets, sets, (size_t)n_sets));
     PathOffsetArgs A; A.n_sets = n_sets; A.Lmax = Lmax; A.L = d_L; A.closed = d_cl; A.in = d_in; A.sets = d_sets; A.out = d_out; A.sp = d_sp; A.run = d_run; A.t_end = d_tend; A.stats = d_stats; A.bad = d_bad;
     hipLaunchKernelGGL(k_path_offset, dim3((unsigned)n_traj), dim3(PO_THREADS), 0, h->stream, A);
     LAUNCH_CHECK(h);
@@ -1439,14 +1447,8 @@ int pg_offset_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
                  ": the offset knots are so dense that s does not increase strictly in the library's element type (ds_min " + std::to_string(st[k].ds_min) + ")";
         return PG_ERR_INVALID;
     }
-    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
-    for (size_t k = 0; k < n_traj; k++) {
-        if (L_out) L_out[k] = lens[k];
-        if (closed_out) closed_out[k] = cls[k / (size_t)n_sets];
-    }
     if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_offset_stats));
-    if (!install) return PG_OK;
-    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));      // (ends: t of the last knot as stored, what pg_set_trajectories reads from channels_out)
+    return finish_library(h, D, d_out, d_len, lens, cls, n_sets, Lmax, install, L_out, closed_out, channels_out, std::move(ends));
 }
 
 // ---- pg_clip_tubes: every (path, obstacle set) pair of a path library x a library of obstacle sets (pg_tube_clip.hip).  One launch, one workgroup per pair ----
@@ -1481,23 +1483,9 @@ int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, 
     REQUIRE(h, L && channels_in && sets, "pg_clip_tubes: null argument");
     REQUIRE(h, n_path >= 1 && n_sets >= 1 && Lmax >= 2, "pg_clip_tubes: need n_path >= 1, n_sets >= 1 and Lmax >= 2");
     REQUIRE(h, n_obs >= 0, "pg_clip_tubes: n_obs < 0");
-    REQUIRE(h, (double)n_path * (double)n_sets <= 2147483647.0, "pg_clip_tubes: n_path * n_sets must fit 31 bits");
-    // (the largest buffer of the call holds n_path * n_sets * 10 * Lmax elements: its size in bytes has to fit the size arithmetic, with room for the sums around it)
-    REQUIRE(h, (double)n_path * (double)n_sets * 10.0 * (double)Lmax * 8.0 < 4611686018427387904.0,
-            "pg_clip_tubes: n_path * n_sets * 10 * Lmax elements are more than the allocation arithmetic holds");
+    REQUIRE_NO(h, "pg_clip_tubes: ", pair_count_problem(n_path, n_sets, Lmax));
     const size_t stride = (size_t)10 * Lmax;
-    for (int k = 0; k < n_path; k++) {
-        REQUIRE(h, L[k] >= 2 && L[k] <= Lmax, "pg_clip_tubes: every path needs 2 <= L[k] <= Lmax");
-        const bool cl = closed && closed[k] != 0;
-        REQUIRE(h, !cl || L[k] >= 3, "pg_clip_tubes: a closed path needs >= 3 knots");
-        const double* c = channels_in + (size_t)k * stride;
-        for (int ch = 0; ch < 10; ch++) {
-            if (ch == PO_T || ch == PO_V || ch == PO_A) continue;
-            for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(c[(size_t)ch * Lmax + i]), "pg_clip_tubes: a geometry value of a valid knot is not finite");
-        }
-        const double* s = c + (size_t)PO_S * Lmax;
-        for (int i = 1; i < L[k]; i++) REQUIRE(h, (real)s[i] > (real)s[i - 1], "pg_clip_tubes: s must increase strictly over the valid knots");
-    }
+    for (int k = 0; k < n_path; k++) REQUIRE_NO(h, "pg_clip_tubes: ", source_path_problem(L[k], Lmax, closed && closed[k] != 0, channels_in + (size_t)k * stride));
     int max_count = 0;
     for (int j = 0; j < n_sets; j++) {
         REQUIRE_NO(h, "pg_clip_tubes: ", obstacle_set_problem(sets[j], n_obs, obstacles));
@@ -1506,9 +1494,8 @@ int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, 
     HIPCHK(h, hipSetDevice(h->cfg.device));
 
     const size_t n_traj = (size_t)n_path * n_sets, total = n_traj * stride, n_in = (size_t)n_path * stride, n_rep = n_traj * (size_t)max_count;
-    std::vector<int> lens(n_traj), cls((size_t)n_path);
-    for (size_t k = 0; k < n_traj; k++) lens[k] = L[k / (size_t)n_sets];
-    for (int k = 0; k < n_path; k++) cls[(size_t)k] = closed ? closed[k] : 0;
+    std::vector<int> lens, cls;
+    pair_vectors(n_path, n_sets, L, closed, lens, cls);
     CallBufs D; double *d_in = nullptr, *d_scr = nullptr, *d_tend = nullptr; real* d_out = nullptr; int *d_L = nullptr, *d_cl = nullptr, *d_len = nullptr;
     pg_obstacle_set* d_sets = nullptr; pg_obstacle* d_obs = nullptr; pg_clip_stats* d_stats = nullptr; pg_obstacle_report* d_rep = nullptr;
     HIPCHK(h, D.alloc(d_in, n_in));
@@ -1522,13 +1509,12 @@ int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, 
     HIPCHK(h, D.alloc(d_obs, (size_t)std::max(n_obs, 1)));
     HIPCHK(h, D.alloc(d_stats, n_traj));
     HIPCHK(h, D.alloc(d_rep, std::max(n_rep, (size_t)1)));
-    // (plain copies, as install_trajectories uses: the host arrays are consumed when each returns, on every way out.  The source travels as the doubles given)
-    HIPCHK(h, hipMemcpy(d_in, channels_in, n_in * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_L, L, (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_cl, cls.data(), (size_t)n_path * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_len, lens.data(), n_traj * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_sets, sets, (size_t)n_sets * sizeof(pg_obstacle_set), hipMemcpyHostToDevice));
-    if (n_obs > 0 && obstacles) HIPCHK(h, hipMemcpy(d_obs, obstacles, (size_t)n_obs * sizeof(pg_obstacle), hipMemcpyHostToDevice));
+    HIPCHK(h, to_device(d_in, channels_in, n_in));            // (the source travels as the doubles given)
+    HIPCHK(h, to_device(d_L, L, (size_t)n_path));
+    HIPCHK(h, to_device(d_cl, cls.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_len, lens.data(), n_traj));
+    HIPCHK(h, to_device(d_sets, sets, (size_t)n_sets));
+    if (n_obs > 0 && obstacles) HIPCHK(h, to_device(d_obs, obstacles, (size_t)n_obs));
     TubeClipArgs A; A.n_sets = n_sets; A.Lmax = Lmax; A.max_count = max_count; A.L = d_L; A.closed = d_cl; A.in = d_in; A.sets = d_sets; A.obs = d_obs; A.out = d_out; A.scratch = d_scr;
     A.t_end = d_tend; A.stats = d_stats; A.report = d_rep;
     hipLaunchKernelGGL(k_tube_clip, dim3((unsigned)n_traj), dim3(TC_THREADS), 0, h->stream, A);
@@ -1540,15 +1526,9 @@ int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, 
     HIPCHK(h, hipMemcpyAsync(ends.data(), d_tend, n_traj * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (report && n_rep > 0) HIPCHK(h, hipMemcpyAsync(rp.data(), d_rep, n_rep * sizeof(pg_obstacle_report), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
-    { int rc = down(h, channels_out, d_out, total); if (rc) return rc; }
-    for (size_t k = 0; k < n_traj; k++) {
-        if (L_out) L_out[k] = lens[k];
-        if (closed_out) closed_out[k] = cls[k / (size_t)n_sets];
-    }
     if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_clip_stats));
     if (report && n_rep > 0) memcpy(report, rp.data(), n_rep * sizeof(pg_obstacle_report));
-    if (!install) return PG_OK;
-    return replace_trajectories(h, D, d_out, d_len, (int)n_traj, Lmax, L[0], std::move(ends));      // (ends: t of the last knot as stored, what pg_set_trajectories reads from channels_out)
+    return finish_library(h, D, d_out, d_len, lens, cls, n_sets, Lmax, install, L_out, closed_out, channels_out, std::move(ends));
 }
 
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no

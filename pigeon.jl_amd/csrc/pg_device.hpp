@@ -524,6 +524,8 @@ PG_DEV Steady steady_state(const DevVehicle& P, real V, real A_tan, real kappa, 
 }
 
 // ---- trajectory (trajectories.jl) ----
+// the rows of one trajectory [10][Lmax] that the host names by index, in the order of TrajView's channels
+enum { CH_T = 0, CH_S = 1, CH_V = 2, CH_A = 3, CH_KAPPA = 7 };
 struct TrajView {
     int L;
     const real *t, *s, *V, *A, *E, *N, *psi, *kappa, *edge_L, *edge_R;   // theta, phi are carried by the tube but read by nothing on this path
