@@ -476,6 +476,67 @@ int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, 
                   int32_t n_sets, const pg_obstacle_set* sets, int32_t n_obs, const pg_obstacle* obstacles, int32_t install,
                   int32_t* L_out, int32_t* closed_out, double* channels_out, pg_clip_stats* stats, pg_obstacle_report* report);
 
+/* Refining the path: every (path, refine set) pair of a path library and a library of refine sets as a trajectory, computed on the device in the layout
+ * pg_set_trajectories takes -- the same path with more knots where a manoeuvre or an obstacle needs them.  pg_offset_paths and pg_clip_tubes are knot-wise ("What the
+ * knots see" above): this is the maker that chooses the knots for a library that already exists, whatever made it.  Every source knot stays a knot, with its own values,
+ * and the arc length is the source's: offset sets, obstacle reports and route events written against the source stay valid on the result.  The reference has no path
+ * maker (src/ros_integration.jl:13-16 reads files), so the scheme is build-defined (tests/path_refine_numpy.py is its numpy twin).  channels_in is read as the doubles
+ * given, ALL arithmetic is double in both libraries, every operation rounded on its own (no contraction), and a value is rounded to the library's element type once, on
+ * store: the fp32 library's output is exactly the fp64 library's rounded to float, and the stats are the same doubles.  Below, a parenthesis is one rounded operation;
+ * min, max, ceil and | | are exact.
+ *   Parts     u_i = s_i - s_first.  Source interval i = [s_i, s_{i+1}], diff = s_{i+1} - s_i.  Its wanted spacing w_i = the minimum of ds and of the ds_w of every used
+ *             window (s_lo < +Inf) that reaches into the interval's interior: s_lo < u_{i+1} and s_hi > u_i.  m_i = 1 when w_i is +Inf or diff <= w_i; else with
+ *             q = diff / w_i:  m_i = ceil(q), refused unless q <= 4096.  The interval is cut into m_i equal parts.
+ *   Offsets   o_0 = 0, o_{i+1} = o_i + m_i, L_out = o_{L-1} + 1.  The prefix is over integers: its order cannot show (on the device it is the blocked scan of
+ *             pg_make_paths (Prefix) with c = ceil((L - 1) / 256)).  Output knot o_i + k is sub-knot k of interval i, 0 <= k < m_i; output knot L_out - 1 is the last
+ *             source knot.  Sub-knot 0 of an interval and the last knot are SOURCE knots: all ten channels are copied.
+ *   Sub-knot  0 < k < m_i:  tau = (diff k) / m_i,  s = s_i + tau.  With lin(x) = x_i + (((x_{i+1} - x_i) tau) / diff):  kappa = lin(kappa), edge_L = lin(edge_L),
+ *             edge_R = lin(edge_R) -- linear inside the interval, the controller's own lookup.
+ *   Heading   b = (0.5 (kappa_{i+1} - kappa_i)) / diff,  a = ((psi_{i+1} - psi_i) / diff) - (b diff),  psi(v) = psi_i + (v (a + (v b))),  psi = psi(tau): the clothoid the two
+ *             curvatures define, tilted so that it ends on the source's psi_{i+1}.  On a pg_make_paths library a is kappa_i up to rounding; closure_psi_max reports
+ *             |a - kappa_i| diff.
+ *   Position  dE/ds = -sin psi, dN/ds = cos psi.  A piece [va, vb]: half = 0.5 (vb - va), mid = 0.5 (va + vb), the four Gauss-Legendre nodes v_q = mid + (half x_q) and
+ *             weights of pg_make_paths in ascending order;  pE = -(half sum_q (w_q sin psi(v_q))),  pN = half sum_q (w_q cos psi(v_q)), the sums from 0 in the order of
+ *             the nodes.  I(v) = piece [0, (0.5 v)] + piece [(0.5 v), v], as l_j(u) of pg_fit_paths.  The closure of the interval:  cE = (E_{i+1} - E_i) - IE(diff),
+ *             cN alike -- how far the source's own E and N are from its psi and kappa.  E = E_i + (IE(tau) + ((tau / diff) cE)),  N alike: the refined curve passes
+ *             through every source knot.
+ *   Speed     W = (V_i V_i) + ((((V_{i+1} V_{i+1}) - (V_i V_i)) tau) / diff),  V = sqrt(W),  A = A_i (constant over an interval under the Result rule of pg_plan_speeds);
+ *             t = t_i + (((t_{i+1} - t_i) ((2 tau) / (V_i + V))) / ((2 diff) / (V_i + V_{i+1}))): the Result rule on the sub-interval, scaled so that it ends on the
+ *             source's t_{i+1}.
+ *   Stats     length = s_{L-1} - s_0;  ds_min, ds_max over the differences of neighbouring output s (as doubles);  n_added = L_out - L;  m_max = the largest m_i;
+ *             closure_pos_max = the largest sqrt((cE cE) + (cN cN));  closure_psi_max = the largest (|a - kappa_i| diff);  kappa_abs_max over the output knots.
+ * L_out, t, s, V, A, psi, kappa, both edges and every stat but closure_pos_max reproduce the twin bit for bit (they carry no libm call but sqrt); E, N and
+ * closure_pos_max are within 8 * 2^-52 * (|E or N| + ds_max of the source) of it (sin, cos).  Left out: coarsening (no source knot is ever dropped), equal spacing over
+ * the whole path (the parts are equal inside a source interval only), and reading the source from the installed library (it is handed in, as to the other makers). */
+typedef struct pg_refine_set {
+    double ds;                /* the largest spacing wanted everywhere, metres: +Inf (none), or finite and > 0 */
+    double s_lo[4], s_hi[4];  /* up to 4 windows in metres of the SOURCE arclength from its first knot; s_lo = +Inf: the slot is unused.  Else s_lo finite, s_hi finite and > s_lo */
+    double ds_w[4];           /* the largest spacing wanted inside window j; finite and > 0 in a used slot.  Windows may overlap: the smallest spacing holds */
+    double reserved[3];       /* 0 */
+} pg_refine_set;              /* 128 bytes */
+typedef struct pg_refine_stats {   /* one per output trajectory; computed in double in both libraries */
+    double length, ds_min, ds_max, closure_pos_max, closure_psi_max, kappa_abs_max;
+    int32_t n_added, m_max;
+    double reserved;          /* 0 */
+} pg_refine_stats;            /* 64 bytes */
+/* { +Inf, {+Inf x 4}, {+Inf x 4}, {+Inf x 4}, {0, 0, 0} }: the identity */
+pg_refine_set pg_default_refine_set(void);
+/* channels_in [n_path][10][Lmax], L and closed are what pg_offset_paths takes (closed NULL: every path is open); V and t of the valid knots are read as well.  Output
+ * trajectory k = path * n_sets + set: channels_out [n_path * n_sets][10][Lmax_out], stats [n_path * n_sets], L_out [n_path * n_sets] (the pair's own knot count) and
+ * closed_out [n_path * n_sets] (= closed[path]; 0 where closed is NULL); each may be NULL.  Every channel is 0 at and past L_out.  install != 0 hands the device buffer to
+ * the handle, with no host round trip: the handle is then exactly as after pg_set_trajectories(h, n_path * n_sets, Lmax_out, L_out, channels_out).  Synchronous.  A handle
+ * that never calls this launches what it launched before.
+ * PG_ERR_INVALID, everything the host can decide validated before the first allocation (the handle and its installed library are left unchanged): a null L, channels_in or
+ * sets; n_path or n_sets < 1; Lmax or Lmax_out < 2; L[k] outside [2, Lmax]; a closed path of fewer than 3 knots; s that does not increase strictly over the valid knots
+ * (in the library's element type); a non-finite geometry value, a V that is not finite and > 0 or a non-finite t in a valid knot; ds that is neither +Inf nor finite and
+ * > 0; s_lo that is neither finite nor +Inf; a used window whose s_hi is not finite and > s_lo or whose ds_w is not finite and > 0; a NaN in an unused slot; reserved
+ * != 0; a (path, set) pair with an interval of more than 4096 parts (the message names path, set and interval); a pair whose L_out exceeds Lmax_out (the message names
+ * path, set, the count and Lmax_out); n_path * n_sets * 10 * max(Lmax, Lmax_out) elements beyond the allocation arithmetic.  After the launch and before any install: a
+ * pair whose s does not increase strictly in the library's element type (the fp32 library under a very fine ds_w).  A window beyond a path's end has no effect. */
+int pg_refine_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
+                    int32_t n_sets, const pg_refine_set* sets, int32_t Lmax_out, int32_t install,
+                    int32_t* L_out, int32_t* closed_out, double* channels_out, pg_refine_stats* stats);
+
 /* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
  * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car
  * (src/ros_integration.jl:48-99), so the feature is build-defined (tests/start_make_numpy.py is its numpy twin).  After pg_make_paths / pg_fit_paths / pg_plan_speeds

@@ -794,6 +794,46 @@ end
 "{ 0, 0, 0.0, Inf, 0.0, 0, 0, (0, 0, 0) } as the library states them (pg_default_obstacle_set): the identity"
 default_obstacle_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_obstacle_set), PgObstacleSet, ())
 
+# Refining the path (pg_refine_paths): knots inserted into a path library where a manoeuvre or an obstacle needs them, on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_refine_set (128 bytes): the largest spacing wanted everywhere (Inf: none), up to four windows in the source's arc length (s_lo = Inf: unused) with the largest spacing wanted inside each, three reserved zeros"
+struct PgRefineSet
+    ds::Float64
+    s_lo::NTuple{4,Float64}
+    s_hi::NTuple{4,Float64}
+    ds_w::NTuple{4,Float64}
+    reserved::NTuple{3,Float64}
+end
+"windows: up to four (s_lo, s_hi, ds_w); PgRefineSet() is the identity"
+function PgRefineSet(; ds=Inf, windows=())
+    length(windows) <= 4 || error("PgRefineSet: at most 4 windows")
+    slot(f) = ntuple(j -> j <= length(windows) ? Float64(windows[j][f]) : Inf, 4)
+    PgRefineSet(Float64(ds), slot(1), slot(2), slot(3), (0.0, 0.0, 0.0))
+end
+"pg_refine_stats (64 bytes), one per output trajectory"
+struct PgRefineStats
+    length::Float64
+    ds_min::Float64
+    ds_max::Float64
+    closure_pos_max::Float64
+    closure_psi_max::Float64
+    kappa_abs_max::Float64
+    n_added::Int32
+    m_max::Int32
+    reserved::Float64
+end
+"channels_in [Lmax, 10, n_path], L and closed as offset_paths! takes them, Lmax_out the knot capacity of the output (the library refuses a pair that needs more, naming its count) -> (channels_out [Lmax_out, 10, n_path * n_sets], L_out, closed_out, stats), trajectory k = path * n_sets + set (0-based); install = true leaves the handle as pg_set_trajectories with channels_out would"
+function refine_paths!(mpc::BatchedTrajectoryTrackingMPC, channels_in::Array{Float64,3}, L::Vector{Int32}, closed::Vector{Int32}, sets::Vector{PgRefineSet}, Lmax_out::Integer; install::Bool=false)
+    (sizeof(PgRefineSet), sizeof(PgRefineStats)) == (128, 64) || error("PigeonMI355X.jl: the pg_refine_paths structures differ from include/pigeon_mpc.h")
+    Lmax, _, n_path = size(channels_in)
+    n = n_path * length(sets)
+    out = zeros(Float64, Lmax_out, 10, n); L_out = zeros(Int32, n); closed_out = zeros(Int32, n); stats = Vector{PgRefineStats}(undef, n)
+    check(mpc, ccall(sym(mpc, :pg_refine_paths), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{PgRefineSet}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{PgRefineStats}),
+                     mpc.handle, Int32(n_path), Int32(Lmax), L, closed, channels_in, Int32(length(sets)), sets, Int32(Lmax_out), Int32(install), L_out, closed_out, out, stats), "pg_refine_paths")
+    out, L_out, closed_out, stats
+end
+"{ Inf, (Inf x 4), (Inf x 4), (Inf x 4), (0, 0, 0) } as the library states them (pg_default_refine_set): the identity"
+default_refine_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_refine_set), PgRefineSet, ())
+
 # Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
 "pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
 struct PgStartSet

@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_start_set", "pg_make_starts",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_refine_set", "pg_refine_paths", "pg_default_start_set", "pg_make_starts",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -305,6 +305,24 @@ TUBE_CLIP_PROTOTYPES = {
 }
 
 
+class pg_refine_set(C.Structure):
+    """include/pigeon_mpc.h pg_refine_set: the largest spacing wanted everywhere (+Inf: none), up to four windows in the source's arc length (s_lo = +Inf: unused) with the
+    largest spacing wanted inside each, three reserved zeros."""
+    _fields_ = [("ds", C.c_double), ("s_lo", C.c_double * 4), ("s_hi", C.c_double * 4), ("ds_w", C.c_double * 4), ("reserved", C.c_double * 3)]
+
+
+class pg_refine_stats(C.Structure):
+    """include/pigeon_mpc.h pg_refine_stats: one per output trajectory."""
+    _fields_ = [(n, C.c_double) for n in ["length", "ds_min", "ds_max", "closure_pos_max", "closure_psi_max", "kappa_abs_max"]] + [("n_added", C.c_int32), ("m_max", C.c_int32), ("reserved", C.c_double)]
+
+
+# path refiner (include/pigeon_mpc.h: pg_refine_paths)
+PATH_REFINE_PROTOTYPES = {
+    "pg_refine_paths": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.POINTER(pg_refine_set), C.c_int32, C.c_int32,
+                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(pg_refine_stats)],
+}
+
+
 START_RANGES = ["s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v"]      # the 13 channels of the draws, in their order
 START_MODES = ["s_mode", "e_mode", "steady", "time_mode", "other_mode"]
 
@@ -342,7 +360,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, START_MAKE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, PATH_REFINE_PROTOTYPES, START_MAKE_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -358,6 +376,8 @@ def load_library(precision="f64"):
     lib.pg_default_offset_set.restype = pg_offset_set
     lib.pg_default_obstacle_set.argtypes = []
     lib.pg_default_obstacle_set.restype = pg_obstacle_set
+    lib.pg_default_refine_set.argtypes = []
+    lib.pg_default_refine_set.restype = pg_refine_set
     lib.pg_default_start_set.argtypes = []
     lib.pg_default_start_set.restype = pg_start_set
     lib.pg_default_route.argtypes = []

@@ -855,7 +855,7 @@ static int response_call(pg_handle* h, const char* who_, const SetLib<Host, Dev>
 extern "C" {
 
 // The ONE routine that replaces the handle's trajectory library (install_trajectories for pg_set_trajectory / pg_set_trajectories after their upload, finish_library for
-// the five makers -- pg_plan_speeds, pg_make_paths, pg_fit_paths, pg_offset_paths, pg_clip_tubes -- after their kernels).  The rule: h->d_traj [n_traj][10][Lmax] and h->d_traj_len [n_traj] are device memory the handle owns, and h->dc.traj / traj_len / n_traj / traj_stride
+// the six makers -- pg_plan_speeds, pg_make_paths, pg_fit_paths, pg_offset_paths, pg_clip_tubes, pg_refine_paths -- after their kernels).  The rule: h->d_traj [n_traj][10][Lmax] and h->d_traj_len [n_traj] are device memory the handle owns, and h->dc.traj / traj_len / n_traj / traj_stride
 // describe exactly that pair.  The caller hands in a FINISHED library held by its CallBufs, with trajectory.t[end] of every trajectory in fp64; no call touches the
 // handle's library before this point, so one that fails earlier leaves it whole.  In this order: wait for the stream (a launch still queued reads the old pair), free
 // the old pair and take the new one (HandleBufs::adopt; the caller's pointers are nulled), fill the view, drop the index
@@ -888,8 +888,8 @@ static int install_trajectories(pg_handle* h, int n_traj, int Lmax, const int32_
     return replace_trajectories(h, D, traj, len, n_traj, Lmax, L[0], std::move(ends));
 }
 
-// ---- what the five makers of a trajectory library share on the host (pg_plan_speeds, pg_make_paths, pg_fit_paths, pg_offset_paths, pg_clip_tubes below) ----
-// One path of a source library (the three pair makers): L valid knots of Lmax, c = its channels [10][Lmax].  What is wrong with it (nullptr: nothing), tested in this
+// ---- what the six makers of a trajectory library share on the host (pg_plan_speeds, pg_make_paths, pg_fit_paths, pg_offset_paths, pg_clip_tubes, pg_refine_paths below) ----
+// One path of a source library (the four pair makers): L valid knots of Lmax, c = its channels [10][Lmax].  What is wrong with it (nullptr: nothing), tested in this
 // order.  t, V and A are not geometry: each maker says after this what it needs of them
 static const char* source_path_problem(int L, int Lmax, bool closed, const double* c) {
     if (!(L >= 2 && L <= Lmax)) return "every path needs 2 <= L[k] <= Lmax";
@@ -1529,6 +1529,109 @@ int pg_clip_tubes(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, 
     if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_clip_stats));
     if (report && n_rep > 0) memcpy(report, rp.data(), n_rep * sizeof(pg_obstacle_report));
     return finish_library(h, D, d_out, d_len, lens, cls, n_sets, Lmax, install, L_out, closed_out, channels_out, std::move(ends));
+}
+
+// ---- pg_refine_paths: every (path, refine set) pair of a path library x a library of refine sets (pg_path_refine.hip).  One launch, one workgroup per pair; the one pair
+// maker whose output has its own knot counts and its own Lmax_out ----
+static_assert(sizeof(pg_refine_set) == 128 && sizeof(pg_refine_stats) == 64, "the sizes include/pigeon_mpc.h states");
+pg_refine_set pg_default_refine_set(void) {
+    pg_refine_set s; s.ds = INFINITY;
+    for (int j = 0; j < 4; j++) { s.s_lo[j] = INFINITY; s.s_hi[j] = INFINITY; s.ds_w[j] = INFINITY; }
+    s.reserved[0] = 0.0; s.reserved[1] = 0.0; s.reserved[2] = 0.0;
+    return s;
+}
+static const char* refine_set_problem(const pg_refine_set& s) {
+    if (!(s.ds == INFINITY || (std::isfinite(s.ds) && s.ds > 0.0))) return "ds of a set is +Inf or finite and > 0";
+    for (int j = 0; j < 4; j++) {
+        const bool used = std::isfinite(s.s_lo[j]);
+        if (!(used || s.s_lo[j] == INFINITY)) return "s_lo of a window is finite or +Inf";
+        if (used && !(std::isfinite(s.s_hi[j]) && s.s_hi[j] > s.s_lo[j])) return "a window of a set needs a finite s_hi > s_lo";
+        if (used && !(std::isfinite(s.ds_w[j]) && s.ds_w[j] > 0.0)) return "a window of a set needs a finite ds_w > 0";
+        if (!used && (std::isnan(s.s_hi[j]) || std::isnan(s.ds_w[j]))) return "s_hi or ds_w of an unused window is NaN";
+    }
+    if (s.reserved[0] != 0.0 || s.reserved[1] != 0.0 || s.reserved[2] != 0.0) return "reserved of a set must be 0";
+    return nullptr;
+}
+int pg_refine_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
+                    int32_t n_sets, const pg_refine_set* sets, int32_t Lmax_out, int32_t install,
+                    int32_t* L_out, int32_t* closed_out, double* channels_out, pg_refine_stats* stats) {
+#pragma clang fp contract(off)
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, L && channels_in && sets, "pg_refine_paths: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && Lmax >= 2, "pg_refine_paths: need n_path >= 1, n_sets >= 1 and Lmax >= 2");
+    REQUIRE(h, Lmax_out >= 2, "pg_refine_paths: need Lmax_out >= 2");
+    REQUIRE_NO(h, "pg_refine_paths: ", pair_count_problem(n_path, n_sets, std::max(Lmax, Lmax_out)));
+    const size_t stride = (size_t)10 * Lmax, stride_out = (size_t)10 * Lmax_out;
+    for (int k = 0; k < n_path; k++) {
+        const double* c = channels_in + (size_t)k * stride;
+        REQUIRE_NO(h, "pg_refine_paths: ", source_path_problem(L[k], Lmax, closed && closed[k] != 0, c));
+        const double* V = c + (size_t)CH_V * Lmax; const double* t = c + (size_t)CH_T * Lmax;
+        for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(V[i]) && V[i] > 0.0, "pg_refine_paths: V of a valid knot is not finite and > 0");
+        for (int i = 0; i < L[k]; i++) REQUIRE(h, std::isfinite(t[i]), "pg_refine_paths: t of a valid knot is not finite");
+    }
+    for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_refine_paths: ", refine_set_problem(sets[j]));
+    // the pairs: L_out = 1 + sum of m_i in the kernel's own arithmetic (rf_parts is one function for host and device)
+    const size_t n_traj = (size_t)n_path * n_sets;
+    std::vector<int> lens, cls;
+    pair_vectors(n_path, n_sets, L, closed, lens, cls);
+    for (int k = 0; k < n_path; k++) {
+        const double* s = channels_in + (size_t)k * stride + (size_t)CH_S * Lmax;
+        for (int j = 0; j < n_sets; j++) {
+            long long count = 1;
+            for (int i = 0; i + 1 < L[k]; i++) {
+                const int m = rf_parts(sets[j], s[i + 1] - s[i], s[i] - s[0], s[i + 1] - s[0]);
+                if (m > RF_M_MAX) {
+                    h->err = "pg_refine_paths: path " + std::to_string(k) + ", set " + std::to_string(j) + ", interval " + std::to_string(i) + " would be cut into more than " +
+                             std::to_string((int)RF_M_MAX) + " parts";
+                    return PG_ERR_INVALID;
+                }
+                count += m;
+            }
+            if (count > (long long)Lmax_out) {
+                h->err = "pg_refine_paths: path " + std::to_string(k) + ", set " + std::to_string(j) + " has " + std::to_string(count) + " knots, more than Lmax_out = " +
+                         std::to_string(Lmax_out);
+                return PG_ERR_INVALID;
+            }
+            lens[(size_t)k * n_sets + j] = (int)count;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t total = n_traj * stride_out, n_in = (size_t)n_path * stride;
+    CallBufs D; double *d_in = nullptr, *d_clos = nullptr, *d_tend = nullptr; real* d_out = nullptr; int *d_L = nullptr, *d_len = nullptr, *d_off = nullptr, *d_bad = nullptr;
+    pg_refine_set* d_sets = nullptr; pg_refine_stats* d_stats = nullptr;
+    HIPCHK(h, D.alloc(d_in, n_in));
+    HIPCHK(h, D.alloc(d_out, total));
+    HIPCHK(h, D.alloc(d_off, n_traj * (size_t)Lmax));
+    HIPCHK(h, D.alloc(d_clos, 2 * n_traj * (size_t)Lmax));
+    HIPCHK(h, D.alloc(d_tend, n_traj));
+    HIPCHK(h, D.alloc(d_L, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_len, n_traj));
+    HIPCHK(h, D.alloc(d_bad, n_traj));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_stats, n_traj));
+    HIPCHK(h, to_device(d_in, channels_in, n_in));            // (the source travels as the doubles given)
+    HIPCHK(h, to_device(d_L, L, (size_t)n_path));
+    HIPCHK(h, to_device(d_len, lens.data(), n_traj));
+    HIPCHK(h, to_device(d_sets, sets, (size_t)n_sets));
+    PathRefineArgs A; A.n_sets = n_sets; A.Lmax = Lmax; A.Lmax_out = Lmax_out; A.L = d_L; A.len = d_len; A.in = d_in; A.sets = d_sets; A.out = d_out; A.off = d_off; A.clos = d_clos;
+    A.t_end = d_tend; A.stats = d_stats; A.bad = d_bad;
+    hipLaunchKernelGGL(k_path_refine, dim3((unsigned)n_traj), dim3(RF_THREADS), 0, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_refine_stats> st(n_traj);
+    std::vector<int> bad(n_traj);
+    std::vector<double> ends(n_traj);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_traj * sizeof(pg_refine_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ends.data(), d_tend, n_traj * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, n_traj * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    for (size_t k = 0; k < n_traj; k++) if (bad[k]) {
+        h->err = "pg_refine_paths: path " + std::to_string(k / (size_t)n_sets) + ", set " + std::to_string(k % (size_t)n_sets) +
+                 ": the refined knots are so dense that s does not increase strictly in the library's element type (ds_min " + std::to_string(st[k].ds_min) + ")";
+        return PG_ERR_INVALID;
+    }
+    if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_refine_stats));
+    return finish_library(h, D, d_out, d_len, lens, cls, n_sets, Lmax_out, install, L_out, closed_out, channels_out, std::move(ends));
 }
 
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, refine_parts as _refine_parts, REFINE_M_MAX
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -21,6 +21,7 @@ SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
 PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
 OFFSET_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_offset_stats._fields_])      # 64 bytes, the layout of pg_offset_stats
+REFINE_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_refine_stats._fields_])      # 64 bytes, the layout of pg_refine_stats
 CLIP_STATS_DTYPE = np.dtype([("width_min", np.float64), ("u_width_min", np.float64), ("reserved_d", np.float64, (2,))] + [(n, np.int32) for n in ("n_clip_L", "n_clip_R", "n_blocked", "n_centre_out", "n_seen", "n_ignored")] + [("reserved", np.int32, (2,))])      # 64 bytes, the layout of pg_clip_stats
 OBSTACLE_REPORT_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_obstacle_report._fields_])      # 64 bytes, the layout of pg_obstacle_report
 FIT_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_fit_stats._fields_])      # 80 bytes, the layout of pg_fit_stats
@@ -520,6 +521,81 @@ class BatchedTrajectoryTrackingMPC:
                                          st, rp), "pg_clip_tubes")
         reports = np.frombuffer(rp, dtype=OBSTACLE_REPORT_DTYPE)[:n_traj * max_count].reshape(n_traj, max_count).copy()
         return self._made_tubes(out, L, len(arr), install), np.frombuffer(st, dtype=CLIP_STATS_DTYPE).copy(), reports
+
+    # ---- refining the path (pg_refine_paths): every (path, refine set) pair of a path library x a library of refine sets, computed on the device ----
+    @classmethod
+    def pack_refines(cls, sets):
+        """vehicles.refine(...) dicts (refine / refine_for / refine_around; one, or a list) or pg_refine_set structures -> a ctypes array of pg_refine_set.  Raises
+        ValueError for a set outside the ranges of include/pigeon_mpc.h (the library refuses the same sets with PG_ERR_INVALID)."""
+        def fill(rec, p):
+            extra = set(p) - {"ds", "windows"}
+            if extra:
+                raise ValueError(f"refine_paths: a set has fields a refine set does not have: {sorted(extra)}")
+            full = _default_refine(**p)
+            rec.ds = full["ds"]
+            for j in range(4):
+                rec.s_lo[j], rec.s_hi[j], rec.ds_w[j] = full["windows"][j] if j < len(full["windows"]) else (math.inf, math.inf, math.inf)
+        arr = cls._pack(_lib.pg_refine_set, [sets] if isinstance(sets, (dict, _lib.pg_refine_set)) else sets, fill)
+        if len(arr) < 1:
+            raise ValueError("refine_paths: at least one refine set")
+        for k, r in enumerate(arr):
+            if not (r.ds == math.inf or (math.isfinite(r.ds) and r.ds > 0.0)):
+                raise ValueError(f"refine_paths: ds of set {k} is +Inf or finite and > 0")
+            for j in range(4):
+                used = math.isfinite(r.s_lo[j])
+                if not (used or r.s_lo[j] == math.inf):
+                    raise ValueError(f"refine_paths: s_lo of window {j} of set {k} is finite or +Inf")
+                if used and not (math.isfinite(r.s_hi[j]) and r.s_hi[j] > r.s_lo[j] and math.isfinite(r.ds_w[j]) and r.ds_w[j] > 0.0):
+                    raise ValueError(f"refine_paths: window {j} of set {k} needs a finite s_hi > s_lo and a finite ds_w > 0")
+                if not used and (math.isnan(r.s_hi[j]) or math.isnan(r.ds_w[j])):
+                    raise ValueError(f"refine_paths: s_hi or ds_w of the unused window {j} of set {k} is NaN")
+            if any(v != 0.0 for v in r.reserved):
+                raise ValueError(f"refine_paths: reserved of set {k} must be 0")
+        return arr
+
+    @staticmethod
+    def refined_lengths(L, ch, arr):
+        """L_out [n_path * n_sets] of pg_refine_paths, on the host: 1 + the sum of vehicles.refine_parts over the intervals of every (path, set) pair.  Raises ValueError
+        where the library refuses an interval of more than 4096 parts."""
+        out = np.zeros(len(L) * len(arr), dtype=np.int32)
+        for p in range(len(L)):
+            s = [float(v) for v in ch[p, 1, :int(L[p])]]
+            u = [v - s[0] for v in s]
+            for j, r in enumerate(arr):
+                rset = dict(ds=r.ds, windows=[(r.s_lo[q], r.s_hi[q], r.ds_w[q]) for q in range(4)])
+                plain = rset["ds"] == math.inf and all(w[0] == math.inf for w in rset["windows"])
+                count = 1
+                for i in range(len(s) - 1):
+                    m = 1 if plain else _refine_parts(rset, s[i + 1] - s[i], u[i], u[i + 1])
+                    if m > REFINE_M_MAX:
+                        raise ValueError(f"refine_paths: path {p}, set {j}, interval {i} would be cut into more than {REFINE_M_MAX} parts")
+                    count += m
+                if count > 2**31 - 1:
+                    raise ValueError(f"refine_paths: path {p}, set {j} has {count} knots")
+                out[p * len(arr) + j] = count
+        return out
+
+    def refine_paths(self, paths, sets, closed=None, Lmax_out=None, install=False):
+        """Knots inserted into a path library where a manoeuvre or an obstacle needs them, on the device (pg_refine_paths; the scheme is stated in include/pigeon_mpc.h):
+        paths = TrajectoryTubes or the channel array, sets = vehicles.refine(ds, windows) / refine_for(offset_set) / refine_around(report_row, source, ds_w, reach) dicts,
+        closed = None / one flag / one per path.  Every source knot stays a knot with its own values and the arc length is the source's, so offset sets, obstacle reports
+        and route events written against the source hold on the result.  Lmax_out: the knot capacity of the output (None: the largest L_out, computed on the host).
+        Returns (tubes, stats): the n_path * n_sets TrajectoryTubes in the order k = path * n_sets + set, each with its own knot count, and a structured array with the
+        fields of pg_refine_stats.  install=True makes them the handle's trajectory library (as set_trajectories(tubes) would, without the host round trip)."""
+        L, ch, cl = self.pack_paths(paths, closed)
+        arr = self.pack_refines(sets)
+        n_traj = len(L) * len(arr)
+        if Lmax_out is None:
+            Lmax_out = int(self.refined_lengths(L, ch, arr).max())
+        if not (Lmax_out == int(Lmax_out) and 2 <= Lmax_out <= 2**31 - 1):
+            raise ValueError("refine_paths: Lmax_out is an integer >= 2")
+        Lmax_out = int(Lmax_out)
+        out = np.zeros((n_traj, 10, Lmax_out))
+        Lo = np.zeros(n_traj, dtype=np.int32)
+        st = (_lib.pg_refine_stats * n_traj)()
+        self._chk(self.lib.pg_refine_paths(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, Lmax_out, int(bool(install)), _p(Lo, c_i32p), None,
+                                           _p(out), st), "pg_refine_paths")
+        return self._made_tubes(out, Lo, 1, install), np.frombuffer(st, dtype=REFINE_STATS_DTYPE).copy()
 
     # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
     @classmethod

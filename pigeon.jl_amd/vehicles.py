@@ -286,6 +286,77 @@ def pass_by_around(report_row, edges_at, ramp, x_min=0.1):
     return pass_by(0.5 * (hi + lo), u1 - float(ramp), u1, u2, u2 + float(ramp), x_min=x_min)
 
 
+REFINE_M_MAX = 4096      # the most parts one source interval may be cut into (pg_refine_paths)
+
+
+def refine(ds=math.inf, windows=()):
+    """One refine set for refine_paths (pg_refine_set).  refine() is the library's default (pg_default_refine_set), the identity.  ds: the largest knot spacing wanted
+    everywhere (m; +Inf: none).  windows: up to four (s_lo, s_hi, ds_w) -- the largest spacing ds_w wanted between s_lo and s_hi, metres of the source's arc length from
+    its first knot.  A source interval a window reaches into is cut WHOLE into equal parts no longer than ds_w; windows may overlap (the smallest spacing holds), one
+    beyond the path's end has no effect.  Build-defined: the reference has no path maker."""
+    w = [(float(a), float(b), float(c)) for a, b, c in windows]
+    if len(w) > 4:
+        raise ValueError(f"refine: {len(w)} windows (at most 4)")
+    return dict(ds=float(ds), windows=w)
+
+
+def refine_parts(rset, diff, u_lo, u_hi):
+    """m_i of pg_refine_paths, restated: the parts the source interval [u_lo, u_hi] (arc length from the first knot) of length diff is cut into under the set;
+    REFINE_M_MAX + 1 stands for every count above REFINE_M_MAX (the library refuses it).  Python floats are doubles and every operation is one rounding, as in the library."""
+    w = rset["ds"]
+    for s_lo, s_hi, ds_w in rset["windows"]:
+        if s_lo < math.inf and s_lo < u_hi and s_hi > u_lo:
+            w = min(w, ds_w)
+    if not w < math.inf or diff <= w:
+        return 1
+    q = diff / w
+    if not q <= float(REFINE_M_MAX):
+        return REFINE_M_MAX + 1
+    return int(math.ceil(q))
+
+
+def refine_for(offset_set, knots=10):
+    """The refine set that gives the rise and the fall window of an offset set (lane_change, pass_by, pass_by_around) at least `knots` knot intervals each: a window
+    (s_a, s_b, (s_b - s_a) / knots) per ramp.  An offset set without windows gives the identity."""
+    if not (knots == int(knots) and knots >= 1):
+        raise ValueError("refine_for: knots is an integer >= 1")
+    w = []
+    for a, b in ((offset_set["s_a"], offset_set["s_b"]), (offset_set["s_c"], offset_set["s_d"])):
+        if math.isfinite(a):
+            w.append((a, b, (b - a) / float(knots)))
+    return refine(windows=w)
+
+
+def refine_around(seen, source, ds_w, reach, radius=None):
+    """The refine set that puts knots ds_w apart around one disc, from `reach` metres before the first to `reach` after the last place it can be seen.  seen: the disc's
+    record of clip_tubes' reports (the fields of pg_obstacle_report), or an obstacle(...) dict; source: the path (a TrajectoryTube or its channel array [10][L]).
+    A record with side != 0: from u(k_first) - reach to u(k_last) + reach.  A record with side = 0 (no knot saw the disc): the closest knot's arc length -+ (R + reach),
+    R = `radius` (the disc's radius plus the set's margin; the record does not carry it) -- choose reach to cover the knot spacing there.  An obstacle: its projection
+    onto the source's chords on the host, -+ (radius + reach)."""
+    s, E, N, _, _, _ = _path_rows(source)
+    s0, ds_w, reach = float(s[0]), float(ds_w), float(reach)
+    if isinstance(seen, dict) and "E" in seen:
+        R = float(seen["radius"]) if radius is None else float(radius)
+        best = (math.inf, 0.0)
+        for i in range(len(s) - 1):
+            aE, aN = float(E[i]), float(N[i])
+            dE, dN = float(E[i + 1]) - aE, float(N[i + 1]) - aN
+            lam = min(1.0, max(0.0, ((seen["E"] - aE) * dE + (seen["N"] - aN) * dN) / (dE * dE + dN * dN)))
+            q = (seen["E"] - (aE + lam * dE)) ** 2 + (seen["N"] - (aN + lam * dN)) ** 2
+            if q < best[0]:
+                best = (q, float(s[i]) + lam * (float(s[i + 1]) - float(s[i])) - s0)
+        lo, hi = best[1] - (R + reach), best[1] + (R + reach)
+    elif int(seen["side"]) != 0:
+        lo, hi = float(s[int(seen["k_first"])]) - s0 - reach, float(s[int(seen["k_last"])]) - s0 + reach
+    else:
+        if radius is None:
+            raise ValueError("refine_around: a record with side = 0 needs radius= (the disc's radius plus the set's margin)")
+        lo, hi = float(seen["u_at"]) - (float(radius) + reach), float(seen["u_at"]) + (float(radius) + reach)
+    if not hi > lo:
+        raise ValueError("refine_around: the window is empty (reach >= 0, and > 0 where a single knot sees the disc)")
+    return refine(windows=[(lo, hi, ds_w)])
+
+
 START_RANGES = ("s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v")
 START_MODES = ("s_mode", "e_mode", "steady", "time_mode", "other_mode")
 
