@@ -301,8 +301,8 @@ int pg_make_paths(pg_handle* h, int32_t n_path, const pg_path_spec* specs, int32
  *             t = s / V_ref, V = V_ref, A = 0.
  *   Unwrap    k_0 = 0;  k_i = k_{i-1} - 1 where psi_raw_i - psi_raw_{i-1} > 3.141592653589793, k_{i-1} + 1 where it is < -3.141592653589793, else k_{i-1};
  *             psi_i = psi_raw_i + (k_i 6.283185307179586).  The prefix is over integers: its order cannot show.
- * Everything but atan2 reproduces the twin bit for bit; psi, turn and closure_psi are within 8 * 2^-52 * max(pi, |psi|) of it.  Interpolation, not smoothing: the curvature of
- * noisy waypoints is the caller's to judge (kappa_abs_max). */
+ * Everything but atan2 reproduces the twin bit for bit; psi, turn and closure_psi are within 8 * 2^-52 * max(pi, |psi|) of it.  Interpolation, not smoothing: noisy waypoints
+ * (a rounded survey) go through pg_smooth_waypoints below first, whose output is what this call takes. */
 typedef struct pg_waypoint {
     double E, N;            /* finite; two neighbouring waypoints of a path must not coincide */
     double edge_L, edge_R;  /* the tube edges at the waypoint, linear in u across a span; finite, edge_L > edge_R */
@@ -536,6 +536,85 @@ pg_refine_set pg_default_refine_set(void);
 int pg_refine_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L, const int32_t* closed, const double* channels_in,
                     int32_t n_sets, const pg_refine_set* sets, int32_t Lmax_out, int32_t install,
                     int32_t* L_out, int32_t* closed_out, double* channels_out, pg_refine_stats* stats);
+
+/* Smoothing surveyed waypoints: every (path, smoothing set) pair of a library of waypoint lists and a library of smoothing sets as smoothed waypoints, computed on the
+ * device -- a cubic smoothing spline (Reinsch) of E and of N over the chord-length parameter, natural on an open path and periodic on a closed one.  pg_fit_paths
+ * interpolates, so the rounding of a recorded survey is differentiated twice into kappa; this is the call that comes before it: waypoints in, waypoints out, and a library
+ * of sets with per-pair stats to choose lambda from.  The reference reads its paths from files (src/ros_integration.jl:13-16), so the scheme is build-defined
+ * (tests/wp_smooth_numpy.py is its twin).  Waypoints are doubles in both libraries and ALL arithmetic is double, every operation rounded on its own (no contraction): both
+ * libraries return the same bits.  The scheme has only + - * / sqrt, so the twin reproduces every output bit for bit.  Below, a parenthesis is one rounded operation, a sum
+ * or product without one is taken from the left, and min, max, | | and the comparisons are exact.  n = n_wp; im = i - 1, ip = i + 1, modulo n.
+ *   Chords    The spans and h_j = sqrt((dE dE) + (dN dN)) of the INPUT waypoints exactly as pg_fit_paths states them (Spans), with p_j = 1 / h_j and the slopes dE / h_j,
+ *             dN / h_j.  An open path has no span n - 1: h_{n-1} = p_{n-1} = 0 and its slopes are 0 (only places the rows below do not reach read them).
+ *   U         U_0 = 0 and U_{j+1} = P_{j / c} + r_{j+1}, the blocked prefix order of pg_make_paths (Prefix) over h_0 .. h_{n-2}, c = ceil((n - 1) / 256): the
+ *             cumulative chord length of waypoint i, in which the windows are given.
+ *   winv      winv_i = 1; then for k = 0 .. n_win - 1 in turn: where u_lo[k] <= U_i <= u_hi[k], winv_i = factor[k] (the last listed window that holds U_i wins).
+ *             pin_ends on an open path: winv_0 = winv_{n-1} = 0.  winv = 0 pins a waypoint, a factor above 1 smooths it more.
+ *   System    (R + lambda Q^T Winv Q) gamma = Q^T y per coordinate y in {E, N}, with Q the second-difference operator (column i holds p_im, q_i = (-p_im) - p_i and p_i
+ *             in the rows im, i, ip), R_ii = (h_im + h_i) / 3, R_{i,ip} = h_i / 6.  The band of row i in closed form:
+ *               a0 = ((winv_im (p_im p_im)) + (winv_i (q_i q_i))) + (winv_ip (p_i p_i));   a1 = p_i ((winv_i q_i) + (winv_ip q_ip));   a2 = winv_ip (p_i p_ip);
+ *               D_i = ((h_im + h_i) / 3) + (lambda a0);   E1_i = (h_i / 6) + (lambda a1)  [the place (i, ip)];   E2_i = lambda a2  [the place (i, ip + 1)];
+ *             the right-hand side f_i = slope_i - slope_im.  The matrix is symmetric positive definite and pentadiagonal.
+ *   Band      The rows r = 0 .. m - 1 of a band (D, E1, E2) by the LDL^T recurrence without pivoting; an entry before row 0 is 0, a pivot before row 0 is 1:
+ *               e1 = E1_{r-1}, e2 = E2_{r-2};  l2_r = e2 / d_{r-2};  c1 = e1 - (e2 l1_{r-1});  l1_r = c1 / d_{r-1};  d_r = (D_r - (e2 l2_r)) - (c1 l1_r);
+ *               z_r = (f_r - (l1_r z_{r-1})) - (l2_r z_{r-2});   then for r = m - 1 .. 0:  x_r = ((z_r / d_r) - (l1_{r+1} x_{r+1})) - (l2_{r+2} x_{r+2}), a term past the
+ *             last row left out as 0.  One factorisation serves every right-hand side.
+ *   Open      The rows are the waypoints 1 .. n - 2 (m = n - 2), gamma_0 = gamma_{n-1} = 0 (natural ends).  Two waypoints have no row.
+ *   Closed    All n rows, indices modulo n: a cyclic pentadiagonal system, solved exactly by bordering.  The band B is the rows and columns 0 .. n - 3 (m = n - 2), the
+ *             border the unknowns a = n - 2 and b = n - 1.  Column a of C has E2_{n-2}, E2_{n-4}, E1_{n-3} in the rows 0, n - 4, n - 3; column b has E1_{n-1}, E2_{n-1},
+ *             E2_{n-3} in the rows 0, 1, n - 3 (n >= 5 keeps them apart).  Za, Zb solve B Z = C, x0 solves B x0 = f.  A product C^T x is its three terms in the order of
+ *             the rows listed, from the left.  S00 = D_a - (Ca^T Za), S01 = E1_a - (Ca^T Zb), S11 = D_b - (Cb^T Zb), det = (S00 S11) - (S01 S01);
+ *             ra = f_a - (Ca^T x0), rb = f_b - (Cb^T x0);  gamma_a = ((S11 ra) - (S01 rb)) / det,  gamma_b = ((S00 rb) - (S01 ra)) / det;
+ *             gamma_i = (x0_i - (Za_i gamma_a)) - (Zb_i gamma_b) for i <= n - 3.
+ *   Result    g_i = y_i - (lambda (winv_i (((p_im gamma_im) + (q_i gamma_i)) + (p_i gamma_ip)))): lambda = 0 and a pinned waypoint return y_i itself (y - (0 x); a
+ *             coordinate that is -0 may come back as +0).  gamma are the second derivatives of the result at the waypoints.
+ *   Walls     The tangent at waypoint i is the first derivative of the spline through g with the second derivatives gamma, over the input's chords:
+ *             t = ((g_ip - g_i) / h_i) - ((h_i ((2 gamma_i) + gamma_ip)) / 6); at the last waypoint of an open path, from the span that ends on it:
+ *             t = ((g_i - g_im) / h_im) + ((h_im ((2 gamma_i) + gamma_im)) / 6).  v = sqrt((tE tE) + (tN tN)); the left normal of the library's convention (dE/ds =
+ *             -sin psi, dN/ds = cos psi, e positive to the left) is nE = (-tN) / v, nN = tE / v.  With dE = gE_i - E_i, dN = gN_i - N_i:  c = (dE nE) + (dN nN), the
+ *             normal part of the displacement.  keep_walls: edge_L = edge_L - c, edge_R = edge_R - c (the tube stays where it was surveyed); else both are copied.
+ *   Stats     dev_i = sqrt((dE dE) + (dN dN));  dev_max and the smallest i that reaches it;  dev_rms = sqrt(Sum((dE dE) + (dN dN)) / n);
+ *             bend = Sum((0 + bE_i) + bN_i) with b_i = gamma_i ((((h_im / 6) gamma_im) + (((h_im + h_i) / 3) gamma_i)) + ((h_i / 6) gamma_ip)): gamma^T R gamma, the
+ *             integral of g''^2;  n_outside counts c > edge_L or c < edge_R against the input's edges;  width_min over (edge_L - edge_R) of the output;  pivot_min over
+ *             the d_r and, on a closed path, S00 and det / S00;  chord_min over the chords of the OUTPUT waypoints, computed as h_j above.
+ *   Sum       Block b = 0 .. 255 holds the waypoints [b c, min((b + 1) c, n)), c = ceil(n / 256), summed from 0 in order; the 256 block totals are summed by the
+ *             tree of neighbouring pairs (T_0 + T_1, T_2 + T_3, ..; then those pairwise; ..).  The order depends on the path's own n alone.
+ * A pair's bits depend on its own path and set alone: not on the batch, its order or n_wp_total.  Left out: choosing lambda (the set library and the stats are the tool),
+ * weights per waypoint inside pg_waypoint, smoothing the edges themselves, decimating (waypoints_from_tube(every=) stays the way), a device-pointer hand-over into
+ * pg_fit_paths, least-squares splines with fewer knots than waypoints. */
+typedef struct pg_smooth_set {
+    double lambda;            /* m^3, finite and >= 0: weighs the integral of g''^2 over the chord parameter against the sum of the squared displacements */
+    double u_lo[4], u_hi[4];  /* the first n_win windows, in metres of the path's cumulative chord length U; u_lo <= u_hi, neither NaN */
+    double factor[4];         /* winv inside window k: finite and >= 0; 0 pins, above 1 smooths more */
+    int32_t n_win;            /* 0 .. 4 */
+    int32_t pin_ends;         /* != 0: the two end waypoints of an OPEN path do not move; not looked at on a closed path */
+    int32_t keep_walls;       /* != 0: edge_L and edge_R of a moved waypoint are shifted by the normal part of its displacement */
+    int32_t reserved;         /* 0 */
+} pg_smooth_set;              /* 120 bytes */
+typedef struct pg_smooth_stats {   /* one per (path, set) pair; computed in double in both libraries */
+    double dev_max, dev_rms;  /* the displacement sqrt(dE dE + dN dN) over the path's waypoints, metres */
+    double i_dev_max;         /* the waypoint (counted from the path's first) of dev_max */
+    double bend;              /* gamma^T R gamma summed over E and N */
+    double n_outside;         /* smoothed points whose normal displacement left the surveyed tube */
+    double width_min;         /* the smallest edge_L - edge_R of the output */
+    double pivot_min;         /* the smallest pivot of the factorisation; +Inf for two waypoints */
+    double chord_min;         /* the smallest chord of the output waypoints */
+    double reserved;          /* 0 */
+} pg_smooth_stats;            /* 72 bytes */
+/* { 0, {0 x 4}, {0 x 4}, {1 x 4}, 0, 0, 0, 0 }: the identity */
+pg_smooth_set pg_default_smooth_set(void);
+/* specs is the array pg_fit_paths takes; only wp0, n_wp and closed are read.  waypoints_out [n_sets][n_wp_total]: block k is the whole input array under set k, so
+ * set k is fitted by adding k * n_wp_total to every wp0, and all sets in one pg_fit_paths call; a waypoint no path refers to is copied as given.  stats [n_path *
+ * n_sets], pair = path * n_sets + set, the order of pg_offset_paths.  Each may be NULL.  Unlike pg_fit_paths, the waypoint ranges of two paths must not overlap (two
+ * writers of one output waypoint).  Nothing is installed: waypoints are not a library.  Synchronous.  A handle that never calls this launches what it launched before.
+ * PG_ERR_INVALID, everything the host can decide validated before the first allocation (the handle and its installed library are left unchanged): a null specs,
+ * waypoints or sets; n_path, n_sets or n_wp_total < 1; an open path with n_wp < 2; a closed path with n_wp < 5 (band and border must not share a place); a waypoint range
+ * outside [0, n_wp_total); ranges of two paths that overlap (the message names both); a non-finite waypoint field; edge_L <= edge_R; a chord that is not finite and > 0;
+ * lambda or a factor of a listed window that is not finite and >= 0; n_win outside [0, 4]; a listed window with a NaN bound or u_lo > u_hi; reserved != 0; n_path *
+ * n_sets beyond 31 bits or the scratch of all pairs beyond the allocation arithmetic.  After the launch and before anything is copied out, naming path, set and
+ * waypoint: a pivot that is not > 0; a non-finite output; edge_L <= edge_R after keep_walls; two neighbouring output waypoints at the same point. */
+int pg_smooth_waypoints(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
+                        int32_t n_sets, const pg_smooth_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats);
 
 /* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
  * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car

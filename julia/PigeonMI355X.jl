@@ -834,6 +834,48 @@ end
 "{ Inf, (Inf x 4), (Inf x 4), (Inf x 4), (0, 0, 0) } as the library states them (pg_default_refine_set): the identity"
 default_refine_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_refine_set), PgRefineSet, ())
 
+# Smoothing surveyed waypoints (pg_smooth_waypoints): a cubic smoothing spline of every (path, smoothing set) pair, on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_smooth_set (120 bytes): lambda in m^3, up to four windows (u_lo, u_hi, factor) in the path's cumulative chord length, of which the first n_win are looked at, the flags pin_ends and keep_walls, a reserved 0"
+struct PgSmoothSet
+    lambda::Float64
+    u_lo::NTuple{4,Float64}
+    u_hi::NTuple{4,Float64}
+    factor::NTuple{4,Float64}
+    n_win::Int32
+    pin_ends::Int32
+    keep_walls::Int32
+    reserved::Int32
+end
+"windows: up to four (u_lo, u_hi, factor); PgSmoothSet() is the identity"
+function PgSmoothSet(; lambda=0.0, windows=(), pin_ends=false, keep_walls=false)
+    length(windows) <= 4 || error("PgSmoothSet: at most 4 windows")
+    slot(f, fill) = ntuple(j -> j <= length(windows) ? Float64(windows[j][f]) : fill, 4)
+    PgSmoothSet(Float64(lambda), slot(1, 0.0), slot(2, 0.0), slot(3, 1.0), Int32(length(windows)), Int32(pin_ends), Int32(keep_walls), Int32(0))
+end
+"pg_smooth_stats (72 bytes), one per (path, set) pair"
+struct PgSmoothStats
+    dev_max::Float64
+    dev_rms::Float64
+    i_dev_max::Float64
+    bend::Float64
+    n_outside::Float64
+    width_min::Float64
+    pivot_min::Float64
+    chord_min::Float64
+    reserved::Float64
+end
+"specs and waypoints as fit_paths! takes them (only wp0, n_wp and closed are read; the ranges of two paths must not overlap) -> (waypoints_out [n_wp_total, n_sets], stats [n_sets, n_path]): column k is the whole waypoint array under set k, so set k is fitted by adding (k - 1) * n_wp_total to every wp0"
+function smooth_waypoints!(mpc::BatchedTrajectoryTrackingMPC, specs::Vector{PgFitSpec}, waypoints::Vector{PgWaypoint}, sets::Vector{PgSmoothSet})
+    (sizeof(PgSmoothSet), sizeof(PgSmoothStats)) == (120, 72) || error("PigeonMI355X.jl: the pg_smooth_waypoints structures differ from include/pigeon_mpc.h")
+    n, ns, nw = length(specs), length(sets), length(waypoints)
+    out = Matrix{PgWaypoint}(undef, nw, ns); stats = Matrix{PgSmoothStats}(undef, ns, n)
+    check(mpc, ccall(sym(mpc, :pg_smooth_waypoints), Cint, (Ptr{Cvoid}, Int32, Ptr{PgFitSpec}, Int32, Ptr{PgWaypoint}, Int32, Ptr{PgSmoothSet}, Ptr{PgWaypoint}, Ptr{PgSmoothStats}),
+                     mpc.handle, Int32(n), specs, Int32(nw), waypoints, Int32(ns), sets, out, stats), "pg_smooth_waypoints")
+    out, stats
+end
+"{ 0, (0 x 4), (0 x 4), (1 x 4), 0, 0, 0, 0 } as the library states them (pg_default_smooth_set): the identity"
+default_smooth_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_smooth_set), PgSmoothSet, ())
+
 # Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
 "pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
 struct PgStartSet

@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -1632,6 +1633,99 @@ int pg_refine_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
     }
     if (stats) memcpy(stats, st.data(), n_traj * sizeof(pg_refine_stats));
     return finish_library(h, D, d_out, d_len, lens, cls, n_sets, Lmax_out, install, L_out, closed_out, channels_out, std::move(ends));
+}
+
+// ---- pg_smooth_waypoints: every (path, smoothing set) pair of a waypoint library x a library of smoothing sets (pg_waypoint_smooth.hip).  One launch, one workgroup per
+// pair; waypoints in, waypoints out: no trajectory library is made, so nothing is installed ----
+static_assert(sizeof(pg_smooth_set) == 120 && sizeof(pg_smooth_stats) == 72, "the sizes include/pigeon_mpc.h states");
+pg_smooth_set pg_default_smooth_set(void) {
+    pg_smooth_set s; s.lambda = 0.0;
+    for (int j = 0; j < 4; j++) { s.u_lo[j] = 0.0; s.u_hi[j] = 0.0; s.factor[j] = 1.0; }
+    s.n_win = 0; s.pin_ends = 0; s.keep_walls = 0; s.reserved = 0;
+    return s;
+}
+static const char* smooth_set_problem(const pg_smooth_set& s) {
+    if (!(std::isfinite(s.lambda) && s.lambda >= 0.0)) return "lambda of a set is finite and >= 0";
+    if (!(s.n_win >= 0 && s.n_win <= 4)) return "n_win of a set lies in [0, 4]";
+    for (int j = 0; j < s.n_win; j++) {
+        if (std::isnan(s.u_lo[j]) || std::isnan(s.u_hi[j]) || s.u_lo[j] > s.u_hi[j]) return "a window of a set needs u_lo <= u_hi";
+        if (!(std::isfinite(s.factor[j]) && s.factor[j] >= 0.0)) return "factor of a window is finite and >= 0";
+    }
+    if (s.reserved != 0) return "reserved of a set must be 0";
+    return nullptr;
+}
+int pg_smooth_waypoints(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
+                        int32_t n_sets, const pg_smooth_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, specs && waypoints && sets, "pg_smooth_waypoints: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && n_wp_total >= 1, "pg_smooth_waypoints: need n_path >= 1, n_sets >= 1 and n_wp_total >= 1");
+    REQUIRE_NO(h, "pg_smooth_waypoints: ", pair_count_problem(n_path, n_sets, 2));
+    for (int k = 0; k < n_path; k++) {
+        const pg_fit_spec& p = specs[k];
+        REQUIRE(h, p.closed ? p.n_wp >= 5 : p.n_wp >= 2, "pg_smooth_waypoints: an open path needs >= 2 waypoints, a closed one >= 5");
+        REQUIRE(h, p.wp0 >= 0 && p.wp0 < n_wp_total && p.n_wp <= n_wp_total - p.wp0, "pg_smooth_waypoints: the waypoints of a path must lie inside [0, n_wp_total)");
+        double C = 0.0;
+        REQUIRE_NO(h, "pg_smooth_waypoints: ", fit_waypoints_problem(p, waypoints, C));
+    }
+    {   // two writers of one output waypoint: the paths in the order of their first waypoint, neighbours compared
+        std::vector<int> order((size_t)n_path);
+        for (int k = 0; k < n_path; k++) order[(size_t)k] = k;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return specs[a].wp0 != specs[b].wp0 ? specs[a].wp0 < specs[b].wp0 : a < b; });
+        for (int k = 0; k + 1 < n_path; k++) {
+            const int a = order[(size_t)k], b = order[(size_t)k + 1];
+            if (specs[a].wp0 + specs[a].n_wp > specs[b].wp0) {
+                h->err = "pg_smooth_waypoints: the waypoint ranges of path " + std::to_string(std::min(a, b)) + " and path " + std::to_string(std::max(a, b)) + " overlap";
+                return PG_ERR_INVALID;
+            }
+        }
+    }
+    for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_smooth_waypoints: ", smooth_set_problem(sets[j]));
+    std::vector<SmoothSpec> recs((size_t)n_path);
+    size_t n_used = 0;
+    int lds_rows = 1;                                         // the rows of the longest path, at most WS_LDS_ROWS: what the launch keeps of the recurrence in LDS
+    for (int k = 0; k < n_path; k++) {
+        lds_rows = std::max(lds_rows, std::min(specs[k].n_wp - 2, (int)WS_LDS_ROWS));
+        SmoothSpec& r = recs[(size_t)k];
+        r.soff = (long long)n_used; r.wp0 = specs[k].wp0; r.n_wp = specs[k].n_wp; r.closed = specs[k].closed ? 1 : 0; r.pad = 0;
+        n_used += (size_t)specs[k].n_wp;                          // (<= n_wp_total: the ranges do not overlap)
+    }
+    REQUIRE(h, (double)n_sets * (double)n_wp_total * (double)WS_ARRAYS * 8.0 < 4611686018427387904.0,
+            "pg_smooth_waypoints: the scratch of all pairs is more than the allocation arithmetic holds");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t n_pair = (size_t)n_path * n_sets, n_all = (size_t)n_wp_total;
+    CallBufs D; pg_waypoint *d_in = nullptr, *d_out = nullptr; SmoothSpec* d_specs = nullptr; pg_smooth_set* d_sets = nullptr; double* d_scr = nullptr;
+    pg_smooth_stats* d_stats = nullptr; int* d_bad = nullptr;
+    HIPCHK(h, D.alloc(d_in, n_all));
+    HIPCHK(h, D.alloc(d_out, (size_t)n_sets * n_all));
+    HIPCHK(h, D.alloc(d_specs, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_scr, (size_t)n_sets * n_used * WS_ARRAYS));
+    HIPCHK(h, D.alloc(d_stats, n_pair));
+    HIPCHK(h, D.alloc(d_bad, 4 * n_pair));
+    HIPCHK(h, to_device(d_in, waypoints, n_all));
+    for (int j = 0; j < n_sets; j++)                          // (every block starts as the input, copied on the device: a pair writes its own path's waypoints alone)
+        HIPCHK(h, hipMemcpyAsync(d_out + (size_t)j * n_all, d_in, n_all * sizeof(pg_waypoint), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, to_device(d_specs, recs.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_sets, sets, (size_t)n_sets));
+    WpSmoothArgs A; A.n_sets = n_sets; A.n_wp_total = n_wp_total; A.lds_rows = lds_rows; A.n_used = (long long)n_used; A.specs = d_specs; A.sets = d_sets; A.in = d_in; A.out = d_out; A.scratch = d_scr;
+    A.stats = d_stats; A.bad = d_bad;
+    hipLaunchKernelGGL(k_wp_smooth, dim3((unsigned)n_pair), dim3(WS_THREADS), (size_t)7 * lds_rows * sizeof(double), h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_smooth_stats> st(n_pair);
+    std::vector<int> bad(4 * n_pair);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_pair * sizeof(pg_smooth_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, 4 * n_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    static const char* const what[4] = {"a pivot of the factorisation is not > 0", "the output is not finite", "edge_L <= edge_R after keep_walls",
+                                        "this output waypoint and the next lie at the same point"};
+    for (size_t k = 0; k < n_pair; k++) for (int c = 0; c < 4; c++) if (bad[4 * k + c] >= 0) {
+        h->err = "pg_smooth_waypoints: path " + std::to_string(k / (size_t)n_sets) + ", set " + std::to_string(k % (size_t)n_sets) + ", waypoint " + std::to_string(bad[4 * k + c]) +
+                 ": " + what[c];
+        return PG_ERR_INVALID;
+    }
+    if (stats) memcpy(stats, st.data(), n_pair * sizeof(pg_smooth_stats));
+    return down_raw(h, waypoints_out, d_out, (size_t)n_sets * n_all * sizeof(pg_waypoint));
 }
 
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, refine_parts as _refine_parts, REFINE_M_MAX
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, smooth as _default_smooth, refine_parts as _refine_parts, REFINE_M_MAX
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -21,6 +21,7 @@ SOLVED, MAX_ITER, NUMERICAL, INFEASIBLE_X0, SOLVED_UNVERIFIED = 1, 2, 3, 4, 5
 SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_speed_plan_stats._fields_])      # 48 bytes, the layout of pg_speed_plan_stats
 PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
 OFFSET_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_offset_stats._fields_])      # 64 bytes, the layout of pg_offset_stats
+SMOOTH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_smooth_stats._fields_])      # 72 bytes, the layout of pg_smooth_stats
 REFINE_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_refine_stats._fields_])      # 64 bytes, the layout of pg_refine_stats
 CLIP_STATS_DTYPE = np.dtype([("width_min", np.float64), ("u_width_min", np.float64), ("reserved_d", np.float64, (2,))] + [(n, np.int32) for n in ("n_clip_L", "n_clip_R", "n_blocked", "n_centre_out", "n_seen", "n_ignored")] + [("reserved", np.int32, (2,))])      # 64 bytes, the layout of pg_clip_stats
 OBSTACLE_REPORT_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_obstacle_report._fields_])      # 64 bytes, the layout of pg_obstacle_report
@@ -596,6 +597,59 @@ class BatchedTrajectoryTrackingMPC:
         self._chk(self.lib.pg_refine_paths(self.h, len(L), ch.shape[2], _p(L, c_i32p), _p(cl, c_i32p), _p(ch), len(arr), arr, Lmax_out, int(bool(install)), _p(Lo, c_i32p), None,
                                            _p(out), st), "pg_refine_paths")
         return self._made_tubes(out, Lo, 1, install), np.frombuffer(st, dtype=REFINE_STATS_DTYPE).copy()
+
+    # ---- smoothing surveyed waypoints (pg_smooth_waypoints): every (path, smoothing set) pair of a waypoint library x a library of smoothing sets, on the device ----
+    @classmethod
+    def pack_smooths(cls, sets):
+        """vehicles.smooth(...) dicts (one, or a list) or pg_smooth_set structures -> a ctypes array of pg_smooth_set.  Raises ValueError for a set outside the ranges of
+        include/pigeon_mpc.h (the library refuses the same sets with PG_ERR_INVALID)."""
+        def fill(rec, p):
+            full = _default_smooth(**p)
+            rec.lam, rec.pin_ends, rec.keep_walls, rec.n_win = full["lam"], int(full["pin_ends"]), int(full["keep_walls"]), len(full["windows"])
+            for j in range(4):
+                rec.u_lo[j], rec.u_hi[j], rec.factor[j] = full["windows"][j] if j < rec.n_win else (0.0, 0.0, 1.0)
+        arr = cls._pack(_lib.pg_smooth_set, [sets] if isinstance(sets, (dict, _lib.pg_smooth_set)) else sets, fill)
+        if len(arr) < 1:
+            raise ValueError("smooth_waypoints: at least one smoothing set")
+        for k, r in enumerate(arr):
+            if not (math.isfinite(r.lam) and r.lam >= 0.0):
+                raise ValueError(f"smooth_waypoints: lam of set {k} is finite and >= 0")
+            if not 0 <= r.n_win <= 4:
+                raise ValueError(f"smooth_waypoints: n_win of set {k} lies in [0, 4]")
+            for j in range(r.n_win):
+                if not r.u_lo[j] <= r.u_hi[j]:
+                    raise ValueError(f"smooth_waypoints: window {j} of set {k} needs u_lo <= u_hi")
+                if not (math.isfinite(r.factor[j]) and r.factor[j] >= 0.0):
+                    raise ValueError(f"smooth_waypoints: factor of window {j} of set {k} is finite and >= 0")
+            if r.reserved != 0:
+                raise ValueError(f"smooth_waypoints: reserved of set {k} must be 0")
+        return arr
+
+    @staticmethod
+    def smoothed_fit_paths(paths, smoothed, k):
+        """The fit_paths list for "every path under set k": paths as smooth_waypoints took them (each needs n_knots), smoothed = its first return value."""
+        return [dict(p, waypoints=smoothed[k][i]) for i, p in enumerate(paths)]
+
+    def smooth_waypoints(self, paths, sets):
+        """Surveyed waypoints smoothed on the device (pg_smooth_waypoints; the scheme is stated in include/pigeon_mpc.h): a cubic smoothing spline of E and N over the
+        chord length for every (path, set) pair.  paths = a list of dict(waypoints=[vehicles.waypoint dicts], closed=False) -- the dicts fit_paths takes; n_knots and V_ref
+        are not looked at --, sets = vehicles.smooth(lam=.., pin_ends=.., keep_walls=.., windows=[vehicles.smooth_window(..)]) dicts.  Returns (smoothed, stats):
+        smoothed[k][i] is the waypoint list of path i under set k (smoothed_fit_paths(paths, smoothed, k) is the list fit_paths takes for set k), stats a structured
+        array [n_path][n_sets] with the fields of pg_smooth_stats (dev_max, dev_rms, i_dev_max, bend, n_outside, width_min, pivot_min, chord_min)."""
+        paths = [dict(p) for p in paths]
+        for k, p in enumerate(paths):
+            if len(p.get("waypoints", ())) < (5 if p.get("closed", False) else 2):
+                raise ValueError(f"smooth_waypoints: path {k} needs 2 waypoints (a closed path 5)")
+            p.setdefault("n_knots", 3)
+        specs, wps, _ = self.pack_fit_specs(paths)
+        arr = self.pack_smooths(sets)
+        n, ns, nw = len(specs), len(arr), len(wps)
+        out = (_lib.pg_waypoint * (ns * nw))()
+        st = (_lib.pg_smooth_stats * (n * ns))()
+        self._chk(self.lib.pg_smooth_waypoints(self.h, n, specs, nw, wps, ns, arr, out, st), "pg_smooth_waypoints")
+        flat = np.frombuffer(out, dtype=np.float64).reshape(ns, nw, 4)
+        smoothed = [[[dict(E=float(w[0]), N=float(w[1]), edge_L=float(w[2]), edge_R=float(w[3])) for w in flat[k, s.wp0:s.wp0 + s.n_wp]] for s in specs] for k in range(ns)]
+        return smoothed, np.frombuffer(st, dtype=SMOOTH_STATS_DTYPE).copy().reshape(n, ns)
 
     # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
     @classmethod

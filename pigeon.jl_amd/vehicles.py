@@ -424,6 +424,30 @@ def waypoint(**overrides):
     return w
 
 
+def smooth(**overrides):
+    """One smoothing set for smooth_waypoints (pg_smooth_set).  smooth() is the library's default (pg_default_smooth_set), the identity.  lam: lambda in m^3, the weight
+    of the integral of g''^2 over the chord parameter against the sum of the squared displacements (0: the waypoints come back bit for bit; 0.1 moves the recorded oval's
+    points by a quarter of a millimetre and takes the rounding out of its curvature).  pin_ends: the two end waypoints of an open path do not move.  keep_walls: the tube
+    edges of a moved waypoint are shifted by the normal part of its displacement, so the walls stay where they were surveyed.  windows: up to four smooth_window(...)
+    entries; the last listed one that holds a waypoint's cumulative chord length sets its inverse weight."""
+    s = dict(lam=0.0, pin_ends=False, keep_walls=False, windows=[])
+    for k, v in overrides.items():
+        if k not in s:
+            raise KeyError(f"{k} is not a field of a smoothing set: {sorted(s)}")
+        s[k] = v
+    s["lam"] = float(s["lam"]); s["pin_ends"] = bool(s["pin_ends"]); s["keep_walls"] = bool(s["keep_walls"])
+    s["windows"] = [(float(a), float(b), float(c)) for a, b, c in s["windows"]]
+    if len(s["windows"]) > 4:
+        raise ValueError(f"smooth: {len(s['windows'])} windows (at most 4)")
+    return s
+
+
+def smooth_window(u_lo, u_hi, factor=0.0):
+    """One window of a smoothing set: the waypoints whose cumulative chord length (metres from the path's first waypoint) lies in [u_lo, u_hi] get the inverse weight
+    `factor` -- 0 pins them ("do not touch the chicane"), above 1 smooths them more than the rest."""
+    return (float(u_lo), float(u_hi), float(factor))
+
+
 def waypoints_from_tube(tube, every=1, closed=False):
     """The knots 0, every, 2 every, .. of a TrajectoryTube -- or of a committed path as its file holds it (the keys posE_m, posN_m, edgeL_m, edgeR_m) -- as a waypoint list
     for fit_paths: "the same track thinned to every n-th point".  closed=True: the file repeats knot 0 as its last knot, which is dropped (fit_paths closes the path itself);
