@@ -357,6 +357,17 @@ START_MAKE_PROTOTYPES = {
 }
 
 
+# device-resident entry points (include/pigeon_mpc.h: pg_set_inputs_dev, pg_step_dev, pg_get_next_control*_dev, pg_hji_lookup*_dev): every array is a raw device address
+DEVICE_RESIDENT_PROTOTYPES = {
+    "pg_set_inputs_dev": [C.c_void_p, C.c_int32] + [C.c_void_p] * 5,
+    "pg_step_dev": [C.c_void_p, C.c_void_p],
+    "pg_get_next_control_dev": [C.c_void_p, C.c_void_p],
+    "pg_get_next_control_hji_dev": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    "pg_hji_lookup_dev": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "pg_hji_lookup8_dev": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+}
+
+
 def load_library(precision="f64"):
     """Loads the HIP library of the requested arithmetic type.  PyTorch-ROCm is imported first so that both share ONE HIP runtime in this process."""
     assert precision in ("f64", "f32", "f64-diag")
@@ -378,7 +389,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, PATH_REFINE_PROTOTYPES, WP_SMOOTH_PROTOTYPES, START_MAKE_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, PATH_REFINE_PROTOTYPES, WP_SMOOTH_PROTOTYPES, START_MAKE_PROTOTYPES, DEVICE_RESIDENT_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int

@@ -1210,6 +1210,25 @@ class BatchedTrajectoryTrackingMPC:
     def step_dev(self, u_out_ptr=None):
         self._chk(self.lib.pg_step_dev(self.h, C.c_void_p(u_out_ptr) if u_out_ptr else None), "pg_step_dev")
 
+    def get_next_control_dev(self, u_ptr):
+        """get_next_control into a device array [B][3] of the library's element type (raw address; None: nothing is written).  Asynchronous on the handle's stream."""
+        self._chk(self.lib.pg_get_next_control_dev(self.h, C.c_void_p(u_ptr) if u_ptr else None), "pg_get_next_control_dev")
+
+    def get_next_control_hji_dev(self, use_HJI_policy, u_ptr, source_ptr=None):
+        """get_next_control_hji into device arrays: u [B][3] of the library's element type, source [B] int32 (either may be None).  Asynchronous on the handle's stream."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._chk(self.lib.pg_get_next_control_hji_dev(self.h, int(bool(use_HJI_policy)), vp(u_ptr), vp(source_ptr)), "pg_get_next_control_hji_dev")
+
+    def hji_lookup_dev(self, B, x7_ptr, V_ptr=None, gradV_ptr=None):
+        """hji_lookup on device arrays of the library's element type: x7 [B][7] in, V [B] and gradV [B][7] out (either may be None).  Returns once the outputs are written."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._chk(self.lib.pg_hji_lookup_dev(self.h, int(B), vp(x7_ptr), vp(V_ptr), vp(gradV_ptr)), "pg_hji_lookup_dev")
+
+    def hji_lookup8_dev(self, B, x7_ptr, out8_ptr):
+        """The packed lookup: out8 [B][8] = (V, gradV[0..6]) per row of x7 [B][7], device arrays of the library's element type.  Asynchronous on the handle's stream."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._chk(self.lib.pg_hji_lookup8_dev(self.h, int(B), vp(x7_ptr), vp(out8_ptr)), "pg_hji_lookup8_dev")
+
     HUMAN_MODES = {"hold": 0, "worst": 1, "script": 2}
     # the records a library adds to those of a rollout with record=True: (key, history setter, library, width)
     LIBRARY_RECORDS = (("applied", "pg_set_applied_history_dev", "actuator", 3), ("command", "pg_set_command_history_dev", "actuator", 3),
