@@ -579,7 +579,7 @@ int pg_refine_paths(pg_handle* h, int32_t n_path, int32_t Lmax, const int32_t* L
  *             the d_r and, on a closed path, S00 and det / S00;  chord_min over the chords of the OUTPUT waypoints, computed as h_j above.
  *   Sum       Block b = 0 .. 255 holds the waypoints [b c, min((b + 1) c, n)), c = ceil(n / 256), summed from 0 in order; the 256 block totals are summed by the
  *             tree of neighbouring pairs (T_0 + T_1, T_2 + T_3, ..; then those pairwise; ..).  The order depends on the path's own n alone.
- * A pair's bits depend on its own path and set alone: not on the batch, its order or n_wp_total.  Left out: choosing lambda (the set library and the stats are the tool),
+ * A pair's bits depend on its own path and set alone: not on the batch, its order or n_wp_total.  Choosing lambda is pg_tune_smoothing below.  Left out:
  * weights per waypoint inside pg_waypoint, smoothing the edges themselves, decimating (waypoints_from_tube(every=) stays the way), a device-pointer hand-over into
  * pg_fit_paths, least-squares splines with fewer knots than waypoints. */
 typedef struct pg_smooth_set {
@@ -615,6 +615,54 @@ pg_smooth_set pg_default_smooth_set(void);
  * waypoint: a pivot that is not > 0; a non-finite output; edge_L <= edge_R after keep_walls; two neighbouring output waypoints at the same point. */
 int pg_smooth_waypoints(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
                         int32_t n_sets, const pg_smooth_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats);
+
+/* Choosing the smoothing weight: every (path, tune set) pair of a library of waypoint lists and a library of tune sets smoothed as pg_smooth_waypoints smooths it, under
+ * the largest weight of a geometric ladder between lambda_lo and lambda_hi whose dev_rms does not exceed the set's target -- "move the points by that much rms and no
+ * more" -- searched and solved on the device in one launch (tests/wp_tune_numpy.py is its twin).  The scheme has only + - * / sqrt and exact comparisons, in double in
+ * both libraries, every operation rounded on its own: both libraries return the twin's bits.  A parenthesis is one rounded operation.
+ *   F         F(lambda) = dev_rms (Stats of pg_smooth_waypoints) of this path under `base` with that lambda: that scheme unchanged, Sum order included.
+ *   Ladder    For a bracket (lo, hi): c_0 = lo, c_16 = hi, then four levels of midpoints, each from its two neighbours on the level above:  c_8 = sqrt((c_0 c_16));
+ *             c_4 = sqrt((c_0 c_8)), c_12 = sqrt((c_8 c_16));  c_2, c_6, c_10, c_14 from c_0, c_4, c_8, c_12, c_16;  the odd ones from the even ones.
+ *   Round 0   The ladder of (lambda_lo, lambda_hi); F at all 17 candidates.  F(c_0) > target: verdict -1, lambda = c_0, the bracket (c_0, c_0), rms_lo = rms_hi =
+ *             F(c_0), done.  Else F(c_16) <= target: verdict +1, lambda = c_16, the bracket (c_16, c_16), rms_lo = rms_hi = F(c_16), done (a path of two waypoints has
+ *             F = 0 everywhere and always ends here).  Else verdict 0 and the narrowing.
+ *   Narrowing j* = the smallest j in 1 .. 16 with F(c_j) > target; the new bracket is (c_{j*-1}, c_{j*}), rms_lo = F(c_{j*-1}), rms_hi = F(c_{j*}).  The rule is total
+ *             (F(c_0) <= target < F(c_16) holds from round 0 on); it is bisection only where F is monotone.
+ *   Rounds    Round t = 1 .. rounds - 1: the ladder of the last bracket.  Stop: where two neighbouring candidates of that ladder are equal, the round evaluates nothing
+ *             and the search ends with the bracket it has.  Otherwise F at its 17 candidates (the two ends give what they gave before: evaluation is deterministic) and
+ *             the narrowing.  rounds_done counts the rounds that evaluated candidates, round 0 included.
+ *   monotone  1 if in every round that evaluated, F(c_j) <= F(c_{j+1}) for j = 0 .. 15; else 0.
+ *   Result    lambda = lo of the last bracket, so dev_rms <= target whenever verdict is 0 or +1.  waypoints_out and stats of the pair are those of pg_smooth_waypoints
+ *             under `base` with that lambda, bit for bit; rms_lo equals stats.dev_rms.
+ * A pair's bits depend on its own path and set alone.  Left out: criteria other than dev_rms (dev_max, a curvature bound, cross-validation), a target per window, a
+ * device-pointer hand-over into pg_fit_paths. */
+typedef struct pg_tune_set {
+    pg_smooth_set base;            /* windows, pin_ends, keep_walls as pg_smooth_waypoints reads them; base.lambda must be 0 */
+    double target;                 /* metres, finite and > 0: the dev_rms (Stats of pg_smooth_waypoints) not to exceed */
+    double lambda_lo, lambda_hi;   /* m^3, finite, 0 < lambda_lo < lambda_hi: the first bracket */
+    int32_t rounds;                /* 1 .. 8: each divides the bracket's ratio by its 16th root */
+    int32_t reserved;              /* 0 */
+} pg_tune_set;                     /* 152 bytes */
+typedef struct pg_tune_stats {     /* one per (path, set) pair, doubles */
+    double lambda;                 /* the chosen weight */
+    double lo, hi;                 /* the last bracket */
+    double rms_lo, rms_hi;         /* dev_rms at its ends */
+    double verdict;                /* 0 bracketed; -1 dev_rms(lambda_lo) > target already; +1 dev_rms(lambda_hi) <= target still */
+    double rounds_done;            /* rounds that evaluated candidates */
+    double monotone;               /* 1 if in every round dev_rms was non-decreasing along the ladder, else 0 */
+    double reserved;               /* 0 */
+} pg_tune_stats;                   /* 72 bytes */
+/* base = pg_default_smooth_set(), target 1e-3, lambda_lo 1e-6, lambda_hi 1e3, rounds 3, 0 */
+pg_tune_set pg_default_tune_set(void);
+/* specs, waypoints, waypoints_out [n_sets][n_wp_total], stats and the pair order path * n_sets + set mean what they mean in pg_smooth_waypoints: block k is the whole
+ * input array under set k, so one pg_fit_paths call still fits all sets.  tune [n_path * n_sets].  Each of the three outputs may be NULL.  Synchronous; nothing is
+ * installed.  A handle that never calls this launches what it launched before.
+ * PG_ERR_INVALID before the first allocation (the handle and its installed library are left unchanged): everything pg_smooth_waypoints refuses about specs, waypoints
+ * and `base`; base.lambda != 0; a target that is not finite and > 0; bounds that are not finite with 0 < lambda_lo < lambda_hi; rounds outside [1, 8]; reserved != 0;
+ * the scratch of all pairs beyond the allocation arithmetic.  After the launch and before anything is copied out: a pivot that is not > 0, or an F that is not finite,
+ * at a candidate of any evaluated round (the message names path, set and round); then pg_smooth_waypoints' four refusals for the final solve. */
+int pg_tune_smoothing(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
+                      int32_t n_sets, const pg_tune_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats, pg_tune_stats* tune);
 
 /* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
  * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car

@@ -876,6 +876,43 @@ end
 "{ 0, (0 x 4), (0 x 4), (1 x 4), 0, 0, 0, 0 } as the library states them (pg_default_smooth_set): the identity"
 default_smooth_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_smooth_set), PgSmoothSet, ())
 
+# Choosing the smoothing weight (pg_tune_smoothing): every (path, tune set) pair smoothed to a target rms, the weight searched on the device.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_tune_set (152 bytes): the smoothing set without a weight (base.lambda must be 0), the dev_rms not to exceed in metres, the first bracket of lambda in m^3, the rounds (1 .. 8), a reserved 0"
+struct PgTuneSet
+    base::PgSmoothSet
+    target::Float64
+    lambda_lo::Float64
+    lambda_hi::Float64
+    rounds::Int32
+    reserved::Int32
+end
+"PgTuneSet() is the library's default; windows, pin_ends and keep_walls as PgSmoothSet takes them"
+PgTuneSet(; target=1e-3, lambda_lo=1e-6, lambda_hi=1e3, rounds=3, windows=(), pin_ends=false, keep_walls=false) =
+    PgTuneSet(PgSmoothSet(; windows=windows, pin_ends=pin_ends, keep_walls=keep_walls), Float64(target), Float64(lambda_lo), Float64(lambda_hi), Int32(rounds), Int32(0))
+"pg_tune_stats (72 bytes), one per (path, set) pair: the chosen weight, the last bracket, dev_rms at its ends, the verdict (0 bracketed, -1 dev_rms(lambda_lo) > target, +1 dev_rms(lambda_hi) <= target), the rounds that evaluated, whether dev_rms was non-decreasing along every ladder"
+struct PgTuneStats
+    lambda::Float64
+    lo::Float64
+    hi::Float64
+    rms_lo::Float64
+    rms_hi::Float64
+    verdict::Float64
+    rounds_done::Float64
+    monotone::Float64
+    reserved::Float64
+end
+"specs and waypoints as smooth_waypoints! takes them -> (waypoints_out [n_wp_total, n_sets], stats [n_sets, n_path], tune [n_sets, n_path]): column k is the whole waypoint array under set k with the weight the search chose"
+function tune_smoothing!(mpc::BatchedTrajectoryTrackingMPC, specs::Vector{PgFitSpec}, waypoints::Vector{PgWaypoint}, sets::Vector{PgTuneSet})
+    (sizeof(PgTuneSet), sizeof(PgTuneStats), sizeof(PgSmoothStats)) == (152, 72, 72) || error("PigeonMI355X.jl: the pg_tune_smoothing structures differ from include/pigeon_mpc.h")
+    n, ns, nw = length(specs), length(sets), length(waypoints)
+    out = Matrix{PgWaypoint}(undef, nw, ns); stats = Matrix{PgSmoothStats}(undef, ns, n); tune = Matrix{PgTuneStats}(undef, ns, n)
+    check(mpc, ccall(sym(mpc, :pg_tune_smoothing), Cint, (Ptr{Cvoid}, Int32, Ptr{PgFitSpec}, Int32, Ptr{PgWaypoint}, Int32, Ptr{PgTuneSet}, Ptr{PgWaypoint}, Ptr{PgSmoothStats}, Ptr{PgTuneStats}),
+                     mpc.handle, Int32(n), specs, Int32(nw), waypoints, Int32(ns), sets, out, stats, tune), "pg_tune_smoothing")
+    out, stats, tune
+end
+"{ default_smooth_set, 1e-3, 1e-6, 1e3, 3, 0 } as the library states them (pg_default_tune_set)"
+default_tune_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_tune_set), PgTuneSet, ())
+
 # Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
 "pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
 struct PgStartSet

@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_refine_set", "pg_refine_paths", "pg_default_smooth_set", "pg_smooth_waypoints", "pg_default_start_set", "pg_make_starts",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_refine_set", "pg_refine_paths", "pg_default_smooth_set", "pg_smooth_waypoints", "pg_default_tune_set", "pg_tune_smoothing", "pg_default_start_set", "pg_make_starts",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -341,6 +341,23 @@ WP_SMOOTH_PROTOTYPES = {
 }
 
 
+class pg_tune_set(C.Structure):
+    """include/pigeon_mpc.h pg_tune_set: the smoothing set without a weight, the dev_rms not to exceed, the first bracket of lambda and the rounds."""
+    _fields_ = [("base", pg_smooth_set), ("target", C.c_double), ("lambda_lo", C.c_double), ("lambda_hi", C.c_double), ("rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class pg_tune_stats(C.Structure):
+    """include/pigeon_mpc.h pg_tune_stats: one per (path, set) pair."""
+    _fields_ = [(n, C.c_double) for n in ["lam", "lo", "hi", "rms_lo", "rms_hi", "verdict", "rounds_done", "monotone", "reserved"]]      # (lam: the header's `lambda`)
+
+
+# smoothing weight search (include/pigeon_mpc.h: pg_tune_smoothing)
+WP_TUNE_PROTOTYPES = {
+    "pg_tune_smoothing": [C.c_void_p, C.c_int32, C.POINTER(pg_fit_spec), C.c_int32, C.POINTER(pg_waypoint), C.c_int32, C.POINTER(pg_tune_set), C.POINTER(pg_waypoint),
+                          C.POINTER(pg_smooth_stats), C.POINTER(pg_tune_stats)],
+}
+
+
 START_RANGES = ["s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v"]      # the 13 channels of the draws, in their order
 START_MODES = ["s_mode", "e_mode", "steady", "time_mode", "other_mode"]
 
@@ -409,6 +426,8 @@ def load_library(precision="f64"):
     lib.pg_default_refine_set.restype = pg_refine_set
     lib.pg_default_smooth_set.argtypes = []
     lib.pg_default_smooth_set.restype = pg_smooth_set
+    lib.pg_default_tune_set.argtypes = []
+    lib.pg_default_tune_set.restype = pg_tune_set
     lib.pg_default_start_set.argtypes = []
     lib.pg_default_start_set.restype = pg_start_set
     lib.pg_default_route.argtypes = []

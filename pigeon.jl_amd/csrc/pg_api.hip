@@ -1654,6 +1654,21 @@ static const char* smooth_set_problem(const pg_smooth_set& s) {
     if (s.reserved != 0) return "reserved of a set must be 0";
     return nullptr;
 }
+// two writers of one output waypoint: the paths in the order of their first waypoint, neighbours compared (empty: none)
+static std::string wp_overlap_problem(int n_path, const pg_fit_spec* specs) {
+    std::vector<int> order((size_t)n_path);
+    for (int k = 0; k < n_path; k++) order[(size_t)k] = k;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return specs[a].wp0 != specs[b].wp0 ? specs[a].wp0 < specs[b].wp0 : a < b; });
+    for (int k = 0; k + 1 < n_path; k++) {
+        const int a = order[(size_t)k], b = order[(size_t)k + 1];
+        if (specs[a].wp0 + specs[a].n_wp > specs[b].wp0)
+            return "the waypoint ranges of path " + std::to_string(std::min(a, b)) + " and path " + std::to_string(std::max(a, b)) + " overlap";
+    }
+    return std::string();
+}
+// what a pair's final solve can report after the launch, in the order of the kernel's bad [4]
+static const char* const smooth_bad_text[4] = {"a pivot of the factorisation is not > 0", "the output is not finite", "edge_L <= edge_R after keep_walls",
+                                               "this output waypoint and the next lie at the same point"};
 int pg_smooth_waypoints(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
                         int32_t n_sets, const pg_smooth_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats) {
     if (!h) return PG_ERR_INVALID;
@@ -1667,17 +1682,9 @@ int pg_smooth_waypoints(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, 
         double C = 0.0;
         REQUIRE_NO(h, "pg_smooth_waypoints: ", fit_waypoints_problem(p, waypoints, C));
     }
-    {   // two writers of one output waypoint: the paths in the order of their first waypoint, neighbours compared
-        std::vector<int> order((size_t)n_path);
-        for (int k = 0; k < n_path; k++) order[(size_t)k] = k;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return specs[a].wp0 != specs[b].wp0 ? specs[a].wp0 < specs[b].wp0 : a < b; });
-        for (int k = 0; k + 1 < n_path; k++) {
-            const int a = order[(size_t)k], b = order[(size_t)k + 1];
-            if (specs[a].wp0 + specs[a].n_wp > specs[b].wp0) {
-                h->err = "pg_smooth_waypoints: the waypoint ranges of path " + std::to_string(std::min(a, b)) + " and path " + std::to_string(std::max(a, b)) + " overlap";
-                return PG_ERR_INVALID;
-            }
-        }
+    {
+        const std::string why = wp_overlap_problem(n_path, specs);
+        if (!why.empty()) { h->err = "pg_smooth_waypoints: " + why; return PG_ERR_INVALID; }
     }
     for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_smooth_waypoints: ", smooth_set_problem(sets[j]));
     std::vector<SmoothSpec> recs((size_t)n_path);
@@ -1717,14 +1724,109 @@ int pg_smooth_waypoints(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, 
     HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_pair * sizeof(pg_smooth_stats), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, 4 * n_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
-    static const char* const what[4] = {"a pivot of the factorisation is not > 0", "the output is not finite", "edge_L <= edge_R after keep_walls",
-                                        "this output waypoint and the next lie at the same point"};
     for (size_t k = 0; k < n_pair; k++) for (int c = 0; c < 4; c++) if (bad[4 * k + c] >= 0) {
         h->err = "pg_smooth_waypoints: path " + std::to_string(k / (size_t)n_sets) + ", set " + std::to_string(k % (size_t)n_sets) + ", waypoint " + std::to_string(bad[4 * k + c]) +
-                 ": " + what[c];
+                 ": " + smooth_bad_text[c];
         return PG_ERR_INVALID;
     }
     if (stats) memcpy(stats, st.data(), n_pair * sizeof(pg_smooth_stats));
+    return down_raw(h, waypoints_out, d_out, (size_t)n_sets * n_all * sizeof(pg_waypoint));
+}
+
+// ---- pg_tune_smoothing: the smoothing weight of every (path, tune set) pair searched on the device and the pair smoothed under it (pg_waypoint_tune.hip).  One launch,
+// one workgroup per pair; waypoints in, waypoints out: nothing is installed ----
+static_assert(sizeof(pg_tune_set) == 152 && sizeof(pg_tune_stats) == 72, "the sizes include/pigeon_mpc.h states");
+pg_tune_set pg_default_tune_set(void) {
+    pg_tune_set s; s.base = pg_default_smooth_set(); s.target = 1e-3; s.lambda_lo = 1e-6; s.lambda_hi = 1e3; s.rounds = 3; s.reserved = 0;
+    return s;
+}
+static const char* tune_set_problem(const pg_tune_set& s) {
+    if (const char* why = smooth_set_problem(s.base)) return why;
+    if (s.base.lambda != 0.0) return "base.lambda of a set must be 0 (the weight is what the call chooses)";
+    if (!(std::isfinite(s.target) && s.target > 0.0)) return "target of a set is finite and > 0";
+    if (!(std::isfinite(s.lambda_lo) && std::isfinite(s.lambda_hi) && 0.0 < s.lambda_lo && s.lambda_lo < s.lambda_hi)) return "the bounds of a set are finite with 0 < lambda_lo < lambda_hi";
+    if (!(s.rounds >= 1 && s.rounds <= 8)) return "rounds of a set lies in [1, 8]";
+    if (s.reserved != 0) return "reserved of a set must be 0";
+    return nullptr;
+}
+int pg_tune_smoothing(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
+                      int32_t n_sets, const pg_tune_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats, pg_tune_stats* tune) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, specs && waypoints && sets, "pg_tune_smoothing: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && n_wp_total >= 1, "pg_tune_smoothing: need n_path >= 1, n_sets >= 1 and n_wp_total >= 1");
+    REQUIRE_NO(h, "pg_tune_smoothing: ", pair_count_problem(n_path, n_sets, 2));
+    for (int k = 0; k < n_path; k++) {
+        const pg_fit_spec& p = specs[k];
+        REQUIRE(h, p.closed ? p.n_wp >= 5 : p.n_wp >= 2, "pg_tune_smoothing: an open path needs >= 2 waypoints, a closed one >= 5");
+        REQUIRE(h, p.wp0 >= 0 && p.wp0 < n_wp_total && p.n_wp <= n_wp_total - p.wp0, "pg_tune_smoothing: the waypoints of a path must lie inside [0, n_wp_total)");
+        double C = 0.0;
+        REQUIRE_NO(h, "pg_tune_smoothing: ", fit_waypoints_problem(p, waypoints, C));
+    }
+    {
+        const std::string why = wp_overlap_problem(n_path, specs);
+        if (!why.empty()) { h->err = "pg_tune_smoothing: " + why; return PG_ERR_INVALID; }
+    }
+    for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_tune_smoothing: ", tune_set_problem(sets[j]));
+    std::vector<SmoothSpec> recs((size_t)n_path);
+    size_t n_used = 0;
+    int rows_max = 1;                                         // the rows of the longest path
+    for (int k = 0; k < n_path; k++) {
+        rows_max = std::max(rows_max, specs[k].n_wp - 2);
+        SmoothSpec& r = recs[(size_t)k];
+        r.soff = (long long)n_used; r.wp0 = specs[k].wp0; r.n_wp = specs[k].n_wp; r.closed = specs[k].closed ? 1 : 0; r.pad = 0;
+        n_used += (size_t)specs[k].n_wp;                          // (<= n_wp_total: the ranges do not overlap)
+    }
+    // the search keeps its state in LDS where a path has at most WT_LDS_ROWS rows, the final solve where it has at most WS_LDS_ROWS; the scratch holds the search's
+    // state only where some path of the call is longer
+    const int tune_rows = std::min(rows_max, (int)WT_LDS_ROWS), lds_rows = std::min(rows_max, (int)WS_LDS_ROWS);
+    const int n_arr = rows_max <= (int)WT_LDS_ROWS ? (int)WT_ARRAYS_LDS : (int)WT_ARRAYS_SCRATCH;
+    REQUIRE(h, (double)n_sets * (double)n_wp_total * (double)WT_ARRAYS_SCRATCH * 8.0 < 4611686018427387904.0,
+            "pg_tune_smoothing: the scratch of all pairs is more than the allocation arithmetic holds");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t n_pair = (size_t)n_path * n_sets, n_all = (size_t)n_wp_total;
+    CallBufs D; pg_waypoint *d_in = nullptr, *d_out = nullptr; SmoothSpec* d_specs = nullptr; pg_tune_set* d_sets = nullptr; double* d_scr = nullptr;
+    pg_smooth_stats* d_stats = nullptr; pg_tune_stats* d_tune = nullptr; int *d_bad = nullptr, *d_bad_tune = nullptr;
+    HIPCHK(h, D.alloc(d_in, n_all));
+    HIPCHK(h, D.alloc(d_out, (size_t)n_sets * n_all));
+    HIPCHK(h, D.alloc(d_specs, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_scr, (size_t)n_sets * n_used * (size_t)n_arr));
+    HIPCHK(h, D.alloc(d_stats, n_pair));
+    HIPCHK(h, D.alloc(d_tune, n_pair));
+    HIPCHK(h, D.alloc(d_bad, 4 * n_pair));
+    HIPCHK(h, D.alloc(d_bad_tune, 2 * n_pair));
+    HIPCHK(h, to_device(d_in, waypoints, n_all));
+    for (int j = 0; j < n_sets; j++)                          // (every block starts as the input, copied on the device: a pair writes its own path's waypoints alone)
+        HIPCHK(h, hipMemcpyAsync(d_out + (size_t)j * n_all, d_in, n_all * sizeof(pg_waypoint), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, to_device(d_specs, recs.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_sets, sets, (size_t)n_sets));
+    WpTuneArgs A; A.n_sets = n_sets; A.n_wp_total = n_wp_total; A.lds_rows = lds_rows; A.tune_rows = tune_rows; A.n_arr = n_arr; A.n_used = (long long)n_used; A.specs = d_specs;
+    A.sets = d_sets; A.in = d_in; A.out = d_out; A.scratch = d_scr; A.stats = d_stats; A.tune = d_tune; A.bad = d_bad; A.bad_tune = d_bad_tune;
+    const size_t lds = std::max((size_t)WT_STATE * WT_CAND * (size_t)tune_rows, (size_t)7 * (size_t)lds_rows) * sizeof(double);      // (at most 60928 bytes)
+    hipLaunchKernelGGL(k_wp_tune, dim3((unsigned)n_pair), dim3(WS_THREADS), lds, h->stream, A);
+    LAUNCH_CHECK(h);
+    std::vector<pg_smooth_stats> st(n_pair);
+    std::vector<pg_tune_stats> tn(n_pair);
+    std::vector<int> bad(4 * n_pair), bad_tune(2 * n_pair);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_pair * sizeof(pg_smooth_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(tn.data(), d_tune, n_pair * sizeof(pg_tune_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, 4 * n_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad_tune.data(), d_bad_tune, 2 * n_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    for (size_t k = 0; k < n_pair; k++) {
+        const std::string who = "pg_tune_smoothing: path " + std::to_string(k / (size_t)n_sets) + ", set " + std::to_string(k % (size_t)n_sets);
+        if (bad_tune[2 * k] >= 0) {
+            h->err = who + ", round " + std::to_string(bad_tune[2 * k]) + ": " + (bad_tune[2 * k + 1] == 0 ? "a pivot of the factorisation is not > 0 at a candidate" : "dev_rms is not finite at a candidate");
+            return PG_ERR_INVALID;
+        }
+        for (int c = 0; c < 4; c++) if (bad[4 * k + c] >= 0) {
+            h->err = who + ", waypoint " + std::to_string(bad[4 * k + c]) + ": " + smooth_bad_text[c];
+            return PG_ERR_INVALID;
+        }
+    }
+    if (stats) memcpy(stats, st.data(), n_pair * sizeof(pg_smooth_stats));
+    if (tune) memcpy(tune, tn.data(), n_pair * sizeof(pg_tune_stats));
     return down_raw(h, waypoints_out, d_out, (size_t)n_sets * n_all * sizeof(pg_waypoint));
 }
 

@@ -31,37 +31,26 @@ PG_DEV double ws_tree(double x, double* sT, int lane, int wave) {
     return a + b;
 }
 
-__global__ __launch_bounds__(WS_THREADS) void k_wp_smooth(WpSmoothArgs P) {
+// Result: g_i = y_i - (lambda (winv_i (((p_im gamma_im) + (q_i gamma_i)) + (p_i gamma_ip))))
+PG_DEV double ws_moved(double y, double lambda, double w, double pm, double q, double p0, double gm, double g0, double gp) {
 #pragma clang fp contract(off)
-    extern __shared__ double sRec[];                              // l1, l2, d, z of four right-hand sides: 7 x lds_rows doubles
-    __shared__ double sW[WS_THREADS / 64], sT[WS_THREADS / 64];
-    __shared__ double sR[WS_THREADS / 64][6];                     // dev max, its index, width min, chord min, n_outside, -
-    __shared__ int sB[WS_THREADS / 64][4];
-    __shared__ double sPiv; __shared__ int sBadRow;
+    const double a = pm * gm, b = q * g0, c = p0 * gp;
+    const double ab = a + b;
+    const double qg = ab + c;
+    const double wq = w * qg;
+    const double lw = lambda * wq;
+    return y - lw;
+}
+
+// The phases that do not depend on lambda, strided over the waypoints by the workgroup: chords h, p = 1 / h and the slopes (into sE, sN), U, winv; ends on a barrier.
+// sW: one double per wavefront
+PG_DEV void ws_setup(const SmoothSpec S, const pg_smooth_set& T, const pg_waypoint* __restrict__ W, double* const aH, double* const aP, double* const aU, double* const aWi,
+                     double* const aGE, double* const aGN, double* const sW) {
+#pragma clang fp contract(off)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t k = blockIdx.x;
-    const int path = (int)(k / (size_t)P.n_sets), set = (int)(k - (size_t)path * P.n_sets);
-    const SmoothSpec S = P.specs[path];
-    const pg_smooth_set T = P.sets[set];
     const int n = S.n_wp, nsp = S.closed ? n : n - 1;
     const bool closed = S.closed != 0;
-    const pg_waypoint* __restrict__ W = P.in + S.wp0;             // every waypoint index below is < n_wp
-    pg_waypoint* const O = P.out + (size_t)set * (size_t)P.n_wp_total + (size_t)S.wp0;
-    double* const A = P.scratch + ((size_t)set * (size_t)P.n_used + (size_t)S.soff) * WS_ARRAYS;
-    const size_t sn = (size_t)n;
-    double* const aH = A + WS_H * sn; double* const aP = A + WS_P * sn; double* const aU = A + WS_U * sn; double* const aWi = A + WS_WINV * sn;
-    double* const aD = A + WS_D * sn; double* const aE1 = A + WS_E1 * sn; double* const aE2 = A + WS_E2 * sn; double* const aFE = A + WS_FE * sn; double* const aFN = A + WS_FN * sn;
-    double* const aGE = A + WS_GE * sn; double* const aGN = A + WS_GN * sn;
-    // the rows of the band system: 1 .. n - 2 of an open path, 0 .. n - 3 of a closed one (its last two unknowns are the border)
-    const int m = n - 2, base = closed ? 0 : 1, nrhs = closed ? 4 : 2;
-    const bool in_lds = m <= P.lds_rows;
-    const size_t rs = in_lds ? (size_t)P.lds_rows : sn;           // m <= rs
-    double* const rec = in_lds ? sRec : A + WS_L1 * sn;
-    double* const rL1 = rec; double* const rL2 = rec + rs; double* const rPv = rec + 2 * rs; double* const rZ = rec + 3 * rs;
-    auto prev = [&](int i) -> int { return i > 0 ? i - 1 : n - 1; };
     auto next = [&](int i) -> int { return i + 1 == n ? 0 : i + 1; };
-    const double lambda = T.lambda;
-
     // ---- chords, 1 / h and slopes (into the arrays gamma takes later), one span per thread; place n - 1 of an open path holds 0 ----
     for (int j = tid; j < n; j += WS_THREADS) {
         double h = 0.0, p = 0.0, sE = 0.0, sN = 0.0;
@@ -103,6 +92,35 @@ __global__ __launch_bounds__(WS_THREADS) void k_wp_smooth(WpSmoothArgs P) {
         aWi[i] = w;
     }
     __syncthreads();
+}
+
+// One pair: the whole scheme for the path S (its waypoints W, its output O) under the set T with the weight `lambda`, by the 256 threads of a workgroup.  A: the pair's
+// WS_ARRAYS arrays of n_wp doubles in scratch; sRec: dynamic LDS of 7 x lds_rows doubles; stat, bad [4]: the pair's records.  k_wp_smooth calls it with T.lambda,
+// k_wp_tune (pg_waypoint_tune.hip) with the weight it has chosen: one text, so the two return the same bits
+PG_DEV void ws_pair(const SmoothSpec S, const pg_smooth_set& T, const double lambda, const int lds_rows, const pg_waypoint* __restrict__ W, pg_waypoint* const O, double* const A,
+                    double* const sRec, pg_smooth_stats* const stat, int* const bad) {
+#pragma clang fp contract(off)
+    __shared__ double sW[WS_THREADS / 64], sT[WS_THREADS / 64];
+    __shared__ double sR[WS_THREADS / 64][6];                     // dev max, its index, width min, chord min, n_outside, -
+    __shared__ int sB[WS_THREADS / 64][4];
+    __shared__ double sPiv; __shared__ int sBadRow;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = S.n_wp, nsp = S.closed ? n : n - 1;             // every waypoint index below is < n_wp
+    const bool closed = S.closed != 0;
+    const size_t sn = (size_t)n;
+    double* const aH = A + WS_H * sn; double* const aP = A + WS_P * sn; double* const aU = A + WS_U * sn; double* const aWi = A + WS_WINV * sn;
+    double* const aD = A + WS_D * sn; double* const aE1 = A + WS_E1 * sn; double* const aE2 = A + WS_E2 * sn; double* const aFE = A + WS_FE * sn; double* const aFN = A + WS_FN * sn;
+    double* const aGE = A + WS_GE * sn; double* const aGN = A + WS_GN * sn;
+    // the rows of the band system: 1 .. n - 2 of an open path, 0 .. n - 3 of a closed one (its last two unknowns are the border)
+    const int m = n - 2, base = closed ? 0 : 1, nrhs = closed ? 4 : 2;
+    const bool in_lds = m <= lds_rows;
+    const size_t rs = in_lds ? (size_t)lds_rows : sn;           // m <= rs
+    double* const rec = in_lds ? sRec : A + WS_L1 * sn;
+    double* const rL1 = rec; double* const rL2 = rec + rs; double* const rPv = rec + 2 * rs; double* const rZ = rec + 3 * rs;
+    auto prev = [&](int i) -> int { return i > 0 ? i - 1 : n - 1; };
+    auto next = [&](int i) -> int { return i + 1 == n ? 0 : i + 1; };
+
+    ws_setup(S, T, W, aH, aP, aU, aWi, aGE, aGN, sW);
     // ---- the band entries of every row and the right-hand sides, in closed form ----
     for (int i = tid; i < n; i += WS_THREADS) {
         const int im = prev(i), ip = next(i);
@@ -168,16 +186,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_wp_smooth(WpSmoothArgs P) {
         const double npm = -pm;
         const double q = npm - p0;
         const double w = aWi[i];
-        auto moved = [&](double y, const double* g) -> double {
-#pragma clang fp contract(off)
-            const double a = pm * g[im], b = q * g[i], c = p0 * g[ip];
-            const double ab = a + b;
-            const double qg = ab + c;
-            const double wq = w * qg;
-            const double lw = lambda * wq;
-            return y - lw;
-        };
-        O[i].E = moved(W[i].E, aGE); O[i].N = moved(W[i].N, aGN);
+        O[i].E = ws_moved(W[i].E, lambda, w, pm, q, p0, aGE[im], aGE[i], aGE[ip]); O[i].N = ws_moved(W[i].N, lambda, w, pm, q, p0, aGN[im], aGN[i], aGN[ip]);
     }
     __syncthreads();
     // ---- the edges, the displacement, the bend and the chords of the result ----
@@ -273,8 +282,17 @@ __global__ __launch_bounds__(WS_THREADS) void k_wp_smooth(WpSmoothArgs P) {
         const double ms = d2tot / (double)n;
         R.dev_max = dmax; R.dev_rms = sqrt(ms); R.i_dev_max = imax; R.bend = btot; R.n_outside = nout; R.width_min = wmin; R.pivot_min = pivot_min; R.chord_min = cmin;
         R.reserved = 0.0;
-        P.stats[k] = R;
-        int* const bad = P.bad + 4 * k;
+        *stat = R;
         bad[0] = bad_piv; bad[1] = bad_fin; bad[2] = bad_wall; bad[3] = bad_chord;
     }
+}
+
+__global__ __launch_bounds__(WS_THREADS) void k_wp_smooth(WpSmoothArgs P) {
+    extern __shared__ double sRec[];                              // l1, l2, d, z of four right-hand sides: 7 x lds_rows doubles
+    const size_t k = blockIdx.x;
+    const int path = (int)(k / (size_t)P.n_sets), set = (int)(k - (size_t)path * P.n_sets);
+    const SmoothSpec S = P.specs[path];
+    const pg_smooth_set T = P.sets[set];
+    ws_pair(S, T, T.lambda, P.lds_rows, P.in + S.wp0, P.out + (size_t)set * (size_t)P.n_wp_total + (size_t)S.wp0,
+            P.scratch + ((size_t)set * (size_t)P.n_used + (size_t)S.soff) * WS_ARRAYS, sRec, P.stats + k, P.bad + 4 * k);
 }

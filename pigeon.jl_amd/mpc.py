@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, smooth as _default_smooth, refine_parts as _refine_parts, REFINE_M_MAX
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, smooth as _default_smooth, tune as _default_tune, refine_parts as _refine_parts, REFINE_M_MAX
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -22,6 +22,7 @@ SPEED_PLAN_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int
 PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fields_])      # 48 bytes, the layout of pg_path_stats
 OFFSET_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_offset_stats._fields_])      # 64 bytes, the layout of pg_offset_stats
 SMOOTH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_smooth_stats._fields_])      # 72 bytes, the layout of pg_smooth_stats
+TUNE_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_tune_stats._fields_])      # 72 bytes, the layout of pg_tune_stats
 REFINE_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_refine_stats._fields_])      # 64 bytes, the layout of pg_refine_stats
 CLIP_STATS_DTYPE = np.dtype([("width_min", np.float64), ("u_width_min", np.float64), ("reserved_d", np.float64, (2,))] + [(n, np.int32) for n in ("n_clip_L", "n_clip_R", "n_blocked", "n_centre_out", "n_seen", "n_ignored")] + [("reserved", np.int32, (2,))])      # 64 bytes, the layout of pg_clip_stats
 OBSTACLE_REPORT_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_obstacle_report._fields_])      # 64 bytes, the layout of pg_obstacle_report
@@ -650,6 +651,57 @@ class BatchedTrajectoryTrackingMPC:
         flat = np.frombuffer(out, dtype=np.float64).reshape(ns, nw, 4)
         smoothed = [[[dict(E=float(w[0]), N=float(w[1]), edge_L=float(w[2]), edge_R=float(w[3])) for w in flat[k, s.wp0:s.wp0 + s.n_wp]] for s in specs] for k in range(ns)]
         return smoothed, np.frombuffer(st, dtype=SMOOTH_STATS_DTYPE).copy().reshape(n, ns)
+
+    # ---- choosing the smoothing weight (pg_tune_smoothing): every (path, tune set) pair smoothed to a target rms, the weight searched on the device ----
+    @classmethod
+    def pack_tunes(cls, sets):
+        """vehicles.tune(...) dicts (one, or a list) or pg_tune_set structures -> a ctypes array of pg_tune_set.  Raises ValueError for a set outside the ranges of
+        include/pigeon_mpc.h (the library refuses the same sets with PG_ERR_INVALID)."""
+        def fill(rec, p):
+            unknown = set(p) - {"base", "target", "lambda_lo", "lambda_hi", "rounds"}
+            if unknown:
+                raise ValueError(f"tune_smoothing: {sorted(unknown)} are not fields of a tune set")
+            full = _default_tune(**{k: v for k, v in p.items() if k != "base"})
+            rec.base = cls.pack_smooths([p.get("base", full["base"])])[0]
+            rec.target, rec.lambda_lo, rec.lambda_hi, rec.rounds, rec.reserved = full["target"], full["lambda_lo"], full["lambda_hi"], full["rounds"], 0
+        arr = cls._pack(_lib.pg_tune_set, [sets] if isinstance(sets, (dict, _lib.pg_tune_set)) else sets, fill)
+        if len(arr) < 1:
+            raise ValueError("tune_smoothing: at least one tune set")
+        for k, r in enumerate(arr):
+            cls.pack_smooths([r.base])
+            if r.base.lam != 0.0:
+                raise ValueError(f"tune_smoothing: base.lam of set {k} must be 0 (the weight is what the call chooses)")
+            if not (math.isfinite(r.target) and r.target > 0.0):
+                raise ValueError(f"tune_smoothing: target of set {k} is finite and > 0")
+            if not (math.isfinite(r.lambda_lo) and math.isfinite(r.lambda_hi) and 0.0 < r.lambda_lo < r.lambda_hi):
+                raise ValueError(f"tune_smoothing: the bounds of set {k} are finite with 0 < lambda_lo < lambda_hi")
+            if not 1 <= r.rounds <= 8:
+                raise ValueError(f"tune_smoothing: rounds of set {k} lies in [1, 8]")
+            if r.reserved != 0:
+                raise ValueError(f"tune_smoothing: reserved of set {k} must be 0")
+        return arr
+
+    def tune_smoothing(self, paths, sets):
+        """Surveyed waypoints smoothed to a target rms on the device (pg_tune_smoothing; the scheme is stated in include/pigeon_mpc.h): for every (path, set) pair the
+        largest weight of a geometric ladder between lambda_lo and lambda_hi whose dev_rms stays within the set's target, and the path smoothed under it.  paths as
+        smooth_waypoints takes them, sets = vehicles.tune(target=.., lambda_lo=.., lambda_hi=.., rounds=.., pin_ends=.., keep_walls=.., windows=[..]) dicts.  Returns
+        (smoothed, stats, tune): smoothed and stats as smooth_waypoints returns them, tune a structured array [n_path][n_sets] with the fields of pg_tune_stats (lam,
+        lo, hi, rms_lo, rms_hi, verdict, rounds_done, monotone)."""
+        paths = [dict(p) for p in paths]
+        for k, p in enumerate(paths):
+            if len(p.get("waypoints", ())) < (5 if p.get("closed", False) else 2):
+                raise ValueError(f"tune_smoothing: path {k} needs 2 waypoints (a closed path 5)")
+            p.setdefault("n_knots", 3)
+        specs, wps, _ = self.pack_fit_specs(paths)
+        arr = self.pack_tunes(sets)
+        n, ns, nw = len(specs), len(arr), len(wps)
+        out = (_lib.pg_waypoint * (ns * nw))()
+        st = (_lib.pg_smooth_stats * (n * ns))()
+        tn = (_lib.pg_tune_stats * (n * ns))()
+        self._chk(self.lib.pg_tune_smoothing(self.h, n, specs, nw, wps, ns, arr, out, st, tn), "pg_tune_smoothing")
+        flat = np.frombuffer(out, dtype=np.float64).reshape(ns, nw, 4)
+        smoothed = [[[dict(E=float(w[0]), N=float(w[1]), edge_L=float(w[2]), edge_R=float(w[3])) for w in flat[k, s.wp0:s.wp0 + s.n_wp]] for s in specs] for k in range(ns)]
+        return smoothed, np.frombuffer(st, dtype=SMOOTH_STATS_DTYPE).copy().reshape(n, ns), np.frombuffer(tn, dtype=TUNE_STATS_DTYPE).copy().reshape(n, ns)
 
     # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
     @classmethod

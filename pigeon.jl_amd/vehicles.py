@@ -442,6 +442,15 @@ def smooth(**overrides):
     return s
 
 
+def tune(target=1e-3, lambda_lo=1e-6, lambda_hi=1e3, rounds=3, **smooth_kw):
+    """One tune set for tune_smoothing (pg_tune_set).  tune() is the library's default (pg_default_tune_set).  target: the rms displacement in metres not to exceed --
+    how good the surveyed positions are, say 1e-3 for positions rounded to a millimetre.  lambda_lo < lambda_hi: the first bracket of the weight in m^3.  rounds: 1 .. 8,
+    each divides the bracket's ratio by its 16th root.  smooth_kw: pin_ends, keep_walls and windows as smooth() takes them; the weight itself is what the call chooses."""
+    if "lam" in smooth_kw:
+        raise KeyError("lam is what tune_smoothing chooses: give target, lambda_lo and lambda_hi")
+    return dict(base=smooth(**smooth_kw), target=float(target), lambda_lo=float(lambda_lo), lambda_hi=float(lambda_hi), rounds=int(rounds))
+
+
 def smooth_window(u_lo, u_hi, factor=0.0):
     """One window of a smoothing set: the waypoints whose cumulative chord length (metres from the path's first waypoint) lies in [u_lo, u_hi] get the inverse weight
     `factor` -- 0 pins them ("do not touch the chicane"), above 1 smooths them more than the rest."""
