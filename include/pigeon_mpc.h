@@ -664,6 +664,91 @@ pg_tune_set pg_default_tune_set(void);
 int pg_tune_smoothing(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
                       int32_t n_sets, const pg_tune_set* sets, pg_waypoint* waypoints_out, pg_smooth_stats* stats, pg_tune_stats* tune);
 
+/* The line inside the tube: every (path, line set) pair of a library of waypoint lists and a library of line sets as waypoints moved along their normals, each inside its
+ * own edge_R .. edge_L, to the least discrete bending energy -- the line of least curvature the walls allow, which pg_plan_speeds turns into speed --, computed on the
+ * device.  Waypoints in, waypoints out, as pg_smooth_waypoints: the output goes straight into pg_fit_paths.  The reference reads its paths from files
+ * (src/ros_integration.jl:13-16), so the scheme is build-defined (tests/line_opt_numpy.py is its twin).  Waypoints are doubles in both libraries and ALL arithmetic is
+ * double, every operation rounded on its own (no contraction); the scheme has only + - * / sqrt and exact comparisons, so both libraries return the twin's bits in every
+ * output and stat.  A parenthesis is one rounded operation, a sum or product without one is taken from the left.  n = n_wp; im = i - 1, ip = i + 1, modulo n.
+ *   Chords    h_j, p_j = 1 / h_j and the slopes of the INPUT waypoints exactly as pg_smooth_waypoints states them (Chords; place n - 1 of an open path holds 0),
+ *             q_i = (-p_im) - p_i, and U as there (U).
+ *   Normal    The tangent at waypoint i is the chord from waypoint im to waypoint ip: tE = E_ip - E_im, tN = N_ip - N_im; at the two ends of an open path it is
+ *             one-sided (waypoint 0: from 0 to 1; waypoint n - 1: from n - 2 to n - 1).  v = sqrt((tE tE) + (tN tN)), nE = (-tN) / v, nN = tE / v: the library's left
+ *             normal (dE/ds = -sin psi, dN/ds = cos psi, e positive to the left: the convention of Walls in pg_smooth_waypoints).  The unknown alpha_i moves waypoint i
+ *             by alpha_i metres along n_i.
+ *   Bend rows Every waypoint j with two neighbours has a row (all of a closed path; 1 .. n - 2 of an open one): f_j = slope_j - slope_jm per coordinate, the weight
+ *             w_j = 2 / (h_jm + h_j); a waypoint without a row (the two ends of an open path) has w_j = 0.  The energy is
+ *               J(alpha) = Sum_j w_j |f_j + (p_jm alpha_jm n_jm) + (q_j alpha_j n_j) + (p_j alpha_jp n_jp)|^2,
+ *             the second divided difference of the moved points over the INPUT's chords (the usual linearisation: chords and normals stay the input's).
+ *   Hessian   H = A^T W A + mu I, pentadiagonal in alpha and cyclic on a closed path.  With a0_i, a1_i, a2_i the closed forms of pg_smooth_waypoints (System) with w in
+ *             the place of winv, each taken as 0 + (1 a) (that band with lambda = 1 and 0 in the place of its R terms), and the dot products c0_i = (nE_i nE_i) + (nN_i nN_i), c1_i = (nE_i nE_ip) + (nN_i nN_ip), c2_i = (nE_i nE_ip2) + (nN_i nN_ip2)
+ *             (ip2 = i + 2 modulo n):  D_i = (c0_i a0_i) + mu;  E1_i = c1_i a1_i  [the place (i, ip)];  E2_i = c2_i a2_i  [the place (i, ip + 1)].  On an open path
+ *             p_{n-1} = 0 and w_0 = w_{n-1} = 0 make the places that would wrap 0.
+ *             g = A^T W f:  with k_y,j = w_j f_y,j per coordinate y,  s_y = ((p_im k_y,im) + (q_i k_y,i)) + (p_i k_y,ip);  g_i = (nE_i s_E) + (nN_i s_N).
+ *   Box       margin_i = margin; then for k = 0 .. n_win - 1 in turn: where u_lo[k] <= U_i <= u_hi[k], margin_i = win_margin[k] and pinned_i = (win_pin[k] != 0) (the
+ *             last listed window that holds U_i decides both).  lo_i = max(edge_R_i + margin_i, -alpha_max), hi_i = min(edge_L_i - margin_i, alpha_max); a pinned
+ *             waypoint has lo_i = hi_i = 0; pin_ends pins the two ends of an OPEN path.  clip(x)_i = c where c = x if x > lo_i else lo_i, then hi_i where c > hi_i.
+ *   Solve     ADMM with the scaled dual and ONE factorisation of K = H + rho I, whose band is (D_i + rho, E1_i, E2_i).  The band recurrence, the way back and the
+ *             bordering are those of pg_smooth_waypoints (Band, Closed) word for word: on an open path over all n rows (m = n); on a closed one the band is the rows
+ *             0 .. n - 3 with the border a = n - 2, b = n - 1, and Za, Zb, S00, S01, S11 and det are computed once.
+ *             Start: z_i = clip(0)_i, u_i = 0.  Iteration k = 1, 2, ..:
+ *               b_i = (rho (z_i - u_i)) - g_i;   x = K^-1 b;   z'_i = clip(x_i + u_i);   u_i = u_i + (x_i - z'_i);
+ *               r_prim = max_i |x_i - z'_i|;   r_dual = rho (max_i |z'_i - z_i|);   z = z'.
+ *             Both residuals are maxima (from 0, by >), so their order cannot show.  The solve stops after `iters` iterations, or after the first iteration with
+ *             r_prim <= tol and r_dual <= tol (tol = 0 runs them all unless both residuals are exactly 0); iters_done = k.
+ *   Result    alpha = z, inside the box by construction whatever the iteration count.  E_out = E + (alpha nE), N_out = N + (alpha nN); a waypoint with alpha = 0
+ *             returns its input bits (copied, not computed).  keep_walls: edge_L = edge_L - alpha, edge_R = edge_R - alpha (the walls stay where they were surveyed,
+ *             so a second call re-linearises about the first result); else both are copied.
+ *   Stats     term_i(alpha) = w_i ((rE rE) + (rN rN)) with r_y = ((f_y,i + (p_im (alpha_im n_y,im))) + (q_i (alpha_i n_y,i))) + (p_i (alpha_ip n_y,ip));
+ *             bend_in = Sum_i w_i ((fE_i fE_i) + (fN_i fN_i)) = J(0), bend_out = Sum_i term_i(alpha) = J(alpha), by the Sum rule of pg_smooth_waypoints;
+ *             alpha_abs_max and the smallest i that reaches it;  n_active counts alpha_i == lo_i or alpha_i == hi_i (a pinned waypoint counts);  r_prim, r_dual of
+ *             the last iteration;  pivot_min over the d_r and, on a closed path, S00 and det / S00;  chord_min over the chords of the OUTPUT waypoints, computed as
+ *             h_j above;  width_min over (edge_L - edge_R) of the output.
+ * A pair's bits depend on its own path and set alone.  The scheme is for waypoints METRES apart: the bend Hessian's condition grows like n^4, and on a dense survey (the
+ * recorded ovals: 999 waypoints 0.24 m apart) this ADMM does not converge in 1000 iterations at any rho -- thin it with waypoints_from_tube(every=) first.  r_prim,
+ * r_dual and iters_done tell the caller.  Left out: re-linearising inside the call (call it again on its output), minimum-time objectives, a curvature bound, weights
+ * per waypoint, a device-pointer hand-over into pg_fit_paths, an adaptive rho. */
+typedef struct pg_line_set {
+    double mu;                /* 1/m^3, finite and > 0: the regularisation mu I of the Hessian */
+    double rho;               /* 1/m^3, finite and > 0: the ADMM penalty */
+    double margin;            /* metres, finite and >= 0: kept between the line and each edge */
+    double alpha_max;         /* metres, finite and > 0: the largest move along the normal */
+    double tol;               /* metres, finite and >= 0: stops where r_prim <= tol and r_dual <= tol */
+    double u_lo[4], u_hi[4];  /* the first n_win windows, in metres of the path's cumulative chord length U; u_lo <= u_hi, neither NaN */
+    double win_margin[4];     /* the margin inside window k: finite and >= 0 */
+    int32_t win_pin[4];       /* != 0: window k pins its waypoints (lo = hi = 0) */
+    int32_t iters;            /* 1 .. 4096 */
+    int32_t n_win;            /* 0 .. 4 */
+    int32_t pin_ends;         /* != 0: the two end waypoints of an OPEN path do not move; not looked at on a closed path */
+    int32_t keep_walls;       /* != 0: edge_L and edge_R of a moved waypoint are shifted by -alpha */
+    int32_t reserved[2];      /* 0 */
+} pg_line_set;                /* 176 bytes */
+typedef struct pg_line_stats {     /* one per (path, set) pair; doubles, computed in double in both libraries */
+    double bend_in, bend_out; /* J(0) and J(alpha), 1/m */
+    double alpha_abs_max;     /* metres */
+    double i_alpha_max;       /* the waypoint (counted from the path's first) of alpha_abs_max */
+    double n_active;          /* waypoints whose alpha is at a bound */
+    double r_prim, r_dual;    /* of the last iteration */
+    double iters_done;
+    double pivot_min;         /* the smallest pivot of the factorisation of H + rho I */
+    double chord_min;         /* the smallest chord of the output waypoints */
+    double width_min;         /* the smallest edge_L - edge_R of the output */
+    double reserved;          /* 0 */
+} pg_line_stats;              /* 96 bytes */
+/* { mu 1e-6, rho 0.1, margin 0.5, alpha_max 2, tol 0, windows {0 x 4}, {0 x 4}, {0 x 4}, {0 x 4}, iters 1000, 0, 0, 0, {0, 0} }: mu and rho want scaling by
+ * 1 / h_mean^3 of the path (vehicles.line does it in the Python mirror) */
+pg_line_set pg_default_line_set(void);
+/* specs, waypoints, waypoints_out [n_sets][n_wp_total] and the pair order path * n_sets + set mean what they mean in pg_smooth_waypoints; stats [n_path * n_sets].
+ * waypoints_out and stats may each be NULL.  Nothing is installed: waypoints are not a library.  Synchronous.  A handle that never calls this launches what it launched
+ * before.
+ * PG_ERR_INVALID before the first allocation (the handle and its installed library are left unchanged): everything pg_smooth_waypoints refuses about specs and waypoints
+ * (a closed path of fewer than 5 waypoints and overlapping ranges included); mu, rho or alpha_max that is not finite and > 0; margin, tol or a listed window's margin
+ * that is not finite and >= 0; iters outside [1, 4096]; n_win outside [0, 4]; a listed window with a NaN bound or u_lo > u_hi; reserved != 0; a waypoint with lo > hi
+ * (the message names path, set and waypoint); the scratch of all pairs beyond the allocation arithmetic.  After the launch and before anything is copied out, naming
+ * path, set and waypoint: a pivot that is not > 0; a non-finite output; two neighbouring output waypoints at the same point. */
+int pg_optimize_line(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
+                     int32_t n_sets, const pg_line_set* sets, pg_waypoint* waypoints_out, pg_line_stats* stats);
+
 /* Making the starts (pg_make_starts): the inputs of a batch -- state, control, t0, other car, time offset, what pg_set_inputs takes -- placed on the INSTALLED trajectory
  * library under a library of start sets, on the device, one lane per instance (pg_start_make.hip: k_make_starts).  The reference receives its state from the car
  * (src/ros_integration.jl:48-99), so the feature is build-defined (tests/start_make_numpy.py is its numpy twin).  After pg_make_paths / pg_fit_paths / pg_plan_speeds

@@ -913,6 +913,58 @@ end
 "{ default_smooth_set, 1e-3, 1e-6, 1e3, 3, 0 } as the library states them (pg_default_tune_set)"
 default_tune_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_tune_set), PgTuneSet, ())
 
+# The line inside the tube (pg_optimize_line): every (path, line set) pair moved along its normals to the least bending energy the walls allow.  NOT EXECUTED in the build container, like the rest of this file.
+"pg_line_set (176 bytes): mu and rho in 1/m^3 (scale both by 1 / h_mean^3 of the path), the margin to each edge, the largest move, the stopping tolerance, up to four windows in the cumulative chord length with their own margin or a pin, iters (1 .. 4096), the flags, two reserved zeros"
+struct PgLineSet
+    mu::Float64
+    rho::Float64
+    margin::Float64
+    alpha_max::Float64
+    tol::Float64
+    u_lo::NTuple{4,Float64}
+    u_hi::NTuple{4,Float64}
+    win_margin::NTuple{4,Float64}
+    win_pin::NTuple{4,Int32}
+    iters::Int32
+    n_win::Int32
+    pin_ends::Int32
+    keep_walls::Int32
+    reserved::NTuple{2,Int32}
+end
+"PgLineSet(h_mean=3.74) is mu = 1e-6 / h^3, rho = 0.1 / h^3; windows: (u_lo, u_hi, margin, pin) entries"
+function PgLineSet(; h_mean=1.0, mu=1e-6, rho=0.1, margin=0.5, alpha_max=2.0, tol=0.0, iters=1000, windows=(), pin_ends=false, keep_walls=false)
+    length(windows) <= 4 || error("PgLineSet: at most 4 windows")
+    pad(f, d) = ntuple(j -> j <= length(windows) ? f(windows[j]) : d, 4)
+    PgLineSet(mu / h_mean^3, rho / h_mean^3, margin, alpha_max, tol, pad(w -> Float64(w[1]), 0.0), pad(w -> Float64(w[2]), 0.0), pad(w -> Float64(w[3]), 0.0), pad(w -> Int32(w[4] ? 1 : 0), Int32(0)),
+              Int32(iters), Int32(length(windows)), Int32(pin_ends), Int32(keep_walls), (Int32(0), Int32(0)))
+end
+"pg_line_stats (96 bytes), one per (path, set) pair: J(0) and J(alpha), the largest |alpha| and its waypoint, the waypoints at a bound, both residuals of the last iteration, the iterations done, the smallest pivot, the smallest chord and width of the output"
+struct PgLineStats
+    bend_in::Float64
+    bend_out::Float64
+    alpha_abs_max::Float64
+    i_alpha_max::Float64
+    n_active::Float64
+    r_prim::Float64
+    r_dual::Float64
+    iters_done::Float64
+    pivot_min::Float64
+    chord_min::Float64
+    width_min::Float64
+    reserved::Float64
+end
+"specs and waypoints as smooth_waypoints! takes them -> (waypoints_out [n_wp_total, n_sets], stats [n_sets, n_path]): column k is the whole waypoint array under set k"
+function optimize_line!(mpc::BatchedTrajectoryTrackingMPC, specs::Vector{PgFitSpec}, waypoints::Vector{PgWaypoint}, sets::Vector{PgLineSet})
+    (sizeof(PgLineSet), sizeof(PgLineStats)) == (176, 96) || error("PigeonMI355X.jl: the pg_optimize_line structures differ from include/pigeon_mpc.h")
+    n, ns, nw = length(specs), length(sets), length(waypoints)
+    out = Matrix{PgWaypoint}(undef, nw, ns); stats = Matrix{PgLineStats}(undef, ns, n)
+    check(mpc, ccall(sym(mpc, :pg_optimize_line), Cint, (Ptr{Cvoid}, Int32, Ptr{PgFitSpec}, Int32, Ptr{PgWaypoint}, Int32, Ptr{PgLineSet}, Ptr{PgWaypoint}, Ptr{PgLineStats}),
+                     mpc.handle, Int32(n), specs, Int32(nw), waypoints, Int32(ns), sets, out, stats), "pg_optimize_line")
+    out, stats
+end
+"{ 1e-6, 0.1, 0.5, 2, 0, no windows, 1000, 0, 0, 0 } as the library states them (pg_default_line_set)"
+default_line_set(mpc::BatchedTrajectoryTrackingMPC) = ccall(sym(mpc, :pg_default_line_set), PgLineSet, ())
+
 # Making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library on the device.  NOT EXECUTED in the build container, like the rest of this file.
 "pg_start_set (240 bytes): 13 uniform ranges (lo, hi) in the order of the draws, then the modes and three reserved zeros"
 struct PgStartSet

@@ -33,7 +33,7 @@ class pg_config(C.Structure):
 
 
 # every symbol include/pigeon_mpc.h declares (tests check that the built library exports each one)
-SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_refine_set", "pg_refine_paths", "pg_default_smooth_set", "pg_smooth_waypoints", "pg_default_tune_set", "pg_tune_smoothing", "pg_default_start_set", "pg_make_starts",
+SYMBOLS = ["pg_precision_bits", "pg_abi_layout", "pg_default_config", "pg_default_config_decoupled", "pg_create", "pg_destroy", "pg_last_error", "pg_get_config", "pg_get_u_normalization", "pg_set_trajectory", "pg_set_trajectories", "pg_set_trajectory_index", "pg_default_speed_plan", "pg_plan_speeds", "pg_default_path_segment", "pg_make_paths", "pg_default_waypoint", "pg_fit_paths", "pg_default_offset_set", "pg_offset_paths", "pg_default_obstacle_set", "pg_clip_tubes", "pg_default_refine_set", "pg_refine_paths", "pg_default_smooth_set", "pg_smooth_waypoints", "pg_default_tune_set", "pg_tune_smoothing", "pg_default_line_set", "pg_optimize_line", "pg_default_start_set", "pg_make_starts",
            "pg_set_control_param_sets", "pg_set_control_param_index", "pg_clear_control_param_sets", "pg_get_control_param_sets",
            "pg_set_plant_sets", "pg_set_plant_index", "pg_clear_plant_sets", "pg_get_plant_sets", "pg_get_tracking_state",
            "pg_set_sensor_sets", "pg_set_sensor_index", "pg_set_sensor_seed", "pg_clear_sensor_sets", "pg_get_sensor_sets", "pg_sensor_draws", "pg_get_measured_state", "pg_set_measured_history_dev",
@@ -358,6 +358,27 @@ WP_TUNE_PROTOTYPES = {
 }
 
 
+class pg_line_set(C.Structure):
+    """include/pigeon_mpc.h pg_line_set: the regularisation and the ADMM penalty (1/m^3), the margin to the edges, the largest move, the stopping tolerance, up to four
+    windows in the path's cumulative chord length with their own margin or a pin, the iteration count and the flags."""
+    _fields_ = [("mu", C.c_double), ("rho", C.c_double), ("margin", C.c_double), ("alpha_max", C.c_double), ("tol", C.c_double), ("u_lo", C.c_double * 4), ("u_hi", C.c_double * 4),
+                ("win_margin", C.c_double * 4), ("win_pin", C.c_int32 * 4), ("iters", C.c_int32), ("n_win", C.c_int32), ("pin_ends", C.c_int32), ("keep_walls", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class pg_line_stats(C.Structure):
+    """include/pigeon_mpc.h pg_line_stats: one per (path, set) pair."""
+    _fields_ = [(n, C.c_double) for n in ["bend_in", "bend_out", "alpha_abs_max", "i_alpha_max", "n_active", "r_prim", "r_dual", "iters_done", "pivot_min", "chord_min", "width_min",
+                                          "reserved"]]
+
+
+# line optimiser (include/pigeon_mpc.h: pg_optimize_line)
+LINE_OPT_PROTOTYPES = {
+    "pg_optimize_line": [C.c_void_p, C.c_int32, C.POINTER(pg_fit_spec), C.c_int32, C.POINTER(pg_waypoint), C.c_int32, C.POINTER(pg_line_set), C.POINTER(pg_waypoint),
+                         C.POINTER(pg_line_stats)],
+}
+
+
 START_RANGES = ["s", "e", "dpsi", "v", "uy", "dr", "delta", "fx", "dt0", "other_dx", "other_dy", "other_dpsi", "other_v"]      # the 13 channels of the draws, in their order
 START_MODES = ["s_mode", "e_mode", "steady", "time_mode", "other_mode"]
 
@@ -406,7 +427,7 @@ def load_library(precision="f64"):
     for s in SYMBOLS:
         getattr(lib, s)
     for prototypes in (CONTROL_PARAM_SET_PROTOTYPES, PLANT_SET_PROTOTYPES, SENSOR_SET_PROTOTYPES, ACTUATOR_SET_PROTOTYPES, DISTURBANCE_SET_PROTOTYPES, ESTIMATOR_SET_PROTOTYPES,
-                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, PATH_REFINE_PROTOTYPES, WP_SMOOTH_PROTOTYPES, START_MAKE_PROTOTYPES, DEVICE_RESIDENT_PROTOTYPES):
+                       HUMAN_SET_PROTOTYPES, ROUTE_SET_PROTOTYPES, HJI_SOLVE_PROTOTYPES, SPEED_PLAN_PROTOTYPES, PATH_MAKE_PROTOTYPES, PATH_FIT_PROTOTYPES, PATH_OFFSET_PROTOTYPES, TUBE_CLIP_PROTOTYPES, PATH_REFINE_PROTOTYPES, WP_SMOOTH_PROTOTYPES, LINE_OPT_PROTOTYPES, START_MAKE_PROTOTYPES, DEVICE_RESIDENT_PROTOTYPES):
         for name, argtypes in prototypes.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -428,6 +449,8 @@ def load_library(precision="f64"):
     lib.pg_default_smooth_set.restype = pg_smooth_set
     lib.pg_default_tune_set.argtypes = []
     lib.pg_default_tune_set.restype = pg_tune_set
+    lib.pg_default_line_set.argtypes = []
+    lib.pg_default_line_set.restype = pg_line_set
     lib.pg_default_start_set.argtypes = []
     lib.pg_default_start_set.restype = pg_start_set
     lib.pg_default_route.argtypes = []

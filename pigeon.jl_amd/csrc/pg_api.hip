@@ -1830,6 +1830,119 @@ int pg_tune_smoothing(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, in
     return down_raw(h, waypoints_out, d_out, (size_t)n_sets * n_all * sizeof(pg_waypoint));
 }
 
+// ---- pg_optimize_line: every (path, line set) pair of a waypoint library x a library of line sets moved along its normals to the least bending energy the walls allow
+// (pg_line_opt.hip).  One launch, one workgroup per pair; waypoints in, waypoints out: nothing is installed ----
+static_assert(sizeof(pg_line_set) == 176 && sizeof(pg_line_stats) == 96, "the sizes include/pigeon_mpc.h states");
+pg_line_set pg_default_line_set(void) {
+    pg_line_set s; s.mu = 1e-6; s.rho = 0.1; s.margin = 0.5; s.alpha_max = 2.0; s.tol = 0.0;
+    for (int j = 0; j < 4; j++) { s.u_lo[j] = 0.0; s.u_hi[j] = 0.0; s.win_margin[j] = 0.0; s.win_pin[j] = 0; }
+    s.iters = 1000; s.n_win = 0; s.pin_ends = 0; s.keep_walls = 0; s.reserved[0] = 0; s.reserved[1] = 0;
+    return s;
+}
+static const char* line_set_problem(const pg_line_set& s) {
+    if (!(std::isfinite(s.mu) && s.mu > 0.0)) return "mu of a set is finite and > 0";
+    if (!(std::isfinite(s.rho) && s.rho > 0.0)) return "rho of a set is finite and > 0";
+    if (!(std::isfinite(s.margin) && s.margin >= 0.0)) return "margin of a set is finite and >= 0";
+    if (!(std::isfinite(s.alpha_max) && s.alpha_max > 0.0)) return "alpha_max of a set is finite and > 0";
+    if (!(std::isfinite(s.tol) && s.tol >= 0.0)) return "tol of a set is finite and >= 0";
+    if (!(s.iters >= 1 && s.iters <= 4096)) return "iters of a set lies in [1, 4096]";
+    if (!(s.n_win >= 0 && s.n_win <= 4)) return "n_win of a set lies in [0, 4]";
+    for (int j = 0; j < s.n_win; j++) {
+        if (std::isnan(s.u_lo[j]) || std::isnan(s.u_hi[j]) || s.u_lo[j] > s.u_hi[j]) return "a window of a set needs u_lo <= u_hi";
+        if (!(std::isfinite(s.win_margin[j]) && s.win_margin[j] >= 0.0)) return "the margin of a window is finite and >= 0";
+    }
+    if (s.reserved[0] != 0 || s.reserved[1] != 0) return "reserved of a set must be 0";
+    return nullptr;
+}
+// what a pair can report after the launch, in the order of the kernel's bad [3]
+static const char* const line_bad_text[3] = {"a pivot of the factorisation is not > 0", "the output is not finite", "this output waypoint and the next lie at the same point"};
+int pg_optimize_line(pg_handle* h, int32_t n_path, const pg_fit_spec* specs, int32_t n_wp_total, const pg_waypoint* waypoints,
+                     int32_t n_sets, const pg_line_set* sets, pg_waypoint* waypoints_out, pg_line_stats* stats) {
+    if (!h) return PG_ERR_INVALID;
+    REQUIRE(h, specs && waypoints && sets, "pg_optimize_line: null argument");
+    REQUIRE(h, n_path >= 1 && n_sets >= 1 && n_wp_total >= 1, "pg_optimize_line: need n_path >= 1, n_sets >= 1 and n_wp_total >= 1");
+    REQUIRE_NO(h, "pg_optimize_line: ", pair_count_problem(n_path, n_sets, 2));
+    for (int k = 0; k < n_path; k++) {
+        const pg_fit_spec& p = specs[k];
+        REQUIRE(h, p.closed ? p.n_wp >= 5 : p.n_wp >= 2, "pg_optimize_line: an open path needs >= 2 waypoints, a closed one >= 5");
+        REQUIRE(h, p.wp0 >= 0 && p.wp0 < n_wp_total && p.n_wp <= n_wp_total - p.wp0, "pg_optimize_line: the waypoints of a path must lie inside [0, n_wp_total)");
+        double C = 0.0;
+        REQUIRE_NO(h, "pg_optimize_line: ", fit_waypoints_problem(p, waypoints, C));
+    }
+    {
+        const std::string why = wp_overlap_problem(n_path, specs);
+        if (!why.empty()) { h->err = "pg_optimize_line: " + why; return PG_ERR_INVALID; }
+    }
+    for (int j = 0; j < n_sets; j++) REQUIRE_NO(h, "pg_optimize_line: ", line_set_problem(sets[j]));
+    // the box of every pair in the kernel's own arithmetic (the chords, the blocked prefix U, lo_box: one text for host and device)
+    for (int k = 0; k < n_path; k++) {
+        const pg_fit_spec& p = specs[k];
+        const pg_waypoint* w = waypoints + p.wp0;
+        std::vector<double> hh((size_t)p.n_wp, 0.0), U((size_t)p.n_wp, 0.0);
+        for (int j = 0; j + 1 < p.n_wp; j++) {
+#pragma clang fp contract(off)
+            const double dE = w[j + 1].E - w[j].E, dN = w[j + 1].N - w[j].N;
+            const double ee = dE * dE, nn = dN * dN;
+            hh[(size_t)j] = sqrt(ee + nn);
+        }
+        lo_prefix_host(p.n_wp - 1, hh.data(), U.data());
+        for (int j = 0; j < n_sets; j++) for (int i = 0; i < p.n_wp; i++) {
+            double lo, hi;
+            lo_box(sets[j].margin, sets[j].alpha_max, sets[j].n_win, sets[j].u_lo, sets[j].u_hi, sets[j].win_margin, sets[j].win_pin, U[(size_t)i], w[i].edge_L, w[i].edge_R,
+                   sets[j].pin_ends && !p.closed && (i == 0 || i == p.n_wp - 1), lo, hi);
+            if (lo > hi) {
+                h->err = "pg_optimize_line: path " + std::to_string(k) + ", set " + std::to_string(j) + ", waypoint " + std::to_string(i) +
+                         ": the margins leave no room between the edges (lo > hi)";
+                return PG_ERR_INVALID;
+            }
+        }
+    }
+    std::vector<SmoothSpec> recs((size_t)n_path);
+    size_t n_used = 0;
+    int lds_rows = 1;                                         // the rows of the longest path, at most LO_LDS_ROWS: what the launch keeps of the recurrence in LDS
+    for (int k = 0; k < n_path; k++) {
+        lds_rows = std::max(lds_rows, std::min(specs[k].closed ? specs[k].n_wp - 2 : specs[k].n_wp, (int)LO_LDS_ROWS));
+        SmoothSpec& r = recs[(size_t)k];
+        r.soff = (long long)n_used; r.wp0 = specs[k].wp0; r.n_wp = specs[k].n_wp; r.closed = specs[k].closed ? 1 : 0; r.pad = 0;
+        n_used += (size_t)specs[k].n_wp;                          // (<= n_wp_total: the ranges do not overlap)
+    }
+    REQUIRE(h, (double)n_sets * (double)n_wp_total * (double)LO_ARRAYS * 8.0 < 4611686018427387904.0,
+            "pg_optimize_line: the scratch of all pairs is more than the allocation arithmetic holds");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+
+    const size_t n_pair = (size_t)n_path * n_sets, n_all = (size_t)n_wp_total;
+    CallBufs D; pg_waypoint *d_in = nullptr, *d_out = nullptr; SmoothSpec* d_specs = nullptr; pg_line_set* d_sets = nullptr; double* d_scr = nullptr;
+    pg_line_stats* d_stats = nullptr; int* d_bad = nullptr;
+    HIPCHK(h, D.alloc(d_in, n_all));
+    HIPCHK(h, D.alloc(d_out, (size_t)n_sets * n_all));
+    HIPCHK(h, D.alloc(d_specs, (size_t)n_path));
+    HIPCHK(h, D.alloc(d_sets, (size_t)n_sets));
+    HIPCHK(h, D.alloc(d_scr, (size_t)n_sets * n_used * LO_ARRAYS));
+    HIPCHK(h, D.alloc(d_stats, n_pair));
+    HIPCHK(h, D.alloc(d_bad, 3 * n_pair));
+    HIPCHK(h, to_device(d_in, waypoints, n_all));
+    for (int j = 0; j < n_sets; j++)                          // (every block starts as the input, copied on the device: a pair writes its own path's waypoints alone)
+        HIPCHK(h, hipMemcpyAsync(d_out + (size_t)j * n_all, d_in, n_all * sizeof(pg_waypoint), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, to_device(d_specs, recs.data(), (size_t)n_path));
+    HIPCHK(h, to_device(d_sets, sets, (size_t)n_sets));
+    LineOptArgs A; A.n_sets = n_sets; A.n_wp_total = n_wp_total; A.lds_rows = lds_rows; A.n_used = (long long)n_used; A.specs = d_specs; A.sets = d_sets; A.in = d_in; A.out = d_out; A.scratch = d_scr;
+    A.stats = d_stats; A.bad = d_bad;
+    hipLaunchKernelGGL(k_line_opt, dim3((unsigned)n_pair), dim3(WS_THREADS), (size_t)6 * lds_rows * sizeof(double), h->stream, A);      // (at most 49152 bytes)
+    LAUNCH_CHECK(h);
+    std::vector<pg_line_stats> st(n_pair);
+    std::vector<int> bad(3 * n_pair);
+    HIPCHK(h, hipMemcpyAsync(st.data(), d_stats, n_pair * sizeof(pg_line_stats), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, 3 * n_pair * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));               // (the kernel has run)
+    for (size_t k = 0; k < n_pair; k++) for (int c = 0; c < 3; c++) if (bad[3 * k + c] >= 0) {
+        h->err = "pg_optimize_line: path " + std::to_string(k / (size_t)n_sets) + ", set " + std::to_string(k % (size_t)n_sets) + ", waypoint " + std::to_string(bad[3 * k + c]) +
+                 ": " + line_bad_text[c];
+        return PG_ERR_INVALID;
+    }
+    if (stats) memcpy(stats, st.data(), n_pair * sizeof(pg_line_stats));
+    return down_raw(h, waypoints_out, d_out, (size_t)n_sets * n_all * sizeof(pg_waypoint));
+}
+
 // ---- sensor library: the state the CONTROLLER of a rollout step reads, measured = true + bias + sigma z per channel (k_measure).  No part of any QP's structure and no
 // solver state: nothing is reset ----
 static const char* sensor_set_problem(const pg_sensor& s) {

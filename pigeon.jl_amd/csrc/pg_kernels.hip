@@ -3414,6 +3414,7 @@ __global__ __launch_bounds__(64, PG_SOLVE_WAVES(RING, IPM)) void k_solve(DevCfg 
 #include "pg_path_refine.hip"      // pg_refine_paths: every (path, refine set) pair as a trajectory with knots inserted where a manoeuvre needs them (workgroup = pair)
 #include "pg_waypoint_smooth.hip"  // pg_smooth_waypoints: every (path, smoothing set) pair of a waypoint library as smoothed waypoints, a cubic smoothing spline (workgroup = pair)
 #include "pg_waypoint_tune.hip"    // pg_tune_smoothing: the smoothing weight of every (path, tune set) pair searched on a wavefront, then the pair smoothed under it (workgroup = pair)
+#include "pg_line_opt.hip"         // pg_optimize_line: every (path, line set) pair of a waypoint library moved along its normals to the least bending energy the walls allow (workgroup = pair)
 #include "pg_start_make.hip"        // pg_make_starts: the inputs of a batch placed on the installed trajectory library under a library of start sets (lane = instance)
 #include "pg_route.hip"             // route sets: an instance changes trajectory during a rollout (k_route: wave = instance)
 

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .trajectories import TrajectoryTube
-from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, smooth as _default_smooth, tune as _default_tune, refine_parts as _refine_parts, REFINE_M_MAX
+from .vehicles import X1, CoupledControlParams, DecoupledControlParams, actuator as _identity_actuator, disturbance as _identity_disturbance, estimator as _identity_estimator, human as _identity_human, route as _route, speed_plan as _default_speed_plan, path_segment as _default_path_segment, waypoint as _default_waypoint, start as _default_start, offset as _default_offset, obstacle_set as _default_obstacle_set, refine as _default_refine, smooth as _default_smooth, tune as _default_tune, line as _default_line, refine_parts as _refine_parts, REFINE_M_MAX
 
 c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
@@ -23,6 +23,7 @@ PATH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_path_stats._fie
 OFFSET_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_offset_stats._fields_])      # 64 bytes, the layout of pg_offset_stats
 SMOOTH_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_smooth_stats._fields_])      # 72 bytes, the layout of pg_smooth_stats
 TUNE_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_tune_stats._fields_])      # 72 bytes, the layout of pg_tune_stats
+LINE_STATS_DTYPE = np.dtype([(n, np.float64) for n, _ in _lib.pg_line_stats._fields_])      # 96 bytes, the layout of pg_line_stats
 REFINE_STATS_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_refine_stats._fields_])      # 64 bytes, the layout of pg_refine_stats
 CLIP_STATS_DTYPE = np.dtype([("width_min", np.float64), ("u_width_min", np.float64), ("reserved_d", np.float64, (2,))] + [(n, np.int32) for n in ("n_clip_L", "n_clip_R", "n_blocked", "n_centre_out", "n_seen", "n_ignored")] + [("reserved", np.int32, (2,))])      # 64 bytes, the layout of pg_clip_stats
 OBSTACLE_REPORT_DTYPE = np.dtype([(n, np.float64 if c is C.c_double else np.int32) for n, c in _lib.pg_obstacle_report._fields_])      # 64 bytes, the layout of pg_obstacle_report
@@ -702,6 +703,60 @@ class BatchedTrajectoryTrackingMPC:
         flat = np.frombuffer(out, dtype=np.float64).reshape(ns, nw, 4)
         smoothed = [[[dict(E=float(w[0]), N=float(w[1]), edge_L=float(w[2]), edge_R=float(w[3])) for w in flat[k, s.wp0:s.wp0 + s.n_wp]] for s in specs] for k in range(ns)]
         return smoothed, np.frombuffer(st, dtype=SMOOTH_STATS_DTYPE).copy().reshape(n, ns), np.frombuffer(tn, dtype=TUNE_STATS_DTYPE).copy().reshape(n, ns)
+
+    # ---- the line inside the tube (pg_optimize_line): every (path, line set) pair of a waypoint library x a library of line sets, on the device ----
+    @classmethod
+    def pack_lines(cls, sets):
+        """vehicles.line(...) dicts (one, or a list) or pg_line_set structures -> a ctypes array of pg_line_set.  Raises ValueError for a set outside the ranges of
+        include/pigeon_mpc.h (the library refuses the same sets with PG_ERR_INVALID)."""
+        def fill(rec, p):
+            full = _default_line(**p)
+            rec.mu, rec.rho, rec.margin, rec.alpha_max, rec.tol = full["mu"], full["rho"], full["margin"], full["alpha_max"], full["tol"]
+            rec.iters, rec.pin_ends, rec.keep_walls, rec.n_win = full["iters"], int(full["pin_ends"]), int(full["keep_walls"]), len(full["windows"])
+            for j in range(4):
+                rec.u_lo[j], rec.u_hi[j], rec.win_margin[j], rec.win_pin[j] = full["windows"][j] if j < rec.n_win else (0.0, 0.0, 0.0, 0)
+        arr = cls._pack(_lib.pg_line_set, [sets] if isinstance(sets, (dict, _lib.pg_line_set)) else sets, fill)
+        if len(arr) < 1:
+            raise ValueError("optimize_line: at least one line set")
+        for k, r in enumerate(arr):
+            for name, strict in (("mu", True), ("rho", True), ("alpha_max", True), ("margin", False), ("tol", False)):
+                v = getattr(r, name)
+                if not (math.isfinite(v) and (v > 0.0 if strict else v >= 0.0)):
+                    raise ValueError(f"optimize_line: {name} of set {k} is finite and {'> 0' if strict else '>= 0'}")
+            if not 1 <= r.iters <= 4096:
+                raise ValueError(f"optimize_line: iters of set {k} lies in [1, 4096]")
+            if not 0 <= r.n_win <= 4:
+                raise ValueError(f"optimize_line: n_win of set {k} lies in [0, 4]")
+            for j in range(r.n_win):
+                if not r.u_lo[j] <= r.u_hi[j]:
+                    raise ValueError(f"optimize_line: window {j} of set {k} needs u_lo <= u_hi")
+                if not (math.isfinite(r.win_margin[j]) and r.win_margin[j] >= 0.0):
+                    raise ValueError(f"optimize_line: the margin of window {j} of set {k} is finite and >= 0")
+            if r.reserved[0] != 0 or r.reserved[1] != 0:
+                raise ValueError(f"optimize_line: reserved of set {k} must be 0")
+        return arr
+
+    def optimize_line(self, paths, sets):
+        """The line of least bending energy inside the tube, on the device (pg_optimize_line; the scheme is stated in include/pigeon_mpc.h): every waypoint moved along
+        its normal inside its own edge_R .. edge_L, for every (path, set) pair.  paths as smooth_waypoints takes them (waypoints metres apart: thin a dense survey with
+        vehicles.waypoints_from_tube(every=) first), sets = vehicles.line(h_mean=.., margin=.., alpha_max=.., iters=.., tol=.., pin_ends=.., keep_walls=..,
+        windows=[vehicles.line_window(..)]) dicts.  Returns (lines, stats): lines[k][i] is the waypoint list of path i under set k (smoothed_fit_paths(paths, lines, k) is
+        the list fit_paths takes for set k), stats a structured array [n_path][n_sets] with the fields of pg_line_stats (bend_in, bend_out, alpha_abs_max, i_alpha_max,
+        n_active, r_prim, r_dual, iters_done, pivot_min, chord_min, width_min)."""
+        paths = [dict(p) for p in paths]
+        for k, p in enumerate(paths):
+            if len(p.get("waypoints", ())) < (5 if p.get("closed", False) else 2):
+                raise ValueError(f"optimize_line: path {k} needs 2 waypoints (a closed path 5)")
+            p.setdefault("n_knots", 3)
+        specs, wps, _ = self.pack_fit_specs(paths)
+        arr = self.pack_lines(sets)
+        n, ns, nw = len(specs), len(arr), len(wps)
+        out = (_lib.pg_waypoint * (ns * nw))()
+        st = (_lib.pg_line_stats * (n * ns))()
+        self._chk(self.lib.pg_optimize_line(self.h, n, specs, nw, wps, ns, arr, out, st), "pg_optimize_line")
+        flat = np.frombuffer(out, dtype=np.float64).reshape(ns, nw, 4)
+        lines = [[[dict(E=float(w[0]), N=float(w[1]), edge_L=float(w[2]), edge_R=float(w[3])) for w in flat[k, s.wp0:s.wp0 + s.n_wp]] for s in specs] for k in range(ns)]
+        return lines, np.frombuffer(st, dtype=LINE_STATS_DTYPE).copy().reshape(n, ns)
 
     # ---- making the starts (pg_make_starts): the inputs of a batch placed on the installed trajectory library under a library of start sets, on the device ----
     @classmethod

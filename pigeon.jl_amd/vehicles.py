@@ -457,6 +457,38 @@ def smooth_window(u_lo, u_hi, factor=0.0):
     return (float(u_lo), float(u_hi), float(factor))
 
 
+def line(h_mean=1.0, **overrides):
+    """One line set for optimize_line (pg_line_set).  mu and rho are given as multiples of 1 / h_mean^3, h_mean the path's mean chord in metres: line(h_mean=3.74) is
+    mu = 1e-6 / h^3, rho = 0.1 / h^3, the scale at which the bend Hessian's entries are of order one (EXPERIMENTS 43: on the committed ovals taken every 16th point 1000
+    iterations leave r_prim at 5e-7 m with rho = 0.1 / h^3, 2e-4 m with 0.03 and 1e-5 m with 0.3; ten times more or less still converges, more slowly).  line() with h_mean = 1 is the library's
+    default (pg_default_line_set).  margin: metres kept between the line and each edge.  alpha_max: the largest move along the normal.  iters: 1 .. 4096.  tol: stops
+    where both ADMM residuals are at most this (0: all iterations).  pin_ends: the ends of an open path do not move.  keep_walls: the edges are shifted by -alpha, so the
+    walls stay where they were surveyed and a second call re-linearises about the first result.  windows: up to four line_window(...) entries; the last listed one that
+    holds a waypoint's cumulative chord length sets its margin, or pins it."""
+    s = dict(mu=1e-6, rho=0.1, margin=0.5, alpha_max=2.0, tol=0.0, iters=1000, pin_ends=False, keep_walls=False, windows=[])
+    for k, v in overrides.items():
+        if k not in s:
+            raise KeyError(f"{k} is not a field of a line set: {sorted(s)} (and h_mean)")
+        s[k] = v
+    h3 = float(h_mean) ** 3
+    if not (math.isfinite(h3) and h3 > 0.0):
+        raise ValueError("line: h_mean is finite and > 0")
+    s["mu"] = float(s["mu"]) / h3; s["rho"] = float(s["rho"]) / h3
+    for k in ("margin", "alpha_max", "tol"):
+        s[k] = float(s[k])
+    s["iters"] = int(s["iters"]); s["pin_ends"] = bool(s["pin_ends"]); s["keep_walls"] = bool(s["keep_walls"])
+    s["windows"] = [(float(a), float(b), float(c), int(bool(d))) for a, b, c, d in s["windows"]]
+    if len(s["windows"]) > 4:
+        raise ValueError(f"line: {len(s['windows'])} windows (at most 4)")
+    return s
+
+
+def line_window(u_lo, u_hi, margin=0.5, pin=False):
+    """One window of a line set: the waypoints whose cumulative chord length (metres from the path's first waypoint) lies in [u_lo, u_hi] keep `margin` metres to each
+    edge instead of the set's own -- or, with pin=True, do not move at all ("the line through the gate is the surveyed one")."""
+    return (float(u_lo), float(u_hi), float(margin), int(bool(pin)))
+
+
 def waypoints_from_tube(tube, every=1, closed=False):
     """The knots 0, every, 2 every, .. of a TrajectoryTube -- or of a committed path as its file holds it (the keys posE_m, posN_m, edgeL_m, edgeR_m) -- as a waypoint list
     for fit_paths: "the same track thinned to every n-th point".  closed=True: the file repeats knot 0 as its last knot, which is dropped (fit_paths closes the path itself);

@@ -13,7 +13,7 @@ instruction it is not entitled to:
     made once per sweep: the fp32 library's paths are exactly the fp64 library's rounded to float; k_path_fit, which fits a path library to waypoints under the same rule
     and for the same reasons; k_path_offset, which offsets a path library into lanes, lane changes and pass-bys under the same rule -- the source is read as the doubles
     given --; k_tube_clip, which narrows the tubes of a path library around obstacle sets under the same rule (the stats and reports are the same doubles in both
-    libraries); k_path_refine, which inserts knots into a path library under the same rule; k_wp_smooth, which smooths waypoints, doubles in both libraries: both return the same bits; k_wp_tune, which searches the smoothing weight and smooths under it by the same text; k_make_starts, which places a batch on the installed library in double -- draws, the controller's lookup restated in double on the channels as
+    libraries); k_path_refine, which inserts knots into a path library under the same rule; k_wp_smooth, which smooths waypoints, doubles in both libraries: both return the same bits; k_wp_tune, which searches the smoothing weight and smooths under it by the same text; k_line_opt, which moves waypoints along their normals to the least bending energy, doubles in both libraries; k_make_starts, which places a batch on the installed library in double -- draws, the controller's lookup restated in double on the channels as
     held, placement -- and rounds on store; k_route, whose time offset of a switched instance is t0 - (t_proj + t_join) in double -- its
     projection is in the library's element type) may use fp64 arithmetic;
   * everything else (k_solve, k_linearize, k_limits, k_qp_dec, k_project, k_hji_*) must be pure fp32.
@@ -24,7 +24,7 @@ import re
 import sys
 
 TIME_KERNELS = ("k_time_steps", "k_nodes", "k_nodes_linearize", "k_nodes_warm", "k_nodes_dec", "k_advance", "k_advance_safety", "k_node_finish", "k_nodes_recheck",
-                "k_advance_lib", "k_advance_safety_lib", "k_node_finish_lib", "k_speed_plan", "k_path_make", "k_path_fit", "k_path_offset", "k_tube_clip", "k_path_refine", "k_wp_smooth", "k_wp_tune", "k_make_starts", "k_route")
+                "k_advance_lib", "k_advance_safety_lib", "k_node_finish_lib", "k_speed_plan", "k_path_make", "k_path_fit", "k_path_offset", "k_tube_clip", "k_path_refine", "k_wp_smooth", "k_wp_tune", "k_line_opt", "k_make_starts", "k_route")
 HARMLESS = re.compile(r"^v_(cvt_|cmp_|cmpx_|frexp_)")
 
 
